@@ -3,6 +3,7 @@
 
     python bench.py --gpus N --steps K --warmup W           (N > 1: launched by torch.distributed.run,
                                                               one rank per GPU; RANK/LOCAL_RANK/... from env)
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR   (also writes what the last timed step computed, DIR/*.npy)
 
 Workload = BASELINE.json configs[3]: synthetic 16-label mask, 1024^3 semantic RGB grid (M1 of
 SURVEY.md 8(d): carve_voxel_grid_with_masks(sem1024, binary), 6 algorithmic bytes per voxel).
@@ -30,6 +31,33 @@ import numpy as np  # noqa: E402
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 INFINITY_CACHE_BYTES = 256 << 20   # memory-side cache in front of the HBM (MI355X_MICROARCH.md)
 ALG_BYTES_PER_VOXEL = 6        # M1: read 3 + write 3
+DUMP_SAMPLE_VOXELS = 1 << 22   # --dump-outputs: 4M voxels x 3 channels as float32 = 48 MiB, inside the 64 MB the dump may take
+
+
+def dump_outputs(out_dir, d_buf, planes, S):
+    """--dump-outputs: what the last timed step handed its caller, the carved (planes, S, S, 3) u8 grid at the start of `d_buf`,
+    as .npy files two builds can be compared on:
+        carved_sample_rgb.npy        float32 (N, 3)   RGB of N voxels at fixed positions (seed 0, sorted flat indices of the grid)
+        carved_plane_byte_sums.npy   float64 (planes,) sum of all bytes of each X-plane (every voxel counts)
+    A directory this function creates gets a `*` .gitignore, so a dump inside a checkout leaves `git status` clean."""
+    if not os.path.isdir(out_dir):
+        os.makedirs(out_dir)
+        with open(os.path.join(out_dir, ".gitignore"), "w") as f:
+            f.write("*\n")
+    plane = S * S
+    nvox = planes * plane
+    idx = np.sort(np.random.default_rng(0).choice(nvox, min(nvox, DUMP_SAMPLE_VOXELS), replace=False))
+    sample = np.empty((idx.size, 3), np.float32)
+    plane_sums = np.empty(planes, np.float64)
+    chunk = max(1, (192 << 20) // (plane * 3))                     # X-planes per download
+    for p0 in range(0, planes, chunk):
+        p1 = min(planes, p0 + chunk)
+        block = d_buf.download((p1 - p0, plane * 3), byte_offset=p0 * plane * 3)
+        plane_sums[p0:p1] = block.sum(axis=1, dtype=np.uint64)
+        lo, hi = np.searchsorted(idx, (p0 * plane, p1 * plane))
+        sample[lo:hi] = block.reshape(-1, 3)[idx[lo:hi] - p0 * plane]
+    np.save(os.path.join(out_dir, "carved_sample_rgb.npy"), sample)
+    np.save(os.path.join(out_dir, "carved_plane_byte_sums.npy"), plane_sums)
 
 
 def cpu_baseline(S, d_in, m_wh, planes):
@@ -151,7 +179,11 @@ def main():
                     "(tools/slab_pmc.sh -> profiles/pmc_traffic.json); the JSON line is marked and is not a bench result")
     ap.add_argument("--weak", action="store_true", help="weak scaling: every rank carves its own full S^3 grid (default: the ONE "
                     "S^3 grid of the BASELINE metric is split into X-slabs = strong scaling)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (a seeded "
+                    "sample of the carved grid and its per-plane byte sums) to DIR/*.npy; one process only")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -160,6 +192,8 @@ def main():
         if world == 1 and args.gpus > 1:
             sys.exit("bench.py --gpus N>1 must be launched with torch.distributed.run (one rank per GPU)")
         args.gpus = world
+    if args.dump_outputs and world != 1:
+        sys.exit("bench.py --dump-outputs runs in one process (--gpus 1)")
     # PB3D_BENCH_ONE_DEVICE=1: rehearsal of the multi-rank control flow on a 1-GPU box (all ranks on GPU 0, no RCCL)
     one_device = os.environ.get("PB3D_BENCH_ONE_DEVICE") == "1"
     os.environ["PB3D_DEVICE"] = "0" if one_device else str(local_rank)
@@ -225,6 +259,8 @@ def main():
     t = cp.allreduce_max(t_local)
     kernel_ms = e1.elapsed_ms_since(e0) / args.steps     # HIP events on the stream the kernel runs on
     kernel_ms_max = cp.allreduce_max(kernel_ms)
+    if args.dump_outputs:           # before the extras below reuse d_full as scratch
+        dump_outputs(args.dump_outputs, d_full, planes, S)
 
     total_vox = planes * world * S * S
     value = total_vox * args.steps / t / 1e6
