@@ -3,7 +3,7 @@
 // Round 4: this file held five generations of table-driven byte-tile kernels for 0/1 data (k_rotate_bits, _bits32, _bits16w, _bits8p and
 // their table builders, 1 400 lines).  Every rotation step on 0/1 data -- chains and single steps alike -- now runs bit-sliced
 // (csrc/sliced.hip: a single 60-degree step through slice -> table step -> un-slice measured equal or faster at every size from 512-class
-// grids up, 5 us slower at 128^3; tools/singlestep_ab.py, profiles/r04_singlestep_ab.jsonl), single 90-degree steps on the permutation
+// grids up, 5 us slower at 128^3; the A/B record of that measurement was not kept), single 90-degree steps on the permutation
 // kernels (csrc/rotate_tiled.hip).  What remains here is the kernel that evaluates SciPy's arithmetic voxel by voxel: grids with values
 // other than 0/1, shapes the sliced chain does not take, and the pinned reference of the parity tests (tune sliced = 1).
 //

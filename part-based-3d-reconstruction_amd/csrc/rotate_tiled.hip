@@ -8,21 +8,9 @@
 // cos(90 deg) = 6.1e-17 drops ~1 % of the border cells and that is reproduced, not patterned.
 // The kernel is then a tiled transpose inside each Y-plane: the source tile is staged through LDS
 // with coalesced dword row loads, outputs are gathered from LDS and stored as packed dwords.
-#include "pb3d_internal.h"
+#include "rot90.h"
 
 namespace {
-
-struct RotParams {
-    double m00, m01, m02, off0;
-    double m20, m21, m22, off2;
-};
-
-__device__ __forceinline__ double coord(double x, double z, double ma, double mb, double mc, double off) {
-    double c = __dadd_rn(0.0, __dmul_rn(x, ma));
-    c = __dadd_rn(c, __dmul_rn(0.0, mb));
-    c = __dadd_rn(c, __dmul_rn(z, mc));
-    return __dadd_rn(c, off);
-}
 
 // nearest source voxel of output (x,z), or false when SciPy's bounds test rejects the coordinate
 __device__ __forceinline__ bool source_of(const RotParams& p, i64 x, i64 z, i64 W, i64 D, int* n0, int* n2) {
@@ -185,10 +173,6 @@ static inline unsigned tilemap_blocks(const TileMap& m) {
     return m.order == 1 ? (unsigned)((i64)m.nzt * m.nxt * m.nyc) : (unsigned)(8ll * m.nzt * m.nxt * ((m.nyc + 7) / 8));
 }
 
-typedef u32 u32x4 __attribute__((ext_vector_type(4)));
-typedef u32x4 u32x4_u __attribute__((aligned(1)));     // 16-byte access at any byte alignment (rows of odd-sized grids)
-typedef u32 u32_u __attribute__((aligned(1)));
-
 // (K4, global_carve(binary, rgb, 90): the per-row piece kernels k_global_carve90v / 90f of rounds 1-3 are gone -- the stream kernel
 // k_global_carve90s in csrc/bits90.hip is faster on every shape, profiles/r04_global_carve90_stream_vs_piece_kernels.jsonl.)
 
@@ -203,24 +187,18 @@ typedef u32 u32_u __attribute__((aligned(1)));
 // 4-byte block with ds_read_b32 and transposes it with v_perm_b32 into four 16-byte output runs.
 // Global loads of plane y+1 are issued before plane y is computed.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ u32 perm(u32 hi, u32 lo, u32 sel) { return __builtin_amdgcn_perm(hi, lo, sel); }
-
-#ifndef ROT90_WAVES
-#define ROT90_WAVES 4
-#endif
-// DEPTH planes of global loads are in flight per workgroup (register ring, statically indexed by the unrolled slot loop);
-// the LDS tile is double-buffered so a plane costs ONE barrier.  Measured at 1024^3: DEPTH 1 with 4 workgroups/CU 0.51 ms;
-// DEPTH 2 (3 workgroups/CU) 0.55; DEPTH 3-4 (2/CU) 0.63 -- resident waves matter more than bytes in flight.  The memory
-// system's own bound for this traffic (tools/kbench3.hip: 16 KiB tiles of 128-byte rows 1 MiB apart on both sides, no
-// transpose) is 0.455 ms, a linear copy with the same workgroup shape 0.41 ms.
+// One plane of global loads is in flight per workgroup; the LDS tile is double-buffered so a plane costs ONE barrier.  Measured at
+// 1024^3: 4 workgroups/CU 0.51 ms; a register ring of 2 planes in flight (3 workgroups/CU) 0.55, of 3-4 planes (2/CU) 0.63 --
+// resident waves matter more than bytes in flight.  The memory system's own bound for this traffic (tools/kbench3.hip: 16 KiB tiles
+// of 128-byte rows 1 MiB apart on both sides, no transpose) is 0.455 ms, a linear copy with the same workgroup shape 0.41 ms.
 // RAGGED = false: D % 16 == 0 and c2 % 16 == 0, every piece is whole and the byte-wise paths are compiled out (they cost
 // 25 % at 1024^3 when merely present)
 // (Round 4: the colour-writing and plane-shifted forms of this kernel are gone -- global_carve chains write their colours from the
 // bit-sliced volume, csrc/sliced.hip, and rows that are not whole lines take the flat kernels below.)
-template <int DEPTH, bool RAGGED>
-__global__ __launch_bounds__(256, ROT90_WAVES) void k_rot90(const u8* __restrict__ in, u8* __restrict__ out, const u8* __restrict__ mask_src,
-                                               const u8* __restrict__ mask_dst, const u32* __restrict__ vbits, int nw, int c0, int c2,
-                                               i64 W, i64 H, i64 D, int TY, TileMap tm) {
+template <bool RAGGED>
+__global__ __launch_bounds__(256, 4) void k_rot90(const u8* __restrict__ in, u8* __restrict__ out, const u8* __restrict__ mask_src,
+                                                  const u8* __restrict__ mask_dst, const u32* __restrict__ vbits, int nw, int c0, int c2,
+                                                  i64 W, i64 H, i64 D, int TY, TileMap tm) {
     __shared__ __attribute__((aligned(16))) u8 tiles[2][128 * 128];
     const int tid = threadIdx.x;
     i64 zt, xt, yc;
@@ -238,41 +216,22 @@ __global__ __launch_bounds__(256, ROT90_WAVES) void k_rot90(const u8* __restrict
     const int g = 7 - zg;                               // row group holding this thread's 16 source rows
     const u32 rd_off = (u32)(16 * g * 128 + 16 * ((xg >> 2) ^ g) + 4 * (xg & 3));
     const i64 zo = z0 + 16 * zg;                          // first z of this thread's run
-    // 16 validity bits of row x for z = zlo .. zlo + 15 (zero outside [0, D): the table is zero there, negative z are shifted out)
-    auto vwin = [&](i64 x, i64 zlo) -> u32 {
-        if (x >= W || zlo <= -16 || zlo >= D) return 0u;
-        const i64 zs = zlo < 0 ? 0 : zlo;
-        const u32* vr = vbits + x * nw + (zs >> 5);
-        u32 v = (u32)((((u64)vr[1] << 32) | (u64)vr[0]) >> (zs & 31)) & 0xffffu;
-        if (zlo < 0) v = (v << (int)(-zlo)) & 0xffffu;
-        return v;
-    };
-    u32 vb[4];
+    u32 vb[4];                                          // validity bits of this thread's four output runs
 #pragma unroll
-    for (int i = 0; i < 4; ++i) vb[i] = vwin(x0 + 4 * xg + i, zo);
-    // Everything a plane needs from global memory is issued together, DEPTH planes ahead: the 16-byte source pieces, the
+    for (int i = 0; i < 4; ++i) vb[i] = x0 + 4 * xg + i < W ? valid16(vbits, nw, x0 + 4 * xg + i, zo, D) : 0u;
+    // Everything a plane needs from global memory is issued together, one plane ahead: the 16-byte source pieces, the
     // source-row mask bytes (applied when the data lands, so the two loads are not dependent) and the
     // destination-row mask bytes.
-    u32x4 stg[DEPTH][4];
-    u32 msk[DEPTH];    // bit j: source-row mask of piece j ; bits 4..7: destination-row mask of row i
-    auto load_plane = [&](u32x4 (&sg)[4], u32& mkout, i64 y) {
+    u32x4 stg[4];
+    u32 msk;           // bit j: source-row mask of piece j ; bits 4..7: destination-row mask of row i
+    auto load_plane = [&](i64 y) {
         u32 mk = 0;
-        const i64 rbase = rbase0;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const i64 n0 = rbase + (tid >> 3) + 32 * j;
-            sg[j] = (u32x4)(0u);
+            const i64 n0 = rbase0 + (tid >> 3) + 32 * j;
+            stg[j] = (u32x4)(0u);
             if (y < y_end && (RAGGED ? cmode != 0 : cmode == 2) && n0 >= 0 && n0 < W) {
-                const u8* sp = in + (n0 * H + y) * D + scol;
-                // a ragged piece may be read whole as long as it stays inside the volume: the bytes beyond the row belong to
-                // the neighbouring row and are dropped by the validity bits (their source column is outside [0, D))
-                if (!RAGGED || cmode == 2 || (sp >= in && sp + 16 <= in + W * H * D)) sg[j] = __builtin_nontemporal_load((const u32x4_u*)sp);
-                else {
-                    u32 t4[4] = {0, 0, 0, 0};
-                    for (int b = 0; b < 16; ++b)
-                        if (scol + b >= 0 && scol + b < D) t4[b >> 2] |= (u32)sp[b] << (8 * (b & 3));
-                    sg[j].x = t4[0]; sg[j].y = t4[1]; sg[j].z = t4[2]; sg[j].w = t4[3];
-                }
+                stg[j] = load_piece(in, (n0 * H + y) * D + scol, W * H * D, !RAGGED || cmode == 2, scol, D);
                 mk |= (u32)((mask_src ? mask_src[n0 * H + y] : (u8)1) != 0) << j;
             }
         }
@@ -281,68 +240,30 @@ __global__ __launch_bounds__(256, ROT90_WAVES) void k_rot90(const u8* __restrict
             const i64 x = x0 + 4 * xg + i;
             if (y < y_end && x < W && vb[i]) mk |= (u32)((mask_dst ? mask_dst[x * H + y] : (u8)1) != 0) << (4 + i);
         }
-        mkout = mk;
+        msk = mk;
     };
-#pragma unroll
-    for (int s = 0; s < DEPTH; ++s) load_plane(stg[s], msk[s], y_beg + s);
+    load_plane(y_beg);
     int buf = 0;
-    for (i64 y0p = y_beg; y0p < y_end; y0p += DEPTH) {
+    for (i64 y = y_beg; y < y_end; ++y) {
+        u8* tile = tiles[buf];
+        buf ^= 1;
+        const u32 mkc = msk;
+        stage4<8, 32>(tile, tid >> 3, cb, stg, mkc);
+        __syncthreads();      // the only barrier of the plane: the other tile buffer was last read before the previous one
+        load_plane(y + 1);
+        u32 d[16];
 #pragma unroll
-        for (int s = 0; s < DEPTH; ++s) {
-            const i64 y = y0p + s;
-            if (y >= y_end) break;                       // uniform
-            u8* tile = tiles[buf];
-            buf ^= 1;
-            const u32 mkc = msk[s];
+        for (int rr = 0; rr < 16; ++rr) d[rr] = *(const u32*)(tile + rd_off + rr * 128);
+        u32 o[4][4];  // o[i][w]: output x = 4 xg + i, bytes q = 4w .. 4w+3 ; byte q <- d[15 - q].byte[i]
+        transpose16x4(d, o);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int lr = (tid >> 3) + 32 * j;
-                *(u32x4*)(tile + lr * 128 + 16 * (cb ^ ((lr >> 4) & 7))) = ((mkc >> j) & 1u) ? stg[s][j] : (u32x4)(0u);
-            }
-            __syncthreads();      // the only barrier of the plane: the other tile buffer was last read before the previous one
-            load_plane(stg[s], msk[s], y + DEPTH);
-            u32 d[16];
-#pragma unroll
-            for (int rr = 0; rr < 16; ++rr) d[rr] = *(const u32*)(tile + rd_off + rr * 128);
-            u32 o[4][4];  // o[i][w]: output x = 4 xg + i, bytes q = 4w .. 4w+3 ; byte q <- d[15 - q].byte[i]
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                const u32 A = d[15 - 4 * w], B = d[14 - 4 * w], Cc = d[13 - 4 * w], E = d[12 - 4 * w];
-                const u32 t0 = perm(B, A, 0x05010400u), t1 = perm(B, A, 0x07030602u);
-                const u32 u0 = perm(E, Cc, 0x05010400u), u1 = perm(E, Cc, 0x07030602u);
-                o[0][w] = perm(u0, t0, 0x05040100u);
-                o[1][w] = perm(u0, t0, 0x07060302u);
-                o[2][w] = perm(u1, t1, 0x05040100u);
-                o[3][w] = perm(u1, t1, 0x07060302u);
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const i64 x = x0 + 4 * xg + i;
-                if (x >= W || zo >= D) continue;
-                const u32 vbi = vb[i];
-                u32x4 r = (u32x4)(0u);
-                if ((mkc >> (4 + i)) & 1u) {
-                    r.x = o[i][0]; r.y = o[i][1]; r.z = o[i][2]; r.w = o[i][3];
-                    if (vbi != 0xffffu) {  // border cells rejected by the f64 bounds test (rare)
-                        u32 mw[4];
-#pragma unroll
-                        for (int w = 0; w < 4; ++w) {
-                            const u32 b4 = (vbi >> (4 * w)) & 0xfu;
-                            mw[w] = ((b4 & 1u) ? 0x000000ffu : 0u) | ((b4 & 2u) ? 0x0000ff00u : 0u) | ((b4 & 4u) ? 0x00ff0000u : 0u) |
-                                    ((b4 & 8u) ? 0xff000000u : 0u);
-                        }
-                        r.x &= mw[0]; r.y &= mw[1]; r.z &= mw[2]; r.w &= mw[3];
-                    }
-                }
-                u8* op = out + (x * H + y) * D + zo;
-                if (!RAGGED || zo + 15 < D) __builtin_nontemporal_store(r, (u32x4_u*)op);
-                else {
-                    const u32 t4[4] = {r.x, r.y, r.z, r.w};
-                    const int k = (int)(D - zo);                       // 1..15 bytes: whole dwords, then bytes
-                    for (int j = 0; j < (k >> 2); ++j) *(u32_u*)(op + 4 * j) = t4[j];
-                    for (int b = k & ~3; b < k; ++b) op[b] = (u8)(t4[b >> 2] >> (8 * (b & 3)));
-                }
-            }
+        for (int i = 0; i < 4; ++i) {
+            const i64 x = x0 + 4 * xg + i;
+            if (x >= W || zo >= D) continue;
+            const u32x4 r = (mkc >> (4 + i)) & 1u ? kept_run(o[i], vb[i]) : (u32x4)(0u);
+            u8* op = out + (x * H + y) * D + zo;
+            if (!RAGGED || zo + 15 < D) __builtin_nontemporal_store(r, (u32x4_u*)op);
+            else store_head(op, r, (int)(D - zo));
         }
     }
 }
@@ -372,14 +293,9 @@ __global__ __launch_bounds__(1024) void k_rot90w(const u8* __restrict__ in, u8* 
     const int g = 15 - zg;                               // row group holding this thread's 16 source rows
     const u32 rd_off = (u32)(16 * g * 256 + 16 * ((xg >> 2) ^ g) + 4 * (xg & 3));
     const i64 zo = z0 + 16 * zg;
-    u32 vb[4];
+    u32 vb[4];                                          // validity bits of this thread's four output runs
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const i64 x = x0 + 4 * xg + i;
-        u32 v = 0;
-        if (x < W && zo < D) { const u32* vr = vbits + x * nw + (zo >> 5); v = (u32)((((u64)vr[1] << 32) | (u64)vr[0]) >> (zo & 31)) & 0xffffu; }
-        vb[i] = v;
-    }
+    for (int i = 0; i < 4; ++i) vb[i] = x0 + 4 * xg + i < W ? valid16(vbits, nw, x0 + 4 * xg + i, zo, D) : 0u;
     // The workgroup's mask flags (blk_on): its 256 source rows and 256 output rows are the same for all of its planes, and the mask
     // bytes of one row's planes are neighbours in memory -- fetched once, eight planes per load, kept as 0 / 1 flags behind the tile:
     // flag of plane y_beg + p at blk[512 p + r], r < 256 a source row, 256 + r an output row.  (Per plane, every thread fetched the
@@ -443,46 +359,20 @@ __global__ __launch_bounds__(1024) void k_rot90w(const u8* __restrict__ in, u8* 
 #pragma unroll
             for (int j = 0; j < 4; ++j) mkc |= (u32)(((ms_raw >> (8 * j)) & 0xffu) != 0) << j | (u32)(((md_raw >> (8 * j)) & 0xffu) != 0) << (4 + j);
         }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int lr = (tid >> 4) + 64 * j;
-            *(u32x4*)(wtile + lr * 256 + 16 * (cb ^ ((lr >> 4) & 15))) = ((mkc >> j) & 1u) ? stg[j] : (u32x4)(0u);
-        }
+        stage4<16, 64>(wtile, tid >> 4, cb, stg, mkc);
         __syncthreads();
         load_plane(y + 1);
         u32 d[16];
 #pragma unroll
         for (int rr = 0; rr < 16; ++rr) d[rr] = *(const u32*)(wtile + rd_off + rr * 256);
         __syncthreads();                                  // the tile is free again: the next plane's data may be written
-        u32 o[4][4];
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const u32 A = d[15 - 4 * w], B = d[14 - 4 * w], Cc = d[13 - 4 * w], E = d[12 - 4 * w];
-            const u32 t0 = perm(B, A, 0x05010400u), t1 = perm(B, A, 0x07030602u);
-            const u32 u0 = perm(E, Cc, 0x05010400u), u1 = perm(E, Cc, 0x07030602u);
-            o[0][w] = perm(u0, t0, 0x05040100u);
-            o[1][w] = perm(u0, t0, 0x07060302u);
-            o[2][w] = perm(u1, t1, 0x05040100u);
-            o[3][w] = perm(u1, t1, 0x07060302u);
-        }
+        u32 o[4][4];  // o[i][w]: output x = 4 xg + i, bytes q = 4w .. 4w+3 ; byte q <- d[15 - q].byte[i]
+        transpose16x4(d, o);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const i64 x = x0 + 4 * xg + i;
             if (x >= W || zo >= D) continue;
-            const u32 vbi = vb[i];
-            u32x4 r = (u32x4)(0u);
-            if ((mkc >> (4 + i)) & 1u) {
-                r.x = o[i][0]; r.y = o[i][1]; r.z = o[i][2]; r.w = o[i][3];
-                if (vbi != 0xffffu) {
-                    u32 mw[4];
-#pragma unroll
-                    for (int w = 0; w < 4; ++w) {
-                        const u32 b4 = (vbi >> (4 * w)) & 0xfu;
-                        mw[w] = ((b4 & 1u) ? 0x000000ffu : 0u) | ((b4 & 2u) ? 0x0000ff00u : 0u) | ((b4 & 4u) ? 0x00ff0000u : 0u) | ((b4 & 8u) ? 0xff000000u : 0u);
-                    }
-                    r.x &= mw[0]; r.y &= mw[1]; r.z &= mw[2]; r.w &= mw[3];
-                }
-            }
+            const u32x4 r = (mkc >> (4 + i)) & 1u ? kept_run(o[i], vb[i]) : (u32x4)(0u);
             __builtin_nontemporal_store(r, (u32x4*)(out + (x * H + y) * D + zo));
         }
     }
@@ -498,9 +388,9 @@ __global__ __launch_bounds__(1024) void k_rot90w(const u8* __restrict__ in, u8* 
 // (y, z) = divmod(128 s + j, D) and comes from source row n0 = c0 - z of plane y: 128 row reads of 128 bytes along x, as in k_rot90;
 // LDS layout, transpose and thread roles are k_rot90's (local source row lr holds byte j = 127 - lr).
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256, ROT90_WAVES) void k_rot90_flat(const u8* __restrict__ in, u8* __restrict__ out, const u8* __restrict__ mask_src,
-                                                                 const u8* __restrict__ mask_dst, const u32* __restrict__ vbits, int nw, int c0, int c2,
-                                                                 i64 W, i64 H, i64 D, int TS, TileMap tm, pb3d_magic mD, i64 nseg) {
+__global__ __launch_bounds__(256, 4) void k_rot90_flat(const u8* __restrict__ in, u8* __restrict__ out, const u8* __restrict__ mask_src,
+                                                       const u8* __restrict__ mask_dst, const u32* __restrict__ vbits, int nw, int c0, int c2,
+                                                       i64 W, i64 H, i64 D, int TS, TileMap tm, pb3d_magic mD, i64 nseg) {
     __shared__ __attribute__((aligned(16))) u8 tiles[2][128 * 128];
     const int tid = threadIdx.x;
     i64 zt, xt, sc;
@@ -515,15 +405,6 @@ __global__ __launch_bounds__(256, ROT90_WAVES) void k_rot90_flat(const u8* __res
     const int zg = tid & 7, xg = tid >> 3;
     const int g = 7 - zg;
     const u32 rd_off = (u32)(16 * g * 128 + 16 * ((xg >> 2) ^ g) + 4 * (xg & 3));
-    // 16 validity bits of row x for z = zlo .. zlo + 15 (zero outside [0, D))
-    auto vwin = [&](i64 x, i64 zlo) -> u32 {
-        if (zlo <= -16 || zlo >= D) return 0u;
-        const i64 zs = zlo < 0 ? 0 : zlo;
-        const u32* vr = vbits + x * nw + (zs >> 5);
-        u32 v = (u32)((((u64)vr[1] << 32) | (u64)vr[0]) >> (zs & 31)) & 0xffffu;
-        if (zlo < 0) v = (v << (int)(-zlo)) & 0xffffu;
-        return v;
-    };
     u32x4 stg[4];
     u32 msk;           // bit j: source-row mask of piece j
     u32 keep[4];       // per output row: the 16 keep bits of this thread's piece (validity AND destination-row mask)
@@ -538,16 +419,7 @@ __global__ __launch_bounds__(256, ROT90_WAVES) void k_rot90_flat(const u8* __res
             const i64 n0 = (i64)c0 - (i64)z;
             stg[j] = (u32x4)(0u);
             if (live && (i64)f < HD && cmode != 0 && n0 >= 0 && n0 < W) {          // (f >= H * D: the ragged last segment of a stream that is not whole lines)
-                const u8* sp = in + (n0 * H + (i64)y) * D + scol;
-                // a ragged piece may be read whole as long as it stays inside the volume: the bytes beyond the row belong to
-                // the neighbouring row and are dropped by the validity bits (their source column is outside [0, D))
-                if (cmode == 2 || (sp >= in && sp + 16 <= in + W * HD)) stg[j] = __builtin_nontemporal_load((const u32x4_u*)sp);
-                else {
-                    u32 t4[4] = {0, 0, 0, 0};
-                    for (int b = 0; b < 16; ++b)
-                        if (scol + b >= 0 && scol + b < D) t4[b >> 2] |= (u32)sp[b] << (8 * (b & 3));
-                    stg[j].x = t4[0]; stg[j].y = t4[1]; stg[j].z = t4[2]; stg[j].w = t4[3];
-                }
+                stg[j] = load_piece(in, (n0 * H + (i64)y) * D + scol, W * HD, cmode == 2, scol, D);
                 mk |= (u32)((mask_src ? mask_src[n0 * H + (i64)y] : (u8)1) != 0) << j;
             }
         }
@@ -563,8 +435,8 @@ __global__ __launch_bounds__(256, ROT90_WAVES) void k_rot90_flat(const u8* __res
             const i64 x = x0 + 4 * xg + i;
             u32 k = 0;
             if (pin && x < W) {
-                u32 bits = vwin(x, (i64)z);
-                if (nA < 16) bits |= vwin(x, (i64)z - D);
+                u32 bits = valid16(vbits, nw, x, (i64)z, D);
+                if (nA < 16) bits |= valid16(vbits, nw, x, (i64)z - D, D);
                 if (bits) {
                     const u32 mA = (mask_dst ? mask_dst[x * H + (i64)y] : (u8)1) != 0 ? lowA : 0u;
                     const u32 mB = (nA < 16 && (mask_dst ? mask_dst[x * H + (i64)y + 1] : (u8)1) != 0) ? (0xffffu & ~lowA) : 0u;
@@ -579,11 +451,7 @@ __global__ __launch_bounds__(256, ROT90_WAVES) void k_rot90_flat(const u8* __res
     for (i64 s = s_beg; s < s_end; ++s) {
         u8* tile = tiles[buf];
         buf ^= 1;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int lr = (tid >> 3) + 32 * j;
-            *(u32x4*)(tile + lr * 128 + 16 * (cb ^ ((lr >> 4) & 7))) = ((msk >> j) & 1u) ? stg[j] : (u32x4)(0u);
-        }
+        stage4<8, 32>(tile, tid >> 3, cb, stg, msk);
         __syncthreads();      // the only barrier of the segment: the other tile buffer was last read before the previous one
         u32 kcur[4];
 #pragma unroll
@@ -593,35 +461,12 @@ __global__ __launch_bounds__(256, ROT90_WAVES) void k_rot90_flat(const u8* __res
 #pragma unroll
         for (int rr = 0; rr < 16; ++rr) d[rr] = *(const u32*)(tile + rd_off + rr * 128);
         u32 o[4][4];  // o[i][w]: output x = 4 xg + i, bytes q = 4w .. 4w+3 ; byte q <- d[15 - q].byte[i]
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const u32 A = d[15 - 4 * w], B = d[14 - 4 * w], Cc = d[13 - 4 * w], E = d[12 - 4 * w];
-            const u32 t0 = perm(B, A, 0x05010400u), t1 = perm(B, A, 0x07030602u);
-            const u32 u0 = perm(E, Cc, 0x05010400u), u1 = perm(E, Cc, 0x07030602u);
-            o[0][w] = perm(u0, t0, 0x05040100u);
-            o[1][w] = perm(u0, t0, 0x07060302u);
-            o[2][w] = perm(u1, t1, 0x05040100u);
-            o[3][w] = perm(u1, t1, 0x07060302u);
-        }
+        transpose16x4(d, o);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const i64 x = x0 + 4 * xg + i;
             if (x >= W) continue;
-            const u32 kb = kcur[i];
-            u32x4 r = (u32x4)(0u);
-            if (kb) {
-                r.x = o[i][0]; r.y = o[i][1]; r.z = o[i][2]; r.w = o[i][3];
-                if (kb != 0xffffu) {
-                    u32 mw[4];
-#pragma unroll
-                    for (int w = 0; w < 4; ++w) {
-                        const u32 b4 = (kb >> (4 * w)) & 0xfu;
-                        mw[w] = ((b4 & 1u) ? 0x000000ffu : 0u) | ((b4 & 2u) ? 0x0000ff00u : 0u) | ((b4 & 4u) ? 0x00ff0000u : 0u) |
-                                ((b4 & 8u) ? 0xff000000u : 0u);
-                    }
-                    r.x &= mw[0]; r.y &= mw[1]; r.z &= mw[2]; r.w &= mw[3];
-                }
-            }
+            const u32x4 r = kcur[i] ? kept_run(o[i], kcur[i]) : (u32x4)(0u);
             if (128 * s + 16 * zg < HD)                                                       // (absent only in a ragged last segment)
                 __builtin_nontemporal_store(r, (u32x4*)(out + x * HD + 128 * s + 16 * zg));     // a whole aligned piece (of a whole aligned line when H * D % 128 == 0)
         }
@@ -671,14 +516,6 @@ __global__ __launch_bounds__(1024) void k_rot90wf(const u8* __restrict__ in, u8*
         const i64 x = x0 + 4 * xg + i;
         iv[i] = (xrow_ok && x < W) ? ivals[x] : 0u;
     }
-    auto vwin = [&](i64 x, i64 zlo) -> u32 {
-        if (zlo <= -16 || zlo >= D) return 0u;
-        const i64 zs = zlo < 0 ? 0 : zlo;
-        const u32* vr = vbits + x * nw + (zs >> 5);
-        u32 v = (u32)((((u64)vr[1] << 32) | (u64)vr[0]) >> (zs & 31)) & 0xffffu;
-        if (zlo < 0) v = (v << (int)(-zlo)) & 0xffffu;
-        return v;
-    };
     // The workgroup's MASK BLOCK: its segments lie in the planes Y0 .. Y1 (a handful: TS * 256 / D), and of the two mask images they
     // touch only the pixels (any source row, those planes) and (the tile's XW output rows, those planes).  Those bytes are fetched
     // ONCE, eight planes of a row per load (they are neighbours in memory), and stay in LDS behind the tile: row r of window w at
@@ -757,17 +594,7 @@ __global__ __launch_bounds__(1024) void k_rot90wf(const u8* __restrict__ in, u8*
         for (int j = 0; j < 4; ++j) {
             stg[j] = (u32x4)(0u);
             if (moff[j] != 0xffffffffu) {
-                const i64 doff = (i64)moff[j] * D + scol;
-                const u8* sp = in + doff;
-                // a ragged block may be read whole as long as it stays inside the volume: the bytes beyond the row belong to the
-                // neighbouring row and are dropped by the validity bits (their source column is outside [0, D))
-                if (cmode == 2 || (doff >= 0 && doff + 16 <= W * HD)) stg[j] = __builtin_nontemporal_load((const u32x4_u*)sp);
-                else {                                                     // the ragged block of the last tile: byte by byte inside [0, D)
-                    u32 t4[4] = {0, 0, 0, 0};
-                    for (int b = 0; b < 16; ++b)
-                        if (scol + b >= 0 && scol + b < D) t4[b >> 2] |= (u32)sp[b] << (8 * (b & 3));
-                    stg[j].x = t4[0]; stg[j].y = t4[1]; stg[j].z = t4[2]; stg[j].w = t4[3];
-                }
+                stg[j] = load_piece(in, (i64)moff[j] * D + scol, W * HD, cmode == 2, scol, D);
             }
         }
         if (!blk_on) {
@@ -784,11 +611,7 @@ __global__ __launch_bounds__(1024) void k_rot90wf(const u8* __restrict__ in, u8*
     addr_seg(s_beg + 1);
     for (i64 s = s_beg; s < s_end; ++s) {
         // ---- the segment's data has arrived: into LDS, with the mask flags
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int lr = (tid >> 4) + 64 * j;
-            *(u32x4*)(wtile + lr * 256 + 16 * (cb ^ ((lr >> 4) & 15))) = stg[j];
-        }
+        stage4<16, 64>(wtile, tid >> 4, cb, stg, 0xfu);
         msh[tid] = (u8)(mraw != 0);
         const int z = pz;
         const int pa = (int)(py - pya);                   // the piece's plane within the segment's (0 .. 2)
@@ -814,7 +637,7 @@ __global__ __launch_bounds__(1024) void k_rot90wf(const u8* __restrict__ in, u8*
                     if (iv[i] != 0xffffffffu) {
                         const int lo = (int)(iv[i] & 0xffffu), hi = (int)(iv[i] >> 16);
                         bits = (bits_between(lo - z, hi - z) & lowA) | (bits_between(lo - (z - (int)D), hi - (z - (int)D)) & ~lowA & 0xffffu);
-                    } else { bits = vwin(x0 + 4 * xg + i, (i64)z); if (nA < 16) bits |= vwin(x0 + 4 * xg + i, (i64)z - D); }
+                    } else { bits = valid16(vbits, nw, x0 + 4 * xg + i, (i64)z, D); if (nA < 16) bits |= valid16(vbits, nw, x0 + 4 * xg + i, (i64)z - D, D); }
                     const u32 mA = ((mdA >> (8 * i)) & 0xffu) ? lowA : 0u;
                     const u32 mB = ((mdB >> (8 * i)) & 0xffu) ? (0xffffu & ~lowA) : 0u;
                     k = bits & (mA | mB) & srcbits;
@@ -828,36 +651,13 @@ __global__ __launch_bounds__(1024) void k_rot90wf(const u8* __restrict__ in, u8*
         __syncthreads();                                  // the tile and the flags are free again: the next segment's may be written
         addr_seg(s + 2);
         if (!xrow_ok || z < 0) continue;                                   // (a piece past the stream's end: ragged last segment only)
-        u32 o[4][4];
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const u32 A = d[15 - 4 * w], B = d[14 - 4 * w], Cc = d[13 - 4 * w], E = d[12 - 4 * w];
-            const u32 t0 = perm(B, A, 0x05010400u), t1 = perm(B, A, 0x07030602u);
-            const u32 u0 = perm(E, Cc, 0x05010400u), u1 = perm(E, Cc, 0x07030602u);
-            o[0][w] = perm(u0, t0, 0x05040100u);
-            o[1][w] = perm(u0, t0, 0x07060302u);
-            o[2][w] = perm(u1, t1, 0x05040100u);
-            o[3][w] = perm(u1, t1, 0x07060302u);
-        }
+        u32 o[4][4];  // o[i][w]: output x = 4 xg + i, bytes q = 4w .. 4w+3 ; byte q <- d[15 - q].byte[i]
+        transpose16x4(d, o);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const i64 x = x0 + 4 * xg + i;
             if (x >= W) continue;
-            const u32 kb = kcur[i];
-            u32x4 r = (u32x4)(0u);
-            if (kb) {
-                r.x = o[i][0]; r.y = o[i][1]; r.z = o[i][2]; r.w = o[i][3];
-                if (kb != 0xffffu) {
-                    u32 mw[4];
-#pragma unroll
-                    for (int w = 0; w < 4; ++w) {
-                        const u32 b4 = (kb >> (4 * w)) & 0xfu;
-                        mw[w] = ((b4 & 1u) ? 0x000000ffu : 0u) | ((b4 & 2u) ? 0x0000ff00u : 0u) | ((b4 & 4u) ? 0x00ff0000u : 0u) |
-                                ((b4 & 8u) ? 0xff000000u : 0u);
-                    }
-                    r.x &= mw[0]; r.y &= mw[1]; r.z &= mw[2]; r.w &= mw[3];
-                }
-            }
+            const u32x4 r = kcur[i] ? kept_run(o[i], kcur[i]) : (u32x4)(0u);
             __builtin_nontemporal_store(r, (u32x4*)(out + x * HD + 256 * s + 16 * zg));
         }
     }
@@ -890,14 +690,6 @@ __global__ __launch_bounds__(256) void k_job_bitset(const u8* __restrict__ mask_
 // true when the (x,z) part of (M, off) is a signed permutation up to 2^-40 with an offset within
 // 2^-20 of an integer: every coordinate of every voxel (< 2^20 per axis) is then within 2^-18 of an
 // integer and the step is an exact byte permutation (see the header of this file).
-// a permutation-like step that pb3d_launch_rotate_perm can run on these buffers: the 90-degree map has no alignment or
-// size condition (k_rot90); the other signed permutations (180, 270 degrees) use the dword kernel k_rotate_perm
-bool pb3d_perm_step_ok(const double M[9], const double off[3], i64 W, i64 D, const void* a, const void* b) {
-    if (!pb3d_is_perm_step(M, off, W, D)) return false;
-    const bool rot90 = nearbyint(M[0]) == 0 && nearbyint(M[2]) == -1 && nearbyint(M[6]) == 1 && nearbyint(M[8]) == 0;
-    return rot90 || (D % 4 == 0 && (((uintptr_t)a | (uintptr_t)b) & 3u) == 0);
-}
-
 bool pb3d_is_perm_step(const double M[9], const double off[3], i64 W, i64 D) {
     if (W >= (1ll << 20) || D >= (1ll << 20)) return false;
     const int idx[4] = {0, 2, 6, 8};
@@ -913,16 +705,28 @@ bool pb3d_is_perm_step(const double M[9], const double off[3], i64 W, i64 D) {
     return true;
 }
 
-// integer form of a permutation-like step: n0 = r00*x + r02*z + c0, n2 = r20*x + r22*z + c2
-struct PermMap {
+// A permutation-like step (pb3d_is_perm_step) as the kernels take it: the f64 parameters of its bounds tests, its integer map
+// n0 = r00*x + r02*z + c0, n2 = r20*x + r22*z + c2, and whether that is the 90-degree map n0 = c0 - z, n2 = x + c2.
+struct PermStep {
+    RotParams p;
     int r00, r02, r20, r22, c0, c2;
+    bool rot90;
 };
 
-static PermMap perm_map(const double M[9], const double off[3]) {
-    PermMap m;
-    m.r00 = (int)nearbyint(M[0]); m.r02 = (int)nearbyint(M[2]); m.r20 = (int)nearbyint(M[6]); m.r22 = (int)nearbyint(M[8]);
-    m.c0 = (int)nearbyint(off[0]); m.c2 = (int)nearbyint(off[2]);
-    return m;
+static PermStep perm_step(const double M[9], const double off[3]) {
+    PermStep s;
+    s.p = {M[0], M[1], M[2], off[0], M[6], M[7], M[8], off[2]};
+    s.r00 = (int)nearbyint(M[0]); s.r02 = (int)nearbyint(M[2]); s.r20 = (int)nearbyint(M[6]); s.r22 = (int)nearbyint(M[8]);
+    s.c0 = (int)nearbyint(off[0]); s.c2 = (int)nearbyint(off[2]);
+    s.rot90 = s.r00 == 0 && s.r02 == -1 && s.r20 == 1 && s.r22 == 0;
+    return s;
+}
+
+// a permutation-like step that pb3d_launch_rotate_perm can run on these buffers: the 90-degree map has no alignment or
+// size condition (k_rot90); the other signed permutations (180, 270 degrees) use the dword kernel k_rotate_perm
+bool pb3d_perm_step_ok(const double M[9], const double off[3], i64 W, i64 D, const void* a, const void* b) {
+    if (!pb3d_is_perm_step(M, off, W, D)) return false;
+    return perm_step(M, off).rot90 || (D % 4 == 0 && (((uintptr_t)a | (uintptr_t)b) & 3u) == 0);
 }
 
 static int build_valid_table(pb3d_ctx* ctx, const RotParams& p, i64 W, i64 D, u32** bits, int* nw) {
@@ -952,39 +756,46 @@ static int build_valid_table(pb3d_ctx* ctx, const RotParams& p, i64 W, i64 D, u3
 
 // the validity bit table of a permutation-like step for other translation units (csrc/sliced.hip: the chain's last step un-slices)
 int pb3d_perm_valid_table(pb3d_ctx* ctx, const double M[9], const double off[3], i64 W, i64 D, u32** bits, int* nw, int* c0, int* c2, bool* rot90) {
-    const RotParams p = {M[0], M[1], M[2], off[0], M[6], M[7], M[8], off[2]};
-    const PermMap pm = perm_map(M, off);
-    *c0 = pm.c0; *c2 = pm.c2;
-    *rot90 = pm.r00 == 0 && pm.r02 == -1 && pm.r20 == 1 && pm.r22 == 0;
-    return build_valid_table(ctx, p, W, D, bits, nw);
+    const PermStep ps = perm_step(M, off);
+    *c0 = ps.c0; *c2 = ps.c2; *rot90 = ps.rot90;
+    return build_valid_table(ctx, ps.p, W, D, bits, nw);
+}
+
+// The kernel of a 90-degree step: the first form whose condition holds, in this order (shapes W x H x D of the plain
+// process_voxel_grid(., ., 90) step, no knobs set).
+//   WF           flat && W >= 160 && H * D < 2^31 - 1024 && W * H < 2^32 - 1 && rot90_wide != 2                     355x512x355, 437x512x437, 500x400x500
+//   FLAT         flat                                                                                               131x256x131
+//   WIDE         D % 16 == 0 && c2 % 16 == 0 && W >= 256 && D >= 256 && rot90_wide != 2, in / out 16-byte aligned   1024^3, 512x278x512
+//   TILE         D % 16 == 0 && c2 % 16 == 0                                                                        128x123x128, 96x96x96
+//   TILE_RAGGED  anything else                                                                                      355x355x355, 100x64x100
+// flat: rows that are not whole lines (D % 128 != 0, D >= 128) whose x-row streams are whole lines (H * D % 128 == 0: every real
+// shape of the reference whose longer mask side is the height) or at least whole 16-byte pieces (H * D % 16 == 0, e.g.
+// 500 x 400 x 500: the last segment of an x-row's stream is ragged, the rows of odd x start mid-line), H * D < 2^31 - 256 and out
+// 128-byte aligned.  Knob rot90_flat: 1 = never flat, 2 = whole-line streams only.  Knob rot90_wide = 2: neither 1024-thread form.
+enum class Rot90Form { WF, FLAT, WIDE, TILE, TILE_RAGGED };
+
+static Rot90Form rot90_form(const pb3d_ctx* ctx, i64 W, i64 H, i64 D, int c2, const void* in, const void* out) {
+    const bool lines_ok = D % 128 != 0 && (H * D) % 128 == 0 && D >= 128 && ctx->tune_rot90_flat != 1;
+    const bool flat16 = D % 128 != 0 && (H * D) % 16 == 0 && D >= 128 && ctx->tune_rot90_flat == 0;
+    const bool flat = (lines_ok || flat16) && H * D < (1ll << 31) - 256 && (((uintptr_t)out) & 127u) == 0;
+    if (flat && W >= 160 && H * D < (1ll << 31) - 1024 && W * H < 0xffffffffll && ctx->tune_rot90_wide != 2) return Rot90Form::WF;
+    if (flat) return Rot90Form::FLAT;
+    if (D % 16 == 0 && c2 % 16 == 0 && W >= 256 && D >= 256 && ctx->tune_rot90_wide != 2 && (((uintptr_t)in | (uintptr_t)out) & 15u) == 0)
+        return Rot90Form::WIDE;
+    return D % 16 == 0 && c2 % 16 == 0 ? Rot90Form::TILE : Rot90Form::TILE_RAGGED;
 }
 
 int pb3d_launch_rotate_perm(pb3d_ctx* ctx, const u8* d_in, i64 W, i64 H, i64 D, const double M[9], const double off[3],
                             const u8* d_mask_src, const u8* d_mask_dst, u8* d_out) {
-    RotParams p = {M[0], M[1], M[2], off[0], M[6], M[7], M[8], off[2]};
-    const PermMap pm = perm_map(M, off);
-    const bool rot90 = pm.r00 == 0 && pm.r02 == -1 && pm.r20 == 1 && pm.r22 == 0;
-    PB3D_REQUIRE(rot90 || (D % 4 == 0 && (((uintptr_t)d_in | (uintptr_t)d_out) & 3u) == 0), "pb3d_rotate_perm: needs D %% 4 == 0");
-    if (rot90 && W <= 65535 * 128 && H <= 65535) {
+    const PermStep ps = perm_step(M, off);
+    PB3D_REQUIRE(ps.rot90 || (D % 4 == 0 && (((uintptr_t)d_in | (uintptr_t)d_out) & 3u) == 0), "pb3d_rotate_perm: needs D %% 4 == 0");
+    if (ps.rot90 && W <= 65535 * 128 && H <= 65535) {
         u32* bits; int nw;
-        PB3D_TRY(build_valid_table(ctx, p, W, D, &bits, &nw));
-        // rows that are not whole lines: the stream of each x-row tiled in whole lines (k_rot90_flat / k_rot90wf) -- streams that are whole lines
-        // (H * D % 128 == 0: every real shape of the reference whose longer mask side is the height) or at least whole 16-byte pieces
-        // (H * D % 16 == 0, e.g. 500 x 400 x 500: the last segment of an x-row's stream is ragged, the rows of odd x start mid-line);
-        // knob rot90_flat: 1 = the row-wise tile kernel instead, 2 = whole-line streams only
-        const bool lines_ok = D % 128 != 0 && (H * D) % 128 == 0 && D >= 128 && ctx->tune_rot90_flat != 1;
-        const bool flat16 = D % 128 != 0 && (H * D) % 16 == 0 && D >= 128 && ctx->tune_rot90_flat == 0;
-        const bool flat = (lines_ok || flat16) && H * D < (1ll << 31) - 256 && (((uintptr_t)d_out) & 127u) == 0;
-        const i64 nzt = (D + 127) / 128;
-        const i64 tiles = nzt * ((W + 127) / 128);
-        const int TY = planes_per_chunk(H, tiles, ctx->cus, 32, ctx->tune_rot90_fill);
-        const TileMap tm = {(int)nzt, (int)((W + 127) / 128), (int)((H + TY - 1) / TY), ctx->tune_rot90_order == 1 ? 1 : 0};
-        dim3 grid(tilemap_blocks(tm));
-#ifndef PB3D_ROT90_DEPTH
-#define PB3D_ROT90_DEPTH 1
-#endif
-        if (flat && W >= 160 && H * D < (1ll << 31) - 1024 && W * H < 0xffffffffll && ctx->tune_rot90_wide != 2) {
-            // 256-byte segments, 1024 threads (tune rot90_wide = 2: the 128-row x 128-byte form below)
+        PB3D_TRY(build_valid_table(ctx, ps.p, W, D, &bits, &nw));
+        const Rot90Form form = rot90_form(ctx, W, H, D, ps.c2, d_in, d_out);
+        switch (form) {
+        case Rot90Form::WF: {
+            // 256-byte segments, 1024 threads (tune rot90_wide = 2: the 128-row x 128-byte form)
             if (!ctx->rot90wf_lds_set) {
                 PB3D_HIP(hipFuncSetAttribute((const void*)k_rot90wf, hipFuncAttributeMaxDynamicSharedMemorySize, 256 * 256 + 48 * 1024));
                 ctx->rot90wf_lds_set = true;
@@ -1003,14 +814,18 @@ int pb3d_launch_rotate_perm(pb3d_ctx* ctx, const u8* d_in, i64 W, i64 H, i64 D, 
             const size_t blk_bytes = (size_t)((W + 16 * npc) * 8 * nwin);
             const int blk_on = blk_bytes <= 48 * 1024 && ctx->tune_rot90_mask_block != 1;
             hipLaunchKernelGGL(k_rot90wf, dim3(tilemap_blocks(fm)), dim3(1024), 256 * 256 + (blk_on ? blk_bytes : 0), ctx->stream, d_in, d_out, d_mask_src, d_mask_dst,
-                               (const u32*)bits, (const u32*)bits + W * nw, nw, pm.c0, pm.c2, W, H, D, TS, fm, pb3d_make_magic((u32)D), nseg, npc, blk_on);
-        } else if (flat) {
+                               (const u32*)bits, (const u32*)bits + W * nw, nw, ps.c0, ps.c2, W, H, D, TS, fm, pb3d_make_magic((u32)D), nseg, npc, blk_on);
+            break;
+        }
+        case Rot90Form::FLAT: {
             const i64 nseg = (H * D + 127) / 128, nxt = (W + 127) / 128;
             const int TS = planes_per_chunk(nseg, nxt, ctx->cus, 32, ctx->tune_rot90_fill);
             const TileMap fm = {1, (int)nxt, (int)((nseg + TS - 1) / TS), ctx->tune_rot90_order == 1 ? 1 : 0};
             hipLaunchKernelGGL(k_rot90_flat, dim3(tilemap_blocks(fm)), dim3(256), 0, ctx->stream, d_in, d_out, d_mask_src, d_mask_dst, (const u32*)bits, nw,
-                               pm.c0, pm.c2, W, H, D, TS, fm, pb3d_make_magic((u32)D), nseg);
-        } else if (D % 16 == 0 && pm.c2 % 16 == 0 && W >= 256 && D >= 256 && ctx->tune_rot90_wide != 2 && (((uintptr_t)d_in | (uintptr_t)d_out) & 15u) == 0) {
+                               ps.c0, ps.c2, W, H, D, TS, fm, pb3d_make_magic((u32)D), nseg);
+            break;
+        }
+        case Rot90Form::WIDE: {
             // the 256 x 256-tile form (tune rot90_wide = 2: the 128-tile kernel).  Measured with tools/tybench.py on one box, variants
             // interleaved (ms, 128-tile kernel -> this one): 1024^3 0.464 -> 0.430, 512^3 0.0665 -> 0.0608, 512 x 278 x 512 0.046 -> 0.035.
             // Workgroups per CU: as many (up to 8) as leave a workgroup at least 4 planes.  With the mask flags in LDS (tools/tybench.py,
@@ -1028,13 +843,21 @@ int pb3d_launch_rotate_perm(pb3d_ctx* ctx, const u8* d_in, i64 W, i64 H, i64 D, 
             const TileMap wm = {(int)((D + 255) / 256), (int)((W + 255) / 256), (int)((H + TYw - 1) / TYw), 0};
             const int blk_on = TYw <= 64 && ctx->tune_rot90_mask_block != 1;                 // the workgroup's mask flags behind the tile: 512 bytes per plane
             hipLaunchKernelGGL(k_rot90w, dim3(tilemap_blocks(wm)), dim3(1024), 256 * 256 + (blk_on ? 512 * TYw : 0), ctx->stream, d_in, d_out, d_mask_src, d_mask_dst,
-                               (const u32*)bits, nw, pm.c0, pm.c2, W, H, D, TYw, wm, blk_on);
-        } else if (D % 16 == 0 && pm.c2 % 16 == 0)
-            hipLaunchKernelGGL((k_rot90<PB3D_ROT90_DEPTH, false>), grid, dim3(256), 0, ctx->stream, d_in, d_out, d_mask_src, d_mask_dst,
-                               (const u32*)bits, nw, pm.c0, pm.c2, W, H, D, TY, tm);
-        else
-            hipLaunchKernelGGL((k_rot90<PB3D_ROT90_DEPTH, true>), grid, dim3(256), 0, ctx->stream, d_in, d_out, d_mask_src, d_mask_dst,
-                               (const u32*)bits, nw, pm.c0, pm.c2, W, H, D, TY, tm);
+                               (const u32*)bits, nw, ps.c0, ps.c2, W, H, D, TYw, wm, blk_on);
+            break;
+        }
+        case Rot90Form::TILE:
+        case Rot90Form::TILE_RAGGED: {
+            const i64 nzt = (D + 127) / 128;
+            const i64 tiles = nzt * ((W + 127) / 128);
+            const int TY = planes_per_chunk(H, tiles, ctx->cus, 32, ctx->tune_rot90_fill);
+            const TileMap tm = {(int)nzt, (int)((W + 127) / 128), (int)((H + TY - 1) / TY), ctx->tune_rot90_order == 1 ? 1 : 0};
+            const dim3 grid(tilemap_blocks(tm));
+            hipLaunchKernelGGL(form == Rot90Form::TILE ? k_rot90<false> : k_rot90<true>, grid, dim3(256), 0, ctx->stream, d_in, d_out, d_mask_src,
+                               d_mask_dst, (const u32*)bits, nw, ps.c0, ps.c2, W, H, D, TY, tm);
+            break;
+        }
+        }
         PB3D_CHECK_LAUNCH();
         return PB3D_OK;
     }
@@ -1043,7 +866,7 @@ int pb3d_launch_rotate_perm(pb3d_ctx* ctx, const u8* d_in, i64 W, i64 H, i64 D, 
     while (TY > 1 && tiles * ((H + TY - 1) / TY) < (i64)ctx->cus * 8) TY >>= 1;
     dim3 grid((unsigned)((D + T - 1) / T), (unsigned)((W + T - 1) / T), (unsigned)((H + TY - 1) / TY));
     PB3D_REQUIRE(grid.y <= 65535u && grid.z <= 65535u, "pb3d_rotate_perm: grid too large");
-    hipLaunchKernelGGL(k_rotate_perm, grid, dim3(256), 0, ctx->stream, d_in, d_out, d_mask_src, d_mask_dst, p, W, H, D, TY);
+    hipLaunchKernelGGL(k_rotate_perm, grid, dim3(256), 0, ctx->stream, d_in, d_out, d_mask_src, d_mask_dst, ps.p, W, H, D, TY);
     PB3D_CHECK_LAUNCH();
     return PB3D_OK;
 }
@@ -1052,12 +875,11 @@ int pb3d_launch_rotate_perm(pb3d_ctx* ctx, const u8* d_in, i64 W, i64 H, i64 D, 
 int pb3d_launch_global_carve90(pb3d_ctx* ctx, const u8* d_bin_hw, const u8* d_rgb_hw3, int C, i64 h, i64 w, const double M[9],
                                const double off[3], i64 x0, i64 x1, u8* d_out_slab) {
     const i64 W = w, H = h, D = w;
-    RotParams p = {M[0], M[1], M[2], off[0], M[6], M[7], M[8], off[2]};
-    const PermMap pm = perm_map(M, off);
-    PB3D_REQUIRE(pm.r00 == 0 && pm.r02 == -1, "pb3d_global_carve: unexpected 90-degree map");
+    const PermStep ps = perm_step(M, off);
+    PB3D_REQUIRE(ps.rot90, "pb3d_global_carve: unexpected 90-degree map");
     u32* bits; int nw;
-    PB3D_TRY(build_valid_table(ctx, p, W, D, &bits, &nw));
-    return pb3d_launch_gc90_stream(ctx, d_bin_hw, d_rgb_hw3, C, (const u32*)bits, nw, pm.c0, W, H, D, x0, x1, d_out_slab);
+    PB3D_TRY(build_valid_table(ctx, ps.p, W, D, &bits, &nw));
+    return pb3d_launch_gc90_stream(ctx, d_bin_hw, d_rgb_hw3, C, (const u32*)bits, nw, ps.c0, W, H, D, x0, x1, d_out_slab);
 }
 
 // All-90-degree part_carve in one sweep (K5).  Returns PB3D_EUNSUPPORTED (without an error message of
@@ -1077,12 +899,10 @@ int pb3d_try_part_carve90(pb3d_ctx* ctx, const u8* d_colored, int C, i64 W, i64 
     PB3D_TRY(pb3d_rotinv(90, M));
     PB3D_TRY(pb3d_offset(M, shape, off));
     if (!pb3d_is_perm_step(M, off, W, D)) return PB3D_EUNSUPPORTED;
-    const PermMap pm = perm_map(M, off);
-    const bool rot90 = pm.r00 == 0 && pm.r02 == -1 && pm.r20 == 1 && pm.r22 == 0;
-    if (!(rot90 && W <= 65535 * 128 && H <= 65535)) return PB3D_EUNSUPPORTED;
-    RotParams p = {M[0], M[1], M[2], off[0], M[6], M[7], M[8], off[2]};
+    const PermStep ps = perm_step(M, off);
+    if (!(ps.rot90 && W <= 65535 * 128 && H <= 65535)) return PB3D_EUNSUPPORTED;
     u32* bits; int nw;
-    PB3D_TRY(build_valid_table(ctx, p, W, D, &bits, &nw));
+    PB3D_TRY(build_valid_table(ctx, ps.p, W, D, &bits, &nw));
     void *A, *AT;
     PB3D_TRY(pb3d_scratch(ctx, 5, (size_t)(W * H) * sizeof(u32), &A));
     PB3D_TRY(pb3d_scratch(ctx, 46, (size_t)(W * H) * sizeof(u32), &AT));
@@ -1097,6 +917,6 @@ int pb3d_try_part_carve90(pb3d_ctx* ctx, const u8* d_colored, int C, i64 W, i64 
                        (u32*)A, (u32*)AT, W, H);
     PB3D_CHECK_LAUNCH();
     int took = 0;
-    PB3D_TRY(pb3d_part_carve90_planes(ctx, d_colored, C, W, H, D, (const u32*)A, (const u32*)AT, nj, (const u32*)bits, nw, pm.c0, pm.c2, d_out, &took));
+    PB3D_TRY(pb3d_part_carve90_planes(ctx, d_colored, C, W, H, D, (const u32*)A, (const u32*)AT, nj, (const u32*)bits, nw, ps.c0, ps.c2, d_out, &took));
     return took ? PB3D_OK : PB3D_EUNSUPPORTED;          // (a plane of bits that does not fit the LDS: the caller's per-job pipeline)
 }
