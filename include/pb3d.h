@@ -352,6 +352,22 @@ int pb3d_guided_carve_label_dev(pb3d_ctx* ctx, uint8_t* d_grid_lab, const int32_
 /* the per-component steps (crops too large for the fused loop) on a label volume */
 int pb3d_crop_occupancy_label_dev(pb3d_ctx* ctx, const uint8_t* d_grid_lab, int64_t A0, int64_t A1, int64_t A2, const int64_t lo[3],
                                   const int64_t hi[3], uint8_t* d_occ);
+/* The labelling of pb3d_label_colors_stats_dev / pb3d_label_values_stats_dev (same contract, same outputs) at a chosen connectivity:
+ * 6, 18 or 26 neighbours, the structures of scipy.ndimage.generate_binary_structure(3, 1 | 2 | 3); 26 is the structure=np.ones((3,3,3))
+ * of extract_top_k_components (reference utils/voxel_utils.py:26).  channels = 3: d_grid is a colour grid and `colors` holds 3 bytes per
+ * colour; 1: a label volume and `colors` holds label values.  The existing entries stay 6-connected. */
+int pb3d_label_colors_conn_stats_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64_t A1, int64_t A2, const uint8_t* colors, int ncolors,
+                                     int channels, int connectivity, int32_t* d_labels, int64_t* ncomp, int64_t cap, int members_only,
+                                     int64_t* bbox_lo_hi, int64_t* count, int64_t* coord_sum, int* stats_valid);
+/* extract_top_k_components (reference utils/voxel_utils.py:24-33) in place on a resident grid WITHOUT a host round trip: the components of
+ * `color` at `connectivity` (26 in the reference) are labelled into d_labels (members only) with their statistics left on the device,
+ * ranked by height (ptp of their axis-1 coordinates; equal heights in label order, as the stable sorted() of :29), the first
+ * min(k, n) (k >= 0) or max(n + k, 0) (k < 0) kept -- the [:k] of :29 -- and the other members zeroed (three zero bytes; label 0 when
+ * channels = 1, where color[0] is the label value).  All queued on the context's stream.  d_status (device, two int64, may be NULL):
+ * [0] = number of components, [1] = 1 when the device could not decide (more than 16384 components, or A1 > 8192: nothing was zeroed;
+ * run pb3d_label_colors_conn_stats_dev + pb3d_component_stats_dev + pb3d_recolor_last_labelled_dev instead). */
+int pb3d_top_k_components_dev(pb3d_ctx* ctx, uint8_t* d_grid, int64_t A0, int64_t A1, int64_t A2, const uint8_t color[3], int channels, int64_t k,
+                              int connectivity, int32_t* d_labels, int64_t* d_status);
 int pb3d_component_paste_label_dev(pb3d_ctx* ctx, const uint8_t* d_grid_lab, const int32_t* d_labels, int32_t id, const uint8_t* d_carved_occ,
                                    int64_t A0, int64_t A1, int64_t A2, const int64_t lo[3], const int64_t hi[3], uint8_t* d_carved);
 int pb3d_extrude_label_dev(pb3d_ctx* ctx, const uint8_t* d_grid_lab, int64_t W, int64_t H, int64_t D, const uint8_t* d_valid, int64_t valid_w,

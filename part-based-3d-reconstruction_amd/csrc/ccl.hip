@@ -1,6 +1,7 @@
 // N1: 3-D connected components (6-connectivity) of up to eight colours in ONE labelling sequence -- scipy.ndimage.label(mask) with
 // the default structure, as called at reference utils/voxel_carving_utils.py:175 (once per part colour from :338) and :254:
-// the components of a colour are numbered in raster order of their first voxel.
+// the components of a colour are numbered in raster order of their first voxel.  18- and 26-connectivity (structure=np.ones((3,3,3)),
+// reference utils/voxel_utils.py:26) add one pass of diagonal links after the face links (k_ccl_merge_diag); nothing else changes.
 //
 // Round-4 form (round 2 built the bit-mask / row-frame design; SQ counters of that version, profiles/r04_ccl_sq_counters_before.txt:
 // k_ccl_init issued 3.1e8 vector + 3.9e8 scalar instructions per 1024^3 launch -- its lane-per-voxel forest initialisation, a serial
@@ -331,6 +332,82 @@ __global__ __launch_bounds__(256) void k_ccl_merge(const u64* __restrict__ bits_
                 reps &= reps - 1;
                 const u64 le = le_mask(i);
                 uf_union(parent, (int)(base + (u32)hi_bit(segM & le)), (int)(base + s + (u32)hi_bit(segN & le)));
+            }
+        }
+    }
+}
+
+// ---- the diagonal links of 18- and 26-connectivity (scipy.ndimage.generate_binary_structure(3, 2 | 3)) ------------------------------
+// Runs after EITHER face form (tile or generic) has made every face link, so both forms get the same diagonal links from one pass.  One
+// lane per 64-voxel window M of row (a0, a1), the forward neighbour rows N with an a2 offset d: N's voxel a2 + d touches M's voxel a2.
+// For a fixed (N, d) the contact set c = M & (N shifted by d) is made of runs along which the pair (run of M, run of N) does not change,
+// so one union per run of c covers every pair -- whatever the ±1 shift does to the gaps (two runs of N one empty voxel apart both touch
+// one run of M, and the reverse).  Fewer are needed:
+//   * rows that ALSO link at d = 0 (the face rows (a0, a1+1), (a0+1, a1), linked by the face pass, and the d = 0 contacts of the
+//     (a0+1, a1±1) rows, linked here at the start of every run): a run of the d = ±1 contact that is two or more voxels long shares a
+//     d = 0 overlap with the same two runs (M on [i0, i1], N on [i0 + d, i1 + d]: both hold [i0 + 1, i1] (d = +1) / [i0, i1 - 1] (d = -1)),
+//     so only ISOLATED contact bits need a union;
+//   * a run that is cut at a window edge only looks shorter or isolated: one redundant union, never a missing one.
+// Nothing here relies on the DIR 1 implied-link skip of the face pass beyond what it proves: the face pass leaves every overlapping pair
+// of face-adjacent runs connected (linked, or implied by other face links), which is all the d = ±1 rule above needs.
+// Contacts across a window edge read bit 63 of the window before / bit 0 of the window after in N's row (bits past A2 are zero, and no
+// window exists before t = 0 or after P - 1: the contacts stop at a2 = 0 and A2 - 1).  N's voxel j = i + d is named by its window's
+// segment (the init pass hangs every segment of a run under the run's first one, so any segment of the run is as good).
+template <int CONN>
+__global__ __launch_bounds__(256) void k_ccl_merge_diag(const u64* __restrict__ bits_all, i64 nwords, pb3d_magic mP, pb3d_magic m1, int A0, int A1,
+                                                        int A2, int* parent) {
+    const u64* __restrict__ bits = bits_all + (i64)blockIdx.y * nwords;
+    const i64 P = mP.d;
+    for (i64 idx = (i64)blockIdx.x * blockDim.x + threadIdx.x; idx < nwords; idx += (i64)gridDim.x * blockDim.x) {
+        const u64 M = bits[idx];
+        if (!M) continue;
+        const u32 row = pb3d_div((u32)idx, mP), t = (u32)idx - row * mP.d;
+        const int x0 = (int)pb3d_div(row, m1), x1 = (int)(row - (u32)x0 * m1.d);
+        const u32 base = row * (u32)A2 + 64u * t;
+        const u64 segM = M & ~(M << 1);
+        // the four forward rows: (a0, a1+1), (a0+1, a1), (a0+1, a1-1), (a0+1, a1+1); 18 takes the last two at d = 0 only
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int y0 = x0 + (r == 0 ? 0 : 1), y1 = x1 + (r == 0 ? 1 : (r == 1 ? 0 : (r == 2 ? -1 : 1)));
+            if (y0 >= A0 || y1 < 0 || y1 >= A1) continue;
+            const bool face = r < 2;
+            const bool side = face || CONN == 26;                             // d = -1, +1 links of this row
+            const u32 rowN = (u32)y0 * (u32)A1 + (u32)y1;
+            const i64 nidx = (i64)rowN * P + t;
+            const u64 N = bits[nidx];
+            const u64 Np = (side && t) ? bits[nidx - 1] : 0ull, Nn = (side && (i64)t + 1 < P) ? bits[nidx + 1] : 0ull;
+            if (!(N | (Np >> 63) | (Nn << 63))) continue;
+            const u32 baseN = rowN * (u32)A2 + 64u * t;
+            const u64 segN = N & ~(N << 1);
+            // N's voxel j (-1 .. 64) -> the node of its segment
+            auto nodeN = [&](int j) -> int {
+                if (j < 0) return (int)(baseN - 64u + (u32)hi_bit(Np & ~(Np << 1)));
+                if (j > 63) return (int)(baseN + 64u);                         // (bit 0 of a window always starts a segment)
+                return (int)(baseN + (u32)hi_bit(segN & le_mask(j)));
+            };
+            auto nodeM = [&](int i) -> int { return (int)(base + (u32)hi_bit(segM & le_mask(i))); };
+            if (!face) {                                                        // d = 0: every run start of the contact
+                const u64 c = M & N;
+                u64 reps = c & ~(c << 1);
+                while (reps) {
+                    const int i = __ffsll((unsigned long long)reps) - 1;
+                    reps &= reps - 1;
+                    uf_union(parent, nodeM(i), nodeN(i));
+                }
+            }
+            if (side) {
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    const int d = s == 0 ? -1 : 1;
+                    const u64 Nd = d < 0 ? ((N << 1) | (Np >> 63)) : ((N >> 1) | (Nn << 63));     // bit i = N's voxel i + d
+                    const u64 c = M & Nd;
+                    u64 reps = c & ~(c << 1) & ~(c >> 1);                       // isolated contacts only (see above)
+                    while (reps) {
+                        const int i = __ffsll((unsigned long long)reps) - 1;
+                        reps &= reps - 1;
+                        uf_union(parent, nodeM(i), nodeN(i + d));
+                    }
+                }
             }
         }
     }
@@ -673,8 +750,9 @@ __global__ __launch_bounds__(256) void k_ccl_fold(int K, int dcap, const i64* __
 // Scratch slot 40: [header 64 B: i64 total[8]] [head: K x kFirst records] [final: K x dcap records] [shadow: kCopies x K x dcap records]
 static int label_colors_impl(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64_t A1, int64_t A2, const uint8_t* colors, int K, int C,
                              int32_t* d_labels, int64_t* ncomp, int64_t cap, bool members_only, int64_t* bbox_lo_hi, int64_t* count,
-                             int64_t* coord_sum, int* stats_valid, pb3d_ccl_dev* dev = nullptr) {
+                             int64_t* coord_sum, int* stats_valid, pb3d_ccl_dev* dev = nullptr, int conn = 6) {
     PB3D_REQUIRE(ctx && colors && ncomp && A0 >= 0 && A1 >= 0 && A2 >= 0, "pb3d_label_color: bad argument");
+    PB3D_REQUIRE(conn == 6 || conn == 18 || conn == 26, "pb3d_label_colors: connectivity is 6, 18 or 26 (got %d)", conn);
     PB3D_REQUIRE(K >= 1 && K <= kMaxColors, "pb3d_label_colors: between 1 and %d colours per call (got %d)", kMaxColors, K);
     const i64 n = A0 * A1 * A2;
     for (int k = 0; k < K; ++k) { ncomp[k] = 0; if (stats_valid) stats_valid[k] = 0; }
@@ -747,6 +825,12 @@ static int label_colors_impl(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, i
                            (int)A0, (int)A1, (int)A2, parent);
     }
     PB3D_CHECK_LAUNCH();
+    if (conn != 6) {        // the diagonal links, after whichever face form ran (6-connectivity launches nothing more)
+        const dim3 dg(pb3d_stream_blocks(ctx, nwords, 256, 16), (unsigned)K);
+        if (conn == 18) hipLaunchKernelGGL(k_ccl_merge_diag<18>, dg, dim3(256), 0, ctx->stream, (const u64*)bits, nwords, mP, m1, (int)A0, (int)A1, (int)A2, parent);
+        else hipLaunchKernelGGL(k_ccl_merge_diag<26>, dg, dim3(256), 0, ctx->stream, (const u64*)bits, nwords, mP, m1, (int)A0, (int)A1, (int)A2, parent);
+        PB3D_CHECK_LAUNCH();
+    }
     hipLaunchKernelGGL(k_ccl_roots, dim3((unsigned)nchunks, (unsigned)K), dim3(256), 0, ctx->stream, (const u64*)bits, nwords, mP, (int)A2, (const int*)parent,
                        (u64*)rootbits, rootflag, chunk_count);
     PB3D_CHECK_LAUNCH();
@@ -855,9 +939,20 @@ extern "C" int pb3d_label_values_stats_dev(pb3d_ctx* ctx, const uint8_t* d_grid_
     return label_colors_impl(ctx, d_grid_lab, A0, A1, A2, values, nvalues, 1, d_labels, ncomp, cap, members_only != 0, bbox_lo_hi, count, coord_sum, stats_valid);
 }
 
-// labelling + statistics of ONE colour with everything left on the device (csrc/components.hip: pb3d_recolor_backward_dev)
+// any of the above at 6-, 18- or 26-connectivity (scipy.ndimage.generate_binary_structure(3, 1 | 2 | 3)); channels = 3: colours, 1: label values
+extern "C" int pb3d_label_colors_conn_stats_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64_t A1, int64_t A2, const uint8_t* colors,
+                                                int ncolors, int channels, int connectivity, int32_t* d_labels, int64_t* ncomp, int64_t cap,
+                                                int members_only, int64_t* bbox_lo_hi, int64_t* count, int64_t* coord_sum, int* stats_valid) {
+    PB3D_REQUIRE(stats_valid != nullptr, "pb3d_label_colors_conn_stats: null output");
+    PB3D_REQUIRE(channels == 1 || channels == 3, "pb3d_label_colors_conn_stats: channels is 1 (labels) or 3 (colours)");
+    return label_colors_impl(ctx, d_grid, A0, A1, A2, colors, ncolors, channels, d_labels, ncomp, cap, members_only != 0, bbox_lo_hi, count, coord_sum,
+                             stats_valid, nullptr, connectivity);
+}
+
+// labelling + statistics of ONE colour with everything left on the device (csrc/components.hip: pb3d_recolor_backward_dev,
+// pb3d_top_k_components_dev)
 int pb3d_ccl_label_on_device(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64_t A1, int64_t A2, const uint8_t color[3], int channels, int32_t* d_labels,
-                             int64_t cap, pb3d_ccl_dev* dev) {
+                             int64_t cap, pb3d_ccl_dev* dev, int connectivity) {
     int64_t ncomp = 0;
-    return label_colors_impl(ctx, d_grid, A0, A1, A2, color, 1, channels, d_labels, &ncomp, cap, true, nullptr, nullptr, nullptr, nullptr, dev);
+    return label_colors_impl(ctx, d_grid, A0, A1, A2, color, 1, channels, d_labels, &ncomp, cap, true, nullptr, nullptr, nullptr, nullptr, dev, connectivity);
 }

@@ -193,6 +193,78 @@ __global__ __launch_bounds__(1024) void k_recolor_select(const i64* __restrict__
     }
 }
 
+// extract_top_k_components' choice (reference utils/voxel_utils.py:27-30): components ranked by height = ptp of their a1 coordinates,
+// largest first, equal heights in label order (sorted() is stable), the first keep of them kept -- keep = min(k, n) for k >= 0 and
+// max(n + k, 0) for k < 0, which is what [:k] takes -- the others flagged.  One workgroup.  Heights are small integers (< A1), so a
+// histogram gives the threshold height and how many of the components AT it are kept; those are the first in label order (one
+// ordered count).  O(n + A1), no cap of its own below dcap.  status[0] = number of components, status[1] = 1 when the records do not
+// hold them all or A1 exceeds the histogram (nothing is flagged then: the caller's host path decides).
+constexpr int kTopkBins = 8192;
+__device__ __forceinline__ u32 block_excl_scan1024(u32 v, u32* part) {
+    const int tid = (int)threadIdx.x;
+    part[tid] = v;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {
+        const u32 t = tid >= off ? part[tid - off] : 0u;
+        __syncthreads();
+        part[tid] += t;
+        __syncthreads();
+    }
+    const u32 inc = part[tid];
+    __syncthreads();
+    return inc - v;
+}
+__device__ __forceinline__ int rec_height(const char* records, int i) {
+    const int* bb = (const int*)(records + (i64)i * 64);
+    return bb[4] - bb[1];
+}
+__global__ __launch_bounds__(1024) void k_topk_select(const i64* __restrict__ total, const char* __restrict__ records, int dcap, int A1, i64 k,
+                                                      u8* __restrict__ flags, i64* __restrict__ status) {
+    __shared__ u32 hist[kTopkBins];
+    __shared__ u32 part[1024];
+    __shared__ int s_thr;
+    __shared__ u32 s_take;
+    const int tid = (int)threadIdx.x;
+    const i64 n = total[0];
+    const bool over = n > dcap || A1 > kTopkBins;
+    if (tid == 0 && status) { status[0] = n; status[1] = over ? 1 : 0; }
+    const int m = over ? 0 : (int)n;
+    const i64 keep = k >= 0 ? (k < m ? k : m) : (m + k > 0 ? m + k : 0);
+    for (int b = tid; b < kTopkBins; b += 1024) hist[b] = 0u;
+    if (tid == 0) { s_thr = kTopkBins; s_take = 0u; }        // keep == 0: no height is kept
+    __syncthreads();
+    for (int i = tid; i < m; i += 1024) atomicAdd(&hist[rec_height(records, i)], 1u);
+    __syncthreads();
+    // thread tid owns the eight bins below kTopkBins - 8 tid: the scan counts the components above its bins
+    constexpr int kPer = kTopkBins / 1024;
+    const int btop = kTopkBins - kPer * tid - 1;
+    u32 mine = 0;
+#pragma unroll
+    for (int j = 0; j < kPer; ++j) mine += hist[btop - j];
+    u32 above = block_excl_scan1024(mine, part);
+#pragma unroll
+    for (int j = 0; j < kPer; ++j) {
+        const u32 h = hist[btop - j];
+        if ((i64)above < keep && (i64)above + h >= keep) { s_thr = btop - j; s_take = (u32)(keep - above); }     // (one bin matches)
+        above += h;
+    }
+    __syncthreads();
+    const int thr = s_thr;
+    const u32 take = s_take;
+    // the components AT the threshold height, in label order: a contiguous block of labels per thread
+    const int per = (m + 1023) / 1024, i0 = tid * per, i1 = i0 + per < m ? i0 + per : m;
+    u32 eq = 0;
+    for (int i = i0; i < i1; ++i) eq += rec_height(records, i) == thr;
+    u32 ord = block_excl_scan1024(eq, part);
+    for (int i = i0; i < i1; ++i) {
+        const int h = rec_height(records, i);
+        bool kept = h > thr;
+        if (h == thr) kept = ord++ < take;
+        flags[i] = kept ? 0 : 1;
+    }
+    for (int i = m + tid; i < dcap; i += 1024) flags[i] = 0;
+}
+
 // extrude_from_surface, axis 2 (reference :218-228): one wavefront per (x,y) column.  start = index of the
 // first occupied voxel from the chosen side (0 / D-1 for an empty column, like np.argmax), then `depth`
 // cells from there, inside the grid, are painted where valid[x,y].
@@ -575,6 +647,37 @@ int pb3d_recolor_backward_dev(pb3d_ctx* ctx, uint8_t* d_grid, int64_t A0, int64_
     const i64 nwords = cl.rows * cl.P;
     hipLaunchKernelGGL(k_recolor_bits, dim3(pb3d_stream_blocks(ctx, (nwords + 63) / 64, 4, 8)), dim3(256), 0, ctx->stream, (const u64*)cl.bits, d_labels,
                        (const u8*)f, nwords, pb3d_make_magic((u32)cl.P), (int)cl.A2, new_color[0], new_color[1], new_color[2], d_grid, channels, dev.dcap);
+    PB3D_CHECK_LAUNCH();
+    return PB3D_OK;
+}
+
+// extract_top_k_components (reference utils/voxel_utils.py:24-33) in place on a resident grid WITHOUT a host round trip: the members-only
+// labelling at `connectivity` with the statistics left on the device, the ranking by one workgroup (k_topk_select), the zeroing over the
+// membership bits -- everything queued on the context's stream.
+constexpr int kTopkDeviceMax = 16384;
+int pb3d_top_k_components_dev(pb3d_ctx* ctx, uint8_t* d_grid, int64_t A0, int64_t A1, int64_t A2, const uint8_t color[3], int channels, int64_t k,
+                              int connectivity, int32_t* d_labels, int64_t* d_status) {
+    PB3D_REQUIRE(ctx && color && A0 >= 0 && A1 >= 0 && A2 >= 0, "pb3d_top_k_components: bad argument");
+    PB3D_REQUIRE(channels == 1 || channels == 3, "pb3d_top_k_components: channels is 1 (labels) or 3 (colours)");
+    PB3D_REQUIRE(connectivity == 6 || connectivity == 18 || connectivity == 26, "pb3d_top_k_components: connectivity is 6, 18 or 26");
+    const i64 nvox = A0 * A1 * A2;
+    if (nvox == 0) {
+        if (d_status) PB3D_HIP(hipMemsetAsync(d_status, 0, 16, ctx->stream));
+        return PB3D_OK;
+    }
+    PB3D_REQUIRE(d_grid && d_labels, "pb3d_top_k_components: null buffer");
+    pb3d_ccl_dev dev;
+    PB3D_TRY(pb3d_ccl_label_on_device(ctx, d_grid, A0, A1, A2, color, channels, d_labels, kTopkDeviceMax, &dev, connectivity));
+    void* f;
+    PB3D_TRY(pb3d_scratch(ctx, 7, (size_t)dev.dcap, &f));
+    hipLaunchKernelGGL(k_topk_select, dim3(1), dim3(1024), 0, ctx->stream, dev.total, dev.records, dev.dcap, (int)(A1 < 0x7fffffff ? A1 : 0x7fffffff), (i64)k,
+                       (u8*)f, (i64*)d_status);
+    PB3D_CHECK_LAUNCH();
+    const pb3d_ctx::CclLast& cl = ctx->ccl_last;
+    PB3D_REQUIRE(cl.valid && cl.rows * cl.P < (1ll << 32), "pb3d_top_k_components: grid too large");
+    const i64 nwords = cl.rows * cl.P;
+    hipLaunchKernelGGL(k_recolor_bits, dim3(pb3d_stream_blocks(ctx, (nwords + 63) / 64, 4, 8)), dim3(256), 0, ctx->stream, (const u64*)cl.bits, d_labels,
+                       (const u8*)f, nwords, pb3d_make_magic((u32)cl.P), (int)cl.A2, (u8)0, (u8)0, (u8)0, d_grid, channels, dev.dcap);
     PB3D_CHECK_LAUNCH();
     return PB3D_OK;
 }

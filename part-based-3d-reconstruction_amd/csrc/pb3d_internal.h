@@ -174,7 +174,7 @@ __device__ __forceinline__ u32 pb3d_div(u32 n, const pb3d_magic g) {
 // record of component c + 1 {int lo[3], hi[3] (inclusive), pad[2]; u64 count, sum[3]}, valid for c < min(total[k], dcap)
 struct pb3d_ccl_dev { const i64* total; const char* records; int dcap; };
 int pb3d_ccl_label_on_device(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64_t A1, int64_t A2, const uint8_t color[3], int channels, int32_t* d_labels,
-                             int64_t cap, pb3d_ccl_dev* dev);
+                             int64_t cap, pb3d_ccl_dev* dev, int connectivity = 6);
 
 // ---- kernels' host launchers used across translation units ---------------------------------
 // process_voxel_grid through the bit-sliced chain (csrc/sliced.hip); *took = 0: not applicable, nothing written

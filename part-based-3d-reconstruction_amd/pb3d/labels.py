@@ -18,7 +18,7 @@ import numpy as np
 from . import _hostmem, _lib
 
 __all__ = ["Palette", "rgb_to_label", "label_to_rgb", "global_carve_labels", "part_carve_labels", "left_right_guided_carve_labels",
-           "extrude_from_surface_labels", "recolor_backward_components_labels", "partwise_carve_labels", "get_voxel_points_by_parts_labels",
+           "extrude_from_surface_labels", "recolor_backward_components_labels", "extract_top_k_components_labels", "partwise_carve_labels", "get_voxel_points_by_parts_labels",
            "voxel_grid_to_points_labels"]
 
 
@@ -242,6 +242,27 @@ def recolor_backward_components_labels(label_grid, label, new_label, k=4, sort_a
     d_g = dev.from_numpy(g)
     try:
         _recolor_dev(d_g, g.shape, int(label), int(new_label), k, sort_axis, label=True)
+        return d_g.download(g.shape)
+    finally:
+        d_g.free()
+
+
+def extract_top_k_components_labels(label_grid, label, k=4):
+    """extract_top_k_components (reference utils/voxel_utils.py:24-33) on a label volume: the k tallest 26-connected components of
+    `label` are kept, the other voxels of that label become 0 (returns a C-contiguous copy)."""
+    from . import device as dev
+    from .voxel_utils import _top_k_dev
+    g = _lib.as_u8(label_grid, "label_grid")
+    if g.ndim != 3:
+        raise ValueError("label_grid must be 3-D")
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)):
+        raise TypeError("k must be an integer")
+    lv = np.asarray(label).reshape(-1)
+    if g.size == 0 or lv.size != 1 or not (0 <= lv[0] <= 255) or lv[0] != np.round(lv[0]):
+        return np.ascontiguousarray(g).copy()
+    d_g = dev.from_numpy(g)
+    try:
+        _top_k_dev(d_g, g.shape, int(lv[0]), k, 1)
         return d_g.download(g.shape)
     finally:
         d_g.free()

@@ -37,7 +37,7 @@ def timeit(fn, reps, warm=2):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=1024)
-    ap.add_argument("--ops", default="M1,M2,M3,M4,M5,M6,M7,M8,A2,A6,A9,N2")
+    ap.add_argument("--ops", default="M1,M2,M3,M4,M5,M6,M7,M8,A2,A6,A9,N2,TK")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--tune", default="", help="development knobs, e.g. rot90_fill=6 (pb3d_set_tuning)")
     a = ap.parse_args()
@@ -97,7 +97,7 @@ def main():
             report("M4", f"one rotate+carve step, {ang} deg", timeit(lambda: dev.rotate_carve(d_occ, S, S, S, M, off, d_mwh, d_o1), a.reps), 2)
     d_occ.free(); d_o1.free(); d_tmp.free()
     d_col = None
-    if any(o in ops for o in ("M5", "M6", "M7", "M8", "A9", "N2")):
+    if any(o in ops for o in ("M5", "M6", "M7", "M8", "A9", "N2", "TK")):
         d_col = dev.DeviceBuffer(nvox * 3)
         ms = timeit(lambda: dev.global_carve(d_bhw, d_rgb, S, S, 90, d_col), a.reps)
         if "M5" in ops:
@@ -180,6 +180,28 @@ def main():
         print(json.dumps({"op": "N2", "name": "recolor_backward_components: recolour pass over the labelling's membership bits (k_recolor_bits)", "size": S, "ms": round(ms, 4),
                           "alg_B_per_voxel": 0.125, "note": "1 bit/voxel read + 4 B label and 3 B colour per member voxel"}), flush=True)
         for b in (d_o, d_v, d_lab):
+            b.free()
+    if "TK" in ops:
+        # extract_top_k_components (reference utils/voxel_utils.py:24-33) on the carved colour grid: the 26-connected labelling of one
+        # colour, members only (3 B/voxel read; labels written at the member voxels, not priced), against the 6-connected one; then the
+        # whole in-place op (labelling + ranking + zeroing over the membership bits: 3 B/voxel + the members' bytes, not priced)
+        from pb3d.voxel_utils import _label_stats_conn
+        col = np.array(pb3d.PART_COLORS["full_building"], np.uint8)
+        d_lab = dev.DeviceBuffer(nvox * 4)
+        out = {}
+        for conn in (6, 26):
+            def lab_conn():
+                out["n"] = _label_stats_conn(d_col, (S, S, S), [col], d_lab, conn, members_only=True)[0][0]
+            report("TK", f"connected components of one colour, {conn}-connected, members only (+ statistics)", timeit(lab_conn, a.reps, warm=1), 3,
+                   {"components": out["n"], "connectivity": conn})
+        d_g = dev.DeviceBuffer(nvox * 3); d_st = dev.DeviceBuffer(16)
+        L.check(lib.pb3d_d2d(L.ctx(), C.c_void_p(d_g.ptr), C.c_void_p(d_col.ptr), nvox * 3))
+        # in place on a copy: the first call zeroes what k = 4 drops, the later ones find the same components minus those (same work)
+        tk = lambda: L.check(lib.pb3d_top_k_components_dev(L.ctx(), C.c_void_p(d_g.ptr), S, S, S, L.p_u8(col), 3, 4, 26, C.c_void_p(d_lab.ptr), C.c_void_p(d_st.ptr)))
+        ms = timeit(tk, a.reps, warm=1)
+        report("TK", "extract_top_k_components(k=4), in place on the device (pb3d_top_k_components_dev)", ms, 3,
+               {"components": int(d_st.download((2,), np.int64)[0])})
+        for b in (d_lab, d_g, d_st):
             b.free()
     if "M7" in ops or "M8" in ops:
         cols = np.ascontiguousarray(np.array(list(pb3d.PART_COLORS.values()), np.uint8))
