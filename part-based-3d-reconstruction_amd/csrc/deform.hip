@@ -319,19 +319,11 @@ int pb3d_deform_iou_batch_dev(pb3d_ctx* ctx, const float* d_pts, int64_t n, cons
         unsigned long long* d_counts = (unsigned long long*)cnt;
         unsigned long long* d_nvalid = d_counts + 2 * kn;
         if (n > 0) {
-            i64 per = (7 * n + 255) / 256;
-            const i64 want = ((i64)ctx->cus * 16 + kn - 1) / kn;
-            if (per > want) per = want;
-            if (per < 1) per = 1;
-            hipLaunchKernelGGL(k_deform_project_batch, dim3((unsigned)per, (unsigned)kn), dim3(256), 0, ctx->stream, d_pts, n, (const DeformTuple*)dt, C,
+            hipLaunchKernelGGL(k_deform_project_batch, dim3(pb3d_batch_blocks(ctx, 7 * n, 256, kn, 16), (unsigned)kn), dim3(256), 0, ctx->stream, d_pts, n, (const DeformTuple*)dt, C,
                                P, A0, A1, A2, npix, (u8*)marks, d_nvalid);
             hipok(hipGetLastError(), "k_deform_project_batch");
         }
-        i64 ib = (npix + 255) / 256;
-        const i64 iwant = ((i64)ctx->cus * 8 + kn - 1) / kn;
-        if (ib > iwant) ib = iwant;
-        if (ib < 1) ib = 1;
-        hipLaunchKernelGGL(k_deform_iou_batch, dim3((unsigned)ib, (unsigned)kn), dim3(256), 0, ctx->stream, (const u8*)marks, d_seg, npix, color[0],
+        hipLaunchKernelGGL(k_deform_iou_batch, dim3(pb3d_batch_blocks(ctx, npix, 256, kn, 8), (unsigned)kn), dim3(256), 0, ctx->stream, (const u8*)marks, d_seg, npix, color[0],
                            color[1], color[2], d_counts);
         hipok(hipGetLastError(), "k_deform_iou_batch");
         hipok(hipMemcpyAsync(hc, cnt, (size_t)kn * 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync");

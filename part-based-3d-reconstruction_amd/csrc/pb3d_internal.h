@@ -151,6 +151,15 @@ static inline unsigned pb3d_stream_blocks(const pb3d_ctx* ctx, i64 work_items, i
     return (unsigned)(need < cap ? need : cap);
 }
 
+// blocks per batch item of a (blocks, batch) grid: enough for one item's work, and no more than blocks_per_cu per CU for the
+// whole batch together (at least one)
+static inline unsigned pb3d_batch_blocks(const pb3d_ctx* ctx, i64 work_items, int per_block, i64 batch, int blocks_per_cu) {
+    i64 need = (work_items + per_block - 1) / per_block;
+    const i64 cap = ((i64)ctx->cus * blocks_per_cu + batch - 1) / batch;
+    if (need > cap) need = cap;
+    return (unsigned)(need < 1 ? 1 : need);
+}
+
 // ---- exact u32 division by a run-time constant (Granlund-Montgomery round-up form): q = (t + ((n - t) >> sa)) >> sb, t = mulhi(m, n).
 // A 64-bit integer division is ~100 vector instructions on gfx950 and the VALU issues one wave instruction per four cycles: kernels
 // that turn a linear voxel index into coordinates with / and % are bound by exactly that.

@@ -16,21 +16,6 @@ namespace {
 
 using namespace pb3d_proj;
 
-// Points are visited from the LAST index down: the winner of a pixel is its largest point index, so once the
-// high indices have claimed their pixels the remaining points mostly lose on a plain read and skip the atomic.
-__global__ __launch_bounds__(256) void k_project_points(const void* __restrict__ pts, i64 n, ProjParams P,
-                                                        u32* __restrict__ winner) {
-    for (i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (i64)gridDim.x * blockDim.x) {
-        const i64 i = n - 1 - t;
-        int ui, vi;
-        if (project_point<0>(P, pts, i, &ui, &vi)) {
-            u32* w = &winner[(i64)vi * P.Wimg + ui];
-            const u32 mine = (u32)(i + 1);
-            if (__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < mine) atomicMax(w, mine);
-        }
-    }
-}
-
 __global__ __launch_bounds__(256) void k_project_resolve(const u32* __restrict__ winner, const u8* __restrict__ cols,
                                                          u8* __restrict__ img, i64 npix) {
     for (i64 px = (i64)blockIdx.x * blockDim.x + threadIdx.x; px < npix; px += (i64)gridDim.x * blockDim.x) {
@@ -44,55 +29,128 @@ __global__ __launch_bounds__(256) void k_project_resolve(const u32* __restrict__
     }
 }
 
-// z-buffer: nearest depth per pixel.  Depths are positive, so float32 order == order of their bit patterns and
-// the sequential "if z < zbuf: zbuf = z" loop of the reference equals an atomicMin on the float32 bits of z
-// (for float64 cameras the stored value is float32(z); float32 rounding is monotone, so min and rounding commute).
-__global__ __launch_bounds__(256) void k_depth_points(const void* __restrict__ pts, i64 n, ProjParams P, u32* __restrict__ zbits) {
-    for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (i64)gridDim.x * blockDim.x) {
-        int ui, vi; double z;
-        if (project_point<1>(P, pts, i, &ui, &vi, &z)) atomicMin(&zbits[(i64)vi * P.Wimg + ui], __float_as_uint((float)z));
-    }
-}
-
-__global__ __launch_bounds__(256) void k_visible_points(const void* __restrict__ pts, i64 n, ProjParams P, const float* __restrict__ zbuf,
-                                                        double eps, int eps_f32, u8* __restrict__ mask) {
-    for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (i64)gridDim.x * blockDim.x) {
-        int ui, vi; double z;
-        if (!project_point<1>(P, pts, i, &ui, &vi, &z)) continue;
-        const i64 px = (i64)vi * P.Wimg + ui;
-        const float zb = zbuf[px];
-        bool hit;
-        if (P.t0) hit = fabs(__dsub_rn(z, (double)zb)) < eps;                       // float64 z - float32 zbuf -> float64
-        else {
-            const float dz = fabsf(__fsub_rn((float)z, zb));                         // float32 z - float32 zbuf
-            hit = eps_f32 ? dz < (float)eps : (double)dz < eps;                     // weak Python float -> float32 compare
-        }
-        if (hit) mask[px] = 1;
-    }
-}
-
-// Sharded form of the scatter (SURVEY.md 8(e), points partition): every rank projects its contiguous range of the
-// point list into a private image of 64-bit keys ((global index + 1) << 24 | b << 16 | g << 8 | r); the last-writer-wins
-// rule is a max over the key, so ONE all-reduce(max) over the ranks followed by a local resolve gives every rank the
-// image the unsharded call produces, with no colour look-up across ranks.
-__global__ __launch_bounds__(256) void k_project_keys(const void* __restrict__ pts, const u8* __restrict__ cols, i64 n, i64 index_base,
-                                                      ProjParams P, unsigned long long* __restrict__ keys) {
-    for (i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (i64)gridDim.x * blockDim.x) {
-        const i64 i = n - 1 - t;
-        int ui, vi;
-        if (project_point<0>(P, pts, i, &ui, &vi)) {
-            unsigned long long* w = &keys[(i64)vi * P.Wimg + ui];
-            const unsigned long long mine = ((unsigned long long)(index_base + i + 1) << 24) | ((unsigned long long)cols[3 * i + 2] << 16) |
-                                            ((unsigned long long)cols[3 * i + 1] << 8) | (unsigned long long)cols[3 * i];
-            if (__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < mine) atomicMax(w, mine);
-        }
-    }
-}
-
 __global__ __launch_bounds__(256) void k_resolve_keys(const unsigned long long* __restrict__ keys, u8* __restrict__ img, i64 npix) {
     for (i64 px = (i64)blockIdx.x * blockDim.x + threadIdx.x; px < npix; px += (i64)gridDim.x * blockDim.x) {
         const unsigned long long k = keys[px];
         img[3 * px] = (u8)(k & 0xff); img[3 * px + 1] = (u8)((k >> 8) & 0xff); img[3 * px + 2] = (u8)((k >> 16) & 0xff);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Sinks: what a projected point does to its pixel, one per operation, shared by the generic kernel (one point at a time,
+// i64 pixel index) and the float32 kernel (groups of four, u32 pixel index).
+//   peek(ok, px)               the plain load of the pixel's current value; for a point that missed the image (!ok) a
+//                              value that makes commit do nothing
+//   commit(ok, cur, i, px, z)  the conditional atomic or store of point i (depth z) given what peek saw
+// MODE is the projection rule (project_xyz / project_f32); REVERSE visits the point list last-first.
+// ------------------------------------------------------------------------------------------------
+
+// Last writer wins: an atomicMax of (i + 1) per pixel.  Points are visited from the LAST index down: the winner of a pixel
+// is its largest point index, so once the high indices have claimed their pixels the remaining points mostly lose on the
+// plain read and skip the atomic.
+struct WinnerSink {
+    static constexpr int MODE = 0;
+    static constexpr bool REVERSE = true;
+    u32* __restrict__ winner;
+    __device__ __forceinline__ void shift(i64 off) { winner += off; }
+    template <class I>
+    __device__ __forceinline__ u32 peek(bool ok, I px) const {
+        return ok ? __hip_atomic_load(&winner[px], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0xffffffffu;
+    }
+    template <class I, class Z>
+    __device__ __forceinline__ void commit(bool, u32 cur, i64 i, I px, Z) const {
+        if (cur < (u32)(i + 1)) atomicMax(&winner[px], (u32)(i + 1));
+    }
+};
+
+// Sharded form of the scatter (SURVEY.md 8(e), points partition): every rank projects its contiguous range of the
+// point list into a private image of 64-bit keys ((global index + 1) << 24 | b << 16 | g << 8 | r); the last-writer-wins
+// rule is a max over the key, so ONE all-reduce(max) over the ranks followed by a local resolve gives every rank the
+// image the unsharded call produces, with no colour look-up across ranks.  Indices are distinct, so the index part decides.
+struct KeySink {
+    static constexpr int MODE = 0;
+    static constexpr bool REVERSE = true;
+    const u8* __restrict__ cols;
+    i64 index_base;
+    unsigned long long* __restrict__ keys;
+    template <class I>
+    __device__ __forceinline__ unsigned long long peek(bool ok, I px) const {
+        return ok ? __hip_atomic_load(&keys[px], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ~0ull;
+    }
+    template <class I, class Z>
+    __device__ __forceinline__ void commit(bool, unsigned long long cur, i64 i, I px, Z) const {
+        const unsigned long long mine = (unsigned long long)(index_base + i + 1) << 24;      // the colour bits are read only to store
+        if (cur < mine)
+            atomicMax(&keys[px], mine | ((unsigned long long)cols[3 * i + 2] << 16) | ((unsigned long long)cols[3 * i + 1] << 8) | (unsigned long long)cols[3 * i]);
+    }
+};
+
+// z-buffer: nearest depth per pixel.  Depths are positive, so float32 order == order of their bit patterns and
+// the sequential "if z < zbuf: zbuf = z" loop of the reference equals an atomicMin on the float32 bits of z
+// (for float64 cameras the stored value is float32(z); float32 rounding is monotone, so min and rounding commute).
+struct DepthSink {
+    static constexpr int MODE = 1;
+    static constexpr bool REVERSE = false;
+    u32* __restrict__ zbits;
+    template <class I>
+    __device__ __forceinline__ u32 peek(bool ok, I px) const {
+        return ok ? __hip_atomic_load(&zbits[px], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+    }
+    template <class I, class Z>
+    __device__ __forceinline__ void commit(bool, u32 cur, i64, I px, Z z) const {
+        if (cur > __float_as_uint((float)z)) atomicMin(&zbits[px], __float_as_uint((float)z));
+    }
+};
+
+// visible where |z - zbuf| < eps.  A float64 camera (t0; only the generic kernel, whose z is a double, sees one) subtracts
+// in float64; otherwise z - zbuf is a float32 difference, compared in float32 when eps is a weak Python float (eps_f32).
+struct VisibleSink {
+    static constexpr int MODE = 1;
+    static constexpr bool REVERSE = false;
+    const float* __restrict__ zbuf;
+    double eps;
+    int eps_f32, t0;
+    u8* __restrict__ mask;
+    template <class I>
+    __device__ __forceinline__ float peek(bool ok, I px) const { return ok ? zbuf[px] : 0.0f; }
+    template <class I, class Z>
+    __device__ __forceinline__ void commit(bool ok, float zb, i64, I px, Z z) const {
+        if (sizeof(Z) == sizeof(double) && t0) {
+            if (ok && fabs(__dsub_rn((double)z, (double)zb)) < eps) mask[px] = 1;                  // float64 z - float32 zbuf -> float64
+        } else {
+            const float dz = fabsf(__fsub_rn((float)z, zb));                                        // float32 z - float32 zbuf
+            if (ok && (eps_f32 ? dz < (float)eps : (double)dz < eps)) mask[px] = 1;                // weak Python float -> float32 compare
+        }
+    }
+};
+
+// The camera of a launch: ONE camera travels by value in the kernel arguments; a batch of K cameras (grid y = K) reads
+// cams[blockIdx.y] and moves the sink to that camera's image, blockIdx.y * npix further on.
+template <class T>
+struct CamBatch {
+    const T* cams;
+    i64 npix;
+};
+template <class T, class Sink>
+__device__ __forceinline__ T camera(const T& P, Sink&) { return P; }
+template <class T, class Sink>
+__device__ __forceinline__ T camera(const CamBatch<T>& B, Sink& sink) {
+    sink.shift((i64)blockIdx.y * B.npix);
+    return B.cams[blockIdx.y];
+}
+
+// generic path: any precision combination, one point per thread
+template <class Cam, class Sink>
+__global__ __launch_bounds__(256) void k_project(const void* __restrict__ pts, i64 n, Cam cam, Sink sink) {
+    const ProjParams P = camera(cam, sink);
+    for (i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (i64)gridDim.x * blockDim.x) {
+        const i64 i = Sink::REVERSE ? n - 1 - t : t;
+        int ui, vi;
+        double z = 0.0;
+        if (project_point<Sink::MODE>(P, pts, i, &ui, &vi, &z)) {
+            const i64 px = (i64)vi * P.Wimg + ui;
+            sink.commit(true, sink.peek(true, px), i, px, z);
+        }
     }
 }
 
@@ -132,31 +190,41 @@ __device__ __forceinline__ bool project_f32(const ProjF32& P, float x, float y, 
     return true;
 }
 
-// sink(i0, ok[4], px[4], z[4]) once per group of four points (i0 = index of the group's first point; ok = lands in the
-// image; px = pixel index): the four projections are finished before the sink runs, so its four dependent image
-// reads / atomics are issued back to back instead of one L2 round trip after another.  REVERSE visits the list last-first.
-template <int MODE, class Sink>
-__device__ __forceinline__ void group_f32(const ProjF32& P, const float q[12], int live, i64 i0, Sink& sink) {
+// One group of four points (i0 = index of the group's first point): the four projections are finished and all four
+// pixels peeked before the first commit, so the four dependent image reads / atomics are issued back to back instead of
+// one L2 round trip after another.  Commits go in visiting order (k = 3..0 in a reverse sweep).
+template <class Sink>
+__device__ __forceinline__ void group_f32(const ProjF32& P, const float q[12], int live, i64 i0, const Sink& sink) {
     bool ok[4]; u32 px[4]; float z[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         int ui = 0, vi = 0;
         z[k] = 0.0f;
-        ok[k] = k < live && project_f32<MODE>(P, q[3 * k], q[3 * k + 1], q[3 * k + 2], &ui, &vi, &z[k]);
+        ok[k] = k < live && project_f32<Sink::MODE>(P, q[3 * k], q[3 * k + 1], q[3 * k + 2], &ui, &vi, &z[k]);
         px[k] = (u32)vi * (u32)P.Wimg + (u32)ui;
     }
-    sink(i0, ok, px, z);
+    decltype(sink.peek(true, px[0])) cur[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) cur[k] = sink.peek(ok[k], px[k]);
+    if (Sink::REVERSE) {
+#pragma unroll
+        for (int k = 3; k >= 0; --k) sink.commit(ok[k], cur[k], i0 + k, px[k], z[k]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) sink.commit(ok[k], cur[k], i0 + k, px[k], z[k]);
+    }
 }
 
-template <int MODE, bool REVERSE, class Sink>
-__device__ __forceinline__ void sweep_f32(const float* __restrict__ pts, i64 n, const ProjF32& P, bool vec, Sink sink) {
+template <class Sink>
+__device__ __forceinline__ void sweep_f32(const float* __restrict__ pts, i64 n, const ProjF32& P, bool vec, const Sink& sink) {
+    constexpr bool REVERSE = Sink::REVERSE;
     const i64 nfull = n >> 2;                      // groups of four whole points
     const i64 gtid = (i64)blockIdx.x * blockDim.x + threadIdx.x, gsz = (i64)gridDim.x * blockDim.x;
     float q[12];
     if (REVERSE && gtid == 0 && (n & 3)) {        // the ragged tail holds the highest indices: first in a reverse sweep
 #pragma unroll
         for (int k = 0; k < 12; ++k) q[k] = k < 3 * (int)(n & 3) ? pts[12 * nfull + k] : 0.0f;
-        group_f32<MODE>(P, q, (int)(n & 3), 4 * nfull, sink);
+        group_f32(P, q, (int)(n & 3), 4 * nfull, sink);
     }
     if (vec) {
         // the next group's three vectors are requested before this group is projected (software prefetch)
@@ -173,75 +241,27 @@ __device__ __forceinline__ void sweep_f32(const float* __restrict__ pts, i64 n, 
 #pragma unroll
             for (int k = 0; k < 3; ++k) { q[4 * k] = nx[k].x; q[4 * k + 1] = nx[k].y; q[4 * k + 2] = nx[k].z; q[4 * k + 3] = nx[k].w; }
             if (t + gsz < nfull) fetch(t + gsz);
-            group_f32<MODE>(P, q, 4, 4 * c, sink);
+            group_f32(P, q, 4, 4 * c, sink);
         }
     } else {
         for (i64 t = gtid; t < nfull; t += gsz) {
             const i64 c = REVERSE ? nfull - 1 - t : t;
 #pragma unroll
             for (int k = 0; k < 12; ++k) q[k] = pts[12 * c + k];
-            group_f32<MODE>(P, q, 4, 4 * c, sink);
+            group_f32(P, q, 4, 4 * c, sink);
         }
     }
     if (!REVERSE && gtid == 0 && (n & 3)) {
 #pragma unroll
         for (int k = 0; k < 12; ++k) q[k] = k < 3 * (int)(n & 3) ? pts[12 * nfull + k] : 0.0f;
-        group_f32<MODE>(P, q, (int)(n & 3), 4 * nfull, sink);
+        group_f32(P, q, (int)(n & 3), 4 * nfull, sink);
     }
 }
 
-__global__ __launch_bounds__(256) void k_project_points_f32(const float* __restrict__ pts, i64 n, ProjF32 P, int vec, u32* __restrict__ winner) {
-    sweep_f32<0, true>(pts, n, P, vec != 0, [&](i64 i0, const bool* ok, const u32* px, const float*) {
-        u32 cur[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) cur[k] = ok[k] ? __hip_atomic_load(&winner[px[k]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0xffffffffu;
-#pragma unroll
-        for (int k = 3; k >= 0; --k)
-            if (cur[k] < (u32)(i0 + k + 1)) atomicMax(&winner[px[k]], (u32)(i0 + k + 1));
-    });
-}
-
-__global__ __launch_bounds__(256) void k_project_keys_f32(const float* __restrict__ pts, const u8* __restrict__ cols, i64 n, i64 index_base,
-                                                          ProjF32 P, int vec, unsigned long long* __restrict__ keys) {
-    sweep_f32<0, true>(pts, n, P, vec != 0, [&](i64 i0, const bool* ok, const u32* px, const float*) {
-        unsigned long long cur[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) cur[k] = ok[k] ? __hip_atomic_load(&keys[px[k]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ~0ull;
-#pragma unroll
-        for (int k = 3; k >= 0; --k) {
-            const i64 i = i0 + k;
-            if ((cur[k] >> 24) < (unsigned long long)(index_base + i + 1)) {
-                const unsigned long long mine = ((unsigned long long)(index_base + i + 1) << 24) | ((unsigned long long)cols[3 * i + 2] << 16) |
-                                                ((unsigned long long)cols[3 * i + 1] << 8) | (unsigned long long)cols[3 * i];
-                atomicMax(&keys[px[k]], mine);
-            }
-        }
-    });
-}
-
-__global__ __launch_bounds__(256) void k_depth_points_f32(const float* __restrict__ pts, i64 n, ProjF32 P, int vec, u32* __restrict__ zbits) {
-    sweep_f32<1, false>(pts, n, P, vec != 0, [&](i64, const bool* ok, const u32* px, const float* z) {
-        u32 cur[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) cur[k] = ok[k] ? __hip_atomic_load(&zbits[px[k]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (cur[k] > __float_as_uint(z[k])) atomicMin(&zbits[px[k]], __float_as_uint(z[k]));
-    });
-}
-
-__global__ __launch_bounds__(256) void k_visible_points_f32(const float* __restrict__ pts, i64 n, ProjF32 P, int vec, const float* __restrict__ zbuf,
-                                                            double eps, int eps_f32, u8* __restrict__ mask) {
-    sweep_f32<1, false>(pts, n, P, vec != 0, [&](i64, const bool* ok, const u32* px, const float* z) {
-        float zb[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) zb[k] = ok[k] ? zbuf[px[k]] : 0.0f;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float dz = fabsf(__fsub_rn(z[k], zb[k]));
-            if (ok[k] && (eps_f32 ? dz < (float)eps : (double)dz < eps)) mask[px[k]] = 1;
-        }
-    });
+template <class Cam, class Sink>
+__global__ __launch_bounds__(256) void k_project_f32(const float* __restrict__ pts, i64 n, Cam cam, int vec, Sink sink) {
+    const ProjF32 P = camera(cam, sink);
+    sweep_f32(pts, n, P, vec != 0, sink);
 }
 
 // the fast path applies when nothing in the call is float64
@@ -256,13 +276,26 @@ bool f32_path(const ProjParams& P, ProjF32* F) {
 inline int vec_ok(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 inline unsigned f32_blocks(pb3d_ctx* ctx, i64 n) { return pb3d_stream_blocks(ctx, n / 4 + 1, 256, 0); }      // one workgroup per 1024 points
 
-struct IouParams {
-    int ncolors;
-    u8 colors[3 * 32];
-};
+// scatter the n points of one camera into the sink's image: the float32 kernel when f32_path accepts P, else the generic one
+template <class Sink>
+int project_scatter(pb3d_ctx* ctx, const void* d_pts, i64 n, const ProjParams& P, const Sink& sink) {
+    if (n == 0) return PB3D_OK;
+    ProjF32 F;
+    if (f32_path(P, &F))
+        hipLaunchKernelGGL((k_project_f32<ProjF32, Sink>), dim3(f32_blocks(ctx, n)), dim3(256), 0, ctx->stream, (const float*)d_pts, n, F,
+                           vec_ok(d_pts), sink);
+    else
+        hipLaunchKernelGGL((k_project<ProjParams, Sink>), dim3(pb3d_stream_blocks(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, d_pts, n, P, sink);
+    PB3D_CHECK_LAUNCH();
+    return PB3D_OK;
+}
 
-__global__ __launch_bounds__(256) void k_partwise_iou(const u8* __restrict__ a, const u8* __restrict__ b, i64 npix,
-                                                      IouParams P, unsigned long long* __restrict__ counts) {
+// Per-colour intersection / union pixel counts of image a against the RGB image b: colour_a(px, c) writes pixel px's
+// colour in a to c[0..2].  One ballot per colour and wave; lane 0 adds the popcounts to the block's LDS tally (acc[2k] =
+// intersection, acc[2k + 1] = union) and the block adds its tally to counts[0 .. 2 * ncolors) once.
+template <class ColourA>
+__device__ __forceinline__ void iou_counts(ColourA colour_a, const u8* __restrict__ b, i64 npix, int ncolors, const u8* colors,
+                                           unsigned long long* __restrict__ counts) {
     __shared__ u32 acc[64];
     if (threadIdx.x < 64) acc[threadIdx.x] = 0;
     __syncthreads();
@@ -272,14 +305,14 @@ __global__ __launch_bounds__(256) void k_partwise_iou(const u8* __restrict__ a, 
     for (i64 it = 0; it < nloop; ++it) {
         const i64 px = it * stride + (i64)blockIdx.x * blockDim.x + threadIdx.x;
         const bool live = px < npix;
-        u8 a0 = 0, a1 = 0, a2 = 0, b0 = 0, b1 = 0, b2 = 0;
+        u8 a[3] = {0, 0, 0}, b0 = 0, b1 = 0, b2 = 0;
         if (live) {
-            a0 = a[3 * px]; a1 = a[3 * px + 1]; a2 = a[3 * px + 2];
+            colour_a(px, a);
             b0 = b[3 * px]; b1 = b[3 * px + 1]; b2 = b[3 * px + 2];
         }
-        for (int k = 0; k < P.ncolors; ++k) {
-            const u8 c0 = P.colors[3 * k], c1 = P.colors[3 * k + 1], c2 = P.colors[3 * k + 2];
-            const bool ma = live && a0 == c0 && a1 == c1 && a2 == c2;
+        for (int k = 0; k < ncolors; ++k) {
+            const u8 c0 = colors[3 * k], c1 = colors[3 * k + 1], c2 = colors[3 * k + 2];
+            const bool ma = live && a[0] == c0 && a[1] == c1 && a[2] == c2;
             const bool mb = live && b0 == c0 && b1 == c1 && b2 == c2;
             const u32 ni = (u32)__popcll(__ballot(ma && mb)), nu = (u32)__popcll(__ballot(ma || mb));
             if (lane == 0) {
@@ -289,7 +322,17 @@ __global__ __launch_bounds__(256) void k_partwise_iou(const u8* __restrict__ a, 
         }
     }
     __syncthreads();
-    if ((int)threadIdx.x < 2 * P.ncolors && acc[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (unsigned long long)acc[threadIdx.x]);
+    if ((int)threadIdx.x < 2 * ncolors && acc[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (unsigned long long)acc[threadIdx.x]);
+}
+
+struct IouParams {
+    int ncolors;
+    u8 colors[3 * 32];
+};
+
+__global__ __launch_bounds__(256) void k_partwise_iou(const u8* __restrict__ a, const u8* __restrict__ b, i64 npix,
+                                                      IouParams P, unsigned long long* __restrict__ counts) {
+    iou_counts([&](i64 px, u8 c[3]) { c[0] = a[3 * px]; c[1] = a[3 * px + 1]; c[2] = a[3 * px + 2]; }, b, npix, P.ncolors, P.colors, counts);
 }
 
 
@@ -300,68 +343,16 @@ __global__ __launch_bounds__(256) void k_partwise_iou(const u8* __restrict__ a, 
 // camera), a second one resolves every camera's winners to colours on the fly and counts intersections / unions against the
 // part image -- the K projected images are never written -- and ONE copy brings the K x P counters back.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_project_points_batch(const void* __restrict__ pts, i64 n, const ProjParams* __restrict__ cams,
-                                                              i64 npix, u32* __restrict__ winners) {
-    const ProjParams P = cams[blockIdx.y];
-    u32* winner = winners + (i64)blockIdx.y * npix;
-    for (i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (i64)gridDim.x * blockDim.x) {
-        const i64 i = n - 1 - t;
-        int ui, vi;
-        if (project_point<0>(P, pts, i, &ui, &vi)) {
-            u32* w = &winner[(i64)vi * P.Wimg + ui];
-            const u32 mine = (u32)(i + 1);
-            if (__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < mine) atomicMax(w, mine);
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void k_project_points_batch_f32(const float* __restrict__ pts, i64 n, const ProjF32* __restrict__ cams, int vec,
-                                                                  i64 npix, u32* __restrict__ winners) {
-    const ProjF32 P = cams[blockIdx.y];
-    u32* winner = winners + (i64)blockIdx.y * npix;
-    sweep_f32<0, true>(pts, n, P, vec != 0, [&](i64 i0, const bool* ok, const u32* px, const float*) {
-        u32 cur[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) cur[k] = ok[k] ? __hip_atomic_load(&winner[px[k]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0xffffffffu;
-#pragma unroll
-        for (int k = 3; k >= 0; --k)
-            if (cur[k] < (u32)(i0 + k + 1)) atomicMax(&winner[px[k]], (u32)(i0 + k + 1));
-    });
-}
-
 __global__ __launch_bounds__(256) void k_iou_winners_batch(const u32* __restrict__ winners, const u8* __restrict__ cols, const u8* __restrict__ seg,
                                                            i64 npix, int ncolors, const u8* __restrict__ colors, unsigned long long* __restrict__ counts) {
-    __shared__ u32 acc[64];
-    __shared__ u8 cl[96];
-    if (threadIdx.x < 64) acc[threadIdx.x] = 0;
+    __shared__ u8 cl[96];                          // written before iou_counts' first barrier
     if (threadIdx.x < 96) cl[threadIdx.x] = (int)threadIdx.x < 3 * ncolors ? colors[threadIdx.x] : (u8)0;
-    __syncthreads();
     const u32* winner = winners + (i64)blockIdx.y * npix;
-    const int lane = threadIdx.x & 63;
-    const i64 stride = (i64)gridDim.x * blockDim.x;
-    const i64 nloop = (npix + stride - 1) / stride;  // same trip count for every lane: ballots stay convergent
-    for (i64 it = 0; it < nloop; ++it) {
-        const i64 px = it * stride + (i64)blockIdx.x * blockDim.x + threadIdx.x;
-        const bool live = px < npix;
-        u8 a0 = 0, a1 = 0, a2 = 0, b0 = 0, b1 = 0, b2 = 0;
-        if (live) {
-            const u32 w = winner[px];
-            if (w) { const u8* c = cols + (i64)(w - 1) * 3; a0 = c[0]; a1 = c[1]; a2 = c[2]; }
-            b0 = seg[3 * px]; b1 = seg[3 * px + 1]; b2 = seg[3 * px + 2];
-        }
-        for (int k = 0; k < ncolors; ++k) {
-            const u8 c0 = cl[3 * k], c1 = cl[3 * k + 1], c2 = cl[3 * k + 2];
-            const bool ma = live && a0 == c0 && a1 == c1 && a2 == c2;
-            const bool mb = live && b0 == c0 && b1 == c1 && b2 == c2;
-            const u32 ni = (u32)__popcll(__ballot(ma && mb)), nu = (u32)__popcll(__ballot(ma || mb));
-            if (lane == 0) {
-                if (ni) atomicAdd(&acc[2 * k], ni);
-                if (nu) atomicAdd(&acc[2 * k + 1], nu);
-            }
-        }
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < 2 * ncolors && acc[threadIdx.x]) atomicAdd(&counts[(i64)blockIdx.y * 64 + threadIdx.x], (unsigned long long)acc[threadIdx.x]);
+    iou_counts([&](i64 px, u8 c[3]) {
+                   const u32 w = winner[px];
+                   if (w) { const u8* s = cols + (i64)(w - 1) * 3; c[0] = s[0]; c[1] = s[1]; c[2] = s[2]; }
+               },
+               seg, npix, ncolors, cl, counts + (i64)blockIdx.y * 64);
 }
 
 }  // namespace
@@ -377,26 +368,12 @@ int pb3d_project_dev(pb3d_ctx* ctx, const void* d_pts, int pts_f64, const uint8_
     const i64 npix = (i64)Himg * Wimg;
     if (npix == 0) return PB3D_OK;
     PB3D_REQUIRE(d_img && (n == 0 || (d_pts && d_cols)), "pb3d_project: null buffer");
-    for (int k = 0; k < 4; ++k) PB3D_REQUIRE(prec[k] == 0 || prec[k] == 1, "pb3d_project: prec[%d] must be 0 or 1", k);
-    PB3D_REQUIRE(prec[1] >= prec[0] && prec[2] >= prec[1] && prec[3] >= prec[1], "pb3d_project: precision may only widen");
+    ProjParams P;
+    PB3D_TRY(fill_proj(&P, pts_f64, R, cam, f, cx, cy, prec, Himg, Wimg));
     void* winner;
     PB3D_TRY(pb3d_scratch(ctx, 8, (size_t)npix * sizeof(u32), &winner));
     PB3D_HIP(hipMemsetAsync(winner, 0, (size_t)npix * sizeof(u32), ctx->stream));
-    ProjParams P;
-    memcpy(P.R, R, sizeof(P.R)); memcpy(P.cam, cam, sizeof(P.cam));
-    P.f = f; P.cx = cx; P.cy = cy;
-    P.t0 = prec[0]; P.tm = prec[1]; P.tu = prec[2]; P.tv = prec[3];
-    P.Himg = Himg; P.Wimg = Wimg; P.pts_f64 = pts_f64 ? 1 : 0;
-    ProjF32 F;
-    if (n > 0) {
-        if (f32_path(P, &F))
-            hipLaunchKernelGGL(k_project_points_f32, dim3(f32_blocks(ctx, n)), dim3(256), 0, ctx->stream, (const float*)d_pts, n, F,
-                               vec_ok(d_pts), (u32*)winner);
-        else
-            hipLaunchKernelGGL(k_project_points, dim3(pb3d_stream_blocks(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, d_pts, n, P,
-                               (u32*)winner);
-        PB3D_CHECK_LAUNCH();
-    }
+    PB3D_TRY(project_scatter(ctx, d_pts, n, P, WinnerSink{(u32*)winner}));
     hipLaunchKernelGGL(k_project_resolve, dim3(pb3d_stream_blocks(ctx, npix, 256, 8)), dim3(256), 0, ctx->stream,
                        (const u32*)winner, d_cols, d_img, npix);
     PB3D_CHECK_LAUNCH();
@@ -414,17 +391,7 @@ int pb3d_project_keys_dev(pb3d_ctx* ctx, const void* d_pts, int pts_f64, const u
     ProjParams P;
     PB3D_TRY(fill_proj(&P, pts_f64, R, cam, f, cx, cy, prec, Himg, Wimg));
     PB3D_HIP(hipMemsetAsync(d_keys, 0, (size_t)npix * sizeof(uint64_t), ctx->stream));
-    ProjF32 F;
-    if (n > 0) {
-        if (f32_path(P, &F))
-            hipLaunchKernelGGL(k_project_keys_f32, dim3(f32_blocks(ctx, n)), dim3(256), 0, ctx->stream, (const float*)d_pts, d_cols, n,
-                               index_base, F, vec_ok(d_pts), (unsigned long long*)d_keys);
-        else
-            hipLaunchKernelGGL(k_project_keys, dim3(pb3d_stream_blocks(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, d_pts, d_cols, n,
-                               index_base, P, (unsigned long long*)d_keys);
-        PB3D_CHECK_LAUNCH();
-    }
-    return PB3D_OK;
+    return project_scatter(ctx, d_pts, n, P, KeySink{d_cols, index_base, (unsigned long long*)d_keys});
 }
 
 int pb3d_project_resolve_keys_dev(pb3d_ctx* ctx, const uint64_t* d_keys, int Himg, int Wimg, uint8_t* d_img) {
@@ -447,16 +414,7 @@ int pb3d_depth_buffer_dev(pb3d_ctx* ctx, const void* d_pts, int pts_f64, int64_t
     ProjParams P;
     PB3D_TRY(fill_proj(&P, pts_f64, R, cam, f, cx, cy, prec, Himg, Wimg));
     PB3D_HIP(hipMemsetD32Async((hipDeviceptr_t)d_zbuf, 0x7f800000, (size_t)npix, ctx->stream));   // +inf
-    ProjF32 F;
-    if (n > 0) {
-        if (f32_path(P, &F))
-            hipLaunchKernelGGL(k_depth_points_f32, dim3(f32_blocks(ctx, n)), dim3(256), 0, ctx->stream, (const float*)d_pts, n, F,
-                               vec_ok(d_pts), (u32*)d_zbuf);
-        else
-            hipLaunchKernelGGL(k_depth_points, dim3(pb3d_stream_blocks(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, d_pts, n, P, (u32*)d_zbuf);
-        PB3D_CHECK_LAUNCH();
-    }
-    return PB3D_OK;
+    return project_scatter(ctx, d_pts, n, P, DepthSink{(u32*)d_zbuf});
 }
 
 int pb3d_visible_mask_dev(pb3d_ctx* ctx, const void* d_pts, int pts_f64, int64_t n, const double R[9], const double cam[3], double f,
@@ -469,17 +427,7 @@ int pb3d_visible_mask_dev(pb3d_ctx* ctx, const void* d_pts, int pts_f64, int64_t
     ProjParams P;
     PB3D_TRY(fill_proj(&P, pts_f64, R, cam, f, cx, cy, prec, Himg, Wimg));
     PB3D_HIP(hipMemsetAsync(d_mask, 0, (size_t)npix, ctx->stream));
-    ProjF32 F;
-    if (n > 0) {
-        if (f32_path(P, &F))
-            hipLaunchKernelGGL(k_visible_points_f32, dim3(f32_blocks(ctx, n)), dim3(256), 0, ctx->stream, (const float*)d_pts, n, F,
-                               vec_ok(d_pts), d_zbuf, eps, eps_f32, d_mask);
-        else
-            hipLaunchKernelGGL(k_visible_points, dim3(pb3d_stream_blocks(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, d_pts, n, P, d_zbuf, eps,
-                               eps_f32, d_mask);
-        PB3D_CHECK_LAUNCH();
-    }
-    return PB3D_OK;
+    return project_scatter(ctx, d_pts, n, P, VisibleSink{d_zbuf, eps, eps_f32, P.t0, d_mask});
 }
 
 int pb3d_partwise_iou_dev(pb3d_ctx* ctx, const uint8_t* d_a, const uint8_t* d_b, int64_t npix,
@@ -527,54 +475,40 @@ int pb3d_project_iou_batch_dev(pb3d_ctx* ctx, const void* d_pts, int pts_f64, co
     PB3D_TRY(pb3d_scratch(ctx, 22, 128, &dcolors));
     PB3D_HIP(hipMemcpyAsync(dcolors, colors, (size_t)3 * ncolors, hipMemcpyHostToDevice, ctx->stream));
     ProjParams* hp = (ProjParams*)malloc((size_t)kc * sizeof(ProjParams));
+    ProjF32* hf = (ProjF32*)malloc((size_t)kc * sizeof(ProjF32));
     unsigned long long* hc = (unsigned long long*)malloc((size_t)kc * 64 * sizeof(unsigned long long));
-    if (!hp || !hc) { free(hp); free(hc); pb3d_set_error("pb3d_project_iou_batch: out of host memory"); return PB3D_ENOMEM; }
+    if (!hp || !hf || !hc) { free(hp); free(hf); free(hc); pb3d_set_error("pb3d_project_iou_batch: out of host memory"); return PB3D_ENOMEM; }
     int rc = PB3D_OK;
     for (i64 k0 = 0; k0 < ncams && rc == PB3D_OK; k0 += kc) {
         const i64 kn = ncams - k0 < kc ? ncams - k0 : kc;
-        bool all_f32 = true;
-        ProjF32* hf = (ProjF32*)hp;                      // the float32 records are smaller: they share the staging area
+        bool all_f32 = true;                             // the float32 kernel runs a pass only when it takes every camera of it
         for (i64 k = 0; k < kn && rc == PB3D_OK; ++k) {
             const pb3d_camera* c = cams + k0 + k;
-            ProjParams P;
-            rc = fill_proj(&P, pts_f64, c->R, c->cam, c->f, c->cx, c->cy, c->prec, Himg, Wimg);
-            ProjF32 F;
-            if (rc == PB3D_OK && !f32_path(P, &F)) all_f32 = false;
+            rc = fill_proj(&hp[k], pts_f64, c->R, c->cam, c->f, c->cx, c->cy, c->prec, Himg, Wimg);
+            if (rc == PB3D_OK && !f32_path(hp[k], &hf[k])) all_f32 = false;
         }
         if (rc != PB3D_OK) break;
-        for (i64 k = 0; k < kn; ++k) {
-            const pb3d_camera* c = cams + k0 + k;
-            ProjParams P;
-            fill_proj(&P, pts_f64, c->R, c->cam, c->f, c->cx, c->cy, c->prec, Himg, Wimg);
-            if (all_f32) f32_path(P, &hf[k]); else hp[k] = P;
-        }
         auto hipok = [&](hipError_t e, const char* what) {
             if (e != hipSuccess && rc == PB3D_OK) { pb3d_set_error("%s failed: %s", what, hipGetErrorString(e)); rc = PB3D_ENODEVICE; }
         };
-        hipok(hipMemcpyAsync(dcams, hp, (size_t)kn * (all_f32 ? sizeof(ProjF32) : sizeof(ProjParams)), hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync");
+        hipok(hipMemcpyAsync(dcams, all_f32 ? (const void*)hf : (const void*)hp, (size_t)kn * (all_f32 ? sizeof(ProjF32) : sizeof(ProjParams)),
+                             hipMemcpyHostToDevice, ctx->stream), "hipMemcpyAsync");
         hipok(hipMemsetAsync(winners, 0, (size_t)(kn * npix) * sizeof(u32), ctx->stream), "hipMemsetAsync");
         hipok(hipMemsetAsync(counts, 0, (size_t)kn * 64 * sizeof(unsigned long long), ctx->stream), "hipMemsetAsync");
         if (rc != PB3D_OK) break;
         if (n > 0) {
             // enough blocks per camera to fill the chip between them, never more than the points need
-            i64 per_cam = all_f32 ? (n / 4 + 256) / 256 : (n + 255) / 256;
-            const i64 want = ((i64)ctx->cus * 16 + kn - 1) / kn;
-            if (per_cam > want) per_cam = want;
-            if (per_cam < 1) per_cam = 1;
             if (all_f32)
-                hipLaunchKernelGGL(k_project_points_batch_f32, dim3((unsigned)per_cam, (unsigned)kn), dim3(256), 0, ctx->stream, (const float*)d_pts, n,
-                                   (const ProjF32*)dcams, vec_ok(d_pts), npix, (u32*)winners);
+                hipLaunchKernelGGL((k_project_f32<CamBatch<ProjF32>, WinnerSink>), dim3(pb3d_batch_blocks(ctx, n / 4 + 1, 256, kn, 16), (unsigned)kn),
+                                   dim3(256), 0, ctx->stream, (const float*)d_pts, n, CamBatch<ProjF32>{(const ProjF32*)dcams, npix}, vec_ok(d_pts),
+                                   WinnerSink{(u32*)winners});
             else
-                hipLaunchKernelGGL(k_project_points_batch, dim3((unsigned)per_cam, (unsigned)kn), dim3(256), 0, ctx->stream, d_pts, n,
-                                   (const ProjParams*)dcams, npix, (u32*)winners);
-            hipok(hipGetLastError(), "k_project_points_batch");
+                hipLaunchKernelGGL((k_project<CamBatch<ProjParams>, WinnerSink>), dim3(pb3d_batch_blocks(ctx, n, 256, kn, 16), (unsigned)kn), dim3(256),
+                                   0, ctx->stream, d_pts, n, CamBatch<ProjParams>{(const ProjParams*)dcams, npix}, WinnerSink{(u32*)winners});
+            hipok(hipGetLastError(), "k_project batch");
         }
-        i64 ib = (npix + 255) / 256;
-        const i64 iwant = ((i64)ctx->cus * 8 + kn - 1) / kn;
-        if (ib > iwant) ib = iwant;
-        if (ib < 1) ib = 1;
-        hipLaunchKernelGGL(k_iou_winners_batch, dim3((unsigned)ib, (unsigned)kn), dim3(256), 0, ctx->stream, (const u32*)winners, d_cols, d_seg, npix,
-                           ncolors, (const u8*)dcolors, (unsigned long long*)counts);
+        hipLaunchKernelGGL(k_iou_winners_batch, dim3(pb3d_batch_blocks(ctx, npix, 256, kn, 8), (unsigned)kn), dim3(256), 0, ctx->stream,
+                           (const u32*)winners, d_cols, d_seg, npix, ncolors, (const u8*)dcolors, (unsigned long long*)counts);
         hipok(hipGetLastError(), "k_iou_winners_batch");
         hipok(hipMemcpyAsync(hc, counts, (size_t)kn * 64 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream), "hipMemcpyAsync");
         ++ctx->sync_count; hipok(hipStreamSynchronize(ctx->stream), "hipStreamSynchronize");
@@ -585,7 +519,7 @@ int pb3d_project_iou_batch_dev(pb3d_ctx* ctx, const void* d_pts, int pts_f64, co
                 uni[(k0 + k) * ncolors + c] = (int64_t)hc[k * 64 + 2 * c + 1];
             }
     }
-    free(hp); free(hc);
+    free(hp); free(hf); free(hc);
     return rc;
 }
 

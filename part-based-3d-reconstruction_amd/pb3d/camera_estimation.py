@@ -100,7 +100,7 @@ class CameraObjective:
         (the random / coordinate stages of the aligner evaluate dozens of cameras around the current one).  Exactly the values
         of the one-at-a-time path: the same point kernel per camera, the same integer counts, the same float64 mean."""
         from .camera_geometry import look_at_rotation_batch
-        from .projection_utils import _promotes_to_f64
+        from .projection_utils import _promotion_flags
         params = list(params)
         K = len(params)
         if K == 0:
@@ -124,8 +124,7 @@ class CameraObjective:
                 _, _, R, cam, prec = camera_args(np.zeros((1, 3), self._pts_dtype), p["cam_pos"], p["target"], p["f"], p["cx"], p["cy"])
                 cams["R"][k] = R.reshape(9); cams["cam"][k] = cam; t0s.append(int(prec[0]))
         for k, p in enumerate(params):
-            tm = int(t0s[k] or _promotes_to_f64(p["f"]))
-            cams["prec"][k] = (t0s[k], tm, int(tm or _promotes_to_f64(p["cx"])), int(tm or _promotes_to_f64(p["cy"])))
+            cams["prec"][k] = _promotion_flags(t0s[k], p["f"], p["cx"], p["cy"])
             cams["f"][k] = float(p["f"]); cams["cx"][k] = float(p["cx"]); cams["cy"][k] = float(p["cy"])
         P = len(self._colors)
         inter = np.zeros((K, P), np.int64); uni = np.zeros((K, P), np.int64)
