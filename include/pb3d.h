@@ -368,6 +368,28 @@ int pb3d_label_colors_conn_stats_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64
  * run pb3d_label_colors_conn_stats_dev + pb3d_component_stats_dev + pb3d_recolor_last_labelled_dev instead). */
 int pb3d_top_k_components_dev(pb3d_ctx* ctx, uint8_t* d_grid, int64_t A0, int64_t A1, int64_t A2, const uint8_t color[3], int channels, int64_t k,
                               int connectivity, int32_t* d_labels, int64_t* d_status);
+/* The members of up to PB3D_CCL_MAX_COLORS chosen components of a labelling just made on the context (pb3d_label_colors_conn_stats_dev
+ * or any pb3d_label_*): what extract_minaret_voxels_by_label (reference utils/camera_estimation.py:176-216), extract_minaret_masks_by_label
+ * (:247-325) and the keypoints of extract_top_bottom_voxel_points (:329-336) take from `labeled == cid`, without a pass over the grid per
+ * component.  d_grid / channels as the labelling had them (3: colour grid; 1: label volume), d_labels the volume it wrote.  Selection k is
+ * colour colors[k * channels ..], label labels[k] in THAT colour's numbering, box bbox_lo_hi[6k ..] (lo inclusive, hi exclusive, the
+ * labelling's statistics; a box outside (A0, A1, A2) is PB3D_EINVAL); only its box is walked.  A voxel is a member when its grid bytes equal
+ * the colour and its label equals labels[k]: the label is read only where the colour matches, so a members_only volume (unspecified
+ * entries elsewhere) serves as well as a full one, and the labelling's membership bits are not consulted.  `outputs` ORs:
+ *   PB3D_MEMBERS_COORDS  d_coords (device, int64): the members' (a0, a1, a2) in raster order -- np.argwhere(labeled == cid) order --
+ *                        selection k in rows [counts[0] + .. + counts[k - 1], + counts[k]) (counts: host, the components' voxel counts);
+ *                        at most counts[k] rows are written per selection;
+ *   PB3D_MEMBERS_ROWS    d_rows (device, nsel x 8 int64, cleared by the call): {count, sum a0, sum a1, sum a2} of the members on the box's
+ *                        bottom axis-1 row (lo[1]), then the same for its top row (hi[1] - 1);
+ *   PB3D_MEMBERS_MASK    d_masks (device, nsel x A0*A1*A2 uint8, cleared by the call): 1 at the members, 0 elsewhere (the image form of a
+ *                        (1, H, W) labelling is the (H, W) mask).
+ * More than PB3D_CCL_MAX_COLORS selections, or a NULL buffer for a requested output, is PB3D_EINVAL.  Queued on the context's stream. */
+#define PB3D_MEMBERS_COORDS 1
+#define PB3D_MEMBERS_ROWS 2
+#define PB3D_MEMBERS_MASK 4
+int pb3d_component_members_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64_t A1, int64_t A2, int channels, const int32_t* d_labels,
+                               int nsel, const uint8_t* colors, const int32_t* labels, const int64_t* bbox_lo_hi, const int64_t* counts, int outputs,
+                               int64_t* d_coords, int64_t* d_rows, uint8_t* d_masks);
 int pb3d_component_paste_label_dev(pb3d_ctx* ctx, const uint8_t* d_grid_lab, const int32_t* d_labels, int32_t id, const uint8_t* d_carved_occ,
                                    int64_t A0, int64_t A1, int64_t A2, const int64_t lo[3], const int64_t hi[3], uint8_t* d_carved);
 int pb3d_extrude_label_dev(pb3d_ctx* ctx, const uint8_t* d_grid_lab, int64_t W, int64_t H, int64_t D, const uint8_t* d_valid, int64_t valid_w,

@@ -1,8 +1,8 @@
 """pb3d -- MI355X-native semantic voxel carving & re-projection (host side).
 
 Mirrors the reference's L2 function surface (utils.voxel_carving_utils, utils.voxel_utils,
-utils.projection_utils, utils.camera_geometry, utils.camera_estimation.compute_partwise_iou,
-utils.config) on top of libpb3d.so.  `install()` rebinds those names inside an imported
+utils.projection_utils, utils.camera_geometry, utils.camera_estimation.compute_partwise_iou and the
+minaret extraction, utils.config) on top of libpb3d.so.  `install()` rebinds those names inside an imported
 reference `utils` package so notebooks 1-3 run unchanged.
 """
 from . import _hostmem, _lib, device, dist, formats, labels  # noqa: F401
@@ -14,6 +14,8 @@ from ._hostmem import set_result_pool  # noqa: F401
 from .camera_estimation import (CameraObjective, compute_partwise_iou, coordinate_descent, powell_search, projection_iou_by_part,  # noqa: F401
                                 random_search)
 from .eval_helpers_intra import compute_global_depth_buffer, project_part_visible  # noqa: F401
+from .minarets import (extract_minaret_kps_for_view, extract_minaret_masks_by_label, extract_minaret_voxels_by_label,  # noqa: F401
+                       extract_top_bottom_image_points, extract_top_bottom_voxel_points)
 from .mask_utils import load_and_prepare_masks, load_mask, mask_parts_from_image  # noqa: F401
 from .camera_geometry import look_at_rotation, project  # noqa: F401
 from .deformation_estimation import (build_deformed_grid, deform_coords, deform_part, evaluate_part_deform,  # noqa: F401
@@ -31,7 +33,8 @@ _PATCH = {
                             "recolor_backward_components", "partwise_carve"],
     "voxel_utils": ["get_voxel_points_by_parts", "extract_top_k_components", "voxel_grid_to_points"],
     "projection_utils": ["project_colored_voxels"],
-    "camera_estimation": ["compute_partwise_iou"],
+    "camera_estimation": ["compute_partwise_iou", "extract_minaret_voxels_by_label", "extract_minaret_masks_by_label",
+                          "extract_top_bottom_voxel_points", "extract_top_bottom_image_points", "extract_minaret_kps_for_view"],
     "eval_helpers_intra": ["compute_global_depth_buffer", "project_part_visible"],
 }
 

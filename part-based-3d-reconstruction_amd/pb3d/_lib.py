@@ -91,6 +91,7 @@ _SIGNATURES = {
     "pb3d_component_stats_dev": [vp, vp, i64, i64, i64, i64, i64p, i64p, i64p],
     "pb3d_label_colors_conn_stats_dev": [vp, vp, i64, i64, i64, u8p, C.c_int, C.c_int, C.c_int, vp, i64p, i64, C.c_int, i64p, i64p, i64p, intp],
     "pb3d_top_k_components_dev": [vp, vp, i64, i64, i64, u8p, C.c_int, i64, C.c_int, vp, vp],
+    "pb3d_component_members_dev": [vp, vp, i64, i64, i64, C.c_int, vp, C.c_int, u8p, C.POINTER(C.c_int32), i64p, i64p, C.c_int, vp, vp, vp],
     "pb3d_crop_occupancy_dev": [vp, vp, i64, i64, i64, i64p, i64p, vp],
     "pb3d_crop_occupancy_label_dev": [vp, vp, i64, i64, i64, i64p, i64p, vp],
     "pb3d_component_paste_dev": [vp, vp, vp, C.c_int32, vp, i64, i64, i64, i64p, i64p, vp],

@@ -5,6 +5,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from .minarets import (extract_minaret_kps_for_view, extract_minaret_masks_by_label, extract_minaret_voxels_by_label,  # noqa: F401
+                       extract_top_bottom_image_points, extract_top_bottom_voxel_points)
 
 __all__ = ["compute_partwise_iou", "CameraObjective", "projection_iou_by_part", "random_search", "coordinate_descent", "powell_search"]
 

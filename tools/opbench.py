@@ -245,9 +245,78 @@ def main():
             print(json.dumps(r), flush=True)
             d_img.free()
         d_pts.free(); d_pc.free()
+    if "MN" in ops:
+        minarets(a.reps, res)
     if d_col is not None:
         d_col.free()
     return res
+
+
+def minarets(reps, res):
+    """extract_minaret_voxels_by_label (reference utils/camera_estimation.py:176-216) on the stored Taj grid (512 x 278 x 512) and on a
+    1024^3 grid with four tall components: the labelling of the two minaret colours (6-connected, members only, statistics, one host
+    round trip) and the member pass over the four chosen boxes (pb3d_component_members_dev: coordinates; row sums only) timed apart,
+    then the whole NumPy-signature call (host wall time, upload and download included)."""
+    from pb3d import minarets as mn
+    lib, L = pb3d._lib.load(), pb3d._lib
+    colors = [pb3d.PART_COLORS["front_minarets"], pb3d.PART_COLORS["back_minarets"]]
+    taj = np.load(os.path.join(ROOT, "tests", "golden", "stored_Taj_voxel_grid.npz"))["voxel_grid"]
+    S = 1024
+    for name, shape3 in (("Taj 512x278x512", taj.shape[:3]), ("synthetic 1024^3, four tall components", (S, S, S))):
+        nvox = int(np.prod(shape3))
+        d_g = dev.DeviceBuffer(nvox * 3)
+        if name.startswith("Taj"):
+            d_g.upload(taj)
+        else:
+            d_g.zero()
+            for x0, cols4 in ((100, ((100, 900, colors[0]), (800, 880, colors[1]))), (800, ((100, 860, colors[1]), (800, 840, colors[0])))):
+                plane = np.zeros((S, S, 3), np.uint8)          # one (a1, a2) plane of the columns at a0 in [x0, x0 + 32)
+                for z0, h, col in cols4:
+                    plane[50:50 + h, z0:z0 + 32] = col
+                for x in range(x0, x0 + 32):
+                    d_g.upload(plane, x * S * S * 3)
+        d_lab = dev.DeviceBuffer(nvox * 4)
+        cols, where = mn._distinct(colors)
+        labs = {}
+        lab_fn = lambda: labs.__setitem__("lab", mn._Labelling(d_g, shape3, cols, d_lab, 6, 1024))
+        ms_lab = timeit(lab_fn, reps, warm=1)
+        lab = labs["lab"]
+        sel = mn._four_minarets(lab, where)
+        counts = np.array([s[3] for s in sel], np.int64)
+        ccols = np.ascontiguousarray(np.stack([cols[s[0]] for s in sel]))
+        labels = np.ascontiguousarray([s[1] for s in sel], np.int32)
+        bbox = np.ascontiguousarray(np.stack([s[2] for s in sel]), np.int64)
+        d_xyz = dev.DeviceBuffer(int(counts.sum()) * 24); d_rows = dev.DeviceBuffer(4 * 64)
+
+        def members(outputs):
+            L.check(lib.pb3d_component_members_dev(L.ctx(), C.c_void_p(d_g.ptr), *shape3, 3, C.c_void_p(d_lab.ptr), 4, L.p_u8(ccols),
+                                                   labels.ctypes.data_as(C.POINTER(C.c_int32)), bbox.ctypes.data_as(L.i64p),
+                                                   counts.ctypes.data_as(L.i64p), outputs, C.c_void_p(d_xyz.ptr), C.c_void_p(d_rows.ptr), None))
+        ms_coords = timeit(lambda: members(1), reps, warm=1)
+        ms_rows = timeit(lambda: members(2), reps, warm=1)
+        box_vox = int(sum(np.prod(b[3:] - b[:3]) for b in bbox))
+        r = {"op": "MN", "name": f"extract_minaret_voxels_by_label, {name}", "shape": list(shape3), "labelling_ms": round(ms_lab, 4),
+             "members_coords_ms": round(ms_coords, 4), "members_rows_ms": round(ms_rows, 4), "members": int(counts.sum()),
+             "box_voxels": box_vox, "box_fraction": round(box_vox / nvox, 5),
+             "components": int(sum(lab.recs[ci][0] for ci in range(len(cols))))}
+        if name.startswith("Taj"):
+            t = []
+            for _ in range(reps + 1):
+                t0 = time.perf_counter()
+                pb3d.extract_minaret_voxels_by_label(taj, colors)
+                t.append(time.perf_counter() - t0)
+            r["numpy_api_ms"] = round(1e3 * float(np.median(t[1:])), 3)
+            grid = dev.DeviceGrid(d_g, taj.shape)
+            t = []
+            for _ in range(reps + 1):
+                t0 = time.perf_counter()
+                pb3d.extract_minaret_voxels_by_label(grid, colors)
+                t.append(time.perf_counter() - t0)
+            r["device_grid_api_ms"] = round(1e3 * float(np.median(t[1:])), 3)
+        print(json.dumps(r), flush=True)
+        res.append(r)
+        for b in (d_g, d_lab, d_xyz, d_rows):
+            b.free()
 
 
 if __name__ == "__main__":
