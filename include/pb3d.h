@@ -57,7 +57,7 @@ int pb3d_device_info(pb3d_ctx* ctx, char* name, int name_cap, int* compute_units
 int pb3d_sync(pb3d_ctx* ctx);
 /* Development knobs (results never depend on them; they select between kernels that are all bit-exact, and the parity tests use them to
  * run both forms of a kernel on the same grids).  Every knob has a name -- "sliced", "rot90_wide", "rot90_flat", "rot90_fill",
- * "rot90_mask_block", "global_composed", "per_job", "points_fill", "points_onepass", "orient_tile", "ccl_*", "s32_*", "no_table_cache",
+ * "rot90_mask_block", "global_composed", "per_job", "orient_tile", "ccl_*", "s32_*", "no_table_cache",
  * "uncap", "crop_ablate" (csrc/ctx.hip lists them with their ranges); an unknown name or a value out of range is PB3D_EINVAL.  Initial
  * values come from the environment, read ONCE in pb3d_create: PB3D_KNOBS="name=value,name=value" (any knob), and PB3D_SLICED,
  * PB3D_ROT90_WIDE, PB3D_S32_GPW, PB3D_UNCAP. */
@@ -175,12 +175,10 @@ int pb3d_points_count_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int6
                           const uint8_t* colors, int ncolors, int stride, int64_t* n);
 int pb3d_points_fill_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64_t A1, int64_t A2, int C,
                          const uint8_t* colors, int ncolors, int stride, int64_t n, float* d_pts, uint8_t* d_cols);
-/* One-pass form (stride 1) FOR CAPACITY-BOUNDED CALLERS ONLY -- it is the SLOWER form on MI355X: count + fill above takes 2.3 ms at
- * 1024^3 / 416 M points, this entry 4.1-4.5 ms (a decoupled look-back waits for flags that cross XCDs).  Use
- * it when the output buffers exist before the count is known and a second sweep cannot be scheduled; otherwise count, then fill.
- * The selected voxels are counted AND written in a single sweep of the grid (ordered stream compaction).
- * capacity = rows d_pts (n x 3 float32) / d_cols (n x C) can take; *n is the number of selected voxels.  If *n > capacity the
- * buffers hold only whole blocks that fitted and the call must be repeated with capacity >= *n.  Synchronises (returns *n). */
+/* count + fill in one call (stride 1, a 16-byte aligned grid), for callers whose output buffers exist before the count is known.
+ * capacity = rows d_pts (n x 3 float32) / d_cols (n x C) can take; *n is the number of selected voxels.  If *n <= capacity the
+ * buffers hold the points when the call returns; otherwise nothing is written and the call must be repeated with capacity >= *n.
+ * It keeps its state apart from pb3d_points_count_dev / pb3d_points_fill_dev: it may run between the two.  Synchronises (returns *n). */
 int pb3d_points_extract_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64_t A1, int64_t A2, int C, const uint8_t* colors, int ncolors,
                             int64_t capacity, float* d_pts, uint8_t* d_cols, int64_t* n);
 int pb3d_points_count(pb3d_ctx* ctx, const uint8_t* grid, int64_t A0, int64_t A1, int64_t A2, int C,

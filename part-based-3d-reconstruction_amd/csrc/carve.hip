@@ -593,7 +593,7 @@ int pb3d_part_carve_dev(pb3d_ctx* ctx, const uint8_t* d_colored, int64_t W, int6
     const i64 ngroups = nvox / 16, vtail = 16 * ngroups;                    // the last nvox % 16 voxels: scalar kernels from vtail on
     const pb3d_magic mD = pb3d_make_magic((u32)(D > 0 ? D : 1));
     const unsigned gblocks = pb3d_stream_blocks(ctx, ngroups > 0 ? ngroups : 1, 256, 8);
-    // up to eight such jobs: each leaves its carved occupancy in its own volume and ONE pass merges them (k_part_multi16); tune misc3 = 2
+    // up to eight such jobs: each leaves its carved occupancy in its own volume and ONE pass merges them (k_part_multi16); knob per_job = 1
     // keeps the job-by-job keep-OR passes
     JobList jl; jl.n = 0;
     for (int j = 0; j < njobs; ++j)

@@ -90,6 +90,7 @@ int pb3d_create(int device, pb3d_ctx** out) {
     ctx->pinned_bytes = 1 << 16;
     e = hipHostMalloc(&ctx->pinned, ctx->pinned_bytes, hipHostMallocDefault);
     if (e != hipSuccess) {
+        (void)hipEventDestroy(ctx->s32_ev);
         (void)hipStreamDestroy(ctx->stream);
         free(ctx);
         pb3d_set_error("hipHostMalloc failed: %s", hipGetErrorString(e));
@@ -110,6 +111,7 @@ int pb3d_create(int device, pb3d_ctx** out) {
             if (rc != PB3D_OK) {
                 if (eq == std::string::npos) pb3d_set_error("PB3D_KNOBS: '%s' is not name=value", item.c_str());
                 (void)hipHostFree(ctx->pinned);
+                (void)hipEventDestroy(ctx->s32_ev);
                 (void)hipStreamDestroy(ctx->stream);
                 free(ctx);
                 return PB3D_EINVAL;
@@ -136,8 +138,6 @@ const Knob kKnobs[] = {
     {"ccl_init_blocks", &pb3d_ctx::tune_ccl_init_blocks, 0, 1 << 20, "a count of workgroups per CU"},
     {"ccl_tilecols", &pb3d_ctx::tune_ccl_tilecols, 0, 64, "at most 64"},
     {"ccl_merge", &pb3d_ctx::tune_ccl_merge, 0, 1, "0 (tile kernels) or 1 (pairwise kernel)"},
-    {"points_fill", &pb3d_ctx::tune_points_fill, 0, 1, "0 (wave-private fill) or 1 (block form)"},
-    {"points_onepass", &pb3d_ctx::tune_points_onepass, 0, 1, "0 (count + fill) or 1 (one-pass look-back form in the host entry)"},
     {"orient_tile", &pb3d_ctx::tune_orient_tile, 0, 1, "0 (128-pixel tiles where they apply) or 1 (never)"},
     {"global_composed", &pb3d_ctx::tune_global_composed, 0, 1, "0 (mask bits -> sliced chain -> colours) or 1 (ones -> process -> colour)"},
     {"per_job", &pb3d_ctx::tune_per_job, 0, 1, "0 (merged / fused forms) or 1 (job by job)"},

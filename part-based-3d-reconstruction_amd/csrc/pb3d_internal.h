@@ -34,7 +34,6 @@ struct pb3d_ctx {
     int tune_rot90_order;       // knob "rot90_order": 1 = tiles in plain x-fastest order instead of one plane chunk per XCD
     int tune_rot90_flat;        // knob "rot90_flat": 0 = choose, 1 = never the flat (stream) forms: the row-wise tile kernel, 2 = flat only on whole-line streams
     int tune_rot90_mask_block;  // knob "rot90_mask_block": 1 = the 90-degree kernels fetch their mask bytes per plane / segment instead of once into LDS
-    int tune_points_onepass;    // knob "points_onepass": 1 = the host entry of the point extraction uses the one-pass (look-back) form
     int tune_orient_tile;       // knob "orient_tile": 1 = pb3d_orient_dev without its 128-pixel tile kernel
     int tune_global_composed;   // knob "global_composed": 1 = global_carve with other angle steps as ones -> process -> colour (parity tests run both)
     int tune_per_job;           // knob "per_job": 1 = part_carve's non-90 jobs one by one (no merged pass); label forms of global_carve / part_carve by their per-job passes
@@ -53,7 +52,6 @@ struct pb3d_ctx {
     int tune_ccl_blocks;        // knob "ccl_blocks": workgroups per CU of the labelling's last pass (0 = default)
     int tune_ccl_init_blocks;   // knob "ccl_init_blocks": workgroups per CU of the labelling's first pass (0 = 16)
     int tune_ccl_tilecols;      // knob "ccl_tilecols": windows per level of a plane-to-plane merge tile (0 = 32)
-    int tune_points_fill;       // knob "points_fill": 1 = the block form of the two-pass fill (k_points_fill16; development A/B)
     int tune_ccl_merge;         // knob "ccl_merge": 0 = tile kernels where the rows fit, 1 = always the pairwise kernel (development A/B)
     // Growable device scratch slots used by the host-pointer entry points (no hipMalloc /
     // hipFree per call once warm).
@@ -72,7 +70,6 @@ struct pb3d_ctx {
         int C, ncolors, stride;
         u8 colors[3 * 32];
         bool valid;
-        bool extracted;     // the points already sit in scratch 1 / 3 (single-pass extraction during the count)
     } pts;
     // state kept between pb3d_deform_count and pb3d_deform_fill
     struct {

@@ -885,11 +885,10 @@ def test_points_colour_sets_hash_probe(pb3d_gpu, oracle):
 
 
 @pytest.mark.gpu
-def test_points_wave_fill_and_block_fill(pb3d_gpu, oracle):
-    """the fill pass of the count -> size -> fill protocol in its wave-private form (k_points_fillw, round 4) and in the block form it
-    replaced (knob points_fill = 1), both against the oracle: rows shorter than a lane's four voxels (several row ends inside one
-    lane), sizes that are not multiples of 4 / 16 / 1024 / 4096, densities from a handful of points per wave (head and tail bytes only)
-    to full, RGB grids and 1-byte label volumes."""
+def test_points_wave_fill(pb3d_gpu, oracle):
+    """the fill pass of the count -> size -> fill protocol (the wave-private k_points_fillw) against the oracle: rows shorter than a
+    lane's four voxels (several row ends inside one lane), sizes that are not multiples of 4 / 16 / 1024 / 4096, densities from a
+    handful of points per wave (head and tail bytes only) to full, RGB grids and 1-byte label volumes."""
     from pb3d import labels as L
     rng = np.random.default_rng(404)
     PC = oracle.PART_COLORS
@@ -905,17 +904,77 @@ def test_points_wave_fill_and_block_fill(pb3d_gpu, oracle):
             op, oc = oracle.get_voxel_points_by_parts(grid, PC, sel)
             ap, ac, _ = oracle.voxel_grid_to_points(grid, stride=1)
             lab = L.rgb_to_label(grid, palette)
-            for knob in (0, 1):
-                pb3d_gpu._lib.set_tuning("points_fill", knob)
-                try:
-                    gp, gc = pb3d_gpu.get_voxel_points_by_parts(grid, PC, sel)
-                    assert np.array_equal(gp, op) and np.array_equal(gc, oc), (shp, dens, knob, "parts")
-                    gp, gc, _ = pb3d_gpu.voxel_grid_to_points(grid, stride=1)
-                    assert np.array_equal(gp, ap) and np.array_equal(gc, ac), (shp, dens, knob, "all")
-                    gp, gc = L.get_voxel_points_by_parts_labels(lab, palette, sel)
-                    assert np.array_equal(gp, op) and np.array_equal(gc, oc), (shp, dens, knob, "labels")
-                finally:
-                    pb3d_gpu._lib.set_tuning("points_fill", 0)
+            gp, gc = pb3d_gpu.get_voxel_points_by_parts(grid, PC, sel)
+            assert np.array_equal(gp, op) and np.array_equal(gc, oc), (shp, dens, "parts")
+            gp, gc, _ = pb3d_gpu.voxel_grid_to_points(grid, stride=1)
+            assert np.array_equal(gp, ap) and np.array_equal(gc, ac), (shp, dens, "all")
+            gp, gc = L.get_voxel_points_by_parts_labels(lab, palette, sel)
+            assert np.array_equal(gp, op) and np.array_equal(gc, oc), (shp, dens, "labels")
+
+
+@pytest.mark.gpu
+def test_points_count_extract_fill_interleaved(pb3d_gpu, oracle):
+    """pb3d_points_extract_dev (count + fill in one call) keeps its state apart from a pending count -> fill pair: count_dev(A),
+    extract_dev(B), fill_dev(A) gives A's points, for the 16-voxel kernels and the generic ones (stride 2); extract_dev gives B's
+    points, and with too small a capacity reports the exact count and writes nothing."""
+    import ctypes as C
+    from pb3d import device as dev
+    L, lib = pb3d_gpu._lib, pb3d_gpu._lib.load()
+    rng = np.random.default_rng(405)
+    PC = oracle.PART_COLORS
+    names = list(PC)
+    pal = np.array([PC[n] for n in names], np.uint8)
+
+    def rgb_grid(shp, dens):
+        return pal[rng.integers(0, len(pal), shp)] * (rng.random(shp) < dens)[..., None].astype(np.uint8)
+
+    def on_device(grid):
+        d = dev.DeviceBuffer(grid.nbytes).upload(grid)
+        assert d.ptr % 16 == 0
+        return d
+
+    gb = rgb_grid((37, 29, 61), 0.4)                                         # B: another size, other contents, other colours
+    sel_b = names[3:7]
+    cols_b = np.ascontiguousarray(pal[3:7])
+    want_bp, want_bc = oracle.get_voxel_points_by_parts(gb, PC, sel_b)
+    d_b = on_device(gb)
+    ga = rgb_grid((45, 70, 33), 0.3)
+    lab = rng.integers(0, 16, (51, 18, 77)).astype(np.uint8) * (rng.random((51, 18, 77)) < 0.5)
+    labels = np.array([1, 4, 9, 15], np.uint8)
+    op, oc = oracle.get_voxel_points_by_parts(ga, PC, names[:4])
+    sp, sc, _ = oracle.voxel_grid_to_points(ga, stride=2)
+    a0, a1, a2 = np.nonzero(np.isin(lab, labels))
+    cases = [   # (grid A, channels, colours, stride, expected points, expected colours)
+        (ga, 3, np.ascontiguousarray(pal[:4]), 1, op, oc),
+        (ga, 3, np.zeros((0, 3), np.uint8), 2, sp, sc),
+        (lab, 1, labels, 1, np.stack([a2, a1, a0], axis=1).astype(np.float32), lab[a0, a1, a2][:, None]),
+    ]
+    for ci, (g, ch, cols, stride, want_p, want_c) in enumerate(cases):
+        A0, A1, A2 = g.shape[:3]
+        d_a = on_device(g)
+        n = C.c_int64(0)
+        L.check(lib.pb3d_points_count_dev(L.ctx(), C.c_void_p(d_a.ptr), A0, A1, A2, ch, L.p_u8(cols), len(cols), stride, C.byref(n)))
+        assert n.value == len(want_p), ci
+        nb = len(want_bp)
+        d_bp = dev.DeviceBuffer(nb * 12); d_bc = dev.DeviceBuffer(nb * 3)
+        for cap in (nb - 1, nb):
+            d_bp.upload(np.full(nb * 12, 0xA5, np.uint8)); d_bc.upload(np.full(nb * 3, 0xA5, np.uint8))
+            n2 = C.c_int64(0)
+            L.check(lib.pb3d_points_extract_dev(L.ctx(), C.c_void_p(d_b.ptr), *gb.shape[:3], 3, L.p_u8(cols_b), len(cols_b), cap,
+                                                C.c_void_p(d_bp.ptr), C.c_void_p(d_bc.ptr), C.byref(n2)))
+            assert n2.value == nb, (ci, cap)
+            if cap < nb:
+                assert (d_bp.download((nb * 12,)) == 0xA5).all() and (d_bc.download((nb * 3,)) == 0xA5).all(), (ci, "written past capacity")
+            else:
+                assert np.array_equal(d_bp.download((nb, 3), np.float32), want_bp) and np.array_equal(d_bc.download((nb, 3)), want_bc), (ci, "B")
+        d_ap = dev.DeviceBuffer(max(1, n.value) * 12); d_ac = dev.DeviceBuffer(max(1, n.value) * ch)
+        L.check(lib.pb3d_points_fill_dev(L.ctx(), C.c_void_p(d_a.ptr), A0, A1, A2, ch, L.p_u8(cols), len(cols), stride, n.value,
+                                         C.c_void_p(d_ap.ptr), C.c_void_p(d_ac.ptr)))
+        got_p = d_ap.download((n.value, 3), np.float32); got_c = d_ac.download((n.value, ch))
+        assert np.array_equal(got_p, want_p) and np.array_equal(got_c, want_c), (ci, "A")
+        for b in (d_a, d_ap, d_ac, d_bp, d_bc):
+            b.free()
+    d_b.free()
 
 
 @pytest.mark.gpu
@@ -948,16 +1007,17 @@ def test_part_carve_odd_shapes_w_ne_d(pb3d_gpu, oracle):
 
 
 @pytest.mark.gpu
-def test_named_knobs(pb3d_gpu):
-    """development knobs have names (include/pb3d.h: pb3d_set_tuning): an unknown name and a value out of range are refused with a
-    message that says what the knob takes; PB3D_KNOBS is parsed by pb3d_create (a bad entry fails the creation loudly)."""
+def test_named_knobs_and_retired_names(pb3d_gpu):
+    """development knobs have names (include/pb3d.h: pb3d_set_tuning): an unknown name -- the retired misc* and points_* knobs
+    included -- and a value out of range are refused with a message that says what the knob takes; PB3D_KNOBS is parsed by
+    pb3d_create (a bad entry fails the creation loudly)."""
     import subprocess, sys
     L = pb3d_gpu._lib
-    for name, bad in (("sliced", 2), ("rot90_flat", 3), ("per_job", -1), ("points_fill", 5)):
+    for name, bad in (("sliced", 2), ("rot90_flat", 3), ("per_job", -1), ("ccl_merge", 2)):
         with pytest.raises(ValueError, match=name):
             L.set_tuning(name, bad)
         L.set_tuning(name, 0)
-    for name in ("misc0", "misc3", "no_such_knob"):
+    for name in ("misc0", "misc3", "points_fill", "points_onepass", "no_such_knob"):
         with pytest.raises(ValueError, match="unknown knob"):
             L.set_tuning(name, 1)
     code = "import sys; sys.path.insert(0, %r); import pb3d; pb3d._lib.ctx(); print('created')" % PKG
@@ -1450,7 +1510,8 @@ def test_full_size_points_and_projection_1024(pb3d_gpu, oracle):
         got_c = d_pc.download((c1 - c0, 3), byte_offset=c0 * 3)
         want_p = np.stack([a2, a1, np.full(len(a1), a)], axis=1).astype(np.float32)
         assert np.array_equal(got_p, want_p) and np.array_equal(got_c, plane[a1, a2]), a
-    # ---- the one-pass form (decoupled look-back): same count, same rows, in the same order; too small a capacity is reported
+    # ---- count + fill in one call (pb3d_points_extract_dev): same count, same rows, in the same order; too small a capacity is reported
+    #      with the exact count and nothing written
     d_pts2 = dev.DeviceBuffer(npts * 12); d_pc2 = dev.DeviceBuffer(npts * 3)
     n2 = C.c_int64(0)
     L.check(lib.pb3d_points_extract_dev(L.ctx(), C.c_void_p(d_col.ptr), S, S, S, 3, L.p_u8(cols), len(cols), npts, C.c_void_p(d_pts2.ptr),
@@ -1461,9 +1522,14 @@ def test_full_size_points_and_projection_1024(pb3d_gpu, oracle):
         if c1 > c0:
             assert np.array_equal(d_pts2.download((c1 - c0, 3), np.float32, byte_offset=c0 * 12), d_pts.download((c1 - c0, 3), np.float32, byte_offset=c0 * 12))
             assert np.array_equal(d_pc2.download((c1 - c0, 3), byte_offset=c0 * 3), d_pc.download((c1 - c0, 3), byte_offset=c0 * 3))
+    for b in (d_pts2, d_pc2):
+        L.check(lib.pb3d_dev_memset(L.ctx(), C.c_void_p(b.ptr), 0xA5, b.nbytes))
     L.check(lib.pb3d_points_extract_dev(L.ctx(), C.c_void_p(d_col.ptr), S, S, S, 3, L.p_u8(cols), len(cols), npts // 2, C.c_void_p(d_pts2.ptr),
                                         C.c_void_p(d_pc2.ptr), C.byref(n2)))
     assert n2.value == npts                                                  # the count is still exact; the caller sees n > capacity
+    for b in (d_pts2, d_pc2):
+        for o in range(0, b.nbytes, 1 << 28):
+            assert (b.download((min(1 << 28, b.nbytes - o),), byte_offset=o) == 0xA5).all(), ("written past capacity", o)
     d_pts2.free(); d_pc2.free()
     # ---- M8 on the full list
     from pb3d.camera_geometry import look_at_rotation
@@ -1493,6 +1559,45 @@ def test_full_size_points_and_projection_1024(pb3d_gpu, oracle):
     assert hit.any() and np.array_equal(img[hit], sub[hit])
     for b in (d_col, d_pts, d_pc, d_img, d_keys):
         b.free()
+
+
+@pytest.mark.gpu
+def test_points_past_2_32_voxels(pb3d_gpu):
+    """count -> fill on a C = 1 grid of more than 2^32 voxels (4100 x 1024 x 1024, 4.3 GB): zero but for planted planes at the
+    start, on both sides of voxel 2^32 (plane 4096 starts there; one run of voxels straddles it) and at the end.  Every planted
+    plane's points and bytes equal np.nonzero of that plane, for occupancy (no label set) and for a label set."""
+    import ctypes as C
+    from pb3d import device as dev
+    L, lib = pb3d_gpu._lib, pb3d_gpu._lib.load()
+    A0, A1, A2 = 4100, 1024, 1024
+    plane = A1 * A2
+    assert 4096 * plane == 2 ** 32
+    rng = np.random.default_rng(406)
+    planted = {a: rng.integers(1, 16, (A1, A2)).astype(np.uint8) * (rng.random((A1, A2)) < 0.2) for a in (0, 4095, 4096, A0 - 1)}
+    planted[4095][-3:] = 7                   # the last three rows of plane 4095 and the first two of plane 4096:
+    planted[4096][:2] = 7                    # voxels 2^32 - 3072 .. 2^32 + 2047
+    d_g = dev.DeviceBuffer(A0 * plane)
+    assert d_g.ptr % 16 == 0                 # the 16-voxel kernels
+    d_g.zero()
+    for a, pl in planted.items():
+        d_g.upload(pl, byte_offset=a * plane)
+    for labels in (np.zeros(0, np.uint8), np.array([2, 7, 11], np.uint8)):
+        sel = {a: np.isin(pl, labels) if len(labels) else pl != 0 for a, pl in planted.items()}
+        n = C.c_int64(0)
+        L.check(lib.pb3d_points_count_dev(L.ctx(), C.c_void_p(d_g.ptr), A0, A1, A2, 1, L.p_u8(labels), len(labels), 1, C.byref(n)))
+        assert n.value == sum(int(m.sum()) for m in sel.values()), labels
+        d_p = dev.DeviceBuffer(n.value * 12); d_c = dev.DeviceBuffer(n.value)
+        L.check(lib.pb3d_points_fill_dev(L.ctx(), C.c_void_p(d_g.ptr), A0, A1, A2, 1, L.p_u8(labels), len(labels), 1, n.value,
+                                         C.c_void_p(d_p.ptr), C.c_void_p(d_c.ptr)))
+        c0 = 0
+        for a in sorted(sel):
+            a1, a2 = np.nonzero(sel[a])
+            want_p = np.stack([a2, a1, np.full(len(a1), a)], axis=1).astype(np.float32)
+            assert np.array_equal(d_p.download((len(a1), 3), np.float32, byte_offset=c0 * 12), want_p), (labels, a)
+            assert np.array_equal(d_c.download((len(a1),), byte_offset=c0), planted[a][a1, a2]), (labels, a)
+            c0 += len(a1)
+        d_p.free(); d_c.free()
+    d_g.free()
 
 
 @pytest.mark.gpu
@@ -1898,7 +2003,7 @@ def test_recolour_entries_agree(pb3d_gpu, oracle):
 
 def test_rot90_flat_ragged_streams(pb3d_gpu, oracle):
     """the flat 90-degree kernel on x-row streams that are whole 16-byte pieces but not whole lines (H * D % 16 == 0, % 128 != 0, e.g.
-    500 x 400 x 500): ragged last segment, rows of odd x starting mid-line -- against the tile kernel (tune misc2 = 4) and the oracle."""
+    500 x 400 x 500): ragged last segment, rows of odd x starting mid-line -- against the tile kernel (knob rot90_flat = 2) and the oracle."""
     rng = np.random.default_rng(43)
     for (W, H, D) in [(200, 12, 204), (260, 10, 136), (131, 4, 140), (300, 8, 250), (150, 24, 202)]:
         assert (H * D) % 16 == 0 and (H * D) % 128 != 0 and D >= 128

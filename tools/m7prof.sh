@@ -1,6 +1,6 @@
 #!/bin/bash
 # Point extraction (M7) under rocprofv3: per-kernel time, FETCH_SIZE / WRITE_SIZE (separate passes) and the SQ counters of the count and
-# fill kernels.  usage: tools/m7prof.sh <tag> [opbench args, e.g. --tune points_fill=1]
+# fill kernels.  usage: tools/m7prof.sh <tag> [opbench args, e.g. --reps 10]
 tag=$1; shift
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/m7_$tag; mkdir -p $O

@@ -226,7 +226,7 @@ def main():
                                                               C.c_void_p(d_pts.ptr), C.c_void_p(d_pc.ptr), C.byref(n1)))
             ms1 = timeit(one, max(2, a.reps // 2), warm=1)
             assert n1.value == npts
-            report("M7", "get_voxel_points_by_parts (10 parts): ONE pass (pb3d_points_extract_dev, decoupled look-back)", ms1,
+            report("M7", "get_voxel_points_by_parts (10 parts): count + fill in one call (pb3d_points_extract_dev)", ms1,
                    round(3 + 15 * fillfrac, 3), {"points": npts, "fill": round(fillfrac, 4)})
         if "M8" in ops and npts:
             from pb3d.camera_geometry import look_at_rotation
