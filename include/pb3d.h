@@ -209,6 +209,48 @@ int pb3d_visible_mask_dev(pb3d_ctx* ctx, const void* d_pts, int pts_f64, int64_t
                           double cx, double cy, const int prec[4], const float* d_zbuf, int Himg, int Wimg, double eps, int eps_f32,
                           uint8_t* d_mask);
 
+/* ---- notebook 4 on the device (row N6), reference utils/eval_helpers_intra.py:287-748 ------------------------------------
+ * The z-buffer and visibility passes of run_minaret_iou_evaluation / run_part_minaret_binary_iou without point lists: the
+ * (A0,A1,A2,C) uint8 grid (C = 3: RGB, C = 1: labels) is read directly, voxel (a0,a1,a2) being the point (x = a2, y = a1,
+ * z = a0) of the reference's np.where (:139-140, :710-717); a voxel is occupied where any channel is non-zero.  The camera
+ * arguments and eps / eps_f32 are those of pb3d_depth_buffer_dev / pb3d_visible_mask_dev, with the grid's points float32.
+ * Colour tables hold ncolors <= 31 entries of C bytes, none of them 0 (black / label 0 is the empty voxel); a zbuf of
+ * another shape than the image, a bad C or too many colours are refused before any device work, and a null context after them.
+ * grid_depth_buffer: bit for bit pb3d_depth_buffer_dev on the grid's points (compute_global_depth_buffer, :134-163).
+ * grid_visible_bits: bits[v,u] bit k = some voxel of colour k is visible (|Z - zbuf| < eps, :168-190), bit 31 = some occupied
+ *   voxel is; d_zbuf may come from another grid (:669-684 tests the init grid's minarets against the deformed grid's z-buffer).
+ *   Bit k equals pb3d_visible_mask_dev on get_voxel_points_by_parts(grid, colour k), bit 31 on every occupied voxel (:710-728).
+ * points_visible_bits: bit k = some point of list k (counts[k] rows of 3; pts_type 0 float32, 1 float64, 2 int64) is visible
+ *   (:509-526: the int64 np.argwhere sets of extract_minaret_voxels_by_label; prec[0] = 1 for them, as NumPy promotes).
+ * color_presence: d_bitmap (PB3D_PRESENCE_BYTES, bit r | g << 8 | b << 16, or the label) = the non-zero values of nvox voxels
+ *   (compute_binary_gt's np.unique, :274-280); d_present[0] bit k = colour k of the table is among them (may be null when
+ *   ncolors == 0).
+ * mask_bits: bits[px] bit k = RGB mask pixel px has colour k (np.any(mask_parts_from_image(...) > 0), :650-653), bit 31 = its
+ *   colour is in d_bitmap (compute_binary_gt, :281-284; d_bitmap may be null: no bit 31).
+ * iou_rows: per row r, pred = pred[px] & pred_bits, gt = gt[px] & gt_bits and (no gate, or gate[px] & gate_bits);
+ *   d_counts[2r] = #(pred & gt), d_counts[2r+1] = #(pred | gt) (_iou_bool, :269-272; the gate is :525's gt_m & pr_all).
+ *   A null image is all zero.  nrows <= 32. */
+#define PB3D_PRESENCE_BYTES ((size_t)1 << 21)
+typedef struct pb3d_iou_row {
+    const uint32_t* pred;
+    const uint32_t* gt;
+    const uint32_t* gate;
+    uint32_t pred_bits, gt_bits, gate_bits;
+} pb3d_iou_row;
+int pb3d_grid_depth_buffer_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64_t A1, int64_t A2, int C, const double R[9],
+                               const double cam[3], double f, double cx, double cy, const int prec[4], int Himg, int Wimg, float* d_zbuf);
+int pb3d_grid_visible_bits_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64_t A1, int64_t A2, int C, const uint8_t* colors,
+                               int ncolors, const double R[9], const double cam[3], double f, double cx, double cy, const int prec[4],
+                               const float* d_zbuf, int zH, int zW, int Himg, int Wimg, double eps, int eps_f32, uint32_t* d_bits);
+int pb3d_points_visible_bits_dev(pb3d_ctx* ctx, const void* const* d_lists, const int64_t* counts, int nlists, int pts_type, const double R[9],
+                                 const double cam[3], double f, double cx, double cy, const int prec[4], const float* d_zbuf, int zH, int zW,
+                                 int Himg, int Wimg, double eps, int eps_f32, uint32_t* d_bits);
+int pb3d_color_presence_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t nvox, int C, uint32_t* d_bitmap, const uint8_t* colors, int ncolors,
+                            int64_t* d_present);
+int pb3d_mask_bits_dev(pb3d_ctx* ctx, const uint8_t* d_mask, int64_t npix, const uint8_t* colors, int ncolors, const uint32_t* d_bitmap,
+                       uint32_t* d_bits);
+int pb3d_iou_rows_dev(pb3d_ctx* ctx, const pb3d_iou_row* rows, int nrows, int64_t npix, int64_t* d_counts);
+
 /* ---- compute_partwise_iou, reference utils/camera_estimation.py:770-787 -------------------
  * per colour k: inter[k] = #(a==c & b==c), uni[k] = #(a==c | b==c) over npix RGB pixels. */
 int pb3d_partwise_iou_dev(pb3d_ctx* ctx, const uint8_t* d_a, const uint8_t* d_b, int64_t npix,

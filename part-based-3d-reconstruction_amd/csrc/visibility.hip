@@ -1,0 +1,440 @@
+// Notebook 4 (intra-method evaluation, reference utils/eval_helpers_intra.py:287-748) on the device: z-buffers and visible-part bits
+// straight from a voxel grid, visible bits of several point lists, the colour set of a grid, and per-row IoU counts.
+//
+// The reference builds every z-buffer and visibility mask from a point list (np.where over the grid, then a Python loop per point);
+// the point path of project.hip does the same on the device (count + fill + scatter).  Here the grid itself is walked: voxel
+// (a0, a1, a2) is the point (x = a2, y = a1, z = a0), projected by the same project_xyz<1> as the point path, so every pixel and depth
+// is the point path's bit for bit.
+//
+// Grid walk: a lane owns four consecutive a2 columns of one a1 row and walks them along a0 for up to kChunk steps, loading the four
+// voxels with dword loads where the rows allow it (lanes of a wave take consecutive a2).  Under a front camera a column along a0 lands
+// on a handful of pixels, so each column keeps a run: the minimum depth (or the OR of visible bits) while its pixel stays the same,
+// flushed with one atomic when the pixel changes or the walk ends.  The run is exact: float32 min and bit OR are order-free.
+#include "pb3d_internal.h"
+#include "project_point.h"
+
+namespace {
+
+using namespace pb3d_proj;
+
+constexpr int kMaxColours = 31;           // bits 0..30: colours / labels / lists; bit 31: any occupied voxel
+constexpr u32 kAnyBit = 0x80000000u;
+constexpr int kChunk = 64;                // a0 steps per lane
+constexpr int kMaxRows = 32;
+
+struct Walk {
+    const u8* grid;
+    i64 A0, A1, A2, ngx, nitems;
+    int vec;                              // rows of whole dwords: 4 voxels of a lane = 1 (C = 1) or 3 (C = 3) aligned dword loads
+};
+
+struct Colours {
+    u32 key[kMaxColours];                 // r | g << 8 | b << 16 (C = 3) or the label (C = 1); never 0
+    int n;
+};
+
+__device__ __forceinline__ u32 colour_bits(const Colours& c, u32 key) {
+    u32 b = 0;
+    for (int k = 0; k < c.n; ++k) b |= (u32)(c.key[k] == key) << k;
+    return b;
+}
+
+// the four voxels (a0, a1, a2 .. a2 + 3) as keys; columns past A2 read as 0 (empty)
+template <int C>
+__device__ __forceinline__ void load4(const Walk& w, i64 a0, i64 a1, i64 a2, u32 v[4]) {
+    const u8* p = w.grid + ((a0 * w.A1 + a1) * w.A2 + a2) * C;
+    if (w.vec) {
+        if (C == 1) {
+            const u32 x = *(const u32*)p;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[k] = (x >> (8 * k)) & 0xffu;
+        } else {
+            const u32 x0 = ((const u32*)p)[0], x1 = ((const u32*)p)[1], x2 = ((const u32*)p)[2];
+            v[0] = x0 & 0xffffffu;
+            v[1] = (x0 >> 24) | ((x1 & 0xffffu) << 8);
+            v[2] = (x1 >> 16) | ((x2 & 0xffu) << 16);
+            v[3] = x2 >> 8;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            v[k] = 0;
+            if (a2 + k < w.A2) v[k] = C == 1 ? (u32)p[k] : (u32)p[3 * k] | ((u32)p[3 * k + 1] << 8) | ((u32)p[3 * k + 2] << 16);
+        }
+    }
+}
+
+// the reference's visibility test |Z - zbuf| < eps (project.hip VisibleSink): float64 for a float64 camera, else a float32
+// difference compared in float32 when eps is a weak Python float
+__device__ __forceinline__ bool visible(double z, float zb, int t0, double eps, int eps_f32) {
+    if (t0) return fabs(__dsub_rn(z, (double)zb)) < eps;
+    const float dz = fabsf(__fsub_rn((float)z, zb));
+    return eps_f32 ? dz < (float)eps : (double)dz < eps;
+}
+
+__device__ __forceinline__ void flush_min(u32* __restrict__ zbits, i64 px, u32 z) {
+    if (px >= 0 && __hip_atomic_load(&zbits[px], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > z) atomicMin(&zbits[px], z);
+}
+
+__device__ __forceinline__ void flush_or(u32* __restrict__ bits, i64 px, u32 b) {
+    if (px >= 0 && b && (b & ~__hip_atomic_load(&bits[px], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) atomicOr(&bits[px], b);
+}
+
+// (a) zbits[v, u] = float32 bits of the minimum Z over the occupied voxels landing on (u, v)
+template <int C>
+__global__ __launch_bounds__(256) void k_grid_depth(Walk w, ProjParams P, u32* __restrict__ zbits) {
+    const i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= w.nitems) return;
+    const i64 a2 = (t % w.ngx) * 4, r = t / w.ngx, a1 = r % w.A1, a0s = (r / w.A1) * kChunk;
+    const i64 a0e = a0s + kChunk < w.A0 ? a0s + kChunk : w.A0;
+    i64 px[4] = {-1, -1, -1, -1};
+    u32 zr[4] = {0, 0, 0, 0};
+    for (i64 a0 = a0s; a0 < a0e; ++a0) {
+        u32 v[4];
+        load4<C>(w, a0, a1, a2, v);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (!v[k]) continue;
+            const double p[3] = {(double)(a2 + k), (double)a1, (double)a0};
+            int ui, vi;
+            double z;
+            if (!project_xyz<1>(P, p, &ui, &vi, &z)) continue;
+            const i64 q = (i64)vi * P.Wimg + ui;
+            const u32 zb = __float_as_uint((float)z);
+            if (q == px[k]) {
+                zr[k] = zb < zr[k] ? zb : zr[k];
+            } else {
+                flush_min(zbits, px[k], zr[k]);
+                px[k] = q; zr[k] = zb;
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) flush_min(zbits, px[k], zr[k]);
+}
+
+// (b) bits[v, u] |= (1 << k) for a visible voxel of colour k, | kAnyBit for any visible occupied voxel
+template <int C>
+__global__ __launch_bounds__(256) void k_grid_visible_bits(Walk w, ProjParams P, const float* __restrict__ zbuf, double eps, int eps_f32,
+                                                           Colours cols, u32* __restrict__ bits) {
+    const i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= w.nitems) return;
+    const i64 a2 = (t % w.ngx) * 4, r = t / w.ngx, a1 = r % w.A1, a0s = (r / w.A1) * kChunk;
+    const i64 a0e = a0s + kChunk < w.A0 ? a0s + kChunk : w.A0;
+    i64 px[4] = {-1, -1, -1, -1};
+    u32 br[4] = {0, 0, 0, 0};
+    float zr[4] = {0.f, 0.f, 0.f, 0.f};
+    for (i64 a0 = a0s; a0 < a0e; ++a0) {
+        u32 v[4];
+        load4<C>(w, a0, a1, a2, v);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (!v[k]) continue;
+            const double p[3] = {(double)(a2 + k), (double)a1, (double)a0};
+            int ui, vi;
+            double z;
+            if (!project_xyz<1>(P, p, &ui, &vi, &z)) continue;
+            const i64 q = (i64)vi * P.Wimg + ui;
+            if (q != px[k]) {
+                flush_or(bits, px[k], br[k]);
+                px[k] = q; br[k] = 0; zr[k] = zbuf[q];
+            }
+            if (visible(z, zr[k], P.t0, eps, eps_f32)) br[k] |= kAnyBit | colour_bits(cols, v[k]);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) flush_or(bits, px[k], br[k]);
+}
+
+// (c) bits[v, u] |= 1 << list for a visible point of list `list` (blockIdx.y)
+struct Lists {
+    const void* p[kMaxColours];
+    i64 n[kMaxColours];
+    int type;                             // 0 float32, 1 float64, 2 int64
+};
+
+__global__ __launch_bounds__(256) void k_points_visible_bits(Lists L, ProjParams P, const float* __restrict__ zbuf, double eps, int eps_f32,
+                                                             u32* __restrict__ bits) {
+    const int list = blockIdx.y;
+    const i64 n = L.n[list];
+    const u32 mine = 1u << list;
+    for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (i64)gridDim.x * blockDim.x) {
+        double p[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            p[k] = L.type == 2 ? (double)((const long long*)L.p[list])[3 * i + k]
+                 : L.type == 1 ? ((const double*)L.p[list])[3 * i + k] : (double)((const float*)L.p[list])[3 * i + k];
+        int ui, vi;
+        double z;
+        if (!project_xyz<1>(P, p, &ui, &vi, &z)) continue;
+        const i64 q = (i64)vi * P.Wimg + ui;
+        if (visible(z, zbuf[q], P.t0, eps, eps_f32)) flush_or(bits, q, mine);
+    }
+}
+
+// (d, pass one) bitmap bit `key` for every non-zero voxel value.  A lane sends a key only when it differs from its previous one and
+// its bit is not set yet, and the wave sends each distinct key once (leader loop).
+__device__ __forceinline__ void send_keys(u32 cand, u32* __restrict__ bitmap) {
+    if (cand && ((bitmap[cand >> 5] >> (cand & 31)) & 1u)) cand = 0;      // already known (a plain, mostly L1-hit load)
+    u64 pend = __ballot(cand != 0);
+    while (pend) {
+        const int leader = __ffsll((unsigned long long)pend) - 1;
+        const u32 k = (u32)__shfl((int)cand, leader);
+        if (cand == k) {
+            if ((int)__lane_id() == leader) flush_or(bitmap, (i64)(k >> 5), 1u << (k & 31));
+            cand = 0;
+        }
+        pend = __ballot(cand != 0);
+    }
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void k_color_presence(const u8* __restrict__ grid, i64 nvox, int vec, u32* __restrict__ bitmap) {
+    const i64 ng = (nvox + 3) / 4, stride = (i64)gridDim.x * blockDim.x;
+    // wave-uniform trip count: every lane of a wave takes part in each ballot of send_keys
+    const i64 wave0 = ((i64)blockIdx.x * blockDim.x + threadIdx.x) & ~(i64)63;
+    u32 last = 0;
+    for (i64 base = wave0; base < ng; base += stride) {
+        const i64 g = base + __lane_id();
+        u32 v[4] = {0, 0, 0, 0};
+        if (g < ng) {
+            const u8* p = grid + g * 4 * C;
+            if (vec) {
+                if (C == 1) {
+                    const u32 x = *(const u32*)p;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) v[k] = (x >> (8 * k)) & 0xffu;
+                } else {
+                    const u32 x0 = ((const u32*)p)[0], x1 = ((const u32*)p)[1], x2 = ((const u32*)p)[2];
+                    v[0] = x0 & 0xffffffu; v[1] = (x0 >> 24) | ((x1 & 0xffffu) << 8); v[2] = (x1 >> 16) | ((x2 & 0xffu) << 16); v[3] = x2 >> 8;
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (g * 4 + k < nvox) v[k] = C == 1 ? (u32)p[k] : (u32)p[3 * k] | ((u32)p[3 * k + 1] << 8) | ((u32)p[3 * k + 2] << 16);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const u32 cand = v[k] && v[k] != last ? v[k] : 0u;
+            if (v[k]) last = v[k];
+            send_keys(cand, bitmap);
+        }
+    }
+}
+
+// present[0] bit k = colour k is in the bitmap
+__global__ void k_presence_probe(const u32* __restrict__ bitmap, Colours cols, i64* __restrict__ present) {
+    i64 b = 0;
+    for (int k = 0; k < cols.n; ++k) b |= (i64)((bitmap[cols.key[k] >> 5] >> (cols.key[k] & 31)) & 1u) << k;
+    *present = b;
+}
+
+// (d, pass two, and the part ground truths) bits[px] = colour matches of an RGB mask pixel, | kAnyBit where its colour is in the bitmap
+__global__ __launch_bounds__(256) void k_mask_bits(const u8* __restrict__ mask, i64 npix, Colours cols, const u32* __restrict__ bitmap,
+                                                   u32* __restrict__ bits) {
+    for (i64 px = (i64)blockIdx.x * blockDim.x + threadIdx.x; px < npix; px += (i64)gridDim.x * blockDim.x) {
+        const u32 key = (u32)mask[3 * px] | ((u32)mask[3 * px + 1] << 8) | ((u32)mask[3 * px + 2] << 16);
+        u32 b = colour_bits(cols, key);
+        if (bitmap && key && ((bitmap[key >> 5] >> (key & 31)) & 1u)) b |= kAnyBit;
+        bits[px] = b;
+    }
+}
+
+// (e) per row: pred = pred[px] & pred_bits, gt = gt[px] & gt_bits [& gate[px] & gate_bits]; counts[2r] += |pred & gt|,
+// counts[2r + 1] += |pred | gt|.  Lane r of a wave keeps row r's tally (the ballots are wave-uniform); one atomic per wave and row.
+struct Rows {
+    pb3d_iou_row r[kMaxRows];
+    int n;
+};
+
+__device__ __forceinline__ bool hit(const uint32_t* img, uint32_t m, i64 px, bool in) {
+    return in && img && (img[px] & m);
+}
+
+__global__ __launch_bounds__(256) void k_iou_rows(Rows R, i64 npix, unsigned long long* __restrict__ counts) {
+    const int lane = __lane_id();
+    const i64 stride = (i64)gridDim.x * blockDim.x;
+    unsigned long long ai = 0, au = 0;
+    for (i64 base = ((i64)blockIdx.x * blockDim.x + threadIdx.x) & ~(i64)63; base < npix; base += stride) {
+        const i64 px = base + lane;
+        const bool in = px < npix;
+        for (int r = 0; r < R.n; ++r) {
+            const pb3d_iou_row& row = R.r[r];
+            const bool pr = hit(row.pred, row.pred_bits, px, in);
+            const bool gt = hit(row.gt, row.gt_bits, px, in) && (!row.gate || hit(row.gate, row.gate_bits, px, in));
+            const unsigned long long ni = __popcll(__ballot(pr && gt)), nu = __popcll(__ballot(pr || gt));
+            if (lane == r) { ai += ni; au += nu; }
+        }
+    }
+    if (lane < R.n && au) {
+        atomicAdd(&counts[2 * lane], ai);
+        atomicAdd(&counts[2 * lane + 1], au);
+    }
+}
+
+// ---- host helpers -------------------------------------------------------------------------------
+int grid_args(const char* fn, const uint8_t* d_grid, i64 A0, i64 A1, i64 A2, int C) {
+    PB3D_REQUIRE(C == 1 || C == 3, "%s: C must be 1 (labels) or 3 (RGB), got %d", fn, C);
+    PB3D_REQUIRE(A0 >= 0 && A1 >= 0 && A2 >= 0, "%s: bad grid shape", fn);
+    PB3D_REQUIRE(A0 * A1 * A2 == 0 || d_grid, "%s: null grid", fn);
+    return PB3D_OK;
+}
+
+int colour_args(const char* fn, const uint8_t* colors, int ncolors, int C, Colours* out) {
+    PB3D_REQUIRE(ncolors >= 0 && ncolors <= kMaxColours, "%s: at most %d colours (bit 31 is 'any'), got %d", fn, kMaxColours, ncolors);
+    PB3D_REQUIRE(ncolors == 0 || colors, "%s: null colour table", fn);
+    memset(out, 0, sizeof(*out));
+    out->n = ncolors;
+    for (int k = 0; k < ncolors; ++k) {
+        const uint8_t* c = colors + (i64)k * C;
+        out->key[k] = C == 1 ? c[0] : (u32)c[0] | ((u32)c[1] << 8) | ((u32)c[2] << 16);
+        PB3D_REQUIRE(out->key[k] != 0, "%s: colour %d is black / label 0 (the empty voxel)", fn, k);
+    }
+    return PB3D_OK;
+}
+
+Walk make_walk(const uint8_t* d_grid, i64 A0, i64 A1, i64 A2, int C) {
+    Walk w;
+    w.grid = d_grid; w.A0 = A0; w.A1 = A1; w.A2 = A2;
+    w.ngx = (A2 + 3) / 4;
+    w.nitems = w.ngx * A1 * ((A0 + kChunk - 1) / kChunk);
+    w.vec = (A2 % 4 == 0) && ((((uintptr_t)d_grid) & 3u) == 0);
+    (void)C;
+    return w;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pb3d_grid_depth_buffer_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64_t A1, int64_t A2, int C, const double R[9],
+                               const double cam[3], double f, double cx, double cy, const int prec[4], int Himg, int Wimg, float* d_zbuf) {
+    PB3D_TRY(grid_args("pb3d_grid_depth_buffer", d_grid, A0, A1, A2, C));
+    PB3D_REQUIRE(R && cam && prec && Himg >= 0 && Wimg >= 0, "pb3d_grid_depth_buffer: bad argument");
+    PB3D_REQUIRE(ctx, "pb3d_grid_depth_buffer: null context");
+    const i64 npix = (i64)Himg * Wimg;
+    if (npix == 0) return PB3D_OK;
+    PB3D_REQUIRE(d_zbuf, "pb3d_grid_depth_buffer: null buffer");
+    ProjParams P;
+    PB3D_TRY(fill_proj(&P, 0, R, cam, f, cx, cy, prec, Himg, Wimg));
+    PB3D_HIP(hipMemsetD32Async((hipDeviceptr_t)d_zbuf, 0x7f800000, (size_t)npix, ctx->stream));   // +inf
+    const Walk w = make_walk(d_grid, A0, A1, A2, C);
+    if (w.nitems == 0) return PB3D_OK;
+    const unsigned blocks = (unsigned)((w.nitems + 255) / 256);
+    if (C == 1) hipLaunchKernelGGL(k_grid_depth<1>, dim3(blocks), dim3(256), 0, ctx->stream, w, P, (u32*)d_zbuf);
+    else hipLaunchKernelGGL(k_grid_depth<3>, dim3(blocks), dim3(256), 0, ctx->stream, w, P, (u32*)d_zbuf);
+    PB3D_CHECK_LAUNCH();
+    return PB3D_OK;
+}
+
+int pb3d_grid_visible_bits_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64_t A1, int64_t A2, int C, const uint8_t* colors,
+                               int ncolors, const double R[9], const double cam[3], double f, double cx, double cy, const int prec[4],
+                               const float* d_zbuf, int zH, int zW, int Himg, int Wimg, double eps, int eps_f32, uint32_t* d_bits) {
+    PB3D_TRY(grid_args("pb3d_grid_visible_bits", d_grid, A0, A1, A2, C));
+    Colours cols;
+    PB3D_TRY(colour_args("pb3d_grid_visible_bits", colors, ncolors, C, &cols));
+    PB3D_REQUIRE(R && cam && prec && Himg >= 0 && Wimg >= 0, "pb3d_grid_visible_bits: bad argument");
+    PB3D_REQUIRE(zH == Himg && zW == Wimg, "pb3d_grid_visible_bits: zbuf is %dx%d, the image %dx%d", zH, zW, Himg, Wimg);
+    PB3D_REQUIRE(ctx, "pb3d_grid_visible_bits: null context");
+    const i64 npix = (i64)Himg * Wimg;
+    if (npix == 0) return PB3D_OK;
+    PB3D_REQUIRE(d_zbuf && d_bits, "pb3d_grid_visible_bits: null buffer");
+    ProjParams P;
+    PB3D_TRY(fill_proj(&P, 0, R, cam, f, cx, cy, prec, Himg, Wimg));
+    PB3D_HIP(hipMemsetAsync(d_bits, 0, (size_t)npix * 4, ctx->stream));
+    const Walk w = make_walk(d_grid, A0, A1, A2, C);
+    if (w.nitems == 0) return PB3D_OK;
+    const unsigned blocks = (unsigned)((w.nitems + 255) / 256);
+    if (C == 1) hipLaunchKernelGGL(k_grid_visible_bits<1>, dim3(blocks), dim3(256), 0, ctx->stream, w, P, d_zbuf, eps, eps_f32, cols, d_bits);
+    else hipLaunchKernelGGL(k_grid_visible_bits<3>, dim3(blocks), dim3(256), 0, ctx->stream, w, P, d_zbuf, eps, eps_f32, cols, d_bits);
+    PB3D_CHECK_LAUNCH();
+    return PB3D_OK;
+}
+
+int pb3d_points_visible_bits_dev(pb3d_ctx* ctx, const void* const* d_lists, const int64_t* counts, int nlists, int pts_type, const double R[9],
+                                 const double cam[3], double f, double cx, double cy, const int prec[4], const float* d_zbuf, int zH, int zW,
+                                 int Himg, int Wimg, double eps, int eps_f32, uint32_t* d_bits) {
+    PB3D_REQUIRE(nlists >= 0 && nlists <= kMaxColours, "pb3d_points_visible_bits: at most %d point lists, got %d", kMaxColours, nlists);
+    PB3D_REQUIRE(pts_type >= 0 && pts_type <= 2, "pb3d_points_visible_bits: pts_type is 0 (float32), 1 (float64) or 2 (int64)");
+    PB3D_REQUIRE(nlists == 0 || (d_lists && counts), "pb3d_points_visible_bits: null list table");
+    PB3D_REQUIRE(R && cam && prec && Himg >= 0 && Wimg >= 0, "pb3d_points_visible_bits: bad argument");
+    PB3D_REQUIRE(zH == Himg && zW == Wimg, "pb3d_points_visible_bits: zbuf is %dx%d, the image %dx%d", zH, zW, Himg, Wimg);
+    Lists L;
+    memset(&L, 0, sizeof(L));
+    L.type = pts_type;
+    i64 nmax = 0;
+    for (int k = 0; k < nlists; ++k) {
+        PB3D_REQUIRE(counts[k] >= 0 && (counts[k] == 0 || d_lists[k]), "pb3d_points_visible_bits: bad list %d", k);
+        L.p[k] = d_lists[k]; L.n[k] = counts[k];
+        nmax = counts[k] > nmax ? counts[k] : nmax;
+    }
+    PB3D_REQUIRE(ctx, "pb3d_points_visible_bits: null context");
+    const i64 npix = (i64)Himg * Wimg;
+    if (npix == 0) return PB3D_OK;
+    PB3D_REQUIRE(d_zbuf && d_bits, "pb3d_points_visible_bits: null buffer");
+    ProjParams P;
+    PB3D_TRY(fill_proj(&P, pts_type == 1, R, cam, f, cx, cy, prec, Himg, Wimg));
+    PB3D_HIP(hipMemsetAsync(d_bits, 0, (size_t)npix * 4, ctx->stream));
+    if (nmax == 0) return PB3D_OK;
+    hipLaunchKernelGGL(k_points_visible_bits, dim3(pb3d_batch_blocks(ctx, nmax, 256, nlists, 8), nlists), dim3(256), 0, ctx->stream, L, P,
+                       d_zbuf, eps, eps_f32, d_bits);
+    PB3D_CHECK_LAUNCH();
+    return PB3D_OK;
+}
+
+int pb3d_color_presence_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t nvox, int C, uint32_t* d_bitmap, const uint8_t* colors, int ncolors,
+                            int64_t* d_present) {
+    PB3D_TRY(grid_args("pb3d_color_presence", d_grid, nvox, 1, 1, C));
+    Colours cols;
+    PB3D_TRY(colour_args("pb3d_color_presence", colors, ncolors, C, &cols));
+    PB3D_REQUIRE(ctx, "pb3d_color_presence: null context");
+    PB3D_REQUIRE(d_bitmap && (ncolors == 0 || d_present), "pb3d_color_presence: null buffer");
+    PB3D_HIP(hipMemsetAsync(d_bitmap, 0, PB3D_PRESENCE_BYTES, ctx->stream));
+    if (nvox > 0) {
+        const int vec = (nvox % 4 == 0) && ((((uintptr_t)d_grid) & 3u) == 0);
+        const unsigned blocks = pb3d_stream_blocks(ctx, (nvox + 3) / 4, 256, 8);
+        if (C == 1) hipLaunchKernelGGL(k_color_presence<1>, dim3(blocks), dim3(256), 0, ctx->stream, d_grid, nvox, vec, d_bitmap);
+        else hipLaunchKernelGGL(k_color_presence<3>, dim3(blocks), dim3(256), 0, ctx->stream, d_grid, nvox, vec, d_bitmap);
+        PB3D_CHECK_LAUNCH();
+    }
+    if (d_present) {
+        hipLaunchKernelGGL(k_presence_probe, dim3(1), dim3(1), 0, ctx->stream, (const u32*)d_bitmap, cols, (i64*)d_present);
+        PB3D_CHECK_LAUNCH();
+    }
+    return PB3D_OK;
+}
+
+int pb3d_mask_bits_dev(pb3d_ctx* ctx, const uint8_t* d_mask, int64_t npix, const uint8_t* colors, int ncolors, const uint32_t* d_bitmap,
+                       uint32_t* d_bits) {
+    Colours cols;
+    PB3D_TRY(colour_args("pb3d_mask_bits", colors, ncolors, 3, &cols));
+    PB3D_REQUIRE(npix >= 0, "pb3d_mask_bits: bad argument");
+    PB3D_REQUIRE(ctx, "pb3d_mask_bits: null context");
+    if (npix == 0) return PB3D_OK;
+    PB3D_REQUIRE(d_mask && d_bits, "pb3d_mask_bits: null buffer");
+    hipLaunchKernelGGL(k_mask_bits, dim3(pb3d_stream_blocks(ctx, npix, 256, 8)), dim3(256), 0, ctx->stream, d_mask, npix, cols,
+                       (const u32*)d_bitmap, d_bits);
+    PB3D_CHECK_LAUNCH();
+    return PB3D_OK;
+}
+
+int pb3d_iou_rows_dev(pb3d_ctx* ctx, const pb3d_iou_row* rows, int nrows, int64_t npix, int64_t* d_counts) {
+    PB3D_REQUIRE(nrows >= 0 && nrows <= kMaxRows, "pb3d_iou_rows: at most %d rows, got %d", kMaxRows, nrows);
+    PB3D_REQUIRE(npix >= 0 && (nrows == 0 || rows), "pb3d_iou_rows: bad argument");
+    PB3D_REQUIRE(ctx, "pb3d_iou_rows: null context");
+    if (nrows == 0) return PB3D_OK;
+    PB3D_REQUIRE(d_counts, "pb3d_iou_rows: null buffer");
+    Rows R;
+    memset(&R, 0, sizeof(R));
+    R.n = nrows;
+    for (int k = 0; k < nrows; ++k) R.r[k] = rows[k];
+    PB3D_HIP(hipMemsetAsync(d_counts, 0, (size_t)nrows * 2 * sizeof(int64_t), ctx->stream));
+    if (npix == 0) return PB3D_OK;
+    hipLaunchKernelGGL(k_iou_rows, dim3(pb3d_stream_blocks(ctx, npix, 256, 4)), dim3(256), 0, ctx->stream, R, npix,
+                       (unsigned long long*)d_counts);
+    PB3D_CHECK_LAUNCH();
+    return PB3D_OK;
+}
+
+}  // extern "C"

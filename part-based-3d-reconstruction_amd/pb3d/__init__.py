@@ -13,7 +13,9 @@ from .labels import (Palette, extrude_from_surface_labels, get_voxel_points_by_p
 from ._hostmem import set_result_pool  # noqa: F401
 from .camera_estimation import (CameraObjective, compute_partwise_iou, coordinate_descent, powell_search, projection_iou_by_part,  # noqa: F401
                                 random_search)
-from .eval_helpers_intra import compute_global_depth_buffer, project_part_visible  # noqa: F401
+from .eval_helpers_intra import (color_presence, compute_binary_gt, compute_global_depth_buffer, grid_depth_buffer, grid_visible_bits,  # noqa: F401
+                                 points_visible_bits, project_part_visible, run_minaret_iou_evaluation, run_minaret_kp_evaluation,
+                                 run_part_minaret_binary_iou)
 from .minarets import (extract_minaret_kps_for_view, extract_minaret_masks_by_label, extract_minaret_voxels_by_label,  # noqa: F401
                        extract_top_bottom_image_points, extract_top_bottom_voxel_points)
 from .mask_utils import load_and_prepare_masks, load_mask, mask_parts_from_image  # noqa: F401
@@ -35,7 +37,10 @@ _PATCH = {
     "projection_utils": ["project_colored_voxels"],
     "camera_estimation": ["compute_partwise_iou", "extract_minaret_voxels_by_label", "extract_minaret_masks_by_label",
                           "extract_top_bottom_voxel_points", "extract_top_bottom_image_points", "extract_minaret_kps_for_view"],
-    "eval_helpers_intra": ["compute_global_depth_buffer", "project_part_visible"],
+    # load_mask is left out: utils.mask_utils has a load_mask of its own (another signature) and install() rebinds by name
+    "eval_helpers_intra": ["compute_global_depth_buffer", "project_part_visible", "load_voxel_grid", "resize_mask_to_voxel_grid",
+                           "load_camera_json", "project_keypoints", "compute_binary_gt", "_iou_bool", "run_minaret_kp_evaluation",
+                           "run_minaret_iou_evaluation", "run_part_minaret_binary_iou"],
 }
 
 
@@ -62,6 +67,9 @@ def install(utils_pkg=None):
             if n in mod.__dict__ and mod.__dict__[n] is not fn:
                 mod.__dict__[n] = fn
                 patched.append((modname, n))
+    ev = sys.modules.get(utils_pkg.__name__ + ".eval_helpers_intra")
+    if ev is not None:      # visualize=True of the notebook-4 evaluations calls the reference's own plotting functions
+        here.eval_helpers_intra._REF["module"] = ev
     vis = sys.modules.get(utils_pkg.__name__ + ".visualization")
     if vis is not None and hasattr(vis, "plot_voxel"):
         here.voxel_carving_utils.plot_voxel = vis.plot_voxel

@@ -126,7 +126,22 @@ _SIGNATURES = {
     "pb3d_project_keys_dev": [vp, vp, C.c_int, vp, i64, i64, dblp, dblp, C.c_double, C.c_double, C.c_double, intp, C.c_int, C.c_int, vp],
     "pb3d_project_resolve_keys_dev": [vp, vp, C.c_int, C.c_int, vp],
     "pb3d_allreduce_max_u64_dev": [vp, vp, C.c_size_t],
+    "pb3d_grid_depth_buffer_dev": [vp, vp, i64, i64, i64, C.c_int, dblp, dblp, C.c_double, C.c_double, C.c_double, intp, C.c_int, C.c_int, vp],
+    "pb3d_grid_visible_bits_dev": [vp, vp, i64, i64, i64, C.c_int, u8p, C.c_int, dblp, dblp, C.c_double, C.c_double, C.c_double, intp, vp,
+                                   C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, vp],
+    "pb3d_points_visible_bits_dev": [vp, C.POINTER(vp), i64p, C.c_int, C.c_int, dblp, dblp, C.c_double, C.c_double, C.c_double, intp, vp,
+                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, vp],
+    "pb3d_color_presence_dev": [vp, vp, i64, C.c_int, vp, u8p, C.c_int, vp],
+    "pb3d_mask_bits_dev": [vp, vp, i64, u8p, C.c_int, vp, vp],
+    "pb3d_iou_rows_dev": [vp, C.c_void_p, C.c_int, i64, vp],
 }
+class IouRow(C.Structure):
+    """pb3d_iou_row (include/pb3d.h)"""
+    _fields_ = [("pred", vp), ("gt", vp), ("gate", vp), ("pred_bits", C.c_uint32), ("gt_bits", C.c_uint32), ("gate_bits", C.c_uint32)]
+
+
+PRESENCE_BYTES = 1 << 21    # PB3D_PRESENCE_BYTES: one bit per 24-bit colour
+
 _RESTYPES = {"pb3d_dtype_bytes": C.c_size_t, "pb3d_sync_count": C.c_int64, "pb3d_last_error": C.c_char_p, "pb3d_destroy": None, "pb3d_event_destroy": None}
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -39,6 +39,12 @@ def resize_to_max(img, max_dim, interpolation="nearest"):
     nw, nh = int(w * s), int(h * s)
     if nw <= 0 or nh <= 0:
         raise ValueError("resize to an empty image")
+    return resize_nearest(img, nw, nh)
+
+
+def resize_nearest(img, nw, nh):
+    """cv2.resize(img, (nw, nh), interpolation=cv2.INTER_NEAREST)"""
+    h, w = img.shape[:2]
     # OpenCV's INTER_NEAREST index rule, with its own arithmetic (imgproc/resize.cpp): inv_scale = (double)dst / src;
     # ifx = 1.0 / inv_scale; sx = min(cvFloor(x * ifx), src - 1).  (x * (src / dst) differs from it by an ulp for some size pairs.)
     ifx = 1.0 / (nw / float(w)); ify = 1.0 / (nh / float(h))

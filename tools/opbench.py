@@ -247,6 +247,8 @@ def main():
         d_pts.free(); d_pc.free()
     if "MN" in ops:
         minarets(a.reps, res)
+    if "N6" in ops:
+        intra_eval(a.reps, res)
     if d_col is not None:
         d_col.free()
     return res
@@ -316,6 +318,104 @@ def minarets(reps, res):
         print(json.dumps(r), flush=True)
         res.append(r)
         for b in (d_g, d_lab, d_xyz, d_rows):
+            b.free()
+
+
+def intra_eval(reps, res):
+    """Notebook 4's resident evaluation of one monument and camera (reference utils/eval_helpers_intra.py:605-738): (a) grid z-buffer,
+    (b) visible-part bits (7 colours + any), (d) colour set + ground-truth bits, (e) the 19 IoU rows -- each timed alone, then the whole
+    monument (two z-buffers, three bit passes, d, e) -- beside the point path it replaces: count + fill of the occupied points +
+    pb3d_depth_buffer_dev, and count + fill + pb3d_visible_mask_dev per colour and for all occupied voxels.  Itimad's deformed grid
+    (512 x 381 x 512, the largest stored) under its final front and drone cameras, and a 1024^3 synthetic semantic grid."""
+    from pb3d import eval_helpers_intra as ev
+    lib, L = pb3d._lib.load(), pb3d._lib
+    g = os.path.join(ROOT, "tests", "golden")
+    PC = pb3d.PART_COLORS
+    real = ev.load_voxel_grid(os.path.join(g, "stored_Itimad_deformed_voxel_grid.npz"))
+    S = 1024
+    pal = [tuple(int(v) for v in c) for c in dev.synth_palette16() if c.any()][:7]
+    cases = []
+    for view in ("front", "drone"):
+        cam = ev.load_camera_json(os.path.join(g, "stored_Itimad_camera_params_final.json"), view)
+        mask = ev.resize_mask_to_voxel_grid(ev.load_mask(os.path.join(g, f"data_Itimad_{view}_mask.png")), real)
+        cases.append((f"Itimad deformed {'x'.join(map(str, real.shape[:3]))}, {view}", real, cam, mask,
+                      [PC[p] for p in ev.PARTS] + [PC["front_minarets"], PC["back_minarets"]]))
+    rng = np.random.default_rng(0)
+    smask = np.array(pal, np.uint8)[rng.integers(0, len(pal), (S // 8, S // 8))].repeat(8, 0).repeat(8, 1)
+    for view, cp in (("front", [S / 2, S / 2, -1.5 * S]), ("drone", [S / 2, 2.2 * S, -1.2 * S])):
+        cam = {"cam_pos": np.array(cp, np.float32), "target": np.array([S / 2, S / 2, S / 2], np.float32), "f": 1.0 * S, "cx": S / 2,
+               "cy": S / 2}
+        cases.append((f"synthetic {S}^3, {view}", None, cam, smask, pal))
+    for name, grid, cam, mask, colours in cases:
+        if grid is None:
+            d_g = dev.DeviceBuffer(S ** 3 * 3)
+            dev.synth_sem(0, S, S, S, 7, d_g)
+            shape = (S, S, S, 3)
+        else:
+            d_g = dev.from_numpy(grid); shape = grid.shape
+        H, W = mask.shape[:2]
+        d_m = dev.from_numpy(np.ascontiguousarray(mask[:, :, :3]))
+        z1, z2 = dev.DeviceBuffer(H * W * 4), dev.DeviceBuffer(H * W * 4)
+        b1, b2, b3, gt = (dev.DeviceBuffer(H * W * 4) for _ in range(4))
+        bm, cnt = dev.DeviceBuffer(L.PRESENCE_BYTES), dev.DeviceBuffer(19 * 16 + 8)
+        rows = [(b1, 1 << (k % 5), gt, 1 << (k % 5), None, 0) for k in range(15)] + [(b1, 96, gt, 96, None, 0), (b3, 3, gt, 96, None, 0),
+                                                                                      (b1, 1 << 31, gt, 1 << 31, None, 0), (b2, 1 << 31, gt, 1 << 31, None, 0)]
+        a_ms = timeit(lambda: ev.depth_buffer_resident(d_g, shape, cam, H, W, out=z1), reps)
+        b_ms = timeit(lambda: ev.visible_bits_resident(d_g, shape, colours, cam, z1, (H, W), H, W, out=b1), reps)
+
+        def d_pass():
+            ev.presence_resident(d_g, shape, colours, cnt.at(19 * 16), out=bm)
+            ev.mask_bits_resident(d_m, H * W, colours, bm, out=gt)
+        d_ms = timeit(d_pass, reps)
+        e_ms = timeit(lambda: ev.iou_rows_resident(rows, H * W, cnt), reps)
+
+        def monument():
+            d_pass()
+            ev.depth_buffer_resident(d_g, shape, cam, H, W, out=z1)
+            ev.depth_buffer_resident(d_g, shape, cam, H, W, out=z2)
+            ev.visible_bits_resident(d_g, shape, colours, cam, z1, (H, W), H, W, out=b1)
+            ev.visible_bits_resident(d_g, shape, colours, cam, z2, (H, W), H, W, out=b2)
+            ev.visible_bits_resident(d_g, shape, colours[5:], cam, z2, (H, W), H, W, out=b3)
+            ev.iou_rows_resident(rows, H * W, cnt)
+            cnt.download((19 * 2 + 1,), np.int64)
+        mon_ms = timeit(monument, reps)
+        # the point path: every pass extracts its points on the device first (count: one host round trip)
+        _, _, R, cpos, prec = pb3d.projection_utils.camera_args(np.zeros((1, 3), np.float32), cam["cam_pos"], cam["target"], cam["f"],
+                                                               cam["cx"], cam["cy"])
+        n0 = C.c_int64(0)
+        L.check(lib.pb3d_points_count_dev(L.ctx(), C.c_void_p(d_g.ptr), *shape[:3], 3, None, 0, 1, C.byref(n0)))
+        d_pts, d_pc, d_vm = dev.DeviceBuffer(max(1, n0.value) * 12), dev.DeviceBuffer(max(1, n0.value) * 3), dev.DeviceBuffer(H * W)
+
+        def extract(col):
+            n = C.c_int64(0)
+            tab = None if col is None else np.ascontiguousarray(np.array(col, np.uint8).reshape(1, 3))
+            pc = None if tab is None else L.p_u8(tab)
+            L.check(lib.pb3d_points_count_dev(L.ctx(), C.c_void_p(d_g.ptr), *shape[:3], 3, pc, 0 if tab is None else 1, 1, C.byref(n)))
+            assert n.value * 12 <= d_pts.nbytes, "point buffer too small"
+            L.check(lib.pb3d_points_fill_dev(L.ctx(), C.c_void_p(d_g.ptr), *shape[:3], 3, pc, 0 if tab is None else 1, 1, n.value,
+                                             C.c_void_p(d_pts.ptr), C.c_void_p(d_pc.ptr)))
+            return n.value
+
+        def point_zbuf():
+            n = extract(None)
+            L.check(lib.pb3d_depth_buffer_dev(L.ctx(), C.c_void_p(d_pts.ptr), 0, n, L.p_dbl(R), L.p_dbl(cpos), float(cam["f"]), float(cam["cx"]),
+                                              float(cam["cy"]), prec, H, W, C.c_void_p(z1.ptr)))
+
+        def point_bits():
+            for col in list(colours) + [None]:
+                n = extract(col)
+                L.check(lib.pb3d_visible_mask_dev(L.ctx(), C.c_void_p(d_pts.ptr), 0, n, L.p_dbl(R), L.p_dbl(cpos), float(cam["f"]),
+                                                  float(cam["cx"]), float(cam["cy"]), prec, C.c_void_p(z1.ptr), H, W, 1e-3, 1, C.c_void_p(d_vm.ptr)))
+        pa_ms = timeit(point_zbuf, reps)
+        pb_ms = timeit(point_bits, reps)
+        nocc = extract(None)
+        r = {"op": "N6", "name": f"notebook-4 evaluation, {name}", "shape": list(shape[:3]), "image": [H, W], "occupied": nocc,
+             "colours": len(colours), "a_grid_zbuf_ms": round(a_ms, 4), "b_visible_bits_ms": round(b_ms, 4),
+             "d_presence_and_gt_ms": round(d_ms, 4), "e_iou_rows_ms": round(e_ms, 4), "monument_resident_ms": round(mon_ms, 4),
+             "point_path_zbuf_ms": round(pa_ms, 4), "point_path_bits_ms": round(pb_ms, 4)}
+        print(json.dumps(r), flush=True)
+        res.append(r)
+        for b in (d_g, d_m, z1, z2, b1, b2, b3, gt, bm, cnt, d_pts, d_pc, d_vm):
             b.free()
 
 
