@@ -251,6 +251,27 @@ int pb3d_mask_bits_dev(pb3d_ctx* ctx, const uint8_t* d_mask, int64_t npix, const
                        uint32_t* d_bits);
 int pb3d_iou_rows_dev(pb3d_ctx* ctx, const pb3d_iou_row* rows, int nrows, int64_t npix, int64_t* d_counts);
 
+/* ---- inter-method point-cloud metrics (row I5), reference utils/eval_helpers.py ----------------------------------------------------
+ * Point lists are (n, 3) rows of float32 (*_f64 = 0) or float64 (*_f64 = 1); everything is computed in float64 (float32 is widened, as
+ * cKDTree and NearestNeighbors widen it).  Counts are limited to 2^31 - 1 points per list.
+ * points_bounds: d_out[0..3) = min, d_out[3..6) = max over the n >= 1 points, exact (all_pts.min(0) / .max(0), :84-85).
+ * nn_dist: d_out[i] = the k-th smallest (k = 1 or 2, with multiplicity) of sqrt((dx*dx + dy*dy) + dz*dz) from query i to the nr
+ *   reference points, bit for bit what cKDTree(r).query(q, k)[0][:, k - 1] and NearestNeighbors(k).fit(r).kneighbors(q) return
+ *   (chamfer_distance :38-42, fscore_with_threshold :53-59, compute_nn_stats :120-123 with k = 2 on the set itself, so a point's own
+ *   copy counts at 0, compute_nn_distances :223-227).  nr >= k when nq > 0.  Builds a uniform cell index of the reference set in
+ *   scratch and waits once for the set's bounding box; the query itself is enqueued.
+ * nn_grid_shape: the cells per axis of the index nn_dist builds for nr reference points in this box (no device work).
+ * voxel_iou_counts: the occupancy, dilation and counts of voxel_iou (:83-111).  The host computes bounds_min, step (float32 values
+ *   when calc_f32: both lists float32, NumPy's float32 arithmetic) and iters with the reference's expressions; the device sets voxel
+ *   clip(int((p - bounds_min) / step), 0, resolution - 1) of every point (a NaN or out-of-range quotient gives voxel 0, as NumPy's
+ *   cast does on x86), dilates both grids iters times with the 6-neighbour cross and a zero border (binary_dilation) and writes
+ *   d_counts[0] = #(A & B), d_counts[1] = #(A | B).  1 <= resolution <= 2048, iters >= 0 (0: no dilation). */
+int pb3d_points_bounds_dev(pb3d_ctx* ctx, const void* d_pts, int pts_f64, int64_t n, double* d_out);
+int pb3d_nn_dist_dev(pb3d_ctx* ctx, const void* d_q, int q_f64, int64_t nq, const void* d_r, int r_f64, int64_t nr, int k, double* d_out);
+int pb3d_nn_grid_shape(const double bounds[6], int64_t nr, int64_t cells[3]);
+int pb3d_voxel_iou_counts_dev(pb3d_ctx* ctx, const void* d_a, int a_f64, int64_t na, const void* d_b, int b_f64, int64_t nb,
+                              const double bounds_min[3], double step, int calc_f32, int resolution, int iters, int64_t* d_counts);
+
 /* ---- compute_partwise_iou, reference utils/camera_estimation.py:770-787 -------------------
  * per colour k: inter[k] = #(a==c & b==c), uni[k] = #(a==c | b==c) over npix RGB pixels. */
 int pb3d_partwise_iou_dev(pb3d_ctx* ctx, const uint8_t* d_a, const uint8_t* d_b, int64_t npix,

@@ -1,0 +1,502 @@
+// I5: the inter-method point-cloud metrics (reference utils/eval_helpers.py) -- exact nearest-neighbour distances and voxel_iou counts.
+//
+// Every metric of eval_helpers.py rests on one primitive: for each point of A, the distance to its nearest (k = 1) or second-nearest
+// (k = 2) point of B.  The reference takes it from cKDTree.query / NearestNeighbors.kneighbors, which on float64 (float32 is widened
+// first) return exactly sqrt((dx*dx + dy*dy) + dz*dz) of the nearest point, with no FMA.  Ties and which neighbour was picked never
+// reach a metric, so a search that finds the minimum of that expression is bit-exact.  The Makefile passes -ffp-contract=off: the
+// squared distance is three separate multiplies and two adds, in this order, and one correctly rounded sqrt at the end (__dsqrt_rn).
+//
+// Index: a uniform grid of cells over the reference set's bounding box (exact min / max, k_bounds_*), cell size
+// chosen on the host from the box and the point count for about kPerCell points per cell; the points are binned by a count pass, the
+// exclusive scan of csrc/points.hip and a scatter into cell-sorted SoA float64 arrays (order within a cell is free: atomics).
+// Query: the queries are binned the same way and processed in cell order (the lanes of a wave walk the same cells); each searches
+// Chebyshev rings of growing radius around its cell, clamped to the grid, pruning (x) planes and z-runs of cells whose box is farther
+// than the current k-th best, and stops once the lower bound on the distance to every cell not yet visited exceeds the k-th best.
+// The bound counts only faces of the visited box that still have cells beyond them, adds the query's distance to the grid box along
+// the other axes (queries far outside the box), and is shrunk by a relative margin, so a point that rounding put in a neighbouring
+// cell can never be missed; the final comparison is strict with a margin, never an exact tie.
+#include <cmath>
+
+#include "pb3d_internal.h"
+
+namespace {
+
+constexpr int kBoundsBlocks = 512;
+constexpr double kPerCell = 2.0;             // points per cell the grid aims at
+constexpr i64 kMaxCells = 1ll << 25;         // cap on the cell count (index memory: 12 bytes per cell)
+constexpr i64 kMaxPoints = (1ll << 31) - 1;  // sorted positions and query slots are 32-bit
+constexpr int kMaxResolution = 2048;         // voxel_iou: two (res^3 / 8)-byte bit grids plus a ping-pong copy
+constexpr double kMargin = 1e-12;            // relative margin of every pruning comparison (rounding errors are ~1e-15)
+
+template <bool F64>
+__device__ __forceinline__ void load3(const void* p, i64 i, double* x, double* y, double* z) {
+    if (F64) {
+        const double* d = (const double*)p + 3 * i;
+        *x = d[0]; *y = d[1]; *z = d[2];
+    } else {
+        const float* f = (const float*)p + 3 * i;
+        *x = (double)f[0]; *y = (double)f[1]; *z = (double)f[2];
+    }
+}
+
+// ---- exact bounding box: per-block min / max, then one block over the partials -> out[0..3) = min, out[3..6) = max -------------------
+template <bool F64>
+__global__ __launch_bounds__(256) void k_bounds_partial(const void* __restrict__ pts, i64 n, double* __restrict__ part) {
+    __shared__ double red[6][4];
+    double m[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (i64)gridDim.x * 256) {
+        double x, y, z;
+        load3<F64>(pts, i, &x, &y, &z);
+        m[0] = fmin(m[0], x); m[1] = fmin(m[1], y); m[2] = fmin(m[2], z);
+        m[3] = fmax(m[3], x); m[4] = fmax(m[4], y); m[5] = fmax(m[5], z);
+    }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+        double v = m[c];
+        for (int off = 32; off > 0; off >>= 1) {
+            const double o = __shfl_xor(v, off);
+            v = c < 3 ? fmin(v, o) : fmax(v, o);
+        }
+        if (lane == 0) red[c][w] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        const int c = threadIdx.x;
+        double v = red[c][0];
+        for (int k = 1; k < 4; ++k) v = c < 3 ? fmin(v, red[c][k]) : fmax(v, red[c][k]);
+        part[(i64)blockIdx.x * 6 + c] = v;
+    }
+}
+
+__global__ __launch_bounds__(64) void k_bounds_final(const double* __restrict__ part, int nblocks, double* __restrict__ out) {
+    if (threadIdx.x >= 6) return;
+    const int c = threadIdx.x;
+    double v = c < 3 ? INFINITY : -INFINITY;
+    for (int b = 0; b < nblocks; ++b) v = c < 3 ? fmin(v, part[b * 6 + c]) : fmax(v, part[b * 6 + c]);
+    out[c] = v;
+}
+
+// d_out: 6 doubles; scratch slot 41 holds the partials
+int launch_bounds(pb3d_ctx* ctx, const void* d_pts, int f64, i64 n, double* d_out) {
+    const unsigned need = pb3d_stream_blocks(ctx, n, 256, 2);
+    const unsigned nb = need < (unsigned)kBoundsBlocks ? need : (unsigned)kBoundsBlocks;
+    void* part;
+    PB3D_TRY(pb3d_scratch(ctx, 41, (size_t)kBoundsBlocks * 6 * sizeof(double), &part));
+    if (f64) hipLaunchKernelGGL(k_bounds_partial<true>, dim3(nb), dim3(256), 0, ctx->stream, d_pts, n, (double*)part);
+    else hipLaunchKernelGGL(k_bounds_partial<false>, dim3(nb), dim3(256), 0, ctx->stream, d_pts, n, (double*)part);
+    PB3D_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_bounds_final, dim3(1), dim3(64), 0, ctx->stream, (const double*)part, (int)nb, d_out);
+    PB3D_CHECK_LAUNCH();
+    return PB3D_OK;
+}
+
+// ---- the cell grid ------------------------------------------------------------------------------------------------------------------
+struct Grid {
+    double lo[3], hi[3];      // the reference set's exact bounding box
+    double inv[3], h[3];      // cells per unit length (0 on a one-cell axis) and cell width
+    int n[3];                 // cells per axis
+    i64 ncells;
+};
+
+// cell of a coordinate: floor((v - lo) * inv) clamped to [0, n - 1] (NaN -> 0); points and queries use the same function
+__device__ __forceinline__ int cell_of(const Grid& g, int a, double v) {
+    const double t = fmin(fmax(floor((v - g.lo[a]) * g.inv[a]), 0.0), (double)(g.n[a] - 1));
+    return (int)t;
+}
+__device__ __forceinline__ i64 cell_index(const Grid& g, int cx, int cy, int cz) { return ((i64)cx * g.n[1] + cy) * g.n[2] + cz; }
+
+// Cell size for about kPerCell points per cell: h^d = (product of the d extents) / (n / kPerCell), computed in logs.  An axis whose
+// extent is below h (zero extent included) gets one cell and leaves the product; the cell count is capped at kMaxCells.
+Grid make_grid(const double b[6], i64 n) {
+    Grid g;
+    bool flat[3];
+    for (int a = 0; a < 3; ++a) {
+        g.lo[a] = b[a];
+        g.hi[a] = b[3 + a];
+        flat[a] = !(b[3 + a] - b[a] > 0.0) || !std::isfinite(b[3 + a] - b[a]);
+    }
+    const double target = std::fmax(1.0, (double)n / kPerCell);
+    double h = 0.0;
+    for (int it = 0; it < 3; ++it) {
+        int d = 0;
+        double lsum = 0.0;
+        for (int a = 0; a < 3; ++a)
+            if (!flat[a]) { ++d; lsum += std::log(b[3 + a] - b[a]); }
+        if (d == 0) break;
+        h = std::exp((lsum - std::log(target)) / d);
+        bool changed = false;
+        for (int a = 0; a < 3; ++a)
+            if (!flat[a] && b[3 + a] - b[a] < h) { flat[a] = true; changed = true; }
+        if (!changed) break;
+    }
+    for (;;) {
+        i64 total = 1;
+        for (int a = 0; a < 3; ++a) {
+            double na = flat[a] ? 1.0 : std::ceil((b[3 + a] - b[a]) / h);
+            na = std::fmin(std::fmax(na, 1.0), (double)kMaxCells);
+            g.n[a] = (int)na;
+            total *= g.n[a];
+            if (total > kMaxCells) total = kMaxCells + 1;
+        }
+        if (total <= kMaxCells) { g.ncells = total; break; }
+        h *= 1.26;      // 2^(1/3): halves the cell count per step
+    }
+    for (int a = 0; a < 3; ++a) {
+        const double ext = b[3 + a] - b[a];
+        g.inv[a] = g.n[a] > 1 ? (double)g.n[a] / ext : 0.0;
+        g.h[a] = g.n[a] > 1 ? ext / (double)g.n[a] : 0.0;
+    }
+    return g;
+}
+
+template <bool F64>
+__global__ __launch_bounds__(256) void k_cell_count(const void* __restrict__ pts, i64 n, Grid g, u32* __restrict__ counts) {
+    for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (i64)gridDim.x * 256) {
+        double x, y, z;
+        load3<F64>(pts, i, &x, &y, &z);
+        atomicAdd(&counts[cell_index(g, cell_of(g, 0, x), cell_of(g, 1, y), cell_of(g, 2, z))], 1u);
+    }
+}
+
+// reference points -> cell-sorted SoA (xs, ys, zs); cursor: zeroed per-cell counters
+template <bool F64>
+__global__ __launch_bounds__(256) void k_cell_scatter_ref(const void* __restrict__ pts, i64 n, Grid g, const i64* __restrict__ start,
+                                                          u32* __restrict__ cursor, double* __restrict__ xs, double* __restrict__ ys,
+                                                          double* __restrict__ zs) {
+    for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (i64)gridDim.x * 256) {
+        double x, y, z;
+        load3<F64>(pts, i, &x, &y, &z);
+        const i64 c = cell_index(g, cell_of(g, 0, x), cell_of(g, 1, y), cell_of(g, 2, z));
+        const i64 pos = start[c] + atomicAdd(&cursor[c], 1u);
+        xs[pos] = x; ys[pos] = y; zs[pos] = z;
+    }
+}
+
+// query indices in cell order
+template <bool F64>
+__global__ __launch_bounds__(256) void k_cell_scatter_query(const void* __restrict__ pts, i64 n, Grid g, const i64* __restrict__ start,
+                                                            u32* __restrict__ cursor, u32* __restrict__ order) {
+    for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (i64)gridDim.x * 256) {
+        double x, y, z;
+        load3<F64>(pts, i, &x, &y, &z);
+        const i64 c = cell_index(g, cell_of(g, 0, x), cell_of(g, 1, y), cell_of(g, 2, z));
+        order[start[c] + atomicAdd(&cursor[c], 1u)] = (u32)i;
+    }
+}
+
+// Lower bound (margin applied) of |v - s| over s in the slab of cells [c0, c1] of axis a: the first and last cells reach the box's
+// exact faces, the others end at lo + c h.  tol: the query's margin on this axis.
+__device__ __forceinline__ double slab_gap(const Grid& g, int a, int c0, int c1, double v, double tol) {
+    const double s0 = c0 == 0 ? g.lo[a] : g.lo[a] + (double)c0 * g.h[a];
+    const double s1 = c1 == g.n[a] - 1 ? g.hi[a] : g.lo[a] + (double)(c1 + 1) * g.h[a];
+    const double d = fmax(s0 - v, v - s1) - tol;
+    return d > 0.0 ? d : 0.0;
+}
+
+// true when a lower bound lb (squared) proves that nothing there beats best (squared, as computed)
+__device__ __forceinline__ bool beyond(double lb, double best) { return lb * (1.0 - kMargin) > best; }
+
+template <int K>
+__device__ __forceinline__ void visit_run(const double* __restrict__ xs, const double* __restrict__ ys, const double* __restrict__ zs,
+                                          i64 s, i64 e, double qx, double qy, double qz, double* b1, double* b2) {
+    double m1 = *b1, m2 = *b2;
+    for (i64 p = s; p < e; ++p) {
+        const double dx = qx - xs[p], dy = qy - ys[p], dz = qz - zs[p];
+        const double d2 = (dx * dx + dy * dy) + dz * dz;
+        if (K == 1) {
+            m1 = fmin(m1, d2);
+        } else {                                    // (m1, m2) = the two smallest of (m1, m2, d2)
+            m2 = fmin(m2, fmax(m1, d2));
+            m1 = fmin(m1, d2);
+        }
+    }
+    *b1 = m1;
+    *b2 = m2;
+}
+
+template <int K, bool F64>
+__global__ __launch_bounds__(256) void k_nn_query(const void* __restrict__ q, i64 nq, const u32* __restrict__ order, Grid g,
+                                                  const i64* __restrict__ start, const double* __restrict__ xs, const double* __restrict__ ys,
+                                                  const double* __restrict__ zs, double* __restrict__ out) {
+    const i64 s = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (s >= nq) return;
+    const u32 qi = order[s];
+    double qv[3];
+    load3<F64>(q, qi, &qv[0], &qv[1], &qv[2]);
+    int c[3];
+    double tol[3], out2[3];     // per axis: margin, squared distance of the query to the box's extent on that axis
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        c[a] = cell_of(g, a, qv[a]);
+        tol[a] = 1e-12 * (fabs(g.lo[a]) + fabs(g.hi[a]) + fabs(qv[a]));
+        const double o = fmax(fmax(g.lo[a] - qv[a], qv[a] - g.hi[a]) - tol[a], 0.0);
+        out2[a] = o * o;
+    }
+    double b1 = INFINITY, b2 = INFINITY;
+    const int rmax = max(max(g.n[0], g.n[1]), g.n[2]);
+    for (int r = 0; r <= rmax; ++r) {
+        const int x0 = max(c[0] - r, 0), x1 = min(c[0] + r, g.n[0] - 1);
+        const int y0 = max(c[1] - r, 0), y1 = min(c[1] + r, g.n[1] - 1);
+        const int z0 = max(c[2] - r, 0), z1 = min(c[2] + r, g.n[2] - 1);
+        for (int i = x0; i <= x1; ++i) {
+            const double gx = slab_gap(g, 0, i, i, qv[0], tol[0]);
+            const double gx2 = gx * gx;
+            if (beyond(gx2, K == 1 ? b1 : b2)) continue;
+            const bool xe = i == c[0] - r || i == c[0] + r;
+            for (int j = y0; j <= y1; ++j) {
+                const double gy = slab_gap(g, 1, j, j, qv[1], tol[1]);
+                const double gxy = gx2 + gy * gy;
+                if (beyond(gxy, K == 1 ? b1 : b2)) continue;
+                const i64 row = cell_index(g, i, j, 0);
+                if (xe || j == c[1] - r || j == c[1] + r) {         // the whole z-run of the ring's face
+                    const double gz = slab_gap(g, 2, z0, z1, qv[2], tol[2]);
+                    if (beyond(gxy + gz * gz, K == 1 ? b1 : b2)) continue;
+                    visit_run<K>(xs, ys, zs, start[row + z0], start[row + z1 + 1], qv[0], qv[1], qv[2], &b1, &b2);
+                } else {                                            // inside the ring's (x, y) box: its two z-end cells only
+                    if (c[2] - r >= 0) {
+                        const double gz = slab_gap(g, 2, c[2] - r, c[2] - r, qv[2], tol[2]);
+                        if (!beyond(gxy + gz * gz, K == 1 ? b1 : b2))
+                            visit_run<K>(xs, ys, zs, start[row + c[2] - r], start[row + c[2] - r + 1], qv[0], qv[1], qv[2], &b1, &b2);
+                    }
+                    if (r > 0 && c[2] + r < g.n[2]) {
+                        const double gz = slab_gap(g, 2, c[2] + r, c[2] + r, qv[2], tol[2]);
+                        if (!beyond(gxy + gz * gz, K == 1 ? b1 : b2))
+                            visit_run<K>(xs, ys, zs, start[row + c[2] + r], start[row + c[2] + r + 1], qv[0], qv[1], qv[2], &b1, &b2);
+                    }
+                }
+            }
+        }
+        // lower bound over the cells not yet visited: per face of the visited box with cells beyond it, the gap to that face plus the
+        // query's distance to the grid box along the other two axes
+        const int lo_[3] = {x0, y0, z0}, hi_[3] = {x1, y1, z1};
+        double lb = INFINITY;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const double rest = out2[(a + 1) % 3] + out2[(a + 2) % 3];
+            if (hi_[a] < g.n[a] - 1) {
+                const double gap = fmax(g.lo[a] + (double)(hi_[a] + 1) * g.h[a] - qv[a] - tol[a], 0.0);
+                lb = fmin(lb, gap * gap + rest);
+            }
+            if (lo_[a] > 0) {
+                const double gap = fmax(qv[a] - (g.lo[a] + (double)lo_[a] * g.h[a]) - tol[a], 0.0);
+                lb = fmin(lb, gap * gap + rest);
+            }
+        }
+        if (lb == INFINITY || beyond(lb, K == 1 ? b1 : b2)) break;
+    }
+    out[qi] = __dsqrt_rn(K == 1 ? b1 : b2);
+}
+
+// ---- voxel_iou: occupancy bits, 6-neighbour dilation, intersection / union counts -------------------------------------------------
+// Bit grid of one cloud: word (x * res + y) * W + z / 32, bit z % 32, W = ceil(res / 32); bits at z >= res stay 0.
+struct Occ {
+    int res, W;
+    double lo[3];      // bounds_min (as float32 values when F32)
+    double step;
+};
+
+// ((p - bounds_min) / step).astype(int), clipped to [0, res - 1]: the cast of a NaN or out-of-range value gives INT64_MIN (x86
+// cvttsd2si, what NumPy's cast compiles to), i.e. 0 after the clip.
+__device__ __forceinline__ int occ_index(double t, int res) {
+    if (!(t >= -9223372036854775808.0 && t < 9223372036854775808.0)) return 0;
+    const i64 i = (i64)t;
+    return i < 0 ? 0 : (i > res - 1 ? res - 1 : (int)i);
+}
+
+template <bool PF64, bool F32>
+__global__ __launch_bounds__(256) void k_occ_bits(const void* __restrict__ pts, i64 n, Occ o, u32* __restrict__ bits) {
+    for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (i64)gridDim.x * 256) {
+        double v[3];
+        load3<PF64>(pts, i, &v[0], &v[1], &v[2]);
+        int idx[3];
+        for (int a = 0; a < 3; ++a) {
+            double t;
+            if (F32) t = (double)__fdiv_rn(__fsub_rn((float)v[a], (float)o.lo[a]), (float)o.step);   // NumPy float32 arithmetic
+            else t = (v[a] - o.lo[a]) / o.step;
+            idx[a] = occ_index(t, o.res);
+        }
+        atomicOr(&bits[((i64)idx[0] * o.res + idx[1]) * o.W + (idx[2] >> 5)], 1u << (idx[2] & 31));
+    }
+}
+
+// one binary_dilation pass with the 6-neighbour cross and a zero border, on `grids` bit grids stored one after the other
+__global__ __launch_bounds__(256) void k_dilate6(const u32* __restrict__ in, u32* __restrict__ out, int res, int W, i64 words, u32 lastmask) {
+    const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (i >= words) return;
+    const int w = (int)(i % W);
+    const i64 rowi = i / W;                     // grid * res^2 + x * res + y
+    const int y = (int)(rowi % res);
+    const int x = (int)((rowi / res) % res);
+    const u32 v = in[i];
+    u32 r = v | (v << 1) | (v >> 1);
+    if (w > 0) r |= in[i - 1] >> 31;
+    if (w < W - 1) r |= in[i + 1] << 31;
+    if (y > 0) r |= in[i - W];
+    if (y < res - 1) r |= in[i + W];
+    if (x > 0) r |= in[i - (i64)res * W];
+    if (x < res - 1) r |= in[i + (i64)res * W];
+    if (w == W - 1) r &= lastmask;
+    out[i] = r;
+}
+
+__global__ __launch_bounds__(256) void k_iou_count(const u32* __restrict__ a, const u32* __restrict__ b, i64 words,
+                                                   unsigned long long* __restrict__ counts) {
+    __shared__ unsigned long long red[2][4];
+    unsigned long long ci = 0, cu = 0;
+    for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < words; i += (i64)gridDim.x * 256) {
+        const u32 x = a[i], y = b[i];
+        ci += __popc(x & y);
+        cu += __popc(x | y);
+    }
+    for (int off = 32; off > 0; off >>= 1) { ci += __shfl_xor(ci, off); cu += __shfl_xor(cu, off); }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) { red[0][w] = ci; red[1][w] = cu; }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        const unsigned long long s = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
+        atomicAdd(&counts[threadIdx.x], s);
+    }
+}
+
+template <bool F32>
+int launch_occ(pb3d_ctx* ctx, const void* d_pts, int f64, i64 n, const Occ& o, u32* bits) {
+    if (n == 0) return PB3D_OK;
+    const unsigned nb = pb3d_stream_blocks(ctx, n, 256, 8);
+    if (f64) hipLaunchKernelGGL((k_occ_bits<true, F32>), dim3(nb), dim3(256), 0, ctx->stream, d_pts, n, o, bits);
+    else hipLaunchKernelGGL((k_occ_bits<false, F32>), dim3(nb), dim3(256), 0, ctx->stream, d_pts, n, o, bits);
+    PB3D_CHECK_LAUNCH();
+    return PB3D_OK;
+}
+
+template <bool F64>
+int bin_points(pb3d_ctx* ctx, const void* d_pts, i64 n, const Grid& g, int count_slot, int start_slot, u32** counts, i64** start) {
+    void *c, *s;
+    PB3D_TRY(pb3d_scratch(ctx, count_slot, (size_t)g.ncells * sizeof(u32), &c));
+    PB3D_TRY(pb3d_scratch(ctx, start_slot, (size_t)(g.ncells + 1) * sizeof(i64), &s));
+    PB3D_HIP(hipMemsetAsync(c, 0, (size_t)g.ncells * sizeof(u32), ctx->stream));
+    hipLaunchKernelGGL(k_cell_count<F64>, dim3(pb3d_stream_blocks(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, d_pts, n, g, (u32*)c);
+    PB3D_CHECK_LAUNCH();
+    PB3D_TRY(pb3d_scan_counts(ctx, (const u32*)c, g.ncells, (i64*)s, 31, 33));
+    PB3D_HIP(hipMemsetAsync(c, 0, (size_t)g.ncells * sizeof(u32), ctx->stream));      // the scatter's cursors
+    *counts = (u32*)c;
+    *start = (i64*)s;
+    return PB3D_OK;
+}
+
+template <bool QF64, bool RF64>
+int nn_run(pb3d_ctx* ctx, const void* d_q, i64 nq, const void* d_r, i64 nr, int k, const Grid& g, double* d_out) {
+    u32 *rc, *qc;
+    i64 *rs, *qs;
+    void *soa, *order;
+    PB3D_TRY(bin_points<RF64>(ctx, d_r, nr, g, 18, 19, &rc, &rs));
+    PB3D_TRY(pb3d_scratch(ctx, 27, (size_t)nr * 3 * sizeof(double), &soa));
+    double* xs = (double*)soa;
+    hipLaunchKernelGGL(k_cell_scatter_ref<RF64>, dim3(pb3d_stream_blocks(ctx, nr, 256, 8)), dim3(256), 0, ctx->stream, d_r, nr, g,
+                       (const i64*)rs, rc, xs, xs + nr, xs + 2 * nr);
+    PB3D_CHECK_LAUNCH();
+    PB3D_TRY(bin_points<QF64>(ctx, d_q, nq, g, 28, 29, &qc, &qs));
+    PB3D_TRY(pb3d_scratch(ctx, 30, (size_t)nq * sizeof(u32), &order));
+    hipLaunchKernelGGL(k_cell_scatter_query<QF64>, dim3(pb3d_stream_blocks(ctx, nq, 256, 8)), dim3(256), 0, ctx->stream, d_q, nq, g,
+                       (const i64*)qs, qc, (u32*)order);
+    PB3D_CHECK_LAUNCH();
+    const dim3 grid((unsigned)((nq + 255) / 256));
+    if (k == 1) hipLaunchKernelGGL((k_nn_query<1, QF64>), grid, dim3(256), 0, ctx->stream, d_q, nq, (const u32*)order, g, (const i64*)rs, xs,
+                                   xs + nr, xs + 2 * nr, d_out);
+    else hipLaunchKernelGGL((k_nn_query<2, QF64>), grid, dim3(256), 0, ctx->stream, d_q, nq, (const u32*)order, g, (const i64*)rs, xs,
+                            xs + nr, xs + 2 * nr, d_out);
+    PB3D_CHECK_LAUNCH();
+    return PB3D_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pb3d_points_bounds_dev(pb3d_ctx* ctx, const void* d_pts, int pts_f64, int64_t n, double* d_out) {
+    PB3D_REQUIRE(n >= 1 && n <= kMaxPoints, "pb3d_points_bounds: need 1 <= n <= 2^31 - 1 points (got %lld)", (long long)n);
+    PB3D_REQUIRE(d_pts != nullptr && d_out != nullptr, "pb3d_points_bounds: null buffer");
+    PB3D_REQUIRE(ctx != nullptr, "pb3d_points_bounds: null context");
+    return launch_bounds(ctx, d_pts, pts_f64, n, d_out);
+}
+
+int pb3d_nn_dist_dev(pb3d_ctx* ctx, const void* d_q, int q_f64, int64_t nq, const void* d_r, int r_f64, int64_t nr, int k, double* d_out) {
+    PB3D_REQUIRE(k == 1 || k == 2, "pb3d_nn_dist: k must be 1 or 2 (got %d)", k);
+    PB3D_REQUIRE(nq >= 0 && nr >= 0, "pb3d_nn_dist: negative point count");
+    PB3D_REQUIRE(nq <= kMaxPoints && nr <= kMaxPoints, "pb3d_nn_dist: at most 2^31 - 1 points per set");
+    if (nq == 0) return PB3D_OK;
+    PB3D_REQUIRE(nr >= k, "pb3d_nn_dist: the reference set needs at least k = %d points (got %lld)", k, (long long)nr);
+    PB3D_REQUIRE(d_q != nullptr && d_r != nullptr && d_out != nullptr, "pb3d_nn_dist: null buffer");
+    PB3D_REQUIRE(ctx != nullptr, "pb3d_nn_dist: null context");
+    void* bb;
+    PB3D_TRY(pb3d_scratch(ctx, 47, 6 * sizeof(double), &bb));
+    double* d_b = (double*)bb;
+    PB3D_TRY(launch_bounds(ctx, d_r, r_f64, nr, d_b));
+    PB3D_HIP(hipMemcpyAsync(ctx->pinned, d_b, 6 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    PB3D_TRY(pb3d_stream_sync(ctx));
+    double b[6];
+    memcpy(b, ctx->pinned, sizeof(b));
+    const Grid g = make_grid(b, nr);
+    if (q_f64 && r_f64) return nn_run<true, true>(ctx, d_q, nq, d_r, nr, k, g, d_out);
+    if (q_f64) return nn_run<true, false>(ctx, d_q, nq, d_r, nr, k, g, d_out);
+    if (r_f64) return nn_run<false, true>(ctx, d_q, nq, d_r, nr, k, g, d_out);
+    return nn_run<false, false>(ctx, d_q, nq, d_r, nr, k, g, d_out);
+}
+
+// the index size of the last pb3d_nn_dist_dev-shaped call on nr reference points with this box (cells per axis; tools/opbench.py)
+int pb3d_nn_grid_shape(const double bounds[6], int64_t nr, int64_t cells[3]) {
+    PB3D_REQUIRE(bounds != nullptr && cells != nullptr && nr >= 1, "pb3d_nn_grid_shape: bad argument");
+    const Grid g = make_grid(bounds, nr);
+    for (int a = 0; a < 3; ++a) cells[a] = g.n[a];
+    return PB3D_OK;
+}
+
+int pb3d_voxel_iou_counts_dev(pb3d_ctx* ctx, const void* d_a, int a_f64, int64_t na, const void* d_b, int b_f64, int64_t nb,
+                              const double bounds_min[3], double step, int calc_f32, int resolution, int iters, int64_t* d_counts) {
+    PB3D_REQUIRE(resolution >= 1 && resolution <= kMaxResolution, "pb3d_voxel_iou_counts: resolution must be in [1, %d] (got %d)",
+                 kMaxResolution, resolution);
+    PB3D_REQUIRE(iters >= 0, "pb3d_voxel_iou_counts: iters must be >= 0 (got %d)", iters);
+    PB3D_REQUIRE(na >= 0 && nb >= 0, "pb3d_voxel_iou_counts: negative point count");
+    PB3D_REQUIRE(na <= kMaxPoints && nb <= kMaxPoints, "pb3d_voxel_iou_counts: at most 2^31 - 1 points per set");
+    PB3D_REQUIRE((na == 0 || d_a) && (nb == 0 || d_b) && bounds_min && d_counts, "pb3d_voxel_iou_counts: null buffer");
+    PB3D_REQUIRE(!calc_f32 || (!a_f64 && !b_f64), "pb3d_voxel_iou_counts: float32 arithmetic needs float32 points");
+    PB3D_REQUIRE(ctx != nullptr, "pb3d_voxel_iou_counts: null context");
+    Occ o;
+    o.res = resolution;
+    o.W = (resolution + 31) / 32;
+    for (int a = 0; a < 3; ++a) o.lo[a] = bounds_min[a];
+    o.step = step;
+    const i64 gw = (i64)resolution * resolution * o.W;      // words of one bit grid
+    void *buf, *tmp;
+    PB3D_TRY(pb3d_scratch(ctx, 44, (size_t)gw * 2 * sizeof(u32), &buf));
+    u32* bits = (u32*)buf;
+    PB3D_HIP(hipMemsetAsync(bits, 0, (size_t)gw * 2 * sizeof(u32), ctx->stream));
+    if (calc_f32) {
+        PB3D_TRY(launch_occ<true>(ctx, d_a, a_f64, na, o, bits));
+        PB3D_TRY(launch_occ<true>(ctx, d_b, b_f64, nb, o, bits + gw));
+    } else {
+        PB3D_TRY(launch_occ<false>(ctx, d_a, a_f64, na, o, bits));
+        PB3D_TRY(launch_occ<false>(ctx, d_b, b_f64, nb, o, bits + gw));
+    }
+    // the dilated set is the L1 ball of radius iters clipped to the grid: it stops changing after 3 (res - 1) passes
+    const int passes = iters < 3 * (resolution - 1) ? iters : 3 * (resolution - 1);
+    if (passes > 0) {
+        PB3D_TRY(pb3d_scratch(ctx, 45, (size_t)gw * 2 * sizeof(u32), &tmp));
+        const u32 lastmask = (resolution & 31) ? (1u << (resolution & 31)) - 1u : 0xffffffffu;
+        u32 *src = bits, *dst = (u32*)tmp;
+        for (int p = 0; p < passes; ++p) {
+            hipLaunchKernelGGL(k_dilate6, dim3((unsigned)((2 * gw + 255) / 256)), dim3(256), 0, ctx->stream, (const u32*)src, dst, resolution,
+                               o.W, 2 * gw, lastmask);
+            PB3D_CHECK_LAUNCH();
+            u32* t = src; src = dst; dst = t;
+        }
+        bits = src;
+    }
+    PB3D_HIP(hipMemsetAsync(d_counts, 0, 2 * sizeof(int64_t), ctx->stream));
+    hipLaunchKernelGGL(k_iou_count, dim3(pb3d_stream_blocks(ctx, gw, 256, 4)), dim3(256), 0, ctx->stream, (const u32*)bits,
+                       (const u32*)(bits + gw), gw, (unsigned long long*)d_counts);
+    PB3D_CHECK_LAUNCH();
+    return PB3D_OK;
+}
+
+}  // extern "C"

@@ -183,6 +183,8 @@ int pb3d_ccl_label_on_device(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, i
                              int64_t cap, pb3d_ccl_dev* dev, int connectivity = 6);
 
 // ---- kernels' host launchers used across translation units ---------------------------------
+// exclusive scan of n u32 counts into n + 1 int64 offsets (the last = total) with points.hip's scan kernels; scratch slots local_slot, seg_slot
+int pb3d_scan_counts(pb3d_ctx* ctx, const u32* d_counts, i64 n, i64* d_offsets, int local_slot, int seg_slot);
 // process_voxel_grid through the bit-sliced chain (csrc/sliced.hip); *took = 0: not applicable, nothing written
 int pb3d_process_grid_sliced(pb3d_ctx* ctx, const u8* d_occ, i64 W, i64 H, i64 D, const u8* d_mask_wh, int angle_interval, u8* d_out,
                              int known_binary, int* took);

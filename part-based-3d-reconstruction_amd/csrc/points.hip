@@ -546,6 +546,25 @@ int fill_pass(pb3d_ctx* ctx, const u8* d_grid, const SelParams& p, bool fast16, 
 
 }  // namespace
 
+// The exclusive scan of count_pass on any u32 count array (the cell index of csrc/nn.hip): offsets[0..n) and offsets[n] = total.
+// Slot local_slot holds n u32 in-segment offsets, slot seg_slot the segment totals and bases.  Enqueue only.
+int pb3d_scan_counts(pb3d_ctx* ctx, const u32* d_counts, i64 n, i64* d_offsets, int local_slot, int seg_slot) {
+    const i64 nseg = (n + kSeg - 1) / kSeg;
+    void *local, *segs;
+    PB3D_TRY(pb3d_scratch(ctx, local_slot, (size_t)n * sizeof(u32), &local));
+    PB3D_TRY(pb3d_scratch(ctx, seg_slot, (size_t)nseg * (sizeof(u32) + sizeof(i64)), &segs));
+    i64* seg_base = (i64*)segs;
+    u32* seg_total = (u32*)(seg_base + nseg);
+    hipLaunchKernelGGL(k_scan_local, dim3((unsigned)nseg), dim3(256), 0, ctx->stream, d_counts, n, (u32*)local, seg_total);
+    PB3D_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_scan_totals, dim3(1), dim3(1024), 0, ctx->stream, (const u32*)seg_total, nseg, seg_base, d_offsets + n);
+    PB3D_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_scan_add, dim3(pb3d_stream_blocks(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, (const u32*)local,
+                       (const i64*)seg_base, n, d_offsets);
+    PB3D_CHECK_LAUNCH();
+    return PB3D_OK;
+}
+
 extern "C" {
 
 int pb3d_points_count_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64_t A1, int64_t A2, int C,

@@ -2,7 +2,7 @@
 
 Mirrors the reference's L2 function surface (utils.voxel_carving_utils, utils.voxel_utils,
 utils.projection_utils, utils.camera_geometry, utils.camera_estimation.compute_partwise_iou and the
-minaret extraction, utils.config) on top of libpb3d.so.  `install()` rebinds those names inside an imported
+minaret extraction, the notebook-4 and inter-method evaluations, utils.config) on top of libpb3d.so.  `install()` rebinds those names inside an imported
 reference `utils` package so notebooks 1-3 run unchanged.
 """
 from . import _hostmem, _lib, device, dist, formats, labels  # noqa: F401
@@ -13,6 +13,8 @@ from .labels import (Palette, extrude_from_surface_labels, get_voxel_points_by_p
 from ._hostmem import set_result_pool  # noqa: F401
 from .camera_estimation import (CameraObjective, compute_partwise_iou, coordinate_descent, powell_search, projection_iou_by_part,  # noqa: F401
                                 random_search)
+from .eval_helpers import (chamfer_distance, compute_f1_curve, compute_nn_distances, compute_nn_stats, f1_curve_from_distances,  # noqa: F401
+                           filter_mesh, fscore_with_threshold, nn_distances, pca_shape_similarity, voxel_iou)
 from .eval_helpers_intra import (color_presence, compute_binary_gt, compute_global_depth_buffer, grid_depth_buffer, grid_visible_bits,  # noqa: F401
                                  points_visible_bits, project_part_visible, run_minaret_iou_evaluation, run_minaret_kp_evaluation,
                                  run_part_minaret_binary_iou)
@@ -41,6 +43,8 @@ _PATCH = {
     "eval_helpers_intra": ["compute_global_depth_buffer", "project_part_visible", "load_voxel_grid", "resize_mask_to_voxel_grid",
                            "load_camera_json", "project_keypoints", "compute_binary_gt", "_iou_bool", "run_minaret_kp_evaluation",
                            "run_minaret_iou_evaluation", "run_part_minaret_binary_iou"],
+    "eval_helpers": ["filter_mesh", "_downsample", "chamfer_distance", "fscore_with_threshold", "pca_shape_similarity", "voxel_iou",
+                     "compute_nn_stats", "compute_nn_distances", "f1_curve_from_distances", "compute_f1_curve"],
 }
 
 

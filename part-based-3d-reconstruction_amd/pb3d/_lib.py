@@ -134,6 +134,10 @@ _SIGNATURES = {
     "pb3d_color_presence_dev": [vp, vp, i64, C.c_int, vp, u8p, C.c_int, vp],
     "pb3d_mask_bits_dev": [vp, vp, i64, u8p, C.c_int, vp, vp],
     "pb3d_iou_rows_dev": [vp, C.c_void_p, C.c_int, i64, vp],
+    "pb3d_points_bounds_dev": [vp, vp, C.c_int, i64, vp],
+    "pb3d_nn_dist_dev": [vp, vp, C.c_int, i64, vp, C.c_int, i64, C.c_int, vp],
+    "pb3d_nn_grid_shape": [dblp, i64, i64p],
+    "pb3d_voxel_iou_counts_dev": [vp, vp, C.c_int, i64, vp, C.c_int, i64, dblp, C.c_double, C.c_int, C.c_int, C.c_int, vp],
 }
 class IouRow(C.Structure):
     """pb3d_iou_row (include/pb3d.h)"""

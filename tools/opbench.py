@@ -40,6 +40,7 @@ def main():
     ap.add_argument("--ops", default="M1,M2,M3,M4,M5,M6,M7,M8,A2,A6,A9,N2,TK")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--tune", default="", help="development knobs, e.g. rot90_fill=6 (pb3d_set_tuning)")
+    ap.add_argument("--no-cpu-ref", action="store_true", help="I5: skip the cKDTree timings of the same inputs")
     a = ap.parse_args()
     for kv in [t for t in a.tune.split(',') if t]:
         pb3d._lib.set_tuning(kv.split('=')[0], int(kv.split('=')[1]))
@@ -249,6 +250,8 @@ def main():
         minarets(a.reps, res)
     if "N6" in ops:
         intra_eval(a.reps, res)
+    if "I5" in ops:
+        inter_eval(a.reps, res, cpu_ref=not a.no_cpu_ref)
     if d_col is not None:
         d_col.free()
     return res
@@ -417,6 +420,98 @@ def intra_eval(reps, res):
         res.append(r)
         for b in (d_g, d_m, z1, z2, b1, b2, b3, gt, bm, cnt, d_pts, d_pc, d_vm):
             b.free()
+
+
+
+def inter_eval(reps, res, cpu_ref=True):
+    """I5, the inter-method metrics (reference utils/eval_helpers.py): pb3d_nn_dist_dev at the reference's sizes (20 k x 20 k both
+    directions, the 50 k k = 2 self-query of compute_nn_stats), the full Taj grid's points (pb3d_points_extract_dev, float32) against
+    the 20 k SfM sample and a 52 032-point cloud (the SfM cloud's size: the sample resampled with 1e-3 jitter) in both directions, and
+    voxel_iou's device counts at 96 and 512.  The SfM clouds are mapped into the grid's frame by the inverse of
+    tests/golden/inter_ref.json's transform.  Every nn time includes the index build and the one host wait for the box; `cells` is
+    the index (cells per axis) built on the reference set.  With cpu_ref, cKDTree(workers=16) build + query of the same float64
+    inputs on this host."""
+    from pb3d.eval_helpers import nn_distances_resident, points_bounds_resident, voxel_iou_counts_resident
+    lib, L = pb3d._lib.load(), pb3d._lib
+    meta = json.load(open(os.path.join(ROOT, "tests", "golden", "inter_ref.json")))
+    scale = float.fromhex(meta["taj_transform"]["scale"])
+    offset = np.array([float.fromhex(v) for v in meta["taj_transform"]["offset"]])
+    sfm = np.load(os.path.join(ROOT, "tests", "golden", "inter_sfm20k.npz"))["sfm"]
+    sfm_vox = np.ascontiguousarray(((sfm - offset) / scale)[:, ::-1])          # extracted points are (a2, a1, a0)
+    rng = np.random.default_rng(0)
+    sfm52 = sfm_vox[rng.integers(0, len(sfm_vox), 52032)] + rng.normal(0, 1e-3 / scale, (52032, 3))
+    taj = np.load(os.path.join(ROOT, "tests", "golden", "stored_Taj_voxel_grid.npz"))["voxel_grid"]
+    nvox = int(np.prod(taj.shape[:3]))
+    d_g = dev.from_numpy(taj)
+    d_tp, d_tc = dev.DeviceBuffer(nvox * 12), dev.DeviceBuffer(nvox * 3)
+    n = C.c_int64(0)
+    L.check(lib.pb3d_points_extract_dev(L.ctx(), C.c_void_p(d_g.ptr), *taj.shape[:3], 3, None, 0, nvox, C.c_void_p(d_tp.ptr),
+                                        C.c_void_p(d_tc.ptr), C.byref(n)))
+    ntaj = n.value
+    taj_pts = d_tp.download((ntaj, 3), np.float32)
+    taj20 = np.ascontiguousarray(taj_pts[rng.choice(ntaj, 20000, replace=False)], np.float64)
+    taj50 = np.ascontiguousarray(taj_pts[rng.choice(ntaj, 50000, replace=False)], np.float64)
+    clouds = {"taj_full": (d_tp, ntaj, False, taj_pts), "sfm20k": (dev.from_numpy(sfm_vox), 20000, True, sfm_vox),
+              "sfm52k": (dev.from_numpy(sfm52), 52032, True, sfm52), "taj20k": (dev.from_numpy(taj20), 20000, True, taj20),
+              "taj50k": (dev.from_numpy(taj50), 50000, True, taj50)}
+    d_out = dev.DeviceBuffer(ntaj * 8)
+
+    def cells_of(name):
+        d, m, f64, host = clouds[name]
+        bb = points_bounds_resident(d, m, f64).download((6,), np.float64)
+        c = (C.c_int64 * 3)()
+        L.check(lib.pb3d_nn_grid_shape(L.p_dbl(bb), m, c))
+        return list(c)
+
+    def ckdtree_ms(q, r, k):
+        try:
+            from scipy.spatial import cKDTree
+        except ImportError:
+            return None
+        q, r = np.asarray(q, np.float64), np.asarray(r, np.float64)
+        best = None
+        for _ in range(2):
+            t0 = time.perf_counter()
+            cKDTree(r).query(q, k=k, workers=16)
+            t = (time.perf_counter() - t0) * 1e3
+            best = t if best is None else min(best, t)
+        return best
+
+    cases = [("sfm20k", "taj20k", 1), ("taj20k", "sfm20k", 1), ("taj50k", "taj50k", 2), ("taj_full", "sfm20k", 1),
+             ("sfm20k", "taj_full", 1), ("taj_full", "sfm52k", 1), ("sfm52k", "taj_full", 1)]
+    for qn, rn, k in cases:
+        dq, nq, qf, hq = clouds[qn]
+        dr, nr, rf, hr = clouds[rn]
+        ms = timeit(lambda: nn_distances_resident(dq, nq, dr, nr, k, qf, rf, out=d_out), reps)
+        r = {"op": "I5", "name": f"nn_dist k={k}: {qn} -> {rn}", "nq": nq, "nr": nr, "ms": round(ms, 4), "cells": cells_of(rn),
+             "Mquery_s": round(nq / ms / 1e3, 1)}
+        if cpu_ref:
+            t = ckdtree_ms(hq, hr, k)
+            if t is not None:
+                r["ckdtree_w16_ms"] = round(t, 2)
+                r["speedup_vs_ckdtree"] = round(t / ms, 1)
+        print(json.dumps(r), flush=True)
+        res.append(r)
+    d_bb = dev.DeviceBuffer(2 * 48)
+    d_cnt = dev.DeviceBuffer(16)
+    for resolution, frac in ((96, 0.01), (512, 0.01)):
+        both = np.concatenate([taj_pts.astype(np.float64), sfm_vox])
+        lo, hi = both.min(0), both.max(0)
+        step = (hi - lo).max() / resolution
+        iters = max(1, int(round((frac * np.linalg.norm(hi - lo)) / step)))
+        d_sf = clouds["sfm20k"][0]
+
+        def run():
+            points_bounds_resident(d_tp, ntaj, False, out=d_bb)
+            points_bounds_resident(d_sf, 20000, True, out=d_bb)
+            voxel_iou_counts_resident(d_tp, ntaj, d_sf, 20000, lo, step, resolution, iters, False, True, out=d_cnt)
+        ms = timeit(run, reps)
+        r = {"op": "I5", "name": f"voxel_iou counts (bounds, occupancy, {iters} dilation passes, counts): taj_full vs sfm20k",
+             "resolution": resolution, "iters": iters, "ms": round(ms, 4), "counts": d_cnt.download((2,), np.int64).tolist()}
+        print(json.dumps(r), flush=True)
+        res.append(r)
+    for b in [d_g, d_tc, d_out, d_bb, d_cnt] + [c[0] for c in clouds.values()]:
+        b.free()
 
 
 if __name__ == "__main__":
