@@ -185,6 +185,28 @@ int pb3d_points_count(pb3d_ctx* ctx, const uint8_t* grid, int64_t A0, int64_t A1
                       const uint8_t* colors, int ncolors, int stride, int64_t* n);
 int pb3d_points_fill(pb3d_ctx* ctx, int64_t n, float* pts, uint8_t* cols); /* after pb3d_points_count on the same ctx */
 
+/* ---- meshify_colored_voxel_grid, reference utils/voxel_utils.py:53-96 -------------------
+ * Binary marching cubes of the lattice grid[::s, ::s, ::s] (occupied = any of its C channels > 0)
+ * in skimage's serial order (Lewiner, level 0.5), plus each vertex's nearest occupied
+ * lattice point.  count: builds the lattice bitmask, counts, scans, synchronises once and returns
+ * nverts / nfaces (an error if either reaches 2^31, or if the lattice is smaller than 2 on an axis).
+ * fill: must follow count with identical grid arguments on the same context; writes verts
+ * (nverts x 3 float32: (s*a2, s*a1, shape[2] - s*a0)), faces (nfaces x 3 int32, skimage's column
+ * order), normals (nverts x 3 float32, skimage's (a0, a1, a2) order) and, if d_cols is not null,
+ * the C bytes of each vertex's nearest occupied lattice voxel.  Enqueue only.
+ * colors: that nearest-voxel search on its own for verts of this grid (the query is the
+ * reference's verts[:, [2,1,0]] / stride; ties go to the smallest lattice index).  Enqueue only. */
+int pb3d_mesh_count_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64_t A1, int64_t A2, int C, int stride,
+                        int64_t* nverts, int64_t* nfaces);
+int pb3d_mesh_fill_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64_t A1, int64_t A2, int C, int stride,
+                       int64_t nverts, int64_t nfaces, float* d_verts, int32_t* d_faces, float* d_normals, uint8_t* d_cols);
+int pb3d_mesh_colors_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64_t A1, int64_t A2, int C, int stride,
+                         const float* d_verts, int64_t nverts, uint8_t* d_cols);
+int pb3d_mesh_count(pb3d_ctx* ctx, const uint8_t* grid, int64_t A0, int64_t A1, int64_t A2, int C, int stride,
+                    int64_t* nverts, int64_t* nfaces);
+int pb3d_mesh_fill(pb3d_ctx* ctx, int64_t nverts, int64_t nfaces, float* verts, int32_t* faces, float* normals,
+                   uint8_t* cols); /* after pb3d_mesh_count on the same ctx; cols may be null */
+
 /* ---- project_colored_voxels, reference utils/projection_utils.py:5-23 ---------------------
  * R = look_at_rotation(cam, target) (host, reference utils/camera_geometry.py:3-14) is
  * passed in.  pts: (n,3) float32 (pts_f64 = 0) or float64 (1); cols (n,3) uint8.

@@ -14,7 +14,7 @@ typedef int64_t i64;
 typedef uint64_t u64;
 typedef uint32_t u32;
 
-#define PB3D_NSCRATCH 48
+#define PB3D_NSCRATCH 58
 #define PB3D_POOL_SLOTS 64
 #define PB3D_POOL_LIVE 4096
 
@@ -71,6 +71,8 @@ struct pb3d_ctx {
         u8 colors[3 * 32];
         bool valid;
     } pts;
+    // what pb3d_mesh_count staged (grid in scratch slot 0) for the pb3d_mesh_fill that follows it
+    struct { i64 A0, A1, A2, nv, nf; int C, stride; bool valid; } mesh;
     // state kept between pb3d_deform_count and pb3d_deform_fill
     struct {
         int ox, oy, oz;

@@ -29,13 +29,13 @@ from .projection_utils import project_colored_voxels  # noqa: F401
 from .voxel_carving_utils import (apply_colored_mask_to_voxel_grid, carve_voxel_grid_with_masks, extrude_from_surface,  # noqa: F401
                                   global_carve, left_right_guided_carve, part_carve, partwise_carve, process_voxel_grid,
                                   recolor_backward_components)
-from .voxel_utils import extract_top_k_components, get_voxel_points_by_parts, voxel_grid_to_points  # noqa: F401
+from .voxel_utils import extract_top_k_components, get_voxel_points_by_parts, meshify_colored_voxel_grid, voxel_grid_to_points  # noqa: F401
 
 _PATCH = {
     "voxel_carving_utils": ["carve_voxel_grid_with_masks", "process_voxel_grid", "apply_colored_mask_to_voxel_grid",
                             "part_carve", "global_carve", "_occupancy", "left_right_guided_carve", "extrude_from_surface",
                             "recolor_backward_components", "partwise_carve"],
-    "voxel_utils": ["get_voxel_points_by_parts", "extract_top_k_components", "voxel_grid_to_points"],
+    "voxel_utils": ["get_voxel_points_by_parts", "extract_top_k_components", "voxel_grid_to_points", "meshify_colored_voxel_grid"],
     "projection_utils": ["project_colored_voxels"],
     "camera_estimation": ["compute_partwise_iou", "extract_minaret_voxels_by_label", "extract_minaret_masks_by_label",
                           "extract_top_bottom_voxel_points", "extract_top_bottom_image_points", "extract_minaret_kps_for_view"],

@@ -65,6 +65,11 @@ _SIGNATURES = {
     "pb3d_points_extract_dev": [vp, vp, i64, i64, i64, C.c_int, u8p, C.c_int, i64, vp, vp, i64p],
     "pb3d_points_count": [vp, u8p, i64, i64, i64, C.c_int, u8p, C.c_int, C.c_int, i64p],
     "pb3d_points_fill": [vp, i64, C.POINTER(C.c_float), u8p],
+    "pb3d_mesh_count_dev": [vp, vp, i64, i64, i64, C.c_int, C.c_int, i64p, i64p],
+    "pb3d_mesh_fill_dev": [vp, vp, i64, i64, i64, C.c_int, C.c_int, i64, i64, vp, vp, vp, vp],
+    "pb3d_mesh_colors_dev": [vp, vp, i64, i64, i64, C.c_int, C.c_int, vp, i64, vp],
+    "pb3d_mesh_count": [vp, u8p, i64, i64, i64, C.c_int, C.c_int, i64p, i64p],
+    "pb3d_mesh_fill": [vp, i64, i64, vp, vp, vp, vp],
     "pb3d_project_dev": [vp, vp, C.c_int, vp, i64, dblp, dblp, C.c_double, C.c_double, C.c_double, intp, C.c_int, C.c_int, vp],
     "pb3d_project": [vp, vp, C.c_int, u8p, i64, dblp, dblp, C.c_double, C.c_double, C.c_double, intp, C.c_int, C.c_int, u8p],
     "pb3d_partwise_iou_dev": [vp, vp, vp, i64, u8p, C.c_int, i64p, i64p],

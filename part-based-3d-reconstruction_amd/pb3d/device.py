@@ -208,3 +208,34 @@ def synth_palette16():
     pal = np.zeros((16, 3), np.uint8)
     _lib.check(_lib.load().pb3d_synth_palette16(_lib.p_u8(pal)))
     return pal
+
+
+def meshify(d_grid, shape, stride=1, download=True):
+    """meshify_colored_voxel_grid of a uint8 grid already in HBM (a DeviceGrid, or a DeviceBuffer with shape = (A0, A1, A2[, C]),
+    C = 1 or 3).  One synchronisation for the counts; download=True returns the NumPy result (one download of each array),
+    download=False returns DeviceBuffers (verts n x 3 float32, faces m x 3 int32, normals n x 3 float32, nearest-voxel bytes n x C)
+    plus (n, m)."""
+    from .voxel_utils import mesh_check, mesh_colors
+    shape = tuple(int(v) for v in shape)
+    if len(shape) not in (3, 4) or (len(shape) == 4 and shape[3] not in (1, 3)):
+        raise ValueError("shape must be (A0, A1, A2[, 1 or 3])")
+    stride = mesh_check(shape, stride)
+    ch = shape[3] if len(shape) == 4 else 1
+    buf = d_grid.buf if isinstance(d_grid, DeviceGrid) else d_grid
+    lib, ctx = _lib.load(), _lib.ctx()
+    nv, nf = C.c_int64(0), C.c_int64(0)
+    _lib.check(lib.pb3d_mesh_count_dev(ctx, _ptr(buf), shape[0], shape[1], shape[2], ch, stride, C.byref(nv), C.byref(nf)))
+    if nv.value == 0:
+        raise ValueError("Surface level must be within volume data range.")
+    n, m = nv.value, nf.value
+    dv, df, dn, dc = DeviceBuffer(n * 12), DeviceBuffer(m * 12), DeviceBuffer(n * 12), DeviceBuffer(n * ch)
+    _lib.check(lib.pb3d_mesh_fill_dev(ctx, _ptr(buf), shape[0], shape[1], shape[2], ch, stride, n, m, _ptr(dv), _ptr(df), _ptr(dn),
+                                      _ptr(dc)))
+    if not download:
+        return (dv, df, dn, dc), (n, m)
+    try:
+        return (dv.download((n, 3), np.float32), df.download((m, 3), np.int32), mesh_colors(dc.download((n, ch))),
+                dn.download((n, 3), np.float32))
+    finally:
+        for b in (dv, df, dn, dc):
+            b.free()

@@ -398,3 +398,20 @@ def _points_labels_occ(g, stride, pal):
             d_p.free(); d_l.free(); d_c.free()
     finally:
         d_g.free()
+
+
+def meshify_colored_voxel_grid_labels(label_grid, palette, stride=1):
+    """meshify_colored_voxel_grid of a 1-byte label volume (label 0 empty, label k = palette colour k-1): the same mesh from a
+    third of the bytes, equal to meshify_colored_voxel_grid(label_to_rgb(label_grid, palette), stride)."""
+    from .voxel_utils import _mesh_host, mesh_check, mesh_colors
+    pal = _pal(palette)
+    lab = np.asarray(label_grid)
+    if lab.ndim != 3:
+        raise ValueError("label_grid must be (A0, A1, A2)")
+    stride = mesh_check(lab.shape, stride)
+    lab = _lib.as_u8(lab, "label_grid")
+    verts, faces, normals, labs = _mesh_host(lab, 1, stride)
+    table = np.concatenate([np.zeros((1, 3), np.uint8), np.asarray(pal.colors, np.uint8).reshape(-1, 3)])
+    if int(labs.max(initial=0)) >= len(table):
+        raise ValueError("label_grid holds labels beyond the palette")
+    return verts, faces, mesh_colors(table[labs[:, 0]]), normals

@@ -252,6 +252,8 @@ def main():
         intra_eval(a.reps, res)
     if "I5" in ops:
         inter_eval(a.reps, res, cpu_ref=not a.no_cpu_ref)
+    if "MESH" in ops:
+        meshify(a.reps, res)
     if d_col is not None:
         d_col.free()
     return res
@@ -512,6 +514,38 @@ def inter_eval(reps, res, cpu_ref=True):
         res.append(r)
     for b in [d_g, d_tc, d_out, d_bb, d_cnt] + [c[0] for c in clouds.values()]:
         b.free()
+
+
+def meshify(reps, res):
+    """MESH, meshify_colored_voxel_grid (csrc/mesh.hip) on the stored Taj and Charminar grids at strides 1, 2 and 4: the resident
+    form (count with its one host wait + fill into device buffers; device events) and the NumPy API (upload, count, fill, the four
+    downloads; host wall clock, best of reps)."""
+    import time
+    for mon in ("Taj", "Charminar"):
+        g = np.load(os.path.join(ROOT, "tests", "golden", f"stored_{mon}_voxel_grid.npz"))["voxel_grid"]
+        d = dev.from_numpy(g)
+        for s in (1, 2, 4):
+            keep = []
+
+            def run():
+                bufs, counts = dev.meshify(d, g.shape, stride=s, download=False)
+                keep.append((bufs, counts))
+            ms = timeit(run, reps)
+            nv, nf = keep[-1][1]
+            for bufs, _ in keep:
+                for b in bufs:
+                    b.free()
+            pb3d.meshify_colored_voxel_grid(g, stride=s)
+            wall = []
+            for _ in range(reps):
+                t0 = time.perf_counter()
+                pb3d.meshify_colored_voxel_grid(g, stride=s)
+                wall.append(time.perf_counter() - t0)
+            r = {"op": "MESH", "name": f"meshify_colored_voxel_grid, stored {mon}", "shape": list(g.shape), "stride": s,
+                 "nverts": int(nv), "nfaces": int(nf), "resident_ms": round(ms, 4), "numpy_api_ms": round(1e3 * min(wall), 3)}
+            print(json.dumps(r), flush=True)
+            res.append(r)
+        d.free()
 
 
 if __name__ == "__main__":
