@@ -169,8 +169,9 @@ int pb3d_part_carve(pb3d_ctx* ctx, const uint8_t* colored, int64_t W, int64_t H,
  * voxel_grid_to_points (:35-51).  Grid (A0,A1,A2[,C]); a voxel on the stride lattice is
  * selected if its RGB equals one of colors[ncolors][3] (ncolors > 0, C == 3) or if any of
  * its C channels is non-zero (ncolors == 0).  Points come out in numpy.where order as
- * float32 (a2,a1,a0)*stride plus the voxel's C bytes.  count first, then fill with
- * buffers of exactly n rows. */
+ * float32 (a2,a1,a0)*stride plus the voxel's C bytes.  count first, then fill with the same
+ * arguments and buffers of exactly n rows.  A fill refuses (PB3D_EINVAL) if another call has
+ * reused the state its count left on the context. */
 int pb3d_points_count_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64_t A1, int64_t A2, int C,
                           const uint8_t* colors, int ncolors, int stride, int64_t* n);
 int pb3d_points_fill_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64_t A1, int64_t A2, int C,
@@ -190,7 +191,8 @@ int pb3d_points_fill(pb3d_ctx* ctx, int64_t n, float* pts, uint8_t* cols); /* af
  * in skimage's serial order (Lewiner, level 0.5), plus each vertex's nearest occupied
  * lattice point.  count: builds the lattice bitmask, counts, scans, synchronises once and returns
  * nverts / nfaces (an error if either reaches 2^31, or if the lattice is smaller than 2 on an axis).
- * fill: must follow count with identical grid arguments on the same context; writes verts
+ * fill: must follow count with identical grid arguments and the counted sizes on the same context, and
+ * refuses (PB3D_EINVAL) if another call has reused the state its count left there; writes verts
  * (nverts x 3 float32: (s*a2, s*a1, shape[2] - s*a0)), faces (nfaces x 3 int32, skimage's column
  * order), normals (nverts x 3 float32, skimage's (a0, a1, a2) order) and, if d_cols is not null,
  * the C bytes of each vertex's nearest occupied lattice voxel.  Enqueue only.
@@ -334,7 +336,8 @@ int pb3d_deform_iou_batch_dev(pb3d_ctx* ctx, const float* d_pts, int64_t n, cons
  * its own mean, x/z scaled by sxz and pushed by kx/kz * sign, y scaled by sy and shifted by -ky (the
  * caller forms kx = shift_xz*W/W_img, ky = shift_y*H/H_img, kz = shift_xz*D/W_img as Python floats, :76-78),
  * rounded half-to-even; the result is np.unique(axis=0): unique rows in lexicographic (x,y,z) order as
- * int64.  count, then fill with a buffer of n_unique rows.  paint writes rgb at grid[z,y,x] of every
+ * int64.  count, then fill with a buffer of n_unique rows; a fill refuses (PB3D_EINVAL) if another call has
+ * reused the state its count left on the context.  paint writes rgb at grid[z,y,x] of every
  * in-bounds deformed coordinate (:120-124, :306-309 for a uniformly coloured part); scatter_colors is the
  * general grid[z,y,x] = cols[k] assignment for unique rows. */
 int pb3d_deform_count_dev(pb3d_ctx* ctx, const float* d_pts, int64_t n, double sxz, double sy, double kx, double ky, double kz,

@@ -585,10 +585,10 @@ int pb3d_part_carve_dev(pb3d_ctx* ctx, const uint8_t* d_colored, int64_t W, int6
     // every slot is requested ONCE with the size its path needs: a regrow frees and reallocates (and drops the cached rotation tables,
     // among them the set the first job's prefetch is about to build)
     void *occ, *carved, *tmp, *keep;
-    PB3D_TRY(pb3d_scratch(ctx, 4, (size_t)nvox, &occ));
-    PB3D_TRY(pb3d_scratch(ctx, 5, (size_t)nvox * (size_t)(multi ? nrest_all : 1), &carved));
-    PB3D_TRY(pb3d_scratch(ctx, 6, (size_t)nvox, &tmp));
-    PB3D_TRY(pb3d_scratch(ctx, 7, std::max((size_t)nvox, (size_t)(W * H) * sizeof(u32)), &keep));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_VOL_OCC, (size_t)nvox, &occ));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_VOL_CARVED, (size_t)nvox * (size_t)(multi ? nrest_all : 1), &carved));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_VOL_TMP, (size_t)nvox, &tmp));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_VOL_KEEP, std::max((size_t)nvox, (size_t)(W * H) * sizeof(u32)), &keep));
     const unsigned blocks = pb3d_stream_blocks(ctx, nvox, 256, 8);
     const i64 ngroups = nvox / 16, vtail = 16 * ngroups;                    // the last nvox % 16 voxels: scalar kernels from vtail on
     const pb3d_magic mD = pb3d_make_magic((u32)(D > 0 ? D : 1));

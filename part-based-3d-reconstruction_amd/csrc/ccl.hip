@@ -747,7 +747,7 @@ __global__ __launch_bounds__(256) void k_ccl_fold(int K, int dcap, const i64* __
 
 }  // namespace
 
-// Scratch slot 40: [header 64 B: i64 total[8]] [head: K x kFirst records] [final: K x dcap records] [shadow: kCopies x K x dcap records]
+// PB3D_SLOT_CCL_RECORDS: [header 64 B: i64 total[8]] [head: K x kFirst records] [final: K x dcap records] [shadow: kCopies x K x dcap records]
 static int label_colors_impl(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64_t A1, int64_t A2, const uint8_t* colors, int K, int C,
                              int32_t* d_labels, int64_t* ncomp, int64_t cap, bool members_only, int64_t* bbox_lo_hi, int64_t* count,
                              int64_t* coord_sum, int* stats_valid, pb3d_ccl_dev* dev = nullptr, int conn = 6) {
@@ -772,9 +772,9 @@ static int label_colors_impl(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, i
     PB3D_REQUIRE(nchunks <= 0x7fffffffll / kMaxColors, "pb3d_label_color: grid too large");
     void *bits, *rootbits, *chunks;
     ctx->ccl_last.valid = false;
-    PB3D_TRY(pb3d_scratch(ctx, 42, (size_t)K * (size_t)nwords * 8, &bits));  // a slot of its own: the bits outlive the call (ctx->ccl_last)
-    PB3D_TRY(pb3d_scratch(ctx, 5, (size_t)K * (size_t)nwords * 8, &rootbits));
-    PB3D_TRY(pb3d_scratch(ctx, 6, (size_t)K * (size_t)nchunks * (8 + 8 * (kWinPerBlock / 64)) + 16, &chunks));   // [root flags | chunk counts | chunk bases]
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_CCL_MEMBER_BITS, (size_t)K * (size_t)nwords * 8, &bits));  // a slot of its own: the bits outlive the call (ctx->ccl_last)
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_CCL_ROOT_BITS, (size_t)K * (size_t)nwords * 8, &rootbits));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_CCL_CHUNKS, (size_t)K * (size_t)nchunks * (8 + 8 * (kWinPerBlock / 64)) + 16, &chunks));   // [root flags | chunk counts | chunk bases]
     // records kept on the device per colour; the shadow copies (same-address atomics serialise: every block flushes into copy
     // blockIdx % ncopies) are bounded to 16 MiB
     int dcap = 0, ncopies = 1;
@@ -785,7 +785,7 @@ static int label_colors_impl(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, i
     }
     const size_t head_bytes = 64 + (size_t)K * kFirst * 64, fin_bytes = (size_t)K * (size_t)dcap * 64;
     void* sblk = nullptr;
-    PB3D_TRY(pb3d_scratch(ctx, 40, head_bytes + fin_bytes * (size_t)(1 + ncopies), &sblk));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_CCL_RECORDS, head_bytes + fin_bytes * (size_t)(1 + ncopies), &sblk));
     char* head = (char*)sblk + 64;
     char* fin = (char*)sblk + head_bytes;
     char* shadow = fin + fin_bytes;
@@ -862,7 +862,7 @@ static int label_colors_impl(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, i
     // the membership bits of THIS label volume stay where they are: consumers that only need the members' labels (the component loop,
     // the recolouring) walk the 1-bit-per-voxel arrays instead of the 4-byte-per-voxel one
     pb3d_ctx::CclLast& cl = ctx->ccl_last;
-    cl.valid = true; cl.labels = d_labels; cl.bits = bits; cl.rows = rows; cl.A2 = A2; cl.P = P; cl.gen = ctx->scratch_slot_gen[42];
+    cl.valid = true; cl.labels = d_labels; cl.bits = bits; cl.rows = rows; cl.A2 = A2; cl.P = P; cl.gen = ctx->scratch_slot_gen[PB3D_SLOT_CCL_MEMBER_BITS];
     cl.members_only = members_only; cl.K = K; cl.C = C;
     for (int k = 0; k < kMaxColors; ++k) cl.colors[k] = cols.c[k];
     if (dev) {          // a consumer on the device (pb3d_recolor_backward_dev): counts and records stay there, no host wait

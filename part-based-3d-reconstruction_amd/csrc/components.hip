@@ -511,8 +511,8 @@ int pb3d_component_stats_dev(pb3d_ctx* ctx, const int32_t* d_labels, int64_t A0,
     const i64 n = A0 * A1 * A2;
     PB3D_REQUIRE(n < (1ll << 31), "pb3d_component_stats: grid too large for 32-bit labels");
     void *bb, *cs;
-    PB3D_TRY(pb3d_scratch(ctx, 6, (size_t)ncomp * 6 * sizeof(int), &bb));
-    PB3D_TRY(pb3d_scratch(ctx, 7, (size_t)ncomp * 4 * sizeof(unsigned long long), &cs));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_STATS_BOXES, (size_t)ncomp * 6 * sizeof(int), &bb));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_STATS_SUMS, (size_t)ncomp * 4 * sizeof(unsigned long long), &cs));
     // lo = +inf, hi = -1, sums = 0 (set on the device: an upload of the initial boxes cost a transfer and a synchronisation per call)
     hipLaunchKernelGGL(k_stats_init, dim3(pb3d_stream_blocks(ctx, ncomp, 256, 8)), dim3(256), 0, ctx->stream, ncomp, (int*)bb, (unsigned long long*)cs);
     PB3D_CHECK_LAUNCH();
@@ -590,10 +590,10 @@ static int recolor_impl(pb3d_ctx* ctx, const int32_t* d_labels, int64_t nvox, co
     if (nvox == 0 || ncomp == 0) return PB3D_OK;
     PB3D_REQUIRE(d_labels && comp_flag && d_grid_rgb, "pb3d_recolor_components: null buffer");
     void* f;
-    PB3D_TRY(pb3d_scratch(ctx, 6, (size_t)ncomp, &f));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_RECOLOR_FLAGS, (size_t)ncomp, &f));
     PB3D_TRY(pb3d_h2d_async(ctx, f, comp_flag, (size_t)ncomp));      // (comp_flag is a caller-owned host buffer: staged, no wait)
     const pb3d_ctx::CclLast& cl = ctx->ccl_last;
-    const bool bits_ok = cl.valid && cl.labels == (const void*)d_labels && cl.rows * cl.A2 == nvox && cl.gen == ctx->scratch_slot_gen[42] &&
+    const bool bits_ok = cl.valid && cl.labels == (const void*)d_labels && cl.rows * cl.A2 == nvox && cl.gen == ctx->scratch_slot_gen[PB3D_SLOT_CCL_MEMBER_BITS] &&
                          cl.rows * cl.P < (1ll << 32) && cl.K == 1;
     PB3D_REQUIRE(!last_labelled || bits_ok, "pb3d_recolor_last_labelled: d_labels is not the volume the last pb3d_label_* call on this context wrote");
     if (last_labelled) {
@@ -638,7 +638,7 @@ int pb3d_recolor_backward_dev(pb3d_ctx* ctx, uint8_t* d_grid, int64_t A0, int64_
     pb3d_ccl_dev dev;
     PB3D_TRY(pb3d_ccl_label_on_device(ctx, d_grid, A0, A1, A2, color, channels, d_labels, kRecolorDeviceMax, &dev));
     void* f;
-    PB3D_TRY(pb3d_scratch(ctx, 7, (size_t)dev.dcap, &f));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_SELECT_FLAGS, (size_t)dev.dcap, &f));
     hipLaunchKernelGGL(k_recolor_select, dim3(1), dim3(1024), 0, ctx->stream, dev.total, dev.records, dev.dcap, keep_k < 0 ? 0 : keep_k, sort_axis, (u8*)f,
                        (i64*)d_status);
     PB3D_CHECK_LAUNCH();
@@ -669,7 +669,7 @@ int pb3d_top_k_components_dev(pb3d_ctx* ctx, uint8_t* d_grid, int64_t A0, int64_
     pb3d_ccl_dev dev;
     PB3D_TRY(pb3d_ccl_label_on_device(ctx, d_grid, A0, A1, A2, color, channels, d_labels, kTopkDeviceMax, &dev, connectivity));
     void* f;
-    PB3D_TRY(pb3d_scratch(ctx, 7, (size_t)dev.dcap, &f));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_SELECT_FLAGS, (size_t)dev.dcap, &f));
     hipLaunchKernelGGL(k_topk_select, dim3(1), dim3(1024), 0, ctx->stream, dev.total, dev.records, dev.dcap, (int)(A1 < 0x7fffffff ? A1 : 0x7fffffff), (i64)k,
                        (u8*)f, (i64*)d_status);
     PB3D_CHECK_LAUNCH();

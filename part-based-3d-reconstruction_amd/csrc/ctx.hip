@@ -172,7 +172,7 @@ void pb3d_destroy(pb3d_ctx* ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     pb3d_comm_destroy(ctx);
     (void)pool_flush(ctx);
-    for (int i = 0; i < PB3D_NSCRATCH; ++i)
+    for (int i = 0; i < PB3D_SLOT_COUNT; ++i)
         if (ctx->scratch[i]) (void)hipFree(ctx->scratch[i]);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->stage) (void)hipHostFree(ctx->stage);
@@ -397,8 +397,9 @@ int pb3d_stream_sync(pb3d_ctx* ctx) {
     return PB3D_OK;
 }
 
-int pb3d_scratch(pb3d_ctx* ctx, int slot, size_t bytes, void** out) {
-    PB3D_REQUIRE(ctx != nullptr && slot >= 0 && slot < PB3D_NSCRATCH, "pb3d_scratch: bad slot");
+int pb3d_scratch(pb3d_ctx* ctx, pb3d_slot slot, size_t bytes, void** out) {
+    PB3D_REQUIRE(ctx != nullptr && slot >= 0 && slot < PB3D_SLOT_COUNT, "pb3d_scratch: bad slot");
+    ++ctx->scratch_use[slot];
     if (ctx->scratch_bytes[slot] < bytes || !ctx->scratch[slot]) {
         if (ctx->scratch[slot]) {
             PB3D_TRY(pb3d_stream_sync(ctx));
@@ -413,5 +414,22 @@ int pb3d_scratch(pb3d_ctx* ctx, int slot, size_t bytes, void** out) {
         ++ctx->scratch_slot_gen[slot];
     }
     *out = ctx->scratch[slot];
+    return PB3D_OK;
+}
+
+void pb3d_pair_record(pb3d_ctx* ctx, pb3d_pair* pr, std::initializer_list<pb3d_slot> slots) {
+    pr->nslots = 0;
+    for (pb3d_slot s : slots) {
+        pr->slot[pr->nslots] = s;
+        pr->use[pr->nslots++] = ctx->scratch_use[s];
+    }
+    pr->valid = true;
+}
+
+int pb3d_pair_check(const pb3d_ctx* ctx, const pb3d_pair& pr, bool same_args, const char* fill, const char* count) {
+    PB3D_REQUIRE(pr.valid, "%s: call %s first", fill, count);
+    for (int i = 0; i < pr.nslots; ++i)
+        PB3D_REQUIRE(ctx->scratch_use[pr.slot[i]] == pr.use[i], "%s: the state of %s was overwritten by another call; count again", fill, count);
+    PB3D_REQUIRE(same_args, "%s: the arguments differ from those of the last %s; count again", fill, count);
     return PB3D_OK;
 }

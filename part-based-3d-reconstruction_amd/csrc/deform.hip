@@ -165,7 +165,7 @@ __global__ __launch_bounds__(256) void k_deform_iou_batch(const u8* __restrict__
 
 int centers(pb3d_ctx* ctx, const float* d_pts, i64 n, double sxz, double sy, double kx, double ky, double kz, DeformParams* P) {
     void* acc;
-    PB3D_TRY(pb3d_scratch(ctx, 11, 8 * sizeof(unsigned long long), &acc));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_DEFORM_ACC, 8 * sizeof(unsigned long long), &acc));
     PB3D_HIP(hipMemsetAsync(acc, 0, 8 * sizeof(unsigned long long), ctx->stream));
     hipLaunchKernelGGL(k_deform_sum, dim3(pb3d_stream_blocks(ctx, n, 256, 4)), dim3(256), 0, ctx->stream, d_pts, n,
                        (unsigned long long*)acc);
@@ -195,14 +195,14 @@ extern "C" {
 int pb3d_deform_count_dev(pb3d_ctx* ctx, const float* d_pts, int64_t n, double sxz, double sy, double kx, double ky, double kz,
                           int64_t* n_unique) {
     PB3D_REQUIRE(ctx && n_unique && n >= 0, "pb3d_deform_count: bad argument");
-    ctx->deform.valid = false;
+    ctx->deform.pair.valid = false;
     *n_unique = 0;
-    if (n == 0) { ctx->deform.n = 0; ctx->deform.valid = true; return PB3D_OK; }
+    if (n == 0) { ctx->deform.n = 0; pb3d_pair_record(ctx, &ctx->deform.pair, {}); return PB3D_OK; }
     PB3D_REQUIRE(d_pts != nullptr, "pb3d_deform_count: null points");
     DeformParams P;
     PB3D_TRY(centers(ctx, d_pts, n, sxz, sy, kx, ky, kz, &P));
     void* bbv;
-    PB3D_TRY(pb3d_scratch(ctx, 11, 8 * sizeof(unsigned long long), &bbv));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_DEFORM_ACC, 8 * sizeof(unsigned long long), &bbv));
     const int init[8] = {0x7fffffff, 0x7fffffff, 0x7fffffff, (int)0x80000000, (int)0x80000000, (int)0x80000000, 0, 0};
     PB3D_HIP(hipMemcpyAsync(bbv, init, sizeof(init), hipMemcpyHostToDevice, ctx->stream));
     const unsigned blocks = pb3d_stream_blocks(ctx, 7 * n, 256, 8);
@@ -219,7 +219,7 @@ int pb3d_deform_count_dev(pb3d_ctx* ctx, const float* d_pts, int64_t n, double s
     PB3D_REQUIRE(X > 0 && Y > 0 && Z > 0 && (double)X * (double)Y * (double)Z <= 34359738368.0,
                  "pb3d_deform: deformed bounding box %lld x %lld x %lld is too large", (long long)X, (long long)Y, (long long)Z);
     void* mark;
-    PB3D_TRY(pb3d_scratch(ctx, 12, (size_t)(X * Y * Z), &mark));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_DEFORM_MARKS, (size_t)(X * Y * Z), &mark));
     PB3D_HIP(hipMemsetAsync(mark, 0, (size_t)(X * Y * Z), ctx->stream));
     hipLaunchKernelGGL(k_deform_mark, dim3(blocks), dim3(256), 0, ctx->stream, d_pts, n, P, bb[0], bb[1], bb[2], Y, Z, (u8*)mark);
     PB3D_CHECK_LAUNCH();
@@ -227,20 +227,20 @@ int pb3d_deform_count_dev(pb3d_ctx* ctx, const float* d_pts, int64_t n, double s
     ctx->deform.X = X; ctx->deform.Y = Y; ctx->deform.Z = Z;
     PB3D_TRY(pb3d_points_count_dev(ctx, (const u8*)mark, X, Y, Z, 1, nullptr, 0, 1, n_unique));
     ctx->deform.n = *n_unique;
-    ctx->deform.valid = true;
+    pb3d_pair_record(ctx, &ctx->deform.pair, {PB3D_SLOT_DEFORM_MARKS, PB3D_SLOT_POINTS_OFFSETS, PB3D_SLOT_POINTS_MASKS});
     return PB3D_OK;
 }
 
 int pb3d_deform_fill_dev(pb3d_ctx* ctx, int64_t n_unique, int64_t* d_coords) {
     PB3D_REQUIRE(ctx != nullptr, "pb3d_deform_fill: null context");
-    PB3D_REQUIRE(ctx->deform.valid && ctx->deform.n == n_unique, "pb3d_deform_fill: call pb3d_deform_count first");
-    ctx->deform.valid = false;
+    PB3D_TRY(pb3d_pair_check(ctx, ctx->deform.pair, ctx->deform.n == n_unique, "pb3d_deform_fill", "pb3d_deform_count"));
+    ctx->deform.pair.valid = false;
     if (n_unique == 0) return PB3D_OK;
     PB3D_REQUIRE(d_coords != nullptr, "pb3d_deform_fill: null output");
     void *pts, *cols;
-    PB3D_TRY(pb3d_scratch(ctx, 13, (size_t)n_unique * 3 * sizeof(float), &pts));
-    PB3D_TRY(pb3d_scratch(ctx, 14, (size_t)n_unique, &cols));
-    PB3D_TRY(pb3d_points_fill_dev(ctx, (const u8*)ctx->scratch[12], ctx->deform.X, ctx->deform.Y, ctx->deform.Z, 1, nullptr, 0, 1,
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_DEFORM_PTS, (size_t)n_unique * 3 * sizeof(float), &pts));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_DEFORM_COLS, (size_t)n_unique, &cols));
+    PB3D_TRY(pb3d_points_fill_dev(ctx, (const u8*)ctx->scratch[PB3D_SLOT_DEFORM_MARKS], ctx->deform.X, ctx->deform.Y, ctx->deform.Z, 1, nullptr, 0, 1,
                                   n_unique, (float*)pts, (u8*)cols));
     hipLaunchKernelGGL(k_pts_to_coords, dim3(pb3d_stream_blocks(ctx, n_unique, 256, 8)), dim3(256), 0, ctx->stream,
                        (const float*)pts, n_unique, ctx->deform.ox, ctx->deform.oy, ctx->deform.oz, (i64*)d_coords);
@@ -267,7 +267,7 @@ int pb3d_scatter_colors_dev(pb3d_ctx* ctx, const int64_t* d_coords, const uint8_
     if (m == 0) return PB3D_OK;
     PB3D_REQUIRE(d_coords && d_cols && d_grid, "pb3d_scatter_colors: null buffer");
     void* flag;
-    PB3D_TRY(pb3d_scratch(ctx, 11, 8 * sizeof(unsigned long long), &flag));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_DEFORM_ACC, 8 * sizeof(unsigned long long), &flag));
     PB3D_HIP(hipMemsetAsync(flag, 0, sizeof(int), ctx->stream));
     hipLaunchKernelGGL(k_scatter_colors, dim3(pb3d_stream_blocks(ctx, m, 256, 8)), dim3(256), 0, ctx->stream, (const i64*)d_coords,
                        d_cols, m, A0, A1, A2, d_grid, (int*)flag);
@@ -300,9 +300,9 @@ int pb3d_deform_iou_batch_dev(pb3d_ctx* ctx, const float* d_pts, int64_t n, cons
     kc = kc < 1 ? 1 : (kc > 8192 ? 8192 : kc);
     if (kc > ntuples) kc = ntuples;
     void *marks, *dt, *cnt;
-    PB3D_TRY(pb3d_scratch(ctx, 12, (size_t)(kc * npix), &marks));
-    PB3D_TRY(pb3d_scratch(ctx, 20, (size_t)kc * sizeof(DeformTuple), &dt));
-    PB3D_TRY(pb3d_scratch(ctx, 21, (size_t)kc * 3 * sizeof(unsigned long long), &cnt));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_DEFORM_BATCH_MARKS, (size_t)(kc * npix), &marks));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_DEFORM_BATCH_TUPLES, (size_t)kc * sizeof(DeformTuple), &dt));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_DEFORM_BATCH_COUNTS, (size_t)kc * 3 * sizeof(unsigned long long), &cnt));
     unsigned long long* hc = (unsigned long long*)malloc((size_t)kc * 3 * sizeof(unsigned long long));
     if (!hc) { pb3d_set_error("pb3d_deform_iou_batch: out of host memory"); return PB3D_ENOMEM; }
     int rc = PB3D_OK;
@@ -342,7 +342,7 @@ int pb3d_deform_count(pb3d_ctx* ctx, const float* pts, int64_t n, double sxz, do
     void* d = nullptr;
     if (n) {
         PB3D_REQUIRE(pts != nullptr, "pb3d_deform_count: null points");
-        PB3D_TRY(pb3d_scratch(ctx, 0, (size_t)n * 3 * sizeof(float), &d));
+        PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_HOST_IN0, (size_t)n * 3 * sizeof(float), &d));
         PB3D_HIP(hipMemcpyAsync(d, pts, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     }
     return pb3d_deform_count_dev(ctx, (const float*)d, n, sxz, sy, kx, ky, kz, n_unique);
@@ -353,7 +353,7 @@ int pb3d_deform_fill(pb3d_ctx* ctx, int64_t n_unique, int64_t* coords) {
     if (n_unique == 0) return pb3d_deform_fill_dev(ctx, 0, nullptr);
     PB3D_REQUIRE(coords != nullptr, "pb3d_deform_fill: null output");
     void* d;
-    PB3D_TRY(pb3d_scratch(ctx, 1, (size_t)n_unique * 3 * sizeof(i64), &d));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_HOST_OUT0, (size_t)n_unique * 3 * sizeof(i64), &d));
     PB3D_TRY(pb3d_deform_fill_dev(ctx, n_unique, (int64_t*)d));
     PB3D_HIP(hipMemcpyAsync(coords, d, (size_t)n_unique * 3 * sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
     PB3D_TRY(pb3d_stream_sync(ctx));

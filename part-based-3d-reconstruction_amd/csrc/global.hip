@@ -47,7 +47,7 @@ int pb3d_global_carve_dev(pb3d_ctx* ctx, const uint8_t* d_bin_hw, const uint8_t*
     PB3D_REQUIRE(x0 == 0 && x1 == W, "pb3d_global_carve: slab output needs the fused 90-degree path (angle_interval=90)");
     const int nsteps = 90 / angle_interval + 1;  // len(range(0, 91, k))
     void* mwh;
-    PB3D_TRY(pb3d_scratch(ctx, 7, (size_t)(W * H), &mwh));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MASK_WH, (size_t)(W * H), &mwh));
     PB3D_TRY(pb3d_transpose_mask_dev(ctx, d_bin_hw, H, W, (u8*)mwh));
     if (nsteps >= 2 && ctx->tune_global_composed != 1) {             // knob global_composed = 1: the composed pipeline (parity tests run both)
         int took = 0;
@@ -56,9 +56,9 @@ int pb3d_global_carve_dev(pb3d_ctx* ctx, const uint8_t* d_bin_hw, const uint8_t*
     }
     // composed pipeline: ones -> process_voxel_grid -> colour
     void *ones, *carved, *tmp;
-    PB3D_TRY(pb3d_scratch(ctx, 4, (size_t)nvox, &ones));
-    PB3D_TRY(pb3d_scratch(ctx, 5, (size_t)nvox, &carved));
-    PB3D_TRY(pb3d_scratch(ctx, 6, (size_t)nvox, &tmp));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_VOL_OCC, (size_t)nvox, &ones));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_VOL_CARVED, (size_t)nvox, &carved));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_VOL_TMP, (size_t)nvox, &tmp));
     PB3D_HIP(hipMemsetAsync(ones, 1, (size_t)nvox, ctx->stream));
     PB3D_TRY(pb3d_process_grid_binary_dev(ctx, (const u8*)ones, W, H, D, (const u8*)mwh, angle_interval, (u8*)carved, (u8*)tmp));
     return pb3d_color_apply_dev(ctx, (const u8*)carved, W, H, D, d_rgb_hw3, d_out_slab);

@@ -248,7 +248,7 @@ static int guided_carve_impl(pb3d_ctx* ctx, uint8_t* d_grid_rgb, const int32_t* 
     }
     // labels of the last labelling on this context: its membership bits are still on the device
     const pb3d_ctx::CclLast& cl = ctx->ccl_last;
-    const bool bits_ok = cl.valid && cl.labels == (const void*)d_labels && cl.rows == W * H && cl.A2 == D && cl.gen == ctx->scratch_slot_gen[42] &&
+    const bool bits_ok = cl.valid && cl.labels == (const void*)d_labels && cl.rows == W * H && cl.A2 == D && cl.gen == ctx->scratch_slot_gen[PB3D_SLOT_CCL_MEMBER_BITS] &&
                          color_index >= 0 && color_index < cl.K;
     // Without the bits the kernel reads labels[] at every voxel of a crop: that is only right for a FULL label volume of ONE colour.  A volume
     // this context wrote for the members only (or for several colours, numbered per colour) must not be read that way.
@@ -266,9 +266,9 @@ static int guided_carve_impl(pb3d_ctx* ctx, uint8_t* d_grid_rgb, const int32_t* 
     }
     const size_t nvox3 = (size_t)(W * H * D) * (size_t)C;
     void *d_masks, *d_counts;
-    PB3D_TRY(pb3d_scratch(ctx, 37, (size_t)mask_bytes + 16, &d_masks));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_GUIDED_MASKS, (size_t)mask_bytes + 16, &d_masks));
     if (queued) d_counts = d_counts_out;
-    else PB3D_TRY(pb3d_scratch(ctx, 39, (size_t)ncomp * sizeof(unsigned long long), &d_counts));
+    else PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_GUIDED_COUNTS, (size_t)ncomp * sizeof(unsigned long long), &d_counts));
     // every host input goes through the context's pinned staging ring: the caller's buffers are free when the call returns
     PB3D_TRY(pb3d_h2d_async(ctx, d_masks, masks, (size_t)mask_bytes));
     PB3D_HIP(hipMemsetAsync(d_counts, 0, (size_t)ncomp * sizeof(unsigned long long), ctx->stream));
@@ -322,9 +322,9 @@ static int guided_carve_impl(pb3d_ctx* ctx, uint8_t* d_grid_rgb, const int32_t* 
         // overwrite what batch b's kernels still read
         const size_t nb = batches.size();
         const size_t slice = ((desc_bytes + par_bytes) + 63) & ~(size_t)63;
-        PB3D_TRY(pb3d_scratch(ctx, 36, slice * nb, &dd));
-        PB3D_TRY(pb3d_scratch(ctx, 38, tab_bytes, &dt));
-        PB3D_TRY(pb3d_scratch(ctx, 43, slice_bytes, &dsl));
+        PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_GUIDED_DESCS, slice * nb, &dd));
+        PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_GUIDED_TABLES, tab_bytes, &dt));
+        PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_GUIDED_SLICES, slice_bytes, &dsl));
         for (size_t bi = 0; bi < nb; ++bi) {
             const i64 a = batches[bi].first, e = batches[bi].second;
             keep_d.emplace_back(); keep_p.emplace_back();

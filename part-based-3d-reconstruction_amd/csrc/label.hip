@@ -267,7 +267,7 @@ int pb3d_rgb_to_label_dev(pb3d_ctx* ctx, const uint8_t* d_rgb, int64_t nvox, con
     LabelHash h;
     PB3D_REQUIRE(build_hash(palette, npal, &h), "pb3d_rgb_to_label: the palette repeats a colour (or black): labels would be ambiguous");
     void* flag;
-    PB3D_TRY(pb3d_scratch(ctx, 23, 64, &flag));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_LABEL_FLAG, 64, &flag));
     PB3D_HIP(hipMemsetAsync(flag, 0, sizeof(int), ctx->stream));
     hipLaunchKernelGGL(k_rgb_to_label, dim3(pb3d_stream_blocks(ctx, (nvox + 15) / 16, 256, 8)), dim3(256), 0, ctx->stream, d_rgb, nvox, h, d_label,
                        (int*)flag);
@@ -283,7 +283,7 @@ static int label_to_rgb_launch(pb3d_ctx* ctx, const uint8_t* d_label, int64_t nv
     Pal256 P;
     PB3D_TRY(palette_words(palette, npal, P.c));
     void* flag;
-    PB3D_TRY(pb3d_scratch(ctx, 23, 64, &flag));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_LABEL_FLAG, 64, &flag));
     PB3D_HIP(hipMemsetAsync(flag, 0, sizeof(int), ctx->stream));
     hipLaunchKernelGGL(k_label_to_rgb, dim3(pb3d_stream_blocks(ctx, (nvox + 15) / 16, 256, 8)), dim3(256), 0, ctx->stream, d_label, nvox, P, npal,
                        d_rgb, (int*)flag);
@@ -320,10 +320,10 @@ int pb3d_global_carve_label_dev(pb3d_ctx* ctx, const uint8_t* d_bin_hw, const ui
         if (pb3d_is_perm_step(M, off, W, D)) return pb3d_launch_global_carve90(ctx, d_bin_hw, d_label_hw, 1, h, w, M, off, 0, W, d_out);
     }
     void *ones, *carved, *tmp, *mwh;
-    PB3D_TRY(pb3d_scratch(ctx, 4, (size_t)nvox, &ones));
-    PB3D_TRY(pb3d_scratch(ctx, 5, (size_t)nvox, &carved));
-    PB3D_TRY(pb3d_scratch(ctx, 6, (size_t)nvox, &tmp));
-    PB3D_TRY(pb3d_scratch(ctx, 7, (size_t)(W * H), &mwh));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_VOL_OCC, (size_t)nvox, &ones));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_VOL_CARVED, (size_t)nvox, &carved));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_VOL_TMP, (size_t)nvox, &tmp));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MASK_WH, (size_t)(W * H), &mwh));
     PB3D_HIP(hipMemsetAsync(ones, 1, (size_t)nvox, ctx->stream));
     PB3D_TRY(pb3d_transpose_mask_dev(ctx, d_bin_hw, H, W, (u8*)mwh));
     PB3D_TRY(pb3d_process_grid_binary_dev(ctx, (const u8*)ones, W, H, D, (const u8*)mwh, angle_interval, (u8*)carved, (u8*)tmp));
@@ -361,10 +361,10 @@ int pb3d_part_carve_label_dev(pb3d_ctx* ctx, const uint8_t* d_label, int64_t W, 
         }
     }
     void *occ, *carved, *tmp, *keep;
-    PB3D_TRY(pb3d_scratch(ctx, 4, (size_t)nvox, &occ));
-    PB3D_TRY(pb3d_scratch(ctx, 5, (size_t)nvox, &carved));
-    PB3D_TRY(pb3d_scratch(ctx, 6, (size_t)nvox, &tmp));
-    PB3D_TRY(pb3d_scratch(ctx, 7, (size_t)nvox, &keep));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_VOL_OCC, (size_t)nvox, &occ));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_VOL_CARVED, (size_t)nvox, &carved));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_VOL_TMP, (size_t)nvox, &tmp));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_VOL_KEEP, (size_t)nvox, &keep));
     const bool wide = D % 16 == 0 && ((((uintptr_t)d_label) | ((uintptr_t)d_out)) & 15u) == 0;
     const unsigned blocks = pb3d_stream_blocks(ctx, wide ? nvox / 16 : nvox, 256, 8);
     bool any = false;

@@ -226,8 +226,8 @@ int pb3d_component_members_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0,
     p.nblocks = (int)nb;
     void *counts_d = nullptr, *offsets_d = nullptr;
     if (outputs & PB3D_MEMBERS_COORDS) {
-        PB3D_TRY(pb3d_scratch(ctx, 16, (size_t)nb * sizeof(u32), &counts_d));
-        PB3D_TRY(pb3d_scratch(ctx, 17, (size_t)nb * sizeof(i64), &offsets_d));
+        PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MEMBERS_COUNTS, (size_t)nb * sizeof(u32), &counts_d));
+        PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MEMBERS_OFFSETS, (size_t)nb * sizeof(i64), &offsets_d));
     }
     if (channels == 3)
         return launch_members<3>(ctx, d_grid, d_labels, p, outputs, (u32*)counts_d, (i64*)offsets_d, d_coords, d_rows, d_masks);

@@ -410,11 +410,11 @@ int make_mesh_params(const u8* d_grid, i64 A0, i64 A1, i64 A2, int C, int stride
     return PB3D_OK;
 }
 
-// bitmask of the lattice into slot 48
+// bitmask of the lattice into PB3D_SLOT_MESH_BITS
 int build_bits(pb3d_ctx* ctx, const MeshParams& p, u64** bits) {
     void* b;
     const i64 rows = p.n0 * p.n1;
-    PB3D_TRY(pb3d_scratch(ctx, 48, (size_t)(rows * p.W) * sizeof(u64), &b));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESH_BITS, (size_t)(rows * p.W) * sizeof(u64), &b));
     const i64 threads = rows * p.W * 64;
     hipLaunchKernelGGL(k_mesh_bits, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream, p, (u64*)b);
     PB3D_CHECK_LAUNCH();
@@ -429,6 +429,7 @@ extern "C" {
 int pb3d_mesh_count_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64_t A1, int64_t A2, int C, int stride,
                         int64_t* nverts, int64_t* nfaces) {
     PB3D_REQUIRE(ctx != nullptr && nverts != nullptr && nfaces != nullptr, "pb3d_mesh_count: null argument");
+    ctx->mesh_dev.pair.valid = false;
     *nverts = *nfaces = 0;
     MeshParams p;
     PB3D_TRY(make_mesh_params(d_grid, A0, A1, A2, C, stride, &p));
@@ -437,14 +438,14 @@ int pb3d_mesh_count_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64_
     u64* bits;
     PB3D_TRY(build_bits(ctx, p, &bits));
     void *vc, *fc, *vo, *fo;
-    PB3D_TRY(pb3d_scratch(ctx, 49, (size_t)nb * sizeof(u32), &vc));
-    PB3D_TRY(pb3d_scratch(ctx, 50, (size_t)nb * sizeof(u32), &fc));
-    PB3D_TRY(pb3d_scratch(ctx, 51, (size_t)(nb + 1) * sizeof(i64), &vo));
-    PB3D_TRY(pb3d_scratch(ctx, 52, (size_t)(nb + 1) * sizeof(i64), &fo));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESH_VERT_COUNTS, (size_t)nb * sizeof(u32), &vc));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESH_FACE_COUNTS, (size_t)nb * sizeof(u32), &fc));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESH_VERT_OFFSETS, (size_t)(nb + 1) * sizeof(i64), &vo));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESH_FACE_OFFSETS, (size_t)(nb + 1) * sizeof(i64), &fo));
     hipLaunchKernelGGL(k_mesh_count, dim3((unsigned)nb), dim3(256), 0, ctx->stream, p, (const u64*)bits, (u32*)vc, (u32*)fc);
     PB3D_CHECK_LAUNCH();
-    PB3D_TRY(pb3d_scan_counts(ctx, (const u32*)vc, nb, (i64*)vo, 53, 54));
-    PB3D_TRY(pb3d_scan_counts(ctx, (const u32*)fc, nb, (i64*)fo, 55, 56));
+    PB3D_TRY(pb3d_scan_counts(ctx, (const u32*)vc, nb, (i64*)vo, PB3D_SLOT_MESH_VSCAN_LOCAL, PB3D_SLOT_MESH_VSCAN_SEGS));
+    PB3D_TRY(pb3d_scan_counts(ctx, (const u32*)fc, nb, (i64*)fo, PB3D_SLOT_MESH_FSCAN_LOCAL, PB3D_SLOT_MESH_FSCAN_SEGS));
     i64 tot[2];
     PB3D_HIP(hipMemcpyAsync(&tot[0], (i64*)vo + nb, sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
     PB3D_HIP(hipMemcpyAsync(&tot[1], (i64*)fo + nb, sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
@@ -453,6 +454,8 @@ int pb3d_mesh_count_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64_
                  (long long)tot[0], (long long)tot[1]);
     *nverts = tot[0];
     *nfaces = tot[1];
+    ctx->mesh_dev.a = pb3d_ctx::MeshArgs{d_grid, A0, A1, A2, tot[0], tot[1], C, stride};
+    pb3d_pair_record(ctx, &ctx->mesh_dev.pair, {PB3D_SLOT_MESH_BITS, PB3D_SLOT_MESH_VERT_OFFSETS, PB3D_SLOT_MESH_FACE_OFFSETS});
     return PB3D_OK;
 }
 
@@ -479,19 +482,22 @@ int pb3d_mesh_fill_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64_t
     PB3D_TRY(make_mesh_params(d_grid, A0, A1, A2, C, stride, &p));
     if (nverts == 0) return PB3D_OK;
     PB3D_REQUIRE(d_verts && d_faces && d_normals, "pb3d_mesh_fill: null buffer");
+    PB3D_TRY(pb3d_pair_check(ctx, ctx->mesh_dev.pair,
+                             pb3d_same_args(ctx->mesh_dev.a, pb3d_ctx::MeshArgs{d_grid, A0, A1, A2, nverts, nfaces, C, stride}),
+                             "pb3d_mesh_fill", "pb3d_mesh_count"));
     const i64 nb = (p.ncubes + 255) / 256;
     const size_t bits_bytes = (size_t)(p.n0 * p.n1 * p.W) * sizeof(u64);
-    PB3D_REQUIRE(ctx->scratch[48] && ctx->scratch_bytes[48] >= bits_bytes && ctx->scratch[51] &&
-                     ctx->scratch_bytes[51] >= (size_t)(nb + 1) * sizeof(i64) && ctx->scratch[52] &&
-                     ctx->scratch_bytes[52] >= (size_t)(nb + 1) * sizeof(i64),
+    PB3D_REQUIRE(ctx->scratch[PB3D_SLOT_MESH_BITS] && ctx->scratch_bytes[PB3D_SLOT_MESH_BITS] >= bits_bytes &&
+                     ctx->scratch[PB3D_SLOT_MESH_VERT_OFFSETS] && ctx->scratch_bytes[PB3D_SLOT_MESH_VERT_OFFSETS] >= (size_t)(nb + 1) * sizeof(i64) &&
+                     ctx->scratch[PB3D_SLOT_MESH_FACE_OFFSETS] && ctx->scratch_bytes[PB3D_SLOT_MESH_FACE_OFFSETS] >= (size_t)(nb + 1) * sizeof(i64),
                  "pb3d_mesh_fill: call pb3d_mesh_count_dev on the same grid first");
-    const u64* bits = (const u64*)ctx->scratch[48];
+    const u64* bits = (const u64*)ctx->scratch[PB3D_SLOT_MESH_BITS];
     void* vb;
-    PB3D_TRY(pb3d_scratch(ctx, 57, (size_t)p.ncubes * sizeof(int), &vb));
-    hipLaunchKernelGGL(k_mesh_verts, dim3((unsigned)nb), dim3(256), 0, ctx->stream, p, bits, (const i64*)ctx->scratch[51], (int*)vb,
-                       d_verts, d_normals);
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESH_VERT_BASE, (size_t)p.ncubes * sizeof(int), &vb));
+    hipLaunchKernelGGL(k_mesh_verts, dim3((unsigned)nb), dim3(256), 0, ctx->stream, p, bits, (const i64*)ctx->scratch[PB3D_SLOT_MESH_VERT_OFFSETS],
+                       (int*)vb, d_verts, d_normals);
     PB3D_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_mesh_faces, dim3((unsigned)nb), dim3(256), 0, ctx->stream, p, bits, (const i64*)ctx->scratch[52],
+    hipLaunchKernelGGL(k_mesh_faces, dim3((unsigned)nb), dim3(256), 0, ctx->stream, p, bits, (const i64*)ctx->scratch[PB3D_SLOT_MESH_FACE_OFFSETS],
                        (const int*)vb, (int*)d_faces);
     PB3D_CHECK_LAUNCH();
     (void)nfaces;
@@ -511,34 +517,35 @@ int pb3d_mesh_count(pb3d_ctx* ctx, const uint8_t* grid, int64_t A0, int64_t A1, 
                     int64_t* nverts, int64_t* nfaces) {
     PB3D_REQUIRE(ctx != nullptr && nverts != nullptr && nfaces != nullptr, "pb3d_mesh_count: null argument");
     PB3D_REQUIRE(A0 >= 0 && A1 >= 0 && A2 >= 0 && (C == 1 || C == 3) && stride >= 1, "pb3d_mesh_count: bad shape");
-    ctx->mesh.valid = false;
+    ctx->mesh.pair.valid = false;
     const size_t nb = (size_t)(A0 * A1 * A2 * C);
     PB3D_REQUIRE(grid != nullptr || nb == 0, "pb3d_mesh_count: null grid");
     void* dg = nullptr;
-    PB3D_TRY(pb3d_scratch(ctx, 0, nb ? nb : 1, &dg));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_HOST_IN0, nb ? nb : 1, &dg));
     if (nb) PB3D_HIP(hipMemcpyAsync(dg, grid, nb, hipMemcpyHostToDevice, ctx->stream));
     PB3D_TRY(pb3d_mesh_count_dev(ctx, (const u8*)dg, A0, A1, A2, C, stride, nverts, nfaces));
-    ctx->mesh.A0 = A0; ctx->mesh.A1 = A1; ctx->mesh.A2 = A2; ctx->mesh.C = C; ctx->mesh.stride = stride;
-    ctx->mesh.nv = *nverts; ctx->mesh.nf = *nfaces;
-    ctx->mesh.valid = true;
+    ctx->mesh.a = pb3d_ctx::MeshArgs{dg, A0, A1, A2, *nverts, *nfaces, C, stride};
+    pb3d_pair_record(ctx, &ctx->mesh.pair, {PB3D_SLOT_HOST_IN0});
     return PB3D_OK;
 }
 
+// the device fill checks the device pair that pb3d_mesh_count ran
 int pb3d_mesh_fill(pb3d_ctx* ctx, int64_t nverts, int64_t nfaces, float* verts, int32_t* faces, float* normals, uint8_t* cols) {
     PB3D_REQUIRE(ctx != nullptr, "pb3d_mesh_fill: null context");
-    PB3D_REQUIRE(ctx->mesh.valid, "pb3d_mesh_fill: call pb3d_mesh_count first");
-    PB3D_REQUIRE(nverts == ctx->mesh.nv && nfaces == ctx->mesh.nf, "pb3d_mesh_fill: sizes do not match the count");
-    ctx->mesh.valid = false;
+    const pb3d_ctx::MeshArgs& a = ctx->mesh.a;
+    PB3D_TRY(pb3d_pair_check(ctx, ctx->mesh.pair, true, "pb3d_mesh_fill", "pb3d_mesh_count"));
+    PB3D_REQUIRE(nverts == a.nv && nfaces == a.nf, "pb3d_mesh_fill: sizes do not match the count");
+    ctx->mesh.pair.valid = false;
     if (nverts == 0) return PB3D_OK;
     PB3D_REQUIRE(verts && faces && normals, "pb3d_mesh_fill: null buffer");
-    const int C = ctx->mesh.C;
+    const int C = (int)a.C;
     void *dv, *df, *dn, *dc = nullptr;
-    PB3D_TRY(pb3d_scratch(ctx, 1, (size_t)nverts * 3 * sizeof(float), &dv));
-    PB3D_TRY(pb3d_scratch(ctx, 2, (size_t)nfaces * 3 * sizeof(int32_t), &df));
-    PB3D_TRY(pb3d_scratch(ctx, 3, (size_t)nverts * 3 * sizeof(float), &dn));
-    if (cols) PB3D_TRY(pb3d_scratch(ctx, 4, (size_t)nverts * C, &dc));
-    PB3D_TRY(pb3d_mesh_fill_dev(ctx, (const u8*)ctx->scratch[0], ctx->mesh.A0, ctx->mesh.A1, ctx->mesh.A2, C, ctx->mesh.stride,
-                                nverts, nfaces, (float*)dv, (int32_t*)df, (float*)dn, (u8*)dc));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_HOST_OUT0, (size_t)nverts * 3 * sizeof(float), &dv));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_HOST_OUT1, (size_t)nfaces * 3 * sizeof(int32_t), &df));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_HOST_OUT2, (size_t)nverts * 3 * sizeof(float), &dn));
+    if (cols) PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESH_HOST_COLS, (size_t)nverts * C, &dc));
+    PB3D_TRY(pb3d_mesh_fill_dev(ctx, (const u8*)a.grid, a.A0, a.A1, a.A2, C, (int)a.stride, nverts, nfaces, (float*)dv, (int32_t*)df, (float*)dn,
+                                (u8*)dc));
     PB3D_HIP(hipMemcpyAsync(verts, dv, (size_t)nverts * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     PB3D_HIP(hipMemcpyAsync(faces, df, (size_t)nfaces * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     PB3D_HIP(hipMemcpyAsync(normals, dn, (size_t)nverts * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));

@@ -77,12 +77,12 @@ __global__ __launch_bounds__(64) void k_bounds_final(const double* __restrict__ 
     out[c] = v;
 }
 
-// d_out: 6 doubles; scratch slot 41 holds the partials
+// d_out: 6 doubles; PB3D_SLOT_NN_BOUNDS_PARTIALS holds the partials
 int launch_bounds(pb3d_ctx* ctx, const void* d_pts, int f64, i64 n, double* d_out) {
     const unsigned need = pb3d_stream_blocks(ctx, n, 256, 2);
     const unsigned nb = need < (unsigned)kBoundsBlocks ? need : (unsigned)kBoundsBlocks;
     void* part;
-    PB3D_TRY(pb3d_scratch(ctx, 41, (size_t)kBoundsBlocks * 6 * sizeof(double), &part));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_NN_BOUNDS_PARTIALS, (size_t)kBoundsBlocks * 6 * sizeof(double), &part));
     if (f64) hipLaunchKernelGGL(k_bounds_partial<true>, dim3(nb), dim3(256), 0, ctx->stream, d_pts, n, (double*)part);
     else hipLaunchKernelGGL(k_bounds_partial<false>, dim3(nb), dim3(256), 0, ctx->stream, d_pts, n, (double*)part);
     PB3D_CHECK_LAUNCH();
@@ -370,14 +370,14 @@ int launch_occ(pb3d_ctx* ctx, const void* d_pts, int f64, i64 n, const Occ& o, u
 }
 
 template <bool F64>
-int bin_points(pb3d_ctx* ctx, const void* d_pts, i64 n, const Grid& g, int count_slot, int start_slot, u32** counts, i64** start) {
+int bin_points(pb3d_ctx* ctx, const void* d_pts, i64 n, const Grid& g, pb3d_slot count_slot, pb3d_slot start_slot, u32** counts, i64** start) {
     void *c, *s;
     PB3D_TRY(pb3d_scratch(ctx, count_slot, (size_t)g.ncells * sizeof(u32), &c));
     PB3D_TRY(pb3d_scratch(ctx, start_slot, (size_t)(g.ncells + 1) * sizeof(i64), &s));
     PB3D_HIP(hipMemsetAsync(c, 0, (size_t)g.ncells * sizeof(u32), ctx->stream));
     hipLaunchKernelGGL(k_cell_count<F64>, dim3(pb3d_stream_blocks(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, d_pts, n, g, (u32*)c);
     PB3D_CHECK_LAUNCH();
-    PB3D_TRY(pb3d_scan_counts(ctx, (const u32*)c, g.ncells, (i64*)s, 31, 33));
+    PB3D_TRY(pb3d_scan_counts(ctx, (const u32*)c, g.ncells, (i64*)s, PB3D_SLOT_NN_SCAN_LOCAL, PB3D_SLOT_NN_SCAN_SEGS));
     PB3D_HIP(hipMemsetAsync(c, 0, (size_t)g.ncells * sizeof(u32), ctx->stream));      // the scatter's cursors
     *counts = (u32*)c;
     *start = (i64*)s;
@@ -389,14 +389,14 @@ int nn_run(pb3d_ctx* ctx, const void* d_q, i64 nq, const void* d_r, i64 nr, int 
     u32 *rc, *qc;
     i64 *rs, *qs;
     void *soa, *order;
-    PB3D_TRY(bin_points<RF64>(ctx, d_r, nr, g, 18, 19, &rc, &rs));
-    PB3D_TRY(pb3d_scratch(ctx, 27, (size_t)nr * 3 * sizeof(double), &soa));
+    PB3D_TRY(bin_points<RF64>(ctx, d_r, nr, g, PB3D_SLOT_NN_REF_COUNTS, PB3D_SLOT_NN_REF_STARTS, &rc, &rs));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_NN_REF_COORDS, (size_t)nr * 3 * sizeof(double), &soa));
     double* xs = (double*)soa;
     hipLaunchKernelGGL(k_cell_scatter_ref<RF64>, dim3(pb3d_stream_blocks(ctx, nr, 256, 8)), dim3(256), 0, ctx->stream, d_r, nr, g,
                        (const i64*)rs, rc, xs, xs + nr, xs + 2 * nr);
     PB3D_CHECK_LAUNCH();
-    PB3D_TRY(bin_points<QF64>(ctx, d_q, nq, g, 28, 29, &qc, &qs));
-    PB3D_TRY(pb3d_scratch(ctx, 30, (size_t)nq * sizeof(u32), &order));
+    PB3D_TRY(bin_points<QF64>(ctx, d_q, nq, g, PB3D_SLOT_NN_QUERY_COUNTS, PB3D_SLOT_NN_QUERY_STARTS, &qc, &qs));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_NN_ORDER, (size_t)nq * sizeof(u32), &order));
     hipLaunchKernelGGL(k_cell_scatter_query<QF64>, dim3(pb3d_stream_blocks(ctx, nq, 256, 8)), dim3(256), 0, ctx->stream, d_q, nq, g,
                        (const i64*)qs, qc, (u32*)order);
     PB3D_CHECK_LAUNCH();
@@ -429,7 +429,7 @@ int pb3d_nn_dist_dev(pb3d_ctx* ctx, const void* d_q, int q_f64, int64_t nq, cons
     PB3D_REQUIRE(d_q != nullptr && d_r != nullptr && d_out != nullptr, "pb3d_nn_dist: null buffer");
     PB3D_REQUIRE(ctx != nullptr, "pb3d_nn_dist: null context");
     void* bb;
-    PB3D_TRY(pb3d_scratch(ctx, 47, 6 * sizeof(double), &bb));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_NN_BOUNDS, 6 * sizeof(double), &bb));
     double* d_b = (double*)bb;
     PB3D_TRY(launch_bounds(ctx, d_r, r_f64, nr, d_b));
     PB3D_HIP(hipMemcpyAsync(ctx->pinned, d_b, 6 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -468,7 +468,7 @@ int pb3d_voxel_iou_counts_dev(pb3d_ctx* ctx, const void* d_a, int a_f64, int64_t
     o.step = step;
     const i64 gw = (i64)resolution * resolution * o.W;      // words of one bit grid
     void *buf, *tmp;
-    PB3D_TRY(pb3d_scratch(ctx, 44, (size_t)gw * 2 * sizeof(u32), &buf));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_VIOU_BITS, (size_t)gw * 2 * sizeof(u32), &buf));
     u32* bits = (u32*)buf;
     PB3D_HIP(hipMemsetAsync(bits, 0, (size_t)gw * 2 * sizeof(u32), ctx->stream));
     if (calc_f32) {
@@ -481,7 +481,7 @@ int pb3d_voxel_iou_counts_dev(pb3d_ctx* ctx, const void* d_a, int a_f64, int64_t
     // the dilated set is the L1 ball of radius iters clipped to the grid: it stops changing after 3 (res - 1) passes
     const int passes = iters < 3 * (resolution - 1) ? iters : 3 * (resolution - 1);
     if (passes > 0) {
-        PB3D_TRY(pb3d_scratch(ctx, 45, (size_t)gw * 2 * sizeof(u32), &tmp));
+        PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_VIOU_DILATED, (size_t)gw * 2 * sizeof(u32), &tmp));
         const u32 lastmask = (resolution & 31) ? (1u << (resolution & 31)) - 1u : 0xffffffffu;
         u32 *src = bits, *dst = (u32*)tmp;
         for (int p = 0; p < passes; ++p) {

@@ -6,6 +6,8 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
+#include <type_traits>
 
 #include "pb3d.h"
 
@@ -14,7 +16,127 @@ typedef int64_t i64;
 typedef uint64_t u64;
 typedef uint32_t u32;
 
-#define PB3D_NSCRATCH 58
+// ---- scratch slots ----------------------------------------------------------------------------
+// The growable device buffers of a context (pb3d_scratch).  Each has one of three lifetimes:
+//   call-local  free again when the entry that requested it returns;
+//   pair state  written by a *_count and read by its *_fill (struct pb3d_pair: the fill refuses if the slot was requested in between);
+//   cache       kept across calls, keyed by scratch_gen / scratch_slot_gen.
+// Two names with one value share the buffer on purpose.  The numbers are fixed: the order and sizes of an op's requests decide when
+// a slot regrows, and a regrow synchronises the stream and drops the cached rotation tables (scratch_gen).
+enum pb3d_slot : int {
+    // call-local, csrc/api_host.hip (and the host flavours in mesh.hip, deform.hip): staged inputs and outputs of the host-pointer
+    // entries.  Pair state of the host points / mesh pairs: their count leaves the staged grid in HOST_IN0 for the fill.
+    PB3D_SLOT_HOST_IN0 = 0,
+    PB3D_SLOT_HOST_OUT0 = 1,
+    PB3D_SLOT_HOST_IN1 = 2,
+    PB3D_SLOT_HOST_OUT1 = PB3D_SLOT_HOST_IN1,           // pb3d_mesh_fill's faces
+    PB3D_SLOT_HOST_IN2 = 3,                             // pb3d_part_carve's carve masks
+    PB3D_SLOT_HOST_OUT2 = PB3D_SLOT_HOST_IN2,           // pb3d_points_fill's colours, pb3d_mesh_fill's normals
+    PB3D_SLOT_HOST_TMP = PB3D_SLOT_HOST_IN2,            // pb3d_process_grid's ping-pong volume
+    // call-local, volume temporaries shared by part_carve (csrc/carve.hip), global_carve (global.hip), the label forms (label.hip),
+    // CCL (ccl.hip), component statistics (components.hip), pb3d_try_part_carve90 (rotate_tiled.hip) and pb3d_mesh_fill (mesh.hip)
+    PB3D_SLOT_VOL_OCC = 4,                              // occupancy / all-ones volume of a carve chain
+    PB3D_SLOT_VOL_CARVED = 5,
+    PB3D_SLOT_VOL_TMP = 6,
+    PB3D_SLOT_VOL_KEEP = 7,
+    PB3D_SLOT_MASK_WH = PB3D_SLOT_VOL_KEEP,             // global_carve / label forms: the transposed (W,H) mask
+    PB3D_SLOT_PART90_JOBS = PB3D_SLOT_VOL_CARVED,       // pb3d_try_part_carve90: job bits per (x, y) column
+    PB3D_SLOT_CCL_ROOT_BITS = PB3D_SLOT_VOL_CARVED,
+    PB3D_SLOT_CCL_CHUNKS = PB3D_SLOT_VOL_TMP,
+    PB3D_SLOT_STATS_BOXES = PB3D_SLOT_VOL_TMP,          // pb3d_component_stats_dev
+    PB3D_SLOT_STATS_SUMS = PB3D_SLOT_VOL_KEEP,
+    PB3D_SLOT_RECOLOR_FLAGS = PB3D_SLOT_VOL_TMP,        // the recolouring's per-component flags
+    PB3D_SLOT_SELECT_FLAGS = PB3D_SLOT_VOL_KEEP,        // top-k / backward recolouring: the selection made on the device
+    PB3D_SLOT_MESH_HOST_COLS = PB3D_SLOT_VOL_OCC,       // pb3d_mesh_fill's colours
+    // call-local, csrc/points.hip: the count pass and its scan
+    PB3D_SLOT_BLOCK_COUNTS = 8,
+    PB3D_SLOT_SCAN_LOCAL = 11,
+    PB3D_SLOT_SCAN_SEGS = 15,
+    PB3D_SLOT_PROJ_WINNER = PB3D_SLOT_BLOCK_COUNTS,     // csrc/project.hip: winner images
+    PB3D_SLOT_DEFORM_ACC = PB3D_SLOT_SCAN_LOCAL,        // csrc/deform.hip: sums, bounding box, out-of-bounds flag
+    // pair state, csrc/points.hip: pb3d_points_count_dev -> pb3d_points_fill_dev (block offsets, 16-voxel selection masks)
+    PB3D_SLOT_POINTS_OFFSETS = 9,
+    PB3D_SLOT_POINTS_MASKS = 25,
+    // call-local, csrc/points.hip: pb3d_points_extract_dev, apart from the pair above (it may run between the pair's halves)
+    PB3D_SLOT_EXTRACT_OFFSETS = 24,
+    PB3D_SLOT_EXTRACT_MASKS = 26,
+    // pair state, csrc/deform.hip: pb3d_deform_count* -> pb3d_deform_fill* (with the points pair, which the count runs on it)
+    PB3D_SLOT_DEFORM_MARKS = 12,
+    PB3D_SLOT_DEFORM_BATCH_MARKS = PB3D_SLOT_DEFORM_MARKS,  // call-local: pb3d_deform_iou_batch_dev
+    // call-local, csrc/deform.hip: pb3d_deform_fill_dev's points
+    PB3D_SLOT_DEFORM_PTS = 13,
+    PB3D_SLOT_DEFORM_COLS = 14,
+    // call-local, csrc/project.hip and deform.hip: the camera / deformation batches
+    PB3D_SLOT_PROJ_BATCH_CAMS = 20,
+    PB3D_SLOT_PROJ_BATCH_COUNTS = 21,
+    PB3D_SLOT_PROJ_BATCH_COLORS = 22,
+    PB3D_SLOT_DEFORM_BATCH_TUPLES = PB3D_SLOT_PROJ_BATCH_CAMS,
+    PB3D_SLOT_DEFORM_BATCH_COUNTS = PB3D_SLOT_PROJ_BATCH_COUNTS,
+    // call-local, csrc/members.hip
+    PB3D_SLOT_MEMBERS_COUNTS = 16,
+    PB3D_SLOT_MEMBERS_OFFSETS = 17,
+    // call-local, csrc/label.hip
+    PB3D_SLOT_LABEL_FLAG = 23,
+    // call-local, csrc/nn.hip: the cell index of the NN search, the bounds, the voxel IoU's bit grids
+    PB3D_SLOT_NN_REF_COUNTS = 18,
+    PB3D_SLOT_NN_REF_STARTS = 19,
+    PB3D_SLOT_NN_REF_COORDS = 27,
+    PB3D_SLOT_NN_QUERY_COUNTS = 28,
+    PB3D_SLOT_NN_QUERY_STARTS = 29,
+    PB3D_SLOT_NN_ORDER = 30,
+    PB3D_SLOT_NN_SCAN_LOCAL = 31,
+    PB3D_SLOT_NN_SCAN_SEGS = 33,
+    PB3D_SLOT_NN_BOUNDS_PARTIALS = 41,
+    PB3D_SLOT_NN_BOUNDS = 47,
+    PB3D_SLOT_VIOU_BITS = 44,
+    PB3D_SLOT_VIOU_DILATED = 45,
+    // cache, csrc/rotate_tiled.hip: the validity table of the last 90-degree step (valid_cache)
+    PB3D_SLOT_ROT_VALID_TABLE = 10,
+    // call-local, csrc/rotate_tiled.hip: pb3d_try_part_carve90's transposed job bits
+    PB3D_SLOT_PART90_JOBS_T = 46,
+    // cache, csrc/sliced.hip: the tile programs of the bit-sliced chain (s32_cache)
+    PB3D_SLOT_S32_TILE_PROGRAMS = 32,
+    // call-local, csrc/sliced.hip
+    PB3D_SLOT_SLICED_FLAG = 34,
+    PB3D_SLOT_SLICED_MASK_BITS = 35,
+    // call-local, csrc/guided.hip
+    PB3D_SLOT_GUIDED_DESCS = 36,
+    PB3D_SLOT_GUIDED_MASKS = 37,
+    PB3D_SLOT_GUIDED_TABLES = 38,
+    PB3D_SLOT_GUIDED_COUNTS = 39,
+    PB3D_SLOT_GUIDED_SLICES = 43,
+    // call-local, csrc/ccl.hip: counts and statistics records of a labelling (read by the caller of pb3d_ccl_label_on_device)
+    PB3D_SLOT_CCL_RECORDS = 40,
+    // cache, csrc/ccl.hip: the membership bits of the last labelled volume (ccl_last)
+    PB3D_SLOT_CCL_MEMBER_BITS = 42,
+    // pair state, csrc/mesh.hip: pb3d_mesh_count_dev -> pb3d_mesh_fill_dev (pb3d_mesh_colors_dev rebuilds MESH_BITS)
+    PB3D_SLOT_MESH_BITS = 48,
+    PB3D_SLOT_MESH_VERT_OFFSETS = 51,
+    PB3D_SLOT_MESH_FACE_OFFSETS = 52,
+    // call-local, csrc/mesh.hip
+    PB3D_SLOT_MESH_VERT_COUNTS = 49,
+    PB3D_SLOT_MESH_FACE_COUNTS = 50,
+    PB3D_SLOT_MESH_VSCAN_LOCAL = 53,
+    PB3D_SLOT_MESH_VSCAN_SEGS = 54,
+    PB3D_SLOT_MESH_FSCAN_LOCAL = 55,
+    PB3D_SLOT_MESH_FSCAN_SEGS = 56,
+    PB3D_SLOT_MESH_VERT_BASE = 57,
+    // call-local, csrc/project.hip: pb3d_partwise_iou_dev's counters.  A slot of their own (they once shared POINTS_OFFSETS):
+    // the IoU may run between the halves of a points pair
+    PB3D_SLOT_IOU_COUNTS = 58,
+
+    PB3D_SLOT_COUNT = 59
+};
+
+// What a *_count leaves for its *_fill: the use counters (pb3d_ctx::scratch_use) of the slots the fill reads, taken when the count has
+// written them.  The fill's arguments are kept next to it, in the pair's own record of pb3d_ctx.
+struct pb3d_pair {
+    bool valid;
+    int nslots;
+    pb3d_slot slot[3];
+    u64 use[3];
+};
+
 #define PB3D_POOL_SLOTS 64
 #define PB3D_POOL_LIVE 4096
 
@@ -53,10 +175,9 @@ struct pb3d_ctx {
     int tune_ccl_init_blocks;   // knob "ccl_init_blocks": workgroups per CU of the labelling's first pass (0 = 16)
     int tune_ccl_tilecols;      // knob "ccl_tilecols": windows per level of a plane-to-plane merge tile (0 = 32)
     int tune_ccl_merge;         // knob "ccl_merge": 0 = tile kernels where the rows fit, 1 = always the pairwise kernel (development A/B)
-    // Growable device scratch slots used by the host-pointer entry points (no hipMalloc /
-    // hipFree per call once warm).
-    void* scratch[PB3D_NSCRATCH];
-    size_t scratch_bytes[PB3D_NSCRATCH];
+    // Growable device scratch slots, named by enum pb3d_slot (no hipMalloc / hipFree per call once warm).
+    void* scratch[PB3D_SLOT_COUNT];
+    size_t scratch_bytes[PB3D_SLOT_COUNT];
     // small pinned host area for counters read back from the device
     void* pinned;
     size_t pinned_bytes;
@@ -64,28 +185,21 @@ struct pb3d_ctx {
     void* stage;
     size_t stage_bytes, stage_head;
     u64 sync_count;             // host waits on the context's stream so far (pb3d_sync_count: tests bound the waits of a pipeline)
-    // state kept between pb3d_points_count and pb3d_points_fill (host-pointer flavour)
-    struct {
-        i64 A0, A1, A2, n;
-        int C, ncolors, stride;
-        u8 colors[3 * 32];
-        bool valid;
-    } pts;
-    // what pb3d_mesh_count staged (grid in scratch slot 0) for the pb3d_mesh_fill that follows it
-    struct { i64 A0, A1, A2, nv, nf; int C, stride; bool valid; } mesh;
-    // state kept between pb3d_deform_count and pb3d_deform_fill
-    struct {
-        int ox, oy, oz;
-        i64 X, Y, Z, n;
-        bool valid;
-    } deform;
-    struct ValidCache { void* buf; u64 gen; i64 W, D; double p[8]; } valid_cache;   // validity bit table of the last 90-degree step (scratch slot 10)
-    // Tile programs of the bit-sliced chain (csrc/sliced.hip, scratch slot 32): valid for these steps on this (W, D)
+    // count -> fill pairs (pb3d_pair_record / pb3d_pair_check): each count's record and the arguments its fill repeats.  The host
+    // flavours' grids are staged in PB3D_SLOT_HOST_IN0; pb3d_deform_count* runs the device points pair on PB3D_SLOT_DEFORM_MARKS.
+    // The argument records are compared byte for byte (pb3d_same_args): 8-byte members only, unused colour bytes zero.
+    struct PointsArgs { const void* grid; i64 A0, A1, A2, n, C, ncolors, stride; u8 colors[3 * 32]; };
+    struct { pb3d_pair pair; PointsArgs a; } pts_dev, pts;
+    struct MeshArgs { const void* grid; i64 A0, A1, A2, nv, nf, C, stride; };
+    struct { pb3d_pair pair; MeshArgs a; } mesh_dev, mesh;
+    struct { pb3d_pair pair; int ox, oy, oz; i64 X, Y, Z, n; } deform;
+    struct ValidCache { void* buf; u64 gen; i64 W, D; double p[8]; } valid_cache;   // validity bit table of the last 90-degree step (PB3D_SLOT_ROT_VALID_TABLE)
+    // Tile programs of the bit-sliced chain (csrc/sliced.hip, PB3D_SLOT_S32_TILE_PROGRAMS): valid for these steps on this (W, D)
     struct S32Cache { bool valid; u64 gen; i64 W, D; int ns; double p[32 * 8]; } s32_cache;
     hipEvent_t s32_ev;          // recorded behind the slice kernel's "not 0/1" flag copy
-    // membership bits of the last labelled volume (csrc/ccl.hip, scratch slot 42): word row * P + t, bit = voxel is a member
+    // membership bits of the last labelled volume (csrc/ccl.hip, PB3D_SLOT_CCL_MEMBER_BITS): word row * P + t, bit = voxel is a member
     // of colour k (K colours labelled together, csrc/ccl.hip: their numbering is per colour, so a label needs its colour's bits to mean anything
-    // once K > 1).  gen = scratch_slot_gen[42] when the bits were written: only a reallocation of THAT slot invalidates them.
+    // once K > 1).  gen = scratch_slot_gen[PB3D_SLOT_CCL_MEMBER_BITS] when the bits were written: only a reallocation of THAT slot invalidates them.
     struct CclLast { bool valid; const void* labels; const void* bits; i64 rows, A2, P; u64 gen; bool members_only; int K, C; u32 colors[PB3D_CCL_MAX_COLORS]; } ccl_last;
     // Device block pool behind pb3d_dev_alloc / pb3d_dev_free: a freed block is kept (no hipFree, no stream synchronisation) and handed
     // to the next request of about its size.  Everything that touches such a block runs on ctx->stream, in order, so a re-used block
@@ -99,7 +213,8 @@ struct pb3d_ctx {
     size_t pool_cached, pool_cap;       // bytes held in pool_free; its limit (PB3D_DEVICE_POOL_MB, default a quarter of the HBM, 0 = off)
     u64 pool_stamp;
     u64 scratch_gen;            // bumped whenever ANY scratch slot is reallocated (cached tables in other slots may have moved)
-    u64 scratch_slot_gen[PB3D_NSCRATCH];    // ... and per slot
+    u64 scratch_slot_gen[PB3D_SLOT_COUNT];  // ... and per slot
+    u64 scratch_use[PB3D_SLOT_COUNT];       // requests of each slot, regrown or not (struct pb3d_pair)
     // RCCL (loaded lazily with dlopen; see comm.hip)
     void* rccl_lib;
     void* rccl_comm;
@@ -134,8 +249,27 @@ void pb3d_set_error(const char* fmt, ...);
 
 #define PB3D_CHECK_LAUNCH() PB3D_HIP(hipGetLastError())
 
-// scratch slot `slot` grown to at least `bytes`
-int pb3d_scratch(pb3d_ctx* ctx, int slot, size_t bytes, void** out);
+// scratch slot `slot` grown to at least `bytes`; counts the request in scratch_use[slot]
+int pb3d_scratch(pb3d_ctx* ctx, pb3d_slot slot, size_t bytes, void** out);
+
+// ---- count / fill pairs ---------------------------------------------------------------------
+// A count records the slots (at most 3) its fill will read once it has written them; the fill calls pb3d_pair_check before any device work.
+void pb3d_pair_record(pb3d_ctx* ctx, pb3d_pair* pr, std::initializer_list<pb3d_slot> slots);
+// PB3D_OK if the count's state is still there: recorded, none of its slots requested since, and the fill repeats the count's
+// arguments (same_args).  Else PB3D_EINVAL with a message that names the pair.
+int pb3d_pair_check(const pb3d_ctx* ctx, const pb3d_pair& pr, bool same_args, const char* fill, const char* count);
+template <class Args>
+bool pb3d_same_args(const Args& a, const Args& b) {
+    static_assert(std::has_unique_object_representations_v<Args>, "an argument record compared byte for byte must have no padding");
+    return memcmp(&a, &b, sizeof(Args)) == 0;
+}
+// the points pair's argument record; colors: ncolors RGB triples, or ncolors 1-byte labels when C == 1 (0 <= ncolors <= 32)
+static inline pb3d_ctx::PointsArgs pb3d_points_args(const void* grid, i64 A0, i64 A1, i64 A2, int C, const u8* colors, int ncolors,
+                                                    int stride, i64 n) {
+    pb3d_ctx::PointsArgs a{grid, A0, A1, A2, n, C, ncolors, stride, {}};
+    if (ncolors) memcpy(a.colors, colors, (size_t)(C == 1 ? 1 : 3) * ncolors);
+    return a;
+}
 // hipStreamSynchronize(ctx->stream) + bookkeeping (the staging ring is empty afterwards)
 int pb3d_stream_sync(pb3d_ctx* ctx);
 
@@ -186,7 +320,7 @@ int pb3d_ccl_label_on_device(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, i
 
 // ---- kernels' host launchers used across translation units ---------------------------------
 // exclusive scan of n u32 counts into n + 1 int64 offsets (the last = total) with points.hip's scan kernels; scratch slots local_slot, seg_slot
-int pb3d_scan_counts(pb3d_ctx* ctx, const u32* d_counts, i64 n, i64* d_offsets, int local_slot, int seg_slot);
+int pb3d_scan_counts(pb3d_ctx* ctx, const u32* d_counts, i64 n, i64* d_offsets, pb3d_slot local_slot, pb3d_slot seg_slot);
 // process_voxel_grid through the bit-sliced chain (csrc/sliced.hip); *took = 0: not applicable, nothing written
 int pb3d_process_grid_sliced(pb3d_ctx* ctx, const u8* d_occ, i64 W, i64 H, i64 D, const u8* d_mask_wh, int angle_interval, u8* d_out,
                              int known_binary, int* took);

@@ -495,10 +495,10 @@ bool aligned16(const u8* d_grid, int stride) { return stride == 1 && (((uintptr_
 // The count pass and the scan of the block counts; *n = the number of selected voxels.  What the fill pass of the same grid and selection
 // reads stays in the context's scratch: the scanned block offsets in slot off_slot and (the 16-voxel kernels) the selection masks in
 // slot mask_slot.  Synchronises (returns *n).
-int count_pass(pb3d_ctx* ctx, const u8* d_grid, const SelParams& p, bool fast16, int off_slot, int mask_slot, i64* n) {
+int count_pass(pb3d_ctx* ctx, const u8* d_grid, const SelParams& p, bool fast16, pb3d_slot off_slot, pb3d_slot mask_slot, i64* n) {
     const i64 nb = (p.nlat + kBlockVox - 1) / kBlockVox;
     void *counts, *offsets;
-    PB3D_TRY(pb3d_scratch(ctx, 8, (size_t)nb * sizeof(u32), &counts));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_BLOCK_COUNTS, (size_t)nb * sizeof(u32), &counts));
     PB3D_TRY(pb3d_scratch(ctx, off_slot, (size_t)(nb + 1) * sizeof(i64), &offsets));
     void* masks = nullptr;
     if (fast16) PB3D_TRY(pb3d_scratch(ctx, mask_slot, (size_t)nb * 256 * sizeof(unsigned short), &masks));
@@ -510,9 +510,9 @@ int count_pass(pb3d_ctx* ctx, const u8* d_grid, const SelParams& p, bool fast16,
     {
         const i64 nseg = (nb + kSeg - 1) / kSeg;
         void *local, *segs;
-        PB3D_TRY(pb3d_scratch(ctx, 11, (size_t)nb * sizeof(u32), &local));
-        PB3D_TRY(pb3d_scratch(ctx, 15, 64 + (size_t)nseg * (sizeof(u32) + sizeof(i64)), &segs));
-        i64* seg_base = (i64*)((u8*)segs + 64);                    // [0,64): the rotate kernels' flag word lives in this slot
+        PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_SCAN_LOCAL, (size_t)nb * sizeof(u32), &local));
+        PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_SCAN_SEGS, 64 + (size_t)nseg * (sizeof(u32) + sizeof(i64)), &segs));
+        i64* seg_base = (i64*)((u8*)segs + 64);                    // [0,64): unused (it held the rotate kernels' flag word once)
         u32* seg_total = (u32*)(seg_base + nseg);
         hipLaunchKernelGGL(k_scan_local, dim3((unsigned)nseg), dim3(256), 0, ctx->stream, (const u32*)counts, nb, (u32*)local, seg_total);
         PB3D_CHECK_LAUNCH();
@@ -529,7 +529,7 @@ int count_pass(pb3d_ctx* ctx, const u8* d_grid, const SelParams& p, bool fast16,
 }
 
 // The fill pass after count_pass(off_slot, mask_slot) on the same grid and selection.  d_pts: n*3 floats, d_cols: n*C bytes.
-int fill_pass(pb3d_ctx* ctx, const u8* d_grid, const SelParams& p, bool fast16, int off_slot, int mask_slot, float* d_pts, u8* d_cols) {
+int fill_pass(pb3d_ctx* ctx, const u8* d_grid, const SelParams& p, bool fast16, pb3d_slot off_slot, pb3d_slot mask_slot, float* d_pts, u8* d_cols) {
     const i64 nb = (p.nlat + kBlockVox - 1) / kBlockVox;
     PB3D_REQUIRE(ctx->scratch[off_slot] && ctx->scratch_bytes[off_slot] >= (size_t)(nb + 1) * sizeof(i64),
                  "pb3d_points_fill: call pb3d_points_count first");
@@ -548,7 +548,7 @@ int fill_pass(pb3d_ctx* ctx, const u8* d_grid, const SelParams& p, bool fast16, 
 
 // The exclusive scan of count_pass on any u32 count array (the cell index of csrc/nn.hip): offsets[0..n) and offsets[n] = total.
 // Slot local_slot holds n u32 in-segment offsets, slot seg_slot the segment totals and bases.  Enqueue only.
-int pb3d_scan_counts(pb3d_ctx* ctx, const u32* d_counts, i64 n, i64* d_offsets, int local_slot, int seg_slot) {
+int pb3d_scan_counts(pb3d_ctx* ctx, const u32* d_counts, i64 n, i64* d_offsets, pb3d_slot local_slot, pb3d_slot seg_slot) {
     const i64 nseg = (n + kSeg - 1) / kSeg;
     void *local, *segs;
     PB3D_TRY(pb3d_scratch(ctx, local_slot, (size_t)n * sizeof(u32), &local));
@@ -570,17 +570,21 @@ extern "C" {
 int pb3d_points_count_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64_t A1, int64_t A2, int C,
                           const uint8_t* colors, int ncolors, int stride, int64_t* n) {
     PB3D_REQUIRE(ctx != nullptr && n != nullptr, "pb3d_points_count: null argument");
+    ctx->pts_dev.pair.valid = false;
     SelParams p;
     PB3D_TRY(make_params(A0, A1, A2, C, colors, ncolors, stride, &p));
     *n = 0;
     if (p.nlat == 0) return PB3D_OK;
     PB3D_REQUIRE(d_grid != nullptr, "pb3d_points_count: null grid");
     PB3D_REQUIRE((p.nlat + kBlockVox - 1) / kBlockVox < (1ll << 31), "pb3d_points_count: grid too large");
-    return count_pass(ctx, d_grid, p, aligned16(d_grid, stride), 9, 25, n);
+    PB3D_TRY(count_pass(ctx, d_grid, p, aligned16(d_grid, stride), PB3D_SLOT_POINTS_OFFSETS, PB3D_SLOT_POINTS_MASKS, n));
+    ctx->pts_dev.a = pb3d_points_args(d_grid, A0, A1, A2, C, colors, ncolors, stride, *n);
+    pb3d_pair_record(ctx, &ctx->pts_dev.pair, {PB3D_SLOT_POINTS_OFFSETS, PB3D_SLOT_POINTS_MASKS});
+    return PB3D_OK;
 }
 
-// Must follow pb3d_points_count_dev with identical arguments on the same context (the scanned block
-// offsets and the selection masks stay in the context's scratch, slots 9 and 25).  d_pts: n*3 floats, d_cols: n*C bytes.
+// Must follow pb3d_points_count_dev with identical arguments on the same context (the scanned block offsets and the selection masks
+// stay in the context's scratch, PB3D_SLOT_POINTS_OFFSETS and PB3D_SLOT_POINTS_MASKS).  d_pts: n*3 floats, d_cols: n*C bytes.
 int pb3d_points_fill_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64_t A1, int64_t A2, int C,
                          const uint8_t* colors, int ncolors, int stride, int64_t n, float* d_pts, uint8_t* d_cols) {
     PB3D_REQUIRE(ctx != nullptr, "pb3d_points_fill: null context");
@@ -588,11 +592,13 @@ int pb3d_points_fill_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64
     PB3D_TRY(make_params(A0, A1, A2, C, colors, ncolors, stride, &p));
     if (p.nlat == 0 || n == 0) return PB3D_OK;
     PB3D_REQUIRE(d_grid && d_pts && d_cols, "pb3d_points_fill: null buffer");
-    return fill_pass(ctx, d_grid, p, aligned16(d_grid, stride), 9, 25, d_pts, d_cols);
+    PB3D_TRY(pb3d_pair_check(ctx, ctx->pts_dev.pair, pb3d_same_args(ctx->pts_dev.a, pb3d_points_args(d_grid, A0, A1, A2, C, colors, ncolors, stride, n)),
+                             "pb3d_points_fill", "pb3d_points_count"));
+    return fill_pass(ctx, d_grid, p, aligned16(d_grid, stride), PB3D_SLOT_POINTS_OFFSETS, PB3D_SLOT_POINTS_MASKS, d_pts, d_cols);
 }
 
-// count + fill in one call.  Its state lives in slots 24 / 26, so a count -> fill pair of the two entries above may have this call
-// between its halves.
+// count + fill in one call.  Its state lives in PB3D_SLOT_EXTRACT_OFFSETS / _MASKS, so a count -> fill pair of the two entries above
+// may have this call between its halves.
 int pb3d_points_extract_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64_t A1, int64_t A2, int C, const uint8_t* colors, int ncolors,
                             int64_t capacity, float* d_pts, uint8_t* d_cols, int64_t* n) {
     PB3D_REQUIRE(ctx != nullptr && n != nullptr && capacity >= 0, "pb3d_points_extract: bad argument");
@@ -603,9 +609,9 @@ int pb3d_points_extract_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, in
     PB3D_REQUIRE(d_grid && (capacity == 0 || (d_pts && d_cols)), "pb3d_points_extract: null buffer");
     PB3D_REQUIRE(aligned16(d_grid, 1), "pb3d_points_extract: needs a 16-byte aligned grid");
     PB3D_REQUIRE((p.nlat + kBlockVox - 1) / kBlockVox < (1ll << 31), "pb3d_points_extract: grid too large");
-    PB3D_TRY(count_pass(ctx, d_grid, p, true, 24, 26, n));
+    PB3D_TRY(count_pass(ctx, d_grid, p, true, PB3D_SLOT_EXTRACT_OFFSETS, PB3D_SLOT_EXTRACT_MASKS, n));
     if (*n == 0 || *n > capacity) return PB3D_OK;
-    PB3D_TRY(fill_pass(ctx, d_grid, p, true, 24, 26, d_pts, d_cols));
+    PB3D_TRY(fill_pass(ctx, d_grid, p, true, PB3D_SLOT_EXTRACT_OFFSETS, PB3D_SLOT_EXTRACT_MASKS, d_pts, d_cols));
     return pb3d_stream_sync(ctx);
 }
 

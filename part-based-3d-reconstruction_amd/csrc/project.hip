@@ -371,7 +371,7 @@ int pb3d_project_dev(pb3d_ctx* ctx, const void* d_pts, int pts_f64, const uint8_
     ProjParams P;
     PB3D_TRY(fill_proj(&P, pts_f64, R, cam, f, cx, cy, prec, Himg, Wimg));
     void* winner;
-    PB3D_TRY(pb3d_scratch(ctx, 8, (size_t)npix * sizeof(u32), &winner));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_PROJ_WINNER, (size_t)npix * sizeof(u32), &winner));
     PB3D_HIP(hipMemsetAsync(winner, 0, (size_t)npix * sizeof(u32), ctx->stream));
     PB3D_TRY(project_scatter(ctx, d_pts, n, P, WinnerSink{(u32*)winner}));
     hipLaunchKernelGGL(k_project_resolve, dim3(pb3d_stream_blocks(ctx, npix, 256, 8)), dim3(256), 0, ctx->stream,
@@ -438,7 +438,7 @@ int pb3d_partwise_iou_dev(pb3d_ctx* ctx, const uint8_t* d_a, const uint8_t* d_b,
     if (ncolors == 0 || npix == 0) return PB3D_OK;
     PB3D_REQUIRE(d_a && d_b && colors, "pb3d_partwise_iou: null buffer");
     void* counts;
-    PB3D_TRY(pb3d_scratch(ctx, 9, 64 * sizeof(unsigned long long), &counts));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_IOU_COUNTS, 64 * sizeof(unsigned long long), &counts));
     PB3D_HIP(hipMemsetAsync(counts, 0, 64 * sizeof(unsigned long long), ctx->stream));
     IouParams P;
     P.ncolors = ncolors;
@@ -469,10 +469,10 @@ int pb3d_project_iou_batch_dev(pb3d_ctx* ctx, const void* d_pts, int pts_f64, co
     kc = kc < 1 ? 1 : (kc > 4096 ? 4096 : kc);
     if (kc > ncams) kc = ncams;
     void *winners, *dcams, *counts, *dcolors;
-    PB3D_TRY(pb3d_scratch(ctx, 8, (size_t)(kc * npix) * sizeof(u32), &winners));
-    PB3D_TRY(pb3d_scratch(ctx, 20, (size_t)kc * sizeof(ProjParams), &dcams));
-    PB3D_TRY(pb3d_scratch(ctx, 21, (size_t)kc * 64 * sizeof(unsigned long long), &counts));
-    PB3D_TRY(pb3d_scratch(ctx, 22, 128, &dcolors));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_PROJ_WINNER, (size_t)(kc * npix) * sizeof(u32), &winners));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_PROJ_BATCH_CAMS, (size_t)kc * sizeof(ProjParams), &dcams));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_PROJ_BATCH_COUNTS, (size_t)kc * 64 * sizeof(unsigned long long), &counts));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_PROJ_BATCH_COLORS, 128, &dcolors));
     PB3D_HIP(hipMemcpyAsync(dcolors, colors, (size_t)3 * ncolors, hipMemcpyHostToDevice, ctx->stream));
     ProjParams* hp = (ProjParams*)malloc((size_t)kc * sizeof(ProjParams));
     ProjF32* hf = (ProjF32*)malloc((size_t)kc * sizeof(ProjF32));

@@ -732,8 +732,8 @@ bool pb3d_perm_step_ok(const double M[9], const double off[3], i64 W, i64 D, con
 static int build_valid_table(pb3d_ctx* ctx, const RotParams& p, i64 W, i64 D, u32** bits, int* nw) {
     const int n = (int)(((D + 63) / 64) * 2 + 2);
     void* buf;
-    PB3D_TRY(pb3d_scratch(ctx, 10, (size_t)W * (n + 1) * sizeof(u32), &buf));           // + one interval word per row (pb3d_valid_ivals)
-    // the table depends on (matrix, offset, W, D) only and slot 10 is private to it: a repeated step (every 90-degree call on one shape)
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_ROT_VALID_TABLE, (size_t)W * (n + 1) * sizeof(u32), &buf));           // + one interval word per row (pb3d_valid_ivals)
+    // the table depends on (matrix, offset, W, D) only and PB3D_SLOT_ROT_VALID_TABLE is private to it: a repeated step (every 90-degree call on one shape)
     // finds it in place -- at 512-class sizes the memset + table kernel were 10 % of a process_voxel_grid(., ., 90) call
     pb3d_ctx::ValidCache& vc = ctx->valid_cache;
     if (vc.buf == buf && vc.gen == ctx->scratch_gen && vc.W == W && vc.D == D && memcmp(vc.p, &p, sizeof(RotParams)) == 0 && ctx->tune_no_table_cache != 1) {
@@ -904,8 +904,8 @@ int pb3d_try_part_carve90(pb3d_ctx* ctx, const u8* d_colored, int C, i64 W, i64 
     u32* bits; int nw;
     PB3D_TRY(build_valid_table(ctx, ps.p, W, D, &bits, &nw));
     void *A, *AT;
-    PB3D_TRY(pb3d_scratch(ctx, 5, (size_t)(W * H) * sizeof(u32), &A));
-    PB3D_TRY(pb3d_scratch(ctx, 46, (size_t)(W * H) * sizeof(u32), &AT));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_PART90_JOBS, (size_t)(W * H) * sizeof(u32), &A));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_PART90_JOBS_T, (size_t)(W * H) * sizeof(u32), &AT));
     u32 on = 0;
     int nj = 0;
     for (int j = 0; j < 32; ++j) {

@@ -617,8 +617,8 @@ static int s32_chain(pb3d_ctx* ctx, const u8* d_occ, i64 W, i64 H, i64 D, const 
     StepParams sp;
     const int ntz = (int)((D + ST - 1) / ST), ntx = (int)((W + ST - 1) / ST), ntiles = ntz * ntx;
     void *flagp, *mb;
-    PB3D_TRY(pb3d_scratch(ctx, 34, 64, &flagp));
-    PB3D_TRY(pb3d_scratch(ctx, 35, (size_t)G * W * sizeof(u32), &mb));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_SLICED_FLAG, 64, &flagp));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_SLICED_MASK_BITS, (size_t)G * W * sizeof(u32), &mb));
     int* flag = (int*)flagp;
     const size_t sbytes = (size_t)G * W * Dp * sizeof(u32);
     void *A = nullptr, *B = nullptr;
@@ -688,7 +688,7 @@ static int s32_chain(pb3d_ctx* ctx, const u8* d_occ, i64 W, i64 H, i64 D, const 
             }
             // the tile programs of this run of steps: where an earlier call left them, or built now
             void* tp;
-            PB3D_TRY(pb3d_scratch(ctx, 32, (size_t)ns * ntiles * sizeof(STile), &tp));
+            PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_S32_TILE_PROGRAMS, (size_t)ns * ntiles * sizeof(STile), &tp));
             pb3d_ctx::S32Cache& sc = ctx->s32_cache;
             const bool hit = ctx->tune_no_table_cache != 1 && sc.valid && sc.gen == ctx->scratch_gen && sc.W == W && sc.D == D && sc.ns == ns &&
                              memcmp(sc.p, sp.p, sizeof(RotParams) * (size_t)ns) == 0;

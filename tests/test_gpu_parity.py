@@ -977,6 +977,157 @@ def test_points_count_extract_fill_interleaved(pb3d_gpu, oracle):
     d_b.free()
 
 
+SENTINEL = 0xA5
+
+
+def _sentinel_buffers(*nbytes):
+    from pb3d import device as dev
+    bufs = [dev.DeviceBuffer(n) for n in nbytes]
+    for b in bufs:
+        b.upload(np.full(b.nbytes, SENTINEL, np.uint8))
+    return bufs
+
+
+def _untouched(*bufs):
+    return all((b.download((b.nbytes,)) == SENTINEL).all() for b in bufs)
+
+
+@pytest.mark.gpu
+def test_points_fill_refuses_reused_state(pb3d_gpu, oracle):
+    """a device points fill refuses (ValueError, nothing launched) when its count's state is no longer there: pb3d_deform_count_dev
+    ran a points count of its own in between, or the fill does not repeat the count's arguments.  The outputs are sized for every
+    voxel of the grids involved plus one 4096-voxel block, so even an unchecked fill would stay inside them.
+    pb3d_partwise_iou_dev keeps its counters apart: count -> IoU -> fill -> fill again equals the oracle both times."""
+    import ctypes as C
+    from pb3d import device as dev
+    L, lib = pb3d_gpu._lib, pb3d_gpu._lib.load()
+    rng = np.random.default_rng(406)
+    PC = oracle.PART_COLORS
+    pal = np.array(list(PC.values()), np.uint8)
+    g = pal[rng.integers(0, len(pal), (9, 8, 10))] * (rng.random((9, 8, 10)) < 0.5)[..., None].astype(np.uint8)
+    cols = np.ascontiguousarray(pal[:5])
+    A0, A1, A2 = g.shape[:3]
+    nvox = A0 * A1 * A2
+    d_g = dev.from_numpy(g)
+    dpts = rng.integers(0, 20, (300, 3)).astype(np.float32)                  # deformed box <= 22^3 voxels
+    d_dp = dev.from_numpy(dpts)
+    rows = 22 ** 3 + 4096
+    d_p, d_c = _sentinel_buffers(rows * 12, rows * 3)
+    n = C.c_int64(0)
+
+    def count():
+        L.check(lib.pb3d_points_count_dev(L.ctx(), C.c_void_p(d_g.ptr), A0, A1, A2, 3, L.p_u8(cols), len(cols), 1, C.byref(n)))
+        assert n.value > 0
+
+    def fill(ncols=len(cols)):
+        L.check(lib.pb3d_points_fill_dev(L.ctx(), C.c_void_p(d_g.ptr), A0, A1, A2, 3, L.p_u8(cols), ncols, 1, n.value,
+                                         C.c_void_p(d_p.ptr), C.c_void_p(d_c.ptr)))
+
+    count()
+    nu = C.c_int64(0)
+    L.check(lib.pb3d_deform_count_dev(L.ctx(), C.c_void_p(d_dp.ptr), len(dpts), 1.0, 1.0, 0.0, 0.0, 0.0, C.byref(nu)))
+    # the deform count ran a points count of its own (on its mark volume): the pair's record is now that one's
+    with pytest.raises(ValueError, match="pb3d_points_fill: the arguments differ from those of the last pb3d_points_count"):
+        fill()
+    assert _untouched(d_p, d_c)
+    count()
+    with pytest.raises(ValueError, match="arguments differ"):
+        fill(len(cols) - 1)
+    assert _untouched(d_p, d_c)
+    # count -> IoU -> fill -> fill again: both fills equal the oracle
+    count()
+    inter = np.zeros(len(cols), np.int64); uni = np.zeros(len(cols), np.int64)
+    L.check(lib.pb3d_partwise_iou_dev(L.ctx(), C.c_void_p(d_g.ptr), C.c_void_p(d_g.ptr), nvox, L.p_u8(cols), len(cols),
+                                      inter.ctypes.data_as(L.i64p), uni.ctypes.data_as(L.i64p)))
+    want_p, want_c = oracle.get_voxel_points_by_parts(g, PC, list(PC)[:5])
+    assert n.value == len(want_p)
+    for _ in range(2):
+        fill()
+        assert np.array_equal(d_p.download((n.value, 3), np.float32), want_p) and np.array_equal(d_c.download((n.value, 3)), want_c)
+    for b in (d_g, d_dp, d_p, d_c):
+        b.free()
+
+
+@pytest.mark.gpu
+def test_host_points_fill_refuses_restaged_grid(pb3d_gpu, oracle):
+    """pb3d_points_count -> pb3d_occupancy -> pb3d_points_fill: the occupancy call stages its input where the count left the grid,
+    so the fill refuses and leaves the caller's arrays alone.  (An all-zero input selects nothing: an unchecked fill would write
+    fewer rows than counted.)  count -> fill still equals the oracle, and the host fill is one-shot as before."""
+    import ctypes as C
+    L, lib = pb3d_gpu._lib, pb3d_gpu._lib.load()
+    rng = np.random.default_rng(407)
+    PC = oracle.PART_COLORS
+    pal = np.array(list(PC.values()), np.uint8)
+    g = np.ascontiguousarray(pal[rng.integers(0, len(pal), (11, 7, 13))] * (rng.random((11, 7, 13)) < 0.4)[..., None].astype(np.uint8))
+    A0, A1, A2 = g.shape[:3]
+    zeros = np.zeros_like(g)
+    occ = np.empty(g.shape[:3], np.uint8)
+    n = C.c_int64(0)
+
+    def count():
+        L.check(lib.pb3d_points_count(L.ctx(), L.p_u8(g), A0, A1, A2, 3, None, 0, 1, C.byref(n)))
+        assert n.value > 0
+        return np.full((n.value, 3), -7.0, np.float32), np.full((n.value, 3), SENTINEL, np.uint8)
+
+    def fill(pts, pc):
+        L.check(lib.pb3d_points_fill(L.ctx(), n.value, pts.ctypes.data_as(C.POINTER(C.c_float)), L.p_u8(pc)))
+
+    pts, pc = count()
+    L.check(lib.pb3d_occupancy(L.ctx(), L.p_u8(zeros), A0 * A1 * A2, L.p_u8(occ)))
+    with pytest.raises(ValueError, match="pb3d_points_fill: the state of pb3d_points_count was overwritten"):
+        fill(pts, pc)
+    assert (pts == -7.0).all() and (pc == SENTINEL).all()
+    pts, pc = count()
+    fill(pts, pc)
+    want_p, want_c, _ = oracle.voxel_grid_to_points(g, stride=1)
+    assert np.array_equal(pts, want_p) and np.array_equal(pc, want_c)
+    with pytest.raises(ValueError, match="call pb3d_points_count first"):
+        fill(pts, pc)
+
+
+@pytest.mark.gpu
+def test_deform_fill_refuses_reused_marks(pb3d_gpu, oracle):
+    """pb3d_deform_count -> pb3d_deform_iou_batch_dev -> pb3d_deform_fill: the batch's marks reuse the count's mark volume, so the
+    fill refuses and leaves the caller's array alone.  The batch runs without points (its marks stay zero: an unchecked fill would
+    select fewer voxels than counted).  The device pair's count -> fill equals the oracle."""
+    import ctypes as C
+    from pb3d import device as dev
+    from pb3d.camera_estimation import CameraObjective
+    from pb3d.deformation_estimation import _scalars
+    from pb3d.projection_utils import camera_args
+    L, lib = pb3d_gpu._lib, pb3d_gpu._lib.load()
+    rng = np.random.default_rng(408)
+    pts = rng.integers(-5, 40, (500, 3)).astype(np.float32)
+    dv = dict(scale_y=1.3, shift_y=7.0, scale_xz=0.8, shift_xz=-11.0)
+    sc = _scalars((77, 131), (64, 70, 66), dv)
+    want = oracle.deform_coords(pts, (77, 131), (64, 70, 66), dv)
+    nu = C.c_int64(0)
+    L.check(lib.pb3d_deform_count(L.ctx(), pts.ctypes.data_as(C.POINTER(C.c_float)), len(pts), *sc, C.byref(nu)))
+    assert nu.value == len(want)
+    H = W = 16
+    _, _, R, cam, prec = camera_args(np.zeros((1, 3), np.float32), np.array([8.0, 8.0, -40.0]), np.array([8.0, 8.0, 8.0]), 30.0, 8.0, 8.0)
+    c = np.zeros(1, CameraObjective._CAM)
+    c["R"][0] = R.reshape(9); c["cam"][0] = cam; c["f"][0] = 30.0; c["cx"][0] = 8.0; c["cy"][0] = 8.0; c["prec"][0] = list(prec)
+    d5 = np.ascontiguousarray([sc], np.float64)
+    color = np.array([255, 0, 0], np.uint8)
+    inter = np.zeros(1, np.int64); uni = np.zeros(1, np.int64); nvalid = np.zeros(1, np.int64)
+    d_img = dev.from_numpy(np.zeros((H, W, 3), np.uint8))
+    L.check(lib.pb3d_deform_iou_batch_dev(L.ctx(), None, 0, L.p_dbl(d5), 1, 64, 70, 66, c.ctypes.data_as(C.c_void_p), H, W,
+                                          C.c_void_p(d_img.ptr), L.p_u8(color), inter.ctypes.data_as(L.i64p), uni.ctypes.data_as(L.i64p),
+                                          nvalid.ctypes.data_as(L.i64p)))
+    out = np.full((nu.value, 3), -7, np.int64)
+    with pytest.raises(ValueError, match="pb3d_deform_fill: the state of pb3d_deform_count was overwritten"):
+        L.check(lib.pb3d_deform_fill(L.ctx(), nu.value, out.ctypes.data_as(L.i64p)))
+    assert (out == -7).all()
+    d_pts = dev.from_numpy(pts)
+    d_out = dev.DeviceBuffer(nu.value * 24)
+    L.check(lib.pb3d_deform_count_dev(L.ctx(), C.c_void_p(d_pts.ptr), len(pts), *sc, C.byref(nu)))
+    L.check(lib.pb3d_deform_fill_dev(L.ctx(), nu.value, C.c_void_p(d_out.ptr)))
+    assert np.array_equal(d_out.download((nu.value, 3), np.int64), want)
+    for b in (d_img, d_pts, d_out):
+        b.free()
+
+
 @pytest.mark.gpu
 def test_part_carve_odd_shapes_w_ne_d(pb3d_gpu, oracle):
     """the fused 90-degree part_carve kernel on shapes the reference's own grids never have (W != D, odd D, non-zero column

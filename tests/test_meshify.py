@@ -219,6 +219,93 @@ def test_resident_form_equals_numpy_form():
 
 
 @pytest.mark.gpu
+def test_mesh_fill_refuses_reused_state():
+    """pb3d_mesh_count_dev(g1) -> pb3d_mesh_colors_dev(g2) -> pb3d_mesh_fill_dev(g1): the colour query rebuilds the lattice bits
+    the count left, so the fill refuses (ValueError, nothing launched).  The outputs are sized for every cube plus one 256-cube
+    block at the table's maxima (12 vertices, 9 triangles per cube), so even an unchecked fill would stay inside them.
+    count -> fill -> fill again: both fills equal the restatement."""
+    import ctypes as C
+    import pb3d
+    from pb3d import device as dev
+    from pb3d.voxel_utils import mesh_colors
+    L, lib = pb3d._lib, pb3d._lib.load()
+    rng = np.random.default_rng(12)
+    shape = (13, 11, 9)
+    A0, A1, A2 = shape
+    g1, g2 = rand_grid(rng, shape, 0.5), rand_grid(rng, shape, 0.3)
+    d1, d2 = dev.from_numpy(g1), dev.from_numpy(g2)
+    ncubes = (A0 - 1) * (A1 - 1) * (A2 - 1)
+    vrows, frows = 12 * (ncubes + 256), 9 * (ncubes + 256)
+    outs = [dev.DeviceBuffer(n) for n in (vrows * 12, frows * 12, vrows * 12, vrows * 3)]     # verts, faces, normals, colours
+    for b in outs:
+        b.upload(np.full(b.nbytes, 0xA5, np.uint8))
+    qv, qc = dev.from_numpy(np.zeros((4, 3), np.float32)), dev.DeviceBuffer(4 * 3)
+    nv, nf = C.c_int64(0), C.c_int64(0)
+    ptr = lambda b: C.c_void_p(b.ptr)
+
+    def fill():
+        L.check(lib.pb3d_mesh_fill_dev(L.ctx(), ptr(d1), A0, A1, A2, 3, 1, nv.value, nf.value, *map(ptr, outs)))
+
+    L.check(lib.pb3d_mesh_count_dev(L.ctx(), ptr(d1), A0, A1, A2, 3, 1, C.byref(nv), C.byref(nf)))
+    assert nv.value > 0
+    L.check(lib.pb3d_mesh_colors_dev(L.ctx(), ptr(d2), A0, A1, A2, 3, 1, ptr(qv), 4, ptr(qc)))
+    with pytest.raises(ValueError, match="pb3d_mesh_fill: the state of pb3d_mesh_count was overwritten"):
+        fill()
+    assert all((b.download((b.nbytes,)) == 0xA5).all() for b in outs)
+    L.check(lib.pb3d_mesh_count_dev(L.ctx(), ptr(d1), A0, A1, A2, 3, 1, C.byref(nv), C.byref(nf)))
+    rv, rf, rc, rn = mr.meshify(g1, 1)
+    for _ in range(2):
+        fill()
+        v = outs[0].download((nv.value, 3), np.float32)
+        assert np.array_equal(v, rv) and np.array_equal(outs[1].download((nf.value, 3), np.int32), rf)
+        assert np.array_equal(outs[2].download((nv.value, 3), np.float32), rn)
+        check_colors(g1, 1, v, mesh_colors(outs[3].download((nv.value, 3))), rc)
+    for b in outs + [d1, d2, qv, qc]:
+        b.free()
+
+
+@pytest.mark.gpu
+def test_host_mesh_fill_refuses_restaged_grid():
+    """pb3d_mesh_count -> pb3d_carve_mask -> pb3d_mesh_fill: the carve stages its grid where the count left its own, so the fill
+    refuses and leaves the caller's arrays alone.  count -> fill still equals the restatement, and the host fill is one-shot as
+    before."""
+    import ctypes as C
+    import pb3d
+    from pb3d.voxel_utils import mesh_colors
+    L, lib = pb3d._lib, pb3d._lib.load()
+    rng = np.random.default_rng(13)
+    shape = (12, 10, 14)
+    A0, A1, A2 = shape
+    g = rand_grid(rng, shape, 0.4)
+    mask = np.ones((A0, A1), np.uint8)
+    carved = np.empty_like(g)
+    nv, nf = C.c_int64(0), C.c_int64(0)
+
+    def count():
+        L.check(lib.pb3d_mesh_count(L.ctx(), L.p_u8(g), A0, A1, A2, 3, 1, C.byref(nv), C.byref(nf)))
+        assert nv.value > 0
+        return (np.full((nv.value, 3), -7.0, np.float32), np.full((nf.value, 3), -7, np.int32), np.full((nv.value, 3), -7.0, np.float32),
+                np.full((nv.value, 3), 0xA5, np.uint8))
+
+    def fill(outs):
+        L.check(lib.pb3d_mesh_fill(L.ctx(), nv.value, nf.value, *[o.ctypes.data_as(C.c_void_p) for o in outs]))
+
+    outs = count()
+    L.check(lib.pb3d_carve_mask(L.ctx(), L.p_u8(g), A0, A1, A2, 3, L.p_u8(mask), L.p_u8(carved)))
+    with pytest.raises(ValueError, match="pb3d_mesh_fill: the state of pb3d_mesh_count was overwritten"):
+        fill(outs)
+    assert all((o == (0xA5 if o.dtype == np.uint8 else -7)).all() for o in outs)
+    outs = count()
+    fill(outs)
+    v, f, n, c = outs
+    rv, rf, rc, rn = mr.meshify(g, 1)
+    assert np.array_equal(v, rv) and np.array_equal(f, rf) and np.array_equal(n, rn)
+    check_colors(g, 1, v, mesh_colors(c), rc)
+    with pytest.raises(ValueError, match="call pb3d_mesh_count first"):
+        fill(outs)
+
+
+@pytest.mark.gpu
 def test_error_cases_raise_like_the_reference():
     import pb3d
     with pytest.raises(ValueError, match="Surface level"):
