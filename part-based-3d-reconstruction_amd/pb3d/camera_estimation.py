@@ -54,9 +54,10 @@ class CameraObjective:
 
     def __init__(self, voxel_pts, voxel_colors, seg_img, selected_labels):
         from . import device as dev
+        from .projection_utils import points_f64
         self._dev = dev
         pts = np.asarray(voxel_pts)
-        self._pf64 = int(pts.dtype == np.float64)
+        self._pf64 = int(points_f64(pts.dtype))
         self._pts_dtype = pts.dtype
         self._pts_host = np.ascontiguousarray(pts, np.float64 if self._pf64 else np.float32)
         if self._pts_host.ndim != 2 or self._pts_host.shape[1] != 3:

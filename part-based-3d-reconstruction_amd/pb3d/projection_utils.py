@@ -23,15 +23,22 @@ def _promotion_flags(t0, f, cx, cy):
     return int(t0), tm, int(tm or _promotes_to_f64(cx)), int(tm or _promotes_to_f64(cy))
 
 
+def points_f64(dtype):
+    """True for the point dtypes the kernels read as float64: float64 itself and the 32- and 64-bit integers, which NumPy
+    promotes with any float camera to float64 (float32 would round their values from 2^24 on).  Narrower types are exact
+    in float32."""
+    return np.result_type(dtype, np.float32) == np.float64
+
+
 def camera_args(pts3d, cam_pos, target, f, cx, cy):
     """Everything the projection kernels need from the caller's camera: the look-at rotation (host NumPy, same
-    dtypes as upstream), the points in their own float width and the NumPy-2 promotion flags of each stage."""
+    dtypes as upstream), the points in a float width that holds their values and the NumPy-2 promotion flags of each stage."""
     pts3d = np.asarray(pts3d)
     cam_pos = np.asarray(cam_pos)
     target = np.asarray(target)
     R = look_at_rotation(cam_pos, target)
     prec = (C.c_int * 4)(*_promotion_flags(np.result_type(pts3d, cam_pos, R) == np.float64, f, cx, cy))
-    pf64 = int(pts3d.dtype == np.float64)
+    pf64 = int(points_f64(pts3d.dtype))
     return (np.ascontiguousarray(pts3d, np.float64 if pf64 else np.float32), pf64, np.ascontiguousarray(R, np.float64),
             np.ascontiguousarray(cam_pos, np.float64), prec)
 
