@@ -39,7 +39,8 @@ enum {
     PB3D_ENODEVICE = -2,    /* no HIP device / HIP runtime error                        */
     PB3D_ENOMEM = -3,       /* device allocation failed                                  */
     PB3D_EUNSUPPORTED = -4, /* argument combination outside what the path needs          */
-    PB3D_ECOMM = -5         /* RCCL not available / collective failed                    */
+    PB3D_ECOMM = -5,        /* RCCL not available / collective failed                    */
+    PB3D_EINDEX = -6        /* an index read from a device buffer is out of range        */
 };
 
 /* ---- lifecycle, device memory, timing (plumbing) ------------------------------------- */
@@ -289,12 +290,45 @@ int pb3d_iou_rows_dev(pb3d_ctx* ctx, const pb3d_iou_row* rows, int nrows, int64_
  *   when calc_f32: both lists float32, NumPy's float32 arithmetic) and iters with the reference's expressions; the device sets voxel
  *   clip(int((p - bounds_min) / step), 0, resolution - 1) of every point (a NaN or out-of-range quotient gives voxel 0, as NumPy's
  *   cast does on x86), dilates both grids iters times with the 6-neighbour cross and a zero border (binary_dilation) and writes
- *   d_counts[0] = #(A & B), d_counts[1] = #(A | B).  1 <= resolution <= 2048, iters >= 0 (0: no dilation). */
+ *   d_counts[0] = #(A & B), d_counts[1] = #(A | B).  1 <= resolution <= 2048, iters >= 0 (0: no dilation).
+ * knn: for each of the nq queries its k nearest reference points (1 <= k <= PB3D_KNN_MAX_K, nr >= k when nq > 0), what
+ *   NearestNeighbors(n_neighbors=k).fit(r).kneighbors(q) computes (compute_surface_metrics :217-218).  d_idx: nq x k int32, positions
+ *   in d_r; d_dist: nq x k float64 or NULL, the distance expression of nn_dist.  A row is ascending by (squared distance as computed,
+ *   then reference index), and the same rule decides which of several equidistant points are in the row, so the result is a function
+ *   of the input alone (the trees break ties by traversal order: on tied input only their distances are comparable).  With q the
+ *   same list as r a point is its own neighbour at distance 0; exact duplicates tie at 0 and are ordered by index.  Input must be
+ *   finite.  Same cell index and one host wait as nn_dist; nn_dist itself (k = 1, 2, distances only) is a separate, lighter path. */
 int pb3d_points_bounds_dev(pb3d_ctx* ctx, const void* d_pts, int pts_f64, int64_t n, double* d_out);
 int pb3d_nn_dist_dev(pb3d_ctx* ctx, const void* d_q, int q_f64, int64_t nq, const void* d_r, int r_f64, int64_t nr, int k, double* d_out);
+#define PB3D_KNN_MAX_K 32
+int pb3d_knn_dev(pb3d_ctx* ctx, const void* d_q, int q_f64, int64_t nq, const void* d_r, int r_f64, int64_t nr, int k, double* d_dist,
+                 int32_t* d_idx);
 int pb3d_nn_grid_shape(const double bounds[6], int64_t nr, int64_t cells[3]);
 int pb3d_voxel_iou_counts_dev(pb3d_ctx* ctx, const void* d_a, int a_f64, int64_t na, const void* d_b, int b_f64, int64_t nb,
                               const double bounds_min[3], double step, int calc_f32, int resolution, int iters, int64_t* d_counts);
+
+/* ---- mesh regularity (the surface block of the inter-method evaluation), reference utils/eval_helpers.py:198-245 --------------------
+ * Vertices are (nv, 3) rows of float32 (verts_f64 = 0) or float64 (1); faces are (nf, 3) rows of int32 (faces_i64 = 0) or int64 (1).
+ * Every entry first checks the face indices on the device: one outside [-nv, nv) is PB3D_EINDEX (NumPy's IndexError) before any
+ * kernel gathers through them (one host wait); indices in [-nv, -1] wrap as NumPy's do.
+ * triangle_normals (:198-203): d_out nf x 3 in the vertex dtype, bit for bit cross(v1 - v0, v2 - v0) / (norm + 1e-8) as NumPy
+ *   evaluates it: every component one product minus one product, each rounded; norm = sqrt((x*x + y*y) + z*z); 1e-8 rounded to the
+ *   vertex dtype.
+ * vertex_normals (:206-212): d_out nv x 3 in the vertex dtype, bit for bit the reference's double loop: each vertex adds the
+ *   normals of its incident faces in ascending face order, starting from 0, in the vertex dtype (a face that names the vertex twice
+ *   adds twice), then / (norm + 1e-8); a vertex in no face gives 0.  No floating-point atomics: incidence lists are counted,
+ *   scanned, filled and sorted, and one lane adds a vertex's list.  Any vertex degree works; a fan of thousands of faces is slow.
+ * surface_metrics (:214-245, the loop body): from the vertices, their normals (vertex dtype) and the nv x k neighbour rows of
+ *   pb3d_knn_dev(verts, verts, k) -- 2 <= k <= PB3D_KNN_MAX_K -- three float64 arrays of length nv, all arithmetic in float64 and
+ *   compensated where it cancels:  normal_std = np.std of degrees(arccos(clip(n_j . n_i, -1, 1))) over the row;  roughness = the
+ *   smallest eigenvalue of the neighbours' covariance (divisor k - 1; PCA(3).explained_variance_[2]), >= 0;  curvature =
+ *   |mean(neighbours) - vertex|.  An index outside [0, nv) in d_idx is PB3D_EINDEX.  The reference's np.mean of each is the caller's. */
+int pb3d_triangle_normals_dev(pb3d_ctx* ctx, const void* d_verts, int verts_f64, int64_t nv, const void* d_faces, int faces_i64, int64_t nf,
+                              void* d_out);
+int pb3d_vertex_normals_dev(pb3d_ctx* ctx, const void* d_verts, int verts_f64, int64_t nv, const void* d_faces, int faces_i64, int64_t nf,
+                            void* d_out);
+int pb3d_surface_metrics_dev(pb3d_ctx* ctx, const void* d_verts, const void* d_normals, int verts_f64, int64_t nv, const int32_t* d_idx, int k,
+                             double* d_normal_std, double* d_roughness, double* d_curvature);
 
 /* ---- compute_partwise_iou, reference utils/camera_estimation.py:770-787 -------------------
  * per colour k: inter[k] = #(a==c & b==c), uni[k] = #(a==c | b==c) over npix RGB pixels. */

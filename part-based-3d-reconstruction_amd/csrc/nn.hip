@@ -288,6 +288,143 @@ __global__ __launch_bounds__(256) void k_nn_query(const void* __restrict__ q, i6
     out[qi] = __dsqrt_rn(K == 1 ? b1 : b2);
 }
 
+// ---- exact k nearest neighbours with indices (compute_surface_metrics, reference utils/eval_helpers.py:217-218) --------------------
+// The same index and ring walk as k_nn_query, beside it: the cell-sorted arrays carry each point's position in the caller's array
+// (ids), and every lane keeps its k best (squared distance as computed, reference index) pairs.  The list is a register array that
+// is only ever indexed by unrolled loops (KC = 8, 20 or 32 slots, the first k in use; a run-time index would put it in scratch
+// memory): slot 0 holds the WORST of the k, so the pruning bound is best[0] whatever k is, and an insertion shifts the worse
+// entries towards slot 0.  Order and membership under ties are decided by (d2, index) alone, so the scatter's order within a cell
+// and the order cells are visited in do not reach the result.
+
+// reference points -> cell-sorted SoA (xs, ys, zs, ids)
+template <bool F64>
+__global__ __launch_bounds__(256) void k_cell_scatter_ref_ids(const void* __restrict__ pts, i64 n, Grid g, const i64* __restrict__ start,
+                                                              u32* __restrict__ cursor, double* __restrict__ xs, double* __restrict__ ys,
+                                                              double* __restrict__ zs, int* __restrict__ ids) {
+    for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (i64)gridDim.x * 256) {
+        double x, y, z;
+        load3<F64>(pts, i, &x, &y, &z);
+        const i64 c = cell_index(g, cell_of(g, 0, x), cell_of(g, 1, y), cell_of(g, 2, z));
+        const i64 pos = start[c] + atomicAdd(&cursor[c], 1u);
+        xs[pos] = x; ys[pos] = y; zs[pos] = z;
+        ids[pos] = (int)i;
+    }
+}
+
+__device__ __forceinline__ bool knn_less(double d2a, int ia, double d2b, int ib) { return d2a < d2b || (d2a == d2b && ia < ib); }
+
+template <int KC>
+struct KBest {
+    double d2[KC];      // slot 0: the k-th best (the worst kept); slot k - 1: the nearest
+    int id[KC];
+    __device__ __forceinline__ void init() {
+#pragma unroll
+        for (int j = 0; j < KC; ++j) { d2[j] = INFINITY; id[j] = 0x7fffffff; }
+    }
+    // (d, i) beats slot 0: drop slot 0, move the entries worse than (d, i) one slot down, put (d, i) above them
+    __device__ __forceinline__ void insert(int k, double d, int i) {
+        bool here = true;                       // (d, i) beats slot j
+#pragma unroll
+        for (int j = 0; j < KC; ++j) {
+            const int u = j + 1 < KC ? j + 1 : j;       // the slot above (a constant once unrolled)
+            const bool above = j + 1 < KC && j + 1 < k && knn_less(d, i, d2[u], id[u]);
+            d2[j] = above ? d2[u] : (here ? d : d2[j]);
+            id[j] = above ? id[u] : (here ? i : id[j]);
+            here = above;
+        }
+    }
+};
+
+template <int KC, bool F64>
+__global__ __launch_bounds__(256) void k_knn_query(const void* __restrict__ q, i64 nq, const u32* __restrict__ order, Grid g,
+                                                   const i64* __restrict__ start, const double* __restrict__ xs, const double* __restrict__ ys,
+                                                   const double* __restrict__ zs, const int* __restrict__ ids, int k,
+                                                   double* __restrict__ out_dist, int* __restrict__ out_idx) {
+    const i64 s = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (s >= nq) return;
+    const u32 qi = order[s];
+    double qv[3];
+    load3<F64>(q, qi, &qv[0], &qv[1], &qv[2]);
+    int c[3];
+    double tol[3], out2[3];     // as in k_nn_query
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        c[a] = cell_of(g, a, qv[a]);
+        tol[a] = 1e-12 * (fabs(g.lo[a]) + fabs(g.hi[a]) + fabs(qv[a]));
+        const double o = fmax(fmax(g.lo[a] - qv[a], qv[a] - g.hi[a]) - tol[a], 0.0);
+        out2[a] = o * o;
+    }
+    KBest<KC> best;
+    best.init();
+    const int rmax = max(max(g.n[0], g.n[1]), g.n[2]);
+    for (int r = 0; r <= rmax; ++r) {
+        const int x0 = max(c[0] - r, 0), x1 = min(c[0] + r, g.n[0] - 1);
+        const int y0 = max(c[1] - r, 0), y1 = min(c[1] + r, g.n[1] - 1);
+        const int z0 = max(c[2] - r, 0), z1 = min(c[2] + r, g.n[2] - 1);
+        for (int i = x0; i <= x1; ++i) {
+            const double gx = slab_gap(g, 0, i, i, qv[0], tol[0]);
+            const double gx2 = gx * gx;
+            if (beyond(gx2, best.d2[0])) continue;
+            const bool xe = i == c[0] - r || i == c[0] + r;
+            for (int j = y0; j <= y1; ++j) {
+                const double gy = slab_gap(g, 1, j, j, qv[1], tol[1]);
+                const double gxy = gx2 + gy * gy;
+                if (beyond(gxy, best.d2[0])) continue;
+                const i64 row = cell_index(g, i, j, 0);
+                i64 s0 = 0, e0 = 0, s1 = 0, e1 = 0;                 // the (at most two) runs of this column, visited by one loop below
+                if (xe || j == c[1] - r || j == c[1] + r) {         // the whole z-run of the ring's face
+                    const double gz = slab_gap(g, 2, z0, z1, qv[2], tol[2]);
+                    if (!beyond(gxy + gz * gz, best.d2[0])) { s0 = start[row + z0]; e0 = start[row + z1 + 1]; }
+                } else {                                            // inside the ring's (x, y) box: its two z-end cells only
+                    if (c[2] - r >= 0) {
+                        const double gz = slab_gap(g, 2, c[2] - r, c[2] - r, qv[2], tol[2]);
+                        if (!beyond(gxy + gz * gz, best.d2[0])) { s0 = start[row + c[2] - r]; e0 = start[row + c[2] - r + 1]; }
+                    }
+                    if (r > 0 && c[2] + r < g.n[2]) {
+                        const double gz = slab_gap(g, 2, c[2] + r, c[2] + r, qv[2], tol[2]);
+                        if (!beyond(gxy + gz * gz, best.d2[0])) { s1 = start[row + c[2] + r]; e1 = start[row + c[2] + r + 1]; }
+                    }
+                }
+#pragma nounroll
+                for (int t = 0; t < 2; ++t) {
+                    const i64 e = t ? e1 : e0;
+#pragma nounroll
+                    for (i64 p = t ? s1 : s0; p < e; ++p) {
+                        const double dx = qv[0] - xs[p], dy = qv[1] - ys[p], dz = qv[2] - zs[p];
+                        const double d2 = (dx * dx + dy * dy) + dz * dz;
+                        const int id = ids[p];
+                        if (knn_less(d2, id, best.d2[0], best.id[0])) best.insert(k, d2, id);
+                    }
+                }
+            }
+        }
+        const int lo_[3] = {x0, y0, z0}, hi_[3] = {x1, y1, z1};     // the bound over the cells not yet visited, as in k_nn_query
+        double lb = INFINITY;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const double rest = out2[(a + 1) % 3] + out2[(a + 2) % 3];
+            if (hi_[a] < g.n[a] - 1) {
+                const double gap = fmax(g.lo[a] + (double)(hi_[a] + 1) * g.h[a] - qv[a] - tol[a], 0.0);
+                lb = fmin(lb, gap * gap + rest);
+            }
+            if (lo_[a] > 0) {
+                const double gap = fmax(qv[a] - (g.lo[a] + (double)lo_[a] * g.h[a]) - tol[a], 0.0);
+                lb = fmin(lb, gap * gap + rest);
+            }
+        }
+        if (lb == INFINITY || beyond(lb, best.d2[0])) break;
+    }
+    // row qi, nearest first: slot k - 1 - j
+#pragma unroll
+    for (int j = 0; j < KC; ++j) {
+        if (j < k) {
+            const i64 o = (i64)qi * k + (k - 1 - j);
+            out_idx[o] = best.id[j];
+            if (out_dist) out_dist[o] = __dsqrt_rn(best.d2[j]);
+        }
+    }
+}
+
 // ---- voxel_iou: occupancy bits, 6-neighbour dilation, intersection / union counts -------------------------------------------------
 // Bit grid of one cloud: word (x * res + y) * W + z / 32, bit z % 32, W = ceil(res / 32); bits at z >= res stay 0.
 struct Occ {
@@ -409,6 +546,50 @@ int nn_run(pb3d_ctx* ctx, const void* d_q, i64 nq, const void* d_r, i64 nr, int 
     return PB3D_OK;
 }
 
+template <int KC, bool QF64>
+void launch_knn(pb3d_ctx* ctx, const void* d_q, i64 nq, const u32* order, const Grid& g, const i64* rs, const double* xs, i64 nr,
+                const int* ids, int k, double* d_dist, int* d_idx) {
+    hipLaunchKernelGGL((k_knn_query<KC, QF64>), dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream, d_q, nq, order, g, rs, xs,
+                       xs + nr, xs + 2 * nr, ids, k, d_dist, d_idx);
+}
+
+template <bool QF64, bool RF64>
+int knn_run(pb3d_ctx* ctx, const void* d_q, i64 nq, const void* d_r, i64 nr, int k, const Grid& g, double* d_dist, int* d_idx) {
+    u32 *rc, *qc;
+    i64 *rs, *qs;
+    void *soa, *idbuf, *order;
+    PB3D_TRY(bin_points<RF64>(ctx, d_r, nr, g, PB3D_SLOT_NN_REF_COUNTS, PB3D_SLOT_NN_REF_STARTS, &rc, &rs));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_NN_REF_COORDS, (size_t)nr * 3 * sizeof(double), &soa));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_KNN_REF_IDS, (size_t)nr * sizeof(int), &idbuf));
+    double* xs = (double*)soa;
+    hipLaunchKernelGGL(k_cell_scatter_ref_ids<RF64>, dim3(pb3d_stream_blocks(ctx, nr, 256, 8)), dim3(256), 0, ctx->stream, d_r, nr, g,
+                       (const i64*)rs, rc, xs, xs + nr, xs + 2 * nr, (int*)idbuf);
+    PB3D_CHECK_LAUNCH();
+    PB3D_TRY(bin_points<QF64>(ctx, d_q, nq, g, PB3D_SLOT_NN_QUERY_COUNTS, PB3D_SLOT_NN_QUERY_STARTS, &qc, &qs));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_NN_ORDER, (size_t)nq * sizeof(u32), &order));
+    hipLaunchKernelGGL(k_cell_scatter_query<QF64>, dim3(pb3d_stream_blocks(ctx, nq, 256, 8)), dim3(256), 0, ctx->stream, d_q, nq, g,
+                       (const i64*)qs, qc, (u32*)order);
+    PB3D_CHECK_LAUNCH();
+    if (k <= 8) launch_knn<8, QF64>(ctx, d_q, nq, (const u32*)order, g, rs, xs, nr, (const int*)idbuf, k, d_dist, d_idx);
+    else if (k <= 20) launch_knn<20, QF64>(ctx, d_q, nq, (const u32*)order, g, rs, xs, nr, (const int*)idbuf, k, d_dist, d_idx);
+    else launch_knn<32, QF64>(ctx, d_q, nq, (const u32*)order, g, rs, xs, nr, (const int*)idbuf, k, d_dist, d_idx);
+    PB3D_CHECK_LAUNCH();
+    return PB3D_OK;
+}
+
+// the reference set's exact box, read back once, and the cell grid made from it
+int grid_of(pb3d_ctx* ctx, const void* d_r, int r_f64, i64 nr, Grid* g) {
+    void* bb;
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_NN_BOUNDS, 6 * sizeof(double), &bb));
+    PB3D_TRY(launch_bounds(ctx, d_r, r_f64, nr, (double*)bb));
+    PB3D_HIP(hipMemcpyAsync(ctx->pinned, bb, 6 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    PB3D_TRY(pb3d_stream_sync(ctx));
+    double b[6];
+    memcpy(b, ctx->pinned, sizeof(b));
+    *g = make_grid(b, nr);
+    return PB3D_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -441,6 +622,23 @@ int pb3d_nn_dist_dev(pb3d_ctx* ctx, const void* d_q, int q_f64, int64_t nq, cons
     if (q_f64) return nn_run<true, false>(ctx, d_q, nq, d_r, nr, k, g, d_out);
     if (r_f64) return nn_run<false, true>(ctx, d_q, nq, d_r, nr, k, g, d_out);
     return nn_run<false, false>(ctx, d_q, nq, d_r, nr, k, g, d_out);
+}
+
+int pb3d_knn_dev(pb3d_ctx* ctx, const void* d_q, int q_f64, int64_t nq, const void* d_r, int r_f64, int64_t nr, int k, double* d_dist,
+                 int32_t* d_idx) {
+    PB3D_REQUIRE(k >= 1 && k <= PB3D_KNN_MAX_K, "pb3d_knn: k must be in [1, %d] (got %d)", PB3D_KNN_MAX_K, k);
+    PB3D_REQUIRE(nq >= 0 && nr >= 0, "pb3d_knn: negative point count");
+    PB3D_REQUIRE(nq <= kMaxPoints && nr <= kMaxPoints, "pb3d_knn: at most 2^31 - 1 points per set");
+    if (nq == 0) return PB3D_OK;
+    PB3D_REQUIRE(nr >= k, "pb3d_knn: the reference set needs at least k = %d points (got %lld)", k, (long long)nr);
+    PB3D_REQUIRE(d_q != nullptr && d_r != nullptr && d_idx != nullptr, "pb3d_knn: null buffer");
+    PB3D_REQUIRE(ctx != nullptr, "pb3d_knn: null context");
+    Grid g;
+    PB3D_TRY(grid_of(ctx, d_r, r_f64, nr, &g));
+    if (q_f64 && r_f64) return knn_run<true, true>(ctx, d_q, nq, d_r, nr, k, g, d_dist, d_idx);
+    if (q_f64) return knn_run<true, false>(ctx, d_q, nq, d_r, nr, k, g, d_dist, d_idx);
+    if (r_f64) return knn_run<false, true>(ctx, d_q, nq, d_r, nr, k, g, d_dist, d_idx);
+    return knn_run<false, false>(ctx, d_q, nq, d_r, nr, k, g, d_dist, d_idx);
 }
 
 // the index size of the last pb3d_nn_dist_dev-shaped call on nr reference points with this box (cells per axis; tools/opbench.py)

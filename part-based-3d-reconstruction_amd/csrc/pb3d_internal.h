@@ -124,8 +124,18 @@ enum pb3d_slot : int {
     // call-local, csrc/project.hip: pb3d_partwise_iou_dev's counters.  A slot of their own (they once shared POINTS_OFFSETS):
     // the IoU may run between the halves of a points pair
     PB3D_SLOT_IOU_COUNTS = 58,
+    // call-local, csrc/nn.hip: pb3d_knn_dev's original index of each cell-sorted reference point (beside NN_REF_COORDS)
+    PB3D_SLOT_KNN_REF_IDS = 59,
+    // call-local, csrc/surface.hip: the index check's flag, face normals, the vertex -> incident-face lists and their scan
+    PB3D_SLOT_SURF_FLAG = 60,
+    PB3D_SLOT_SURF_FACE_NORMALS = 61,
+    PB3D_SLOT_SURF_VERT_COUNTS = 62,
+    PB3D_SLOT_SURF_VERT_STARTS = 63,
+    PB3D_SLOT_SURF_INCIDENT = 64,
+    PB3D_SLOT_SURF_SCAN_LOCAL = 65,
+    PB3D_SLOT_SURF_SCAN_SEGS = 66,
 
-    PB3D_SLOT_COUNT = 59
+    PB3D_SLOT_COUNT = 67
 };
 
 // What a *_count leaves for its *_fill: the use counters (pb3d_ctx::scratch_use) of the slots the fill reads, taken when the count has

@@ -15,6 +15,8 @@ from .camera_estimation import (CameraObjective, compute_partwise_iou, coordinat
                                 random_search)
 from .eval_helpers import (chamfer_distance, compute_f1_curve, compute_nn_distances, compute_nn_stats, f1_curve_from_distances,  # noqa: F401
                            filter_mesh, fscore_with_threshold, nn_distances, pca_shape_similarity, voxel_iou)
+from .eval_helpers import (compute_surface_metrics, compute_triangle_normals, compute_vertex_normals, knn,  # noqa: F401
+                           surface_metrics_per_vertex)
 from .eval_helpers_intra import (color_presence, compute_binary_gt, compute_global_depth_buffer, grid_depth_buffer, grid_visible_bits,  # noqa: F401
                                  points_visible_bits, project_part_visible, run_minaret_iou_evaluation, run_minaret_kp_evaluation,
                                  run_part_minaret_binary_iou)
@@ -44,7 +46,8 @@ _PATCH = {
                            "load_camera_json", "project_keypoints", "compute_binary_gt", "_iou_bool", "run_minaret_kp_evaluation",
                            "run_minaret_iou_evaluation", "run_part_minaret_binary_iou"],
     "eval_helpers": ["filter_mesh", "_downsample", "chamfer_distance", "fscore_with_threshold", "pca_shape_similarity", "voxel_iou",
-                     "compute_nn_stats", "compute_nn_distances", "f1_curve_from_distances", "compute_f1_curve"],
+                     "compute_nn_stats", "compute_nn_distances", "f1_curve_from_distances", "compute_f1_curve", "compute_triangle_normals",
+                     "compute_vertex_normals", "compute_surface_metrics"],
 }
 
 

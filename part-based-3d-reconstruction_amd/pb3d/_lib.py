@@ -143,6 +143,10 @@ _SIGNATURES = {
     "pb3d_nn_dist_dev": [vp, vp, C.c_int, i64, vp, C.c_int, i64, C.c_int, vp],
     "pb3d_nn_grid_shape": [dblp, i64, i64p],
     "pb3d_voxel_iou_counts_dev": [vp, vp, C.c_int, i64, vp, C.c_int, i64, dblp, C.c_double, C.c_int, C.c_int, C.c_int, vp],
+    "pb3d_knn_dev": [vp, vp, C.c_int, i64, vp, C.c_int, i64, C.c_int, vp, vp],
+    "pb3d_triangle_normals_dev": [vp, vp, C.c_int, i64, vp, C.c_int, i64, vp],
+    "pb3d_vertex_normals_dev": [vp, vp, C.c_int, i64, vp, C.c_int, i64, vp],
+    "pb3d_surface_metrics_dev": [vp, vp, vp, C.c_int, i64, vp, C.c_int, vp, vp, vp],
 }
 class IouRow(C.Structure):
     """pb3d_iou_row (include/pb3d.h)"""
@@ -185,6 +189,8 @@ def check(rc):
         msg = load().pb3d_last_error().decode("utf-8", "replace")
         if rc == -1:
             raise ValueError(msg)
+        if rc == -6:        # PB3D_EINDEX
+            raise IndexError(msg)
         raise Pb3dError(f"libpb3d error {rc}: {msg}")
 
 

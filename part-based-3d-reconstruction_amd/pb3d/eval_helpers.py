@@ -11,8 +11,14 @@ thresholds and F1 run there with the reference's own NumPy expressions.  voxel_i
 (pb3d_voxel_iou_counts_dev) after the host has computed bounds_min, step and iters with the reference's expressions from the exact
 device bounding box.  pca_shape_similarity and filter_mesh are host NumPy.
 
+The mesh regularity block (:198-245) runs on the device too (csrc/surface.hip): compute_triangle_normals and compute_vertex_normals
+bit for bit NumPy's, in the vertex dtype; compute_surface_metrics on the exact k nearest neighbours of pb3d_knn_dev (csrc/nn.hip, rows
+ordered by (squared distance, index): sklearn breaks ties by traversal order, so the two agree wherever every vertex's k-th and
+(k+1)-th distances differ) with the per-vertex spread of normal angles, smallest PCA eigenvalue and mean offset in float64; the last
+np.mean of each is the reference's own, on the downloaded per-vertex arrays.
+
 Not mirrored: get_marching_cubes_mesh and pointcloud_to_voxel_grid (marching cubes and the missing
-utils.preprocess_helpers upstream) and compute_surface_metrics."""
+utils.preprocess_helpers upstream)."""
 import ctypes as C
 
 import numpy as np
@@ -21,7 +27,11 @@ from . import _lib
 
 __all__ = ["filter_mesh", "chamfer_distance", "fscore_with_threshold", "pca_shape_similarity", "voxel_iou", "compute_nn_stats",
            "compute_nn_distances", "f1_curve_from_distances", "compute_f1_curve", "nn_distances", "nn_distances_resident",
-           "points_bounds_resident", "voxel_iou_counts_resident", "voxel_iou_counts"]
+           "points_bounds_resident", "voxel_iou_counts_resident", "voxel_iou_counts", "knn", "knn_resident", "compute_triangle_normals",
+           "compute_vertex_normals", "compute_surface_metrics", "surface_metrics_per_vertex", "triangle_normals_resident",
+           "vertex_normals_resident", "surface_metrics_resident", "KNN_MAX_K"]
+
+KNN_MAX_K = 32      # PB3D_KNN_MAX_K
 
 
 # ---- geometry helpers (:18-22) ---------------------------------------------------------------------------------------------------------
@@ -228,6 +238,194 @@ def compute_nn_stats(pts, max_points=50000):
         "NN Mean ↓": nn.mean(),
         "NN Std ↓": nn.std(),
         "NN CV ↓": nn.std() / (nn.mean() + 1e-8)
+    }
+
+
+# ---- exact k nearest neighbours (NearestNeighbors(n_neighbors=k).fit(B).kneighbors(A)) ----------------------------------------------
+def _check_k(k, n_fit):
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)):
+        raise TypeError(f"n_neighbors does not take {type(k)} value, enter integer value")
+    if k < 1 or k > KNN_MAX_K:
+        raise ValueError(f"k must be in [1, {KNN_MAX_K}] (got {k})")
+    if k > n_fit:
+        raise ValueError(f"Expected n_neighbors <= n_samples_fit, but n_neighbors = {k}, n_samples_fit = {n_fit}")
+    return int(k)
+
+
+def _check_k_metrics(k, nv):
+    """compute_surface_metrics' k: the neighbour search's limits, and PCA(n_components=3) needs three samples"""
+    k = _check_k(k, nv)
+    if k < 3:
+        raise ValueError(f"n_components=3 must be between 0 and min(n_samples, n_features)={k} with svd_solver='full'")
+    return k
+
+
+def _finite(a, what):
+    if not np.isfinite(a).all():
+        raise ValueError(f"Input {what} contains NaN or infinity.")
+
+
+def knn_resident(d_A, nA, d_B, nB, k, a_f64=True, b_f64=True, dist=True):
+    """pb3d_knn_dev: (DeviceBuffer of nA x k float64 distances or None, DeviceBuffer of nA x k int32 positions in d_B), each row
+    ascending by (squared distance, position)."""
+    from . import device as dev
+    k = _check_k(k, int(nB))
+    d_idx = dev.DeviceBuffer(max(1, int(nA) * k) * 4)
+    d_dist = dev.DeviceBuffer(max(1, int(nA) * k) * 8) if dist else None
+    try:
+        _lib.check(_lib.load().pb3d_knn_dev(_lib.ctx(), _ptr(d_A), int(bool(a_f64)), int(nA), _ptr(d_B), int(bool(b_f64)), int(nB), k,
+                                            _ptr(d_dist), _ptr(d_idx)))
+    except BaseException:
+        d_idx.free()
+        if d_dist is not None:
+            d_dist.free()
+        raise
+    return d_dist, d_idx
+
+
+def knn(A, B, k):
+    """(dist float64 (len(A), k), idx int32 (len(A), k)): the k nearest points of B for each point of A, nearest first; equal
+    distances in ascending index order, which also decides who is in the row.  The distances are bit for bit
+    NearestNeighbors(n_neighbors=k).fit(B).kneighbors(A)[0]; the indices are too wherever no two candidates tie."""
+    from . import device as dev
+    a, af = _cloud(A, "A")
+    b, bf = _cloud(B, "B")
+    k = _check_k(k, len(b))
+    _finite(a, "A")
+    _finite(b, "B")
+    if len(a) == 0:
+        return np.zeros((0, k), np.float64), np.zeros((0, k), np.int32)
+    d_a = dev.from_numpy(a)
+    d_b = d_a if B is A else dev.from_numpy(b)
+    bufs = [d_a] + ([] if d_b is d_a else [d_b])
+    try:
+        d_dist, d_idx = knn_resident(d_a, len(a), d_b, len(b), k, af, bf)
+        bufs += [d_dist, d_idx]
+        return d_dist.download((len(a), k), np.float64), d_idx.download((len(a), k), np.int32)
+    finally:
+        for buf in bufs:
+            buf.free()
+
+
+# ---- mesh regularity (:198-245) --------------------------------------------------------------------------------------------------------
+def _mesh_arrays(vertices, faces):
+    """(vertices, vertex flag, faces int64) as the kernels read them; the reference's dtypes: float32 stays, other reals -> float64"""
+    v, vf = _cloud(vertices, "vertices")
+    f = np.asarray(faces)
+    if f.dtype.kind not in "iu":
+        raise IndexError("arrays used as indices must be of integer (or boolean) type")
+    if f.ndim != 2 or f.shape[1] != 3:
+        raise ValueError(f"faces must be an (m, 3) array (got shape {f.shape})")
+    if f.dtype.kind == "u" and f.size and int(f.max()) >= len(v):       # before the cast to int64 could wrap it
+        raise IndexError(f"index {int(f.max())} is out of bounds for axis 0 with size {len(v)}")
+    return v, vf, np.ascontiguousarray(f, dtype=np.int64)
+
+
+def triangle_normals_resident(d_verts, nv, d_faces, nf, verts_f64=False, faces_i64=False, out=None):
+    """pb3d_triangle_normals_dev: a DeviceBuffer of nf x 3 face normals in the vertex dtype (IndexError on a bad face index)"""
+    from . import device as dev
+    d_out = out if out is not None else dev.DeviceBuffer(max(1, int(nf)) * 3 * (8 if verts_f64 else 4))
+    _lib.check(_lib.load().pb3d_triangle_normals_dev(_lib.ctx(), _ptr(d_verts), int(bool(verts_f64)), int(nv), _ptr(d_faces),
+                                                     int(bool(faces_i64)), int(nf), _ptr(d_out)))
+    return d_out
+
+
+def vertex_normals_resident(d_verts, nv, d_faces, nf, verts_f64=False, faces_i64=False, out=None):
+    """pb3d_vertex_normals_dev: a DeviceBuffer of nv x 3 vertex normals in the vertex dtype (IndexError on a bad face index)"""
+    from . import device as dev
+    d_out = out if out is not None else dev.DeviceBuffer(max(1, int(nv)) * 3 * (8 if verts_f64 else 4))
+    try:
+        _lib.check(_lib.load().pb3d_vertex_normals_dev(_lib.ctx(), _ptr(d_verts), int(bool(verts_f64)), int(nv), _ptr(d_faces),
+                                                       int(bool(faces_i64)), int(nf), _ptr(d_out)))
+    except BaseException:
+        if out is None:
+            d_out.free()
+        raise
+    return d_out
+
+
+def surface_metrics_resident(d_verts, nv, d_faces, nf, k=20, verts_f64=False, faces_i64=False):
+    """The per-vertex quantities of compute_surface_metrics for a resident mesh (pb3d.device.meshify(..., download=False) hands out
+    float32 vertices and int32 faces): a DeviceBuffer of 3 x nv float64 -- normal angle spread (degrees), smallest PCA eigenvalue,
+    |neighbour mean - vertex| -- from pb3d_vertex_normals_dev, pb3d_knn_dev on the vertices themselves and pb3d_surface_metrics_dev.
+    The vertices must be finite."""
+    from . import device as dev
+    nv = int(nv)
+    k = _check_k_metrics(k, nv)
+    bufs = []
+    try:
+        d_n = vertex_normals_resident(d_verts, nv, d_faces, nf, verts_f64, faces_i64)
+        bufs.append(d_n)
+        _, d_idx = knn_resident(d_verts, nv, d_verts, nv, k, verts_f64, verts_f64, dist=False)
+        bufs.append(d_idx)
+        d_out = dev.DeviceBuffer(max(1, nv) * 3 * 8)
+        try:
+            _lib.check(_lib.load().pb3d_surface_metrics_dev(_lib.ctx(), _ptr(d_verts), _ptr(d_n), int(bool(verts_f64)), nv, _ptr(d_idx), k,
+                                                            d_out.at(0), d_out.at(nv * 8), d_out.at(2 * nv * 8)))
+        except BaseException:
+            d_out.free()
+            raise
+        return d_out
+    finally:
+        for buf in bufs:
+            buf.free()
+
+
+def _normals(vertices, faces, per_vertex):
+    from . import device as dev
+    v, vf, f = _mesh_arrays(vertices, faces)
+    n = len(v) if per_vertex else len(f)
+    if len(v) == 0 and len(f):
+        v[f[:, 0]]                                                      # the reference's IndexError
+    if n == 0:
+        return np.zeros((0, 3), v.dtype)
+    d_v, d_f = dev.from_numpy(v), dev.from_numpy(f if len(f) else np.zeros((1, 3), np.int64))
+    d_out = None
+    try:
+        fn = vertex_normals_resident if per_vertex else triangle_normals_resident
+        d_out = fn(d_v, len(v), d_f, len(f), vf, True)
+        return d_out.download((n, 3), v.dtype)
+    finally:
+        for buf in (d_v, d_f, d_out):
+            if buf is not None:
+                buf.free()
+
+
+def compute_triangle_normals(vertices, faces):
+    """(m, 3) unit face normals in the vertex dtype, bit for bit the reference's (:198-203)"""
+    return _normals(vertices, faces, per_vertex=False)
+
+
+def compute_vertex_normals(vertices, faces):
+    """(n, 3) vertex normals in the vertex dtype: the face normals of each vertex added in ascending face order and normalised, bit for
+    bit the reference's loop (:206-212)"""
+    return _normals(vertices, faces, per_vertex=True)
+
+
+def surface_metrics_per_vertex(vertices, faces, k=20):
+    """(normal_stds, roughness_vals, mean_curvatures): the three per-vertex lists of compute_surface_metrics as float64 arrays"""
+    from . import device as dev
+    v, vf, f = _mesh_arrays(vertices, faces)
+    k = _check_k_metrics(k, len(v))
+    _finite(v, "X")
+    d_v, d_f = dev.from_numpy(v), dev.from_numpy(f if len(f) else np.zeros((1, 3), np.int64))
+    d_out = None
+    try:
+        d_out = surface_metrics_resident(d_v, len(v), d_f, len(f), k, vf, True)
+        out = d_out.download((3, len(v)), np.float64)
+        return out[0], out[1], out[2]
+    finally:
+        for buf in (d_v, d_f, d_out):
+            if buf is not None:
+                buf.free()
+
+
+def compute_surface_metrics(vertices, faces, k=20):
+    normal_stds, roughness_vals, mean_curvatures = surface_metrics_per_vertex(vertices, faces, k)
+    return {
+        "Normal StdDev (°)": np.mean(normal_stds),
+        "Mean Roughness (λ₃)": np.mean(roughness_vals),
+        "Mean Curvature": np.mean(mean_curvatures),
     }
 
 
