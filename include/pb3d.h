@@ -17,6 +17,10 @@
  *     return without synchronising (call pb3d_sync); the un-suffixed entry points take
  *     HOST pointers, stage through device scratch and return when the result is in the
  *     caller's buffer (these are what the NumPy shim calls);
+ *   - device pointers need the alignment of their element type and no more (any byte for
+ *     uint8_t*, 4 for float* / int32_t* / uint32_t*, 8 for double* / int64_t* / uint64_t*),
+ *     unless the entry says otherwise: a view into a larger allocation (a slab, a rank's slot)
+ *     is as good as the allocation's base; only speed may depend on the address;
  *   - a context belongs to one GPU and one HIP stream; use it from one thread at a time.
  *   - There is NO CPU fallback: every op fails with PB3D_ENODEVICE when no GPU is present.
  */
@@ -148,7 +152,8 @@ int pb3d_color_apply(pb3d_ctx* ctx, const uint8_t* carved, int64_t W, int64_t H,
 /* ---- global_carve, reference utils/voxel_carving_utils.py:269-298 -------------------------
  * ones((w,h,w)) -> process_voxel_grid -> colour.  bin_hw: (h,w) truthiness uint8,
  * rgb_hw3: (h,w,3).  out: (w,h,w,3).  The x-range [x0,x1) variant computes only that slab
- * of the output (slab pointer = start of the slab), for sharded runs. */
+ * of the output (slab pointer = start of the slab, any byte address), for sharded runs; a
+ * proper slab needs angle_interval == 90 (PB3D_EINVAL otherwise). */
 int pb3d_global_carve_dev(pb3d_ctx* ctx, const uint8_t* d_bin_hw, const uint8_t* d_rgb_hw3, int64_t h, int64_t w,
                           int angle_interval, int64_t x0, int64_t x1, uint8_t* d_out_slab);
 int pb3d_global_carve(pb3d_ctx* ctx, const uint8_t* bin_hw, const uint8_t* rgb_hw3, int64_t h, int64_t w,
@@ -553,7 +558,9 @@ int pb3d_part_carve_label_dev(pb3d_ctx* ctx, const uint8_t* d_label, int64_t W, 
 /* ---- seeded synthetic inputs generated on the device ---------------------
  * mask16: labels (S,S) uint8 in 0..15 by the closed formula scaled from S=1024; binary and
  * rgb derive from it.  Any output pointer may be NULL.  sem grid: palette[label16 of a
- * splitmix64 hash of the voxel index] (kind 0) -- worst case for any sparsity trick. */
+ * splitmix64 hash of the voxel index] (kind 0) -- worst case for any sparsity trick.
+ * pb3d_synth_sem_dev needs d_slab_rgb 4-byte aligned (it stores dwords) and refuses other
+ * pointers with PB3D_EINVAL. */
 int pb3d_synth_mask16_dev(pb3d_ctx* ctx, int64_t S, uint8_t* d_label_hw, uint8_t* d_binary_hw, uint8_t* d_rgb_hw3,
                           uint8_t* d_binary_wh);
 int pb3d_synth_sem_dev(pb3d_ctx* ctx, int64_t x0, int64_t x1, int64_t H, int64_t D, uint64_t seed, uint8_t* d_slab_rgb);

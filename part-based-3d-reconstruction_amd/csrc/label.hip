@@ -10,9 +10,9 @@
 
 #include "pb3d_internal.h"
 
-namespace {
+#include "lane48.h"      // u32x4, and u32x4_u: the conversions take caller pointers at any byte address
 
-typedef u32 u32x4 __attribute__((ext_vector_type(4)));
+namespace {
 
 struct LabelHash {
     u32 K;            // odd 24-bit multiplier; entry = bits 31..24 of mul24(colour, K)
@@ -63,7 +63,7 @@ __global__ __launch_bounds__(256) void k_rgb_to_label(const u8* __restrict__ rgb
         const i64 v0 = 16 * g;
         u32 w[12];
         if (v0 + 16 <= nvox) {
-            const u32x4* p = (const u32x4*)(rgb + 3 * v0);
+            const u32x4_u* p = (const u32x4_u*)(rgb + 3 * v0);
 #pragma unroll
             for (int k = 0; k < 3; ++k) { const u32x4 t = p[k]; w[4 * k] = t.x; w[4 * k + 1] = t.y; w[4 * k + 2] = t.z; w[4 * k + 3] = t.w; }
         } else {
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(256) void k_rgb_to_label(const u8* __restrict__ rgb
             if (!hit && v0 + i < nvox) bad = true;
             out[i >> 2] |= (hit ? (t & 0xffu) : 0xffu) << (8 * (i & 3));
         }
-        if (v0 + 16 <= nvox) { u32x4 r; r.x = out[0]; r.y = out[1]; r.z = out[2]; r.w = out[3]; *(u32x4*)(label + v0) = r; }
+        if (v0 + 16 <= nvox) { u32x4 r; r.x = out[0]; r.y = out[1]; r.z = out[2]; r.w = out[3]; *(u32x4_u*)(label + v0) = r; }
         else for (i64 i = 0; v0 + i < nvox; ++i) label[v0 + i] = (u8)(out[i >> 2] >> (8 * (i & 3)));
     }
     if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(unknown, 1);
@@ -102,7 +102,7 @@ __global__ __launch_bounds__(256) void k_label_to_rgb(const u8* __restrict__ lab
     for (i64 g = (i64)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += (i64)gridDim.x * blockDim.x) {
         const i64 v0 = 16 * g;
         u32 l[4] = {0, 0, 0, 0};
-        if (v0 + 16 <= nvox) { const u32x4 t = *(const u32x4*)(label + v0); l[0] = t.x; l[1] = t.y; l[2] = t.z; l[3] = t.w; }
+        if (v0 + 16 <= nvox) { const u32x4 t = *(const u32x4_u*)(label + v0); l[0] = t.x; l[1] = t.y; l[2] = t.z; l[3] = t.w; }
         else for (i64 i = 0; v0 + i < nvox; ++i) l[i >> 2] |= (u32)label[v0 + i] << (8 * (i & 3));
         u32 c[16];
 #pragma unroll
@@ -120,7 +120,7 @@ __global__ __launch_bounds__(256) void k_label_to_rgb(const u8* __restrict__ lab
             w[3 * q + 2] = (d >> 16) | (e << 8);
         }
         if (v0 + 16 <= nvox) {
-            u32x4* o = (u32x4*)(rgb + 3 * v0);
+            u32x4_u* o = (u32x4_u*)(rgb + 3 * v0);
 #pragma unroll
             for (int k = 0; k < 3; ++k) { u32x4 r; r.x = w[4 * k]; r.y = w[4 * k + 1]; r.z = w[4 * k + 2]; r.w = w[4 * k + 3]; o[k] = r; }
         } else {
