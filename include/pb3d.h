@@ -335,6 +335,21 @@ int pb3d_vertex_normals_dev(pb3d_ctx* ctx, const void* d_verts, int verts_f64, i
 int pb3d_surface_metrics_dev(pb3d_ctx* ctx, const void* d_verts, const void* d_normals, int verts_f64, int64_t nv, const int32_t* d_idx, int k,
                              double* d_normal_std, double* d_roughness, double* d_curvature);
 
+/* ---- density volume of a point cloud, reference utils/eval_helpers.py:178-189 (pointcloud_to_voxel_grid) ---------------------------
+ * d_out: grid_size^3 float32, bit for bit the reference's volume for the resident (n, 3) list d_pts (float32 rows, or float64 with
+ * pts_f64 = 1; any 4- / 8-byte aligned base):
+ *   norm = (p - min) / ((max - min).max() + 1e-8), its y column shifted so that the maximum is 0 (normalize_preserve_aspect), every
+ *   operation rounded in the point dtype; voxel = trunc(norm * (grid_size - 1)), a negative index wrapping to the far planes as NumPy's
+ *   does; the value of a voxel is (float)min(count, 2^24), where np.add.at on float32 stops growing.
+ *   radius > 0: three passes of the Gaussian filter along axes 0, 1, 2 with the 2 * radius + 1 float64 `weights` (symmetric; the
+ *   host builds them, radius = int(4 * sigma + 0.5)), float32 in and out of every pass, per output in float64
+ *   tmp = in[l] * w[r]; for jj = -r .. -1: tmp += (in[l + jj] + in[l - jj]) * w[r + jj], reflect boundary, no FMA.  radius = 0: no
+ *   filter, weights may be NULL.  Last, the six faces of the cube are 0 (grid_size <= 2: all of it).
+ * 1 <= n <= 2^31 - 1, 1 <= grid_size <= 1024, 0 <= radius <= 64.  The coordinates must be finite: the entry computes the exact bounds
+ * on the device, waits once for them and refuses bounds that are not finite.  Scratch: one volume of 4 * grid_size^3 bytes. */
+int pb3d_density_grid_resident(pb3d_ctx* ctx, const void* d_pts, int pts_f64, int64_t n, int grid_size, const double* weights, int radius,
+                               float* d_out);
+
 /* ---- compute_partwise_iou, reference utils/camera_estimation.py:770-787 -------------------
  * per colour k: inter[k] = #(a==c & b==c), uni[k] = #(a==c | b==c) over npix RGB pixels. */
 int pb3d_partwise_iou_dev(pb3d_ctx* ctx, const uint8_t* d_a, const uint8_t* d_b, int64_t npix,

@@ -134,8 +134,13 @@ enum pb3d_slot : int {
     PB3D_SLOT_SURF_INCIDENT = 64,
     PB3D_SLOT_SURF_SCAN_LOCAL = 65,
     PB3D_SLOT_SURF_SCAN_SEGS = 66,
+    // call-local, csrc/density.hip: the bounds read back by the host, the u32 count volume (the filter's second pass writes its float32
+    // result over it) and the filter weights.  Slots of their own: the bounds pass inside uses NN_BOUNDS_PARTIALS, nothing else
+    PB3D_SLOT_DENSITY_BOUNDS = 67,
+    PB3D_SLOT_DENSITY_COUNTS = 68,
+    PB3D_SLOT_DENSITY_WEIGHTS = 69,
 
-    PB3D_SLOT_COUNT = 67
+    PB3D_SLOT_COUNT = 70
 };
 
 // What a *_count leaves for its *_fill: the use counters (pb3d_ctx::scratch_use) of the slots the fill reads, taken when the count has

@@ -147,6 +147,7 @@ _SIGNATURES = {
     "pb3d_triangle_normals_dev": [vp, vp, C.c_int, i64, vp, C.c_int, i64, vp],
     "pb3d_vertex_normals_dev": [vp, vp, C.c_int, i64, vp, C.c_int, i64, vp],
     "pb3d_surface_metrics_dev": [vp, vp, vp, C.c_int, i64, vp, C.c_int, vp, vp, vp],
+    "pb3d_density_grid_resident": [vp, vp, C.c_int, i64, C.c_int, dblp, C.c_int, vp],
 }
 class IouRow(C.Structure):
     """pb3d_iou_row (include/pb3d.h)"""

@@ -17,9 +17,15 @@ ordered by (squared distance, index): sklearn breaks ties by traversal order, so
 (k+1)-th distances differ) with the per-vertex spread of normal angles, smallest PCA eigenvalue and mean offset in float64; the last
 np.mean of each is the reference's own, on the downloaded per-vertex arrays.
 
-Not mirrored: get_marching_cubes_mesh and pointcloud_to_voxel_grid (marching cubes and the missing
-utils.preprocess_helpers upstream)."""
+pointcloud_to_voxel_grid (:178-189) runs on the device as well (csrc/density.hip, pb3d_density_grid_resident): the normalisation of
+pb3d.preprocess_helpers in the point dtype from the exact device bounds, integer counts by atomics (exact in any order; a float32
+cell of np.add.at stops at 2^24, so the value is min(count, 2^24)), then the reference's Gaussian filter restated pass by pass -- its
+float64 summation order per output, float32 between the passes, reflect boundary, no FMA -- and the zero faces.  The volume is bit
+for bit the reference's at any point count, so full-resolution clouds and finer grids need no downsampling.
+
+Not mirrored: get_marching_cubes_mesh (no scikit-image here to take float-level marching-cubes fixtures from)."""
 import ctypes as C
+import operator
 
 import numpy as np
 
@@ -29,9 +35,11 @@ __all__ = ["filter_mesh", "chamfer_distance", "fscore_with_threshold", "pca_shap
            "compute_nn_distances", "f1_curve_from_distances", "compute_f1_curve", "nn_distances", "nn_distances_resident",
            "points_bounds_resident", "voxel_iou_counts_resident", "voxel_iou_counts", "knn", "knn_resident", "compute_triangle_normals",
            "compute_vertex_normals", "compute_surface_metrics", "surface_metrics_per_vertex", "triangle_normals_resident",
-           "vertex_normals_resident", "surface_metrics_resident", "KNN_MAX_K"]
+           "vertex_normals_resident", "surface_metrics_resident", "KNN_MAX_K", "pointcloud_to_voxel_grid", "density_grid_resident"]
 
 KNN_MAX_K = 32      # PB3D_KNN_MAX_K
+DENSITY_MAX_GRID = 1024     # the limits of pb3d_density_grid_resident
+DENSITY_MAX_RADIUS = 64
 
 
 # ---- geometry helpers (:18-22) ---------------------------------------------------------------------------------------------------------
@@ -226,6 +234,63 @@ def voxel_iou_counts(A, B, resolution=96, dilate_frac=0.01):
 def voxel_iou(A, B, resolution=96, dilate_frac=0.01):
     inter, union = voxel_iou_counts(A, B, resolution, dilate_frac)
     return inter / union if union > 0 else np.nan
+
+
+# ---- density volume (:178-189) ---------------------------------------------------------------------------------------------------------
+def _density_args(grid_size, sigma):
+    """(grid_size, radius, weights): the limits of pb3d_density_grid_resident checked before anything is allocated, and the Gaussian
+    kernel as the reference's Gaussian filter builds it (float64, radius = int(4 * sigma + 0.5), normalised by its own sum)"""
+    G = operator.index(grid_size)
+    if not 1 <= G <= DENSITY_MAX_GRID:
+        raise ValueError(f"grid_size must be in [1, {DENSITY_MAX_GRID}] (got {G})")
+    if not sigma > 0:
+        return G, 0, None
+    sd = float(sigma)
+    radius = int(4.0 * sd + 0.5)
+    if radius > DENSITY_MAX_RADIUS:
+        raise ValueError(f"sigma = {sd} gives a filter radius of {radius}; the device filter is limited to radius {DENSITY_MAX_RADIUS} "
+                         f"(sigma < {(DENSITY_MAX_RADIUS + 0.5) / 4.0})")
+    x = np.arange(-radius, radius + 1)
+    phi_x = np.exp(-0.5 / (sd * sd) * x ** 2)
+    return G, radius, np.ascontiguousarray(phi_x / phi_x.sum())
+
+
+def density_grid_resident(d_pts, n, grid_size=128, sigma=1.0, f64=True, out=None):
+    """pb3d_density_grid_resident: a DeviceBuffer of grid_size^3 float32, pointcloud_to_voxel_grid of the resident (n, 3) list d_pts
+    (float64 rows, or float32 with f64 False), bit for bit the reference's volume.  The coordinates must be finite."""
+    from . import device as dev
+    G, radius, w = _density_args(grid_size, sigma)
+    d_out = out if out is not None else dev.DeviceBuffer(G ** 3 * 4)
+    try:
+        _lib.check(_lib.load().pb3d_density_grid_resident(_lib.ctx(), _ptr(d_pts), int(bool(f64)), int(n), G,
+                                                          None if w is None else _lib.p_dbl(w), radius, _ptr(d_out)))
+    except BaseException:
+        if out is None:
+            d_out.free()
+        raise
+    return d_out
+
+
+def pointcloud_to_voxel_grid(points, grid_size=128, sigma=1.0):
+    """float32 (grid_size,) * 3 density volume, bit for bit the reference's: the cloud normalised by
+    pb3d.preprocess_helpers.normalize_preserve_aspect in its own dtype (float32 stays float32, other reals become float64), the points
+    counted per voxel trunc(norm * (grid_size - 1)) -- the y indices are <= 0 and wrap to the far planes, as NumPy's do -- smoothed by
+    the reference's Gaussian filter when sigma > 0, and the six faces set to 0."""
+    from . import device as dev
+    p, f64 = _cloud(points)
+    G, _, _ = _density_args(grid_size, sigma)
+    if len(p) == 0:
+        raise ValueError("zero-size array to reduction operation minimum which has no identity")
+    _finite(p, "points")
+    d_p = dev.from_numpy(p)
+    d_out = None
+    try:
+        d_out = density_grid_resident(d_p, len(p), G, sigma, f64)
+        return d_out.download((G, G, G), np.float32)
+    finally:
+        d_p.free()
+        if d_out is not None:
+            d_out.free()
 
 
 # ---- regularity metrics (:118-130) -----------------------------------------------------------------------------------------------------

@@ -254,6 +254,8 @@ def main():
         inter_eval(a.reps, res, cpu_ref=not a.no_cpu_ref)
     if "MESH" in ops:
         meshify(a.reps, res)
+    if "DENS" in ops:
+        density(a.reps, res, cpu_ref=not a.no_cpu_ref)
     if d_col is not None:
         d_col.free()
     return res
@@ -546,6 +548,55 @@ def meshify(reps, res):
             print(json.dumps(r), flush=True)
             res.append(r)
         d.free()
+
+
+def density(reps, res, cpu_ref=True):
+    """DENS, pointcloud_to_voxel_grid (csrc/density.hip) on every point of the stored Taj grid (pb3d_points_extract_dev, float32) at
+    grid_size 128 and 512, sigma 1: the resident form (bounds with their one host wait, clear, scatter, three filter passes; device
+    events), the NumPy API (upload, the same, download of the volume; host wall clock, best of reps) and, with cpu_ref, the reference's
+    composition -- normalisation, np.add.at, scipy.ndimage.gaussian_filter, zero faces -- on this host and the same input (context
+    only: one CPU measurement, and the reference itself samples 20-50 k points first)."""
+    from pb3d.eval_helpers import density_grid_resident
+    from pb3d.preprocess_helpers import normalize_preserve_aspect
+    lib, L = pb3d._lib.load(), pb3d._lib
+    taj = np.load(os.path.join(ROOT, "tests", "golden", "stored_Taj_voxel_grid.npz"))["voxel_grid"]
+    nvox = int(np.prod(taj.shape[:3]))
+    d_g = dev.from_numpy(taj)
+    d_tp, d_tc = dev.DeviceBuffer(nvox * 12), dev.DeviceBuffer(nvox * 3)
+    n = C.c_int64(0)
+    L.check(lib.pb3d_points_extract_dev(L.ctx(), C.c_void_p(d_g.ptr), *taj.shape[:3], 3, None, 0, nvox, C.c_void_p(d_tp.ptr),
+                                        C.c_void_p(d_tc.ptr), C.byref(n)))
+    npts = n.value
+    pts = d_tp.download((npts, 3), np.float32)
+    for G in (128, 512):
+        d_out = dev.DeviceBuffer(G ** 3 * 4)
+        ms = timeit(lambda: density_grid_resident(d_tp, npts, G, 1.0, f64=False, out=d_out), reps)
+        got = d_out.download((G, G, G), np.float32)
+        d_out.free()
+        pb3d.pointcloud_to_voxel_grid(pts, G, 1.0)
+        wall = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            pb3d.pointcloud_to_voxel_grid(pts, G, 1.0)
+            wall.append(time.perf_counter() - t0)
+        r = {"op": "DENS", "name": "pointcloud_to_voxel_grid, every point of the stored Taj grid", "grid_shape": list(taj.shape[:3]),
+             "points": int(npts), "grid_size": G, "sigma": 1.0, "resident_ms": round(ms, 4), "numpy_api_ms": round(1e3 * min(wall), 3)}
+        if cpu_ref:
+            from scipy.ndimage import gaussian_filter
+            t0 = time.perf_counter()
+            idx = (normalize_preserve_aspect(pts) * (G - 1)).astype(int)
+            vol = np.zeros((G, G, G), np.float32)
+            np.add.at(vol, (idx[:, 0], idx[:, 1], idx[:, 2]), 1)
+            vol = gaussian_filter(vol, sigma=1.0)
+            vol[[0, -1], :, :] = 0
+            vol[:, [0, -1], :] = 0
+            vol[:, :, [0, -1]] = 0
+            r["reference_cpu_ms"] = round(1e3 * (time.perf_counter() - t0), 1)
+            r["equal_bits"] = bool(np.array_equal(vol.view(np.uint32), got.view(np.uint32)))
+        print(json.dumps(r), flush=True)
+        res.append(r)
+    for b in (d_g, d_tp, d_tc):
+        b.free()
 
 
 if __name__ == "__main__":
