@@ -350,6 +350,36 @@ int pb3d_surface_metrics_dev(pb3d_ctx* ctx, const void* d_verts, const void* d_n
 int pb3d_density_grid_resident(pb3d_ctx* ctx, const void* d_pts, int pts_f64, int64_t n, int grid_size, const double* weights, int radius,
                                float* d_out);
 
+/* ---- notebook 2: bbox camera init and projection overlays, reference utils/camera_estimation.py:56-108, :346-477 ----------------
+ * grid_bounds: d_out[0] = the number of voxels of the resident (A0,A1,A2,C) grid whose colour (C = 3) / label (C = 1) is one of the
+ *   ncolors <= 31 non-zero `colors` (ncolors = 0: any non-zero voxel), d_out[1..3] = their inclusive minimum (a0, a1, a2), d_out[4..6]
+ *   the maximum (7 int64 on the device; count 0 leaves INT64_MAX / -1).  One read of the grid; replaces
+ *   get_voxel_points_by_parts(...)[0].min / max(axis=0) of :61-66 (x = a2, y = a1, z = a0) without building the point list.
+ * grid_hit_bits: d_bits (Himg x Wimg uint32, cleared first) bit k = some voxel of colors[k] projects onto the pixel with the
+ *   arithmetic of project_colored_voxels (utils/projection_utils.py:5-23: Z < 1e-8 clamped, no depth test; voxel (a0,a1,a2) is the
+ *   float32 point (a2,a1,a0); R, cam, prec as for pb3d_project_dev).  That is all(proj == colour) of a projection of the part alone
+ *   (:387-395), for up to 31 parts in one sweep of the grid.
+ * overlay_compose: the images of visualize_voxel_projection_iou from d_bits (nplanes = ceil(nparts / 31) bit images one after the
+ *   other; part j is bit j % 31 of plane j / 31), the resident d_image (Himg,Wimg,3) and the parts' RGB `colors` (nparts <= 248).
+ *   PB3D_OVERLAY_PART_ON_WHOLE (:394-419): d_vis = nparts images; image j is (0.7 * proj + 0.3 * image).astype(uint8) in float64 with
+ *     proj = colour j where bit j is set, then (255,255,0) on binary_dilation(gt & prj) & ~(gt & prj), gt = all(image == colour j)
+ *     (the 4-neighbour cross, outside = false); d_counts[2j] = #(gt & prj), d_counts[2j+1] = #(gt | prj).
+ *   PB3D_OVERLAY_WHOLE_ON_WHOLE (:433-452): one image, gt = any(image != bg), prj = any bit (or d_extra_prj[px] != 0, an optional
+ *     Himg x Wimg uint8 mask of parts projected elsewhere): green gt only, red prj only, yellow both; d_counts[0..1].
+ *   PB3D_OVERLAY_WHOLE_ON_WHOLE_COLOR (:462-466): one image, per channel the sum of the colours of the parts whose bit is set,
+ *     clipped at 255, blended with the image as above; no counts. */
+#define PB3D_OVERLAY_PART_ON_WHOLE 0
+#define PB3D_OVERLAY_WHOLE_ON_WHOLE 1
+#define PB3D_OVERLAY_WHOLE_ON_WHOLE_COLOR 2
+int pb3d_grid_bounds_resident(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64_t A1, int64_t A2, int C, const uint8_t* colors, int ncolors,
+                         int64_t* d_out);
+int pb3d_grid_hit_bits_resident(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64_t A1, int64_t A2, int C, const uint8_t* colors,
+                           int ncolors, const double R[9], const double cam[3], double f, double cx, double cy, const int prec[4], int Himg,
+                           int Wimg, uint32_t* d_bits);
+int pb3d_overlay_compose_resident(pb3d_ctx* ctx, const uint32_t* d_bits, int nplanes, const uint8_t* d_image, int Himg, int Wimg,
+                             const uint8_t* colors, int nparts, const uint8_t bg[3], const uint8_t* d_extra_prj, int mode, uint8_t* d_vis,
+                             int64_t* d_counts);
+
 /* ---- compute_partwise_iou, reference utils/camera_estimation.py:770-787 -------------------
  * per colour k: inter[k] = #(a==c & b==c), uni[k] = #(a==c | b==c) over npix RGB pixels. */
 int pb3d_partwise_iou_dev(pb3d_ctx* ctx, const uint8_t* d_a, const uint8_t* d_b, int64_t npix,

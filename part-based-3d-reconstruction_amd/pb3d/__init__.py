@@ -13,6 +13,8 @@ from .labels import (Palette, extrude_from_surface_labels, get_voxel_points_by_p
 from ._hostmem import set_result_pool  # noqa: F401
 from .camera_estimation import (CameraObjective, compute_partwise_iou, coordinate_descent, powell_search, projection_iou_by_part,  # noqa: F401
                                 random_search)
+from .camera_estimation import (auto_compute_initial_params_matching_bbox, bbox_init_from_bounds, optimize_camera_with_keypoints,  # noqa: F401
+                                projection_overlays, visualize_voxel_projection_iou)
 from .eval_helpers import (chamfer_distance, compute_f1_curve, compute_nn_distances, compute_nn_stats, f1_curve_from_distances,  # noqa: F401
                            filter_mesh, fscore_with_threshold, nn_distances, pca_shape_similarity, voxel_iou)
 from .eval_helpers import (compute_surface_metrics, compute_triangle_normals, compute_vertex_normals, knn,  # noqa: F401
@@ -42,7 +44,8 @@ _PATCH = {
     "voxel_utils": ["get_voxel_points_by_parts", "extract_top_k_components", "voxel_grid_to_points", "meshify_colored_voxel_grid"],
     "projection_utils": ["project_colored_voxels"],
     "camera_estimation": ["compute_partwise_iou", "extract_minaret_voxels_by_label", "extract_minaret_masks_by_label",
-                          "extract_top_bottom_voxel_points", "extract_top_bottom_image_points", "extract_minaret_kps_for_view"],
+                          "extract_top_bottom_voxel_points", "extract_top_bottom_image_points", "extract_minaret_kps_for_view",
+                          "auto_compute_initial_params_matching_bbox", "optimize_camera_with_keypoints", "visualize_voxel_projection_iou"],
     # load_mask is left out: utils.mask_utils has a load_mask of its own (another signature) and install() rebinds by name
     "eval_helpers_intra": ["compute_global_depth_buffer", "project_part_visible", "load_voxel_grid", "resize_mask_to_voxel_grid",
                            "load_camera_json", "project_keypoints", "compute_binary_gt", "_iou_bool", "run_minaret_kp_evaluation",
@@ -79,6 +82,9 @@ def install(utils_pkg=None):
     ev = sys.modules.get(utils_pkg.__name__ + ".eval_helpers_intra")
     if ev is not None:      # visualize=True of the notebook-4 evaluations calls the reference's own plotting functions
         here.eval_helpers_intra._REF["module"] = ev
+    ce = sys.modules.get(utils_pkg.__name__ + ".camera_estimation")
+    if ce is not None and hasattr(ce, "minimize"):      # the keypoint fit runs the reference's own minimiser
+        here.camera_estimation._REF["minimize"] = ce.minimize
     vis = sys.modules.get(utils_pkg.__name__ + ".visualization")
     if vis is not None and hasattr(vis, "plot_voxel"):
         here.voxel_carving_utils.plot_voxel = vis.plot_voxel

@@ -1,5 +1,6 @@
-"""Per-part IoU between a projected image and a mask; host mirror of
-reference utils/camera_estimation.py:770-787 (the inner metric of every re-projection loop)."""
+"""Camera estimation of notebooks 2 and 3; mirror of reference utils/camera_estimation.py: the per-part IoU (:770-787, the inner
+metric of every re-projection loop), the aligner's objective and search loops (:597-725), the bbox camera init (:56-108), the
+keypoint fit (:110-170) and the projection-IoU overlays (:346-477)."""
 import ctypes as C
 
 import numpy as np
@@ -8,7 +9,11 @@ from . import _lib
 from .minarets import (extract_minaret_kps_for_view, extract_minaret_masks_by_label, extract_minaret_voxels_by_label,  # noqa: F401
                        extract_top_bottom_image_points, extract_top_bottom_voxel_points)
 
-__all__ = ["compute_partwise_iou", "CameraObjective", "projection_iou_by_part", "random_search", "coordinate_descent", "powell_search"]
+__all__ = ["compute_partwise_iou", "CameraObjective", "projection_iou_by_part", "random_search", "coordinate_descent", "powell_search",
+           "auto_compute_initial_params_matching_bbox", "bbox_init_from_bounds", "optimize_camera_with_keypoints", "projection_overlays",
+           "visualize_voxel_projection_iou"]
+
+_REF = {}       # install() leaves the reference's own `minimize` here (optimize_camera_with_keypoints)
 
 
 def partwise_iou_counts(proj_mask, gt_mask, colors):
@@ -298,3 +303,293 @@ def powell_search(objective, base, maxiter, minimize, lock_xy_equal=False):
                    options={"maxiter": int(maxiter), "maxfev": int(maxiter) * 10, "xtol": 1e-3, "ftol": 1e-3, "disp": False})
     p = from_vec(res.x)
     return p, -objective(p)
+
+
+# =====================================================================================================
+# Notebook 2: the bbox camera init (:56-108), the keypoint fit (:110-170) and the overlays (:346-477)
+# =====================================================================================================
+def grid_bounds(voxel_grid, colors=None):
+    """(count, lo, hi): the number of voxels whose colour (RGB grid) or label ((A0,A1,A2) grid) is in `colors` (None or empty: any
+    non-zero voxel; at most 31, none of them zero) and their inclusive int64 bounds (a0, a1, a2) -- np.where(mask) reduced on the
+    device in one read of the grid (pb3d_grid_bounds_resident).  count 0: lo and hi are None."""
+    from . import device as dev
+    from . import eval_helpers_intra as ev
+    d_g, shape, owned = ev._grid(voxel_grid)
+    A0, A1, A2, Cc = shape
+    tab = ev._colour_table(colors if colors is not None else [], Cc)
+    d_o = dev.DeviceBuffer(7 * 8)
+    try:
+        _lib.check(_lib.load().pb3d_grid_bounds_resident(_lib.ctx(), ev._ptr(d_g), A0, A1, A2, Cc, _lib.p_u8(tab), len(tab), C.c_void_p(d_o.ptr)))
+        out = d_o.download((7,), np.int64)
+    finally:
+        ev._free(d_o, d_g if owned else None)
+    if out[0] == 0:
+        return 0, None, None
+    return int(out[0]), out[1:4].copy(), out[4:7].copy()
+
+
+def hit_bits_resident(d_grid, shape, colors, cam_params, H, W, out=None):
+    """pb3d_grid_hit_bits_resident into a (H, W) uint32 image: `out` (a DeviceBuffer or a ctypes pointer into one) or a new DeviceBuffer"""
+    from . import device as dev
+    from . import eval_helpers_intra as ev
+    A0, A1, A2, Cc = shape
+    R, cp, prec = ev._cam(cam_params, np.float32)
+    tab = ev._colour_table(colors, Cc)
+    d_b = out if out is not None else dev.DeviceBuffer(max(1, int(H) * int(W)) * 4)
+    _lib.check(_lib.load().pb3d_grid_hit_bits_resident(_lib.ctx(), ev._ptr(d_grid), A0, A1, A2, Cc, _lib.p_u8(tab), len(tab), _lib.p_dbl(R),
+                                                  _lib.p_dbl(cp), float(cam_params["f"]), float(cam_params["cx"]), float(cam_params["cy"]),
+                                                  prec, int(H), int(W), d_b if isinstance(d_b, C.c_void_p) else C.c_void_p(d_b.ptr)))
+    return d_b
+
+
+def grid_hit_bits(voxel_grid, colors, cam_params, H, W):
+    """(H, W) uint32: bit k = some voxel of colors[k] (at most 31) projects onto the pixel, i.e.
+    np.all(project_colored_voxels(*get_voxel_points_by_parts(grid, .., [part k]), ...) == colors[k], axis=-1) for every k in one sweep"""
+    from . import eval_helpers_intra as ev
+    d_g, shape, owned = ev._grid(voxel_grid)
+    d_b = None
+    try:
+        d_b = hit_bits_resident(d_g, shape, colors, cam_params, H, W)
+        return d_b.download((int(H), int(W)), np.uint32)
+    finally:
+        ev._free(d_b, d_g if owned else None)
+
+
+def bbox_init_from_bounds(lo, hi, img_bbox_min, img_bbox_max, H_img, W_img, fov_deg=30):
+    """The scalar half of auto_compute_initial_params_matching_bbox (:64-108), host only: `lo` / `hi` are the inclusive voxel bounds
+    (a0, a1, a2) of the chosen parts, img_bbox_min / img_bbox_max the (x, y) integer bounds of the image mask.  Upstream's NumPy
+    expressions and dtypes: the bounds become the float32 (x, y, z) = (a2, a1, a0) rows that voxel_pts.min / max(axis=0) give.
+    `lo` None (the parts have no voxel): the ValueError that voxel_pts.min(axis=0) raises upstream."""
+    if lo is None:
+        np.empty((0, 3), np.float32).min(axis=0)
+    bbox_min = np.array([lo[2], lo[1], lo[0]]).astype(np.float32)
+    bbox_max = np.array([hi[2], hi[1], hi[0]]).astype(np.float32)
+    voxel_center = (bbox_min + bbox_max) / 2
+    voxel_size = np.linalg.norm(bbox_max - bbox_min)
+    img_bbox_width = np.linalg.norm(np.asarray(img_bbox_max) - np.asarray(img_bbox_min))
+    cam_pos = voxel_center + np.array([0, 0, -voxel_size * 2.0])
+    target = voxel_center
+    f = H_img / (2 * np.tan(np.deg2rad(fov_deg) / 2))
+    approx_voxel_proj_width = (voxel_size * f) / (voxel_size * 2.0)
+    scale_factor = img_bbox_width / approx_voxel_proj_width
+    f_adjusted = f * scale_factor
+    init_params = {"cam_pos": cam_pos, "target": target, "f": f_adjusted, "cx": W_img / 2, "cy": H_img / 2}
+    print(f"Estimated scale factor: {scale_factor:.4f}")
+    print(f"Adjusted focal length: {f_adjusted:.2f}")
+    return init_params
+
+
+def auto_compute_initial_params_matching_bbox(voxel_grid, image, part_colors, parts_for_alignment, fov_deg=30):
+    """Initial camera whose projection roughly matches the bounding box of the image mask (:56-108).  The voxel bounding box comes from
+    one device read of the grid (grid_bounds; NumPy grid or DeviceGrid) instead of a point list; the image bbox and the scalars are
+    upstream's NumPy expressions on the host.  No voxel of the parts, or no pixel: the ValueError of NumPy's min of an empty array."""
+    from .mask_utils import mask_parts_from_image
+    image = np.asarray(image)
+    H_img, W_img = image.shape[:2]
+    cols = []
+    for p in parts_for_alignment:
+        c = np.asarray(part_colors[p]).reshape(-1)
+        if c.size != 3:
+            raise ValueError("a part colour is (R, G, B)")
+        if np.all((c >= 0) & (c <= 255)) and np.all(c == np.floor(c)):       # any other value never equals a uint8 voxel
+            cols.append(tuple(int(v) for v in c))
+    cols = list(dict.fromkeys(cols))
+    if (0, 0, 0) in cols or len(cols) > 31:
+        # black selects the empty voxels and is no colour bit: the point path
+        from .voxel_utils import get_voxel_points_by_parts
+        grid = voxel_grid.numpy() if hasattr(voxel_grid, "numpy") else voxel_grid
+        pts = np.concatenate([get_voxel_points_by_parts(grid, {"p": c}, ["p"])[0] for c in cols])
+        lo = pts.min(axis=0)[::-1]; hi = pts.max(axis=0)[::-1]
+    else:
+        n, lo, hi = grid_bounds(voxel_grid, cols) if cols else (0, None, None)
+        if n == 0:                                          # upstream fails on the voxels before it looks at the image
+            return bbox_init_from_bounds(None, None, None, None, H_img, W_img, fov_deg)
+    seg_img = mask_parts_from_image(image, part_colors, parts_for_alignment)
+    mask = np.any(seg_img > 0, axis=-1)
+    ys, xs = np.where(mask)
+    img_bbox_min = np.array([xs.min(), ys.min()])
+    img_bbox_max = np.array([xs.max(), ys.max()])
+    return bbox_init_from_bounds(lo, hi, img_bbox_min, img_bbox_max, H_img, W_img, fov_deg)
+
+
+def optimize_camera_with_keypoints(voxel_keypoints_dict, image_keypoints_dict, image, init_params, loss_type='L2', minimize=None):
+    """Fit camera position, target and intrinsics to the keypoints (:110-170); host only.  Upstream's loss term for term over
+    pb3d.camera_geometry.project, the same x0 order, bounds, method='L-BFGS-B' and prints.
+
+    `minimize` is the minimiser upstream imports from its optimisation library.  The package itself imports none (as powell_search,
+    it takes the caller's): after pb3d.install() the reference's own `minimize` is used; otherwise pass it."""
+    from .camera_geometry import project
+    if minimize is None:
+        minimize = _REF.get("minimize")
+    if minimize is None:
+        raise TypeError("optimize_camera_with_keypoints needs the L-BFGS-B minimiser: pass minimize=<optimize module>.minimize "
+                        "(pb3d.install() takes it from the reference package)")
+    H, W = image.shape[:2]
+    keys = list(image_keypoints_dict.keys())
+
+    def loss_fn(x):
+        cam_x, cam_y, cam_z, target_x, target_y, target_z, f, cx, cy = x
+        cam_pos = np.array([cam_x, cam_y, cam_z])
+        target = np.array([target_x, target_y, target_z])
+        total = 0
+        for k in keys:
+            proj_pt = project(voxel_keypoints_dict[k], cam_pos, target, f, cx, cy)
+            gt_pt = image_keypoints_dict[k]
+            error = np.abs(proj_pt - gt_pt) if loss_type == 'L1' else (proj_pt - gt_pt) ** 2
+            total += error.sum()
+        return total
+
+    x0 = [*init_params['cam_pos'], *init_params['target'], init_params['f'], init_params['cx'], init_params['cy']]
+    bounds = [(-W, 2 * W), (-H, 2 * H), (-2000, 100),       # cam_x, cam_y, cam_z
+              (-W, 2 * W), (-H, 2 * H), (-2000, 100),       # target_x, target_y, target_z
+              (10, 2000),                                   # f
+              (0, W), (0, H)]                               # cx, cy
+    result = minimize(loss_fn, x0, bounds=bounds, method='L-BFGS-B')
+    cam_x, cam_y, cam_z, target_x, target_y, target_z, f, cx, cy = result.x
+    final_params = {"cam_pos": np.array([cam_x, cam_y, cam_z]), "target": np.array([target_x, target_y, target_z]), "f": f, "cx": cx,
+                    "cy": cy}
+    print("\n📷 Optimized Camera Parameters:")
+    for k, v in final_params.items():
+        print(f"{k}: {v}")
+    print(f"📉 Final Reprojection Loss: {result.fun:.2f}")
+    return final_params
+
+
+OVERLAY_MODES = {"part_on_whole": 0, "whole_on_whole": 1, "whole_on_whole_color": 2}      # PB3D_OVERLAY_* of include/pb3d.h
+_SWEEP = 31                                                                               # colour bits of one grid sweep
+
+
+def _iou(inter, union):
+    return (inter / union) if union > 0 else 0.0
+
+
+def _outline_host(vis, gt, prj):
+    """outline_projection (:363-367) for a part that took the point path: the 4-neighbour cross, outside the image false"""
+    m = gt & prj
+    d = m.copy()
+    d[1:] |= m[:-1]; d[:-1] |= m[1:]; d[:, 1:] |= m[:, :-1]; d[:, :-1] |= m[:, 1:]
+    vis[d & ~m] = [255, 255, 0]
+    return vis
+
+
+def _overlays(voxel_grid, part_colors, image, cam_params, mode):
+    """[(part or None, title, vis, iou)] of projection_overlays"""
+    from . import device as dev
+    from . import eval_helpers_intra as ev
+    d_g, shape, owned = ev._grid(voxel_grid)
+    bufs = [d_g] if owned else []
+    try:
+        if shape[3] != 3:
+            raise ValueError("voxel_grid must be (A0,A1,A2,3) RGB")
+        img = _lib.as_u8(image, "image")
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError("image must be (H,W,3)")
+        H, W = img.shape[:2]
+        npix = H * W
+        # which parts can be a colour bit, and which of those have voxels (:382-385 skips the others)
+        cand, black = [], []
+        for part, color in part_colors.items():
+            c = np.asarray(color).reshape(-1)
+            if c.size != 3:
+                raise ValueError("a part colour is (R, G, B)")
+            if not (np.all((c >= 0) & (c <= 255)) and np.all(c == np.floor(c))):
+                continue                                    # never equals a uint8 voxel: no points upstream
+            (cand if np.any(c != 0) else black).append((part, np.ascontiguousarray(c.astype(np.uint8))))
+        live = []
+        d_present = dev.DeviceBuffer(8); bufs.append(d_present)
+        d_bm = dev.DeviceBuffer(_lib.PRESENCE_BYTES); bufs.append(d_bm)
+        for s in range(0, len(cand), _SWEEP):
+            chunk = cand[s:s + _SWEEP]
+            ev.presence_resident(d_g, shape, [c for _, c in chunk], d_present, out=d_bm)
+            present = int(d_present.download((1,), np.int64)[0])
+            live += [pc for k, pc in enumerate(chunk) if (present >> k) & 1]
+        # black parts select the empty voxels: the point path (its own projection; the mask is merged on the host)
+        host = {}
+        if black:
+            from .projection_utils import project_colored_voxels
+            from .voxel_utils import get_voxel_points_by_parts
+            grid_np = voxel_grid.numpy() if isinstance(voxel_grid, dev.DeviceGrid) else np.asarray(voxel_grid)
+            for part, c8 in black:
+                pts, col = get_voxel_points_by_parts(grid_np, {part: tuple(int(v) for v in c8)}, [part])
+                if pts.shape[0] == 0:
+                    continue
+                proj = project_colored_voxels(pts, col, cam_params["cam_pos"], cam_params["target"], cam_params["f"], cam_params["cx"],
+                                              cam_params["cy"], H, W)
+                host[part] = (c8, proj, np.all(proj == c8, axis=-1))
+        if mode == "part_on_part" and (live or host):
+            raise NameError("name 'proj_f' is not defined")             # upstream's :414, at the first part that has voxels
+        if mode not in OVERLAY_MODES:
+            return []
+        if len(live) > 8 * _SWEEP:
+            raise ValueError(f"at most {8 * _SWEEP} parts with voxels")
+        nplanes = (len(live) + _SWEEP - 1) // _SWEEP
+        d_bits = dev.DeviceBuffer(max(1, nplanes * npix) * 4); bufs.append(d_bits)
+        for s in range(nplanes):
+            hit_bits_resident(d_g, shape, [c for _, c in live[s * _SWEEP:(s + 1) * _SWEEP]], cam_params, H, W, out=d_bits.at(s * npix * 4))
+        d_img = dev.from_numpy(img) if npix else dev.DeviceBuffer(1)
+        bufs.append(d_img)
+        tab = np.ascontiguousarray(np.array([c for _, c in live], np.uint8).reshape(-1, 3))
+        bg = np.array(part_colors.get("background", (0, 0, 0)), dtype=np.uint8)
+        m = OVERLAY_MODES[mode]
+        nimg = len(live) if m == 0 else 1
+        ncnt = 2 * len(live) if m == 0 else 2
+        d_vis = dev.DeviceBuffer(max(1, nimg * npix * 3)); bufs.append(d_vis)
+        d_cnt = dev.DeviceBuffer(max(1, ncnt) * 8); bufs.append(d_cnt)
+        d_extra = None
+        if m == 1 and host:
+            extra = np.zeros((H, W), bool)
+            for _, _, prj in host.values():
+                extra |= prj
+            d_extra = dev.from_numpy(extra.view(np.uint8)); bufs.append(d_extra)
+        _lib.check(_lib.load().pb3d_overlay_compose_resident(_lib.ctx(), C.c_void_p(d_bits.ptr), nplanes, C.c_void_p(d_img.ptr), H, W, _lib.p_u8(tab),
+                                                        len(live), _lib.p_u8(bg), ev._ptr(d_extra), m, C.c_void_p(d_vis.ptr),
+                                                        C.c_void_p(d_cnt.ptr)))
+        vis = d_vis.download((nimg, H, W, 3)) if nimg else np.zeros((0, H, W, 3), np.uint8)
+        cnt = d_cnt.download((max(1, ncnt),), np.int64)
+        if m == 1:
+            return [(None, f"Combined Binary | IoU: {_iou(cnt[0], cnt[1]):.3f}", vis[0], _iou(cnt[0], cnt[1]))]
+        if m == 2:
+            return [(None, "Combined Color Projection Overlay", vis[0], None)]      # a black projection adds nothing to the sum
+        done = {part: (vis[j], _iou(cnt[2 * j], cnt[2 * j + 1])) for j, (part, _) in enumerate(live)}
+        for part, (c8, proj, prj) in host.items():
+            gt = np.all(img == c8, axis=-1)
+            v = _outline_host((0.7 * proj + 0.3 * img).astype(np.uint8), gt, prj)
+            done[part] = (v, _iou(np.logical_and(gt, prj).sum(), np.logical_or(gt, prj).sum()))
+        return [(part, f"{part} | IoU: {done[part][1]:.3f}", done[part][0], done[part][1]) for part in part_colors if part in done]
+    finally:
+        ev._free(*bufs)
+
+
+def projection_overlays(voxel_grid, part_colors, image, cam_params, mode):
+    """The images of visualize_voxel_projection_iou (:346-477) without matplotlib: [(title, vis, iou), ...] in upstream's order --
+    'part_on_whole': one per part that has voxels; 'whole_on_whole': the combined binary overlay; 'whole_on_whole_color': the combined
+    colour overlay (iou None: upstream computes none).  The grid (NumPy or DeviceGrid) is swept ONCE per 31 parts for the bits of
+    every part (pb3d_grid_hit_bits_resident) and the images are composed in one launch (pb3d_overlay_compose_resident).
+    'part_on_part' cannot run upstream (:414 names proj_f, which does not exist): NameError when any part has voxels, [] otherwise."""
+    return [(title, vis, iou) for _, title, vis, iou in _overlays(voxel_grid, part_colors, image, cam_params, mode)]
+
+
+def visualize_voxel_projection_iou(voxel_grid, part_colors, image, cam_params, mode='part_on_whole', save=False, save_root='visualisation'):
+    """Show (and save) the overlays of projection_overlays with upstream's figures, titles, prints and file names (:346-477)."""
+    import os
+
+    import matplotlib.pyplot as plt
+    if save:
+        save_dir = os.path.join(save_root, mode)
+        os.makedirs(save_dir, exist_ok=True)
+    items = _overlays(voxel_grid, part_colors, image, cam_params, mode)
+    if mode == "whole_on_whole":
+        print("Visualizing combined binary projection vs. binary ground-truth...")
+    if mode == "whole_on_whole_color":
+        print("Visualizing full-color projection overlay...")
+    names = {"whole_on_whole": "combined_binary_overlay.png", "whole_on_whole_color": "combined_color_overlay.png"}
+    for part, title, vis, _ in items:
+        plt.figure(figsize=(6, 6))
+        plt.imshow(vis)
+        plt.title(title)
+        plt.axis("off")
+        if save:
+            path = os.path.join(save_dir, names.get(mode, f"{part}_overlay.png"))
+            plt.savefig(path)
+            print(f"Saved {path}")
+        plt.show()

@@ -1,5 +1,5 @@
 """Device-resident timing of every op of the path (M1..M8 of SURVEY.md 8(d), plus the N1/N2 kernels of the notebook-1 chain) on
-synthetic inputs.  Development/measurement tool: python tools/opbench.py [--size 1024] [--shape WxHxD] [--ops M1,M3,...,N2]; one JSON
+synthetic inputs.  Development/measurement tool: python tools/opbench.py [--size 1024] [--shape WxHxD] [--ops M1,M3,...,N2,overlays]; one JSON
 line per op.  Pricing: `alg_B_per_voxel` is SURVEY 8(d)'s algorithmic figure for the sweeps that are EXECUTED (a folded 0-degree step
 moves nothing and is not priced); ops whose intermediates are not bytes (the bit-sliced chains) also carry `moved_B_per_voxel`, the
 bytes that cross the HBM by design, and their `frac_of_8TBs` is computed from THAT (never from bytes that are not moved)."""
@@ -256,6 +256,8 @@ def main():
         meshify(a.reps, res)
     if "DENS" in ops:
         density(a.reps, res, cpu_ref=not a.no_cpu_ref)
+    if "overlays" in ops:
+        overlays(a.reps, res)
     if d_col is not None:
         d_col.free()
     return res
@@ -597,6 +599,62 @@ def density(reps, res, cpu_ref=True):
         res.append(r)
     for b in (d_g, d_tp, d_tc):
         b.free()
+
+
+def overlays(reps, res):
+    """overlays, notebook 2's projection-IoU overlays (csrc/overlay.hip) on the stored Akbar grid and, when the fixture is present,
+    Itimad's deformed 512 x 381 x 512 grid, under the final front camera and the ten colours of PART_COLORS: the resident sweep
+    (pb3d_grid_hit_bits_resident) and one compose launch per mode (device events), projection_overlays through the NumPy API and with a
+    resident DeviceGrid, and beside them the existing projection_iou_by_part on the same grid and camera (host wall clock, median and
+    min / max of reps after one warm-up call: upload, presence, sweep, compose and downloads included)."""
+    from pb3d import camera_estimation as ce
+    from pb3d import eval_helpers_intra as ev
+    lib, L = pb3d._lib.load(), pb3d._lib
+    g = os.path.join(ROOT, "tests", "golden")
+    PC = pb3d.PART_COLORS
+    cols = list(PC.values())
+    tab = np.ascontiguousarray(np.array(cols, np.uint8))
+    bg = np.array(PC["background"], np.uint8)
+
+    def wall(key, fn):
+        fn()
+        t = []
+        for _ in range(max(3, reps)):
+            t0 = time.perf_counter()
+            fn()
+            t.append(time.perf_counter() - t0)
+        r[key] = round(1e3 * float(np.median(t)), 3)
+        r["wall_min_max_ms"][key] = [round(1e3 * min(t), 3), round(1e3 * max(t), 3)]
+
+    for mon, path in (("Akbar", "stored_Akbar_voxel_grid.npz"), ("Itimad deformed", "stored_Itimad_deformed_voxel_grid.npz")):
+        if not os.path.exists(os.path.join(g, path)):
+            continue
+        grid = ev.load_voxel_grid(os.path.join(g, path))
+        name = mon.split()[0]
+        cam = ev.load_camera_json(os.path.join(g, f"stored_{name}_camera_params_final.json"), "front")
+        image = np.ascontiguousarray(ev.resize_mask_to_voxel_grid(ev.load_mask(os.path.join(g, f"data_{name}_front_mask.png")), grid)[:, :, :3])
+        H, W = image.shape[:2]
+        d_g = dev.from_numpy(grid); d_img = dev.from_numpy(image)
+        d_bits = dev.DeviceBuffer(H * W * 4); d_vis = dev.DeviceBuffer(len(cols) * H * W * 3); d_cnt = dev.DeviceBuffer(len(cols) * 16)
+        sweep_ms = timeit(lambda: ce.hit_bits_resident(d_g, grid.shape, cols, cam, H, W, out=d_bits), reps)
+        compose = {}
+        for mode, m in ce.OVERLAY_MODES.items():
+            fn = lambda: L.check(lib.pb3d_overlay_compose_resident(L.ctx(), C.c_void_p(d_bits.ptr), 1, C.c_void_p(d_img.ptr), H, W, L.p_u8(tab), len(cols),
+                                                              L.p_u8(bg), None, m, C.c_void_p(d_vis.ptr), C.c_void_p(d_cnt.ptr)))
+            compose[mode] = round(timeit(fn, reps), 4)
+        resident = dev.DeviceGrid(d_g, grid.shape)
+        r = {"op": "overlays", "name": f"projection overlays, {mon} {'x'.join(map(str, grid.shape[:3]))}, final front camera", "image": [H, W],
+             "parts": len(cols), "sweep_resident_ms": round(sweep_ms, 4), "compose_resident_ms": compose, "wall_min_max_ms": {}}
+        for mode in ce.OVERLAY_MODES:
+            wall(f"{mode}_numpy_api_ms", lambda: ce.projection_overlays(grid, PC, image, cam, mode))
+            wall(f"{mode}_device_grid_ms", lambda: ce.projection_overlays(resident, PC, image, cam, mode))
+        wall("projection_iou_by_part_ms", lambda: ce.projection_iou_by_part(grid, PC, image, cam))
+        for mode in ("part_on_whole", "whole_on_whole"):          # the two modes that return what projection_iou_by_part returns, plus images
+            r[f"per_part_over_{mode}"] = round(r["projection_iou_by_part_ms"] / r[f"{mode}_numpy_api_ms"], 2)
+        print(json.dumps(r), flush=True)
+        res.append(r)
+        for b in (d_g, d_img, d_bits, d_vis, d_cnt):
+            b.free()
 
 
 if __name__ == "__main__":
