@@ -380,6 +380,35 @@ int pb3d_overlay_compose_resident(pb3d_ctx* ctx, const uint32_t* d_bits, int npl
                              const uint8_t* colors, int nparts, const uint8_t bg[3], const uint8_t* d_extra_prj, int mode, uint8_t* d_vis,
                              int64_t* d_counts);
 
+/* ---- perspective carve: silhouette carving of a resident grid by pinhole views -------------------------------------------------
+ * The reference carves by orthographic views only; this applies the pinhole arithmetic of project_colored_voxels (reference
+ * utils/projection_utils.py:5-23) to the cameras notebook 2 fits.  Voxel (a0,a1,a2) of the uint8 (A0,A1,A2,C) grid, C = 3 (RGB) or 1
+ * (labels), is the float32 point (x = a2, y = a1, z = a0), occupied where any channel is non-zero.  A voxel is SUBJECT when it is
+ * occupied and, for ncolors > 0, its colour / label is one of the ncolors <= 31 non-zero `colors`; every other voxel is copied.
+ * For a subject voxel and a view the pixel (u, v) is exactly the one project_colored_voxels paints: (p - cam) @ R.T in the float
+ * width prec[0] names, Z < 1e-8 clamped to 1e-8, u = (X/Z)*f + cx, v = -(Y/Z)*f + cy with the per-stage widths prec[1..3], rint
+ * (half to even), then 0 <= u < Wimg, 0 <= v < Himg (R, cam, prec as for pb3d_project_dev: the host's look_at_rotation and the
+ * NumPy promotion flags of float32 points).  The view REJECTS the voxel when the pixel is inside the image and the mask is clear
+ * there; a pixel outside the image (NaN included) rejects it too, or accepts it with outside_keep != 0.  d_maskbits: Himg rows of
+ * (Wimg + 31) / 32 uint32 words on the device, pixel u of a row is bit u & 31 of word u >> 5.
+ * Views apply in order: the first view that rejects a voxel zeroes all its channels and later views are not evaluated for it;
+ * d_removed[k] (nviews int64 on the device, zeroed by the entry, may be NULL) counts the voxels view k zeroed.  Hence carving by
+ * [a, b] is carving by [a], then its result by [b], with the counts side by side, and carving twice is carving once.
+ * d_out != d_grid: every voxel is written (the buffers may not overlap); d_out == d_grid: in place, only zeroed voxels are written.
+ * Any base address: rows of whole dwords on 4-byte aligned buffers move as dwords, everything else byte by byte.  Eight views go
+ * into one launch; further views carve d_out in place.  nviews = 0 copies.  Axes up to 2^24.  Refused before any device work (and
+ * before the context is looked at): C other than 1 or 3, a negative shape, a null grid of a non-empty shape, ncolors > 31 or a black
+ * colour, nviews < 0 or a null table, Himg or Wimg <= 0, a null mask, prec flags other than 0 / 1 or narrowing. */
+typedef struct pb3d_carve_view {
+    double R[9], cam[3], f, cx, cy;
+    int prec[4];
+    int Himg, Wimg;
+    const uint32_t* d_maskbits;
+} pb3d_carve_view;
+int pb3d_perspective_carve_resident(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64_t A1, int64_t A2, int C, const uint8_t* colors,
+                                    int ncolors, const pb3d_carve_view* views, int nviews, int outside_keep, uint8_t* d_out,
+                                    int64_t* d_removed);
+
 /* ---- compute_partwise_iou, reference utils/camera_estimation.py:770-787 -------------------
  * per colour k: inter[k] = #(a==c & b==c), uni[k] = #(a==c | b==c) over npix RGB pixels. */
 int pb3d_partwise_iou_dev(pb3d_ctx* ctx, const uint8_t* d_a, const uint8_t* d_b, int64_t npix,

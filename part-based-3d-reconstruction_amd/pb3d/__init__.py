@@ -5,7 +5,7 @@ utils.projection_utils, utils.camera_geometry, utils.camera_estimation.compute_p
 minaret extraction, the notebook-4 and inter-method evaluations, utils.config) on top of libpb3d.so.  `install()` rebinds those names inside an imported
 reference `utils` package so notebooks 1-3 run unchanged.
 """
-from . import _hostmem, _lib, device, dist, formats, labels  # noqa: F401
+from . import _hostmem, _lib, device, dist, formats, labels, perspective  # noqa: F401
 from .formats import load_camera_params, load_voxel_grid, save_camera_params, save_voxel_grid  # noqa: F401
 from .labels import (Palette, extrude_from_surface_labels, get_voxel_points_by_parts_labels, global_carve_labels, label_to_rgb,  # noqa: F401
                      left_right_guided_carve_labels, part_carve_labels, partwise_carve_labels, recolor_backward_components_labels, rgb_to_label,
@@ -32,6 +32,7 @@ from .deformation_estimation import (build_deformed_grid, deform_coords, deform_
                                      evaluate_part_deform_batch)
 from .config import INTERIOR_PARTS, MAX_DIM, PART_COLORS, PART_COLORS_NP  # noqa: F401
 from .projection_utils import project_colored_voxels  # noqa: F401
+from .perspective import pack_mask_bits, perspective_carve, perspective_carve_resident  # noqa: F401
 from .voxel_carving_utils import (apply_colored_mask_to_voxel_grid, carve_voxel_grid_with_masks, extrude_from_surface,  # noqa: F401
                                   global_carve, left_right_guided_carve, part_carve, partwise_carve, process_voxel_grid,
                                   recolor_backward_components)

@@ -1,0 +1,140 @@
+"""Perspective carve: silhouette carving of a voxel grid by pinhole views (csrc/pcarve.hip).
+
+The reference carves by orthographic views only.  With the cameras notebook 2 fits for the front and the aerial image, the next
+step is to carve the coloured grid by those views: a voxel goes when it projects onto background in some view.  The pixel of a
+voxel is exactly the one project_colored_voxels (reference utils/projection_utils.py:5-23) paints it on; include/pb3d.h states the
+semantics to the bit."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .device import _ptr
+from .eval_helpers_intra import _cam, _colour_table, _free, _grid
+
+__all__ = ["perspective_carve", "perspective_carve_resident", "pack_mask_bits"]
+
+MAX_COLOURS = 31
+
+
+def pack_mask_bits(mask):
+    """(H, (W + 31) // 32) uint32 bit image of an (H, W) mask of any dtype or an (H, W, 3) one: pixel u of a row is bit u & 31 of
+    word u >> 5, set where any value of the pixel is non-zero.  Host NumPy."""
+    m = np.asarray(mask)
+    if m.ndim == 3 and m.shape[2] == 3:
+        m = np.any(m != 0, axis=2)
+    elif m.ndim == 2:
+        m = m != 0
+    else:
+        raise ValueError(f"a mask is (H, W) or (H, W, 3), got shape {m.shape}")
+    H, W = m.shape
+    if H == 0 or W == 0:
+        raise ValueError(f"a mask has at least one pixel, got shape {m.shape}")
+    padded = np.zeros((H, (W + 31) // 32 * 32), np.uint8)
+    padded[:, :W] = m
+    return np.ascontiguousarray(np.packbits(padded, axis=1, bitorder="little")).view("<u4")
+
+
+class _DeviceMaskBits:
+    """pack_mask_bits of a mask on the device.  perspective_carve_resident makes one per host mask and call; a caller that carves by
+    the same masks again and again (tools/pcarvebench.py) makes them once and passes them in place of the masks."""
+
+    def __init__(self, mask):
+        from . import device as dev
+        bits = pack_mask_bits(mask)
+        self.H, self.W = int(bits.shape[0]), int(np.asarray(mask).shape[1])
+        self.buf = dev.from_numpy_async(bits)
+
+    def free(self):
+        self.buf.free()
+
+
+def _subject_table(colors, Cc):
+    """(uint8 table, ncolors); None selects every occupied voxel"""
+    if colors is None:
+        return np.zeros((0, Cc), np.uint8), 0
+    tab = _colour_table(colors, Cc)
+    if len(tab) == 0:
+        raise ValueError("colors is None (every occupied voxel) or a list of colours, got an empty list")
+    if len(tab) > MAX_COLOURS:
+        raise ValueError(f"at most {MAX_COLOURS} subject colours, got {len(tab)}")
+    if not tab.any(axis=1).all():
+        raise ValueError("a subject colour is black / label 0 (the empty voxel)")
+    return tab, len(tab)
+
+
+def _outside(outside):
+    if outside not in ("carve", "keep"):
+        raise ValueError(f"outside is 'carve' or 'keep', got {outside!r}")
+    return int(outside == "keep")
+
+
+def perspective_carve_resident(d_grid, shape, views, colors=None, outside="carve", out=None, d_removed=None):
+    """pb3d_perspective_carve_resident, queued on the context's stream: nothing is downloaded and the host does not wait.
+    d_grid: DeviceBuffer (or a pointer into one, DeviceBuffer.at) of the (A0, A1, A2, C) uint8 grid, shape = (A0, A1, A2, C) with
+    C = 1 or 3.  views: (mask, cam) pairs, mask a host array or a _DeviceMaskBits, cam a dict with cam_pos, target, f, cx, cy.
+    out: DeviceBuffer of the result (it may not overlap the grid), None = in place.  d_removed: DeviceBuffer of len(views) int64 (or
+    a pointer into one), None = no counts.  Returns `out` (d_grid when in place)."""
+    A0, A1, A2, Cc = (int(v) for v in shape)
+    keep = _outside(outside)
+    tab, ncol = _subject_table(colors, Cc)
+    views = list(views)
+    arr = (_lib.CarveView * max(1, len(views)))()
+    owned = []
+    try:
+        for k, (mask, cam) in enumerate(views):
+            mb = mask if isinstance(mask, _DeviceMaskBits) else _DeviceMaskBits(mask)
+            if mb is not mask:
+                owned.append(mb)
+            R, cp, prec = _cam(cam, np.float32)
+            v = arr[k]
+            v.R[:] = R.reshape(9).tolist(); v.cam[:] = cp.reshape(3).tolist()
+            v.f, v.cx, v.cy = float(cam["f"]), float(cam["cx"]), float(cam["cy"])
+            v.prec[:] = list(prec)
+            v.Himg, v.Wimg, v.d_maskbits = mb.H, mb.W, mb.buf.ptr
+        dst = d_grid if out is None else out
+        _lib.check(_lib.load().pb3d_perspective_carve_resident(_lib.ctx(), _ptr(d_grid), A0, A1, A2, Cc, _lib.p_u8(tab) if ncol else None, ncol,
+                                                               C.cast(arr, C.c_void_p), len(views), keep, _ptr(dst), _ptr(d_removed)))
+        return dst
+    finally:
+        for mb in owned:        # the context's pool hands a freed block out again only behind this stream's work
+            mb.free()
+
+
+def perspective_carve(voxel_grid, views, colors=None, outside="carve", return_counts=False):
+    """Carve a grid by perspective views: a new grid in which every subject voxel that some view rejects is zero.
+
+    voxel_grid: uint8 (A0,A1,A2,3) RGB or (A0,A1,A2) labels, a NumPy array or a DeviceGrid (then the result is a new DeviceGrid).
+    Voxel (a0,a1,a2) is the float32 point (x = a2, y = a1, z = a0), occupied where any channel is non-zero.
+    views: a sequence of (mask, cam); mask (H,W) of any dtype or (H,W,3), set where any value is non-zero, each view with its own
+    size; cam a dict with cam_pos, target, f, cx, cy (the camera JSONs of notebook 2 through load_camera_json).
+    colors: None, or at most 31 non-black colours / non-zero labels: only voxels of these are subject, the others are copied.
+    A view rejects a subject voxel whose pixel (project_colored_voxels' arithmetic, to the bit) is inside the image on a clear
+    mask pixel; a pixel outside the image rejects with outside="carve" and accepts with outside="keep".  Views apply in order and
+    the first rejection zeroes the voxel.  return_counts=True also returns the int64 (K,) array of voxels zeroed per view."""
+    from . import device as dev
+    views = list(views)
+    _outside(outside)       # every argument is checked before anything is uploaded
+    for mask, _ in views:
+        if not isinstance(mask, _DeviceMaskBits):
+            m = np.asarray(mask)
+            if not (m.ndim == 2 or (m.ndim == 3 and m.shape[2] == 3)) or 0 in m.shape[:2]:
+                raise ValueError(f"a mask is a non-empty (H, W) or (H, W, 3) array, got shape {m.shape}")
+    grid_shape = tuple(voxel_grid.shape if isinstance(voxel_grid, dev.DeviceGrid) else np.shape(voxel_grid))
+    if len(grid_shape) not in (3, 4) or (len(grid_shape) == 4 and grid_shape[3] != 3):
+        raise ValueError("voxel_grid must be (A0,A1,A2,3) RGB or (A0,A1,A2) labels")
+    _subject_table(colors, 3 if len(grid_shape) == 4 else 1)
+    d_g, shape, owned = _grid(voxel_grid)
+    nbytes = int(np.prod(shape, dtype=np.int64))
+    d_out = dev.DeviceBuffer(max(1, nbytes))
+    d_rem = dev.DeviceBuffer(8 * max(1, len(views))) if return_counts else None
+    try:
+        perspective_carve_resident(d_g, shape, views, colors, outside, out=d_out, d_removed=d_rem if len(views) else None)
+        counts = d_rem.download((len(views),), np.int64) if return_counts else None
+        if isinstance(voxel_grid, dev.DeviceGrid):
+            res, d_out = dev.DeviceGrid(d_out, grid_shape), None
+        else:
+            res = d_out.download(grid_shape)
+    finally:
+        _free(d_out, d_rem, d_g if owned else None)
+    return (res, counts) if return_counts else res
