@@ -409,6 +409,39 @@ int pb3d_perspective_carve_resident(pb3d_ctx* ctx, const uint8_t* d_grid, int64_
                                     int ncolors, const pb3d_carve_view* views, int nviews, int outside_keep, uint8_t* d_out,
                                     int64_t* d_removed);
 
+/* ---- perspective paint: the visible voxels of a resident grid take the colours of the pixels the views see them at -------------
+ * The perspective counterpart of apply_colored_mask_to_voxel_grid, on the grid conventions of the perspective carve above: voxel
+ * (a0,a1,a2) of the uint8 (A0,A1,A2,C) grid is the float32 point (x = a2, y = a1, z = a0), occupied where any channel is non-zero,
+ * SUBJECT when it is occupied and, for ncolors > 0, of one of the ncolors <= 31 non-zero `colors`; every other voxel is copied.
+ * View k holds a camera (R, cam, f, cx, cy, prec as for pb3d_grid_visible_bits_dev), an image d_image of Himg x Wimg x C bytes (RGB
+ * for C = 3, labels for C = 1; any base address) and a z-buffer d_zbuf of Himg x Wimg float32, normally pb3d_grid_depth_buffer_dev
+ * of the grid BEFORE painting under the same camera (compute_global_depth_buffer, reference utils/eval_helpers_intra.py:134-160).
+ * View k SEES a subject voxel when the arithmetic of that z-buffer accepts its point (Z > 1e-6 and the rounded pixel (u, v) inside
+ * the image) and |Z - d_zbuf[v,u]| < eps as project_part_visible (:168-190) evaluates it: in float64 for a float64 camera, else on
+ * the float32 difference, compared in float32 when eps_f32 != 0 (eps a weak Python float) and in float64 otherwise.
+ * View k PAINTS the voxel when it sees it and d_image[v,u] is neither black / label 0 nor one of the nskip <= 8 `skip` colours /
+ * labels (nskip * C bytes; black never paints whether listed or not: it would delete the voxel).
+ * The views are tried in order; the first that paints a voxel decides its colour, a voxel no view paints keeps its own.
+ * d_painted[k] (nviews int64 on the device, zeroed by the entry, may be NULL) counts the voxels whose colour view k decided, whether
+ * or not the value changed.  Painting never changes occupancy, so z-buffers made from the input grid do not depend on the order of
+ * the views and the result is the same in place and out of place.
+ * d_out != d_grid: every voxel is written (the buffers may not overlap); d_out == d_grid: in place, only decided voxels are written.
+ * Any base address: rows of whole dwords on 4-byte aligned buffers move as dwords, everything else byte by byte.  nviews = 0 copies.
+ * Axes up to 2^24.  Refused before any device work (and before the context is looked at): C other than 1 or 3, a negative shape, a
+ * null grid of a non-empty shape, ncolors > 31 or a black colour, nviews outside 0..8 or a null table, nskip outside 0..8 or a null
+ * table, eps_f32 other than 0 / 1, Himg or Wimg <= 0, a null image or z-buffer, prec flags other than 0 / 1 or narrowing, a null
+ * output, an output that overlaps the grid in part. */
+typedef struct pb3d_paint_view {
+    double R[9], cam[3], f, cx, cy;
+    int prec[4];
+    int Himg, Wimg;
+    const uint8_t* d_image;
+    const float* d_zbuf;
+} pb3d_paint_view;
+int pb3d_perspective_paint_resident(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64_t A1, int64_t A2, int C, const uint8_t* colors,
+                                    int ncolors, const pb3d_paint_view* views, int nviews, const uint8_t* skip, int nskip, double eps,
+                                    int eps_f32, uint8_t* d_out, int64_t* d_painted);
+
 /* ---- compute_partwise_iou, reference utils/camera_estimation.py:770-787 -------------------
  * per colour k: inter[k] = #(a==c & b==c), uni[k] = #(a==c | b==c) over npix RGB pixels. */
 int pb3d_partwise_iou_dev(pb3d_ctx* ctx, const uint8_t* d_a, const uint8_t* d_b, int64_t npix,

@@ -32,7 +32,8 @@ from .deformation_estimation import (build_deformed_grid, deform_coords, deform_
                                      evaluate_part_deform_batch)
 from .config import INTERIOR_PARTS, MAX_DIM, PART_COLORS, PART_COLORS_NP  # noqa: F401
 from .projection_utils import project_colored_voxels  # noqa: F401
-from .perspective import pack_mask_bits, perspective_carve, perspective_carve_resident  # noqa: F401
+from .perspective import (pack_mask_bits, perspective_carve, perspective_carve_resident, perspective_paint,  # noqa: F401
+                          perspective_paint_resident)
 from .voxel_carving_utils import (apply_colored_mask_to_voxel_grid, carve_voxel_grid_with_masks, extrude_from_surface,  # noqa: F401
                                   global_carve, left_right_guided_carve, part_carve, partwise_carve, process_voxel_grid,
                                   recolor_backward_components)

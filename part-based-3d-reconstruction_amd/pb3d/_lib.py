@@ -153,6 +153,8 @@ _SIGNATURES = {
                                C.c_int, vp],
     "pb3d_overlay_compose_resident": [vp, vp, C.c_int, vp, C.c_int, C.c_int, u8p, C.c_int, u8p, vp, C.c_int, vp, vp],
     "pb3d_perspective_carve_resident": [vp, vp, i64, i64, i64, C.c_int, u8p, C.c_int, C.c_void_p, C.c_int, C.c_int, vp, vp],
+    "pb3d_perspective_paint_resident": [vp, vp, i64, i64, i64, C.c_int, u8p, C.c_int, C.c_void_p, C.c_int, u8p, C.c_int, C.c_double, C.c_int,
+                                        vp, vp],
 }
 class IouRow(C.Structure):
     """pb3d_iou_row (include/pb3d.h)"""
@@ -163,6 +165,12 @@ class CarveView(C.Structure):
     """pb3d_carve_view (include/pb3d.h)"""
     _fields_ = [("R", C.c_double * 9), ("cam", C.c_double * 3), ("f", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
                 ("prec", C.c_int * 4), ("Himg", C.c_int), ("Wimg", C.c_int), ("d_maskbits", vp)]
+
+
+class PaintView(C.Structure):
+    """pb3d_paint_view (include/pb3d.h)"""
+    _fields_ = [("R", C.c_double * 9), ("cam", C.c_double * 3), ("f", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("prec", C.c_int * 4), ("Himg", C.c_int), ("Wimg", C.c_int), ("d_image", vp), ("d_zbuf", vp)]
 
 
 PRESENCE_BYTES = 1 << 21    # PB3D_PRESENCE_BYTES: one bit per 24-bit colour

@@ -1,20 +1,26 @@
-"""Perspective carve: silhouette carving of a voxel grid by pinhole views (csrc/pcarve.hip).
+"""Perspective carve and paint: silhouette carving of a voxel grid by pinhole views (csrc/pcarve.hip), and the colours of the views'
+images on the voxels they see (csrc/ppaint.hip).
 
 The reference carves by orthographic views only.  With the cameras notebook 2 fits for the front and the aerial image, the next
 step is to carve the coloured grid by those views: a voxel goes when it projects onto background in some view.  The pixel of a
 voxel is exactly the one project_colored_voxels (reference utils/projection_utils.py:5-23) paints it on; include/pb3d.h states the
-semantics to the bit."""
+semantics to the bit.
+
+perspective_paint is the second half, as apply_colored_mask_to_voxel_grid is for the orthographic carve: a voxel a view sees (the
+reference's z-buffer test, utils/eval_helpers_intra.py:134-190) takes the colour of the pixel it is seen at."""
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
 from .device import _ptr
-from .eval_helpers_intra import _cam, _colour_table, _free, _grid
+from .eval_helpers_intra import _cam, _colour_table, _eps_f32, _free, _grid, depth_buffer_resident
 
-__all__ = ["perspective_carve", "perspective_carve_resident", "pack_mask_bits"]
+__all__ = ["perspective_carve", "perspective_carve_resident", "pack_mask_bits", "perspective_paint", "perspective_paint_resident"]
 
 MAX_COLOURS = 31
+MAX_PAINT_VIEWS = 8
+MAX_SKIP = 8
 
 
 def pack_mask_bits(mask):
@@ -137,4 +143,148 @@ def perspective_carve(voxel_grid, views, colors=None, outside="carve", return_co
             res = d_out.download(grid_shape)
     finally:
         _free(d_out, d_rem, d_g if owned else None)
+    return (res, counts) if return_counts else res
+
+
+# ---- perspective paint -------------------------------------------------------------------------------------------------------------
+class _DeviceImage:
+    """A view's (H, W, 3) RGB or (H, W) label image on the device.  perspective_paint_resident makes one per host image and call; a
+    caller whose image is resident already wraps it: _DeviceImage(DeviceBuffer or pointer into one, H, W)."""
+
+    def __init__(self, image, H=None, W=None):
+        from . import device as dev
+        if H is None:
+            img = _lib.as_u8(image, "a view's image")
+            self.H, self.W = int(img.shape[0]), int(img.shape[1])
+            self.buf, self.owned = dev.from_numpy_async(img), True
+        else:
+            self.H, self.W, self.buf, self.owned = int(H), int(W), image, False
+
+    def free(self):
+        if self.owned:
+            self.buf.free()
+
+
+def _image_shape(image, Cc):
+    """(H, W) of a view's image, checked against the grid's channels"""
+    if isinstance(image, _DeviceImage):
+        H, W = image.H, image.W
+    else:
+        m = _lib.as_u8(image, "a view's image")
+        if m.ndim != (3 if Cc == 3 else 2) or (Cc == 3 and m.shape[2] != 3):
+            raise ValueError(f"the image of a view is (H, W, 3) for an RGB grid and (H, W) for a label grid, got shape {m.shape}")
+        H, W = m.shape[:2]
+    if H <= 0 or W <= 0:
+        raise ValueError(f"the image of a view has at least one pixel, got {H} x {W}")
+    return int(H), int(W)
+
+
+def _skip_table(skip, Cc):
+    tab = _colour_table(skip, Cc)
+    if len(tab) > MAX_SKIP:
+        raise ValueError(f"at most {MAX_SKIP} skip colours, got {len(tab)}")
+    return tab
+
+
+def _paint_args(Cc, views, colors, skip):
+    """the host-only checks of both entries: (views as a list, [(H, W)], subject table, ncolors, skip table)"""
+    views = list(views)
+    if len(views) > MAX_PAINT_VIEWS:
+        raise ValueError(f"at most {MAX_PAINT_VIEWS} views, got {len(views)}")
+    sizes = [_image_shape(image, Cc) for image, _ in views]
+    tab, ncol = _subject_table(colors, Cc)
+    return views, sizes, tab, ncol, _skip_table(skip, Cc)
+
+
+def perspective_paint_resident(d_grid, shape, views, d_zbufs, colors=None, skip=(), eps=1e-3, out=None, d_painted=None):
+    """pb3d_perspective_paint_resident, queued on the context's stream: nothing is downloaded and the host does not wait.
+    d_grid: DeviceBuffer (or a pointer into one, DeviceBuffer.at) of the (A0, A1, A2, C) uint8 grid, shape = (A0, A1, A2, C) with
+    C = 1 or 3.  views: (image, cam) pairs, image a host array or a _DeviceImage, cam a dict with cam_pos, target, f, cx, cy.
+    d_zbufs: per view the DeviceBuffer (or pointer) of its float32 (H, W) z-buffer, normally depth_buffer_resident of the grid before
+    painting.  out: DeviceBuffer of the result (it may not overlap the grid in part), None = in place.  d_painted: DeviceBuffer of
+    len(views) int64 (or a pointer into one), None = no counts.  Returns `out` (d_grid when in place)."""
+    A0, A1, A2, Cc = (int(v) for v in shape)
+    views, sizes, tab, ncol, sk = _paint_args(Cc, views, colors, skip)
+    d_zbufs = list(d_zbufs)
+    if len(d_zbufs) != len(views):
+        raise ValueError(f"{len(views)} views but {len(d_zbufs)} z-buffers")
+    cams = [_cam(cam, np.float32) for _, cam in views]
+    eps_f32 = max([_eps_f32(prec, eps) for _, _, prec in cams], default=0)     # read by float32 cameras only
+    arr = (_lib.PaintView * max(1, len(views)))()
+    owned = []
+    try:
+        for k, ((image, cam), (H, W), (R, cp, prec)) in enumerate(zip(views, sizes, cams)):
+            im = image if isinstance(image, _DeviceImage) else _DeviceImage(image)
+            if im is not image:
+                owned.append(im)
+            v = arr[k]
+            v.R[:] = R.reshape(9).tolist(); v.cam[:] = cp.reshape(3).tolist()
+            v.f, v.cx, v.cy = float(cam["f"]), float(cam["cx"]), float(cam["cy"])
+            v.prec[:] = list(prec)
+            v.Himg, v.Wimg, v.d_image, v.d_zbuf = H, W, _ptr(im.buf), _ptr(d_zbufs[k])
+        dst = d_grid if out is None else out
+        _lib.check(_lib.load().pb3d_perspective_paint_resident(_lib.ctx(), _ptr(d_grid), A0, A1, A2, Cc, _lib.p_u8(tab) if ncol else None, ncol,
+                                                               C.cast(arr, C.c_void_p), len(views), _lib.p_u8(sk) if len(sk) else None, len(sk),
+                                                               float(eps), eps_f32, _ptr(dst), _ptr(d_painted)))
+        return dst
+    finally:
+        for im in owned:        # the context's pool hands a freed block out again only behind this stream's work
+            im.free()
+
+
+def perspective_paint(voxel_grid, views, colors=None, skip=(), eps=1e-3, zbufs=None, return_counts=False):
+    """Paint a grid by perspective views: a new grid in which every subject voxel some view paints has that view's pixel colour.
+    include/pb3d.h (pb3d_perspective_paint_resident) states the semantics.
+
+    voxel_grid: uint8 (A0,A1,A2,3) RGB or (A0,A1,A2) labels, a NumPy array or a DeviceGrid (then the result is a new DeviceGrid).
+    Voxel (a0,a1,a2) is the float32 point (x = a2, y = a1, z = a0), occupied where any channel is non-zero.
+    views: a sequence of at most 8 (image, cam); image uint8 (H,W,3) for an RGB grid, (H,W) for a label grid, each view with its own
+    size; cam a dict with cam_pos, target, f, cx, cy whose dtypes decide the float widths as they do for grid_visible_bits.
+    colors: None, or at most 31 non-black colours / non-zero labels: only voxels of these are subject, the others are copied.
+    skip: at most 8 image colours / labels that never paint (the masks' background); black / label 0 never paints.
+    zbufs: None, or per view a float32 (H,W) array or a DeviceBuffer; None = the z-buffer of the input grid under the view's camera.
+    A view sees a subject voxel whose pixel is inside the image (Z > 1e-6) with |Z - zbuf[v,u]| < eps, and paints it when the pixel is
+    neither black nor in skip.  Views are tried in order, the first that paints a voxel decides its colour, a voxel no view paints
+    keeps its own.  return_counts=True also returns the int64 (K,) array of voxels decided per view."""
+    from . import device as dev
+    grid_shape = tuple(voxel_grid.shape if isinstance(voxel_grid, dev.DeviceGrid) else np.shape(voxel_grid))
+    if len(grid_shape) not in (3, 4) or (len(grid_shape) == 4 and grid_shape[3] != 3):
+        raise ValueError("voxel_grid must be (A0,A1,A2,3) RGB or (A0,A1,A2) labels")
+    views, sizes, _, _, _ = _paint_args(3 if len(grid_shape) == 4 else 1, views, colors, skip)      # every argument is checked before anything is uploaded
+    for _, cam in views:
+        _cam(cam, np.float32)
+    host_z = [None] * len(views)
+    if zbufs is not None:
+        zbufs = list(zbufs)
+        if len(zbufs) != len(views):
+            raise ValueError(f"{len(views)} views but {len(zbufs)} z-buffers")
+        for k, (zb, hw) in enumerate(zip(zbufs, sizes)):
+            if not isinstance(zb, dev.DeviceBuffer):
+                host_z[k] = np.ascontiguousarray(zb, np.float32)
+                if host_z[k].shape != hw:
+                    raise ValueError(f"the z-buffer of view {k} is {host_z[k].shape}, its image {hw}")
+            elif zb.nbytes != 4 * hw[0] * hw[1]:
+                raise ValueError(f"the z-buffer of view {k} holds {zb.nbytes} bytes, its {hw[0]} x {hw[1]} image needs {4 * hw[0] * hw[1]}")
+    d_g, shape, owned = _grid(voxel_grid)
+    nbytes = int(np.prod(shape, dtype=np.int64))
+    d_out = d_cnt = None
+    mine = []
+    try:
+        d_out = dev.DeviceBuffer(max(1, nbytes))
+        d_cnt = dev.DeviceBuffer(8 * max(1, len(views))) if return_counts else None
+        d_z = []
+        for k, ((_, cam), (H, W)) in enumerate(zip(views, sizes)):
+            if zbufs is None:
+                mine.append(depth_buffer_resident(d_g, shape, cam, H, W))
+            elif host_z[k] is not None:
+                mine.append(dev.from_numpy_async(host_z[k]))
+            d_z.append(mine[-1] if zbufs is None or host_z[k] is not None else zbufs[k])
+        perspective_paint_resident(d_g, shape, views, d_z, colors, skip, eps, out=d_out, d_painted=d_cnt if len(views) else None)
+        counts = d_cnt.download((len(views),), np.int64) if return_counts else None
+        if isinstance(voxel_grid, dev.DeviceGrid):
+            res, d_out = dev.DeviceGrid(d_out, grid_shape), None
+        else:
+            res = d_out.download(grid_shape)
+    finally:
+        _free(d_out, d_cnt, d_g if owned else None, *mine)
     return (res, counts) if return_counts else res
