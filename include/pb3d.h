@@ -350,6 +350,35 @@ int pb3d_surface_metrics_dev(pb3d_ctx* ctx, const void* d_verts, const void* d_n
 int pb3d_density_grid_resident(pb3d_ctx* ctx, const void* d_pts, int pts_f64, int64_t n, int grid_size, const double* weights, int radius,
                                float* d_out);
 
+/* ---- rigid ICP of two point clouds: the registration the inter-method metrics assume ("Align all reconstructions", reference
+ * results/4.Inter-method_3D/README.md; its utils/preprocess_helpers.py is not shipped, so the arithmetic below is the specification) --
+ * Point lists as for the metrics above: (n, 3) rows of float32 (*_f64 = 0) or float64 (1), at most 2^31 - 1 points, finite.  All
+ * arithmetic is float64, every product and sum rounded on its own (no FMA); float32 is widened first.
+ * transform_points: d_out (n x 3 float64) row i = T s_i for the row-major 3 x 4 T = [R | t]:
+ *     p_h = ((T[h][0] * s.x + T[h][1] * s.y) + T[h][2] * s.z) + T[h][3].          n = 0 is fine (nothing written).
+ * icp_index: bins the nt >= 1 target points into a cell index the context keeps (the index of knn above: exact box, cells, cell-sorted
+ *   coordinates and ids) and, if bounds is not NULL, writes the target's exact box there (min 3, max 3; host memory).  One host wait.
+ *   The index belongs to (d_tgt, nt, tgt_f64) and stays until the next icp_index call on the context; other calls do not disturb it.
+ * icp_step: one point-to-point step against the index, enqueued without a host wait.  For every source point s
+ *     p = T s (transform_points);   j = the target position with the smallest (d2, j), d2 = (dx*dx + dy*dy) + dz*dz, d = p - q_j
+ *         (exactly knn with k = 1 on the transformed points: the lowest position wins a tie);
+ *     the pair is USED when max_dist2 < 0 (no gate) or d2 <= max_dist2 (the caller forms max_dist * max_dist once);
+ *     a used pair contributes 1 to the count and the 16 terms  P = p - cp (3),  Q = q_j - cq (3),  P_a * Q_b for a, b row-major (9),
+ *     d2 (1);  an unused pair contributes 0 and +0.0 sixteen times.
+ *   d_out (17 x 8 bytes on the device): the int64 count, then the 16 float64 sums.  Summation order, a function of (ns, i) alone:
+ *     point i is lane i % 64 of wave (i / 64) % 4 of workgroup i / 256 (lanes past ns hold +0.0).  A wave adds by the butterfly
+ *     v += v[lane ^ off] for off = 32, 16, 8, 4, 2, 1; a workgroup's sum is ((w0 + w1) + w2) + w3 of its wave sums: one partial row
+ *     per workgroup.  Then one 256-thread workgroup: thread t starts from +0.0 and adds partial rows t, t + 256, t + 512, ... in
+ *     ascending order, and the 256 values are reduced the same way.  No floating-point atomics; two calls on the same input give
+ *     the same bytes.
+ *   ns = 0: count 0 and sixteen +0.0 (no index needed).  nt = 0 with ns > 0 is PB3D_EINVAL.  A step whose (d_tgt, nt, tgt_f64) is not
+ *   what the context's index was built for, or that finds no index, is PB3D_EINVAL: it never rebuilds silently.  A transformed point
+ *   that is not finite has no nearest point and is not used. */
+int pb3d_transform_points_resident(pb3d_ctx* ctx, const void* d_src, int src_f64, int64_t n, const double T[12], double* d_out);
+int pb3d_icp_index_resident(pb3d_ctx* ctx, const void* d_tgt, int tgt_f64, int64_t nt, double bounds[6]);
+int pb3d_icp_step_resident(pb3d_ctx* ctx, const void* d_src, int src_f64, int64_t ns, const void* d_tgt, int tgt_f64, int64_t nt,
+                           const double T[12], double max_dist2, const double cp[3], const double cq[3], void* d_out);
+
 /* ---- notebook 2: bbox camera init and projection overlays, reference utils/camera_estimation.py:56-108, :346-477 ----------------
  * grid_bounds: d_out[0] = the number of voxels of the resident (A0,A1,A2,C) grid whose colour (C = 3) / label (C = 1) is one of the
  *   ncolors <= 31 non-zero `colors` (ncolors = 0: any non-zero voxel), d_out[1..3] = their inclusive minimum (a0, a1, a2), d_out[4..6]

@@ -92,12 +92,7 @@ int launch_bounds(pb3d_ctx* ctx, const void* d_pts, int f64, i64 n, double* d_ou
 }
 
 // ---- the cell grid ------------------------------------------------------------------------------------------------------------------
-struct Grid {
-    double lo[3], hi[3];      // the reference set's exact bounding box
-    double inv[3], h[3];      // cells per unit length (0 on a one-cell axis) and cell width
-    int n[3];                 // cells per axis
-    i64 ncells;
-};
+using Grid = pb3d_nn_grid;      // pb3d_internal.h (csrc/icp.hip keeps one between calls)
 
 // cell of a coordinate: floor((v - lo) * inv) clamped to [0, n - 1] (NaN -> 0); points and queries use the same function
 __device__ __forceinline__ int cell_of(const Grid& g, int a, double v) {
@@ -591,6 +586,45 @@ int grid_of(pb3d_ctx* ctx, const void* d_r, int r_f64, i64 nr, Grid* g) {
 }
 
 }  // namespace
+
+// ---- the index kept between calls (csrc/icp.hip): knn_run's two halves, the reference half into the caller's slots ------------------
+int pb3d_nn_index_build(pb3d_ctx* ctx, const void* d_r, int r_f64, i64 nr, pb3d_slot starts_slot, pb3d_slot coords_slot, pb3d_slot ids_slot,
+                        pb3d_nn_index* ix) {
+    PB3D_TRY(grid_of(ctx, d_r, r_f64, nr, &ix->g));
+    u32* rc;
+    i64* rs;
+    void *soa, *idbuf;
+    if (r_f64) PB3D_TRY(bin_points<true>(ctx, d_r, nr, ix->g, PB3D_SLOT_NN_REF_COUNTS, starts_slot, &rc, &rs));
+    else PB3D_TRY(bin_points<false>(ctx, d_r, nr, ix->g, PB3D_SLOT_NN_REF_COUNTS, starts_slot, &rc, &rs));
+    PB3D_TRY(pb3d_scratch(ctx, coords_slot, (size_t)nr * 3 * sizeof(double), &soa));
+    PB3D_TRY(pb3d_scratch(ctx, ids_slot, (size_t)nr * sizeof(int), &idbuf));
+    double* xs = (double*)soa;
+    const dim3 grid(pb3d_stream_blocks(ctx, nr, 256, 8));
+    if (r_f64) hipLaunchKernelGGL(k_cell_scatter_ref_ids<true>, grid, dim3(256), 0, ctx->stream, d_r, nr, ix->g, (const i64*)rs, rc, xs, xs + nr,
+                                  xs + 2 * nr, (int*)idbuf);
+    else hipLaunchKernelGGL(k_cell_scatter_ref_ids<false>, grid, dim3(256), 0, ctx->stream, d_r, nr, ix->g, (const i64*)rs, rc, xs, xs + nr,
+                            xs + 2 * nr, (int*)idbuf);
+    PB3D_CHECK_LAUNCH();
+    ix->nr = nr;
+    ix->starts = rs;
+    ix->xs = xs;
+    ix->ids = (const int*)idbuf;
+    return PB3D_OK;
+}
+
+int pb3d_nn_index_nearest(pb3d_ctx* ctx, const pb3d_nn_index& ix, const double* d_q, i64 nq, int* d_idx) {
+    u32* qc;
+    i64* qs;
+    void* order;
+    PB3D_TRY(bin_points<true>(ctx, d_q, nq, ix.g, PB3D_SLOT_NN_QUERY_COUNTS, PB3D_SLOT_NN_QUERY_STARTS, &qc, &qs));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_NN_ORDER, (size_t)nq * sizeof(u32), &order));
+    hipLaunchKernelGGL(k_cell_scatter_query<true>, dim3(pb3d_stream_blocks(ctx, nq, 256, 8)), dim3(256), 0, ctx->stream, (const void*)d_q, nq,
+                       ix.g, (const i64*)qs, qc, (u32*)order);
+    PB3D_CHECK_LAUNCH();
+    launch_knn<8, true>(ctx, d_q, nq, (const u32*)order, ix.g, ix.starts, ix.xs, ix.nr, ix.ids, 1, nullptr, d_idx);
+    PB3D_CHECK_LAUNCH();
+    return PB3D_OK;
+}
 
 extern "C" {
 

@@ -139,8 +139,34 @@ enum pb3d_slot : int {
     PB3D_SLOT_DENSITY_BOUNDS = 67,
     PB3D_SLOT_DENSITY_COUNTS = 68,
     PB3D_SLOT_DENSITY_WEIGHTS = 69,
+    // cache, csrc/icp.hip: the target's cell index of an alignment (icp_index) -- cell starts, cell-sorted SoA coordinates and each
+    // sorted point's original position.  Slots of their own: the index outlives the call that builds it, and every other search
+    // (NN_REF_*) may run between two steps
+    PB3D_SLOT_ICP_INDEX_STARTS = 70,
+    PB3D_SLOT_ICP_INDEX_COORDS = 71,
+    PB3D_SLOT_ICP_INDEX_IDS = 72,
+    // call-local, csrc/icp.hip: a step's transformed source points, their nearest target positions and the per-workgroup partial rows
+    PB3D_SLOT_ICP_MOVED = 73,
+    PB3D_SLOT_ICP_NEAREST = 74,
+    PB3D_SLOT_ICP_PARTIALS = 75,
 
-    PB3D_SLOT_COUNT = 70
+    PB3D_SLOT_COUNT = 76
+};
+
+// ---- the cell index of the exact nearest-neighbour search (csrc/nn.hip) -----------------------------------
+struct pb3d_nn_grid {
+    double lo[3], hi[3];      // the reference set's exact bounding box
+    double inv[3], h[3];      // cells per unit length (0 on a one-cell axis) and cell width
+    int n[3];                 // cells per axis
+    i64 ncells;
+};
+// a reference set binned once and kept in the caller's slots (pb3d_nn_index_build); valid while those slots are
+struct pb3d_nn_index {
+    pb3d_nn_grid g;
+    i64 nr;
+    const i64* starts;        // ncells + 1 cell starts
+    const double* xs;         // cell-sorted SoA coordinates: xs, xs + nr, xs + 2 nr
+    const int* ids;           // position of each sorted point in the caller's list
 };
 
 // What a *_count leaves for its *_fill: the use counters (pb3d_ctx::scratch_use) of the slots the fill reads, taken when the count has
@@ -216,6 +242,9 @@ struct pb3d_ctx {
     // of colour k (K colours labelled together, csrc/ccl.hip: their numbering is per colour, so a label needs its colour's bits to mean anything
     // once K > 1).  gen = scratch_slot_gen[PB3D_SLOT_CCL_MEMBER_BITS] when the bits were written: only a reallocation of THAT slot invalidates them.
     struct CclLast { bool valid; const void* labels; const void* bits; i64 rows, A2, P; u64 gen; bool members_only; int K, C; u32 colors[PB3D_CCL_MAX_COLORS]; } ccl_last;
+    // the target index of an alignment (csrc/icp.hip, PB3D_SLOT_ICP_INDEX_*): built by pb3d_icp_index_resident for this (pointer, count,
+    // width), read by every pb3d_icp_step_resident.  gen = scratch_slot_gen of the three slots when it was written.
+    struct IcpIndex { bool valid; const void* tgt; i64 nt; int f64; u64 gen[3]; pb3d_nn_index ix; } icp_index;
     // Device block pool behind pb3d_dev_alloc / pb3d_dev_free: a freed block is kept (no hipFree, no stream synchronisation) and handed
     // to the next request of about its size.  Everything that touches such a block runs on ctx->stream, in order, so a re-used block
     // is never written before its previous reader has finished.  The NumPy-signature API allocates and frees a volume-sized buffer
@@ -336,6 +365,12 @@ int pb3d_ccl_label_on_device(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, i
 // ---- kernels' host launchers used across translation units ---------------------------------
 // exclusive scan of n u32 counts into n + 1 int64 offsets (the last = total) with points.hip's scan kernels; scratch slots local_slot, seg_slot
 int pb3d_scan_counts(pb3d_ctx* ctx, const u32* d_counts, i64 n, i64* d_offsets, pb3d_slot local_slot, pb3d_slot seg_slot);
+// csrc/nn.hip for csrc/icp.hip: bin the nr >= 1 reference points (one host wait for the exact box) into the three given slots; then,
+// any number of times, the position in the reference list of the nearest point ((d2, position) smallest: pb3d_knn_dev with k = 1) of
+// each of nq float64 queries -> d_idx (enqueued; only the query binning is redone)
+int pb3d_nn_index_build(pb3d_ctx* ctx, const void* d_r, int r_f64, i64 nr, pb3d_slot starts_slot, pb3d_slot coords_slot, pb3d_slot ids_slot,
+                        pb3d_nn_index* ix);
+int pb3d_nn_index_nearest(pb3d_ctx* ctx, const pb3d_nn_index& ix, const double* d_q, i64 nq, int* d_idx);
 // process_voxel_grid through the bit-sliced chain (csrc/sliced.hip); *took = 0: not applicable, nothing written
 int pb3d_process_grid_sliced(pb3d_ctx* ctx, const u8* d_occ, i64 W, i64 H, i64 D, const u8* d_mask_wh, int angle_interval, u8* d_out,
                              int known_binary, int* took);

@@ -20,7 +20,8 @@ from .eval_helpers import (chamfer_distance, compute_f1_curve, compute_nn_distan
 from .eval_helpers import (compute_surface_metrics, compute_triangle_normals, compute_vertex_normals, knn,  # noqa: F401
                            surface_metrics_per_vertex)
 from .eval_helpers import density_grid_resident, pointcloud_to_voxel_grid  # noqa: F401
-from .preprocess_helpers import flip_y_axis, normalize_preserve_aspect  # noqa: F401
+from .preprocess_helpers import (best_fit_transform_from_sums, flip_y_axis, icp_align, icp_align_resident, normalize_preserve_aspect,  # noqa: F401
+                                 transform_points, transform_points_resident)
 from .eval_helpers_intra import (color_presence, compute_binary_gt, compute_global_depth_buffer, grid_depth_buffer, grid_visible_bits,  # noqa: F401
                                  points_visible_bits, project_part_visible, run_minaret_iou_evaluation, run_minaret_kp_evaluation,
                                  run_part_minaret_binary_iou)

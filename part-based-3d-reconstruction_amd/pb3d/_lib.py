@@ -155,6 +155,9 @@ _SIGNATURES = {
     "pb3d_perspective_carve_resident": [vp, vp, i64, i64, i64, C.c_int, u8p, C.c_int, C.c_void_p, C.c_int, C.c_int, vp, vp],
     "pb3d_perspective_paint_resident": [vp, vp, i64, i64, i64, C.c_int, u8p, C.c_int, C.c_void_p, C.c_int, u8p, C.c_int, C.c_double, C.c_int,
                                         vp, vp],
+    "pb3d_transform_points_resident": [vp, vp, C.c_int, i64, dblp, vp],
+    "pb3d_icp_index_resident": [vp, vp, C.c_int, i64, dblp],
+    "pb3d_icp_step_resident": [vp, vp, C.c_int, i64, vp, C.c_int, i64, dblp, C.c_double, dblp, dblp, vp],
 }
 class IouRow(C.Structure):
     """pb3d_iou_row (include/pb3d.h)"""

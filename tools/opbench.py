@@ -252,6 +252,8 @@ def main():
         intra_eval(a.reps, res)
     if "I5" in ops:
         inter_eval(a.reps, res, cpu_ref=not a.no_cpu_ref)
+    if "ICP" in ops:
+        icp(a.reps, res, cpu_ref=not a.no_cpu_ref)
     if "MESH" in ops:
         meshify(a.reps, res)
     if "DENS" in ops:
@@ -517,6 +519,96 @@ def inter_eval(reps, res, cpu_ref=True):
         print(json.dumps(r), flush=True)
         res.append(r)
     for b in [d_g, d_tc, d_out, d_bb, d_cnt] + [c[0] for c in clouds.values()]:
+        b.free()
+
+
+def icp(reps, res, cpu_ref=True):
+    """ICP, icp_align (csrc/icp.hip on the search of csrc/nn.hip) between every point of the stored Taj grid (float32) and the 20 k SfM
+    sample in voxel coordinates (float64), both ways, the source displaced by 5 degrees about the target's centre and 2 % of its
+    extent.  ICP/step: the index build (with its one host wait) and one enqueued step, device events.  ICP/align: icp_align_resident
+    with max_iterations 1 and 10 (tolerance 0: no early stop; index build, steps and the 17-value downloads; host wall clock, best of
+    reps) -- the difference over 9 is what an iteration costs once the target is binned.  With cpu_ref, 10 iterations of a host ICP
+    on the same clouds (one cKDTree of the target, query with 16 workers, the same 3 x 3 solve) as context, not as a threshold."""
+    import math
+    from pb3d import preprocess_helpers as ph
+    lib, L = pb3d._lib.load(), pb3d._lib
+    meta = json.load(open(os.path.join(ROOT, "tests", "golden", "inter_ref.json")))
+    scale = float.fromhex(meta["taj_transform"]["scale"])
+    offset = np.array([float.fromhex(v) for v in meta["taj_transform"]["offset"]])
+    sfm = np.load(os.path.join(ROOT, "tests", "golden", "inter_sfm20k.npz"))["sfm"]
+    sfm_vox = np.ascontiguousarray(((sfm - offset) / scale)[:, ::-1])
+    taj = np.load(os.path.join(ROOT, "tests", "golden", "stored_Taj_voxel_grid.npz"))["voxel_grid"]
+    nvox = int(np.prod(taj.shape[:3]))
+    d_g = dev.from_numpy(taj)
+    d_tp, d_tc = dev.DeviceBuffer(nvox * 12), dev.DeviceBuffer(nvox * 3)
+    n = C.c_int64(0)
+    L.check(lib.pb3d_points_extract_dev(L.ctx(), C.c_void_p(d_g.ptr), *taj.shape[:3], 3, None, 0, nvox, C.c_void_p(d_tp.ptr),
+                                        C.c_void_p(d_tc.ptr), C.byref(n)))
+    ntaj = n.value
+    taj_pts = d_tp.download((ntaj, 3), np.float32)
+    clouds = {"taj_full": (d_tp, ntaj, False, taj_pts), "sfm20k": (dev.from_numpy(sfm_vox), 20000, True, sfm_vox)}
+    d_out = dev.DeviceBuffer(17 * 8)
+
+    def displaced(host):
+        lo, hi = host.min(0).astype(np.float64), host.max(0).astype(np.float64)
+        c, ext = 0.5 * (lo + hi), float((hi - lo).max())
+        a = np.array([1.0, 2.0, 3.0]) / math.sqrt(14.0)
+        K = np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+        th = math.radians(5.0)
+        M = np.eye(4)
+        M[:3, :3] = np.eye(3) + math.sin(th) * K + (1.0 - math.cos(th)) * (K @ K)
+        M[:3, 3] = c - M[:3, :3] @ c + np.array([0.02, -0.03, 0.01]) * ext
+        return M
+
+    def wall(fn):
+        fn()
+        t = []
+        for _ in range(max(3, reps)):
+            t0 = time.perf_counter()
+            fn()
+            t.append(time.perf_counter() - t0)
+        return round(1e3 * min(t), 3)
+
+    def host_icp(src, tgt, init, iters):
+        from scipy.spatial import cKDTree
+        src, tgt = np.asarray(src, np.float64), np.asarray(tgt, np.float64)
+        tree = cKDTree(tgt)
+        c = 0.5 * (tgt.min(0) + tgt.max(0))
+        T = init.copy()
+        for _ in range(iters):
+            p = src @ T[:3, :3].T + T[:3, 3]
+            d, j = tree.query(p, workers=16)
+            P, Q = p - c, tgt[j] - c
+            sums = np.concatenate([P.sum(0), Q.sum(0), (P.T @ Q).reshape(9), [(d * d).sum()]])
+            T = ph.best_fit_transform_from_sums(len(p), sums, c, c) @ T
+        return T
+
+    for sn, tn in (("taj_full", "sfm20k"), ("sfm20k", "taj_full")):
+        ds, ns, sf, hs = clouds[sn]
+        dt, nt, tf, ht = clouds[tn]
+        init = displaced(ht)
+        index_ms = timeit(lambda: ph.icp_index_resident(dt, nt, tf), reps)
+        box = ph.icp_index_resident(dt, nt, tf)
+        c = 0.5 * (box[:3] + box[3:])
+        step_ms = timeit(lambda: ph.icp_step_resident(ds, ns, dt, nt, init, -1.0, c, c, sf, tf, out=d_out), reps)
+        raw = d_out.download((17,), np.float64)
+        r = {"op": "ICP/step", "name": f"icp step: {sn} -> {tn}", "ns": ns, "nt": nt, "index_ms": round(index_ms, 4), "step_ms": round(step_ms, 4),
+             "Mpoint_s": round(ns / step_ms / 1e3, 1), "rmse": math.sqrt(raw[16] / ns)}
+        print(json.dumps(r), flush=True)
+        res.append(r)
+        t1 = wall(lambda: ph.icp_align_resident(ds, ns, dt, nt, 1, 0.0, None, init, False, sf, tf))
+        t10 = wall(lambda: ph.icp_align_resident(ds, ns, dt, nt, 10, 0.0, None, init, False, sf, tf))
+        _, hist, _ = ph.icp_align_resident(ds, ns, dt, nt, 10, 0.0, None, init, True, sf, tf)
+        r = {"op": "ICP/align", "name": f"icp_align_resident: {sn} -> {tn}", "ns": ns, "nt": nt, "max_iterations_1_ms": t1,
+             "max_iterations_10_ms": t10, "per_further_iteration_ms": round((t10 - t1) / 9, 3), "rmse_first_last": [hist[0][1], hist[-1][1]]}
+        if cpu_ref:
+            try:
+                r["ckdtree_w16_icp_10_iterations_ms"] = wall(lambda: host_icp(hs, ht, init, 10))
+            except ImportError:
+                pass
+        print(json.dumps(r), flush=True)
+        res.append(r)
+    for b in [d_g, d_tc, d_out] + [c[0] for c in clouds.values()]:
         b.free()
 
 
