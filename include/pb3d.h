@@ -379,6 +379,38 @@ int pb3d_icp_index_resident(pb3d_ctx* ctx, const void* d_tgt, int tgt_f64, int64
 int pb3d_icp_step_resident(pb3d_ctx* ctx, const void* d_src, int src_f64, int64_t ns, const void* d_tgt, int tgt_f64, int64_t nt,
                            const double T[12], double max_dist2, const double cp[3], const double cq[3], void* d_out);
 
+/* ---- facade plane, box crop and the pieces of the four-way completion: steps 2-4 of the inter-method preprocessing (reference
+ * results/4.Inter-method_3D/README.md; its utils/preprocess_helpers.py is not shipped, so the arithmetic below is the specification) --
+ * Point lists as for ICP: (n, 3) rows of float32 (*_f64 = 0) or float64 (1), n <= 2^31 - 1.  All arithmetic is float64 after widening,
+ * every product and sum rounded on its own (no FMA).  Every entry is enqueued without a host wait.
+ * The RESIDUAL of a point p = (x, y, z) to a plane row (a, b, c, d) is r = ((a * x + b * y) + c * z) + d; p is an INLIER when
+ * fabs(r) <= tau.  A NaN residual (a NaN row, a NaN coordinate) is never an inlier.  tau >= 0 and not NaN, else PB3D_EINVAL.
+ * plane_hypotheses: d_planes (K x 4 float64 on the device, 1 <= K <= 4096) row k from the points a, b, c at positions
+ *   d_triplets[3k .. 3k + 2] (int64 on the device):
+ *     u = b - a, v = c - a;   w = (u.y*v.z - u.z*v.y, u.z*v.x - u.x*v.z, u.x*v.y - u.y*v.x);   L = sqrt((w.x*w.x + w.y*w.y) + w.z*w.z);
+ *     nrm = w / L (three divisions);   d = -((nrm.x*a.x + nrm.y*a.y) + nrm.z*a.z);   row = (nrm.x, nrm.y, nrm.z, d).
+ *   A row whose L is not a finite number above 0 (a repeated index, an exactly collinear triplet, an overflow) is four NaNs; so is a
+ *   row with an index outside [0, n), and nothing is gathered through such an index.
+ * plane_score: d_counts[k] (K int64 on the device, overwritten) = the number of inliers of row k of d_planes among the n points.  The
+ *   points are read once for all K planes; the counts are exact integers (integer atomics) and a function of the input alone.
+ *   n = 0: zeros.  1 <= K <= 4096.
+ * plane_moments: d_out (12 x 8 bytes on the device) = the int64 count of the inliers of `plane` (host, 4 values), then 11 float64 sums
+ *   over the inliers:  P = p - pivot (3);  P.x*P.x, P.x*P.y, P.x*P.z, P.y*P.y, P.y*P.z, P.z*P.z (6);  r (1);  r*r (1).  A point that is
+ *   not an inlier contributes 0 and +0.0 eleven times.  The summation order is the one stated for pb3d_icp_step_resident with n for
+ *   ns (point i is lane i % 64 of wave (i / 64) % 4 of workgroup i / 256; butterfly; ((w0 + w1) + w2) + w3; the one-workgroup pass over
+ *   the partial rows).  No floating-point atomics; two calls on the same input give the same bytes.  n = 0: count 0 and eleven +0.0.
+ * points_crop_box: order-keeping compaction.  Row i survives when lo[a] <= p[a] <= hi[a] on all three axes (the point widened, the box
+ *   closed, lo / hi on the host; a NaN coordinate fails).  The surviving rows are copied byte for byte, in the input's dtype and order,
+ *   to the front of d_out (capacity n rows; rows past the count are not written), their positions in the input go to d_idx (int32;
+ *   may be NULL) and the count to d_count (one int64 on the device).  n = 0: count 0. */
+int pb3d_plane_hypotheses_resident(pb3d_ctx* ctx, const void* d_pts, int pts_f64, int64_t n, const int64_t* d_triplets, int K, double* d_planes);
+int pb3d_plane_score_resident(pb3d_ctx* ctx, const void* d_pts, int pts_f64, int64_t n, const double* d_planes, int K, double tau,
+                              int64_t* d_counts);
+int pb3d_plane_moments_resident(pb3d_ctx* ctx, const void* d_pts, int pts_f64, int64_t n, const double plane[4], double tau,
+                                const double pivot[3], void* d_out);
+int pb3d_points_crop_box_resident(pb3d_ctx* ctx, const void* d_pts, int pts_f64, int64_t n, const double lo[3], const double hi[3], void* d_out,
+                                  int32_t* d_idx, int64_t* d_count);
+
 /* ---- notebook 2: bbox camera init and projection overlays, reference utils/camera_estimation.py:56-108, :346-477 ----------------
  * grid_bounds: d_out[0] = the number of voxels of the resident (A0,A1,A2,C) grid whose colour (C = 3) / label (C = 1) is one of the
  *   ncolors <= 31 non-zero `colors` (ncolors = 0: any non-zero voxel), d_out[1..3] = their inclusive minimum (a0, a1, a2), d_out[4..6]

@@ -9,18 +9,21 @@
 //   k_icp_terms       one point per thread in the ORIGINAL order, 256 consecutive points per workgroup: gathers target row j, forms the
 //                     16 terms (+0.0 for a pair the gate rejects and for the lanes past the end) and reduces them to one partial row
 //                     per workgroup                                                        -> PB3D_SLOT_ICP_PARTIALS
-//   k_icp_final       one 256-thread workgroup: thread t adds partial rows t, t + 256, ... in ascending order, then the same reduction
+//   pb3d_k_rows_final one 256-thread workgroup: thread t adds partial rows t, t + 256, ... in ascending order, then the same reduction
+//                     (csrc/reduce_rows.h, shared with csrc/plane.hip)
 // and nothing waits for the host.  The summation order is a function of (ns, point index) alone: no floating-point atomics, and the
 // cell-sorted query order of the search (free within a cell) never reaches a sum, because the terms are formed from the index array in
 // the caller's order.  The Makefile passes -ffp-contract=off: every product and sum below is one rounded operation.
 #include <cmath>
 
 #include "pb3d_internal.h"
+#include "reduce_rows.h"
 
 namespace {
 
 constexpr i64 kMaxPoints = (1ll << 31) - 1;  // as csrc/nn.hip: sorted positions and query slots are 32-bit
-constexpr int kRow = 17;                     // a partial row and the result: the int64 count, then the 16 float64 sums
+constexpr int kSums = 16;
+constexpr int kRow = kSums + 1;              // a partial row and the result: the int64 count, then the 16 float64 sums
 
 struct Xf { double t[12]; };                 // row-major 3 x 4 [R | t]
 struct Pivots { double cp[3], cq[3]; };
@@ -44,27 +47,6 @@ __global__ __launch_bounds__(256) void k_icp_transform(const void* __restrict__ 
 #pragma unroll
         for (int h = 0; h < 3; ++h) out[3 * i + h] = ((T.t[4 * h] * x + T.t[4 * h + 1] * y) + T.t[4 * h + 2] * z) + T.t[4 * h + 3];
     }
-}
-
-// The workgroup's 256 (count, 16 values) -> row[0] = count, row[1 + c] = sum c: per wave the butterfly v += shfl_xor(v, off) for
-// off = 32 ... 1 (every lane ends with the same bits: IEEE addition commutes), then the four wave sums added left to right.
-__device__ __forceinline__ void reduce_row(double v[16], i64 cnt, double* __restrict__ row) {
-    __shared__ double red[4][16];
-    __shared__ i64 redc[4];
-#pragma unroll
-    for (int c = 0; c < 16; ++c)
-        for (int off = 32; off > 0; off >>= 1) v[c] += __shfl_xor(v[c], off);
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) {
-#pragma unroll
-        for (int c = 0; c < 16; ++c) red[w][c] = v[c];
-        redc[w] = cnt;
-    }
-    __syncthreads();
-    const int t = threadIdx.x;
-    if (t < 16) row[1 + t] = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
-    if (t == 16) ((i64*)row)[0] = redc[0] + redc[1] + redc[2] + redc[3];
 }
 
 template <bool TF64>
@@ -99,21 +81,7 @@ __global__ __launch_bounds__(256) void k_icp_terms(const double* __restrict__ mo
             }
         }
     }
-    reduce_row(v, cnt, part + (i64)blockIdx.x * kRow);
-}
-
-__global__ __launch_bounds__(256) void k_icp_final(const double* __restrict__ part, i64 nrows, double* __restrict__ out) {
-    double v[16];
-#pragma unroll
-    for (int c = 0; c < 16; ++c) v[c] = 0.0;
-    i64 cnt = 0;
-    for (i64 r = threadIdx.x; r < nrows; r += 256) {
-        const double* row = part + r * kRow;
-        cnt += ((const i64*)row)[0];
-#pragma unroll
-        for (int c = 0; c < 16; ++c) v[c] += row[1 + c];
-    }
-    reduce_row(v, cnt, out);
+    pb3d_reduce_row<kSums>(v, cnt, part + (i64)blockIdx.x * kRow);
 }
 
 int launch_transform(pb3d_ctx* ctx, const void* d_src, int f64, i64 n, const double T[12], double* d_out) {
@@ -190,7 +158,7 @@ int pb3d_icp_step_resident(pb3d_ctx* ctx, const void* d_src, int src_f64, int64_
     else hipLaunchKernelGGL(k_icp_terms<false>, dim3((unsigned)nrows), dim3(256), 0, ctx->stream, (const double*)moved, (const int*)nearest,
                             (i64)ns, d_tgt, (i64)nt, max_dist2, pv, (double*)part);
     PB3D_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_icp_final, dim3(1), dim3(256), 0, ctx->stream, (const double*)part, nrows, (double*)d_out);
+    hipLaunchKernelGGL(pb3d_k_rows_final<kSums>, dim3(1), dim3(256), 0, ctx->stream, (const double*)part, nrows, (double*)d_out);
     PB3D_CHECK_LAUNCH();
     return PB3D_OK;
 }

@@ -149,8 +149,15 @@ enum pb3d_slot : int {
     PB3D_SLOT_ICP_MOVED = 73,
     PB3D_SLOT_ICP_NEAREST = 74,
     PB3D_SLOT_ICP_PARTIALS = 75,
+    // call-local, csrc/plane.hip: the per-workgroup partial rows of a plane refit; the crop's per-workgroup survivor counts, their
+    // offsets and the two slots of its pb3d_scan_counts
+    PB3D_SLOT_PLANE_PARTIALS = 76,
+    PB3D_SLOT_CROP_COUNTS = 77,
+    PB3D_SLOT_CROP_OFFSETS = 78,
+    PB3D_SLOT_CROP_SCAN_LOCAL = 79,
+    PB3D_SLOT_CROP_SCAN_SEGS = 80,
 
-    PB3D_SLOT_COUNT = 76
+    PB3D_SLOT_COUNT = 81
 };
 
 // ---- the cell index of the exact nearest-neighbour search (csrc/nn.hip) -----------------------------------

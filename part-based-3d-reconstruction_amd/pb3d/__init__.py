@@ -22,6 +22,9 @@ from .eval_helpers import (compute_surface_metrics, compute_triangle_normals, co
 from .eval_helpers import density_grid_resident, pointcloud_to_voxel_grid  # noqa: F401
 from .preprocess_helpers import (best_fit_transform_from_sums, flip_y_axis, icp_align, icp_align_resident, normalize_preserve_aspect,  # noqa: F401
                                  transform_points, transform_points_resident)
+from .preprocess_helpers import (crop_to_box, crop_to_box_resident, fit_plane_ransac, fit_plane_ransac_resident,  # noqa: F401
+                                 plane_alignment_transform, plane_from_moments, plane_hypotheses_resident, plane_moments_resident,
+                                 plane_score_resident, symmetric_completion, symmetric_completion_resident)
 from .eval_helpers_intra import (color_presence, compute_binary_gt, compute_global_depth_buffer, grid_depth_buffer, grid_visible_bits,  # noqa: F401
                                  points_visible_bits, project_part_visible, run_minaret_iou_evaluation, run_minaret_kp_evaluation,
                                  run_part_minaret_binary_iou)

@@ -11,8 +11,14 @@ rigid point-to-point ICP with both clouds resident on the device.  There is no u
 arithmetic to the bit: per iteration the device transforms the source, finds every point's exact nearest target point against an
 index built once per alignment (csrc/icp.hip on the search of csrc/nn.hip, ties to the lowest index) and reduces the pairs to a
 count and 16 float64 sums in a fixed order; the host downloads those 17 values, solves the 3 x 3 problem
-(best_fit_transform_from_sums) and composes the transform.  The SfM preprocessing, the facade-plane fit and the symmetric completion
-of that file are not mirrored."""
+(best_fit_transform_from_sums) and composes the transform.
+
+crop_to_box, fit_plane_ransac + plane_alignment_transform and symmetric_completion are steps 2-4 of the same README: crop the dense
+cloud to the sparse cloud's box, estimate the dominant facade plane and turn it onto the Z axis, and the naive four-way completion.
+Again include/pb3d.h states the arithmetic (csrc/plane.hip): the device builds K plane hypotheses from K point triplets, scores all
+of them against the resident cloud in one sweep with exact integer counts, and reduces the inliers of a plane to a count and 11
+float64 sums in the ICP step's fixed order; the host draws the triplets, picks the best row, and solves the 3 x 3 eigen problem of a
+refit (plane_from_moments).  What is still not mirrored: loading and segmenting the SfM cloud, and the CAD model."""
 import ctypes as C
 import math
 
@@ -21,7 +27,9 @@ import numpy as np
 from . import _lib
 
 __all__ = ["normalize_preserve_aspect", "flip_y_axis", "transform_points", "transform_points_resident", "best_fit_transform_from_sums",
-           "icp_align", "icp_align_resident", "icp_index_resident", "icp_step_resident"]
+           "icp_align", "icp_align_resident", "icp_index_resident", "icp_step_resident", "plane_hypotheses_resident", "plane_score_resident",
+           "plane_moments_resident", "crop_to_box_resident", "plane_from_moments", "fit_plane_ransac", "fit_plane_ransac_resident",
+           "plane_alignment_transform", "crop_to_box", "symmetric_completion", "symmetric_completion_resident"]
 
 
 def normalize_preserve_aspect(points):
@@ -53,7 +61,10 @@ def _finite(a, what):
 
 
 def _ptr(b):
-    return None if b is None else C.c_void_p(b.ptr)
+    """the device address of a DeviceBuffer, or of a place inside one (DeviceBuffer.at)"""
+    if b is None or isinstance(b, C.c_void_p):
+        return b
+    return C.c_void_p(b.ptr)
 
 
 def _transform(T, what="T"):
@@ -217,3 +228,292 @@ def icp_align(source, target, max_iterations=50, tolerance=1e-9, max_distance=No
         d_s.free()
         if d_t is not d_s:
             d_t.free()
+
+
+# ---- facade plane, box crop, four-way completion ---------------------------------------------------------------------------------------
+MAX_HYPOTHESES = 4096
+
+
+def plane_hypotheses_resident(d_P, n, d_triplets, K, f64=True, out=None):
+    """pb3d_plane_hypotheses_resident: a DeviceBuffer of K x 4 float64, row k the plane (unit normal, d) through the three points of the
+    resident (n, 3) list that the resident int64 triplet k names; four NaNs for a degenerate or out-of-range triplet"""
+    from . import device as dev
+    d_out = out if out is not None else dev.DeviceBuffer(max(1, int(K)) * 32)
+    _lib.check(_lib.load().pb3d_plane_hypotheses_resident(_lib.ctx(), _ptr(d_P), int(bool(f64)), int(n), _ptr(d_triplets), int(K), _ptr(d_out)))
+    return d_out
+
+
+def plane_score_resident(d_P, n, d_planes, K, tau, f64=True, out=None):
+    """pb3d_plane_score_resident: a DeviceBuffer of K int64, the number of points within tau of each of the K resident plane rows"""
+    from . import device as dev
+    d_out = out if out is not None else dev.DeviceBuffer(max(1, int(K)) * 8)
+    _lib.check(_lib.load().pb3d_plane_score_resident(_lib.ctx(), _ptr(d_P), int(bool(f64)), int(n), _ptr(d_planes), int(K), float(tau), _ptr(d_out)))
+    return d_out
+
+
+def plane_moments_resident(d_P, n, plane, tau, pivot, f64=True, out=None):
+    """pb3d_plane_moments_resident: a DeviceBuffer of 12 x 8 bytes -- the int64 count of the points within tau of `plane` (a, b, c, d)
+    and the 11 float64 sums of a refit about `pivot`"""
+    from . import device as dev
+    plane = np.ascontiguousarray(plane, dtype=np.float64).reshape(4)
+    pivot = np.ascontiguousarray(pivot, dtype=np.float64).reshape(3)
+    d_out = out if out is not None else dev.DeviceBuffer(12 * 8)
+    _lib.check(_lib.load().pb3d_plane_moments_resident(_lib.ctx(), _ptr(d_P), int(bool(f64)), int(n), _lib.p_dbl(plane), float(tau),
+                                                       _lib.p_dbl(pivot), _ptr(d_out)))
+    return d_out
+
+
+def _box(lo, hi):
+    lo = np.ascontiguousarray(lo, dtype=np.float64).reshape(3)
+    hi = np.ascontiguousarray(hi, dtype=np.float64).reshape(3)
+    if np.isnan(lo).any() or np.isnan(hi).any():
+        raise ValueError("crop_to_box: a box corner is NaN")
+    return lo, hi
+
+
+def crop_to_box_resident(d_P, n, lo, hi, f64=True, out=None, index=None):
+    """pb3d_points_crop_box_resident: (d_out, count) -- the rows of the resident (n, 3) list inside the closed box [lo, hi], in their
+    order and dtype, at the front of d_out (a DeviceBuffer of n rows; allocated when `out` is None).  index: a DeviceBuffer of n int32
+    that receives the surviving rows' positions, or None.  The count is downloaded (the one host wait)."""
+    from . import device as dev
+    lo, hi = _box(lo, hi)
+    row = 24 if f64 else 12
+    d_out = out if out is not None else dev.DeviceBuffer(max(1, int(n)) * row)
+    d_count = dev.DeviceBuffer(8)
+    try:
+        _lib.check(_lib.load().pb3d_points_crop_box_resident(_lib.ctx(), _ptr(d_P), int(bool(f64)), int(n), _lib.p_dbl(lo), _lib.p_dbl(hi),
+                                                             _ptr(d_out), _ptr(index), _ptr(d_count)))
+        count = int(d_count.download((1,), np.int64)[0])
+    except BaseException:
+        if out is None:
+            d_out.free()
+        raise
+    finally:
+        d_count.free()
+    return d_out, count
+
+
+def crop_to_box(points, lo, hi, return_index=False):
+    """points[mask] for mask = all(lo <= p) & all(p <= hi) per row (the box is closed, a NaN coordinate fails), compacted on the device;
+    float32 clouds stay float32, other real dtypes become float64.  return_index=True: (cropped, np.flatnonzero(mask))."""
+    from . import device as dev
+    p, pf = _cloud(points, "points")
+    lo, hi = _box(lo, hi)
+    n = len(p)
+    if n == 0:
+        return (p.copy(), np.zeros(0, np.intp)) if return_index else p.copy()
+    d_p = dev.from_numpy(p)
+    d_idx = dev.DeviceBuffer(n * 4) if return_index else None
+    d_out = None
+    try:
+        d_out, count = crop_to_box_resident(d_p, n, lo, hi, pf, index=d_idx)
+        out = d_out.download((count, 3), p.dtype) if count else np.zeros((0, 3), p.dtype)
+        if not return_index:
+            return out
+        idx = d_idx.download((count,), np.int32) if count else np.zeros(0, np.int32)
+        return out, idx.astype(np.intp)
+    finally:
+        d_p.free()
+        if d_idx is not None:
+            d_idx.free()
+        if d_out is not None:
+            d_out.free()
+
+
+def plane_from_moments(count, sums, pivot):
+    """(normal, d, eigenvalues) of the least-squares plane of the points a refit summed: sums[0:3] = sum(p - pivot), sums[3:9] =
+    sum of (P.x*P.x, P.x*P.y, P.x*P.z, P.y*P.y, P.y*P.z, P.z*P.z) (later values are not read).  m = S / count,
+    Cov = (S2 - outer(S, S) / count) / count; the normal is np.linalg.eigh's eigenvector of the smallest eigenvalue, signed so that its
+    component of largest magnitude (the lowest axis on a tie) is positive; d = -normal . (m + pivot).  Eigenvalues ascending."""
+    count = int(count)
+    sums = np.asarray(sums, np.float64).reshape(-1)
+    pivot = np.asarray(pivot, np.float64).reshape(3)
+    if count < 3:
+        raise ValueError(f"a plane fit needs at least 3 points (got {count})")
+    S = sums[0:3]
+    xx, xy, xz, yy, yz, zz = sums[3:9]
+    S2 = np.array([[xx, xy, xz], [xy, yy, yz], [xz, yz, zz]])
+    m = S / count
+    cov = (S2 - np.outer(S, S) / count) / count
+    ev, vec = np.linalg.eigh(cov)
+    nrm = vec[:, 0].copy()
+    if nrm[int(np.argmax(np.abs(nrm)))] < 0.0:
+        nrm = -nrm
+    c = m + pivot
+    d = -((nrm[0] * c[0] + nrm[1] * c[1]) + nrm[2] * c[2])
+    return nrm, float(d), ev
+
+
+def _ransac_args(n, inlier_threshold, num_hypotheses, refine_iterations):
+    tau = float(inlier_threshold)
+    if not (tau >= 0.0 and math.isfinite(tau)):
+        raise ValueError(f"inlier_threshold must be finite and >= 0 (got {inlier_threshold})")
+    for name, v, lo in (("num_hypotheses", num_hypotheses, 1), ("refine_iterations", refine_iterations, 0)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < lo:
+            raise ValueError(f"{name} must be an integer >= {lo} (got {v!r})")
+    if num_hypotheses > MAX_HYPOTHESES:
+        raise ValueError(f"num_hypotheses must be in [1, {MAX_HYPOTHESES}] (got {num_hypotheses})")
+    if n < 3:
+        raise ValueError(f"fit_plane_ransac: a plane needs at least 3 points (got {n})")
+    return tau, int(num_hypotheses), int(refine_iterations)
+
+
+def fit_plane_ransac_resident(d_P, n, inlier_threshold, num_hypotheses=1024, seed=0, refine_iterations=2, return_history=False, f64=True):
+    """fit_plane_ransac on a resident (n, 3) list (a DeviceBuffer; float64 rows, or float32 with f64 False).  One upload of the
+    triplets, the hypotheses and score entries, one download of K planes and K counts; then per refit one moments call about the box
+    centre (pb3d_points_bounds_dev, once) and a download of its 12 numbers.  The coordinates must be finite (not checked here)."""
+    from . import device as dev
+    n = int(n)
+    tau, K, refits = _ransac_args(n, inlier_threshold, num_hypotheses, refine_iterations)
+    triplets = np.random.default_rng(seed).integers(0, n, size=(K, 3), dtype=np.int64)
+    bufs = []
+
+    def buf(b):
+        bufs.append(b)
+        return b
+
+    try:
+        d_trip = buf(dev.from_numpy(triplets))
+        d_pc = buf(dev.DeviceBuffer(K * 40))                        # K x 4 planes, then K counts: one download
+        plane_hypotheses_resident(d_P, n, d_trip, K, f64, out=d_pc.at(0))
+        plane_score_resident(d_P, n, d_pc.at(0), K, tau, f64, out=d_pc.at(K * 32))
+        raw = d_pc.download((K * 5,), np.float64)
+        planes, counts = raw[:4 * K].reshape(K, 4).copy(), raw[4 * K:].view(np.int64).copy()
+        best = int(np.argmax(counts))                               # the first maximum: ties go to the lowest k
+        if counts[best] < 3:
+            raise ValueError(f"fit_plane_ransac: the best hypothesis has {int(counts[best])} inliers (a plane needs 3)")
+        normal, d, inliers = planes[best, :3].copy(), float(planes[best, 3]), int(counts[best])
+        refit_log = []
+        if refits:
+            d_box = buf(dev.DeviceBuffer(48))
+            _lib.check(_lib.load().pb3d_points_bounds_dev(_lib.ctx(), _ptr(d_P), int(bool(f64)), n, _ptr(d_box)))
+            box = d_box.download((6,), np.float64)
+            pivot = 0.5 * (box[:3] + box[3:])
+            d_mom = buf(dev.DeviceBuffer(12 * 8))
+            for _ in range(refits):
+                plane_moments_resident(d_P, n, (normal[0], normal[1], normal[2], d), tau, pivot, f64, out=d_mom)
+                raw = d_mom.download((12,), np.float64)
+                count, sums = int(raw[:1].view(np.int64)[0]), raw[1:].copy()
+                if count < 3:
+                    raise ValueError(f"fit_plane_ransac: a refit found only {count} inliers (a plane needs 3)")
+                normal, d, _ = plane_from_moments(count, sums, pivot)
+                refit_log.append((count, sums, normal, d))
+            # the inliers of the plane that is returned: one more sweep, of one plane
+            d_one = buf(dev.from_numpy(np.array([normal[0], normal[1], normal[2], d], np.float64)))
+            plane_score_resident(d_P, n, d_one, 1, tau, f64, out=d_pc.at(K * 32))
+            inliers = int(d_pc.download((1,), np.int64, K * 32)[0])
+    finally:
+        for b in bufs:
+            b.free()
+    if return_history:
+        return normal, d, inliers, {"triplets": triplets, "planes": planes, "counts": counts, "best": best, "refits": refit_log}
+    return normal, d, inliers
+
+
+def fit_plane_ransac(points, inlier_threshold, num_hypotheses=1024, seed=0, refine_iterations=2, return_history=False):
+    """The dominant plane of a cloud by RANSAC: (normal, d, inlier_count) with normal . p + d = 0, |normal| = 1.
+
+    num_hypotheses planes through the point triplets np.random.default_rng(seed).integers(0, n, size=(K, 3), dtype=np.int64) are
+    scored by the number of points within inlier_threshold of them (all K in one sweep of the resident cloud); the best has the highest
+    count, ties to the lowest k.  Each of the refine_iterations refits replaces the plane by the least-squares plane of its inliers
+    (plane_from_moments of the device's sums about the box centre).  inlier_count is the number of points within the threshold of the
+    plane that is returned.  return_history=True adds a dict: triplets, planes (K x 4, NaN rows for degenerate triplets), counts, best
+    and refits = [(count, sums, normal, d) per refit].  ValueError for fewer than 3 points, a threshold that is negative or not finite,
+    K outside [1, 4096], points that are not finite, or fewer than 3 inliers at any stage.  float32 clouds stay float32 on the device."""
+    from . import device as dev
+    p, pf = _cloud(points, "points")
+    _ransac_args(len(p), inlier_threshold, num_hypotheses, refine_iterations)
+    _finite(p, "points")
+    d_p = dev.from_numpy(p)
+    try:
+        return fit_plane_ransac_resident(d_p, len(p), inlier_threshold, num_hypotheses, seed, refine_iterations, return_history, pf)
+    finally:
+        d_p.free()
+
+
+def plane_alignment_transform(normal, d):
+    """float64 4 x 4 [R | t]: R is the rotation about normal x (0, 0, 1) (Rodrigues) that takes `normal` to (0, 0, 1), t = (0, 0, d),
+    so the plane normal . p + d = 0 lands on z = 0 (apply it with transform_points).  A normal of exactly (0, 0, -1) takes the half
+    turn about x.  The normal is normalised first (and d with it)."""
+    nrm = np.asarray(normal, np.float64).reshape(3)
+    L = math.sqrt(float((nrm[0] * nrm[0] + nrm[1] * nrm[1]) + nrm[2] * nrm[2]))
+    d = float(d)
+    if not (L > 0.0 and math.isfinite(L) and math.isfinite(d)):
+        raise ValueError("plane_alignment_transform: the plane must be finite with a non-zero normal")
+    x, y, z = (float(v) / L for v in nrm)
+    M = np.eye(4)
+    s2 = x * x + y * y
+    if s2 == 0.0 and z < 0.0:
+        M[1, 1] = M[2, 2] = -1.0
+    else:
+        a, b = y, -x                                # v = normal x (0, 0, 1) = (a, b, 0); R = I + [v]x + [v]x^2 / (1 + z)
+        h = 1.0 / (1.0 + z) if z >= 0.0 else (1.0 - z) / s2      # the same number, without the cancellation next to z = -1
+        M[:3, :3] = [[1.0 - h * b * b, h * a * b, b], [h * a * b, 1.0 - h * a * a, -a], [-b, a, z]]
+    M[2, 3] = d / L
+    return M
+
+
+_QUARTER = np.array([[0.0, 0.0, 1.0], [0.0, 1.0, 0.0], [-1.0, 0.0, 0.0]])       # a quarter turn about +Y: (x, y, z) -> (z, y, -x)
+
+
+def quarter_turn_transforms(centre):
+    """the four float64 4 x 4 of symmetric_completion: R_q = q quarter turns about Y (entries exactly 0 / +-1), t = c - R_q c for
+    c = (cx, 0, cz)"""
+    cx, cz = (float(v) for v in np.asarray(centre, np.float64).reshape(2))
+    if not (math.isfinite(cx) and math.isfinite(cz)):
+        raise ValueError("symmetric_completion: the centre must be finite")
+    c = np.array([cx, 0.0, cz])
+    out, R = [], np.eye(3)
+    for _ in range(4):
+        M = np.eye(4)
+        M[:3, :3] = R + 0.0                         # + 0.0: no -0.0 entries
+        M[:3, 3] = c - M[:3, :3] @ c
+        out.append(M)
+        R = _QUARTER @ R
+    return out
+
+
+def symmetric_completion_resident(d_P, n, centre=None, f64=True):
+    """symmetric_completion on a resident (n, 3) list: a DeviceBuffer of 4n x 3 float64 (four transform_points_resident calls)"""
+    from . import device as dev
+    n = int(n)
+    if centre is None:
+        if n < 1:
+            raise ValueError("symmetric_completion: an empty cloud has no box; give a centre")
+        d_box = dev.DeviceBuffer(48)
+        try:
+            _lib.check(_lib.load().pb3d_points_bounds_dev(_lib.ctx(), _ptr(d_P), int(bool(f64)), n, _ptr(d_box)))
+            box = d_box.download((6,), np.float64)
+        finally:
+            d_box.free()
+        centre = (0.5 * (box[0] + box[3]), 0.5 * (box[2] + box[5]))
+    Ts = quarter_turn_transforms(centre)
+    d_out = dev.DeviceBuffer(max(1, 4 * n) * 24)
+    try:
+        for q, T in enumerate(Ts):
+            transform_points_resident(d_P, n, T, f64, out=d_out.at(q * n * 24))
+    except BaseException:
+        d_out.free()
+        raise
+    return d_out
+
+
+def symmetric_completion(points, centre=None):
+    """The naive four-way completion of a facade cloud: float64 (4n, 3), rows [q n, (q + 1) n) the cloud turned by q quarter turns about
+    the axis parallel to Y through centre = (cx, cz) (default: the x / z centre of the cloud's box).  Copy 0 is the input widened to
+    float64 (a -0.0 coordinate comes out as +0.0)."""
+    from . import device as dev
+    p, pf = _cloud(points, "points")
+    _finite(p, "points")
+    n = len(p)
+    if n == 0:
+        return np.zeros((0, 3), np.float64)
+    d_p = dev.from_numpy(p)
+    try:
+        d_out = symmetric_completion_resident(d_p, n, centre, pf)
+        try:
+            return d_out.download((4 * n, 3), np.float64)
+        finally:
+            d_out.free()
+    finally:
+        d_p.free()

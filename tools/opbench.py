@@ -1,5 +1,5 @@
 """Device-resident timing of every op of the path (M1..M8 of SURVEY.md 8(d), plus the N1/N2 kernels of the notebook-1 chain) on
-synthetic inputs.  Development/measurement tool: python tools/opbench.py [--size 1024] [--shape WxHxD] [--ops M1,M3,...,N2,overlays]; one JSON
+synthetic inputs.  Development/measurement tool: python tools/opbench.py [--size 1024] [--shape WxHxD] [--ops M1,M3,...,N2,overlays,ICP,PLANE]; one JSON
 line per op.  Pricing: `alg_B_per_voxel` is SURVEY 8(d)'s algorithmic figure for the sweeps that are EXECUTED (a folded 0-degree step
 moves nothing and is not priced); ops whose intermediates are not bytes (the bit-sliced chains) also carry `moved_B_per_voxel`, the
 bytes that cross the HBM by design, and their `frac_of_8TBs` is computed from THAT (never from bytes that are not moved)."""
@@ -254,6 +254,8 @@ def main():
         inter_eval(a.reps, res, cpu_ref=not a.no_cpu_ref)
     if "ICP" in ops:
         icp(a.reps, res, cpu_ref=not a.no_cpu_ref)
+    if "PLANE" in ops:
+        plane(a.reps, res, cpu_ref=not a.no_cpu_ref)
     if "MESH" in ops:
         meshify(a.reps, res)
     if "DENS" in ops:
@@ -609,6 +611,109 @@ def icp(reps, res, cpu_ref=True):
         print(json.dumps(r), flush=True)
         res.append(r)
     for b in [d_g, d_tc, d_out] + [c[0] for c in clouds.values()]:
+        b.free()
+
+
+FP64_VECTOR_PEAK = 78.6e12     # the spec sheet's vector FP64 rate of the MI355X, FLOP/s with a fused multiply-add counted as two
+
+
+def plane(reps, res, cpu_ref=True):
+    """PLANE, fit_plane_ransac's device entries (csrc/plane.hip) on every point of the stored Taj grid (float32) and on the 20 k SfM
+    sample in voxel coordinates (float64), K = 1024 hypotheses, tau = 1 % of the extent, device events.  PLANE/score: hypotheses +
+    score enqueued together, the score alone, and one refit (moments) about the box centre with the best hypothesis.  The score's
+    float64 operations are 6 n K (three products and three sums per point and plane; fabs and the compare are not counted); their
+    rate is set against the spec sheet's vector FP64 rate, which counts a fused multiply-add as two -- the stated arithmetic rounds
+    every product and sum on its own, so half of that rate is this kernel's ceiling.  PLANE/crop: the Taj points cropped to the SfM
+    sample's box.  With cpu_ref, the wall time of the same scoring in NumPy on this host (the restatement's loop: all 1024 planes of
+    the 20 k cloud; 16 planes of the Taj cloud, named as such) as context, not as a threshold."""
+    from pb3d import preprocess_helpers as ph
+    lib, L = pb3d._lib.load(), pb3d._lib
+    meta = json.load(open(os.path.join(ROOT, "tests", "golden", "inter_ref.json")))
+    scale = float.fromhex(meta["taj_transform"]["scale"])
+    offset = np.array([float.fromhex(v) for v in meta["taj_transform"]["offset"]])
+    sfm = np.load(os.path.join(ROOT, "tests", "golden", "inter_sfm20k.npz"))["sfm"]
+    sfm_vox = np.ascontiguousarray(((sfm - offset) / scale)[:, ::-1])
+    taj = np.load(os.path.join(ROOT, "tests", "golden", "stored_Taj_voxel_grid.npz"))["voxel_grid"]
+    nvox = int(np.prod(taj.shape[:3]))
+    d_g = dev.from_numpy(taj)
+    d_tp, d_tc = dev.DeviceBuffer(nvox * 12), dev.DeviceBuffer(nvox * 3)
+    cnt = C.c_int64(0)
+    L.check(lib.pb3d_points_extract_dev(L.ctx(), C.c_void_p(d_g.ptr), *taj.shape[:3], 3, None, 0, nvox, C.c_void_p(d_tp.ptr),
+                                        C.c_void_p(d_tc.ptr), C.byref(cnt)))
+    ntaj = cnt.value
+    taj_pts = d_tp.download((ntaj, 3), np.float32)
+    clouds = {"taj_full": (d_tp, ntaj, False, taj_pts), "sfm20k": (dev.from_numpy(sfm_vox), 20000, True, sfm_vox)}
+    K = 1024
+
+    def numpy_score(host, planes, tau):
+        p = np.ascontiguousarray(host, dtype=np.float64)
+        x, y, z = (np.ascontiguousarray(p[:, a])[None, :] for a in range(3))
+        step = max(1, (1 << 22) // len(p))
+        counts = np.zeros(len(planes), np.int64)
+        with np.errstate(invalid="ignore"):
+            for k in range(0, len(planes), step):
+                q = planes[k:k + step]
+                r = q[:, 0:1] * x
+                r += q[:, 1:2] * y
+                r += q[:, 2:3] * z
+                r += q[:, 3:4]
+                np.abs(r, out=r)
+                counts[k:k + step] = (r <= tau).sum(1)
+        return counts
+
+    for name, (d_p, n, f64, host) in clouds.items():
+        lo, hi = host.min(0).astype(np.float64), host.max(0).astype(np.float64)
+        tau, pivot = 0.01 * float((hi - lo).max()), 0.5 * (lo + hi)
+        trip = np.random.default_rng(0).integers(0, n, size=(K, 3), dtype=np.int64)
+        d_trip = dev.from_numpy(trip)
+        d_planes, d_counts, d_mom = dev.DeviceBuffer(K * 32), dev.DeviceBuffer(K * 8), dev.DeviceBuffer(12 * 8)
+
+        def both():
+            ph.plane_hypotheses_resident(d_p, n, d_trip, K, f64, out=d_planes)
+            ph.plane_score_resident(d_p, n, d_planes, K, tau, f64, out=d_counts)
+
+        both_ms = timeit(both, reps)
+        score_ms = timeit(lambda: ph.plane_score_resident(d_p, n, d_planes, K, tau, f64, out=d_counts), reps)
+        counts = d_counts.download((K,), np.int64)
+        planes = d_planes.download((K, 4), np.float64)
+        best = int(np.argmax(counts))
+        refit_ms = timeit(lambda: ph.plane_moments_resident(d_p, n, planes[best], tau, pivot, f64, out=d_mom), reps)
+        raw = d_mom.download((12,), np.float64)
+        flops = 6.0 * n * K
+        r = {"op": "PLANE/score", "name": f"plane hypotheses + score + one refit: {name}", "n": n, "K": K, "dtype": "float64" if f64 else "float32",
+             "hypotheses_and_score_ms": round(both_ms, 4), "score_ms": round(score_ms, 4), "refit_moments_ms": round(refit_ms, 4),
+             "score_fp64_TFLOP_s": round(flops / score_ms / 1e9, 3), "score_frac_of_fp64_vector_peak": round(flops / (score_ms * 1e-3) / FP64_VECTOR_PEAK, 4),
+             "score_point_GB_s": round(n * (24 if f64 else 12) / score_ms / 1e6, 2), "best_inlier_share": round(int(counts[best]) / n, 4),
+             "refit_count": int(raw[:1].view(np.int64)[0])}
+        if cpu_ref:
+            kk = K if n <= 100000 else 16
+            t0 = time.perf_counter()
+            ref = numpy_score(host, planes[:kk], tau)
+            r[f"numpy_score_{kk}_planes_ms"] = round(1e3 * (time.perf_counter() - t0), 1)
+            r["numpy_counts_equal"] = bool(np.array_equal(ref, counts[:kk]))
+        print(json.dumps(r), flush=True)
+        res.append(r)
+        for b in (d_trip, d_planes, d_counts, d_mom):
+            b.free()
+    # the dense cloud cropped to the sparse cloud's box
+    lo, hi = sfm_vox.min(0), sfm_vox.max(0)
+    d_out, d_idx, d_count = dev.DeviceBuffer(ntaj * 12), dev.DeviceBuffer(ntaj * 4), dev.DeviceBuffer(8)
+    fn = lambda: L.check(lib.pb3d_points_crop_box_resident(L.ctx(), C.c_void_p(d_tp.ptr), 0, ntaj, L.p_dbl(lo), L.p_dbl(hi), C.c_void_p(d_out.ptr),
+                                                           C.c_void_p(d_idx.ptr), C.c_void_p(d_count.ptr)))
+    crop_ms = timeit(fn, reps)
+    kept = int(d_count.download((1,), np.int64)[0])
+    moved = ntaj * 12 * 2 + kept * 16             # two reads of the points (count, fill), the surviving rows and their positions written
+    r = {"op": "PLANE/crop", "name": "crop_to_box: taj_full to the sfm20k box", "n": ntaj, "kept": kept, "ms": round(crop_ms, 4),
+         "alg_GB_s": round(moved / crop_ms / 1e6, 1), "frac_of_8TBs": round(moved / crop_ms / 1e6 / PEAK, 4)}
+    if cpu_ref:
+        t0 = time.perf_counter()
+        m = ((lo <= taj_pts) & (taj_pts <= hi)).all(1)
+        got = taj_pts[m]
+        r["numpy_mask_and_take_ms"] = round(1e3 * (time.perf_counter() - t0), 1)
+        r["numpy_count_equal"] = bool(len(got) == kept)
+    print(json.dumps(r), flush=True)
+    res.append(r)
+    for b in [d_g, d_tc, d_out, d_idx, d_count] + [c[0] for c in clouds.values()]:
         b.free()
 
 
