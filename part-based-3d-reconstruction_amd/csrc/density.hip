@@ -21,7 +21,6 @@
 
 namespace {
 
-constexpr i64 kMaxPoints = (1ll << 31) - 1;
 constexpr int kMaxGrid = 1024;               // G^3 <= 2^30: a voxel's linear index fits u32
 constexpr int kMaxRadius = 64;               // int(4 * sigma + 0.5) for sigma up to 16
 constexpr u32 kFloatCap = 1u << 24;          // where repeated "+ 1" stops changing a float32
@@ -152,7 +151,7 @@ extern "C" int pb3d_density_grid_resident(pb3d_ctx* ctx, const void* d_pts, int 
                                           int radius, float* d_out) {
     PB3D_REQUIRE(grid_size >= 1 && grid_size <= kMaxGrid, "pb3d_density_grid: grid_size must be in [1, %d] (got %d)", kMaxGrid, grid_size);
     PB3D_REQUIRE(radius >= 0 && radius <= kMaxRadius, "pb3d_density_grid: the filter radius must be in [0, %d] (got %d)", kMaxRadius, radius);
-    PB3D_REQUIRE(n >= 1 && n <= kMaxPoints, "pb3d_density_grid: need 1 <= n <= 2^31 - 1 points (got %lld)", (long long)n);
+    PB3D_REQUIRE(n >= 1 && n <= pb3d_max_points, "pb3d_density_grid: need 1 <= n <= 2^31 - 1 points (got %lld)", (long long)n);
     PB3D_REQUIRE(d_pts != nullptr && d_out != nullptr && (radius == 0 || weights != nullptr), "pb3d_density_grid: null buffer");
     PB3D_REQUIRE(ctx != nullptr, "pb3d_density_grid: null context");
 

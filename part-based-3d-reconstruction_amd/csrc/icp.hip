@@ -21,7 +21,6 @@
 
 namespace {
 
-constexpr i64 kMaxPoints = (1ll << 31) - 1;  // as csrc/nn.hip: sorted positions and query slots are 32-bit
 constexpr int kSums = 16;
 constexpr int kRow = kSums + 1;              // a partial row and the result: the int64 count, then the 16 float64 sums
 
@@ -29,21 +28,10 @@ struct Xf { double t[12]; };                 // row-major 3 x 4 [R | t]
 struct Pivots { double cp[3], cq[3]; };
 
 template <bool F64>
-__device__ __forceinline__ void load3(const void* p, i64 i, double* x, double* y, double* z) {
-    if (F64) {
-        const double* d = (const double*)p + 3 * i;
-        *x = d[0]; *y = d[1]; *z = d[2];
-    } else {
-        const float* f = (const float*)p + 3 * i;
-        *x = (double)f[0]; *y = (double)f[1]; *z = (double)f[2];
-    }
-}
-
-template <bool F64>
 __global__ __launch_bounds__(256) void k_icp_transform(const void* __restrict__ src, i64 n, Xf T, double* __restrict__ out) {
     for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (i64)gridDim.x * 256) {
         double x, y, z;
-        load3<F64>(src, i, &x, &y, &z);
+        pb3d_load3<F64>(src, i, &x, &y, &z);
 #pragma unroll
         for (int h = 0; h < 3; ++h) out[3 * i + h] = ((T.t[4 * h] * x + T.t[4 * h + 1] * y) + T.t[4 * h + 2] * z) + T.t[4 * h + 3];
     }
@@ -62,7 +50,7 @@ __global__ __launch_bounds__(256) void k_icp_terms(const double* __restrict__ mo
         if (j >= 0 && j < nt) {                 // a moved point that is not finite found nobody: not used (and nothing is gathered)
             const double p[3] = {moved[3 * i], moved[3 * i + 1], moved[3 * i + 2]};
             double q[3];
-            load3<TF64>(tgt, j, &q[0], &q[1], &q[2]);
+            pb3d_load3<TF64>(tgt, j, q);
             const double dx = p[0] - q[0], dy = p[1] - q[1], dz = p[2] - q[2];
             const double d2 = (dx * dx + dy * dy) + dz * dz;
             if (max_dist2 < 0.0 || d2 <= max_dist2) {
@@ -101,7 +89,7 @@ const pb3d_slot kIndexSlots[3] = {PB3D_SLOT_ICP_INDEX_STARTS, PB3D_SLOT_ICP_INDE
 extern "C" {
 
 int pb3d_transform_points_resident(pb3d_ctx* ctx, const void* d_src, int src_f64, int64_t n, const double T[12], double* d_out) {
-    PB3D_REQUIRE(n >= 0 && n <= kMaxPoints, "pb3d_transform_points: need 0 <= n <= 2^31 - 1 points (got %lld)", (long long)n);
+    PB3D_REQUIRE(n >= 0 && n <= pb3d_max_points, "pb3d_transform_points: need 0 <= n <= 2^31 - 1 points (got %lld)", (long long)n);
     PB3D_REQUIRE(T != nullptr, "pb3d_transform_points: null transform");
     if (n == 0) return PB3D_OK;
     PB3D_REQUIRE(d_src != nullptr && d_out != nullptr, "pb3d_transform_points: null buffer");
@@ -110,7 +98,7 @@ int pb3d_transform_points_resident(pb3d_ctx* ctx, const void* d_src, int src_f64
 }
 
 int pb3d_icp_index_resident(pb3d_ctx* ctx, const void* d_tgt, int tgt_f64, int64_t nt, double bounds[6]) {
-    PB3D_REQUIRE(nt >= 1 && nt <= kMaxPoints, "pb3d_icp_index: need 1 <= nt <= 2^31 - 1 target points (got %lld)", (long long)nt);
+    PB3D_REQUIRE(nt >= 1 && nt <= pb3d_max_points, "pb3d_icp_index: need 1 <= nt <= 2^31 - 1 target points (got %lld)", (long long)nt);
     PB3D_REQUIRE(d_tgt != nullptr, "pb3d_icp_index: null buffer");
     PB3D_REQUIRE(ctx != nullptr, "pb3d_icp_index: null context");
     pb3d_ctx::IcpIndex& ii = ctx->icp_index;
@@ -129,7 +117,7 @@ int pb3d_icp_index_resident(pb3d_ctx* ctx, const void* d_tgt, int tgt_f64, int64
 int pb3d_icp_step_resident(pb3d_ctx* ctx, const void* d_src, int src_f64, int64_t ns, const void* d_tgt, int tgt_f64, int64_t nt,
                            const double T[12], double max_dist2, const double cp[3], const double cq[3], void* d_out) {
     PB3D_REQUIRE(ns >= 0 && nt >= 0, "pb3d_icp_step: negative point count");
-    PB3D_REQUIRE(ns <= kMaxPoints && nt <= kMaxPoints, "pb3d_icp_step: at most 2^31 - 1 points per set");
+    PB3D_REQUIRE(ns <= pb3d_max_points && nt <= pb3d_max_points, "pb3d_icp_step: at most 2^31 - 1 points per set");
     PB3D_REQUIRE(T != nullptr && cp != nullptr && cq != nullptr && d_out != nullptr, "pb3d_icp_step: null argument");
     PB3D_REQUIRE(max_dist2 == max_dist2, "pb3d_icp_step: the squared gate is NaN");
     PB3D_REQUIRE(ns == 0 || nt >= 1, "pb3d_icp_step: the target is empty");

@@ -24,20 +24,8 @@ namespace {
 constexpr int kBoundsBlocks = 512;
 constexpr double kPerCell = 2.0;             // points per cell the grid aims at
 constexpr i64 kMaxCells = 1ll << 25;         // cap on the cell count (index memory: 12 bytes per cell)
-constexpr i64 kMaxPoints = (1ll << 31) - 1;  // sorted positions and query slots are 32-bit
 constexpr int kMaxResolution = 2048;         // voxel_iou: two (res^3 / 8)-byte bit grids plus a ping-pong copy
 constexpr double kMargin = 1e-12;            // relative margin of every pruning comparison (rounding errors are ~1e-15)
-
-template <bool F64>
-__device__ __forceinline__ void load3(const void* p, i64 i, double* x, double* y, double* z) {
-    if (F64) {
-        const double* d = (const double*)p + 3 * i;
-        *x = d[0]; *y = d[1]; *z = d[2];
-    } else {
-        const float* f = (const float*)p + 3 * i;
-        *x = (double)f[0]; *y = (double)f[1]; *z = (double)f[2];
-    }
-}
 
 // ---- exact bounding box: per-block min / max, then one block over the partials -> out[0..3) = min, out[3..6) = max -------------------
 template <bool F64>
@@ -46,7 +34,7 @@ __global__ __launch_bounds__(256) void k_bounds_partial(const void* __restrict__
     double m[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
     for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (i64)gridDim.x * 256) {
         double x, y, z;
-        load3<F64>(pts, i, &x, &y, &z);
+        pb3d_load3<F64>(pts, i, &x, &y, &z);
         m[0] = fmin(m[0], x); m[1] = fmin(m[1], y); m[2] = fmin(m[2], z);
         m[3] = fmax(m[3], x); m[4] = fmax(m[4], y); m[5] = fmax(m[5], z);
     }
@@ -149,22 +137,24 @@ template <bool F64>
 __global__ __launch_bounds__(256) void k_cell_count(const void* __restrict__ pts, i64 n, Grid g, u32* __restrict__ counts) {
     for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (i64)gridDim.x * 256) {
         double x, y, z;
-        load3<F64>(pts, i, &x, &y, &z);
+        pb3d_load3<F64>(pts, i, &x, &y, &z);
         atomicAdd(&counts[cell_index(g, cell_of(g, 0, x), cell_of(g, 1, y), cell_of(g, 2, z))], 1u);
     }
 }
 
-// reference points -> cell-sorted SoA (xs, ys, zs); cursor: zeroed per-cell counters
+// reference points -> cell-sorted SoA (xs, ys, zs) and, where ids is given, each sorted point's position in the caller's list;
+// cursor: zeroed per-cell counters
 template <bool F64>
 __global__ __launch_bounds__(256) void k_cell_scatter_ref(const void* __restrict__ pts, i64 n, Grid g, const i64* __restrict__ start,
                                                           u32* __restrict__ cursor, double* __restrict__ xs, double* __restrict__ ys,
-                                                          double* __restrict__ zs) {
+                                                          double* __restrict__ zs, int* __restrict__ ids) {
     for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (i64)gridDim.x * 256) {
         double x, y, z;
-        load3<F64>(pts, i, &x, &y, &z);
+        pb3d_load3<F64>(pts, i, &x, &y, &z);
         const i64 c = cell_index(g, cell_of(g, 0, x), cell_of(g, 1, y), cell_of(g, 2, z));
         const i64 pos = start[c] + atomicAdd(&cursor[c], 1u);
         xs[pos] = x; ys[pos] = y; zs[pos] = z;
+        if (ids) ids[pos] = (int)i;
     }
 }
 
@@ -174,7 +164,7 @@ __global__ __launch_bounds__(256) void k_cell_scatter_query(const void* __restri
                                                             u32* __restrict__ cursor, u32* __restrict__ order) {
     for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (i64)gridDim.x * 256) {
         double x, y, z;
-        load3<F64>(pts, i, &x, &y, &z);
+        pb3d_load3<F64>(pts, i, &x, &y, &z);
         const i64 c = cell_index(g, cell_of(g, 0, x), cell_of(g, 1, y), cell_of(g, 2, z));
         order[start[c] + atomicAdd(&cursor[c], 1u)] = (u32)i;
     }
@@ -192,33 +182,16 @@ __device__ __forceinline__ double slab_gap(const Grid& g, int a, int c0, int c1,
 // true when a lower bound lb (squared) proves that nothing there beats best (squared, as computed)
 __device__ __forceinline__ bool beyond(double lb, double best) { return lb * (1.0 - kMargin) > best; }
 
-template <int K>
-__device__ __forceinline__ void visit_run(const double* __restrict__ xs, const double* __restrict__ ys, const double* __restrict__ zs,
-                                          i64 s, i64 e, double qx, double qy, double qz, double* b1, double* b2) {
-    double m1 = *b1, m2 = *b2;
-    for (i64 p = s; p < e; ++p) {
-        const double dx = qx - xs[p], dy = qy - ys[p], dz = qz - zs[p];
-        const double d2 = (dx * dx + dy * dy) + dz * dz;
-        if (K == 1) {
-            m1 = fmin(m1, d2);
-        } else {                                    // (m1, m2) = the two smallest of (m1, m2, d2)
-            m2 = fmin(m2, fmax(m1, d2));
-            m1 = fmin(m1, d2);
-        }
-    }
-    *b1 = m1;
-    *b2 = m2;
-}
-
-template <int K, bool F64>
-__global__ __launch_bounds__(256) void k_nn_query(const void* __restrict__ q, i64 nq, const u32* __restrict__ order, Grid g,
-                                                  const i64* __restrict__ start, const double* __restrict__ xs, const double* __restrict__ ys,
-                                                  const double* __restrict__ zs, double* __restrict__ out) {
-    const i64 s = (i64)blockIdx.x * 256 + threadIdx.x;
-    if (s >= nq) return;
-    const u32 qi = order[s];
-    double qv[3];
-    load3<F64>(q, qi, &qv[0], &qv[1], &qv[2]);
+// ---- the ring walk: one query against the index, for every search ----------------------------------------------------------------
+// Best is the search's "best so far" and supplies two things: bound(), the pruning bound (the k-th best squared distance, as
+// computed), and visit(pts, s, e, qv), which takes the run [s, e) of the cell-sorted arrays.  A column's runs (at most two) are decided
+// first and then visited by ONE loop: a visit at each of the three places a run is chosen would inline KBest's insertion three
+// times and take k_knn_query<8> and <20> to 256 registers.  The second z-end cell of a column is therefore tested against a bound
+// that the first has not tightened yet; pruning only ever skips cells, so no result depends on it.
+struct Sorted { const double *xs, *ys, *zs; const int* ids; };     // the cell-sorted arrays (ids: null in the distance-only search)
+template <class Best>
+__device__ __forceinline__ void ring_walk(const Grid& g, const i64* __restrict__ start, const Sorted& pts, const double (&qv)[3],
+                                          Best& best) {
     int c[3];
     double tol[3], out2[3];     // per axis: margin, squared distance of the query to the box's extent on that axis
 #pragma unroll
@@ -228,7 +201,6 @@ __global__ __launch_bounds__(256) void k_nn_query(const void* __restrict__ q, i6
         const double o = fmax(fmax(g.lo[a] - qv[a], qv[a] - g.hi[a]) - tol[a], 0.0);
         out2[a] = o * o;
     }
-    double b1 = INFINITY, b2 = INFINITY;
     const int rmax = max(max(g.n[0], g.n[1]), g.n[2]);
     for (int r = 0; r <= rmax; ++r) {
         const int x0 = max(c[0] - r, 0), x1 = min(c[0] + r, g.n[0] - 1);
@@ -237,29 +209,26 @@ __global__ __launch_bounds__(256) void k_nn_query(const void* __restrict__ q, i6
         for (int i = x0; i <= x1; ++i) {
             const double gx = slab_gap(g, 0, i, i, qv[0], tol[0]);
             const double gx2 = gx * gx;
-            if (beyond(gx2, K == 1 ? b1 : b2)) continue;
+            if (beyond(gx2, best.bound())) continue;
             const bool xe = i == c[0] - r || i == c[0] + r;
             for (int j = y0; j <= y1; ++j) {
                 const double gy = slab_gap(g, 1, j, j, qv[1], tol[1]);
                 const double gxy = gx2 + gy * gy;
-                if (beyond(gxy, K == 1 ? b1 : b2)) continue;
+                if (beyond(gxy, best.bound())) continue;
                 const i64 row = cell_index(g, i, j, 0);
+                i64 s0 = 0, e0 = 0, s1 = 0, e1 = 0;
+                const auto z_run = [&](int za, int zb, i64* s, i64* e) {     // the cells [za, zb] of this column, unless pruned
+                    const double gz = slab_gap(g, 2, za, zb, qv[2], tol[2]);
+                    if (!beyond(gxy + gz * gz, best.bound())) { *s = start[row + za]; *e = start[row + zb + 1]; }
+                };
                 if (xe || j == c[1] - r || j == c[1] + r) {         // the whole z-run of the ring's face
-                    const double gz = slab_gap(g, 2, z0, z1, qv[2], tol[2]);
-                    if (beyond(gxy + gz * gz, K == 1 ? b1 : b2)) continue;
-                    visit_run<K>(xs, ys, zs, start[row + z0], start[row + z1 + 1], qv[0], qv[1], qv[2], &b1, &b2);
+                    z_run(z0, z1, &s0, &e0);
                 } else {                                            // inside the ring's (x, y) box: its two z-end cells only
-                    if (c[2] - r >= 0) {
-                        const double gz = slab_gap(g, 2, c[2] - r, c[2] - r, qv[2], tol[2]);
-                        if (!beyond(gxy + gz * gz, K == 1 ? b1 : b2))
-                            visit_run<K>(xs, ys, zs, start[row + c[2] - r], start[row + c[2] - r + 1], qv[0], qv[1], qv[2], &b1, &b2);
-                    }
-                    if (r > 0 && c[2] + r < g.n[2]) {
-                        const double gz = slab_gap(g, 2, c[2] + r, c[2] + r, qv[2], tol[2]);
-                        if (!beyond(gxy + gz * gz, K == 1 ? b1 : b2))
-                            visit_run<K>(xs, ys, zs, start[row + c[2] + r], start[row + c[2] + r + 1], qv[0], qv[1], qv[2], &b1, &b2);
-                    }
+                    if (c[2] - r >= 0) z_run(c[2] - r, c[2] - r, &s0, &e0);
+                    if (r > 0 && c[2] + r < g.n[2]) z_run(c[2] + r, c[2] + r, &s1, &e1);
                 }
+#pragma nounroll
+                for (int t = 0; t < 2; ++t) best.visit(pts, t ? s1 : s0, t ? e1 : e0, qv);
             }
         }
         // lower bound over the cells not yet visited: per face of the visited box with cells beyond it, the gap to that face plus the
@@ -278,46 +247,61 @@ __global__ __launch_bounds__(256) void k_nn_query(const void* __restrict__ q, i6
                 lb = fmin(lb, gap * gap + rest);
             }
         }
-        if (lb == INFINITY || beyond(lb, K == 1 ? b1 : b2)) break;
+        if (lb == INFINITY || beyond(lb, best.bound())) break;
     }
-    out[qi] = __dsqrt_rn(K == 1 ? b1 : b2);
+}
+
+// the distance-only search (K = 1 or 2): the two smallest squared distances seen; whose they are never reaches a metric
+template <int K>
+struct NearBest {
+    double m1, m2;
+    __device__ __forceinline__ double bound() const { return K == 1 ? m1 : m2; }
+    __device__ __forceinline__ void visit(const Sorted& pts, i64 s, i64 e, const double (&q)[3]) {
+        for (i64 p = s; p < e; ++p) {
+            const double dx = q[0] - pts.xs[p], dy = q[1] - pts.ys[p], dz = q[2] - pts.zs[p];
+            const double d2 = (dx * dx + dy * dy) + dz * dz;
+            if (K == 2) m2 = fmin(m2, fmax(m1, d2));    // (m1, m2) = the two smallest of (m1, m2, d2)
+            m1 = fmin(m1, d2);
+        }
+    }
+};
+
+template <int K, bool F64>
+__global__ __launch_bounds__(256) void k_nn_query(const void* __restrict__ q, i64 nq, const u32* __restrict__ order, Grid g,
+                                                  const i64* __restrict__ start, const double* __restrict__ xs, const double* __restrict__ ys,
+                                                  const double* __restrict__ zs, double* __restrict__ out) {
+    const i64 s = (i64)blockIdx.x * 256 + threadIdx.x;
+    if (s >= nq) return;
+    const u32 qi = order[s];
+    double qv[3];
+    pb3d_load3<F64>(q, qi, qv);
+    NearBest<K> best = {INFINITY, INFINITY};
+    const Sorted pts = {xs, ys, zs, nullptr};
+    ring_walk(g, start, pts, qv, best);
+    out[qi] = __dsqrt_rn(best.bound());
 }
 
 // ---- exact k nearest neighbours with indices (compute_surface_metrics, reference utils/eval_helpers.py:217-218) --------------------
-// The same index and ring walk as k_nn_query, beside it: the cell-sorted arrays carry each point's position in the caller's array
+// The same index and the same ring_walk as k_nn_query: the cell-sorted arrays carry each point's position in the caller's array
 // (ids), and every lane keeps its k best (squared distance as computed, reference index) pairs.  The list is a register array that
 // is only ever indexed by unrolled loops (KC = 8, 20 or 32 slots, the first k in use; a run-time index would put it in scratch
-// memory): slot 0 holds the WORST of the k, so the pruning bound is best[0] whatever k is, and an insertion shifts the worse
+// memory): slot 0 holds the WORST of the k, so the pruning bound is d2[0] whatever k is, and an insertion shifts the worse
 // entries towards slot 0.  Order and membership under ties are decided by (d2, index) alone, so the scatter's order within a cell
 // and the order cells are visited in do not reach the result.
-
-// reference points -> cell-sorted SoA (xs, ys, zs, ids)
-template <bool F64>
-__global__ __launch_bounds__(256) void k_cell_scatter_ref_ids(const void* __restrict__ pts, i64 n, Grid g, const i64* __restrict__ start,
-                                                              u32* __restrict__ cursor, double* __restrict__ xs, double* __restrict__ ys,
-                                                              double* __restrict__ zs, int* __restrict__ ids) {
-    for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (i64)gridDim.x * 256) {
-        double x, y, z;
-        load3<F64>(pts, i, &x, &y, &z);
-        const i64 c = cell_index(g, cell_of(g, 0, x), cell_of(g, 1, y), cell_of(g, 2, z));
-        const i64 pos = start[c] + atomicAdd(&cursor[c], 1u);
-        xs[pos] = x; ys[pos] = y; zs[pos] = z;
-        ids[pos] = (int)i;
-    }
-}
-
 __device__ __forceinline__ bool knn_less(double d2a, int ia, double d2b, int ib) { return d2a < d2b || (d2a == d2b && ia < ib); }
 
 template <int KC>
 struct KBest {
+    int k;              // 1 <= k <= KC slots in use
     double d2[KC];      // slot 0: the k-th best (the worst kept); slot k - 1: the nearest
     int id[KC];
-    __device__ __forceinline__ void init() {
+    __device__ __forceinline__ void init(int k_) {
+        k = k_;
 #pragma unroll
         for (int j = 0; j < KC; ++j) { d2[j] = INFINITY; id[j] = 0x7fffffff; }
     }
     // (d, i) beats slot 0: drop slot 0, move the entries worse than (d, i) one slot down, put (d, i) above them
-    __device__ __forceinline__ void insert(int k, double d, int i) {
+    __device__ __forceinline__ void insert(double d, int i) {
         bool here = true;                       // (d, i) beats slot j
 #pragma unroll
         for (int j = 0; j < KC; ++j) {
@@ -326,6 +310,16 @@ struct KBest {
             d2[j] = above ? d2[u] : (here ? d : d2[j]);
             id[j] = above ? id[u] : (here ? i : id[j]);
             here = above;
+        }
+    }
+    __device__ __forceinline__ double bound() const { return d2[0]; }
+    __device__ __forceinline__ void visit(const Sorted& pts, i64 s, i64 e, const double (&q)[3]) {
+#pragma nounroll
+        for (i64 p = s; p < e; ++p) {
+            const double dx = q[0] - pts.xs[p], dy = q[1] - pts.ys[p], dz = q[2] - pts.zs[p];
+            const double dd = (dx * dx + dy * dy) + dz * dz;
+            const int i = pts.ids[p];
+            if (knn_less(dd, i, d2[0], id[0])) insert(dd, i);
         }
     }
 };
@@ -339,76 +333,11 @@ __global__ __launch_bounds__(256) void k_knn_query(const void* __restrict__ q, i
     if (s >= nq) return;
     const u32 qi = order[s];
     double qv[3];
-    load3<F64>(q, qi, &qv[0], &qv[1], &qv[2]);
-    int c[3];
-    double tol[3], out2[3];     // as in k_nn_query
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        c[a] = cell_of(g, a, qv[a]);
-        tol[a] = 1e-12 * (fabs(g.lo[a]) + fabs(g.hi[a]) + fabs(qv[a]));
-        const double o = fmax(fmax(g.lo[a] - qv[a], qv[a] - g.hi[a]) - tol[a], 0.0);
-        out2[a] = o * o;
-    }
+    pb3d_load3<F64>(q, qi, qv);
     KBest<KC> best;
-    best.init();
-    const int rmax = max(max(g.n[0], g.n[1]), g.n[2]);
-    for (int r = 0; r <= rmax; ++r) {
-        const int x0 = max(c[0] - r, 0), x1 = min(c[0] + r, g.n[0] - 1);
-        const int y0 = max(c[1] - r, 0), y1 = min(c[1] + r, g.n[1] - 1);
-        const int z0 = max(c[2] - r, 0), z1 = min(c[2] + r, g.n[2] - 1);
-        for (int i = x0; i <= x1; ++i) {
-            const double gx = slab_gap(g, 0, i, i, qv[0], tol[0]);
-            const double gx2 = gx * gx;
-            if (beyond(gx2, best.d2[0])) continue;
-            const bool xe = i == c[0] - r || i == c[0] + r;
-            for (int j = y0; j <= y1; ++j) {
-                const double gy = slab_gap(g, 1, j, j, qv[1], tol[1]);
-                const double gxy = gx2 + gy * gy;
-                if (beyond(gxy, best.d2[0])) continue;
-                const i64 row = cell_index(g, i, j, 0);
-                i64 s0 = 0, e0 = 0, s1 = 0, e1 = 0;                 // the (at most two) runs of this column, visited by one loop below
-                if (xe || j == c[1] - r || j == c[1] + r) {         // the whole z-run of the ring's face
-                    const double gz = slab_gap(g, 2, z0, z1, qv[2], tol[2]);
-                    if (!beyond(gxy + gz * gz, best.d2[0])) { s0 = start[row + z0]; e0 = start[row + z1 + 1]; }
-                } else {                                            // inside the ring's (x, y) box: its two z-end cells only
-                    if (c[2] - r >= 0) {
-                        const double gz = slab_gap(g, 2, c[2] - r, c[2] - r, qv[2], tol[2]);
-                        if (!beyond(gxy + gz * gz, best.d2[0])) { s0 = start[row + c[2] - r]; e0 = start[row + c[2] - r + 1]; }
-                    }
-                    if (r > 0 && c[2] + r < g.n[2]) {
-                        const double gz = slab_gap(g, 2, c[2] + r, c[2] + r, qv[2], tol[2]);
-                        if (!beyond(gxy + gz * gz, best.d2[0])) { s1 = start[row + c[2] + r]; e1 = start[row + c[2] + r + 1]; }
-                    }
-                }
-#pragma nounroll
-                for (int t = 0; t < 2; ++t) {
-                    const i64 e = t ? e1 : e0;
-#pragma nounroll
-                    for (i64 p = t ? s1 : s0; p < e; ++p) {
-                        const double dx = qv[0] - xs[p], dy = qv[1] - ys[p], dz = qv[2] - zs[p];
-                        const double d2 = (dx * dx + dy * dy) + dz * dz;
-                        const int id = ids[p];
-                        if (knn_less(d2, id, best.d2[0], best.id[0])) best.insert(k, d2, id);
-                    }
-                }
-            }
-        }
-        const int lo_[3] = {x0, y0, z0}, hi_[3] = {x1, y1, z1};     // the bound over the cells not yet visited, as in k_nn_query
-        double lb = INFINITY;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const double rest = out2[(a + 1) % 3] + out2[(a + 2) % 3];
-            if (hi_[a] < g.n[a] - 1) {
-                const double gap = fmax(g.lo[a] + (double)(hi_[a] + 1) * g.h[a] - qv[a] - tol[a], 0.0);
-                lb = fmin(lb, gap * gap + rest);
-            }
-            if (lo_[a] > 0) {
-                const double gap = fmax(qv[a] - (g.lo[a] + (double)lo_[a] * g.h[a]) - tol[a], 0.0);
-                lb = fmin(lb, gap * gap + rest);
-            }
-        }
-        if (lb == INFINITY || beyond(lb, best.d2[0])) break;
-    }
+    best.init(k);
+    const Sorted pts = {xs, ys, zs, ids};
+    ring_walk(g, start, pts, qv, best);
     // row qi, nearest first: slot k - 1 - j
 #pragma unroll
     for (int j = 0; j < KC; ++j) {
@@ -440,7 +369,7 @@ template <bool PF64, bool F32>
 __global__ __launch_bounds__(256) void k_occ_bits(const void* __restrict__ pts, i64 n, Occ o, u32* __restrict__ bits) {
     for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (i64)gridDim.x * 256) {
         double v[3];
-        load3<PF64>(pts, i, &v[0], &v[1], &v[2]);
+        pb3d_load3<PF64>(pts, i, v);
         int idx[3];
         for (int a = 0; a < 3; ++a) {
             double t;
@@ -516,62 +445,6 @@ int bin_points(pb3d_ctx* ctx, const void* d_pts, i64 n, const Grid& g, pb3d_slot
     return PB3D_OK;
 }
 
-template <bool QF64, bool RF64>
-int nn_run(pb3d_ctx* ctx, const void* d_q, i64 nq, const void* d_r, i64 nr, int k, const Grid& g, double* d_out) {
-    u32 *rc, *qc;
-    i64 *rs, *qs;
-    void *soa, *order;
-    PB3D_TRY(bin_points<RF64>(ctx, d_r, nr, g, PB3D_SLOT_NN_REF_COUNTS, PB3D_SLOT_NN_REF_STARTS, &rc, &rs));
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_NN_REF_COORDS, (size_t)nr * 3 * sizeof(double), &soa));
-    double* xs = (double*)soa;
-    hipLaunchKernelGGL(k_cell_scatter_ref<RF64>, dim3(pb3d_stream_blocks(ctx, nr, 256, 8)), dim3(256), 0, ctx->stream, d_r, nr, g,
-                       (const i64*)rs, rc, xs, xs + nr, xs + 2 * nr);
-    PB3D_CHECK_LAUNCH();
-    PB3D_TRY(bin_points<QF64>(ctx, d_q, nq, g, PB3D_SLOT_NN_QUERY_COUNTS, PB3D_SLOT_NN_QUERY_STARTS, &qc, &qs));
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_NN_ORDER, (size_t)nq * sizeof(u32), &order));
-    hipLaunchKernelGGL(k_cell_scatter_query<QF64>, dim3(pb3d_stream_blocks(ctx, nq, 256, 8)), dim3(256), 0, ctx->stream, d_q, nq, g,
-                       (const i64*)qs, qc, (u32*)order);
-    PB3D_CHECK_LAUNCH();
-    const dim3 grid((unsigned)((nq + 255) / 256));
-    if (k == 1) hipLaunchKernelGGL((k_nn_query<1, QF64>), grid, dim3(256), 0, ctx->stream, d_q, nq, (const u32*)order, g, (const i64*)rs, xs,
-                                   xs + nr, xs + 2 * nr, d_out);
-    else hipLaunchKernelGGL((k_nn_query<2, QF64>), grid, dim3(256), 0, ctx->stream, d_q, nq, (const u32*)order, g, (const i64*)rs, xs,
-                            xs + nr, xs + 2 * nr, d_out);
-    PB3D_CHECK_LAUNCH();
-    return PB3D_OK;
-}
-
-template <int KC, bool QF64>
-void launch_knn(pb3d_ctx* ctx, const void* d_q, i64 nq, const u32* order, const Grid& g, const i64* rs, const double* xs, i64 nr,
-                const int* ids, int k, double* d_dist, int* d_idx) {
-    hipLaunchKernelGGL((k_knn_query<KC, QF64>), dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream, d_q, nq, order, g, rs, xs,
-                       xs + nr, xs + 2 * nr, ids, k, d_dist, d_idx);
-}
-
-template <bool QF64, bool RF64>
-int knn_run(pb3d_ctx* ctx, const void* d_q, i64 nq, const void* d_r, i64 nr, int k, const Grid& g, double* d_dist, int* d_idx) {
-    u32 *rc, *qc;
-    i64 *rs, *qs;
-    void *soa, *idbuf, *order;
-    PB3D_TRY(bin_points<RF64>(ctx, d_r, nr, g, PB3D_SLOT_NN_REF_COUNTS, PB3D_SLOT_NN_REF_STARTS, &rc, &rs));
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_NN_REF_COORDS, (size_t)nr * 3 * sizeof(double), &soa));
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_KNN_REF_IDS, (size_t)nr * sizeof(int), &idbuf));
-    double* xs = (double*)soa;
-    hipLaunchKernelGGL(k_cell_scatter_ref_ids<RF64>, dim3(pb3d_stream_blocks(ctx, nr, 256, 8)), dim3(256), 0, ctx->stream, d_r, nr, g,
-                       (const i64*)rs, rc, xs, xs + nr, xs + 2 * nr, (int*)idbuf);
-    PB3D_CHECK_LAUNCH();
-    PB3D_TRY(bin_points<QF64>(ctx, d_q, nq, g, PB3D_SLOT_NN_QUERY_COUNTS, PB3D_SLOT_NN_QUERY_STARTS, &qc, &qs));
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_NN_ORDER, (size_t)nq * sizeof(u32), &order));
-    hipLaunchKernelGGL(k_cell_scatter_query<QF64>, dim3(pb3d_stream_blocks(ctx, nq, 256, 8)), dim3(256), 0, ctx->stream, d_q, nq, g,
-                       (const i64*)qs, qc, (u32*)order);
-    PB3D_CHECK_LAUNCH();
-    if (k <= 8) launch_knn<8, QF64>(ctx, d_q, nq, (const u32*)order, g, rs, xs, nr, (const int*)idbuf, k, d_dist, d_idx);
-    else if (k <= 20) launch_knn<20, QF64>(ctx, d_q, nq, (const u32*)order, g, rs, xs, nr, (const int*)idbuf, k, d_dist, d_idx);
-    else launch_knn<32, QF64>(ctx, d_q, nq, (const u32*)order, g, rs, xs, nr, (const int*)idbuf, k, d_dist, d_idx);
-    PB3D_CHECK_LAUNCH();
-    return PB3D_OK;
-}
-
 // the reference set's exact box, read back once, and the cell grid made from it
 int grid_of(pb3d_ctx* ctx, const void* d_r, int r_f64, i64 nr, Grid* g) {
     void* bb;
@@ -585,25 +458,20 @@ int grid_of(pb3d_ctx* ctx, const void* d_r, int r_f64, i64 nr, Grid* g) {
     return PB3D_OK;
 }
 
-}  // namespace
-
-// ---- the index kept between calls (csrc/icp.hip): knn_run's two halves, the reference half into the caller's slots ------------------
-int pb3d_nn_index_build(pb3d_ctx* ctx, const void* d_r, int r_f64, i64 nr, pb3d_slot starts_slot, pb3d_slot coords_slot, pb3d_slot ids_slot,
-                        pb3d_nn_index* ix) {
-    PB3D_TRY(grid_of(ctx, d_r, r_f64, nr, &ix->g));
+// The host pipeline of a search is grid_of, then two halves.  The reference half bins the reference list on the grid of ix and scatters
+// it into cell-sorted arrays in the caller's slots (ids_slot null: no ids) -> the rest of ix.
+template <bool F64>
+int index_reference_t(pb3d_ctx* ctx, const void* d_r, i64 nr, pb3d_slot starts_slot, pb3d_slot coords_slot, const pb3d_slot* ids_slot,
+                      pb3d_nn_index* ix) {
     u32* rc;
     i64* rs;
-    void *soa, *idbuf;
-    if (r_f64) PB3D_TRY(bin_points<true>(ctx, d_r, nr, ix->g, PB3D_SLOT_NN_REF_COUNTS, starts_slot, &rc, &rs));
-    else PB3D_TRY(bin_points<false>(ctx, d_r, nr, ix->g, PB3D_SLOT_NN_REF_COUNTS, starts_slot, &rc, &rs));
+    void *soa, *idbuf = nullptr;
+    PB3D_TRY(bin_points<F64>(ctx, d_r, nr, ix->g, PB3D_SLOT_NN_REF_COUNTS, starts_slot, &rc, &rs));
     PB3D_TRY(pb3d_scratch(ctx, coords_slot, (size_t)nr * 3 * sizeof(double), &soa));
-    PB3D_TRY(pb3d_scratch(ctx, ids_slot, (size_t)nr * sizeof(int), &idbuf));
+    if (ids_slot) PB3D_TRY(pb3d_scratch(ctx, *ids_slot, (size_t)nr * sizeof(int), &idbuf));
     double* xs = (double*)soa;
-    const dim3 grid(pb3d_stream_blocks(ctx, nr, 256, 8));
-    if (r_f64) hipLaunchKernelGGL(k_cell_scatter_ref_ids<true>, grid, dim3(256), 0, ctx->stream, d_r, nr, ix->g, (const i64*)rs, rc, xs, xs + nr,
-                                  xs + 2 * nr, (int*)idbuf);
-    else hipLaunchKernelGGL(k_cell_scatter_ref_ids<false>, grid, dim3(256), 0, ctx->stream, d_r, nr, ix->g, (const i64*)rs, rc, xs, xs + nr,
-                            xs + 2 * nr, (int*)idbuf);
+    hipLaunchKernelGGL(k_cell_scatter_ref<F64>, dim3(pb3d_stream_blocks(ctx, nr, 256, 8)), dim3(256), 0, ctx->stream, d_r, nr, ix->g,
+                       (const i64*)rs, rc, xs, xs + nr, xs + 2 * nr, (int*)idbuf);
     PB3D_CHECK_LAUNCH();
     ix->nr = nr;
     ix->starts = rs;
@@ -611,25 +479,66 @@ int pb3d_nn_index_build(pb3d_ctx* ctx, const void* d_r, int r_f64, i64 nr, pb3d_
     ix->ids = (const int*)idbuf;
     return PB3D_OK;
 }
+int index_reference(pb3d_ctx* ctx, const void* d_r, int r_f64, i64 nr, pb3d_slot starts_slot, pb3d_slot coords_slot, const pb3d_slot* ids_slot,
+                    pb3d_nn_index* ix) {
+    return r_f64 ? index_reference_t<true>(ctx, d_r, nr, starts_slot, coords_slot, ids_slot, ix)
+                 : index_reference_t<false>(ctx, d_r, nr, starts_slot, coords_slot, ids_slot, ix);
+}
 
-int pb3d_nn_index_nearest(pb3d_ctx* ctx, const pb3d_nn_index& ix, const double* d_q, i64 nq, int* d_idx) {
+// The query half: the queries' positions in the cell order of grid g -> PB3D_SLOT_NN_ORDER
+template <bool F64>
+int order_queries_t(pb3d_ctx* ctx, const void* d_q, i64 nq, const Grid& g, const u32** order) {
     u32* qc;
     i64* qs;
-    void* order;
-    PB3D_TRY(bin_points<true>(ctx, d_q, nq, ix.g, PB3D_SLOT_NN_QUERY_COUNTS, PB3D_SLOT_NN_QUERY_STARTS, &qc, &qs));
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_NN_ORDER, (size_t)nq * sizeof(u32), &order));
-    hipLaunchKernelGGL(k_cell_scatter_query<true>, dim3(pb3d_stream_blocks(ctx, nq, 256, 8)), dim3(256), 0, ctx->stream, (const void*)d_q, nq,
-                       ix.g, (const i64*)qs, qc, (u32*)order);
+    void* o;
+    PB3D_TRY(bin_points<F64>(ctx, d_q, nq, g, PB3D_SLOT_NN_QUERY_COUNTS, PB3D_SLOT_NN_QUERY_STARTS, &qc, &qs));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_NN_ORDER, (size_t)nq * sizeof(u32), &o));
+    hipLaunchKernelGGL(k_cell_scatter_query<F64>, dim3(pb3d_stream_blocks(ctx, nq, 256, 8)), dim3(256), 0, ctx->stream, d_q, nq, g,
+                       (const i64*)qs, qc, (u32*)o);
     PB3D_CHECK_LAUNCH();
-    launch_knn<8, true>(ctx, d_q, nq, (const u32*)order, ix.g, ix.starts, ix.xs, ix.nr, ix.ids, 1, nullptr, d_idx);
+    *order = (const u32*)o;
+    return PB3D_OK;
+}
+int order_queries(pb3d_ctx* ctx, const void* d_q, int q_f64, i64 nq, const Grid& g, const u32** order) {
+    return q_f64 ? order_queries_t<true>(ctx, d_q, nq, g, order) : order_queries_t<false>(ctx, d_q, nq, g, order);
+}
+
+// one lane per query, in the cell order
+template <int K>
+int launch_nn(pb3d_ctx* ctx, const pb3d_nn_index& ix, const void* d_q, int q_f64, i64 nq, const u32* order, double* d_out) {
+    hipLaunchKernelGGL((q_f64 ? k_nn_query<K, true> : k_nn_query<K, false>), dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream,
+                       d_q, nq, order, ix.g, ix.starts, ix.xs, ix.xs + ix.nr, ix.xs + 2 * ix.nr, d_out);
     PB3D_CHECK_LAUNCH();
     return PB3D_OK;
+}
+template <int KC>
+int launch_knn(pb3d_ctx* ctx, const pb3d_nn_index& ix, const void* d_q, int q_f64, i64 nq, const u32* order, int k, double* d_dist,
+               int* d_idx) {
+    hipLaunchKernelGGL((q_f64 ? k_knn_query<KC, true> : k_knn_query<KC, false>), dim3((unsigned)((nq + 255) / 256)), dim3(256), 0,
+                       ctx->stream, d_q, nq, order, ix.g, ix.starts, ix.xs, ix.xs + ix.nr, ix.xs + 2 * ix.nr, ix.ids, k, d_dist, d_idx);
+    PB3D_CHECK_LAUNCH();
+    return PB3D_OK;
+}
+
+}  // namespace
+
+// ---- the index kept between calls (csrc/icp.hip): pb3d_knn_dev's two halves, the reference half into the caller's slots ------------
+int pb3d_nn_index_build(pb3d_ctx* ctx, const void* d_r, int r_f64, i64 nr, pb3d_slot starts_slot, pb3d_slot coords_slot, pb3d_slot ids_slot,
+                        pb3d_nn_index* ix) {
+    PB3D_TRY(grid_of(ctx, d_r, r_f64, nr, &ix->g));
+    return index_reference(ctx, d_r, r_f64, nr, starts_slot, coords_slot, &ids_slot, ix);
+}
+
+int pb3d_nn_index_nearest(pb3d_ctx* ctx, const pb3d_nn_index& ix, const double* d_q, i64 nq, int* d_idx) {
+    const u32* order;
+    PB3D_TRY(order_queries(ctx, d_q, 1, nq, ix.g, &order));
+    return launch_knn<8>(ctx, ix, d_q, 1, nq, order, 1, nullptr, d_idx);
 }
 
 extern "C" {
 
 int pb3d_points_bounds_dev(pb3d_ctx* ctx, const void* d_pts, int pts_f64, int64_t n, double* d_out) {
-    PB3D_REQUIRE(n >= 1 && n <= kMaxPoints, "pb3d_points_bounds: need 1 <= n <= 2^31 - 1 points (got %lld)", (long long)n);
+    PB3D_REQUIRE(n >= 1 && n <= pb3d_max_points, "pb3d_points_bounds: need 1 <= n <= 2^31 - 1 points (got %lld)", (long long)n);
     PB3D_REQUIRE(d_pts != nullptr && d_out != nullptr, "pb3d_points_bounds: null buffer");
     PB3D_REQUIRE(ctx != nullptr, "pb3d_points_bounds: null context");
     return launch_bounds(ctx, d_pts, pts_f64, n, d_out);
@@ -638,41 +547,35 @@ int pb3d_points_bounds_dev(pb3d_ctx* ctx, const void* d_pts, int pts_f64, int64_
 int pb3d_nn_dist_dev(pb3d_ctx* ctx, const void* d_q, int q_f64, int64_t nq, const void* d_r, int r_f64, int64_t nr, int k, double* d_out) {
     PB3D_REQUIRE(k == 1 || k == 2, "pb3d_nn_dist: k must be 1 or 2 (got %d)", k);
     PB3D_REQUIRE(nq >= 0 && nr >= 0, "pb3d_nn_dist: negative point count");
-    PB3D_REQUIRE(nq <= kMaxPoints && nr <= kMaxPoints, "pb3d_nn_dist: at most 2^31 - 1 points per set");
+    PB3D_REQUIRE(nq <= pb3d_max_points && nr <= pb3d_max_points, "pb3d_nn_dist: at most 2^31 - 1 points per set");
     if (nq == 0) return PB3D_OK;
     PB3D_REQUIRE(nr >= k, "pb3d_nn_dist: the reference set needs at least k = %d points (got %lld)", k, (long long)nr);
     PB3D_REQUIRE(d_q != nullptr && d_r != nullptr && d_out != nullptr, "pb3d_nn_dist: null buffer");
     PB3D_REQUIRE(ctx != nullptr, "pb3d_nn_dist: null context");
-    void* bb;
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_NN_BOUNDS, 6 * sizeof(double), &bb));
-    double* d_b = (double*)bb;
-    PB3D_TRY(launch_bounds(ctx, d_r, r_f64, nr, d_b));
-    PB3D_HIP(hipMemcpyAsync(ctx->pinned, d_b, 6 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    PB3D_TRY(pb3d_stream_sync(ctx));
-    double b[6];
-    memcpy(b, ctx->pinned, sizeof(b));
-    const Grid g = make_grid(b, nr);
-    if (q_f64 && r_f64) return nn_run<true, true>(ctx, d_q, nq, d_r, nr, k, g, d_out);
-    if (q_f64) return nn_run<true, false>(ctx, d_q, nq, d_r, nr, k, g, d_out);
-    if (r_f64) return nn_run<false, true>(ctx, d_q, nq, d_r, nr, k, g, d_out);
-    return nn_run<false, false>(ctx, d_q, nq, d_r, nr, k, g, d_out);
+    pb3d_nn_index ix;
+    const u32* order;
+    PB3D_TRY(grid_of(ctx, d_r, r_f64, nr, &ix.g));
+    PB3D_TRY(index_reference(ctx, d_r, r_f64, nr, PB3D_SLOT_NN_REF_STARTS, PB3D_SLOT_NN_REF_COORDS, nullptr, &ix));
+    PB3D_TRY(order_queries(ctx, d_q, q_f64, nq, ix.g, &order));
+    return k == 1 ? launch_nn<1>(ctx, ix, d_q, q_f64, nq, order, d_out) : launch_nn<2>(ctx, ix, d_q, q_f64, nq, order, d_out);
 }
 
 int pb3d_knn_dev(pb3d_ctx* ctx, const void* d_q, int q_f64, int64_t nq, const void* d_r, int r_f64, int64_t nr, int k, double* d_dist,
                  int32_t* d_idx) {
     PB3D_REQUIRE(k >= 1 && k <= PB3D_KNN_MAX_K, "pb3d_knn: k must be in [1, %d] (got %d)", PB3D_KNN_MAX_K, k);
     PB3D_REQUIRE(nq >= 0 && nr >= 0, "pb3d_knn: negative point count");
-    PB3D_REQUIRE(nq <= kMaxPoints && nr <= kMaxPoints, "pb3d_knn: at most 2^31 - 1 points per set");
+    PB3D_REQUIRE(nq <= pb3d_max_points && nr <= pb3d_max_points, "pb3d_knn: at most 2^31 - 1 points per set");
     if (nq == 0) return PB3D_OK;
     PB3D_REQUIRE(nr >= k, "pb3d_knn: the reference set needs at least k = %d points (got %lld)", k, (long long)nr);
     PB3D_REQUIRE(d_q != nullptr && d_r != nullptr && d_idx != nullptr, "pb3d_knn: null buffer");
     PB3D_REQUIRE(ctx != nullptr, "pb3d_knn: null context");
-    Grid g;
-    PB3D_TRY(grid_of(ctx, d_r, r_f64, nr, &g));
-    if (q_f64 && r_f64) return knn_run<true, true>(ctx, d_q, nq, d_r, nr, k, g, d_dist, d_idx);
-    if (q_f64) return knn_run<true, false>(ctx, d_q, nq, d_r, nr, k, g, d_dist, d_idx);
-    if (r_f64) return knn_run<false, true>(ctx, d_q, nq, d_r, nr, k, g, d_dist, d_idx);
-    return knn_run<false, false>(ctx, d_q, nq, d_r, nr, k, g, d_dist, d_idx);
+    pb3d_nn_index ix;
+    const u32* order;
+    PB3D_TRY(pb3d_nn_index_build(ctx, d_r, r_f64, nr, PB3D_SLOT_NN_REF_STARTS, PB3D_SLOT_NN_REF_COORDS, PB3D_SLOT_KNN_REF_IDS, &ix));
+    PB3D_TRY(order_queries(ctx, d_q, q_f64, nq, ix.g, &order));
+    if (k <= 8) return launch_knn<8>(ctx, ix, d_q, q_f64, nq, order, k, d_dist, d_idx);
+    if (k <= 20) return launch_knn<20>(ctx, ix, d_q, q_f64, nq, order, k, d_dist, d_idx);
+    return launch_knn<32>(ctx, ix, d_q, q_f64, nq, order, k, d_dist, d_idx);
 }
 
 // the index size of the last pb3d_nn_dist_dev-shaped call on nr reference points with this box (cells per axis; tools/opbench.py)
@@ -689,7 +592,7 @@ int pb3d_voxel_iou_counts_dev(pb3d_ctx* ctx, const void* d_a, int a_f64, int64_t
                  kMaxResolution, resolution);
     PB3D_REQUIRE(iters >= 0, "pb3d_voxel_iou_counts: iters must be >= 0 (got %d)", iters);
     PB3D_REQUIRE(na >= 0 && nb >= 0, "pb3d_voxel_iou_counts: negative point count");
-    PB3D_REQUIRE(na <= kMaxPoints && nb <= kMaxPoints, "pb3d_voxel_iou_counts: at most 2^31 - 1 points per set");
+    PB3D_REQUIRE(na <= pb3d_max_points && nb <= pb3d_max_points, "pb3d_voxel_iou_counts: at most 2^31 - 1 points per set");
     PB3D_REQUIRE((na == 0 || d_a) && (nb == 0 || d_b) && bounds_min && d_counts, "pb3d_voxel_iou_counts: null buffer");
     PB3D_REQUIRE(!calc_f32 || (!a_f64 && !b_f64), "pb3d_voxel_iou_counts: float32 arithmetic needs float32 points");
     PB3D_REQUIRE(ctx != nullptr, "pb3d_voxel_iou_counts: null context");

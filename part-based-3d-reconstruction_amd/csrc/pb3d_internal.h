@@ -175,6 +175,20 @@ struct pb3d_nn_index {
     const double* xs;         // cell-sorted SoA coordinates: xs, xs + nr, xs + 2 nr
     const int* ids;           // position of each sorted point in the caller's list
 };
+constexpr i64 pb3d_max_points = (1ll << 31) - 1;      // of a point list: sorted positions, query slots and ids are 32-bit
+// row i of a float32 or float64 (n, 3) point list, widened to double
+template <bool F64>
+__device__ __forceinline__ void pb3d_load3(const void* p, i64 i, double* x, double* y, double* z) {
+    if (F64) {
+        const double* d = (const double*)p + 3 * i;
+        *x = d[0]; *y = d[1]; *z = d[2];
+    } else {
+        const float* f = (const float*)p + 3 * i;
+        *x = (double)f[0]; *y = (double)f[1]; *z = (double)f[2];
+    }
+}
+template <bool F64>
+__device__ __forceinline__ void pb3d_load3(const void* p, i64 i, double v[3]) { pb3d_load3<F64>(p, i, &v[0], &v[1], &v[2]); }
 
 // What a *_count leaves for its *_fill: the use counters (pb3d_ctx::scratch_use) of the slots the fill reads, taken when the count has
 // written them.  The fill's arguments are kept next to it, in the pair's own record of pb3d_ctx.

@@ -21,7 +21,6 @@
 
 namespace {
 
-constexpr i64 kMaxPoints = (1ll << 31) - 1;
 constexpr int kMaxPlanes = 4096;             // the LDS table of k_plane_score: 16 KB of u32
 constexpr int kSums = 11;
 constexpr int kRow = kSums + 1;              // a refit's partial row and result: the int64 count, then the 11 float64 sums
@@ -35,17 +34,6 @@ struct Box { double lo[3], hi[3]; };
 struct Pivot { double c[3]; };
 
 template <bool F64>
-__device__ __forceinline__ void load3(const void* p, i64 i, double* x, double* y, double* z) {
-    if (F64) {
-        const double* d = (const double*)p + 3 * i;
-        *x = d[0]; *y = d[1]; *z = d[2];
-    } else {
-        const float* f = (const float*)p + 3 * i;
-        *x = (double)f[0]; *y = (double)f[1]; *z = (double)f[2];
-    }
-}
-
-template <bool F64>
 __global__ __launch_bounds__(256) void k_plane_hyp(const void* __restrict__ pts, i64 n, const i64* __restrict__ trip, int K,
                                                    double* __restrict__ planes) {
     const int k = blockIdx.x * 256 + threadIdx.x;
@@ -55,9 +43,9 @@ __global__ __launch_bounds__(256) void k_plane_hyp(const void* __restrict__ pts,
     const i64 ia = trip[3 * k], ib = trip[3 * k + 1], ic = trip[3 * k + 2];
     if (ia >= 0 && ia < n && ib >= 0 && ib < n && ic >= 0 && ic < n) {        // nothing is gathered through an index outside [0, n)
         double a[3], b[3], c[3];
-        load3<F64>(pts, ia, &a[0], &a[1], &a[2]);
-        load3<F64>(pts, ib, &b[0], &b[1], &b[2]);
-        load3<F64>(pts, ic, &c[0], &c[1], &c[2]);
+        pb3d_load3<F64>(pts, ia, a);
+        pb3d_load3<F64>(pts, ib, b);
+        pb3d_load3<F64>(pts, ic, c);
         const double ux = b[0] - a[0], uy = b[1] - a[1], uz = b[2] - a[2];
         const double vx = c[0] - a[0], vy = c[1] - a[1], vz = c[2] - a[2];
         const double wx = uy * vz - uz * vy, wy = uz * vx - ux * vz, wz = ux * vy - uy * vx;
@@ -88,7 +76,7 @@ __global__ __launch_bounds__(256) void k_plane_score(const void* __restrict__ pt
         for (int s = 0; s < kSlots; ++s) {
             const i64 i = tile * kTile + s * 256 + threadIdx.x;
             x[s] = y[s] = z[s] = nan;                                          // a slot past the end is never an inlier
-            if (i < n) load3<F64>(pts, i, &x[s], &y[s], &z[s]);
+            if (i < n) pb3d_load3<F64>(pts, i, &x[s], &y[s], &z[s]);
         }
         for (int k = k0; k < k1; ++k) {                                        // k is wave-uniform: the row comes through the scalar path
             const double a = planes[4 * k], b = planes[4 * k + 1], c = planes[4 * k + 2], d = planes[4 * k + 3];
@@ -117,7 +105,7 @@ __global__ __launch_bounds__(256) void k_plane_terms(const void* __restrict__ pt
     i64 cnt = 0;
     if (i < n) {
         double p[3];
-        load3<F64>(pts, i, &p[0], &p[1], &p[2]);
+        pb3d_load3<F64>(pts, i, p);
         const double r = ((pl.p[0] * p[0] + pl.p[1] * p[1]) + pl.p[2] * p[2]) + pl.p[3];
         if (fabs(r) <= tau) {
             const double P[3] = {p[0] - pv.c[0], p[1] - pv.c[1], p[2] - pv.c[2]};
@@ -135,7 +123,7 @@ __global__ __launch_bounds__(256) void k_plane_terms(const void* __restrict__ pt
 template <bool F64>
 __device__ __forceinline__ bool in_box(const void* pts, i64 i, const Box& bx) {
     double p[3];
-    load3<F64>(pts, i, &p[0], &p[1], &p[2]);
+    pb3d_load3<F64>(pts, i, p);
     bool keep = true;
 #pragma unroll
     for (int a = 0; a < 3; ++a) keep = keep && bx.lo[a] <= p[a] && p[a] <= bx.hi[a];      // a NaN coordinate fails
@@ -184,7 +172,7 @@ __global__ __launch_bounds__(256) void k_crop_fill(const void* __restrict__ pts,
 extern "C" {
 
 int pb3d_plane_hypotheses_resident(pb3d_ctx* ctx, const void* d_pts, int pts_f64, int64_t n, const int64_t* d_triplets, int K, double* d_planes) {
-    PB3D_REQUIRE(n >= 0 && n <= kMaxPoints, "pb3d_plane_hypotheses: need 0 <= n <= 2^31 - 1 points (got %lld)", (long long)n);
+    PB3D_REQUIRE(n >= 0 && n <= pb3d_max_points, "pb3d_plane_hypotheses: need 0 <= n <= 2^31 - 1 points (got %lld)", (long long)n);
     PB3D_REQUIRE(K >= 1 && K <= kMaxPlanes, "pb3d_plane_hypotheses: need 1 <= K <= %d hypotheses (got %d)", kMaxPlanes, K);
     PB3D_REQUIRE(d_triplets != nullptr && d_planes != nullptr, "pb3d_plane_hypotheses: null buffer");
     PB3D_REQUIRE(n == 0 || d_pts != nullptr, "pb3d_plane_hypotheses: null buffer");
@@ -198,7 +186,7 @@ int pb3d_plane_hypotheses_resident(pb3d_ctx* ctx, const void* d_pts, int pts_f64
 
 int pb3d_plane_score_resident(pb3d_ctx* ctx, const void* d_pts, int pts_f64, int64_t n, const double* d_planes, int K, double tau,
                               int64_t* d_counts) {
-    PB3D_REQUIRE(n >= 0 && n <= kMaxPoints, "pb3d_plane_score: need 0 <= n <= 2^31 - 1 points (got %lld)", (long long)n);
+    PB3D_REQUIRE(n >= 0 && n <= pb3d_max_points, "pb3d_plane_score: need 0 <= n <= 2^31 - 1 points (got %lld)", (long long)n);
     PB3D_REQUIRE(K >= 1 && K <= kMaxPlanes, "pb3d_plane_score: need 1 <= K <= %d planes (got %d)", kMaxPlanes, K);
     PB3D_REQUIRE(tau >= 0.0, "pb3d_plane_score: the threshold must be >= 0 and not NaN");
     PB3D_REQUIRE(d_planes != nullptr && d_counts != nullptr, "pb3d_plane_score: null buffer");
@@ -223,7 +211,7 @@ int pb3d_plane_score_resident(pb3d_ctx* ctx, const void* d_pts, int pts_f64, int
 
 int pb3d_plane_moments_resident(pb3d_ctx* ctx, const void* d_pts, int pts_f64, int64_t n, const double plane[4], double tau,
                                 const double pivot[3], void* d_out) {
-    PB3D_REQUIRE(n >= 0 && n <= kMaxPoints, "pb3d_plane_moments: need 0 <= n <= 2^31 - 1 points (got %lld)", (long long)n);
+    PB3D_REQUIRE(n >= 0 && n <= pb3d_max_points, "pb3d_plane_moments: need 0 <= n <= 2^31 - 1 points (got %lld)", (long long)n);
     PB3D_REQUIRE(tau >= 0.0, "pb3d_plane_moments: the threshold must be >= 0 and not NaN");
     PB3D_REQUIRE(plane != nullptr && pivot != nullptr && d_out != nullptr, "pb3d_plane_moments: null argument");
     PB3D_REQUIRE(n == 0 || d_pts != nullptr, "pb3d_plane_moments: null buffer");
@@ -249,7 +237,7 @@ int pb3d_plane_moments_resident(pb3d_ctx* ctx, const void* d_pts, int pts_f64, i
 
 int pb3d_points_crop_box_resident(pb3d_ctx* ctx, const void* d_pts, int pts_f64, int64_t n, const double lo[3], const double hi[3], void* d_out,
                                   int32_t* d_idx, int64_t* d_count) {
-    PB3D_REQUIRE(n >= 0 && n <= kMaxPoints, "pb3d_points_crop_box: need 0 <= n <= 2^31 - 1 points (got %lld)", (long long)n);
+    PB3D_REQUIRE(n >= 0 && n <= pb3d_max_points, "pb3d_points_crop_box: need 0 <= n <= 2^31 - 1 points (got %lld)", (long long)n);
     PB3D_REQUIRE(lo != nullptr && hi != nullptr && d_count != nullptr, "pb3d_points_crop_box: null argument");
     PB3D_REQUIRE(n == 0 || (d_pts != nullptr && d_out != nullptr), "pb3d_points_crop_box: null buffer");
     PB3D_REQUIRE(ctx != nullptr, "pb3d_points_crop_box: null context");

@@ -180,17 +180,6 @@ __device__ __forceinline__ dd dd_sub_from(double x, dd m) {
     return {h, e - (h - s.h)};
 }
 
-template <bool F64>
-__device__ __forceinline__ void load_row3(const void* p, i64 i, double* v) {
-    if (F64) {
-        const double* d = (const double*)p + 3 * i;
-        v[0] = d[0]; v[1] = d[1]; v[2] = d[2];
-    } else {
-        const float* f = (const float*)p + 3 * i;
-        v[0] = (double)f[0]; v[1] = (double)f[1]; v[2] = (double)f[2];
-    }
-}
-
 // degrees(arccos(clip(a . b, -1, 1))), the dot product rounded once
 __device__ __forceinline__ double angle_deg(const double* a, const double* b) {
     dd s = two_prod(a[0], b[0]);
@@ -243,15 +232,15 @@ __global__ __launch_bounds__(256) void k_surface_metrics(const void* __restrict_
     const int* row = idx + i * k;
     const double kk = (double)k;
     double c[3], cn[3];
-    load_row3<F64>(verts, i, c);
-    load_row3<F64>(normals, i, cn);
+    pb3d_load3<F64>(verts, i, c);
+    pb3d_load3<F64>(normals, i, cn);
 
     // neighbour mean and mean angle
     dd sp[3] = {{0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}}, sa = {0.0, 0.0};
     for (int j = 0; j < k; ++j) {
         double p[3], n[3];
-        load_row3<F64>(verts, row[j], p);
-        load_row3<F64>(normals, row[j], n);
+        pb3d_load3<F64>(verts, row[j], p);
+        pb3d_load3<F64>(normals, row[j], n);
 #pragma unroll
         for (int a = 0; a < 3; ++a) sp[a] = dd_add(sp[a], {p[a], 0.0});
         sa = dd_add(sa, {angle_deg(n, cn), 0.0});
@@ -274,7 +263,7 @@ __global__ __launch_bounds__(256) void k_surface_metrics(const void* __restrict_
         dd var = {0.0, 0.0};
         for (int j = 0; j < k; ++j) {
             double n[3];
-            load_row3<F64>(normals, row[j], n);
+            pb3d_load3<F64>(normals, row[j], n);
             const dd dev = dd_sub_from(angle_deg(n, cn), mean_a);
             const double d = dev.h + dev.l;
             var = dd_add_prod(var, d, d);
@@ -289,7 +278,7 @@ __global__ __launch_bounds__(256) void k_surface_metrics(const void* __restrict_
         dd C[6] = {{0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}};    // 00 11 22 01 02 12
         for (int j = 0; j < k; ++j) {
             double p[3];
-            load_row3<F64>(verts, row[j], p);
+            pb3d_load3<F64>(verts, row[j], p);
             dd x[3];
 #pragma unroll
             for (int a = 0; a < 3; ++a) x[a] = dd_sub_from(p[a], mean[a]);

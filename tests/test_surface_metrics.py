@@ -207,7 +207,8 @@ def test_knn_tied_clouds(cloud, dtype):
     q, r = q.astype(dtype), r.astype(dtype)
     check_knn(r, r)
     check_knn(q, r)
-    check_knn(r.astype(np.float64), r)      # mixed precisions of the two lists
+    check_knn(r.astype(np.float64), r)      # mixed precisions of the two lists, both ways
+    check_knn(q.astype(np.float32), r.astype(np.float64))
 
 
 @pytest.mark.gpu
@@ -225,9 +226,11 @@ def test_knn_small_and_degenerate_sets():
     rng = np.random.default_rng(5)
     one = np.repeat(rng.uniform(-1, 1, (1, 3)), 40, 0)      # 40 copies of one point: every distance 0, rows 0..k-1
     check_knn(one, one)
+    check_knn(one, one, ks=(8, 9, 21))                      # the last k of the 8-slot list, the first of the 20- and 32-slot lists
     line = np.zeros((70, 3))
     line[:, 1] = np.arange(70) // 2                         # duplicates on a line: two one-cell axes
     check_knn(line, line)
+    check_knn(line, line, ks=(8, 9, 21))
     check_knn(rng.uniform(-5, 5, (33, 3)), line)
     few = rng.uniform(0, 1, (7, 3))
     check_knn(rng.uniform(-1, 2, (50, 3)), few, ks=(1, 2, 7))
