@@ -3,7 +3,7 @@
 //
 // The reference projects every part on its own (get_voxel_points_by_parts + project_colored_voxels) and keeps all(proj == colour):
 // a per-part projection paints one constant colour, so that mask is "some voxel of the colour lands on the pixel" -- one bit per
-// colour and pixel, and one sweep of the grid gives the bit of every part (k_grid_hit_bits, the walk of grid_walk.h with
+// colour and pixel, and one sweep of the grid gives the bit of every part (k_grid_hit_bits, run_walk of grid_walk.h with
 // project_xyz<0>: Z < 1e-8 is clamped, there is no depth test).  The images are then composed per pixel from the bit image and the
 // resident RGB image (k_overlay_compose).
 //
@@ -11,7 +11,6 @@
 // here with __dmul_rn / __dadd_rn (and the build has -ffp-contract=off), so every byte is NumPy's.
 #include "pb3d_internal.h"
 #include "grid_walk.h"
-#include "project_point.h"
 
 namespace {
 
@@ -33,9 +32,8 @@ __global__ __launch_bounds__(256) void k_grid_bounds(Walk w, Colours cols, long 
     __shared__ int s_box[4][7];
     const i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     int cnt = 0, lo0 = 0x7fffffff, lo1 = 0x7fffffff, lo2 = 0x7fffffff, hi0 = -1, hi1 = -1, hi2 = -1;
-    if (t < w.nitems) {
-        const i64 a2 = (t % w.ngx) * 4, r = t / w.ngx, a1 = r % w.A1, a0s = (r / w.A1) * kChunk;
-        const i64 a0e = a0s + kChunk < w.A0 ? a0s + kChunk : w.A0;
+    i64 a2, a1, a0s, a0e;
+    if (walk_item(w, t, &a2, &a1, &a0s, &a0e)) {
         u32 cols_hit = 0;
         for (i64 a0 = a0s; a0 < a0e; ++a0) {
             u32 v[4];
@@ -90,35 +88,23 @@ __global__ __launch_bounds__(256) void k_grid_bounds(Walk w, Colours cols, long 
 }
 
 // ---- (b) bits[v, u] |= 1 << k for every voxel of colour k whose projection lands on (u, v) --------------------------------------
+struct HitRun {
+    static constexpr int MODE = 0;
+    typedef u32 State;
+    const Colours& cols;
+    u32* __restrict__ bits;
+    __device__ __forceinline__ bool take(u32 v, u32* b) const {       // an empty voxel, which most are, costs no colour loop
+        *b = v ? colour_bits(cols, v) : 0;
+        return *b != 0;
+    }
+    __device__ __forceinline__ void open(i64, u32* br) const { *br = 0; }
+    __device__ __forceinline__ void add(u32* br, u32 b, double) const { *br |= b; }
+    __device__ __forceinline__ void flush(i64 px, u32 br) const { flush_or(bits, px, br); }
+};
+
 template <int C>
 __global__ __launch_bounds__(256) void k_grid_hit_bits(Walk w, ProjParams P, Colours cols, u32* __restrict__ bits) {
-    const i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= w.nitems) return;
-    const i64 a2 = (t % w.ngx) * 4, r = t / w.ngx, a1 = r % w.A1, a0s = (r / w.A1) * kChunk;
-    const i64 a0e = a0s + kChunk < w.A0 ? a0s + kChunk : w.A0;
-    i64 px[4] = {-1, -1, -1, -1};
-    u32 br[4] = {0, 0, 0, 0};
-    for (i64 a0 = a0s; a0 < a0e; ++a0) {
-        u32 v[4];
-        load4<C>(w, a0, a1, a2, v);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (!v[k]) continue;
-            const u32 b = colour_bits(cols, v[k]);
-            if (!b) continue;
-            const double p[3] = {(double)(a2 + k), (double)a1, (double)a0};      // exact in float32: the entry bounds the axes by 2^24
-            int ui, vi;
-            if (!project_xyz<0>(P, p, &ui, &vi)) continue;
-            const i64 q = (i64)vi * P.Wimg + ui;
-            if (q != px[k]) {
-                flush_or(bits, px[k], br[k]);
-                px[k] = q; br[k] = 0;
-            }
-            br[k] |= b;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) flush_or(bits, px[k], br[k]);
+    run_walk<C>(w, P, HitRun{cols, bits});
 }
 
 // ---- (c) the overlay images ------------------------------------------------------------------------------------------------------
@@ -225,8 +211,6 @@ __global__ __launch_bounds__(256) void k_overlay_whole(const u32* __restrict__ b
     }
 }
 
-constexpr i64 kMaxAxis = (i64)1 << 24;    // voxel coordinates are float32 points upstream: exact below 2^24
-
 }  // namespace
 
 extern "C" {
@@ -243,12 +227,7 @@ int pb3d_grid_bounds_resident(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, 
     PB3D_CHECK_LAUNCH();
     const Walk w = make_walk(d_grid, A0, A1, A2, C);
     if (w.nitems == 0) return PB3D_OK;
-    PB3D_REQUIRE((w.nitems + 255) / 256 <= 0x7fffffff, "pb3d_grid_bounds: grid too large for one launch");
-    const unsigned blocks = (unsigned)((w.nitems + 255) / 256);
-    if (C == 1) hipLaunchKernelGGL(k_grid_bounds<1>, dim3(blocks), dim3(256), 0, ctx->stream, w, cols, (long long*)d_out);
-    else hipLaunchKernelGGL(k_grid_bounds<3>, dim3(blocks), dim3(256), 0, ctx->stream, w, cols, (long long*)d_out);
-    PB3D_CHECK_LAUNCH();
-    return PB3D_OK;
+    return launch_walk("pb3d_grid_bounds", ctx, w, C, k_grid_bounds<1>, k_grid_bounds<3>, cols, (long long*)d_out);
 }
 
 int pb3d_grid_hit_bits_resident(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64_t A1, int64_t A2, int C, const uint8_t* colors,
@@ -268,12 +247,7 @@ int pb3d_grid_hit_bits_resident(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0
     PB3D_HIP(hipMemsetAsync(d_bits, 0, (size_t)npix * 4, ctx->stream));
     const Walk w = make_walk(d_grid, A0, A1, A2, C);
     if (w.nitems == 0 || ncolors == 0) return PB3D_OK;
-    PB3D_REQUIRE((w.nitems + 255) / 256 <= 0x7fffffff, "pb3d_grid_hit_bits: grid too large for one launch");
-    const unsigned blocks = (unsigned)((w.nitems + 255) / 256);
-    if (C == 1) hipLaunchKernelGGL(k_grid_hit_bits<1>, dim3(blocks), dim3(256), 0, ctx->stream, w, P, cols, d_bits);
-    else hipLaunchKernelGGL(k_grid_hit_bits<3>, dim3(blocks), dim3(256), 0, ctx->stream, w, P, cols, d_bits);
-    PB3D_CHECK_LAUNCH();
-    return PB3D_OK;
+    return launch_walk("pb3d_grid_hit_bits", ctx, w, C, k_grid_hit_bits<1>, k_grid_hit_bits<3>, P, cols, d_bits);
 }
 
 int pb3d_overlay_compose_resident(pb3d_ctx* ctx, const uint32_t* d_bits, int nplanes, const uint8_t* d_image, int Himg, int Wimg,

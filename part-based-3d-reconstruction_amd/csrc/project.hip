@@ -102,8 +102,8 @@ struct DepthSink {
     }
 };
 
-// visible where |z - zbuf| < eps.  A float64 camera (t0; only the generic kernel, whose z is a double, sees one) subtracts
-// in float64; otherwise z - zbuf is a float32 difference, compared in float32 when eps is a weak Python float (eps_f32).
+// visible where |z - zbuf| < eps (visible(), project_point.h).  Only the generic kernel, whose z is a double, sees a float64 camera
+// (t0); a float32 z widened and narrowed again is itself.
 struct VisibleSink {
     static constexpr int MODE = 1;
     static constexpr bool REVERSE = false;
@@ -115,12 +115,7 @@ struct VisibleSink {
     __device__ __forceinline__ float peek(bool ok, I px) const { return ok ? zbuf[px] : 0.0f; }
     template <class I, class Z>
     __device__ __forceinline__ void commit(bool ok, float zb, i64, I px, Z z) const {
-        if (sizeof(Z) == sizeof(double) && t0) {
-            if (ok && fabs(__dsub_rn((double)z, (double)zb)) < eps) mask[px] = 1;                  // float64 z - float32 zbuf -> float64
-        } else {
-            const float dz = fabsf(__fsub_rn((float)z, zb));                                        // float32 z - float32 zbuf
-            if (ok && (eps_f32 ? dz < (float)eps : (double)dz < eps)) mask[px] = 1;                // weak Python float -> float32 compare
-        }
+        if (ok && visible((double)z, zb, sizeof(Z) == sizeof(double) && t0, eps, eps_f32)) mask[px] = 1;
     }
 };
 

@@ -1,5 +1,6 @@
-// Shared by project.hip and deform.hip: the pinhole arithmetic of reference utils/projection_utils.py:5-23 for ONE point, evaluated
-// in the float widths NumPy-2 promotion gives each stage (see the header of project.hip).
+// Shared by project.hip, deform.hip and the grid walks (grid_walk.h): the pinhole arithmetic of reference
+// utils/projection_utils.py:5-23 for ONE point, evaluated in the float widths NumPy-2 promotion gives each stage (see the header of
+// project.hip), and the visibility test of utils/eval_helpers_intra.py:134-190.
 #pragma once
 #include "pb3d_internal.h"
 
@@ -63,6 +64,13 @@ __device__ __forceinline__ bool project_point(const ProjParams& P, const void* _
     return project_xyz<MODE>(P, p, ui, vi, zout);
 }
 
+// the reference's visibility test |Z - zbuf| < eps: float64 for a float64 camera (t0), else a float32 difference, compared in
+// float32 when eps is a weak Python float (eps_f32)
+__device__ __forceinline__ bool visible(double z, float zb, int t0, double eps, int eps_f32) {
+    if (t0) return fabs(__dsub_rn(z, (double)zb)) < eps;
+    const float dz = fabsf(__fsub_rn((float)z, zb));
+    return eps_f32 ? dz < (float)eps : (double)dz < eps;
+}
 
 // host: validate the promotion flags and fill the kernel parameter block
 inline int fill_proj(ProjParams* P, int pts_f64, const double R[9], const double cam[3], double f, double cx, double cy, const int prec[4],

@@ -10,93 +10,57 @@
 // voxels with dword loads where the rows allow it (lanes of a wave take consecutive a2).  Under a front camera a column along a0 lands
 // on a handful of pixels, so each column keeps a run: the minimum depth (or the OR of visible bits) while its pixel stays the same,
 // flushed with one atomic when the pixel changes or the walk ends.  The run is exact: float32 min and bit OR are order-free.
+// That loop is run_walk of grid_walk.h; k_grid_depth and k_grid_visible_bits are a policy each (what a run holds and how it is flushed).
 #include "pb3d_internal.h"
 #include "grid_walk.h"
-#include "project_point.h"
 
 namespace {
 
 using namespace pb3d_proj;
-using namespace pb3d_walk;      // Walk, Colours, colour_bits, load4, flush_or and the argument checks (grid_walk.h)
+using namespace pb3d_walk;      // Walk, walk_item, Colours, colour_bits, load4, flush_or, launch_walk and the argument checks (grid_walk.h)
 
 constexpr int kMaxRows = 32;
 
-// the reference's visibility test |Z - zbuf| < eps (project.hip VisibleSink): float64 for a float64 camera, else a float32
-// difference compared in float32 when eps is a weak Python float
-__device__ __forceinline__ bool visible(double z, float zb, int t0, double eps, int eps_f32) {
-    if (t0) return fabs(__dsub_rn(z, (double)zb)) < eps;
-    const float dz = fabsf(__fsub_rn((float)z, zb));
-    return eps_f32 ? dz < (float)eps : (double)dz < eps;
-}
+// (a) zbits[v, u] = float32 bits of the minimum Z over the occupied voxels landing on (u, v).  Every Z is positive and finite, so a
+// run opens at +inf and the order of the bits is the order of the depths.
+struct DepthRun {
+    static constexpr int MODE = 1;
+    typedef u32 State;
+    u32* __restrict__ zbits;
+    __device__ __forceinline__ bool take(u32 v, u32* b) const { *b = 0; return v != 0; }
+    __device__ __forceinline__ void open(i64, u32* zr) const { *zr = 0x7f800000u; }
+    __device__ __forceinline__ void add(u32* zr, u32, double z) const { *zr = min(*zr, __float_as_uint((float)z)); }
+    __device__ __forceinline__ void flush(i64 px, u32 zr) const {
+        if (__hip_atomic_load(&zbits[px], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > zr) atomicMin(&zbits[px], zr);
+    }
+};
 
-__device__ __forceinline__ void flush_min(u32* __restrict__ zbits, i64 px, u32 z) {
-    if (px >= 0 && __hip_atomic_load(&zbits[px], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > z) atomicMin(&zbits[px], z);
-}
-
-// (a) zbits[v, u] = float32 bits of the minimum Z over the occupied voxels landing on (u, v)
 template <int C>
 __global__ __launch_bounds__(256) void k_grid_depth(Walk w, ProjParams P, u32* __restrict__ zbits) {
-    const i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= w.nitems) return;
-    const i64 a2 = (t % w.ngx) * 4, r = t / w.ngx, a1 = r % w.A1, a0s = (r / w.A1) * kChunk;
-    const i64 a0e = a0s + kChunk < w.A0 ? a0s + kChunk : w.A0;
-    i64 px[4] = {-1, -1, -1, -1};
-    u32 zr[4] = {0, 0, 0, 0};
-    for (i64 a0 = a0s; a0 < a0e; ++a0) {
-        u32 v[4];
-        load4<C>(w, a0, a1, a2, v);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (!v[k]) continue;
-            const double p[3] = {(double)(a2 + k), (double)a1, (double)a0};
-            int ui, vi;
-            double z;
-            if (!project_xyz<1>(P, p, &ui, &vi, &z)) continue;
-            const i64 q = (i64)vi * P.Wimg + ui;
-            const u32 zb = __float_as_uint((float)z);
-            if (q == px[k]) {
-                zr[k] = zb < zr[k] ? zb : zr[k];
-            } else {
-                flush_min(zbits, px[k], zr[k]);
-                px[k] = q; zr[k] = zb;
-            }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) flush_min(zbits, px[k], zr[k]);
+    run_walk<C>(w, P, DepthRun{zbits});
 }
 
-// (b) bits[v, u] |= (1 << k) for a visible voxel of colour k, | kAnyBit for any visible occupied voxel
+// (b) bits[v, u] |= (1 << k) for a visible voxel of colour k, | kAnyBit for any visible occupied voxel.  A run keeps its pixel's depth.
+struct VisibleRun {
+    static constexpr int MODE = 1;
+    struct State { u32 br; float zr; };
+    const float* __restrict__ zbuf;
+    double eps;
+    int eps_f32, t0;
+    const Colours& cols;
+    u32* __restrict__ bits;
+    __device__ __forceinline__ bool take(u32 v, u32* b) const { *b = v; return v != 0; }
+    __device__ __forceinline__ void open(i64 px, State* s) const { s->br = 0; s->zr = zbuf[px]; }
+    __device__ __forceinline__ void add(State* s, u32 v, double z) const {
+        if (visible(z, s->zr, t0, eps, eps_f32)) s->br |= kAnyBit | colour_bits(cols, v);
+    }
+    __device__ __forceinline__ void flush(i64 px, const State& s) const { flush_or(bits, px, s.br); }
+};
+
 template <int C>
 __global__ __launch_bounds__(256) void k_grid_visible_bits(Walk w, ProjParams P, const float* __restrict__ zbuf, double eps, int eps_f32,
                                                            Colours cols, u32* __restrict__ bits) {
-    const i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= w.nitems) return;
-    const i64 a2 = (t % w.ngx) * 4, r = t / w.ngx, a1 = r % w.A1, a0s = (r / w.A1) * kChunk;
-    const i64 a0e = a0s + kChunk < w.A0 ? a0s + kChunk : w.A0;
-    i64 px[4] = {-1, -1, -1, -1};
-    u32 br[4] = {0, 0, 0, 0};
-    float zr[4] = {0.f, 0.f, 0.f, 0.f};
-    for (i64 a0 = a0s; a0 < a0e; ++a0) {
-        u32 v[4];
-        load4<C>(w, a0, a1, a2, v);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (!v[k]) continue;
-            const double p[3] = {(double)(a2 + k), (double)a1, (double)a0};
-            int ui, vi;
-            double z;
-            if (!project_xyz<1>(P, p, &ui, &vi, &z)) continue;
-            const i64 q = (i64)vi * P.Wimg + ui;
-            if (q != px[k]) {
-                flush_or(bits, px[k], br[k]);
-                px[k] = q; br[k] = 0; zr[k] = zbuf[q];
-            }
-            if (visible(z, zr[k], P.t0, eps, eps_f32)) br[k] |= kAnyBit | colour_bits(cols, v[k]);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) flush_or(bits, px[k], br[k]);
+    run_walk<C>(w, P, VisibleRun{zbuf, eps, eps_f32, P.t0, cols, bits});
 }
 
 // (c) bits[v, u] |= 1 << list for a visible point of list `list` (blockIdx.y)
@@ -150,23 +114,7 @@ __global__ __launch_bounds__(256) void k_color_presence(const u8* __restrict__ g
     for (i64 base = wave0; base < ng; base += stride) {
         const i64 g = base + __lane_id();
         u32 v[4] = {0, 0, 0, 0};
-        if (g < ng) {
-            const u8* p = grid + g * 4 * C;
-            if (vec) {
-                if (C == 1) {
-                    const u32 x = *(const u32*)p;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) v[k] = (x >> (8 * k)) & 0xffu;
-                } else {
-                    const u32 x0 = ((const u32*)p)[0], x1 = ((const u32*)p)[1], x2 = ((const u32*)p)[2];
-                    v[0] = x0 & 0xffffffu; v[1] = (x0 >> 24) | ((x1 & 0xffffu) << 8); v[2] = (x1 >> 16) | ((x2 & 0xffu) << 16); v[3] = x2 >> 8;
-                }
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (g * 4 + k < nvox) v[k] = C == 1 ? (u32)p[k] : (u32)p[3 * k] | ((u32)p[3 * k + 1] << 8) | ((u32)p[3 * k + 2] << 16);
-            }
-        }
+        if (g < ng) load4<C>(grid + g * 4 * C, vec, g * 4, nvox, v);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const u32 cand = v[k] && v[k] != last ? v[k] : 0u;
@@ -234,6 +182,8 @@ int pb3d_grid_depth_buffer_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0,
                                const double cam[3], double f, double cx, double cy, const int prec[4], int Himg, int Wimg, float* d_zbuf) {
     PB3D_TRY(grid_args("pb3d_grid_depth_buffer", d_grid, A0, A1, A2, C));
     PB3D_REQUIRE(R && cam && prec && Himg >= 0 && Wimg >= 0, "pb3d_grid_depth_buffer: bad argument");
+    const Walk w = make_walk(d_grid, A0, A1, A2, C);
+    PB3D_TRY(walk_fits("pb3d_grid_depth_buffer", w));      // here as well as in launch_walk: refused without a context, like the rest
     PB3D_REQUIRE(ctx, "pb3d_grid_depth_buffer: null context");
     const i64 npix = (i64)Himg * Wimg;
     if (npix == 0) return PB3D_OK;
@@ -241,13 +191,8 @@ int pb3d_grid_depth_buffer_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0,
     ProjParams P;
     PB3D_TRY(fill_proj(&P, 0, R, cam, f, cx, cy, prec, Himg, Wimg));
     PB3D_HIP(hipMemsetD32Async((hipDeviceptr_t)d_zbuf, 0x7f800000, (size_t)npix, ctx->stream));   // +inf
-    const Walk w = make_walk(d_grid, A0, A1, A2, C);
     if (w.nitems == 0) return PB3D_OK;
-    const unsigned blocks = (unsigned)((w.nitems + 255) / 256);
-    if (C == 1) hipLaunchKernelGGL(k_grid_depth<1>, dim3(blocks), dim3(256), 0, ctx->stream, w, P, (u32*)d_zbuf);
-    else hipLaunchKernelGGL(k_grid_depth<3>, dim3(blocks), dim3(256), 0, ctx->stream, w, P, (u32*)d_zbuf);
-    PB3D_CHECK_LAUNCH();
-    return PB3D_OK;
+    return launch_walk("pb3d_grid_depth_buffer", ctx, w, C, k_grid_depth<1>, k_grid_depth<3>, P, (u32*)d_zbuf);
 }
 
 int pb3d_grid_visible_bits_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64_t A1, int64_t A2, int C, const uint8_t* colors,
@@ -258,6 +203,8 @@ int pb3d_grid_visible_bits_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0,
     PB3D_TRY(colour_args("pb3d_grid_visible_bits", colors, ncolors, C, &cols));
     PB3D_REQUIRE(R && cam && prec && Himg >= 0 && Wimg >= 0, "pb3d_grid_visible_bits: bad argument");
     PB3D_REQUIRE(zH == Himg && zW == Wimg, "pb3d_grid_visible_bits: zbuf is %dx%d, the image %dx%d", zH, zW, Himg, Wimg);
+    const Walk w = make_walk(d_grid, A0, A1, A2, C);
+    PB3D_TRY(walk_fits("pb3d_grid_visible_bits", w));      // as in pb3d_grid_depth_buffer_dev
     PB3D_REQUIRE(ctx, "pb3d_grid_visible_bits: null context");
     const i64 npix = (i64)Himg * Wimg;
     if (npix == 0) return PB3D_OK;
@@ -265,13 +212,8 @@ int pb3d_grid_visible_bits_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0,
     ProjParams P;
     PB3D_TRY(fill_proj(&P, 0, R, cam, f, cx, cy, prec, Himg, Wimg));
     PB3D_HIP(hipMemsetAsync(d_bits, 0, (size_t)npix * 4, ctx->stream));
-    const Walk w = make_walk(d_grid, A0, A1, A2, C);
     if (w.nitems == 0) return PB3D_OK;
-    const unsigned blocks = (unsigned)((w.nitems + 255) / 256);
-    if (C == 1) hipLaunchKernelGGL(k_grid_visible_bits<1>, dim3(blocks), dim3(256), 0, ctx->stream, w, P, d_zbuf, eps, eps_f32, cols, d_bits);
-    else hipLaunchKernelGGL(k_grid_visible_bits<3>, dim3(blocks), dim3(256), 0, ctx->stream, w, P, d_zbuf, eps, eps_f32, cols, d_bits);
-    PB3D_CHECK_LAUNCH();
-    return PB3D_OK;
+    return launch_walk("pb3d_grid_visible_bits", ctx, w, C, k_grid_visible_bits<1>, k_grid_visible_bits<3>, P, d_zbuf, eps, eps_f32, cols, d_bits);
 }
 
 int pb3d_points_visible_bits_dev(pb3d_ctx* ctx, const void* const* d_lists, const int64_t* counts, int nlists, int pts_type, const double R[9],

@@ -168,16 +168,19 @@ class IouRow(C.Structure):
     _fields_ = [("pred", vp), ("gt", vp), ("gate", vp), ("pred_bits", C.c_uint32), ("gt_bits", C.c_uint32), ("gate_bits", C.c_uint32)]
 
 
+# the camera and image size every view record starts with
+_VIEW_FIELDS = [("R", C.c_double * 9), ("cam", C.c_double * 3), ("f", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("prec", C.c_int * 4), ("Himg", C.c_int), ("Wimg", C.c_int)]
+
+
 class CarveView(C.Structure):
     """pb3d_carve_view (include/pb3d.h)"""
-    _fields_ = [("R", C.c_double * 9), ("cam", C.c_double * 3), ("f", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
-                ("prec", C.c_int * 4), ("Himg", C.c_int), ("Wimg", C.c_int), ("d_maskbits", vp)]
+    _fields_ = _VIEW_FIELDS + [("d_maskbits", vp)]
 
 
 class PaintView(C.Structure):
     """pb3d_paint_view (include/pb3d.h)"""
-    _fields_ = [("R", C.c_double * 9), ("cam", C.c_double * 3), ("f", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
-                ("prec", C.c_int * 4), ("Himg", C.c_int), ("Wimg", C.c_int), ("d_image", vp), ("d_zbuf", vp)]
+    _fields_ = _VIEW_FIELDS + [("d_image", vp), ("d_zbuf", vp)]
 
 
 PRESENCE_BYTES = 1 << 21    # PB3D_PRESENCE_BYTES: one bit per 24-bit colour

@@ -75,6 +75,43 @@ def _outside(outside):
     return int(outside == "keep")
 
 
+def _fill_view(rec, cam):
+    """the camera of a CarveView / PaintView record; returns the promotion flags"""
+    R, cp, prec = _cam(cam, np.float32)
+    rec.R[:] = R.reshape(9).tolist(); rec.cam[:] = cp.reshape(3).tolist()
+    rec.f, rec.cx, rec.cy = float(cam["f"]), float(cam["cx"]), float(cam["cy"])
+    rec.prec[:] = list(prec)
+    return prec
+
+
+def _grid_shape(voxel_grid):
+    from . import device as dev
+    grid_shape = tuple(voxel_grid.shape if isinstance(voxel_grid, dev.DeviceGrid) else np.shape(voxel_grid))
+    if len(grid_shape) not in (3, 4) or (len(grid_shape) == 4 and grid_shape[3] != 3):
+        raise ValueError("voxel_grid must be (A0,A1,A2,3) RGB or (A0,A1,A2) labels")
+    return grid_shape
+
+
+def _rewritten(voxel_grid, grid_shape, nviews, return_counts, run):
+    """The tail of perspective_carve / perspective_paint, once every argument is checked: run(d_grid, shape, d_out, d_counts) rewrites
+    the resident grid into a new buffer; the result is downloaded, or wrapped as a DeviceGrid for a DeviceGrid."""
+    from . import device as dev
+    d_g, shape, owned = _grid(voxel_grid)
+    d_out = d_cnt = None
+    try:
+        d_out = dev.DeviceBuffer(max(1, int(np.prod(shape, dtype=np.int64))))
+        d_cnt = dev.DeviceBuffer(8 * max(1, nviews)) if return_counts else None
+        run(d_g, shape, d_out, d_cnt if nviews else None)
+        counts = d_cnt.download((nviews,), np.int64) if return_counts else None
+        if isinstance(voxel_grid, dev.DeviceGrid):
+            res, d_out = dev.DeviceGrid(d_out, grid_shape), None
+        else:
+            res = d_out.download(grid_shape)
+    finally:
+        _free(d_out, d_cnt, d_g if owned else None)
+    return (res, counts) if return_counts else res
+
+
 def perspective_carve_resident(d_grid, shape, views, colors=None, outside="carve", out=None, d_removed=None):
     """pb3d_perspective_carve_resident, queued on the context's stream: nothing is downloaded and the host does not wait.
     d_grid: DeviceBuffer (or a pointer into one, DeviceBuffer.at) of the (A0, A1, A2, C) uint8 grid, shape = (A0, A1, A2, C) with
@@ -92,12 +129,8 @@ def perspective_carve_resident(d_grid, shape, views, colors=None, outside="carve
             mb = mask if isinstance(mask, _DeviceMaskBits) else _DeviceMaskBits(mask)
             if mb is not mask:
                 owned.append(mb)
-            R, cp, prec = _cam(cam, np.float32)
-            v = arr[k]
-            v.R[:] = R.reshape(9).tolist(); v.cam[:] = cp.reshape(3).tolist()
-            v.f, v.cx, v.cy = float(cam["f"]), float(cam["cx"]), float(cam["cy"])
-            v.prec[:] = list(prec)
-            v.Himg, v.Wimg, v.d_maskbits = mb.H, mb.W, mb.buf.ptr
+            _fill_view(arr[k], cam)
+            arr[k].Himg, arr[k].Wimg, arr[k].d_maskbits = mb.H, mb.W, mb.buf.ptr
         dst = d_grid if out is None else out
         _lib.check(_lib.load().pb3d_perspective_carve_resident(_lib.ctx(), _ptr(d_grid), A0, A1, A2, Cc, _lib.p_u8(tab) if ncol else None, ncol,
                                                                C.cast(arr, C.c_void_p), len(views), keep, _ptr(dst), _ptr(d_removed)))
@@ -118,7 +151,6 @@ def perspective_carve(voxel_grid, views, colors=None, outside="carve", return_co
     A view rejects a subject voxel whose pixel (project_colored_voxels' arithmetic, to the bit) is inside the image on a clear
     mask pixel; a pixel outside the image rejects with outside="carve" and accepts with outside="keep".  Views apply in order and
     the first rejection zeroes the voxel.  return_counts=True also returns the int64 (K,) array of voxels zeroed per view."""
-    from . import device as dev
     views = list(views)
     _outside(outside)       # every argument is checked before anything is uploaded
     for mask, _ in views:
@@ -126,24 +158,10 @@ def perspective_carve(voxel_grid, views, colors=None, outside="carve", return_co
             m = np.asarray(mask)
             if not (m.ndim == 2 or (m.ndim == 3 and m.shape[2] == 3)) or 0 in m.shape[:2]:
                 raise ValueError(f"a mask is a non-empty (H, W) or (H, W, 3) array, got shape {m.shape}")
-    grid_shape = tuple(voxel_grid.shape if isinstance(voxel_grid, dev.DeviceGrid) else np.shape(voxel_grid))
-    if len(grid_shape) not in (3, 4) or (len(grid_shape) == 4 and grid_shape[3] != 3):
-        raise ValueError("voxel_grid must be (A0,A1,A2,3) RGB or (A0,A1,A2) labels")
+    grid_shape = _grid_shape(voxel_grid)
     _subject_table(colors, 3 if len(grid_shape) == 4 else 1)
-    d_g, shape, owned = _grid(voxel_grid)
-    nbytes = int(np.prod(shape, dtype=np.int64))
-    d_out = dev.DeviceBuffer(max(1, nbytes))
-    d_rem = dev.DeviceBuffer(8 * max(1, len(views))) if return_counts else None
-    try:
-        perspective_carve_resident(d_g, shape, views, colors, outside, out=d_out, d_removed=d_rem if len(views) else None)
-        counts = d_rem.download((len(views),), np.int64) if return_counts else None
-        if isinstance(voxel_grid, dev.DeviceGrid):
-            res, d_out = dev.DeviceGrid(d_out, grid_shape), None
-        else:
-            res = d_out.download(grid_shape)
-    finally:
-        _free(d_out, d_rem, d_g if owned else None)
-    return (res, counts) if return_counts else res
+    return _rewritten(voxel_grid, grid_shape, len(views), return_counts, lambda d_g, shape, d_out, d_rem:
+                      perspective_carve_resident(d_g, shape, views, colors, outside, out=d_out, d_removed=d_rem))
 
 
 # ---- perspective paint -------------------------------------------------------------------------------------------------------------
@@ -208,20 +226,15 @@ def perspective_paint_resident(d_grid, shape, views, d_zbufs, colors=None, skip=
     d_zbufs = list(d_zbufs)
     if len(d_zbufs) != len(views):
         raise ValueError(f"{len(views)} views but {len(d_zbufs)} z-buffers")
-    cams = [_cam(cam, np.float32) for _, cam in views]
-    eps_f32 = max([_eps_f32(prec, eps) for _, _, prec in cams], default=0)     # read by float32 cameras only
     arr = (_lib.PaintView * max(1, len(views)))()
+    eps_f32 = max([_eps_f32(_fill_view(arr[k], cam), eps) for k, (_, cam) in enumerate(views)], default=0)     # read by float32 cameras only
     owned = []
     try:
-        for k, ((image, cam), (H, W), (R, cp, prec)) in enumerate(zip(views, sizes, cams)):
+        for k, ((image, _), (H, W)) in enumerate(zip(views, sizes)):
             im = image if isinstance(image, _DeviceImage) else _DeviceImage(image)
             if im is not image:
                 owned.append(im)
-            v = arr[k]
-            v.R[:] = R.reshape(9).tolist(); v.cam[:] = cp.reshape(3).tolist()
-            v.f, v.cx, v.cy = float(cam["f"]), float(cam["cx"]), float(cam["cy"])
-            v.prec[:] = list(prec)
-            v.Himg, v.Wimg, v.d_image, v.d_zbuf = H, W, _ptr(im.buf), _ptr(d_zbufs[k])
+            arr[k].Himg, arr[k].Wimg, arr[k].d_image, arr[k].d_zbuf = H, W, _ptr(im.buf), _ptr(d_zbufs[k])
         dst = d_grid if out is None else out
         _lib.check(_lib.load().pb3d_perspective_paint_resident(_lib.ctx(), _ptr(d_grid), A0, A1, A2, Cc, _lib.p_u8(tab) if ncol else None, ncol,
                                                                C.cast(arr, C.c_void_p), len(views), _lib.p_u8(sk) if len(sk) else None, len(sk),
@@ -247,9 +260,7 @@ def perspective_paint(voxel_grid, views, colors=None, skip=(), eps=1e-3, zbufs=N
     neither black nor in skip.  Views are tried in order, the first that paints a voxel decides its colour, a voxel no view paints
     keeps its own.  return_counts=True also returns the int64 (K,) array of voxels decided per view."""
     from . import device as dev
-    grid_shape = tuple(voxel_grid.shape if isinstance(voxel_grid, dev.DeviceGrid) else np.shape(voxel_grid))
-    if len(grid_shape) not in (3, 4) or (len(grid_shape) == 4 and grid_shape[3] != 3):
-        raise ValueError("voxel_grid must be (A0,A1,A2,3) RGB or (A0,A1,A2) labels")
+    grid_shape = _grid_shape(voxel_grid)
     views, sizes, _, _, _ = _paint_args(3 if len(grid_shape) == 4 else 1, views, colors, skip)      # every argument is checked before anything is uploaded
     for _, cam in views:
         _cam(cam, np.float32)
@@ -265,26 +276,19 @@ def perspective_paint(voxel_grid, views, colors=None, skip=(), eps=1e-3, zbufs=N
                     raise ValueError(f"the z-buffer of view {k} is {host_z[k].shape}, its image {hw}")
             elif zb.nbytes != 4 * hw[0] * hw[1]:
                 raise ValueError(f"the z-buffer of view {k} holds {zb.nbytes} bytes, its {hw[0]} x {hw[1]} image needs {4 * hw[0] * hw[1]}")
-    d_g, shape, owned = _grid(voxel_grid)
-    nbytes = int(np.prod(shape, dtype=np.int64))
-    d_out = d_cnt = None
-    mine = []
-    try:
-        d_out = dev.DeviceBuffer(max(1, nbytes))
-        d_cnt = dev.DeviceBuffer(8 * max(1, len(views))) if return_counts else None
-        d_z = []
-        for k, ((_, cam), (H, W)) in enumerate(zip(views, sizes)):
-            if zbufs is None:
-                mine.append(depth_buffer_resident(d_g, shape, cam, H, W))
-            elif host_z[k] is not None:
-                mine.append(dev.from_numpy_async(host_z[k]))
-            d_z.append(mine[-1] if zbufs is None or host_z[k] is not None else zbufs[k])
-        perspective_paint_resident(d_g, shape, views, d_z, colors, skip, eps, out=d_out, d_painted=d_cnt if len(views) else None)
-        counts = d_cnt.download((len(views),), np.int64) if return_counts else None
-        if isinstance(voxel_grid, dev.DeviceGrid):
-            res, d_out = dev.DeviceGrid(d_out, grid_shape), None
-        else:
-            res = d_out.download(grid_shape)
-    finally:
-        _free(d_out, d_cnt, d_g if owned else None, *mine)
-    return (res, counts) if return_counts else res
+
+    def paint(d_g, shape, d_out, d_cnt):
+        mine = []
+        try:
+            d_z = []
+            for k, ((_, cam), (H, W)) in enumerate(zip(views, sizes)):
+                if zbufs is None:
+                    mine.append(depth_buffer_resident(d_g, shape, cam, H, W))
+                elif host_z[k] is not None:
+                    mine.append(dev.from_numpy_async(host_z[k]))
+                d_z.append(mine[-1] if zbufs is None or host_z[k] is not None else zbufs[k])
+            perspective_paint_resident(d_g, shape, views, d_z, colors, skip, eps, out=d_out, d_painted=d_cnt)
+        finally:
+            _free(*mine)        # the context's pool hands a freed block out again only behind this stream's work
+
+    return _rewritten(voxel_grid, grid_shape, len(views), return_counts, paint)

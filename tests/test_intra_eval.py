@@ -252,6 +252,10 @@ def test_cabi_refuses_bad_arguments():
     assert "black" in _err(lib)
     assert lib.pb3d_grid_visible_bits_dev(None, fake, 4, 4, 4, 3, L.p_u8(cols), 2, *args, fake, 4, 4, 4, 4, 1e-3, 1, fake) == -1
     assert "null context" in _err(lib)
+    big = (64, 1 << 20, 1 << 22)        # 2^40 walk items: more than 2^31 blocks of 256, refused by the shape alone
+    assert lib.pb3d_grid_depth_buffer_dev(None, fake, *big, 3, *args, 4, 4, fake) == -1 and "too large" in _err(lib)
+    assert lib.pb3d_grid_visible_bits_dev(None, fake, *big, 3, L.p_u8(cols), 2, *args, fake, 4, 4, 4, 4, 1e-3, 1, fake) == -1
+    assert "too large" in _err(lib)
     ptrs = (C.c_void_p * 32)(*([16] * 32)); counts = np.ones(32, np.int64)
     assert lib.pb3d_points_visible_bits_dev(None, ptrs, counts.ctypes.data_as(L.i64p), 32, 2, *args, fake, 4, 4, 4, 4, 1e-3, 0, fake) == -1
     assert "at most 31 point lists" in _err(lib)

@@ -43,7 +43,7 @@ What the kernels need, per pointer argument, from reading them (csrc/ = part-bas
                     bytes are stored element by element; mesh_colors reads float32 verts by element.
   extrude, recolor_components, count_nonzero, partwise_iou, label_colors_conn_stats, color_presence
                     byte (grid) and element-typed (int32 labels, uint32 bitmap, int64 counters) accesses only; color_presence
-                    reads dwords only behind visibility.hip:395.  k_extrude_x's 4-byte voxel load uses an align-1 type.
+                    reads dwords only behind pb3d_color_presence_dev's `vec` test.  k_extrude_x's 4-byte voxel load uses an align-1 type.
 """
 import ctypes as C
 import os
@@ -101,7 +101,7 @@ CASES = {
     "pb3d_extrude_dev": ("test_extrude", [("21x13x18", "grid, valid, out; in place", "components.hip:724-746 (bytes, align-1 voxel load)")]),
     "pb3d_count_nonzero_dev": ("test_count_nonzero_partwise_iou", [("n 4099", "bytes; count +8 / +24", "components.hip:486")]),
     "pb3d_partwise_iou_dev": ("test_count_nonzero_partwise_iou", [("40x30", "a, b", "project.hip:433")]),
-    "pb3d_color_presence_dev": ("test_color_presence", [("nvox 4096, 4099", "grid; bitmap +4 / +12; present +8 / +24", "visibility.hip:395 dword <-> byte reads")]),
+    "pb3d_color_presence_dev": ("test_color_presence", [("nvox 4096, 4099", "grid; bitmap +4 / +12; present +8 / +24", "pb3d_color_presence_dev's `vec` test: dword <-> byte reads")]),
     "pb3d_recolor_components_dev": ("test_labelling_and_recolor", [("24x10x27", "labels +4 / +12; grid", "components.hip:127")]),
     "pb3d_top_k_components_dev": ("test_top_k_components", [("20x24x45, k = 1, 4, -1", "grid in place; labels +4 / +12; status +8", "components.hip:658; ccl.hip:108 (align-1 grid reads), components.hip:144 k_recolor_bits")]),
     "pb3d_component_members_dev": ("test_component_members", [("12x10x27, three selections, all outputs", "grid; labels +4 / +12; coords +8 / +24; rows +8; masks +1 / +4 / +16", "members.hip:63,119 (bytes, int32 / int64 by element, 8-byte atomics on d_rows)")]),
