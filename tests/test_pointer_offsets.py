@@ -41,6 +41,11 @@ What the kernels need, per pointer argument, from reading them (csrc/ = part-bas
   component_members grid bytes, int32 labels and int64 coordinates by element, 8-byte atomics on d_rows (int64 aligned), mask bytes.
   mesh              k_mesh_bits reads grid bytes into a scratch bitmask; verts / normals (float32), faces (int32) and the colour
                     bytes are stored element by element; mesh_colors reads float32 verts by element.
+  guided_carve      (all four entries) k_crop_slice loads a voxel's three bytes as ONE dword through an align-1 type and switches to
+                    byte loads by `v + 4 <= vol_end` (guided.hip:73): an address-keyed path at the volume's last voxel.  The scene's
+                    large box ends there, so that voxel sits against the rear guard.  k_crop_chain clears single bytes in place; int32
+                    labels by element (members only: the rest of the arena keeps its fill), the membership bits are scratch, the
+                    queued entry's counts are 8-byte atomics on d_counts (int64 aligned).
   extrude, recolor_components, count_nonzero, partwise_iou, label_colors_conn_stats, color_presence
                     byte (grid) and element-typed (int32 labels, uint32 bitmap, int64 counters) accesses only; color_presence
                     reads dwords only behind pb3d_color_presence_dev's `vec` test.  k_extrude_x's 4-byte voxel load uses an align-1 type.
@@ -109,6 +114,10 @@ CASES = {
     "pb3d_mesh_fill_dev": ("test_mesh", [("13x11x9 stride 1, 17x19x16 stride 2", "grid; verts / faces / normals +4 / +12; cols +1 / +2 / +3", "mesh.hip:497-507 (float32 / int32 by element)")]),
     "pb3d_mesh_colors_dev": ("test_mesh", [("13x11x9 stride 1, 17x19x16 stride 2", "grid; verts +4 / +12; cols +1 / +3", "mesh.hip:314 k_mesh_colors")]),
     "pb3d_label_colors_conn_stats_dev": ("test_labelling_and_recolor", [("24x10x27, 6 and 26 neighbours", "grid +1 / +4; labels +4 / +12", "ccl.hip (bytes, int32 labels)")]),
+    "pb3d_guided_carve_dev": ("test_guided_carve", [("21x37x19 C=3, box ends at the last voxel", "grid in place; labels +4 / +12", "guided.hip:73 dword load <-> byte loads at the volume's last voxel")]),
+    "pb3d_guided_carve_label_dev": ("test_guided_carve", [("21x37x19 C=1, box ends at the last voxel", "grid in place; labels +4 / +12", "guided.hip:72 byte loads, :201 one-byte clears")]),
+    "pb3d_guided_carve_color_dev": ("test_guided_carve", [("21x37x19 C=3,1, colour index 0", "grid in place; labels +4 / +12", "guided.hip:73; the membership bits of a labelling made on the offset grid")]),
+    "pb3d_guided_carve_queue_dev": ("test_guided_carve", [("21x37x19 C=3,1, colour index 0", "grid in place; labels +4 / +12; counts +8 / +24", "guided.hip:73; guided.hip:216 64-bit atomics on d_counts")]),
 }
 
 # every other *_dev entry, and why it is not in the table
@@ -147,10 +156,6 @@ EXEMPT = {
     "pb3d_crop_occupancy_label_dev": "byte accesses into a crop box (components.hip k_crop_occ); no address-keyed path",
     "pb3d_component_paste_dev": "byte accesses into a crop box (components.hip k_comp_paste); no address-keyed path",
     "pb3d_component_paste_label_dev": "byte accesses into a crop box (components.hip k_comp_paste); no address-keyed path",
-    "pb3d_guided_carve_dev": "works in place on crops of the grid through LDS-resident slices (guided.hip); byte accesses to the grid",
-    "pb3d_guided_carve_color_dev": "as pb3d_guided_carve_dev",
-    "pb3d_guided_carve_queue_dev": "as pb3d_guided_carve_dev",
-    "pb3d_guided_carve_label_dev": "as pb3d_guided_carve_dev",
     "pb3d_recolor_backward_dev": "labelling of ccl.hip (in the table) + k_recolor_bits: byte stores, int32 labels by element",
     "pb3d_recolor_last_labelled_dev": "k_recolor_bits: byte stores, int32 labels by element (components.hip)",
     "pb3d_recolor_components_label_dev": "pb3d_recolor_components_dev with one channel (same kernel, in the table)",
@@ -222,8 +227,8 @@ class Run:
         self.ins.append(ar)
         return ar.ptr
 
-    def out(self, nbytes, off, init=None):
-        ar = Arena(self.pb3d, nbytes, off, OUT_FILL, init)
+    def out(self, nbytes, off, init=None, fill=OUT_FILL):
+        ar = Arena(self.pb3d, nbytes, off, fill, init)
         self.outs.append(ar)
         return ar
 
@@ -240,8 +245,8 @@ class Run:
             for i, ar in enumerate(self.outs):
                 got = ar.download()
                 lo, hi = GUARD + ar.off, GUARD + ar.off + ar.n
-                assert (got[:lo] == OUT_FILL).all(), (self.what, "front guard of output", i, "touched at", int(np.flatnonzero(got[:lo] != OUT_FILL)[0]) - lo)
-                assert (got[hi:] == OUT_FILL).all(), (self.what, "rear guard of output", i, "touched at +", int(np.flatnonzero(got[hi:] != OUT_FILL)[0]))
+                assert (got[:lo] == ar.fill).all(), (self.what, "front guard of output", i, "touched at", int(np.flatnonzero(got[:lo] != ar.fill)[0]) - lo)
+                assert (got[hi:] == ar.fill).all(), (self.what, "rear guard of output", i, "touched at +", int(np.flatnonzero(got[hi:] != ar.fill)[0]))
                 pay = got[lo:hi]
                 if written is not None and i in written:
                     keep = np.ones(ar.n, bool)
@@ -893,3 +898,61 @@ def test_mesh(pb3d_gpu):
             dc = r.out(len(rv) * 3, oc)
             r.ok(r.lib.pb3d_mesh_colors_dev(r.ctx, r.inp(grid, og), A0, A1, A2, 3, stride, r.inp(rv, ov), len(rv), dc.ptr))
             check_colors(grid, stride, rv, mesh_colors(r.finish()[0].reshape(-1, 3)), rc)
+
+
+# =====================================================================================================================
+# the fused component loop of left_right_guided_carve
+# =====================================================================================================================
+
+@gpu
+def test_guided_carve(pb3d_gpu, oracle):
+    """label (members only, as the package does) and carve in place on a grid at every byte offset; the scene's large box ends at the
+    volume's last voxel, so k_crop_slice's dword load of the voxel before it and its byte loads of the last one sit against the guard"""
+    import contextlib
+    import io
+    import guided_scenes as gs
+    L = pb3d_gpu._lib
+    sc = gs.scene("corner_small")
+    W, H, D = sc.shape
+    nvox, n, angle, cap = W * H * D, len(sc.boxes), 45, 64
+    buf = io.StringIO()
+    with contextlib.redirect_stdout(buf):
+        want3 = oracle.left_right_guided_carve(sc.grid, sc.sem, sc.color, angle=angle)
+    counts = np.array([int(v) for v in re.findall(r"carved voxels: (\d+)", buf.getvalue())], np.int64)
+    assert len(counts) == n and not np.array_equal(want3, sc.grid)
+    pal = np.ascontiguousarray(np.stack([gs.COLOR, gs.FOREIGN]))
+    grid1, want1 = to_label(sc.grid, pal), to_label(want3, pal)
+    masks, offs = gs.crop_masks(sc.sem, sc.color, sc.boxes)
+    bb = np.ascontiguousarray(sc.boxes)
+    i64 = lambda a: a.ctypes.data_as(L.i64p)
+    lab_offs = [(0, 0)] + [(k, (4, 12)[i % 2]) for i, k in enumerate(BYTE_OFFS)]
+    for ch, grid, want in ((3, sc.grid, want3), (1, grid1, want1)):
+        for entry in ("plain", "color", "queue"):
+            for og, ol in lab_offs:
+                r = Run(pb3d_gpu, ("guided_carve", ch, entry, og, ol))
+                g, lab = r.out(grid.nbytes, og, init=grid, fill=IN_FILL), r.out(nvox * 4, ol)         # (the grid is read too: dirty 0xff slack)
+                nc = (C.c_int64 * 1)(); ok = (C.c_int * 1)()
+                bbox = np.zeros((cap, 6), np.int64); cnt = np.zeros(cap, np.int64); sums = np.zeros((cap, 3), np.int64)
+                if ch == 3:
+                    r.ok(r.lib.pb3d_label_color_stats_dev(r.ctx, g.ptr, W, H, D, L.p_u8(pal[0]), lab.ptr, nc, cap, 1, i64(bbox), i64(cnt), i64(sums), ok))
+                else:
+                    r.ok(r.lib.pb3d_label_value_stats_dev(r.ctx, g.ptr, W, H, D, 1, lab.ptr, nc, cap, 1, i64(bbox), i64(cnt), i64(sums), ok))
+                assert nc[0] == n and ok[0] == 1 and np.array_equal(bbox[:n], bb), r.what
+                cn = np.full(n, -1, np.int64)
+                took = C.c_int(-1)
+                tail = (n, i64(bb), L.p_u8(masks), i64(offs), masks.size, angle)
+                if entry == "plain":
+                    fn = r.lib.pb3d_guided_carve_dev if ch == 3 else r.lib.pb3d_guided_carve_label_dev
+                    r.ok(fn(r.ctx, g.ptr, lab.ptr, W, H, D, *tail, i64(cn), C.byref(took)))
+                elif entry == "color":
+                    r.ok(r.lib.pb3d_guided_carve_color_dev(r.ctx, g.ptr, lab.ptr, 0, ch, W, H, D, *tail, i64(cn), C.byref(took)))
+                else:
+                    dc = r.out(8 * n, (8, 24)[ol % 8 == 4], init=np.full(n, -3, np.int64))
+                    r.ok(r.lib.pb3d_guided_carve_queue_dev(r.ctx, g.ptr, lab.ptr, 0, ch, W, H, D, *tail, dc.ptr, C.byref(took)))
+                assert took.value == 1, r.what
+                outs = r.finish()
+                same(outs[0], want, r.what)
+                if entry == "queue":
+                    same(outs[2], counts, r.what)
+                else:
+                    assert np.array_equal(cn, counts), r.what
