@@ -379,6 +379,32 @@ int pb3d_icp_index_resident(pb3d_ctx* ctx, const void* d_tgt, int tgt_f64, int64
 int pb3d_icp_step_resident(pb3d_ctx* ctx, const void* d_src, int src_f64, int64_t ns, const void* d_tgt, int tgt_f64, int64_t nt,
                            const double T[12], double max_dist2, const double cp[3], const double cq[3], void* d_out);
 
+/* ---- exact k-th smallest of a resident float64 list, and the trimmed ICP step built on it -----------------------------------------
+ * kth_smallest: *d_out (one float64 on the device) = the element at 0-based position `rank` of the n values of d_vals (8-byte aligned)
+ *   sorted by IEEE totalOrder, i.e. by the unsigned key  key = bits ^ (bits >> 63 ? ~0ull : 1ull << 63):
+ *     negatives < -0.0 < +0.0 < positives < +inf < NaNs with a clear sign bit   (NaNs with the sign bit set sort below -inf).
+ *   The result has the exact bytes of an input element.  1 <= n <= 2^31 - 1 and 0 <= rank < n, else PB3D_EINVAL.  Enqueued without a
+ *   host wait.  A radix selection over the keys with integer counters only: two calls on the same input give the same bytes.
+ * icp_step_trimmed: pb3d_icp_step_resident with an order statistic between the search and the sums.  Everything stated there holds
+ *   unchanged (the index and its refusals, p = T s, j, d2, no FMA, the summation order, no host wait).  trim_fraction rho must be
+ *   finite with 0 < rho <= 1, else PB3D_EINVAL.  On top of that:
+ *     a pair is a CANDIDATE when p is finite (so j is valid) and (max_dist2 < 0 or d2 <= max_dist2);  m = the number of candidates.
+ *       (The search pairs a p with an infinite coordinate at d2 = +inf, which icp_step leaves to its gate; here it is no candidate.)
+ *     k = (rho >= 1.0) ? m : min(m, (int64)ceil(rho * (double)m))    -- one rounded float64 product, then ceil; on the device from m;
+ *     tau = the k-th smallest candidate d2 (rank k - 1 of kth_smallest; a pair that is no candidate enters the selection as the quiet
+ *       NaN 0x7FF8000000000000, which sorts above every candidate, +inf included);  m = 0: tau = +0.0;
+ *     a pair is USED when it is a candidate and d2 <= tau: every pair tied at tau is used, so count >= k (no tie-break by index);
+ *     a used pair contributes 1 to the count, the 16 terms of icp_step and a 17th, (P0*P0 + P1*P1) + P2*P2 with P = p - cp; any other
+ *     pair contributes 0 and +0.0 seventeen times.  Rows of 17 sums, reduced in the order stated for icp_step.
+ *   d_out (20 x 8 bytes on the device): the int64 count, the 17 float64 sums, the int64 m, the float64 tau.
+ *   ns = 0: twenty zero words (no index needed).  nt = 0 with ns > 0 is PB3D_EINVAL.
+ *   With rho = 1 the count, m and the first 16 sums are the bytes of pb3d_icp_step_resident on the same input, and tau is the largest
+ *   candidate d2. */
+int pb3d_kth_smallest_resident(pb3d_ctx* ctx, const double* d_vals, int64_t n, int64_t rank, double* d_out);
+int pb3d_icp_step_trimmed_resident(pb3d_ctx* ctx, const void* d_src, int src_f64, int64_t ns, const void* d_tgt, int tgt_f64, int64_t nt,
+                                   const double T[12], double max_dist2, double trim_fraction, const double cp[3], const double cq[3],
+                                   void* d_out /* 20 x 8 bytes */);
+
 /* ---- facade plane, box crop and the pieces of the four-way completion: steps 2-4 of the inter-method preprocessing (reference
  * results/4.Inter-method_3D/README.md; its utils/preprocess_helpers.py is not shipped, so the arithmetic below is the specification) --
  * Point lists as for ICP: (n, 3) rows of float32 (*_f64 = 0) or float64 (1), n <= 2^31 - 1.  All arithmetic is float64 after widening,

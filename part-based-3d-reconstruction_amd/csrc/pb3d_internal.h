@@ -156,8 +156,12 @@ enum pb3d_slot : int {
     PB3D_SLOT_CROP_OFFSETS = 78,
     PB3D_SLOT_CROP_SCAN_LOCAL = 79,
     PB3D_SLOT_CROP_SCAN_SEGS = 80,
+    // call-local, csrc/select.hip: the state (prefix, remaining rank) and the eight digit histograms of a k-th selection
+    PB3D_SLOT_SELECT = 81,
+    // call-local, csrc/icp.hip: a trimmed step's header (candidate count, rank, tau) and the selection keys of its pairs
+    PB3D_SLOT_ICP_KEYS = 82,
 
-    PB3D_SLOT_COUNT = 81
+    PB3D_SLOT_COUNT = 83
 };
 
 // ---- the cell index of the exact nearest-neighbour search (csrc/nn.hip) -----------------------------------
@@ -392,6 +396,9 @@ int pb3d_scan_counts(pb3d_ctx* ctx, const u32* d_counts, i64 n, i64* d_offsets, 
 int pb3d_nn_index_build(pb3d_ctx* ctx, const void* d_r, int r_f64, i64 nr, pb3d_slot starts_slot, pb3d_slot coords_slot, pb3d_slot ids_slot,
                         pb3d_nn_index* ix);
 int pb3d_nn_index_nearest(pb3d_ctx* ctx, const pb3d_nn_index& ix, const double* d_q, i64 nq, int* d_idx);
+// csrc/select.hip for csrc/icp.hip: pb3d_kth_smallest_resident with the rank read from device memory when the selection runs
+// (0 <= *d_rank < n; 1 <= n <= 2^31 - 1; enqueued)
+int pb3d_select_kth(pb3d_ctx* ctx, const double* d_vals, i64 n, const i64* d_rank, double* d_out);
 // process_voxel_grid through the bit-sliced chain (csrc/sliced.hip); *took = 0: not applicable, nothing written
 int pb3d_process_grid_sliced(pb3d_ctx* ctx, const u8* d_occ, i64 W, i64 H, i64 D, const u8* d_mask_wh, int angle_interval, u8* d_out,
                              int known_binary, int* took);

@@ -5,7 +5,7 @@ utils.projection_utils, utils.camera_geometry, utils.camera_estimation.compute_p
 minaret extraction, the notebook-4 and inter-method evaluations, utils.config) on top of libpb3d.so.  `install()` rebinds those names inside an imported
 reference `utils` package so notebooks 1-3 run unchanged.
 """
-from . import _hostmem, _lib, device, dist, formats, labels, perspective  # noqa: F401
+from . import _hostmem, _lib, device, dist, formats, labels, perspective, selection  # noqa: F401
 from .formats import load_camera_params, load_voxel_grid, save_camera_params, save_voxel_grid  # noqa: F401
 from .labels import (Palette, extrude_from_surface_labels, get_voxel_points_by_parts_labels, global_carve_labels, label_to_rgb,  # noqa: F401
                      left_right_guided_carve_labels, part_carve_labels, partwise_carve_labels, recolor_backward_components_labels, rgb_to_label,
@@ -22,6 +22,8 @@ from .eval_helpers import (compute_surface_metrics, compute_triangle_normals, co
 from .eval_helpers import density_grid_resident, pointcloud_to_voxel_grid  # noqa: F401
 from .preprocess_helpers import (best_fit_transform_from_sums, flip_y_axis, icp_align, icp_align_resident, normalize_preserve_aspect,  # noqa: F401
                                  transform_points, transform_points_resident)
+from .preprocess_helpers import best_fit_similarity_from_sums, icp_step_trimmed_resident  # noqa: F401
+from .selection import kth_smallest, kth_smallest_resident  # noqa: F401
 from .preprocess_helpers import (crop_to_box, crop_to_box_resident, fit_plane_ransac, fit_plane_ransac_resident,  # noqa: F401
                                  plane_alignment_transform, plane_from_moments, plane_hypotheses_resident, plane_moments_resident,
                                  plane_score_resident, symmetric_completion, symmetric_completion_resident)

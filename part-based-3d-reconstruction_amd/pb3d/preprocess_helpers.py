@@ -11,7 +11,9 @@ rigid point-to-point ICP with both clouds resident on the device.  There is no u
 arithmetic to the bit: per iteration the device transforms the source, finds every point's exact nearest target point against an
 index built once per alignment (csrc/icp.hip on the search of csrc/nn.hip, ties to the lowest index) and reduces the pairs to a
 count and 16 float64 sums in a fixed order; the host downloads those 17 values, solves the 3 x 3 problem
-(best_fit_transform_from_sums) and composes the transform.
+(best_fit_transform_from_sums) and composes the transform.  With trim_fraction the device also finds, per iteration and without a host
+wait, the exact k-th smallest pair distance (csrc/select.hip) and sums only the pairs up to it; with with_scale the host solve
+estimates Umeyama's scale from one more sum (best_fit_similarity_from_sums).
 
 crop_to_box, fit_plane_ransac + plane_alignment_transform and symmetric_completion are steps 2-4 of the same README: crop the dense
 cloud to the sparse cloud's box, estimate the dominant facade plane and turn it onto the Z axis, and the naive four-way completion.
@@ -27,7 +29,8 @@ import numpy as np
 from . import _lib
 
 __all__ = ["normalize_preserve_aspect", "flip_y_axis", "transform_points", "transform_points_resident", "best_fit_transform_from_sums",
-           "icp_align", "icp_align_resident", "icp_index_resident", "icp_step_resident", "plane_hypotheses_resident", "plane_score_resident",
+           "best_fit_similarity_from_sums", "icp_align", "icp_align_resident", "icp_index_resident", "icp_step_resident",
+           "icp_step_trimmed_resident", "plane_hypotheses_resident", "plane_score_resident",
            "plane_moments_resident", "crop_to_box_resident", "plane_from_moments", "fit_plane_ransac", "fit_plane_ransac_resident",
            "plane_alignment_transform", "crop_to_box", "symmetric_completion", "symmetric_completion_resident"]
 
@@ -135,6 +138,39 @@ def best_fit_transform_from_sums(count, sums, cp, cq):
     return M
 
 
+def best_fit_similarity_from_sums(count, sums, cp, cq, with_scale=True):
+    """The 4 x 4 similarity transform (upper 3 x 3 = s R, R a rotation of determinant +1, s > 0: Umeyama's estimate) that best maps the
+    used source points onto their partners, from the count and the 17 sums of a trimmed step: the 16 of best_fit_transform_from_sums
+    and sums[16] = sum |p - cp|^2.  H, its SVD, d and R are the rigid solve's;
+        var = sums[16] - ((Sp0*Sp0 + Sp1*Sp1) + Sp2*Sp2) / count,   s = ((S0 + S1) + d*S2) / var,   t = (Sq/count + cq) - s R (Sp/count + cp).
+    with_scale=False: exactly best_fit_transform_from_sums(count, sums[:16], cp, cq)."""
+    sums = np.asarray(sums, np.float64).reshape(17)
+    if not with_scale:
+        return best_fit_transform_from_sums(count, sums[:16], cp, cq)
+    count = int(count)
+    cp = np.asarray(cp, np.float64).reshape(3)
+    cq = np.asarray(cq, np.float64).reshape(3)
+    if count < 3:
+        raise ValueError(f"a similarity fit needs at least 3 point pairs (got {count})")
+    Sp, Sq, Spq = sums[0:3], sums[3:6], sums[6:15].reshape(3, 3)
+    H = Spq - np.outer(Sp, Sq) / count
+    U, S, Vt = np.linalg.svd(H)
+    d = np.sign(np.linalg.det(Vt.T @ U.T))
+    R = Vt.T @ np.diag([1.0, 1.0, d]) @ U.T
+    var = sums[16] - ((Sp[0] * Sp[0] + Sp[1] * Sp[1]) + Sp[2] * Sp[2]) / count
+    if not (math.isfinite(var) and var > 0.0):
+        raise ValueError(f"a similarity fit needs source points that are not all equal (their summed squared spread is {var})")
+    s = ((S[0] + S[1]) + d * S[2]) / var
+    if not (math.isfinite(s) and s > 0.0):
+        raise ValueError(f"the similarity fit found no positive finite scale (got {s})")
+    A = s * R
+    t = (Sq / count + cq) - A @ (Sp / count + cp)
+    M = np.eye(4)
+    M[:3, :3] = A
+    M[:3, 3] = t
+    return M
+
+
 def icp_index_resident(d_target, nt, f64=True):
     """pb3d_icp_index_resident: bin the resident (nt, 3) target for the steps that follow; returns its exact box (min 3, max 3)"""
     b = np.zeros(6, np.float64)
@@ -153,6 +189,35 @@ def icp_step_resident(d_source, ns, d_target, nt, T, max_dist2, cp, cq, s_f64=Tr
     _lib.check(_lib.load().pb3d_icp_step_resident(_lib.ctx(), _ptr(d_source), int(bool(s_f64)), int(ns), _ptr(d_target), int(bool(t_f64)),
                                                   int(nt), _lib.p_dbl(t), float(max_dist2), _lib.p_dbl(cp), _lib.p_dbl(cq), _ptr(d_out)))
     return d_out
+
+
+def icp_step_trimmed_resident(d_source, ns, d_target, nt, T, max_dist2, trim_fraction, cp, cq, s_f64=True, t_f64=True, out=None):
+    """pb3d_icp_step_trimmed_resident: a DeviceBuffer of 20 x 8 bytes -- the int64 count of used pairs, 17 float64 sums (the 16 of
+    icp_step_resident and sum |p - cp|^2), the int64 number of candidate pairs m and the float64 tau, the k-th smallest candidate
+    squared distance with k = ceil(trim_fraction * m): the pairs with d2 <= tau are used.  The 4 x 4 (or 3 x 4) T need not be rigid."""
+    from . import device as dev
+    t = _t12(np.asarray(T, np.float64))
+    cp = np.ascontiguousarray(cp, dtype=np.float64).reshape(3)
+    cq = np.ascontiguousarray(cq, dtype=np.float64).reshape(3)
+    d_out = out if out is not None else dev.DeviceBuffer(20 * 8)
+    _lib.check(_lib.load().pb3d_icp_step_trimmed_resident(_lib.ctx(), _ptr(d_source), int(bool(s_f64)), int(ns), _ptr(d_target),
+                                                          int(bool(t_f64)), int(nt), _lib.p_dbl(t), float(max_dist2), float(trim_fraction),
+                                                          _lib.p_dbl(cp), _lib.p_dbl(cq), _ptr(d_out)))
+    return d_out
+
+
+def _trim_args(trim_fraction, with_scale):
+    """(rho or None, with_scale): both defaults -> (None, False), today's path"""
+    if not isinstance(with_scale, (bool, np.bool_)):
+        raise ValueError(f"with_scale must be a bool (got {with_scale!r})")
+    if trim_fraction is None:
+        return None, bool(with_scale)
+    if isinstance(trim_fraction, (bool, np.bool_)) or not isinstance(trim_fraction, (int, float, np.integer, np.floating)):
+        raise ValueError(f"trim_fraction must be a real number in (0, 1], or None (got {trim_fraction!r})")
+    rho = float(trim_fraction)
+    if not (0.0 < rho <= 1.0):
+        raise ValueError(f"trim_fraction must be in (0, 1], or None (got {trim_fraction})")
+    return rho, bool(with_scale)
 
 
 def _icp_args(ns, nt, max_iterations, tolerance, max_distance, init):
@@ -177,25 +242,36 @@ def _icp_args(ns, nt, max_iterations, tolerance, max_distance, init):
 
 
 def icp_align_resident(d_source, ns, d_target, nt, max_iterations=50, tolerance=1e-9, max_distance=None, init=None, return_history=False,
-                       s_f64=True, t_f64=True):
+                       s_f64=True, t_f64=True, trim_fraction=None, with_scale=False):
     """icp_align on resident (ns, 3) / (nt, 3) lists (DeviceBuffers; float64 rows, or float32 with s_f64 / t_f64 False).  The target
-    is binned once; every iteration enqueues one step and downloads its 17 values."""
+    is binned once; every iteration enqueues one step and downloads its 17 values (20 with trim_fraction or with_scale: the trimmed
+    step, whose history entries are (count, rmse, candidates, tau))."""
     from . import device as dev
     max_iterations, tolerance, md2, T = _icp_args(int(ns), int(nt), max_iterations, tolerance, max_distance, init)
+    rho, with_scale = _trim_args(trim_fraction, with_scale)
+    trimmed = rho is not None or with_scale
     box = icp_index_resident(d_target, nt, t_f64)               # the only index build of the alignment
     c = 0.5 * (box[:3] + box[3:])
-    d_out = dev.DeviceBuffer(17 * 8)
+    words = 20 if trimmed else 17
+    d_out = dev.DeviceBuffer(words * 8)
     history, Ts, prev = [], [], None
     try:
         for _ in range(max_iterations):
-            icp_step_resident(d_source, ns, d_target, nt, T, md2, c, c, s_f64, t_f64, out=d_out)
-            raw = d_out.download((17,), np.float64)
-            count, sums = int(raw[:1].view(np.int64)[0]), raw[1:]
+            if trimmed:
+                icp_step_trimmed_resident(d_source, ns, d_target, nt, T, md2, 1.0 if rho is None else rho, c, c, s_f64, t_f64, out=d_out)
+            else:
+                icp_step_resident(d_source, ns, d_target, nt, T, md2, c, c, s_f64, t_f64, out=d_out)
+            raw = d_out.download((words,), np.float64)
+            count, sums = int(raw[:1].view(np.int64)[0]), raw[1:words - 2] if trimmed else raw[1:]
             if count < 3:
                 raise ValueError(f"icp_align: only {count} point pairs within max_distance (a rigid fit needs 3)")
             rmse = math.sqrt(sums[15] / count)
-            T = best_fit_transform_from_sums(count, sums, c, c) @ T
-            history.append((count, rmse))
+            if trimmed:
+                T = best_fit_similarity_from_sums(count, sums, c, c, with_scale) @ T
+                history.append((count, rmse, int(raw[18:19].view(np.int64)[0]), float(raw[19])))
+            else:
+                T = best_fit_transform_from_sums(count, sums, c, c) @ T
+                history.append((count, rmse))
             Ts.append(T)
             if prev is not None and abs(prev - rmse) < tolerance:
                 break
@@ -205,7 +281,8 @@ def icp_align_resident(d_source, ns, d_target, nt, max_iterations=50, tolerance=
     return (T, history, Ts) if return_history else T
 
 
-def icp_align(source, target, max_iterations=50, tolerance=1e-9, max_distance=None, init=None, return_history=False):
+def icp_align(source, target, max_iterations=50, tolerance=1e-9, max_distance=None, init=None, return_history=False, trim_fraction=None,
+              with_scale=False):
     """Rigid point-to-point ICP: the float64 4 x 4 T that moves `source` onto `target` (transform_points(source, T) ~ target).
 
     Every iteration pairs each transformed source point with its exact nearest target point (ties to the lowest index), drops the pairs
@@ -213,17 +290,26 @@ def icp_align(source, target, max_iterations=50, tolerance=1e-9, max_distance=No
     after the update once the pairs' RMS distance changed by less than `tolerance` from the iteration before, or after max_iterations.
     ValueError when an iteration has fewer than 3 pairs.  return_history=True: (T, [(count, rmse) per iteration], [T per iteration]).
     Both clouds are uploaded once and the target is indexed once; an iteration moves 17 numbers to the host.  float32 clouds stay
-    float32 on the device (widened there), other real dtypes become float64; the arithmetic is float64 throughout."""
+    float32 on the device (widened there), other real dtypes become float64; the arithmetic is float64 throughout.
+
+    trim_fraction (a real number in (0, 1]): trimmed ICP for a source that carries clutter or overlaps the target only partly.  Of the
+    m pairs that pass max_distance an iteration uses the k = ceil(trim_fraction * m) closest, and every pair tied with the k-th; the
+    k-th smallest squared distance tau is found exactly on the device, with no host wait.  with_scale=True: a similarity fit -- each
+    iteration also estimates one scale (Umeyama), and the upper 3 x 3 of T is s R.  A similarity fit needs a sensible `init`: trimmed
+    pairs plus a free scale can shrink a badly placed source onto a few target points.  With either argument an iteration moves 20
+    numbers, and the history entries are (count, rmse, candidates, tau); with both left at their defaults nothing changes."""
     from . import device as dev
     s, sf = _cloud(source, "source")
     t, tf = _cloud(target, "target")
     _finite(s, "source")
     _finite(t, "target")
     _icp_args(len(s), len(t), max_iterations, tolerance, max_distance, init)
+    _trim_args(trim_fraction, with_scale)
     d_s = dev.from_numpy(s)
     d_t = d_s if target is source else dev.from_numpy(t)
     try:
-        return icp_align_resident(d_s, len(s), d_t, len(t), max_iterations, tolerance, max_distance, init, return_history, sf, tf)
+        return icp_align_resident(d_s, len(s), d_t, len(t), max_iterations, tolerance, max_distance, init, return_history, sf, tf,
+                                  trim_fraction, with_scale)
     finally:
         d_s.free()
         if d_t is not d_s:

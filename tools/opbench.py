@@ -530,7 +530,9 @@ def icp(reps, res, cpu_ref=True):
     extent.  ICP/step: the index build (with its one host wait) and one enqueued step, device events.  ICP/align: icp_align_resident
     with max_iterations 1 and 10 (tolerance 0: no early stop; index build, steps and the 17-value downloads; host wall clock, best of
     reps) -- the difference over 9 is what an iteration costs once the target is binned.  With cpu_ref, 10 iterations of a host ICP
-    on the same clouds (one cKDTree of the target, query with 16 workers, the same 3 x 3 solve) as context, not as a threshold."""
+    on the same clouds (one cKDTree of the target, query with 16 workers, the same 3 x 3 solve) as context, not as a threshold.
+    ICP/step_trimmed: the trimmed step with rho = 0.75 on the same index and inputs, device events, beside the plain step of the same
+    run.  SELECT/kth: the selection alone (csrc/select.hip) on the step's keys.  ICP/align_trimmed: the whole alignments with rho = 0.75."""
     import math
     from pb3d import preprocess_helpers as ph
     lib, L = pb3d._lib.load(), pb3d._lib
@@ -549,7 +551,7 @@ def icp(reps, res, cpu_ref=True):
     ntaj = n.value
     taj_pts = d_tp.download((ntaj, 3), np.float32)
     clouds = {"taj_full": (d_tp, ntaj, False, taj_pts), "sfm20k": (dev.from_numpy(sfm_vox), 20000, True, sfm_vox)}
-    d_out = dev.DeviceBuffer(17 * 8)
+    d_out, d_out20 = dev.DeviceBuffer(17 * 8), dev.DeviceBuffer(20 * 8)
 
     def displaced(host):
         lo, hi = host.min(0).astype(np.float64), host.max(0).astype(np.float64)
@@ -598,6 +600,30 @@ def icp(reps, res, cpu_ref=True):
              "Mpoint_s": round(ns / step_ms / 1e3, 1), "rmse": math.sqrt(raw[16] / ns)}
         print(json.dumps(r), flush=True)
         res.append(r)
+        # the trimmed step beside it (same index, same inputs, rho = 0.75), and the selection alone on the step's keys: the squared
+        # nearest distances of the moved source (nn_distances squared: the step's d2 up to the rounding of the square root)
+        trim_ms = timeit(lambda: ph.icp_step_trimmed_resident(ds, ns, dt, nt, init, -1.0, 0.75, c, c, sf, tf, out=d_out20), reps)
+        raw = d_out20.download((20,), np.float64)
+        count, m = (int(v) for v in raw[[0, 18]].view(np.int64))
+        r = {"op": "ICP/step_trimmed", "name": f"icp trimmed step, rho 0.75: {sn} -> {tn}", "ns": ns, "nt": nt, "step_ms": round(step_ms, 4),
+             "step_trimmed_ms": round(trim_ms, 4), "trimmed_over_plain": round(trim_ms / step_ms, 3), "count": count, "candidates": m,
+             "tau": float(raw[19])}
+        print(json.dumps(r), flush=True)
+        res.append(r)
+        d_moved = ph.transform_points_resident(ds, ns, init, sf)
+        d_keys = pb3d.eval_helpers.nn_distances_resident(d_moved, ns, dt, nt, 1, True, tf)
+        keys = d_keys.download((ns,), np.float64)
+        d_keys.upload(keys * keys)
+        d_tau = dev.DeviceBuffer(8)
+        kth_ms = timeit(lambda: pb3d.kth_smallest_resident(d_keys, ns, (3 * ns) // 4, out=d_tau), reps)
+        passes, hist_bytes = 8, 8 * 256 * 4
+        r = {"op": "SELECT/kth", "name": f"k-th smallest of the step's keys: {sn} -> {tn}", "n": ns, "rank": (3 * ns) // 4, "ms": round(kth_ms, 4),
+             "passes": passes, "launches": 2 * passes + 1, "bytes_read": passes * 8 * ns + passes * hist_bytes,
+             "GB_s": round((passes * 8 * ns + passes * hist_bytes) / kth_ms / 1e6, 2), "value": float(d_tau.download((1,), np.float64)[0])}
+        print(json.dumps(r), flush=True)
+        res.append(r)
+        for b in (d_moved, d_keys, d_tau):
+            b.free()
         t1 = wall(lambda: ph.icp_align_resident(ds, ns, dt, nt, 1, 0.0, None, init, False, sf, tf))
         t10 = wall(lambda: ph.icp_align_resident(ds, ns, dt, nt, 10, 0.0, None, init, False, sf, tf))
         _, hist, _ = ph.icp_align_resident(ds, ns, dt, nt, 10, 0.0, None, init, True, sf, tf)
@@ -610,7 +636,15 @@ def icp(reps, res, cpu_ref=True):
                 pass
         print(json.dumps(r), flush=True)
         res.append(r)
-    for b in [d_g, d_tc, d_out] + [c[0] for c in clouds.values()]:
+        t1 = wall(lambda: ph.icp_align_resident(ds, ns, dt, nt, 1, 0.0, None, init, False, sf, tf, 0.75))
+        t10 = wall(lambda: ph.icp_align_resident(ds, ns, dt, nt, 10, 0.0, None, init, False, sf, tf, 0.75))
+        _, hist, _ = ph.icp_align_resident(ds, ns, dt, nt, 10, 0.0, None, init, True, sf, tf, 0.75)
+        r = {"op": "ICP/align_trimmed", "name": f"icp_align_resident, rho 0.75: {sn} -> {tn}", "ns": ns, "nt": nt, "max_iterations_1_ms": t1,
+             "max_iterations_10_ms": t10, "per_further_iteration_ms": round((t10 - t1) / 9, 3), "rmse_first_last": [hist[0][1], hist[-1][1]],
+             "count_last": hist[-1][0]}
+        print(json.dumps(r), flush=True)
+        res.append(r)
+    for b in [d_g, d_tc, d_out, d_out20] + [c[0] for c in clouds.values()]:
         b.free()
 
 
