@@ -559,7 +559,9 @@ int pb3d_look_at_batch(const void* eye, const void* target, int is_f64, int64_t 
  * with ONE fixed camera and the IoU of the part's colour against the (Himg,Wimg,3) image d_seg.  inter[k] / uni[k] are the counts
  * compute_partwise_iou forms; nvalid[k] counts the in-bounds (point, jitter) evaluations before np.unique (0 <=> upstream's
  * "No deformed voxels within bounds").  Every point of a part carries the part colour, so the projected image is the set of
- * pixels hit and neither np.unique nor the write order can change the counts. */
+ * pixels hit and neither np.unique nor the write order can change the counts.  A non-finite scalar in any tuple is refused
+ * (PB3D_EINVAL, the message names the tuple and the scalar) before the outputs are written or anything is launched; see below.
+ * With n == 0 the projection is empty: inter = nvalid = 0 and uni = the image's pixels of the colour. */
 int pb3d_deform_iou_batch_dev(pb3d_ctx* ctx, const float* d_pts, int64_t n, const double* deforms5, int ntuples, int64_t A0, int64_t A1,
                               int64_t A2, const pb3d_camera* cam, int Himg, int Wimg, const uint8_t* d_seg, const uint8_t color[3],
                               int64_t* inter, int64_t* uni, int64_t* nvalid);
@@ -572,7 +574,13 @@ int pb3d_deform_iou_batch_dev(pb3d_ctx* ctx, const float* d_pts, int64_t n, cons
  * int64.  count, then fill with a buffer of n_unique rows; a fill refuses (PB3D_EINVAL) if another call has
  * reused the state its count left on the context.  paint writes rgb at grid[z,y,x] of every
  * in-bounds deformed coordinate (:120-124, :306-309 for a uniformly coloured part); scatter_colors is the
- * general grid[z,y,x] = cols[k] assignment for unique rows. */
+ * general grid[z,y,x] = cols[k] assignment for unique rows.  A row outside the grid makes scatter_colors
+ * return PB3D_EINVAL (NumPy would raise IndexError) after its launch: nothing outside the grid is written,
+ * and each in-bounds row's voxel holds either its old bytes or cols[k].
+ * Difference from the reference: a non-finite sxz, sy, kx, ky or kz is refused (PB3D_EINVAL, the message
+ * names the scalar) by count, paint and the tuple batch before any launch; the outputs are untouched and a
+ * pending count -> fill pair is dropped (its fill then asks for a new count).  Upstream, NumPy turns the NaN
+ * into INT64_MIN rows that the bounds filter drops; the conversion is undefined in C++. */
 int pb3d_deform_count_dev(pb3d_ctx* ctx, const float* d_pts, int64_t n, double sxz, double sy, double kx, double ky, double kz,
                           int64_t* n_unique);
 int pb3d_deform_fill_dev(pb3d_ctx* ctx, int64_t n_unique, int64_t* d_coords);

@@ -8,6 +8,8 @@
 // The points are voxel indices (integer-valued float32), so every jittered coordinate is a multiple of
 // 0.25 and the float64 mean NumPy computes is exact_sum / n whatever the summation order; the exact
 // sums are taken with integer atomics.  Non-integer inputs are rejected (PB3D_EUNSUPPORTED).
+#include <cmath>
+
 #include "pb3d_internal.h"
 #include "project_point.h"
 
@@ -188,6 +190,20 @@ int centers(pb3d_ctx* ctx, const float* d_pts, i64 n, double sxz, double sy, dou
     return PB3D_OK;
 }
 
+// NumPy turns a non-finite deformed value into an INT64_MIN row that the reference's bounds filter drops; the conversion is
+// undefined in C++, so the entries refuse such scalars before any device work and drop a pending count -> fill pair.
+int finite5(pb3d_ctx* ctx, const char* who, i64 tuple, const double v[5]) {
+    static const char* const names[5] = {"sxz", "sy", "kx", "ky", "kz"};
+    for (int a = 0; a < 5; ++a) {
+        if (std::isfinite(v[a])) continue;
+        ctx->deform.pair.valid = false;
+        if (tuple < 0) pb3d_set_error("%s: %s is not finite", who, names[a]);
+        else pb3d_set_error("%s: tuple %lld: %s is not finite", who, (long long)tuple, names[a]);
+        return PB3D_EINVAL;
+    }
+    return PB3D_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -195,6 +211,8 @@ extern "C" {
 int pb3d_deform_count_dev(pb3d_ctx* ctx, const float* d_pts, int64_t n, double sxz, double sy, double kx, double ky, double kz,
                           int64_t* n_unique) {
     PB3D_REQUIRE(ctx && n_unique && n >= 0, "pb3d_deform_count: bad argument");
+    const double sc[5] = {sxz, sy, kx, ky, kz};
+    PB3D_TRY(finite5(ctx, "pb3d_deform_count", -1, sc));
     ctx->deform.pair.valid = false;
     *n_unique = 0;
     if (n == 0) { ctx->deform.n = 0; pb3d_pair_record(ctx, &ctx->deform.pair, {}); return PB3D_OK; }
@@ -251,6 +269,8 @@ int pb3d_deform_fill_dev(pb3d_ctx* ctx, int64_t n_unique, int64_t* d_coords) {
 int pb3d_deform_paint_dev(pb3d_ctx* ctx, const float* d_pts, int64_t n, double sxz, double sy, double kx, double ky, double kz,
                           int64_t A0, int64_t A1, int64_t A2, const uint8_t rgb[3], uint8_t* d_grid) {
     PB3D_REQUIRE(ctx && rgb && n >= 0 && A0 >= 0 && A1 >= 0 && A2 >= 0, "pb3d_deform_paint: bad argument");
+    const double sc[5] = {sxz, sy, kx, ky, kz};
+    PB3D_TRY(finite5(ctx, "pb3d_deform_paint", -1, sc));
     if (n == 0 || A0 * A1 * A2 == 0) return PB3D_OK;
     PB3D_REQUIRE(d_pts && d_grid, "pb3d_deform_paint: null buffer");
     DeformParams P;
@@ -287,6 +307,7 @@ int pb3d_deform_iou_batch_dev(pb3d_ctx* ctx, const float* d_pts, int64_t n, cons
     PB3D_REQUIRE(ctx && n >= 0 && ntuples >= 0 && A0 >= 0 && A1 >= 0 && A2 >= 0 && Himg >= 0 && Wimg >= 0, "pb3d_deform_iou_batch: bad argument");
     PB3D_REQUIRE(ntuples == 0 || (deforms5 && cam && color && inter && uni && nvalid), "pb3d_deform_iou_batch: null argument");
     PB3D_REQUIRE(A0 < (1 << 24) && A1 < (1 << 24) && A2 < (1 << 24), "pb3d_deform_iou_batch: grid axis too long for float32 coordinates");
+    for (int k = 0; k < ntuples; ++k) PB3D_TRY(finite5(ctx, "pb3d_deform_iou_batch", k, deforms5 + 5 * (i64)k));
     for (int k = 0; k < ntuples; ++k) inter[k] = uni[k] = nvalid[k] = 0;
     const i64 npix = (i64)Himg * Wimg;
     if (ntuples == 0 || npix == 0) return PB3D_OK;
@@ -339,6 +360,8 @@ int pb3d_deform_iou_batch_dev(pb3d_ctx* ctx, const float* d_pts, int64_t n, cons
 int pb3d_deform_count(pb3d_ctx* ctx, const float* pts, int64_t n, double sxz, double sy, double kx, double ky, double kz,
                       int64_t* n_unique) {
     PB3D_REQUIRE(ctx && n >= 0, "pb3d_deform_count: bad argument");
+    const double sc[5] = {sxz, sy, kx, ky, kz};
+    PB3D_TRY(finite5(ctx, "pb3d_deform_count", -1, sc));
     void* d = nullptr;
     if (n) {
         PB3D_REQUIRE(pts != nullptr, "pb3d_deform_count: null points");
