@@ -405,6 +405,47 @@ int pb3d_icp_step_trimmed_resident(pb3d_ctx* ctx, const void* d_src, int src_f64
                                    const double T[12], double max_dist2, double trim_fraction, const double cp[3], const double cq[3],
                                    void* d_out /* 20 x 8 bytes */);
 
+/* ---- point-cloud normals and the point-to-plane ICP step built on them ----------------------------------------------------------------
+ * point_normals: d_normals (n x 3 float64) = one unit normal per point of the resident (n, 3) list d_pts (float32, or float64 with
+ *   pts_f64 = 1; finite), from d_idx, the n x k int32 rows of pb3d_knn_dev on (pts, pts, k) with 3 <= k <= PB3D_KNN_MAX_K and n >= k.  An
+ *   index outside [0, n) is PB3D_EINDEX, checked on the device before any gather (one host wait), as surface_metrics checks its rows.
+ *   One lane per point, float64 after widening; every product, sum, division and square root below is ONE correctly rounded
+ *   operation -- no FMA and, unlike the roughness of surface_metrics, no double-double.  With x_j the row's points in row order:
+ *     mean        m_a = (((0 + x_0a) + x_1a) + ... + x_(k-1)a) / k;
+ *     covariance  y_j = x_j - m;  C_ab = (((0 + y_0a*y_0b) + y_1a*y_1b) + ...) for the six entries a <= b, no divisor;
+ *     Jacobi      the cyclic 3 x 3 solve of the roughness path as it stands (one text, csrc/jacobi3.h): V = I; up to 8 sweeps over
+ *                 the pairs (p, q) = (0, 1), (0, 2), (1, 2); a pair with C_pq == 0 is skipped; it is rotated when
+ *                 |C_pq| > 2^-70 * sqrt(|C_pp * C_qq|) and set to zero either way; for a rotation
+ *                 tau = (C_qq - C_pp) / (2 * C_pq), t = copysign(1, tau) / (|tau| + sqrt(1 + tau*tau)), c = 1 / sqrt(1 + t*t), s = t*c,
+ *                 C_pp -= t*C_pq, C_qq += t*C_pq, (C_rp, C_rq) = (c*C_rp - s*C_rq, s*C_rp + c*C_rq), and the same for columns p, q of
+ *                 every row of V; a sweep without a rotation is the last;
+ *     normal      the column of V whose diagonal entry of C is smallest, the lowest column on a tie, each component divided by
+ *                 sqrt((n0*n0 + n1*n1) + n2*n2);
+ *     sign        viewpoint NULL: negated when its component of largest magnitude (the lowest on a tie) is negative;
+ *                 viewpoint v (3 finite doubles, host): negated when ((v0-x0)*n0 + (v1-x1)*n1) + (v2-x2)*n2 < 0, x the point itself.
+ *   k coincident neighbours (zero covariance) give (1, 0, 0) before the sign rule.  n = 0 is fine (nothing written).
+ * icp_step_plane: one point-to-plane step against the index of icp_index and d_tgt_normals (nt x 3 float64 on the device, row j the
+ *   normal of target point j; finite).  Word for word pb3d_icp_step_resident and pb3d_icp_step_trimmed_resident: the index and its
+ *   refusals, p = T s, j and d2, the gate, the candidate, k and tau rules, the summation order, no host wait.  trim_fraction < 0:
+ *   untrimmed -- no selection runs, a pair is used as icp_step uses it, and the m and tau words are 0; otherwise it must be in (0, 1]
+ *   and a pair is used as icp_step_trimmed uses it.  0 and NaN are PB3D_EINVAL.  One pivot c serves as cp.
+ *     A used pair contributes 1 to the count and 29 terms.  With n = row j of the normals, (dx, dy, dz) = p - q_j (the differences
+ *     that form d2) and P = p - c:
+ *       r  = (dx*n0 + dy*n1) + dz*n2
+ *       a0 = P1*n2 - P2*n1,  a1 = P2*n0 - P0*n2,  a2 = P0*n1 - P1*n0;     J = (a0, a1, a2, n0, n1, n2)
+ *       terms 0-20: J_u * J_v for u <= v, the upper triangle row-major (00 01 .. 05 11 12 .. 55);  terms 21-26: J_u * r;
+ *       term 27: r * r;  term 28: d2.
+ *     Any other pair contributes 0 and +0.0 twenty-nine times.  Rows of 29 sums, reduced in the order stated for icp_step.
+ *   d_out (32 x 8 bytes on the device): the int64 count, the 29 float64 sums, the int64 m, the float64 tau.  ns = 0: thirty-two zero
+ *   words (no index, no normals needed).  Every term is even in n, so negating any or all target normals leaves all 32 words
+ *   unchanged: the step does not care how the normals are oriented.  The host solves the 6 x 6 system (A x = -g with A from terms
+ *   0-20, g from 21-26, x = (rotation vector, translation) about c). */
+int pb3d_point_normals_resident(pb3d_ctx* ctx, const void* d_pts, int pts_f64, int64_t n, const int32_t* d_idx, int k,
+                                const double* viewpoint /* 3 doubles or NULL */, double* d_normals /* n x 3 float64 */);
+int pb3d_icp_step_plane_resident(pb3d_ctx* ctx, const void* d_src, int src_f64, int64_t ns, const void* d_tgt, int tgt_f64, int64_t nt,
+                                 const double* d_tgt_normals /* nt x 3 float64 */, const double T[12], double max_dist2,
+                                 double trim_fraction, const double c[3], void* d_out /* 32 x 8 bytes */);
+
 /* ---- facade plane, box crop and the pieces of the four-way completion: steps 2-4 of the inter-method preprocessing (reference
  * results/4.Inter-method_3D/README.md; its utils/preprocess_helpers.py is not shipped, so the arithmetic below is the specification) --
  * Point lists as for ICP: (n, 3) rows of float32 (*_f64 = 0) or float64 (1), n <= 2^31 - 1.  All arithmetic is float64 after widening,

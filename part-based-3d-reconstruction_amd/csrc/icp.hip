@@ -1,5 +1,5 @@
 // Rigid ICP of two point clouds, the device half: transform, exact nearest target point, and the 16 (trimmed: 17) float64 sums a
-// point-to-point step needs (include/pb3d.h has the semantics to the bit; pb3d/preprocess_helpers.py runs the 3 x 3 solve and the
+// point-to-point step needs, or the 29 of a point-to-plane step (include/pb3d.h has the semantics to the bit; pb3d/preprocess_helpers.py runs the 3 x 3 solve and the
 // loop on the host).
 //
 // An alignment bins its target ONCE (pb3d_icp_index_resident -> pb3d_nn_index_build of csrc/nn.hip: exact box, cell counts, scan, cell-
@@ -16,7 +16,9 @@
 //   k_icp_keys        one point per thread: d2 of a candidate pair, the sentinel NaN of any other, and the candidate count m
 //   k_icp_rank        k from m and the trim fraction, on the device                       } -> PB3D_SLOT_ICP_KEYS (header, then keys)
 //   pb3d_select_kth   tau = the k-th smallest key (csrc/select.hip), its rank read from the header
-// and its terms kernel (the same template, 17 sums) uses the candidates with d2 <= tau.
+// and its terms kernel (the same template, 17 sums) uses the candidates with d2 <= tau.  A POINT-TO-PLANE step
+// (pb3d_icp_step_plane_resident) is the same chain with another set of terms: the kernel also gathers row j of the target's float64
+// normals and forms the 29 terms of the 6 x 6 normal equations (the upper triangle of J J^T, J r, r r, d2); its trim is optional.
 // The summation order is a function of (ns, point index) alone: no floating-point atomics, and the cell-sorted query order of the
 // search (free within a cell) never reaches a sum, because the terms are formed from the index array in the caller's order.  The
 // Makefile passes -ffp-contract=off: every product and sum below is one rounded operation.
@@ -28,6 +30,7 @@
 namespace {
 
 constexpr int kSums = 16;
+constexpr int kPlaneSums = 29;
 
 struct Xf { double t[12]; };                 // row-major 3 x 4 [R | t]
 struct Pivots { double cp[3], cq[3]; };
@@ -103,24 +106,23 @@ __global__ void k_icp_rank(TrimHeader* __restrict__ hdr, double rho) {
 }
 
 // W = 16: the plain step.  TAU: a trimmed step -- a candidate is used when d2 <= tau, there is a 17th term |P|^2, and workgroup 0
-// writes the candidate count and tau behind the 18 words of the final row pass
-template <bool TF64, int W, bool TAU>
+// writes the candidate count and tau behind the 18 words of the final row pass.  PLANE (W = 29): the point-to-plane terms from row j
+// of nrm, pivot pv.cp; the two words behind the row are always written (0 and +0.0 without TAU)
+template <bool TF64, int W, bool TAU, bool PLANE>
 __global__ __launch_bounds__(256) void k_icp_terms(const double* __restrict__ moved, const int* __restrict__ nearest, i64 ns,
                                                    const void* __restrict__ tgt, i64 nt, double max_dist2, Pivots pv, const TrimHeader* __restrict__ hdr,
-                                                   double* __restrict__ part, double* __restrict__ out) {
-    static_assert(W == (TAU ? 17 : 16), "the trimmed step has 17 sums, the plain step 16");
+                                                   const double* __restrict__ nrm, double* __restrict__ part, double* __restrict__ out) {
+    static_assert(W == (PLANE ? kPlaneSums : TAU ? 17 : 16), "the point-to-plane step has 29 sums, the trimmed step 17, the plain step 16");
     const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
     double v[W];
 #pragma unroll
     for (int c = 0; c < W; ++c) v[c] = 0.0;
     i64 cnt = 0;
     double tau = 0.0;
-    if (TAU) {
-        tau = trim_tau(hdr);
-        if (i == 0) {
-            ((i64*)out)[W + 1] = hdr->m;
-            out[W + 2] = tau;
-        }
+    if (TAU) tau = trim_tau(hdr);
+    if ((TAU || PLANE) && i == 0) {
+        ((i64*)out)[W + 1] = TAU ? hdr->m : 0;
+        out[W + 2] = tau;
     }
     if (i < ns) {
         double p[3], q[3], d2 = 0.0;
@@ -128,15 +130,31 @@ __global__ __launch_bounds__(256) void k_icp_terms(const double* __restrict__ mo
             double P[3], Q[3];
 #pragma unroll
             for (int a = 0; a < 3; ++a) { P[a] = p[a] - pv.cp[a]; Q[a] = q[a] - pv.cq[a]; }
+            if (PLANE) {
+                const double* n = nrm + 3 * (i64)nearest[i];
+                const double dx = p[0] - q[0], dy = p[1] - q[1], dz = p[2] - q[2];       // the differences d2 was formed from
+                const double r = (dx * n[0] + dy * n[1]) + dz * n[2];
+                const double J[6] = {P[1] * n[2] - P[2] * n[1], P[2] * n[0] - P[0] * n[2], P[0] * n[1] - P[1] * n[0], n[0], n[1], n[2]};
+                int c = 0;
 #pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                v[a] = P[a];
-                v[3 + a] = Q[a];
+                for (int a = 0; a < 6; ++a)
 #pragma unroll
-                for (int b = 0; b < 3; ++b) v[6 + 3 * a + b] = P[a] * Q[b];
+                    for (int b = a; b < 6; ++b) v[c++] = J[a] * J[b];
+#pragma unroll
+                for (int a = 0; a < 6; ++a) v[21 + a] = J[a] * r;
+                v[27] = r * r;
+                v[28] = d2;
+            } else {
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    v[a] = P[a];
+                    v[3 + a] = Q[a];
+#pragma unroll
+                    for (int b = 0; b < 3; ++b) v[6 + 3 * a + b] = P[a] * Q[b];
+                }
+                v[15] = d2;
+                if (TAU) v[W - 1] = (P[0] * P[0] + P[1] * P[1]) + P[2] * P[2];
             }
-            v[15] = d2;
-            if (TAU) v[W - 1] = (P[0] * P[0] + P[1] * P[1]) + P[2] * P[2];
             cnt = 1;
         }
     }
@@ -169,13 +187,14 @@ int step_args(const pb3d_ctx* ctx, const char* who, const void* d_src, i64 ns, c
     return PB3D_OK;
 }
 
-// transform, search, [keys, rank, selection,] terms, final row pass.  TRIM: 17 sums and the two words behind them
-template <bool TRIM>
-int run_step(pb3d_ctx* ctx, const char* who, const void* d_src, int src_f64, i64 ns, const void* d_tgt, int tgt_f64, i64 nt, const double T[12],
-             double max_dist2, double rho, const double cp[3], const double cq[3], void* d_out) {
-    constexpr int W = TRIM ? kSums + 1 : kSums;
+// transform, search, [keys, rank, selection,] terms, final row pass.  TRIM: 17 sums and the two words behind them.  PLANE: the 29
+// point-to-plane sums against the normals d_nrm, the two words always, the selection only with TRIM
+template <bool TRIM, bool PLANE>
+int run_step(pb3d_ctx* ctx, const char* who, const void* d_src, int src_f64, i64 ns, const void* d_tgt, int tgt_f64, i64 nt, const double* d_nrm,
+             const double T[12], double max_dist2, double rho, const double cp[3], const double cq[3], void* d_out) {
+    constexpr int W = PLANE ? kPlaneSums : TRIM ? kSums + 1 : kSums;
     if (ns == 0) {
-        PB3D_HIP(hipMemsetAsync(d_out, 0, (W + 1 + (TRIM ? 2 : 0)) * 8, ctx->stream));
+        PB3D_HIP(hipMemsetAsync(d_out, 0, (W + 1 + (TRIM || PLANE ? 2 : 0)) * 8, ctx->stream));
         return PB3D_OK;
     }
     const pb3d_ctx::IcpIndex& ii = ctx->icp_index;
@@ -205,10 +224,10 @@ int run_step(pb3d_ctx* ctx, const char* who, const void* d_src, int src_f64, i64
         PB3D_CHECK_LAUNCH();
         PB3D_TRY(pb3d_select_kth(ctx, (const double*)keys, ns, &hdr->rank, &hdr->tau));
     }
-    if (tgt_f64) hipLaunchKernelGGL((k_icp_terms<true, W, TRIM>), grid, wg, 0, ctx->stream, (const double*)moved, (const int*)nearest, ns, d_tgt, nt,
-                                    max_dist2, pv, (const TrimHeader*)hdr, (double*)part, (double*)d_out);
-    else hipLaunchKernelGGL((k_icp_terms<false, W, TRIM>), grid, wg, 0, ctx->stream, (const double*)moved, (const int*)nearest, ns, d_tgt, nt,
-                            max_dist2, pv, (const TrimHeader*)hdr, (double*)part, (double*)d_out);
+    if (tgt_f64) hipLaunchKernelGGL((k_icp_terms<true, W, TRIM, PLANE>), grid, wg, 0, ctx->stream, (const double*)moved, (const int*)nearest, ns, d_tgt,
+                                    nt, max_dist2, pv, (const TrimHeader*)hdr, d_nrm, (double*)part, (double*)d_out);
+    else hipLaunchKernelGGL((k_icp_terms<false, W, TRIM, PLANE>), grid, wg, 0, ctx->stream, (const double*)moved, (const int*)nearest, ns, d_tgt,
+                            nt, max_dist2, pv, (const TrimHeader*)hdr, d_nrm, (double*)part, (double*)d_out);
     PB3D_CHECK_LAUNCH();
     hipLaunchKernelGGL(pb3d_k_rows_final<W>, dim3(1), dim3(256), 0, ctx->stream, (const double*)part, nrows, (double*)d_out);
     PB3D_CHECK_LAUNCH();
@@ -248,7 +267,7 @@ int pb3d_icp_index_resident(pb3d_ctx* ctx, const void* d_tgt, int tgt_f64, int64
 int pb3d_icp_step_resident(pb3d_ctx* ctx, const void* d_src, int src_f64, int64_t ns, const void* d_tgt, int tgt_f64, int64_t nt,
                            const double T[12], double max_dist2, const double cp[3], const double cq[3], void* d_out) {
     PB3D_TRY(step_args(ctx, "pb3d_icp_step", d_src, ns, d_tgt, nt, T, max_dist2, cp, cq, d_out));
-    return run_step<false>(ctx, "pb3d_icp_step", d_src, src_f64, ns, d_tgt, tgt_f64, nt, T, max_dist2, 1.0, cp, cq, d_out);
+    return run_step<false, false>(ctx, "pb3d_icp_step", d_src, src_f64, ns, d_tgt, tgt_f64, nt, nullptr, T, max_dist2, 1.0, cp, cq, d_out);
 }
 
 int pb3d_icp_step_trimmed_resident(pb3d_ctx* ctx, const void* d_src, int src_f64, int64_t ns, const void* d_tgt, int tgt_f64, int64_t nt,
@@ -256,7 +275,21 @@ int pb3d_icp_step_trimmed_resident(pb3d_ctx* ctx, const void* d_src, int src_f64
                                    void* d_out) {
     PB3D_REQUIRE(trim_fraction > 0.0 && trim_fraction <= 1.0, "pb3d_icp_step_trimmed: the trim fraction must be in (0, 1] (got %g)", trim_fraction);
     PB3D_TRY(step_args(ctx, "pb3d_icp_step_trimmed", d_src, ns, d_tgt, nt, T, max_dist2, cp, cq, d_out));
-    return run_step<true>(ctx, "pb3d_icp_step_trimmed", d_src, src_f64, ns, d_tgt, tgt_f64, nt, T, max_dist2, trim_fraction, cp, cq, d_out);
+    return run_step<true, false>(ctx, "pb3d_icp_step_trimmed", d_src, src_f64, ns, d_tgt, tgt_f64, nt, nullptr, T, max_dist2, trim_fraction, cp, cq,
+                                 d_out);
+}
+
+int pb3d_icp_step_plane_resident(pb3d_ctx* ctx, const void* d_src, int src_f64, int64_t ns, const void* d_tgt, int tgt_f64, int64_t nt,
+                                 const double* d_tgt_normals, const double T[12], double max_dist2, double trim_fraction, const double c[3],
+                                 void* d_out) {
+    const char* who = "pb3d_icp_step_plane";
+    PB3D_REQUIRE(trim_fraction < 0.0 || (trim_fraction > 0.0 && trim_fraction <= 1.0),
+                 "%s: the trim fraction must be in (0, 1], or negative for no trim (got %g)", who, trim_fraction);
+    PB3D_REQUIRE(ns <= 0 || d_tgt_normals != nullptr, "%s: null buffer", who);
+    PB3D_TRY(step_args(ctx, who, d_src, ns, d_tgt, nt, T, max_dist2, c, c, d_out));
+    if (trim_fraction < 0.0)
+        return run_step<false, true>(ctx, who, d_src, src_f64, ns, d_tgt, tgt_f64, nt, d_tgt_normals, T, max_dist2, 1.0, c, c, d_out);
+    return run_step<true, true>(ctx, who, d_src, src_f64, ns, d_tgt, tgt_f64, nt, d_tgt_normals, T, max_dist2, trim_fraction, c, c, d_out);
 }
 
 }  // extern "C"

@@ -399,6 +399,9 @@ int pb3d_nn_index_nearest(pb3d_ctx* ctx, const pb3d_nn_index& ix, const double* 
 // csrc/select.hip for csrc/icp.hip: pb3d_kth_smallest_resident with the rank read from device memory when the selection runs
 // (0 <= *d_rank < n; 1 <= n <= 2^31 - 1; enqueued)
 int pb3d_select_kth(pb3d_ctx* ctx, const double* d_vals, i64 n, const i64* d_rank, double* d_out);
+// csrc/surface.hip for csrc/normals.hip: PB3D_EINDEX (message "<what>: index out of bounds ...") if any of the n int32 (int64 with
+// i64_entries) values of d_idx is outside [lo, hi); the flag is in PB3D_SLOT_SURF_FLAG; one host wait
+int pb3d_check_index_range(pb3d_ctx* ctx, const void* d_idx, int i64_entries, i64 n, i64 lo, i64 hi, const char* what);
 // process_voxel_grid through the bit-sliced chain (csrc/sliced.hip); *took = 0: not applicable, nothing written
 int pb3d_process_grid_sliced(pb3d_ctx* ctx, const u8* d_occ, i64 W, i64 H, i64 D, const u8* d_mask_wh, int angle_interval, u8* d_out,
                              int known_binary, int* took);

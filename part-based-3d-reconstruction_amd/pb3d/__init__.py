@@ -23,6 +23,8 @@ from .eval_helpers import density_grid_resident, pointcloud_to_voxel_grid  # noq
 from .preprocess_helpers import (best_fit_transform_from_sums, flip_y_axis, icp_align, icp_align_resident, normalize_preserve_aspect,  # noqa: F401
                                  transform_points, transform_points_resident)
 from .preprocess_helpers import best_fit_similarity_from_sums, icp_step_trimmed_resident  # noqa: F401
+from .preprocess_helpers import (estimate_normals, estimate_normals_resident, icp_step_plane_resident,  # noqa: F401
+                                 plane_step_from_sums)
 from .selection import kth_smallest, kth_smallest_resident  # noqa: F401
 from .preprocess_helpers import (crop_to_box, crop_to_box_resident, fit_plane_ransac, fit_plane_ransac_resident,  # noqa: F401
                                  plane_alignment_transform, plane_from_moments, plane_hypotheses_resident, plane_moments_resident,

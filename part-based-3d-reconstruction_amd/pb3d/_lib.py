@@ -160,6 +160,8 @@ _SIGNATURES = {
     "pb3d_icp_step_resident": [vp, vp, C.c_int, i64, vp, C.c_int, i64, dblp, C.c_double, dblp, dblp, vp],
     "pb3d_kth_smallest_resident": [vp, vp, i64, i64, vp],
     "pb3d_icp_step_trimmed_resident": [vp, vp, C.c_int, i64, vp, C.c_int, i64, dblp, C.c_double, C.c_double, dblp, dblp, vp],
+    "pb3d_point_normals_resident": [vp, vp, C.c_int, i64, vp, C.c_int, dblp, vp],
+    "pb3d_icp_step_plane_resident": [vp, vp, C.c_int, i64, vp, C.c_int, i64, vp, dblp, C.c_double, C.c_double, dblp, vp],
     "pb3d_plane_hypotheses_resident": [vp, vp, C.c_int, i64, vp, C.c_int, vp],
     "pb3d_plane_score_resident": [vp, vp, C.c_int, i64, vp, C.c_int, C.c_double, vp],
     "pb3d_plane_moments_resident": [vp, vp, C.c_int, i64, dblp, C.c_double, dblp, vp],

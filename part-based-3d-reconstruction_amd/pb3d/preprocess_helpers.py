@@ -13,7 +13,9 @@ index built once per alignment (csrc/icp.hip on the search of csrc/nn.hip, ties 
 count and 16 float64 sums in a fixed order; the host downloads those 17 values, solves the 3 x 3 problem
 (best_fit_transform_from_sums) and composes the transform.  With trim_fraction the device also finds, per iteration and without a host
 wait, the exact k-th smallest pair distance (csrc/select.hip) and sums only the pairs up to it; with with_scale the host solve
-estimates Umeyama's scale from one more sum (best_fit_similarity_from_sums).
+estimates Umeyama's scale from one more sum (best_fit_similarity_from_sums).  With method="point_to_plane" the device step gathers the
+target's normals (given, or estimated once on the device: estimate_normals on the exact k-neighbour rows of csrc/nn.hip, csrc/normals.hip)
+and sums the 29 terms of the 6 x 6 normal equations; the host solves them with a cut-off pseudo-inverse (plane_step_from_sums).
 
 crop_to_box, fit_plane_ransac + plane_alignment_transform and symmetric_completion are steps 2-4 of the same README: crop the dense
 cloud to the sparse cloud's box, estimate the dominant facade plane and turn it onto the Z axis, and the naive four-way completion.
@@ -30,7 +32,8 @@ from . import _lib
 
 __all__ = ["normalize_preserve_aspect", "flip_y_axis", "transform_points", "transform_points_resident", "best_fit_transform_from_sums",
            "best_fit_similarity_from_sums", "icp_align", "icp_align_resident", "icp_index_resident", "icp_step_resident",
-           "icp_step_trimmed_resident", "plane_hypotheses_resident", "plane_score_resident",
+           "icp_step_trimmed_resident", "icp_step_plane_resident", "plane_step_from_sums", "estimate_normals",
+           "estimate_normals_resident", "plane_hypotheses_resident", "plane_score_resident",
            "plane_moments_resident", "crop_to_box_resident", "plane_from_moments", "fit_plane_ransac", "fit_plane_ransac_resident",
            "plane_alignment_transform", "crop_to_box", "symmetric_completion", "symmetric_completion_resident"]
 
@@ -206,6 +209,145 @@ def icp_step_trimmed_resident(d_source, ns, d_target, nt, T, max_dist2, trim_fra
     return d_out
 
 
+def icp_step_plane_resident(d_source, ns, d_target, nt, d_normals, T, max_dist2, trim_fraction, c, s_f64=True, t_f64=True, out=None):
+    """pb3d_icp_step_plane_resident: a DeviceBuffer of 32 x 8 bytes -- the int64 count of used pairs, the 29 float64 sums of one
+    point-to-plane step (the upper triangle of sum J J^T, sum J r, sum r r, sum d2) against the index of icp_index_resident and the
+    resident (nt, 3) float64 target normals, the int64 number of candidate pairs m and the float64 tau.  trim_fraction < 0 (or None):
+    untrimmed, m and tau are 0.  c: the pivot of the rotation."""
+    from . import device as dev
+    t = _t12(np.asarray(T, np.float64))
+    c = np.ascontiguousarray(c, dtype=np.float64).reshape(3)
+    rho = -1.0 if trim_fraction is None else float(trim_fraction)
+    d_out = out if out is not None else dev.DeviceBuffer(32 * 8)
+    _lib.check(_lib.load().pb3d_icp_step_plane_resident(_lib.ctx(), _ptr(d_source), int(bool(s_f64)), int(ns), _ptr(d_target),
+                                                        int(bool(t_f64)), int(nt), _ptr(d_normals), _lib.p_dbl(t), float(max_dist2), rho,
+                                                        _lib.p_dbl(c), _ptr(d_out)))
+    return d_out
+
+
+def plane_step_from_sums(count, sums, c, cutoff=1e-12):
+    """(4 x 4 step, rank): the small rigid motion about the pivot c that minimises the linearised point-to-plane error, from the count
+    and the sums of a point-to-plane step (sums[0:21] = the upper triangle of A = sum J J^T row-major, sums[21:27] = g = sum J r; later
+    entries are not read).  w, V = eigh(A); the eigenpairs with w > cutoff * w[-1] are kept (rank of them: a flat target leaves 3)
+    and x = -V_keep diag(1 / w_keep) V_keep^T g.  omega = x[:3] becomes R by Rodrigues' formula (I + K below |omega| = 1e-12), t = x[3:],
+    and the step is [R | c + t - R c]."""
+    count = int(count)
+    sums = np.asarray(sums, np.float64).reshape(-1)
+    c = np.asarray(c, np.float64).reshape(3)
+    if sums.size < 27:
+        raise ValueError(f"a point-to-plane solve needs the 27 sums of A and g (got {sums.size})")
+    if count < 6:
+        raise ValueError(f"a point-to-plane fit needs at least 6 point pairs (got {count})")
+    A = np.zeros((6, 6))
+    A[np.triu_indices(6)] = sums[:21]
+    A = A + np.triu(A, 1).T
+    g = sums[21:27]
+    w, V = np.linalg.eigh(A)
+    keep = w > cutoff * w[-1]
+    rank = int(keep.sum())
+    M = np.eye(4)
+    if rank == 0:           # A = 0: nothing to solve
+        return M, 0
+    Vk = V[:, keep]
+    x = -(Vk @ ((Vk.T @ g) / w[keep]))
+    om, t = x[:3], x[3:]
+    th = float(np.sqrt((om[0] * om[0] + om[1] * om[1]) + om[2] * om[2]))
+    K = np.array([[0.0, -om[2], om[1]], [om[2], 0.0, -om[0]], [-om[1], om[0], 0.0]])
+    if th < 1e-12:
+        R = np.eye(3) + K
+    else:
+        K = K / th
+        R = np.eye(3) + math.sin(th) * K + (1.0 - math.cos(th)) * (K @ K)
+    M[:3, :3] = R
+    M[:3, 3] = c + t - R @ c
+    return M, rank
+
+
+def _normals_k(k, n):
+    """k of estimate_normals for n points: a plane needs three neighbours, the search has its limit, and a row needs k points"""
+    from .eval_helpers import KNN_MAX_K
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)):
+        raise ValueError(f"k must be an integer (got {k!r})")
+    if k < 3 or k > KNN_MAX_K:
+        raise ValueError(f"k must be in [3, {KNN_MAX_K}] (got {k})")
+    if n < k:
+        raise ValueError(f"estimate_normals: k = {k} neighbours need at least {k} points (got {n})")
+    return int(k)
+
+
+def _viewpoint(orient_towards):
+    if orient_towards is None:
+        return None
+    v = np.asarray(orient_towards)
+    if v.shape != (3,) or v.dtype.kind not in "fiu":
+        raise ValueError(f"orient_towards must be three real numbers, or None (got {orient_towards!r})")
+    v = np.ascontiguousarray(v, dtype=np.float64)
+    _finite(v, "orient_towards")
+    return v
+
+
+def estimate_normals_resident(d_points, n, k=20, orient_towards=None, f64=True, out=None):
+    """pb3d_point_normals_resident on the rows of pb3d_knn_dev: a DeviceBuffer of n x 3 float64 unit normals of the resident (n, 3) list
+    (float64 rows, or float32 with f64 False; finite).  Two host waits: the search's box and the index check."""
+    from . import device as dev
+    from .eval_helpers import knn_resident
+    n = int(n)
+    k = _normals_k(k, n)
+    v = _viewpoint(orient_towards)
+    _, d_idx = knn_resident(d_points, n, d_points, n, k, f64, f64, dist=False)
+    try:
+        d_out = out if out is not None else dev.DeviceBuffer(n * 24)
+        try:
+            _lib.check(_lib.load().pb3d_point_normals_resident(_lib.ctx(), _ptr(d_points), int(bool(f64)), n, _ptr(d_idx), k,
+                                                               None if v is None else _lib.p_dbl(v), _ptr(d_out)))
+        except BaseException:
+            if out is None:
+                d_out.free()
+            raise
+        return d_out
+    finally:
+        d_idx.free()
+
+
+def estimate_normals(points, k=20, orient_towards=None):
+    """float64 (n, 3): a unit normal per point of the cloud, the direction of least spread of its k nearest points (itself included;
+    exact search, ties to the lowest index), on the device.  include/pb3d.h states the arithmetic to the bit.  orient_towards=None: the
+    component of largest magnitude is positive; orient_towards=v: the normal points into the half space of the viewpoint v.
+    ValueError for k < 3, k > KNN_MAX_K, fewer than k points or non-finite input.  float32 clouds stay float32 on the device."""
+    from . import device as dev
+    p, pf = _cloud(points, "points")
+    _normals_k(k, len(p))
+    _viewpoint(orient_towards)
+    _finite(p, "points")
+    d_p = dev.from_numpy(p)
+    try:
+        d_out = estimate_normals_resident(d_p, len(p), k, orient_towards, pf)
+        try:
+            return d_out.download((len(p), 3), np.float64)
+        finally:
+            d_out.free()
+    finally:
+        d_p.free()
+
+
+METHODS = ("point_to_point", "point_to_plane")
+
+
+def _method_args(method, with_scale, normals_k, nt, have_normals):
+    """True for the plane method, after its checks"""
+    if method not in METHODS:
+        raise ValueError(f"method must be one of {METHODS} (got {method!r})")
+    if method == "point_to_point":
+        if have_normals:
+            raise ValueError("target_normals are only read with method='point_to_plane'")
+        return False
+    if with_scale:
+        raise ValueError("with_scale=True needs method='point_to_point': the point-to-plane step is rigid")
+    if not have_normals:
+        _normals_k(normals_k, nt)
+    return True
+
+
 def _trim_args(trim_fraction, with_scale):
     """(rho or None, with_scale): both defaults -> (None, False), today's path"""
     if not isinstance(with_scale, (bool, np.bool_)):
@@ -242,13 +384,18 @@ def _icp_args(ns, nt, max_iterations, tolerance, max_distance, init):
 
 
 def icp_align_resident(d_source, ns, d_target, nt, max_iterations=50, tolerance=1e-9, max_distance=None, init=None, return_history=False,
-                       s_f64=True, t_f64=True, trim_fraction=None, with_scale=False):
+                       s_f64=True, t_f64=True, trim_fraction=None, with_scale=False, method="point_to_point", target_normals=None,
+                       normals_k=20):
     """icp_align on resident (ns, 3) / (nt, 3) lists (DeviceBuffers; float64 rows, or float32 with s_f64 / t_f64 False).  The target
     is binned once; every iteration enqueues one step and downloads its 17 values (20 with trim_fraction or with_scale: the trimmed
-    step, whose history entries are (count, rmse, candidates, tau))."""
+    step, whose history entries are (count, rmse, candidates, tau)).  method="point_to_plane": target_normals is a DeviceBuffer of nt x 3
+    float64, or None to estimate them here from the normals_k nearest neighbours; an iteration downloads 32 values."""
     from . import device as dev
     max_iterations, tolerance, md2, T = _icp_args(int(ns), int(nt), max_iterations, tolerance, max_distance, init)
     rho, with_scale = _trim_args(trim_fraction, with_scale)
+    if _method_args(method, with_scale, normals_k, int(nt), target_normals is not None):
+        return _icp_plane(d_source, ns, d_target, nt, max_iterations, tolerance, md2, T, return_history, s_f64, t_f64, rho, target_normals,
+                          normals_k)
     trimmed = rho is not None or with_scale
     box = icp_index_resident(d_target, nt, t_f64)               # the only index build of the alignment
     c = 0.5 * (box[:3] + box[3:])
@@ -281,8 +428,55 @@ def icp_align_resident(d_source, ns, d_target, nt, max_iterations=50, tolerance=
     return (T, history, Ts) if return_history else T
 
 
+def _icp_plane(d_source, ns, d_target, nt, max_iterations, tolerance, md2, T, return_history, s_f64, t_f64, rho, d_normals, normals_k):
+    """the point-to-plane loop of icp_align_resident, its arguments checked"""
+    from . import device as dev
+    own = d_normals is None
+    if own:
+        d_normals = estimate_normals_resident(d_target, nt, normals_k, None, t_f64)     # once per alignment
+    d_out = None
+    history, Ts, prev = [], [], None
+    try:
+        box = icp_index_resident(d_target, nt, t_f64)
+        c = 0.5 * (box[:3] + box[3:])
+        d_out = dev.DeviceBuffer(32 * 8)
+        for _ in range(max_iterations):
+            icp_step_plane_resident(d_source, ns, d_target, nt, d_normals, T, md2, rho, c, s_f64, t_f64, out=d_out)
+            raw = d_out.download((32,), np.float64)
+            count, sums = int(raw[:1].view(np.int64)[0]), raw[1:30]
+            if count < 6:
+                raise ValueError(f"icp_align: only {count} point pairs within max_distance (a point-to-plane fit needs 6)")
+            rmse_plane, rmse_point = math.sqrt(sums[27] / count), math.sqrt(sums[28] / count)
+            step, rank = plane_step_from_sums(count, sums, c)
+            T = step @ T
+            entry = (count, rmse_plane, rmse_point, rank)
+            history.append(entry if rho is None else entry + (int(raw[30:31].view(np.int64)[0]), float(raw[31])))
+            Ts.append(T)
+            if prev is not None and abs(prev - rmse_plane) < tolerance:
+                break
+            prev = rmse_plane
+    finally:
+        if d_out is not None:
+            d_out.free()
+        if own:
+            d_normals.free()
+    return (T, history, Ts) if return_history else T
+
+
+def _target_normals(target_normals, nt):
+    """float64 (nt, 3), finite, or None"""
+    if target_normals is None:
+        return None
+    n = np.asarray(target_normals)
+    if n.shape != (nt, 3) or n.dtype.kind not in "fiu":
+        raise ValueError(f"target_normals must be a real ({nt}, 3) array, one row per target point (got shape {n.shape}, dtype {n.dtype})")
+    n = np.ascontiguousarray(n, dtype=np.float64)
+    _finite(n, "target_normals")
+    return n
+
+
 def icp_align(source, target, max_iterations=50, tolerance=1e-9, max_distance=None, init=None, return_history=False, trim_fraction=None,
-              with_scale=False):
+              with_scale=False, method="point_to_point", target_normals=None, normals_k=20):
     """Rigid point-to-point ICP: the float64 4 x 4 T that moves `source` onto `target` (transform_points(source, T) ~ target).
 
     Every iteration pairs each transformed source point with its exact nearest target point (ties to the lowest index), drops the pairs
@@ -297,23 +491,39 @@ def icp_align(source, target, max_iterations=50, tolerance=1e-9, max_distance=No
     k-th smallest squared distance tau is found exactly on the device, with no host wait.  with_scale=True: a similarity fit -- each
     iteration also estimates one scale (Umeyama), and the upper 3 x 3 of T is s R.  A similarity fit needs a sensible `init`: trimmed
     pairs plus a free scale can shrink a badly placed source onto a few target points.  With either argument an iteration moves 20
-    numbers, and the history entries are (count, rmse, candidates, tau); with both left at their defaults nothing changes."""
+    numbers, and the history entries are (count, rmse, candidates, tau); with both left at their defaults nothing changes.
+
+    method="point_to_plane": every iteration minimises the pairs' distances along the TARGET's normals instead of the distances
+    themselves, so two samplings of one smooth surface may slide along each other: a facade registers in a handful of iterations
+    where point-to-point pairs creep.  target_normals: a finite (nt, 3) array, one row per target point, of any orientation (the step
+    is even in the normal); None: estimated once on the device from the normals_k nearest target points (estimate_normals).  Each
+    iteration moves 32 numbers, solves a 6 x 6 system with a cut-off pseudo-inverse (plane_step_from_sums: a flat target leaves rank 3
+    and the source is moved into the plane, not along it) and stops once the RMS plane distance changed by less than `tolerance`.
+    History entries are (count, rmse_plane, rmse_point, rank), with (candidates, tau) appended under trim_fraction.  The method is
+    rigid: with_scale=True is a ValueError.  An iteration needs 6 pairs."""
     from . import device as dev
     s, sf = _cloud(source, "source")
     t, tf = _cloud(target, "target")
     _finite(s, "source")
     _finite(t, "target")
     _icp_args(len(s), len(t), max_iterations, tolerance, max_distance, init)
-    _trim_args(trim_fraction, with_scale)
+    _, scaled = _trim_args(trim_fraction, with_scale)
+    _method_args(method, scaled, normals_k, len(t), target_normals is not None)
+    nrm = _target_normals(target_normals, len(t))
     d_s = dev.from_numpy(s)
     d_t = d_s if target is source else dev.from_numpy(t)
+    d_n = None
     try:
+        if nrm is not None:
+            d_n = dev.from_numpy(nrm)
         return icp_align_resident(d_s, len(s), d_t, len(t), max_iterations, tolerance, max_distance, init, return_history, sf, tf,
-                                  trim_fraction, with_scale)
+                                  trim_fraction, with_scale, method, d_n, normals_k)
     finally:
         d_s.free()
         if d_t is not d_s:
             d_t.free()
+        if d_n is not None:
+            d_n.free()
 
 
 # ---- facade plane, box crop, four-way completion ---------------------------------------------------------------------------------------

@@ -532,7 +532,10 @@ def icp(reps, res, cpu_ref=True):
     reps) -- the difference over 9 is what an iteration costs once the target is binned.  With cpu_ref, 10 iterations of a host ICP
     on the same clouds (one cKDTree of the target, query with 16 workers, the same 3 x 3 solve) as context, not as a threshold.
     ICP/step_trimmed: the trimmed step with rho = 0.75 on the same index and inputs, device events, beside the plain step of the same
-    run.  SELECT/kth: the selection alone (csrc/select.hip) on the step's keys.  ICP/align_trimmed: the whole alignments with rho = 0.75."""
+    run.  ICP/normals: the target's normals from its 20 nearest neighbours (search and csrc/normals.hip; host wall clock, and the normals
+    entry alone on ready rows by device events).  ICP/step_plane: the point-to-plane step on those normals, untrimmed and with rho = 0.75,
+    device events, beside the plain step.  SELECT/kth: the selection alone (csrc/select.hip) on the step's keys.  ICP/align_trimmed: the
+    whole alignments with rho = 0.75."""
     import math
     from pb3d import preprocess_helpers as ph
     lib, L = pb3d._lib.load(), pb3d._lib
@@ -551,7 +554,7 @@ def icp(reps, res, cpu_ref=True):
     ntaj = n.value
     taj_pts = d_tp.download((ntaj, 3), np.float32)
     clouds = {"taj_full": (d_tp, ntaj, False, taj_pts), "sfm20k": (dev.from_numpy(sfm_vox), 20000, True, sfm_vox)}
-    d_out, d_out20 = dev.DeviceBuffer(17 * 8), dev.DeviceBuffer(20 * 8)
+    d_out, d_out20, d_out32 = dev.DeviceBuffer(17 * 8), dev.DeviceBuffer(20 * 8), dev.DeviceBuffer(32 * 8)
 
     def displaced(host):
         lo, hi = host.min(0).astype(np.float64), host.max(0).astype(np.float64)
@@ -600,6 +603,27 @@ def icp(reps, res, cpu_ref=True):
              "Mpoint_s": round(ns / step_ms / 1e3, 1), "rmse": math.sqrt(raw[16] / ns)}
         print(json.dumps(r), flush=True)
         res.append(r)
+        # the target's normals (exact 20-neighbour rows, then csrc/normals.hip; two host waits, so host wall clock) and the
+        # point-to-plane step on them beside the plain step: same index, same inputs, untrimmed and with rho = 0.75
+        normals_ms = wall(lambda: ph.estimate_normals_resident(dt, nt, 20, None, tf).free())
+        d_nrm = ph.estimate_normals_resident(dt, nt, 20, None, tf)
+        d_idx = pb3d.eval_helpers.knn_resident(dt, nt, dt, nt, 20, tf, tf, dist=False)[1]
+        kernel_ms = timeit(lambda: L.check(lib.pb3d_point_normals_resident(L.ctx(), C.c_void_p(dt.ptr), int(tf), nt, C.c_void_p(d_idx.ptr), 20,
+                                                                           None, C.c_void_p(d_nrm.ptr))), reps)
+        r = {"op": "ICP/normals", "name": f"estimate_normals_resident, k 20: {tn}", "n": nt, "wall_ms": normals_ms,
+             "normals_entry_ms": round(kernel_ms, 4), "Mpoint_s": round(nt / normals_ms / 1e3, 2)}
+        print(json.dumps(r), flush=True)
+        res.append(r)
+        plane_ms = timeit(lambda: ph.icp_step_plane_resident(ds, ns, dt, nt, d_nrm, init, -1.0, None, c, sf, tf, out=d_out32), reps)
+        raw = d_out32.download((32,), np.float64)
+        plane_trim_ms = timeit(lambda: ph.icp_step_plane_resident(ds, ns, dt, nt, d_nrm, init, -1.0, 0.75, c, sf, tf, out=d_out32), reps)
+        r = {"op": "ICP/step_plane", "name": f"icp point-to-plane step: {sn} -> {tn}", "ns": ns, "nt": nt, "step_ms": round(step_ms, 4),
+             "step_plane_ms": round(plane_ms, 4), "plane_over_plain": round(plane_ms / step_ms, 3), "step_plane_trimmed_ms": round(plane_trim_ms, 4),
+             "Mpoint_s": round(ns / plane_ms / 1e3, 1), "rmse_plane": math.sqrt(raw[28] / ns), "rmse_point": math.sqrt(raw[29] / ns)}
+        print(json.dumps(r), flush=True)
+        res.append(r)
+        d_nrm.free()
+        d_idx.free()
         # the trimmed step beside it (same index, same inputs, rho = 0.75), and the selection alone on the step's keys: the squared
         # nearest distances of the moved source (nn_distances squared: the step's d2 up to the rounding of the square root)
         trim_ms = timeit(lambda: ph.icp_step_trimmed_resident(ds, ns, dt, nt, init, -1.0, 0.75, c, c, sf, tf, out=d_out20), reps)
@@ -644,7 +668,7 @@ def icp(reps, res, cpu_ref=True):
              "count_last": hist[-1][0]}
         print(json.dumps(r), flush=True)
         res.append(r)
-    for b in [d_g, d_tc, d_out, d_out20] + [c[0] for c in clouds.values()]:
+    for b in [d_g, d_tc, d_out, d_out20, d_out32] + [c[0] for c in clouds.values()]:
         b.free()
 
 
