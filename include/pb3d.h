@@ -335,6 +335,70 @@ int pb3d_vertex_normals_dev(pb3d_ctx* ctx, const void* d_verts, int verts_f64, i
 int pb3d_surface_metrics_dev(pb3d_ctx* ctx, const void* d_verts, const void* d_normals, int verts_f64, int64_t nv, const int32_t* d_idx, int k,
                              double* d_normal_std, double* d_roughness, double* d_curvature);
 
+/* ---- a triangle mesh as a comparison target: exact point-to-mesh distances and area-weighted surface samples (step 7 of the reference's
+ * results/4.Inter-method_3D/README.md, "load and align a CAD reference model": its geometry; there is no upstream text, so the arithmetic
+ * below is the specification) -------------------------------------------------------------------------------------------------------
+ * Vertices and faces as for the mesh regularity entries: (nv, 3) rows of float32 (verts_f64 = 0) or float64 (1), (nf, 3) rows of int32
+ * (faces_i64 = 0) or int64 (1), at most 2^31 - 1 of each, any 4- / 8-byte aligned base.  Both entries first check the face indices on
+ * the device: one outside [-nv, nv) is PB3D_EINDEX before any kernel gathers through them (one host wait); indices in [-nv, -1] wrap.
+ * All arithmetic is float64 (float32 vertices and queries are widened first, which is exact), every product, sum, difference, quotient
+ * and square root ONE correctly rounded operation, no FMA.  dot(x, y) = (x0*y0 + x1*y1) + x2*y2; a cross component is one product
+ * minus one product: cross(x, y) = (x1*y2 - x2*y1, x2*y0 - x0*y2, x0*y1 - x1*y0).  div0(x, y) = 0 if y == 0, else x / y.
+ *
+ * mesh_dist: for each of the nq queries (d_q: (nq, 3) rows, float32 or float64 by q_f64) the nearest point of the mesh surface.
+ *   d2(q, face (a, b, c)) and the face's closest point cp:
+ *     ab = b - a, ac = c - a, n = cross(ab, ac).
+ *     If dot(n, n) == 0 the face is DEGENERATE: cp is the best of the segments a->b, b->c, c->a in that order, a later one only if its
+ *       squared distance is strictly smaller.  Segment s0->s1: e = s1 - s0, dd = dot(e, e), t = dot(q - s0, e),
+ *       t = dd == 0 ? 0 : min(max(t / dd, 0), 1), cp = s0 + e*t (per component one product, one sum).
+ *     Otherwise the region walk of Ericson, Real-Time Collision Detection 5.1.5, in its order; the first test that holds decides:
+ *       1. ap = q - a, d1 = dot(ab, ap), d2 = dot(ac, ap);  d1 <= 0 && d2 <= 0                    -> cp = a
+ *       2. bp = q - b, d3 = dot(ab, bp), d4 = dot(ac, bp);  d3 >= 0 && d4 <= d3                   -> cp = b
+ *       3. vc = d1*d4 - d3*d2;  vc <= 0 && d1 >= 0 && d3 <= 0                                      -> cp = a + ab*div0(d1, d1 - d3)
+ *       4. cq = q - c, d5 = dot(ab, cq), d6 = dot(ac, cq);  d6 >= 0 && d5 <= d6                   -> cp = c
+ *       5. vb = d5*d2 - d1*d6;  vb <= 0 && d2 >= 0 && d6 <= 0                                      -> cp = a + ac*div0(d2, d2 - d6)
+ *       6. va = d3*d6 - d5*d4, u1 = d4 - d3, u2 = d5 - d6;  va <= 0 && u1 >= 0 && u2 >= 0           -> cp = b + (c - b)*div0(u1, u1 + u2)
+ *       7. else den = div0(1, (va + vb) + vc)                                                      -> cp = (a + ab*(vb*den)) + ac*(vc*den)
+ *     d = q - cp, d2 = (dx*dx + dy*dy) + dz*dz.
+ *   The result for q is the face with the smallest (d2 as computed, face index) -- ties go to the lowest index, so the result is a
+ *   function of the input alone, as knn's is:  d_dist[i] = sqrt(d2) (nq float64), d_face[i] = that face (nq int32, or NULL),
+ *   d_closest[i] = its cp (nq x 3 float64, or NULL).  nq = 0 does nothing; nf = 0 (or nv = 0) with nq > 0 is PB3D_EINVAL.  Queries and
+ *   vertices must be finite, and small enough that no product above overflows; vertices that are not finite are refused (PB3D_EINVAL).
+ *   Accuracy: d2 is the squared distance to a point OF the face (up to the rounding of cp), so it never undershoots the true distance by
+ *   more than a few ulps of the coordinates; on a sliver it can overshoot, because Ericson's barycentric quotients lose accuracy with the
+ *   aspect (smallest height over longest edge): at most 4 ulps of the coordinate magnitude for aspect >= 1e-3, growing below.  Measured
+ *   overshoot of the distance over the same algorithm in 80-bit long double, coordinates up to 1e3, aspect in [column, 10 x column):
+ *       aspect        1e-1     1e-2     1e-3     1e-4     1e-5     1e-6     1e-7     1e-8
+ *       ulps of 1e3   1.25     1.07     0.98     7.5      5.7e4    9.3e8    1.4e12   2.2e14
+ *       relative      3.5e-10  2.4e-10  3.1e-10  9.5e-11  3.9e-7   5.4e-3   9.8      4.3e2
+ *   Index: the cell grid of nn_dist over the exact box of ALL vertices, sized from nf; a face is listed in every cell of the box
+ *   cell(min corner) .. cell(max corner) per axis.  While the (cell, face) entries exceed 8 * nf and the grid has more than one cell,
+ *   the cells per axis are halved.  Host waits: the index check, the box, and 1 + (number of halvings) for the entry counts; the query
+ *   itself is enqueued.  Scratch: 72 bytes per face, 4 bytes per entry, 12 bytes per cell.
+ * mesh_grid_shape: the cells per axis, the entry count and (if not NULL) the number of halvings of the index the last mesh_dist call on
+ *   this context built (no device work; PB3D_EINVAL before the first such call).
+ * mesh_sample: n points of the surface, stratified by area, a function of (mesh, n, seed) alone.  d_pts: n x 3 float64; d_face: the
+ *   int32 face of each sample, or NULL.
+ *     area    A_f = 0.5 * sqrt(dot(n, n)), n as above.
+ *     prefix  in blocks of 1024 faces: local[f] = the left-to-right running sum inside f's block, starting from the block's first area;
+ *             O_b = the left-to-right running sum of the totals (last local) of the blocks before b, O_0 = 0;  cum[f] = O_b + local[f];
+ *             total = cum[nf - 1].  cum is non-decreasing by construction.
+ *     random  mix(x): x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) * 0x94D049BB133111EB;
+ *             x ^ x >> 31, in uint64 wrap-around arithmetic;  r_j(i) = (double)(mix(mix(seed) + 3*i + j) >> 11) * 2^-53, in [0, 1).
+ *     face    u = ((double)i + r_0) / (double)n * total;  f = the smallest face with cum[f] > u (np.searchsorted(cum, u, 'right')),
+ *             clamped to nf - 1.  A zero-area face has cum[f] == cum[f - 1] and is never that smallest face; the clamp is reached only
+ *             if u rounds up to total itself.
+ *     point   s = sqrt(r_1), wa = 1 - s, wb = s*(1 - r_2), wc = s*r_2;  each coordinate (a*wa + b*wb) + c*wc.
+ *   Sample i lies in stratum [i, i + 1) / n of the cumulative area, so the samples of a face differ from n * A_f / total by less than 2.
+ *   n = 0 does nothing.  nf = 0 with n > 0, or a total that is 0 or not finite, is PB3D_EINVAL.  Host waits: the index check and the
+ *   total.  Scratch: 8 bytes per face. */
+int pb3d_mesh_dist_resident(pb3d_ctx* ctx, const void* d_q, int q_f64, int64_t nq, const void* d_verts, int verts_f64, int64_t nv,
+                            const void* d_faces, int faces_i64, int64_t nf, double* d_dist /* nq */, int32_t* d_face /* nq or NULL */,
+                            double* d_closest /* nq x 3 or NULL */);
+int pb3d_mesh_grid_shape(const pb3d_ctx* ctx, int64_t cells[3], int64_t* entries, int64_t* coarsenings /* or NULL */);
+int pb3d_mesh_sample_resident(pb3d_ctx* ctx, const void* d_verts, int verts_f64, int64_t nv, const void* d_faces, int faces_i64, int64_t nf,
+                              int64_t n, uint64_t seed, double* d_pts /* n x 3 */, int32_t* d_face /* n or NULL */);
+
 /* ---- density volume of a point cloud, reference utils/eval_helpers.py:178-189 (pointcloud_to_voxel_grid) ---------------------------
  * d_out: grid_size^3 float32, bit for bit the reference's volume for the resident (n, 3) list d_pts (float32 rows, or float64 with
  * pts_f64 = 1; any 4- / 8-byte aligned base):

@@ -160,8 +160,21 @@ enum pb3d_slot : int {
     PB3D_SLOT_SELECT = 81,
     // call-local, csrc/icp.hip: a trimmed step's header (candidate count, rank, tau) and the selection keys of its pairs
     PB3D_SLOT_ICP_KEYS = 82,
+    // call-local, csrc/meshdist.hip, the triangle index of pb3d_mesh_dist_resident: the nf x 9 float64 corner table, the vertex box and the
+    // entry total read back by the host, per-cell counts (then the scatter's cursors), cell starts, face ids in cell order and the two
+    // slots of its pb3d_scan_counts.  The query half and the bounds pass inside use NN_QUERY_*, NN_ORDER, NN_SCAN_* and NN_BOUNDS_PARTIALS
+    PB3D_SLOT_MESHD_CORNERS = 83,
+    PB3D_SLOT_MESHD_READBACK = 84,
+    PB3D_SLOT_MESHD_COUNTS = 85,
+    PB3D_SLOT_MESHD_STARTS = 86,
+    PB3D_SLOT_MESHD_IDS = 87,
+    PB3D_SLOT_MESHD_SCAN_LOCAL = 88,
+    PB3D_SLOT_MESHD_SCAN_SEGS = 89,
+    // call-local, csrc/meshdist.hip, pb3d_mesh_sample_resident: the nf cumulative areas and the per-block totals / offsets
+    PB3D_SLOT_MSAMPLE_CUM = 90,
+    PB3D_SLOT_MSAMPLE_BLOCKS = 91,
 
-    PB3D_SLOT_COUNT = 83
+    PB3D_SLOT_COUNT = 92
 };
 
 // ---- the cell index of the exact nearest-neighbour search (csrc/nn.hip) -----------------------------------
@@ -270,6 +283,9 @@ struct pb3d_ctx {
     // the target index of an alignment (csrc/icp.hip, PB3D_SLOT_ICP_INDEX_*): built by pb3d_icp_index_resident for this (pointer, count,
     // width), read by every pb3d_icp_step_resident.  gen = scratch_slot_gen of the three slots when it was written.
     struct IcpIndex { bool valid; const void* tgt; i64 nt; int f64; u64 gen[3]; pb3d_nn_index ix; } icp_index;
+    // the triangle index of the last pb3d_mesh_dist_resident (csrc/meshdist.hip), for pb3d_mesh_grid_shape: cells per axis, (cell, face)
+    // entries, and how often the grid was coarsened to respect the entry cap
+    struct MeshGridLast { bool valid; i64 cells[3], entries, coarsenings; } mesh_grid_last;
     // Device block pool behind pb3d_dev_alloc / pb3d_dev_free: a freed block is kept (no hipFree, no stream synchronisation) and handed
     // to the next request of about its size.  Everything that touches such a block runs on ctx->stream, in order, so a re-used block
     // is never written before its previous reader has finished.  The NumPy-signature API allocates and frees a volume-sized buffer
@@ -396,6 +412,9 @@ int pb3d_scan_counts(pb3d_ctx* ctx, const u32* d_counts, i64 n, i64* d_offsets, 
 int pb3d_nn_index_build(pb3d_ctx* ctx, const void* d_r, int r_f64, i64 nr, pb3d_slot starts_slot, pb3d_slot coords_slot, pb3d_slot ids_slot,
                         pb3d_nn_index* ix);
 int pb3d_nn_index_nearest(pb3d_ctx* ctx, const pb3d_nn_index& ix, const double* d_q, i64 nq, int* d_idx);
+// csrc/nn.hip for csrc/meshdist.hip: the positions of the nq >= 1 queries in the cell order of grid g -> *order (PB3D_SLOT_NN_ORDER;
+// enqueued)
+int pb3d_nn_order_queries(pb3d_ctx* ctx, const void* d_q, int q_f64, i64 nq, const pb3d_nn_grid& g, const u32** order);
 // csrc/select.hip for csrc/icp.hip: pb3d_kth_smallest_resident with the rank read from device memory when the selection runs
 // (0 <= *d_rank < n; 1 <= n <= 2^31 - 1; enqueued)
 int pb3d_select_kth(pb3d_ctx* ctx, const double* d_vals, i64 n, const i64* d_rank, double* d_out);

@@ -20,6 +20,7 @@ from .eval_helpers import (chamfer_distance, compute_f1_curve, compute_nn_distan
 from .eval_helpers import (compute_surface_metrics, compute_triangle_normals, compute_vertex_normals, knn,  # noqa: F401
                            surface_metrics_per_vertex)
 from .eval_helpers import density_grid_resident, pointcloud_to_voxel_grid  # noqa: F401
+from .eval_helpers import cloud_to_mesh_metrics, point_to_mesh_distances, sample_mesh_points  # noqa: F401
 from .preprocess_helpers import (best_fit_transform_from_sums, flip_y_axis, icp_align, icp_align_resident, normalize_preserve_aspect,  # noqa: F401
                                  transform_points, transform_points_resident)
 from .preprocess_helpers import best_fit_similarity_from_sums, icp_step_trimmed_resident  # noqa: F401

@@ -147,6 +147,9 @@ _SIGNATURES = {
     "pb3d_triangle_normals_dev": [vp, vp, C.c_int, i64, vp, C.c_int, i64, vp],
     "pb3d_vertex_normals_dev": [vp, vp, C.c_int, i64, vp, C.c_int, i64, vp],
     "pb3d_surface_metrics_dev": [vp, vp, vp, C.c_int, i64, vp, C.c_int, vp, vp, vp],
+    "pb3d_mesh_dist_resident": [vp, vp, C.c_int, i64, vp, C.c_int, i64, vp, C.c_int, i64, vp, vp, vp],
+    "pb3d_mesh_grid_shape": [vp, i64p, i64p, i64p],
+    "pb3d_mesh_sample_resident": [vp, vp, C.c_int, i64, vp, C.c_int, i64, i64, C.c_uint64, vp, vp],
     "pb3d_density_grid_resident": [vp, vp, C.c_int, i64, C.c_int, dblp, C.c_int, vp],
     "pb3d_grid_bounds_resident": [vp, vp, i64, i64, i64, C.c_int, u8p, C.c_int, vp],
     "pb3d_grid_hit_bits_resident": [vp, vp, i64, i64, i64, C.c_int, u8p, C.c_int, dblp, dblp, C.c_double, C.c_double, C.c_double, intp, C.c_int,

@@ -23,6 +23,12 @@ cell of np.add.at stops at 2^24, so the value is min(count, 2^24)), then the ref
 float64 summation order per output, float32 between the passes, reflect boundary, no FMA -- and the zero faces.  The volume is bit
 for bit the reference's at any point count, so full-resolution clouds and finer grids need no downsampling.
 
+point_to_mesh_distances, sample_mesh_points and cloud_to_mesh_metrics have no upstream text (the reference's README names the step,
+"load and align a CAD reference model", and ships no code for it): a mesh as the other side of the comparison.  csrc/meshdist.hip finds
+the exact nearest point of the surface for every point of a cloud on the cell index of the NN search, with triangles in the cells, and
+draws stratified area-weighted samples that turn a mesh into a cloud for every metric above and for icp_align; include/pb3d.h states
+both to the bit.
+
 Not mirrored: get_marching_cubes_mesh (no scikit-image here to take float-level marching-cubes fixtures from)."""
 import ctypes as C
 import operator
@@ -35,7 +41,9 @@ __all__ = ["filter_mesh", "chamfer_distance", "fscore_with_threshold", "pca_shap
            "compute_nn_distances", "f1_curve_from_distances", "compute_f1_curve", "nn_distances", "nn_distances_resident",
            "points_bounds_resident", "voxel_iou_counts_resident", "voxel_iou_counts", "knn", "knn_resident", "compute_triangle_normals",
            "compute_vertex_normals", "compute_surface_metrics", "surface_metrics_per_vertex", "triangle_normals_resident",
-           "vertex_normals_resident", "surface_metrics_resident", "KNN_MAX_K", "pointcloud_to_voxel_grid", "density_grid_resident"]
+           "vertex_normals_resident", "surface_metrics_resident", "KNN_MAX_K", "pointcloud_to_voxel_grid", "density_grid_resident",
+           "point_to_mesh_distances", "point_to_mesh_distances_resident", "mesh_grid_shape", "sample_mesh_points",
+           "sample_mesh_points_resident", "cloud_to_mesh_metrics"]
 
 KNN_MAX_K = 32      # PB3D_KNN_MAX_K
 DENSITY_MAX_GRID = 1024     # the limits of pb3d_density_grid_resident
@@ -492,6 +500,135 @@ def compute_surface_metrics(vertices, faces, k=20):
         "Mean Roughness (λ₃)": np.mean(roughness_vals),
         "Mean Curvature": np.mean(mean_curvatures),
     }
+
+
+# ---- a triangle mesh as a comparison target (csrc/meshdist.hip; include/pb3d.h states the arithmetic) ---------------------------------
+def point_to_mesh_distances_resident(d_P, nP, d_verts, nv, d_faces, nf, p_f64=True, verts_f64=False, faces_i64=False, return_faces=False,
+                                     return_closest=False):
+    """pb3d_mesh_dist_resident: (DeviceBuffer of nP float64 distances, DeviceBuffer of nP int32 nearest faces or None, DeviceBuffer of
+    nP x 3 float64 closest points or None) of the resident (nP, 3) list d_P against the resident mesh (IndexError on a bad face index).
+    Points and vertices must be finite."""
+    from . import device as dev
+    nP = int(nP)
+    bufs = [dev.DeviceBuffer(max(1, nP) * 8), dev.DeviceBuffer(max(1, nP) * 4) if return_faces else None,
+            dev.DeviceBuffer(max(1, nP) * 24) if return_closest else None]
+    try:
+        _lib.check(_lib.load().pb3d_mesh_dist_resident(_lib.ctx(), _ptr(d_P), int(bool(p_f64)), nP, _ptr(d_verts), int(bool(verts_f64)), int(nv),
+                                                       _ptr(d_faces), int(bool(faces_i64)), int(nf), *[_ptr(b) for b in bufs]))
+    except BaseException:
+        for b in bufs:
+            if b is not None:
+                b.free()
+        raise
+    return tuple(bufs)
+
+
+def mesh_grid_shape():
+    """pb3d_mesh_grid_shape: ((cells per axis), entries, halvings) of the triangle index the last point-to-mesh search built"""
+    cells, entries, halvings = (C.c_int64 * 3)(), C.c_int64(0), C.c_int64(0)
+    _lib.check(_lib.load().pb3d_mesh_grid_shape(_lib.ctx(), cells, C.byref(entries), C.byref(halvings)))
+    return tuple(cells), entries.value, halvings.value
+
+
+def _mesh_on_device(vertices, faces, what):
+    """(vertices, flag, faces) validated for the mesh entries: at least one face, finite vertices"""
+    v, vf, f = _mesh_arrays(vertices, faces)
+    if len(f) == 0:
+        raise ValueError(f"{what}: the mesh has no faces")
+    if len(v) == 0:
+        v[f[:, 0]]                                                      # NumPy's IndexError
+    _finite(v, "vertices")
+    return v, vf, f
+
+
+def point_to_mesh_distances(P, vertices, faces, return_faces=False, return_closest=False):
+    """float64 (len(P),) array: the distance from each point of P to the nearest point of the mesh surface, exact in the sense of
+    include/pb3d.h (Ericson's closest point on every candidate face in float64, the minimum over ALL faces, ties to the lowest face).
+    With return_faces also the int32 face index of each point, with return_closest also the (len(P), 3) float64 closest points, in
+    that order."""
+    from . import device as dev
+    p, pf = _cloud(P, "P")
+    _finite(p, "P")
+    if len(p) == 0:
+        out = (np.zeros(0, np.float64),) + ((np.zeros(0, np.int32),) if return_faces else ()) + \
+            ((np.zeros((0, 3), np.float64),) if return_closest else ())
+        return out if len(out) > 1 else out[0]
+    v, vf, f = _mesh_on_device(vertices, faces, "point_to_mesh_distances")
+    bufs = [dev.from_numpy(p), dev.from_numpy(v), dev.from_numpy(f)]
+    try:
+        outs = point_to_mesh_distances_resident(bufs[0], len(p), bufs[1], len(v), bufs[2], len(f), pf, vf, True, return_faces, return_closest)
+        bufs += [b for b in outs if b is not None]
+        res = [outs[0].download((len(p),), np.float64)]
+        if return_faces:
+            res.append(outs[1].download((len(p),), np.int32))
+        if return_closest:
+            res.append(outs[2].download((len(p), 3), np.float64))
+        return tuple(res) if len(res) > 1 else res[0]
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def _sample_args(n, seed):
+    n, seed = operator.index(n), operator.index(seed)
+    if n < 0:
+        raise ValueError(f"n must be >= 0 (got {n})")
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError(f"seed must be in [0, 2^64) (got {seed})")
+    return n, seed
+
+
+def sample_mesh_points_resident(d_verts, nv, d_faces, nf, n, seed=0, verts_f64=False, faces_i64=False, return_faces=True):
+    """pb3d_mesh_sample_resident: (DeviceBuffer of n x 3 float64 surface points, DeviceBuffer of n int32 faces or None), stratified by
+    area and a function of (mesh, n, seed) alone (ValueError if the mesh's area is 0, IndexError on a bad face index)"""
+    from . import device as dev
+    n, seed = _sample_args(n, seed)
+    d_pts = dev.DeviceBuffer(max(1, n) * 24)
+    d_face = dev.DeviceBuffer(max(1, n) * 4) if return_faces else None
+    try:
+        _lib.check(_lib.load().pb3d_mesh_sample_resident(_lib.ctx(), _ptr(d_verts), int(bool(verts_f64)), int(nv), _ptr(d_faces),
+                                                         int(bool(faces_i64)), int(nf), n, seed, _ptr(d_pts), _ptr(d_face)))
+    except BaseException:
+        d_pts.free()
+        if d_face is not None:
+            d_face.free()
+        raise
+    return d_pts, d_face
+
+
+def sample_mesh_points(vertices, faces, n, seed=0, return_faces=False):
+    """(n, 3) float64 points of the mesh surface, area-weighted and stratified: sample i falls in the i-th of n equal slices of the
+    cumulative face area, so consecutive samples lie on consecutive faces and every face gets its share to within 2 samples.  The
+    same (mesh, n, seed) gives the same bytes.  With return_faces also the int32 face of each sample."""
+    from . import device as dev
+    n, seed = _sample_args(n, seed)
+    if n == 0:
+        return (np.zeros((0, 3), np.float64), np.zeros(0, np.int32)) if return_faces else np.zeros((0, 3), np.float64)
+    v, vf, f = _mesh_on_device(vertices, faces, "sample_mesh_points")
+    bufs = [dev.from_numpy(v), dev.from_numpy(f)]
+    try:
+        d_pts, d_face = sample_mesh_points_resident(bufs[0], len(v), bufs[1], len(f), n, seed, vf, True, return_faces)
+        bufs += [b for b in (d_pts, d_face) if b is not None]
+        pts = d_pts.download((n, 3), np.float64)
+        return (pts, d_face.download((n,), np.int32)) if return_faces else pts
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def cloud_to_mesh_metrics(P, vertices, faces, tau, n_samples=None, seed=0):
+    """A cloud against a mesh, both ways: accuracy = mean distance of P to the surface, completeness = mean distance of n_samples
+    (default len(P)) area-weighted surface samples to P, precision / recall = the shares of each below tau (strict), and their F1 as
+    fscore_with_threshold forms it."""
+    d_P = point_to_mesh_distances(P, vertices, faces)
+    S = sample_mesh_points(vertices, faces, len(d_P) if n_samples is None else n_samples, seed)
+    d_S = nn_distances(S, P)
+    precision = float(np.mean(d_P < tau))
+    recall = float(np.mean(d_S < tau))
+    f1 = 0.0 if (precision + recall) == 0 else (
+        2 * precision * recall / (precision + recall)
+    )
+    return {"accuracy": float(np.mean(d_P)), "completeness": float(np.mean(d_S)), "precision": precision, "recall": recall, "f1": f1}
 
 
 # ---- F1 curve (:214-263) ---------------------------------------------------------------------------------------------------------------

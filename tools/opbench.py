@@ -1,5 +1,5 @@
 """Device-resident timing of every op of the path (M1..M8 of SURVEY.md 8(d), plus the N1/N2 kernels of the notebook-1 chain) on
-synthetic inputs.  Development/measurement tool: python tools/opbench.py [--size 1024] [--shape WxHxD] [--ops M1,M3,...,N2,overlays,ICP,PLANE]; one JSON
+synthetic inputs.  Development/measurement tool: python tools/opbench.py [--size 1024] [--shape WxHxD] [--ops M1,M3,...,N2,overlays,ICP,PLANE,MESHD]; one JSON
 line per op.  Pricing: `alg_B_per_voxel` is SURVEY 8(d)'s algorithmic figure for the sweeps that are EXECUTED (a folded 0-degree step
 moves nothing and is not priced); ops whose intermediates are not bytes (the bit-sliced chains) also carry `moved_B_per_voxel`, the
 bytes that cross the HBM by design, and their `frac_of_8TBs` is computed from THAT (never from bytes that are not moved)."""
@@ -260,6 +260,8 @@ def main():
         meshify(a.reps, res)
     if "DENS" in ops:
         density(a.reps, res, cpu_ref=not a.no_cpu_ref)
+    if "MESHD" in ops:
+        mesh_target(a.reps, res)
     if "overlays" in ops:
         overlays(a.reps, res)
     if d_col is not None:
@@ -805,6 +807,73 @@ def meshify(reps, res):
             print(json.dumps(r), flush=True)
             res.append(r)
         d.free()
+
+
+def mesh_target(reps, res):
+    """MESHD, a mesh as a comparison target (csrc/meshdist.hip) on the stored Taj grid at stride 1: every point of the grid
+    (pb3d_points_extract_dev, float32, mapped into the mesh's frame) against the mesh meshify_colored_voxel_grid makes of it (float32 vertices, int32 faces, resident).
+    MESHD/index: pb3d_mesh_dist_resident with ONE query -- the index check, the corner table, the box, the entry count(s), count / scan /
+    scatter, with their host waits.  MESHD/dist: all points, index build included, and beside it the yardstick pb3d_nn_dist_dev (k = 1) of
+    the same points against the mesh's VERTICES, its index build included too: the two are timed in turn, rep by rep, in the same run
+    (device events; median and min / max of reps after one warm-up of each).  MESHD/sample: 1 M samples, the prefix and its two waits
+    included."""
+    from pb3d.eval_helpers import (mesh_grid_shape, nn_distances_resident, point_to_mesh_distances_resident, sample_mesh_points_resident)
+    lib, L = pb3d._lib.load(), pb3d._lib
+    taj = np.load(os.path.join(ROOT, "tests", "golden", "stored_Taj_voxel_grid.npz"))["voxel_grid"]
+    nvox = int(np.prod(taj.shape[:3]))
+    d_g = dev.from_numpy(taj)
+    d_tp, d_tc = dev.DeviceBuffer(nvox * 12), dev.DeviceBuffer(nvox * 3)
+    n = C.c_int64(0)
+    L.check(lib.pb3d_points_extract_dev(L.ctx(), C.c_void_p(d_g.ptr), *taj.shape[:3], 3, None, 0, nvox, C.c_void_p(d_tp.ptr),
+                                        C.c_void_p(d_tc.ptr), C.byref(n)))
+    npts = n.value
+    pts = d_tp.download((npts, 3), np.float32)              # (a2, a1, a0); the mesh's frame is (a2, a1, shape[2] - a0) (csrc/mesh.hip)
+    pts[:, 2] = np.float32(taj.shape[2]) - pts[:, 2]
+    d_tp.upload(pts)
+    (dv, df, dn, dc), (nv, nf) = dev.meshify(d_g, taj.shape, stride=1, download=False)
+    d_nn = dev.DeviceBuffer(npts * 8)
+
+    def once(fn):
+        def run():
+            for b in fn():
+                if b is not None:
+                    b.free()
+        return timeit(run, 1, warm=0)
+
+    def mesh_dist(nq):
+        return lambda: point_to_mesh_distances_resident(d_tp, nq, dv, nv, df, nf, False, False, False, True, True)
+
+    def vertex_nn():
+        nn_distances_resident(d_tp, npts, dv, nv, 1, False, False, out=d_nn)
+        return []
+
+    def stats(t):
+        return {"ms": round(float(np.median(t)), 4), "min_max_ms": [round(min(t), 4), round(max(t), 4)]}
+
+    once(mesh_dist(1)); once(mesh_dist(npts)); once(vertex_nn)
+    t_index, t_dist, t_nn = [], [], []
+    for _ in range(reps):
+        t_index.append(once(mesh_dist(1)))
+        t_dist.append(once(mesh_dist(npts)))
+        t_nn.append(once(vertex_nn))
+    cells, entries, halvings = mesh_grid_shape()
+    base = {"op": "MESHD", "grid_shape": list(taj.shape[:3]), "points": int(npts), "nverts": int(nv), "nfaces": int(nf), "reps": reps}
+    rows = [dict(base, name="index build + one query (pb3d_mesh_dist_resident, nq = 1)", cells=list(cells), entries=int(entries),
+                 entries_per_face=round(entries / nf, 3), halvings=int(halvings), **stats(t_index)),
+            dict(base, name="point_to_mesh_distances_resident: every grid point -> its own mesh (distance, face, closest point)",
+                 Mquery_s=round(npts / float(np.median(t_dist)) / 1e3, 1), **stats(t_dist)),
+            dict(base, name="yardstick: pb3d_nn_dist_dev k = 1, the same points -> the mesh's vertices", Mquery_s=round(npts / float(np.median(t_nn)) / 1e3, 1),
+                 **stats(t_nn))]
+    rows[1]["ratio_to_vertex_nn"] = round(float(np.median(t_dist)) / float(np.median(t_nn)), 2)
+    once(lambda: sample_mesh_points_resident(dv, nv, df, nf, 1000000, 0, False, False))
+    t_s = [once(lambda: sample_mesh_points_resident(dv, nv, df, nf, 1000000, 0, False, False)) for _ in range(reps)]
+    rows.append(dict(base, name="sample_mesh_points_resident: 1 000 000 samples with their faces", Msample_s=round(1e3 / float(np.median(t_s)), 1),
+                     **stats(t_s)))
+    for r in rows:
+        print(json.dumps(r), flush=True)
+        res.append(r)
+    for b in (d_g, d_tp, d_tc, dv, df, dn, dc, d_nn):
+        b.free()
 
 
 def density(reps, res, cpu_ref=True):
