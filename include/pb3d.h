@@ -542,6 +542,41 @@ int pb3d_plane_moments_resident(pb3d_ctx* ctx, const void* d_pts, int pts_f64, i
 int pb3d_points_crop_box_resident(pb3d_ctx* ctx, const void* d_pts, int pts_f64, int64_t n, const double lo[3], const double hi[3], void* d_out,
                                   int32_t* d_idx, int64_t* d_count);
 
+/* ---- cluster_points: exact DBSCAN of a point cloud, the segmentation step of the same preprocessing (csrc/cluster.hip) ----------------
+ * Point lists as above: (n, 3) rows of float32 (pts_f64 = 0, widened first) or float64 (1), 0 <= n <= 2^31 - 1, coordinates finite
+ * (the caller's duty).  eps finite and > 0, min_samples >= 1, else PB3D_EINVAL.  The result is scikit-learn's
+ * DBSCAN(eps, min_samples).labels_ / core_sample_indices_ to the bit, and a function of the input alone:
+ *   NEIGHBOUR  q is a neighbour of p iff d2 = (dx*dx + dy*dy) + dz*dz <= eps2, with dx = p.x - q.x and so on in float64, every product
+ *              and sum rounded on its own (no FMA), and eps2 = eps * eps one rounded product made once on the host.  d2 has the same
+ *              bits with p and q exchanged; a point is its own neighbour (d2 = 0).
+ *   COUNTS     counts[p] = the number of neighbours of p, itself included: an exact integer (radius outlier removal is counts >= m).
+ *   CORE       core[p] = counts[p] >= min_samples.
+ *   CLUSTERS   the connected components of the neighbour graph restricted to core points.  The ROOT of a cluster is its smallest core
+ *              position in the caller's list; clusters are numbered 0, 1, ... by increasing root.
+ *   BORDER     a non-core point with at least one core neighbour takes the smallest label among its core neighbours.
+ *   NOISE      a non-core point with no core neighbour: label -1.
+ *   SIZES      sizes[c] = the number of points, core and border, labelled c.
+ * radius_count: d_counts (n uint32 on the device) = COUNTS.  One host wait (the cloud's bounding box, for the cell index).
+ * cluster_points: d_labels (n int32), d_core (n bytes, 0 / 1), d_counts (n uint32) and d_sizes (int64, capacity n entries; the first
+ *   *nclusters are written) on the device, *nclusters on the host.  Two host waits: the bounding box and the number of clusters.
+ *   n = 0: *nclusters = 0, nothing written.
+ * labels_member: d_keep[i] (n bytes on the device) = 1 when 0 <= d_labels[i] < nlabels and chosen[d_labels[i]] != 0 (chosen: nlabels
+ *   bytes on the host, staged: it may be reused on return), else 0.  No host wait.
+ * points_select: pb3d_points_crop_box_resident with the predicate d_keep[i] != 0 (n bytes on the device) in the box's place: the
+ *   surviving rows byte for byte in the input's dtype and order at the front of d_out (capacity n rows), their positions in d_idx
+ *   (int32, may be NULL), the count in d_count (one int64 on the device).  No host wait.
+ * cluster_last: the cells per axis of the index of the last radius_count / cluster_points on this context and, with pass_ms not NULL,
+ *   the milliseconds its passes took (index, count, union + flatten, ranks, labels) -- recorded only under the development knob
+ *   "cluster_timing" (pb3d_set_tuning; one more host wait), else PB3D_EINVAL.  Knob "cluster_cell" picks the index's cell edge
+ *   (0: the built-in rule, 1: two points per cell, 2: above eps); no result depends on either knob. */
+int pb3d_radius_count_resident(pb3d_ctx* ctx, const void* d_pts, int pts_f64, int64_t n, double eps, uint32_t* d_counts);
+int pb3d_cluster_points_resident(pb3d_ctx* ctx, const void* d_pts, int pts_f64, int64_t n, double eps, int64_t min_samples, int32_t* d_labels,
+                                 uint8_t* d_core, uint32_t* d_counts, int64_t* d_sizes, int64_t* nclusters);
+int pb3d_labels_member_resident(pb3d_ctx* ctx, const int32_t* d_labels, int64_t n, const uint8_t* chosen, int64_t nlabels, uint8_t* d_keep);
+int pb3d_points_select_resident(pb3d_ctx* ctx, const void* d_pts, int pts_f64, int64_t n, const uint8_t* d_keep, void* d_out, int32_t* d_idx,
+                                int64_t* d_count);
+int pb3d_cluster_last(pb3d_ctx* ctx, int64_t cells[3], double pass_ms[5] /* or NULL */);
+
 /* ---- notebook 2: bbox camera init and projection overlays, reference utils/camera_estimation.py:56-108, :346-477 ----------------
  * grid_bounds: d_out[0] = the number of voxels of the resident (A0,A1,A2,C) grid whose colour (C = 3) / label (C = 1) is one of the
  *   ncolors <= 31 non-zero `colors` (ncolors = 0: any non-zero voxel), d_out[1..3] = their inclusive minimum (a0, a1, a2), d_out[4..6]

@@ -391,7 +391,14 @@ int launch_knn(pb3d_ctx* ctx, const pb3d_nn_index& ix, const void* d_q, int q_f6
 // ---- the index kept between calls (csrc/icp.hip): pb3d_knn_dev's two halves, the reference half into the caller's slots ------------
 int pb3d_nn_index_build(pb3d_ctx* ctx, const void* d_r, int r_f64, i64 nr, pb3d_slot starts_slot, pb3d_slot coords_slot, pb3d_slot ids_slot,
                         pb3d_nn_index* ix) {
+    return pb3d_nn_index_build_edge(ctx, d_r, r_f64, nr, 0.0, starts_slot, coords_slot, ids_slot, ix);
+}
+
+// ... with cells whose edge exceeds min_edge where min_edge > 0 (coarsen_grid; csrc/cluster.hip: the radius of a fixed-radius search)
+int pb3d_nn_index_build_edge(pb3d_ctx* ctx, const void* d_r, int r_f64, i64 nr, double min_edge, pb3d_slot starts_slot, pb3d_slot coords_slot,
+                             pb3d_slot ids_slot, pb3d_nn_index* ix) {
     PB3D_TRY(grid_of(ctx, d_r, r_f64, nr, &ix->g));
+    if (min_edge > 0.0) coarsen_grid(ix->g, min_edge);
     return index_reference(ctx, d_r, r_f64, nr, starts_slot, coords_slot, &ids_slot, ix);
 }
 

@@ -173,8 +173,23 @@ enum pb3d_slot : int {
     // call-local, csrc/meshdist.hip, pb3d_mesh_sample_resident: the nf cumulative areas and the per-block totals / offsets
     PB3D_SLOT_MSAMPLE_CUM = 90,
     PB3D_SLOT_MSAMPLE_BLOCKS = 91,
+    // call-local, csrc/cluster.hip, all of them: the cloud's cell index against itself (cell starts, cell-sorted SoA coordinates, each
+    // sorted point's position in the caller's list), the union-find's parent per point, the root flags, their ranks (n + 1 int64) and
+    // the two slots of that pb3d_scan_counts; the chosen-label table of pb3d_labels_member_resident.  Slots of their own: the index is
+    // read by three walks with scans in between, and nothing of another op may sit under it.  The index build and the query order
+    // inside use NN_REF_COUNTS, NN_QUERY_*, NN_ORDER, NN_SCAN_*, NN_BOUNDS and NN_BOUNDS_PARTIALS (call-local there as here: NN_ORDER
+    // is read by every walk, and no entry of csrc/cluster.hip requests an NN_* slot between its order pass and its last walk)
+    PB3D_SLOT_CLUSTER_STARTS = 92,
+    PB3D_SLOT_CLUSTER_COORDS = 93,
+    PB3D_SLOT_CLUSTER_IDS = 94,
+    PB3D_SLOT_CLUSTER_PARENT = 95,
+    PB3D_SLOT_CLUSTER_ROOT_FLAGS = 96,
+    PB3D_SLOT_CLUSTER_RANKS = 97,
+    PB3D_SLOT_CLUSTER_SCAN_LOCAL = 98,
+    PB3D_SLOT_CLUSTER_SCAN_SEGS = 99,
+    PB3D_SLOT_CLUSTER_CHOSEN = 100,
 
-    PB3D_SLOT_COUNT = 92
+    PB3D_SLOT_COUNT = 101
 };
 
 // ---- the cell index of the exact nearest-neighbour search (csrc/nn.hip) -----------------------------------
@@ -254,6 +269,11 @@ struct pb3d_ctx {
     int tune_ccl_init_blocks;   // knob "ccl_init_blocks": workgroups per CU of the labelling's first pass (0 = 16)
     int tune_ccl_tilecols;      // knob "ccl_tilecols": windows per level of a plane-to-plane merge tile (0 = 32)
     int tune_ccl_merge;         // knob "ccl_merge": 0 = tile kernels where the rows fit, 1 = always the pairwise kernel (development A/B)
+    int tune_cluster_cell;      // knob "cluster_cell": cell edge of csrc/cluster.hip's index: 0 = the built-in rule, 1 = make_grid's (2 points per cell), 2 = above eps
+    int tune_cluster_timing;    // knob "cluster_timing": 1 = pb3d_cluster_points_resident times its passes with events (one more host wait)
+    // the last pb3d_cluster_points_resident / pb3d_radius_count_resident (csrc/cluster.hip) for pb3d_cluster_last: cells per axis of its
+    // index, and with cluster_timing the milliseconds of its passes (index, count, union + flatten, ranks, labels)
+    struct ClusterLast { bool valid, timed; float ms[5]; i64 cells[3]; } cluster_last;
     // Growable device scratch slots, named by enum pb3d_slot (no hipMalloc / hipFree per call once warm).
     void* scratch[PB3D_SLOT_COUNT];
     size_t scratch_bytes[PB3D_SLOT_COUNT];
@@ -411,6 +431,9 @@ int pb3d_scan_counts(pb3d_ctx* ctx, const u32* d_counts, i64 n, i64* d_offsets, 
 // each of nq float64 queries -> d_idx (enqueued; only the query binning is redone)
 int pb3d_nn_index_build(pb3d_ctx* ctx, const void* d_r, int r_f64, i64 nr, pb3d_slot starts_slot, pb3d_slot coords_slot, pb3d_slot ids_slot,
                         pb3d_nn_index* ix);
+// ... in cells whose edge exceeds min_edge (min_edge <= 0: pb3d_nn_index_build), never more cells than that grid has (csrc/cluster.hip)
+int pb3d_nn_index_build_edge(pb3d_ctx* ctx, const void* d_r, int r_f64, i64 nr, double min_edge, pb3d_slot starts_slot, pb3d_slot coords_slot,
+                             pb3d_slot ids_slot, pb3d_nn_index* ix);
 int pb3d_nn_index_nearest(pb3d_ctx* ctx, const pb3d_nn_index& ix, const double* d_q, i64 nq, int* d_idx);
 // csrc/nn.hip for csrc/meshdist.hip: the positions of the nq >= 1 queries in the cell order of grid g -> *order (PB3D_SLOT_NN_ORDER;
 // enqueued)

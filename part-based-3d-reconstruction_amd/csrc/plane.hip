@@ -11,7 +11,8 @@
 //   k_plane_terms    a refit's 11 terms per point in the caller's order, reduced per workgroup of 256 consecutive points, then
 //                    pb3d_k_rows_final<11> (csrc/reduce_rows.h: the summation order of the ICP step, no floating-point atomics)
 //   k_crop_count / k_crop_fill   order-keeping stream compaction: survivors per 256 consecutive points, pb3d_scan_counts, and a fill
-//                    that ranks a survivor by ballots (lower lanes of its wave + the lower waves of its workgroup)
+//                    that ranks a survivor by ballots (lower lanes of its wave + the lower waves of its workgroup).  One shell
+//                    (compact_points) for every per-point predicate: the closed box of crop_to_box, the byte flags of select_points
 // Nothing here waits for the host.  The Makefile passes -ffp-contract=off: every product and sum below is one rounded operation.
 #include <algorithm>
 #include <cmath>
@@ -120,33 +121,43 @@ __global__ __launch_bounds__(256) void k_plane_terms(const void* __restrict__ pt
     pb3d_reduce_row<kSums>(v, cnt, part + (i64)blockIdx.x * kRow);
 }
 
+// ---- the order-keeping compaction shell: one text for every per-point predicate ------------------------------------------------------
+// Keep(i) says whether row i survives.  InBox: the closed box of crop_to_box; Flagged: the caller's byte per point (select_points).
 template <bool F64>
-__device__ __forceinline__ bool in_box(const void* pts, i64 i, const Box& bx) {
-    double p[3];
-    pb3d_load3<F64>(pts, i, p);
-    bool keep = true;
+struct InBox {
+    const void* pts;
+    Box bx;
+    __device__ __forceinline__ bool operator()(i64 i) const {
+        double p[3];
+        pb3d_load3<F64>(pts, i, p);
+        bool keep = true;
 #pragma unroll
-    for (int a = 0; a < 3; ++a) keep = keep && bx.lo[a] <= p[a] && p[a] <= bx.hi[a];      // a NaN coordinate fails
-    return keep;
-}
+        for (int a = 0; a < 3; ++a) keep = keep && bx.lo[a] <= p[a] && p[a] <= bx.hi[a];      // a NaN coordinate fails
+        return keep;
+    }
+};
+struct Flagged {
+    const u8* keep;
+    __device__ __forceinline__ bool operator()(i64 i) const { return keep[i] != 0; }
+};
 
-template <bool F64>
-__global__ __launch_bounds__(256) void k_crop_count(const void* __restrict__ pts, i64 n, Box bx, u32* __restrict__ counts) {
+template <class Keep>
+__global__ __launch_bounds__(256) void k_crop_count(i64 n, Keep pred, u32* __restrict__ counts) {
     __shared__ u32 wsum[4];
     const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
-    const bool keep = i < n && in_box<F64>(pts, i, bx);
+    const bool keep = i < n && pred(i);
     const u32 c = (u32)__popcll(__ballot(keep));
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
 }
 
-template <bool F64>
-__global__ __launch_bounds__(256) void k_crop_fill(const void* __restrict__ pts, i64 n, Box bx, const i64* __restrict__ offsets, i64 nblocks,
+template <bool F64, class Keep>
+__global__ __launch_bounds__(256) void k_crop_fill(const void* __restrict__ pts, i64 n, Keep pred, const i64* __restrict__ offsets, i64 nblocks,
                                                    void* __restrict__ out, int* __restrict__ idx, i64* __restrict__ count) {
     __shared__ u32 wsum[4];
     const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
-    const bool keep = i < n && in_box<F64>(pts, i, bx);
+    const bool keep = i < n && pred(i);
     const unsigned long long m = __ballot(keep);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     if (lane == 0) wsum[w] = (u32)__popcll(m);
@@ -165,6 +176,23 @@ __global__ __launch_bounds__(256) void k_crop_fill(const void* __restrict__ pts,
         d[0] = s[0]; d[1] = s[1]; d[2] = s[2];
     }
     if (idx) idx[pos] = (int)i;
+}
+
+// count per 256 consecutive points, scan, fill: the n >= 1 rows that pred keeps -> the front of d_out, their positions -> d_idx (may be
+// null), their number -> d_count.  Enqueue only.
+template <bool F64, class Keep>
+int compact_points(pb3d_ctx* ctx, const void* d_pts, i64 n, const Keep& pred, void* d_out, int* d_idx, i64* d_count) {
+    const i64 nb = (n + 255) / 256;
+    void *cnt, *off;
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_CROP_COUNTS, (size_t)nb * sizeof(u32), &cnt));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_CROP_OFFSETS, (size_t)(nb + 1) * sizeof(i64), &off));
+    const dim3 grid((unsigned)nb);
+    hipLaunchKernelGGL(k_crop_count<Keep>, grid, dim3(256), 0, ctx->stream, n, pred, (u32*)cnt);
+    PB3D_CHECK_LAUNCH();
+    PB3D_TRY(pb3d_scan_counts(ctx, (const u32*)cnt, nb, (i64*)off, PB3D_SLOT_CROP_SCAN_LOCAL, PB3D_SLOT_CROP_SCAN_SEGS));
+    hipLaunchKernelGGL((k_crop_fill<F64, Keep>), grid, dim3(256), 0, ctx->stream, d_pts, n, pred, (const i64*)off, nb, d_out, d_idx, d_count);
+    PB3D_CHECK_LAUNCH();
+    return PB3D_OK;
 }
 
 }  // namespace
@@ -245,24 +273,25 @@ int pb3d_points_crop_box_resident(pb3d_ctx* ctx, const void* d_pts, int pts_f64,
         PB3D_HIP(hipMemsetAsync(d_count, 0, sizeof(int64_t), ctx->stream));
         return PB3D_OK;
     }
-    const i64 nb = (n + 255) / 256;
-    void *cnt, *off;
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_CROP_COUNTS, (size_t)nb * sizeof(u32), &cnt));
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_CROP_OFFSETS, (size_t)(nb + 1) * sizeof(i64), &off));
     Box bx;
     memcpy(bx.lo, lo, sizeof(bx.lo));
     memcpy(bx.hi, hi, sizeof(bx.hi));
-    const dim3 grid((unsigned)nb);
-    if (pts_f64) hipLaunchKernelGGL(k_crop_count<true>, grid, dim3(256), 0, ctx->stream, d_pts, (i64)n, bx, (u32*)cnt);
-    else hipLaunchKernelGGL(k_crop_count<false>, grid, dim3(256), 0, ctx->stream, d_pts, (i64)n, bx, (u32*)cnt);
-    PB3D_CHECK_LAUNCH();
-    PB3D_TRY(pb3d_scan_counts(ctx, (const u32*)cnt, nb, (i64*)off, PB3D_SLOT_CROP_SCAN_LOCAL, PB3D_SLOT_CROP_SCAN_SEGS));
-    if (pts_f64) hipLaunchKernelGGL(k_crop_fill<true>, grid, dim3(256), 0, ctx->stream, d_pts, (i64)n, bx, (const i64*)off, nb, d_out, (int*)d_idx,
-                                    (i64*)d_count);
-    else hipLaunchKernelGGL(k_crop_fill<false>, grid, dim3(256), 0, ctx->stream, d_pts, (i64)n, bx, (const i64*)off, nb, d_out, (int*)d_idx,
-                            (i64*)d_count);
-    PB3D_CHECK_LAUNCH();
-    return PB3D_OK;
+    if (pts_f64) return compact_points<true>(ctx, d_pts, (i64)n, InBox<true>{d_pts, bx}, d_out, (int*)d_idx, (i64*)d_count);
+    return compact_points<false>(ctx, d_pts, (i64)n, InBox<false>{d_pts, bx}, d_out, (int*)d_idx, (i64*)d_count);
+}
+
+int pb3d_points_select_resident(pb3d_ctx* ctx, const void* d_pts, int pts_f64, int64_t n, const uint8_t* d_keep, void* d_out, int32_t* d_idx,
+                                int64_t* d_count) {
+    PB3D_REQUIRE(n >= 0 && n <= pb3d_max_points, "pb3d_points_select: need 0 <= n <= 2^31 - 1 points (got %lld)", (long long)n);
+    PB3D_REQUIRE(d_count != nullptr, "pb3d_points_select: null argument");
+    PB3D_REQUIRE(n == 0 || (d_pts != nullptr && d_keep != nullptr && d_out != nullptr), "pb3d_points_select: null buffer");
+    PB3D_REQUIRE(ctx != nullptr, "pb3d_points_select: null context");
+    if (n == 0) {
+        PB3D_HIP(hipMemsetAsync(d_count, 0, sizeof(int64_t), ctx->stream));
+        return PB3D_OK;
+    }
+    if (pts_f64) return compact_points<true>(ctx, d_pts, (i64)n, Flagged{d_keep}, d_out, (int*)d_idx, (i64*)d_count);
+    return compact_points<false>(ctx, d_pts, (i64)n, Flagged{d_keep}, d_out, (int*)d_idx, (i64*)d_count);
 }
 
 }  // extern "C"

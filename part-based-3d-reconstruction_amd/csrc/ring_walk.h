@@ -66,6 +66,22 @@ inline Grid make_grid(const double b[6], i64 n) {
     return g;
 }
 
+// The same box in fewer cells: every axis keeps at most floor(extent / (min_edge (1 + 1e-6))) of its cells, so a cell's edge exceeds
+// min_edge and a search of radius min_edge ends with the ring next to the query's cell (27 cells).  Never more cells than g has.
+inline void coarsen_grid(Grid& g, double min_edge) {
+    g.ncells = 1;
+    for (int a = 0; a < 3; ++a) {
+        const double ext = g.hi[a] - g.lo[a];
+        if (g.n[a] > 1) {
+            const double na = std::floor(ext / (min_edge * (1.0 + 1e-6)));
+            if (!(na >= (double)g.n[a])) g.n[a] = na >= 1.0 ? (int)na : 1;      // (a NaN quotient: one cell)
+        }
+        g.inv[a] = g.n[a] > 1 ? (double)g.n[a] / ext : 0.0;
+        g.h[a] = g.n[a] > 1 ? ext / (double)g.n[a] : 0.0;
+        g.ncells *= g.n[a];
+    }
+}
+
 // Lower bound (margin applied) of |v - s| over s in the slab of cells [c0, c1] of axis a: the first and last cells reach the box's
 // exact faces, the others end at lo + c h.  tol: the query's margin on this axis.
 __device__ __forceinline__ double slab_gap(const Grid& g, int a, int c0, int c1, double v, double tol) {

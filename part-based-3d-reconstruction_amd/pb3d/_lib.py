@@ -169,6 +169,11 @@ _SIGNATURES = {
     "pb3d_plane_score_resident": [vp, vp, C.c_int, i64, vp, C.c_int, C.c_double, vp],
     "pb3d_plane_moments_resident": [vp, vp, C.c_int, i64, dblp, C.c_double, dblp, vp],
     "pb3d_points_crop_box_resident": [vp, vp, C.c_int, i64, dblp, dblp, vp, vp, vp],
+    "pb3d_radius_count_resident": [vp, vp, C.c_int, i64, C.c_double, vp],
+    "pb3d_cluster_points_resident": [vp, vp, C.c_int, i64, C.c_double, i64, vp, vp, vp, vp, i64p],
+    "pb3d_labels_member_resident": [vp, vp, i64, u8p, i64, vp],
+    "pb3d_points_select_resident": [vp, vp, C.c_int, i64, vp, vp, vp, vp],
+    "pb3d_cluster_last": [vp, i64p, dblp],
 }
 class IouRow(C.Structure):
     """pb3d_iou_row (include/pb3d.h)"""

@@ -1,5 +1,5 @@
 """Device-resident timing of every op of the path (M1..M8 of SURVEY.md 8(d), plus the N1/N2 kernels of the notebook-1 chain) on
-synthetic inputs.  Development/measurement tool: python tools/opbench.py [--size 1024] [--shape WxHxD] [--ops M1,M3,...,N2,overlays,ICP,PLANE,MESHD]; one JSON
+synthetic inputs.  Development/measurement tool: python tools/opbench.py [--size 1024] [--shape WxHxD] [--ops M1,M3,...,N2,overlays,ICP,PLANE,MESHD,CLUSTER]; one JSON
 line per op.  Pricing: `alg_B_per_voxel` is SURVEY 8(d)'s algorithmic figure for the sweeps that are EXECUTED (a folded 0-degree step
 moves nothing and is not priced); ops whose intermediates are not bytes (the bit-sliced chains) also carry `moved_B_per_voxel`, the
 bytes that cross the HBM by design, and their `frac_of_8TBs` is computed from THAT (never from bytes that are not moved)."""
@@ -256,6 +256,8 @@ def main():
         icp(a.reps, res, cpu_ref=not a.no_cpu_ref)
     if "PLANE" in ops:
         plane(a.reps, res, cpu_ref=not a.no_cpu_ref)
+    if "CLUSTER" in ops:
+        cluster(a.reps, res, cpu_ref=not a.no_cpu_ref)
     if "MESH" in ops:
         meshify(a.reps, res)
     if "DENS" in ops:
@@ -775,6 +777,90 @@ def plane(reps, res, cpu_ref=True):
     res.append(r)
     for b in [d_g, d_tc, d_out, d_idx, d_count] + [c[0] for c in clouds.values()]:
         b.free()
+
+
+def cluster(reps, res, cpu_ref=True):
+    """CLUSTER, cluster_points (csrc/cluster.hip): the 20 k SfM sample at (eps 0.06, min_samples 10) in the frame the fixture is stored
+    in (float64), and every point of the stored Taj grid (float32) at eps = 1.5 and 2.5 voxels with min_samples 10.  Per case and per
+    cell-edge choice of the index (knob cluster_cell: 1 = two points per cell, 2 = cells wider than eps): the whole resident call and
+    the counts alone by device events (best mean of reps), and the call's passes from its own events under knob cluster_timing (index,
+    count, union + flatten, ranks with the host wait, labels).  keep_largest_clusters_resident (k = 1) under the built-in rule.  With
+    cpu_ref, scikit-learn's DBSCAN(algorithm="kd_tree") on the SfM sample on this host, where it is installed (the 12 M Taj points
+    are beyond what it clusters in a benchmark's time)."""
+    from pb3d import cluster as cl
+    lib, L = pb3d._lib.load(), pb3d._lib
+    sfm = np.ascontiguousarray(np.load(os.path.join(ROOT, "tests", "golden", "inter_sfm20k.npz"))["sfm"])
+    taj = np.load(os.path.join(ROOT, "tests", "golden", "stored_Taj_voxel_grid.npz"))["voxel_grid"]
+    nvox = int(np.prod(taj.shape[:3]))
+    d_g = dev.from_numpy(taj)
+    d_tp, d_tc = dev.DeviceBuffer(nvox * 12), dev.DeviceBuffer(nvox * 3)
+    cnt = C.c_int64(0)
+    L.check(lib.pb3d_points_extract_dev(L.ctx(), C.c_void_p(d_g.ptr), *taj.shape[:3], 3, None, 0, nvox, C.c_void_p(d_tp.ptr),
+                                        C.c_void_p(d_tc.ptr), C.byref(cnt)))
+    ntaj = cnt.value
+    d_g.free(); d_tc.free()
+    d_sfm = dev.from_numpy(sfm)
+    cases = [("sfm20k", d_sfm, 20000, True, 0.06, 10), ("taj_full", d_tp, ntaj, False, 1.5, 10), ("taj_full", d_tp, ntaj, False, 2.5, 10)]
+
+    def call(d_p, n, f64, eps, ms):
+        bufs = cl.cluster_points_resident(d_p, n, eps, ms, f64)
+        for b in bufs[:4]:
+            b.free()
+        return bufs[4]
+
+    for name, d_p, n, f64, eps, ms in cases:
+        r = {"op": "CLUSTER", "name": f"cluster_points: {name}", "n": n, "dtype": "float64" if f64 else "float32", "eps": eps, "min_samples": ms}
+        d_cnt = dev.DeviceBuffer(n * 4)
+        try:
+            for knob, tag in ((1, "cells_2_per_cell"), (2, "cells_above_eps")):
+                L.set_tuning("cluster_cell", knob)
+                L.set_tuning("cluster_timing", 1)
+                call(d_p, n, f64, eps, ms)
+                best = None
+                for _ in range(max(2, reps)):
+                    call(d_p, n, f64, eps, ms)
+                    cells, pm = (C.c_int64 * 3)(), (C.c_double * 5)()
+                    L.check(lib.pb3d_cluster_last(L.ctx(), cells, pm))
+                    if best is None or sum(pm) < sum(best):
+                        best = list(pm)
+                L.set_tuning("cluster_timing", 0)
+                whole = min(timeit(lambda: call(d_p, n, f64, eps, ms), reps, warm=1) for _ in range(2))
+                counts = min(timeit(lambda: cl.radius_neighbor_counts_resident(d_p, n, eps, f64, out=d_cnt), reps, warm=1) for _ in range(2))
+                r[tag] = {"cells": list(cells), "call_ms": round(whole, 4), "radius_count_call_ms": round(counts, 4),
+                          "pass_ms": dict(zip(("index", "count", "union_flatten", "ranks_and_wait", "labels"), (round(v, 4) for v in best)))}
+        finally:
+            L.set_tuning("cluster_cell", 0)
+            L.set_tuning("cluster_timing", 0)
+        d_lab, d_core, d_c, d_sz, nc = cl.cluster_points_resident(d_p, n, eps, ms, f64)
+        labels = d_lab.download((n,), np.int32)
+        sizes = d_sz.download((nc,), np.int64) if nc else np.zeros(0, np.int64)
+        r.update({"clusters": nc, "largest": sorted(sizes.tolist(), reverse=True)[:5], "noise": int((labels < 0).sum()),
+                  "core": int(np.count_nonzero(d_core.download((n,), np.uint8)))})
+        for b in (d_lab, d_core, d_c, d_sz, d_cnt):
+            b.free()
+
+        def keep():
+            d_o, d_i, _, _ = cl.keep_largest_clusters_resident(d_p, n, eps, ms, 1, f64)
+            d_o.free(); d_i.free()
+
+        r["keep_largest_k1_call_ms"] = round(timeit(keep, reps, warm=1), 4)
+        if cpu_ref and n <= 100000:
+            try:
+                from sklearn.cluster import DBSCAN
+            except ImportError:
+                DBSCAN = None
+            if DBSCAN is not None:
+                host = sfm
+                t = []
+                for _ in range(3):
+                    t0 = time.perf_counter()
+                    ref = DBSCAN(eps=eps, min_samples=ms, algorithm="kd_tree").fit(host)
+                    t.append(time.perf_counter() - t0)
+                r["sklearn_kd_tree_ms"] = round(1e3 * min(t), 1)
+                r["sklearn_labels_equal"] = bool(np.array_equal(ref.labels_, labels))
+        print(json.dumps(r), flush=True)
+        res.append(r)
+    d_sfm.free(); d_tp.free()
 
 
 def meshify(reps, res):
