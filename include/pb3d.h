@@ -577,6 +577,36 @@ int pb3d_points_select_resident(pb3d_ctx* ctx, const void* d_pts, int pts_f64, i
                                 int64_t* d_count);
 int pb3d_cluster_last(pb3d_ctx* ctx, int64_t cells[3], double pass_ms[5] /* or NULL */);
 
+/* ---- voxel_downsample: voxel-grid downsampling of a point cloud, between segmentation and registration (csrc/downsample.hip) ----------
+ * Point lists as above: (n, 3) rows of float32 (pts_f64 = 0, widened first) or float64 (1), 0 <= n <= 2^31 - 1, coordinates finite
+ * (the caller's duty).  voxel_size finite and > 0, origin NULL or three finite values, reduce one of the two below, else PB3D_EINVAL.
+ * The result is a function of the input and its order alone (two runs give the same bytes):
+ *   ORIGIN    the caller's three float64 values when given.  Otherwise o_a = lo_a - h with lo the cloud's exact per-axis minimum and
+ *             h = 0.5 * voxel_size: one rounded product made once on the host, one rounded subtraction per axis.  With this default the
+ *             voxel membership is Open3D's voxel_down_sample.
+ *   CELL      c_a = floor((p_a - o_a) / voxel_size) in float64: one rounded subtraction, one correctly rounded division, then floor.  A
+ *             point just below a voxel face whose quotient rounds up to the integer belongs to the upper voxel, as it does in NumPy.
+ *   RANGE     every point must have 0 <= c_a < 2^21 on every axis.  The three operations are monotone, so the host decides this from
+ *             the cells of the exact bounds; on failure PB3D_EINVAL with a message that names voxel_size and origin, nothing written.
+ *   VOXELS    two points share a voxel iff their three cells are equal.  Voxels are numbered 0 .. m - 1 by the position of their first
+ *             point in the caller's list: in order of first appearance.
+ *   INDEX     index[v] = that first position (strictly increasing); inverse[i] = the voxel of point i; counts[v] = its number of points.
+ *   CENTROID  (reduce = PB3D_DOWNSAMPLE_CENTROID) per axis s = 0.0, then s = s + (double)p_a over the voxel's points in ascending
+ *             position, one rounded addition each (no FMA); out = s / (double)counts[v], one correctly rounded division; for a float32
+ *             cloud that quotient rounded once to float32.
+ *   FIRST     (reduce = PB3D_DOWNSAMPLE_FIRST) out[v] = row index[v] of the input, byte for byte.
+ * Permuting the input may change the numbering of the voxels and the last bits of the centroids (the order of the additions), never the
+ * partition into voxels.
+ * d_out (capacity n rows of the input's dtype), d_index (n int32) and, where not NULL, d_counts (n uint32): the first *nvoxels entries
+ * are written; d_inverse (n int32, or NULL) whole; *nvoxels on the host.  Two host waits: the bounding box and the number of voxels.
+ * n = 0: *nvoxels = 0, nothing written, no host wait.  A non-finite coordinate (which the Python forms refuse) gives a wrong voxel for
+ * that point, never an access outside the buffers. */
+#define PB3D_DOWNSAMPLE_CENTROID 0
+#define PB3D_DOWNSAMPLE_FIRST 1
+int pb3d_voxel_downsample_resident(pb3d_ctx* ctx, const void* d_pts, int pts_f64, int64_t n, double voxel_size,
+                                   const double origin[3] /* or NULL */, int reduce, void* d_out, int32_t* d_index,
+                                   int32_t* d_inverse /* or NULL */, uint32_t* d_counts /* or NULL */, int64_t* nvoxels);
+
 /* ---- notebook 2: bbox camera init and projection overlays, reference utils/camera_estimation.py:56-108, :346-477 ----------------
  * grid_bounds: d_out[0] = the number of voxels of the resident (A0,A1,A2,C) grid whose colour (C = 3) / label (C = 1) is one of the
  *   ncolors <= 31 non-zero `colors` (ncolors = 0: any non-zero voxel), d_out[1..3] = their inclusive minimum (a0, a1, a2), d_out[4..6]

@@ -188,8 +188,22 @@ enum pb3d_slot : int {
     PB3D_SLOT_CLUSTER_SCAN_LOCAL = 98,
     PB3D_SLOT_CLUSTER_SCAN_SEGS = 99,
     PB3D_SLOT_CLUSTER_CHOSEN = 100,
+    // call-local, csrc/downsample.hip, all of them: the cloud's box read back by the host; the hash table (a power of two >= 2 n slots of 16
+    // bytes: the 64-bit voxel key, the smallest position and the number of its points); each point's slot; the first-appearance flags (then the counts of a centroid call that was given no d_counts); their ranks
+    // (n + 1 int64, then the m + 1 list starts) and the two slots of every pb3d_scan_counts of the call; the (voxel, position) pairs of
+    // the stable sort (key, val and their ping-pong twins, n u32 each) and its run table (256 runs per tile of 2048 pairs: int64
+    // starts, then u32 counts).  The bounds pass inside uses NN_BOUNDS_PARTIALS
+    PB3D_SLOT_DOWNSAMPLE_BOUNDS = 101,
+    PB3D_SLOT_DOWNSAMPLE_TABLE = 102,
+    PB3D_SLOT_DOWNSAMPLE_POINT_SLOT = 103,
+    PB3D_SLOT_DOWNSAMPLE_FLAGS = 104,
+    PB3D_SLOT_DOWNSAMPLE_RANKS = 105,
+    PB3D_SLOT_DOWNSAMPLE_SCAN_LOCAL = 106,
+    PB3D_SLOT_DOWNSAMPLE_SCAN_SEGS = 107,
+    PB3D_SLOT_DOWNSAMPLE_SORT_PAIRS = 108,
+    PB3D_SLOT_DOWNSAMPLE_SORT_HIST = 109,
 
-    PB3D_SLOT_COUNT = 101
+    PB3D_SLOT_COUNT = 110
 };
 
 // ---- the cell index of the exact nearest-neighbour search (csrc/nn.hip) -----------------------------------

@@ -174,6 +174,7 @@ _SIGNATURES = {
     "pb3d_labels_member_resident": [vp, vp, i64, u8p, i64, vp],
     "pb3d_points_select_resident": [vp, vp, C.c_int, i64, vp, vp, vp, vp],
     "pb3d_cluster_last": [vp, i64p, dblp],
+    "pb3d_voxel_downsample_resident": [vp, vp, C.c_int, i64, C.c_double, dblp, C.c_int, vp, vp, vp, vp, i64p],
 }
 class IouRow(C.Structure):
     """pb3d_iou_row (include/pb3d.h)"""

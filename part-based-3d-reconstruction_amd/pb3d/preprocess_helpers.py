@@ -23,6 +23,7 @@ Again include/pb3d.h states the arithmetic (csrc/plane.hip): the device builds K
 of them against the resident cloud in one sweep with exact integer counts, and reduces the inliers of a plane to a count and 11
 float64 sums in the ICP step's fixed order; the host draws the triplets, picks the best row, and solves the 3 x 3 eigen problem of a
 refit (plane_from_moments).  Segmenting the SfM cloud, step 1, is pb3d/cluster.py (cluster_points, keep_largest_clusters: exact DBSCAN
+on the device).  Thinning a cloud to an even density before registration is pb3d/downsample.py (voxel_downsample: a voxel-grid filter
 on the device).  What is still not mirrored: loading the SfM cloud, and the CAD model."""
 import ctypes as C
 import math

@@ -1,5 +1,5 @@
 """Device-resident timing of every op of the path (M1..M8 of SURVEY.md 8(d), plus the N1/N2 kernels of the notebook-1 chain) on
-synthetic inputs.  Development/measurement tool: python tools/opbench.py [--size 1024] [--shape WxHxD] [--ops M1,M3,...,N2,overlays,ICP,PLANE,MESHD,CLUSTER]; one JSON
+synthetic inputs.  Development/measurement tool: python tools/opbench.py [--size 1024] [--shape WxHxD] [--ops M1,M3,...,N2,overlays,ICP,PLANE,MESHD,CLUSTER,DOWNSAMPLE]; one JSON
 line per op.  Pricing: `alg_B_per_voxel` is SURVEY 8(d)'s algorithmic figure for the sweeps that are EXECUTED (a folded 0-degree step
 moves nothing and is not priced); ops whose intermediates are not bytes (the bit-sliced chains) also carry `moved_B_per_voxel`, the
 bytes that cross the HBM by design, and their `frac_of_8TBs` is computed from THAT (never from bytes that are not moved)."""
@@ -258,6 +258,8 @@ def main():
         plane(a.reps, res, cpu_ref=not a.no_cpu_ref)
     if "CLUSTER" in ops:
         cluster(a.reps, res, cpu_ref=not a.no_cpu_ref)
+    if "DOWNSAMPLE" in ops:
+        downsample(a.reps, res, cpu_ref=not a.no_cpu_ref)
     if "MESH" in ops:
         meshify(a.reps, res)
     if "DENS" in ops:
@@ -858,6 +860,58 @@ def cluster(reps, res, cpu_ref=True):
                     t.append(time.perf_counter() - t0)
                 r["sklearn_kd_tree_ms"] = round(1e3 * min(t), 1)
                 r["sklearn_labels_equal"] = bool(np.array_equal(ref.labels_, labels))
+        print(json.dumps(r), flush=True)
+        res.append(r)
+    d_sfm.free(); d_tp.free()
+
+
+def downsample(reps, res, cpu_ref=True):
+    """DOWNSAMPLE, voxel_downsample (csrc/downsample.hip): the 20 k SfM sample (float64) at voxel_size 0.05 and 0.5, and every point of
+    the stored Taj grid (float32, voxel units) at 2, 4 and 8 voxels, both reductions.  The whole resident call by device events (best
+    mean of reps; its two host waits are inside).  reduce="first" runs the hash, the numbering and a gather; "centroid" adds the
+    stable sort of the (voxel, position) pairs and the ordered sums, so their difference is what the order costs.  With cpu_ref, the
+    NumPy restatement of tests/downsample_restate.py on this host's CPU, and whether the device's arrays equal it."""
+    import downsample_restate as dr
+    from pb3d import downsample as ds
+    lib, L = pb3d._lib.load(), pb3d._lib
+    sfm = np.ascontiguousarray(np.load(os.path.join(ROOT, "tests", "golden", "inter_sfm20k.npz"))["sfm"])
+    taj = np.load(os.path.join(ROOT, "tests", "golden", "stored_Taj_voxel_grid.npz"))["voxel_grid"]
+    nvox = int(np.prod(taj.shape[:3]))
+    d_g = dev.from_numpy(taj)
+    d_tp, d_tc = dev.DeviceBuffer(nvox * 12), dev.DeviceBuffer(nvox * 3)
+    cnt = C.c_int64(0)
+    L.check(lib.pb3d_points_extract_dev(L.ctx(), C.c_void_p(d_g.ptr), *taj.shape[:3], 3, None, 0, nvox, C.c_void_p(d_tp.ptr),
+                                        C.c_void_p(d_tc.ptr), C.byref(cnt)))
+    ntaj = cnt.value
+    d_g.free(); d_tc.free()
+    taj_pts = d_tp.download((ntaj, 3), np.float32).copy() if cpu_ref else None
+    d_sfm = dev.from_numpy(sfm)
+    cases = [("sfm20k", d_sfm, sfm, 20000, True, 0.05), ("sfm20k", d_sfm, sfm, 20000, True, 0.5)]
+    cases += [("taj_full", d_tp, taj_pts, ntaj, False, float(v)) for v in (2, 4, 8)]
+    for name, d_p, host, n, f64, vs in cases:
+        r = {"op": "DOWNSAMPLE", "name": f"voxel_downsample: {name}", "n": n, "dtype": "float64" if f64 else "float32", "voxel_size": vs}
+        bufs = [dev.DeviceBuffer(n * w) for w in (24 if f64 else 12, 4, 4, 4)]
+        m = C.c_int64(0)
+        for reduce in ("centroid", "first"):
+            def call():
+                L.check(lib.pb3d_voxel_downsample_resident(L.ctx(), C.c_void_p(d_p.ptr), int(f64), n, vs, None, ds.REDUCE[reduce],
+                                                           *(C.c_void_p(b.ptr) for b in bufs), C.byref(m)))
+            r[f"{reduce}_call_ms"] = round(min(timeit(call, reps, warm=1) for _ in range(2)), 4)
+            if reduce == "centroid":
+                counts = bufs[3].download((m.value,), np.uint32)
+                r.update({"voxels": int(m.value), "largest_voxel": int(counts.max()), "mean_points_per_voxel": round(n / m.value, 2)})
+            if cpu_ref:
+                t = []
+                for _ in range(2):
+                    t0 = time.perf_counter()
+                    ref = dr.restate(host, vs, None, reduce)
+                    t.append(time.perf_counter() - t0)
+                r[f"numpy_{reduce}_ms"] = round(1e3 * min(t), 1)
+                got = (bufs[0].download((m.value, 3), host.dtype), bufs[1].download((m.value,), np.int32),
+                       bufs[2].download((n,), np.int32), bufs[3].download((m.value,), np.uint32))
+                r[f"numpy_{reduce}_equal"] = bool(all(np.array_equal(g, w) for g, w in zip(got, ref)))
+        for b in bufs:
+            b.free()
         print(json.dumps(r), flush=True)
         res.append(r)
     d_sfm.free(); d_tp.free()
