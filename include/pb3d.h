@@ -399,6 +399,47 @@ int pb3d_mesh_grid_shape(const pb3d_ctx* ctx, int64_t cells[3], int64_t* entries
 int pb3d_mesh_sample_resident(pb3d_ctx* ctx, const void* d_verts, int verts_f64, int64_t nv, const void* d_faces, int faces_i64, int64_t nf,
                               int64_t n, uint64_t seed, double* d_pts /* n x 3 */, int32_t* d_face /* n or NULL */);
 
+/* ---- mesh smoothing: the vertex-to-vertex adjacency of a triangle mesh, and Laplacian / Taubin smoothing on it (csrc/smooth.hip) --------
+ * The step between marching cubes and everything that measures or samples the mesh (trimesh.smoothing.filter_taubin, Open3D's
+ * filter_smooth_taubin; uniform weights).  There is no upstream text, so the rules below are the specification, and the result is a
+ * function of the input alone, to the bit.
+ *   INPUT      verts: (nv, 3) rows of float32 (verts_f64 = 0) or float64 (1); faces: (nf, 3) rows of int32 (faces_i64 = 0) or int64 (1)
+ *              with entries in [-nv, nv); entries in [-nv, -1] wrap as NumPy's do.  Anything else is PB3D_EINDEX, checked on the device
+ *              before any kernel gathers through them (one host wait).  Limits: nv <= 2^31 - 1 and 6 * nf <= 2^31 - 1.
+ *   PAIRS      face (a, b, c), after wrapping, emits six directed pairs: (a,b) (b,a) (b,c) (c,b) (c,a) (a,c).  Pairs with equal ends are
+ *              dropped.  This rule alone defines what degenerate faces contribute.
+ *   ADJACENCY  N(i) = the set of j with a pair (i, j), ascending.  starts: nv + 1 int64, N(i) = neighbours[starts[i] .. starts[i + 1]);
+ *              neighbours: int32, total = starts[nv] entries.  The multiplicity of (i, j) is the number of emitted pairs (i, j) (2 for an
+ *              edge between two faces that wind alike or not, 1 for an edge of one face, 4 for an edge of a face given twice); mult[r]
+ *              belongs to neighbours[r].  A vertex is a BOUNDARY vertex if it is an end of a pair with multiplicity 1.
+ *   STEP(f)    all arithmetic float64, each line one rounded IEEE operation, no FMA.  A vertex that is fixed, or has no neighbour,
+ *              keeps its coordinates.  Every other vertex i, per axis:
+ *                  s = 0.0, then s = s + x_j for j in N(i) ascending
+ *                  m = s / deg          (one correctly rounded division, deg converted exactly)
+ *                  d = m - x_i
+ *                  x_i' = x_i + f * d   (a product, then a sum)
+ *              All vertices read the positions from before the step.
+ *   ITERATIONS positions are widened once to float64; `iterations` rounds follow: one STEP(lambda) when mu is NaN (Laplacian), otherwise
+ *              STEP(lambda) then STEP(mu) (Taubin; mu < -lambda < 0 keeps the volume); one rounding to the input dtype at the end.
+ *              iterations = 0 returns the input bytes.  Fixed vertices are the caller's mask (d_fixed: nv uint8, non-zero = fixed, or
+ *              NULL), ORed with the boundary vertices when fix_boundary is set.  Non-finite coordinates are not special: they spread as
+ *              IEEE arithmetic spreads them.
+ * mesh_adjacency: d_starts nv + 1 int64; d_neighbours room for 6 * nf int32, the first *total written; d_mult (or NULL) likewise, uint32;
+ *   d_boundary (or NULL) nv bytes, 1 = boundary vertex.  nf = 0: starts all 0, total 0, no boundary.  Host waits: the index check and total.
+ * mesh_smooth: d_out nv x 3 in the input dtype; it may not alias d_verts.  nf = 0 (or iterations = 0) copies the input; nv = 0 does
+ *   nothing.  PB3D_EINVAL: iterations < 0, lambda not finite, mu infinite.  Host waits: the index check; everything else is enqueued.
+ * Neither keeps anything per vertex while it builds the lists: the 6 * nf pairs go through two stable radix sorts (by the second end,
+ * then by the first), a scan of the "new pair" flags compacts them, and run lengths are the multiplicities -- a vertex that is in every
+ * face is handled like any other.  A step is one lane per vertex; vertices of degree above 32 are summed by one wavefront each, in the
+ * same order.  No floating-point atomics.  Scratch: 220 bytes per face (pairs 96, flags 24, ranks 48, scan 27, neighbours 24) and,
+ * for a smoothing, 57 bytes per vertex (starts 8, boundary 1, the two position buffers 48). */
+int pb3d_mesh_adjacency_resident(pb3d_ctx* ctx, const void* d_faces, int faces_i64, int64_t nv, int64_t nf, int64_t* d_starts /* nv + 1 */,
+                                 int32_t* d_neighbours /* 6 * nf entries, the first *total written */, uint32_t* d_mult /* 6 * nf, or NULL */,
+                                 uint8_t* d_boundary /* nv, or NULL */, int64_t* total);
+int pb3d_mesh_smooth_resident(pb3d_ctx* ctx, const void* d_verts, int verts_f64, int64_t nv, const void* d_faces, int faces_i64, int64_t nf,
+                              int iterations, double lambda, double mu /* NaN: Laplacian */, const uint8_t* d_fixed /* or NULL */,
+                              int fix_boundary, void* d_out /* nv x 3 in the input dtype; may not alias d_verts */);
+
 /* ---- density volume of a point cloud, reference utils/eval_helpers.py:178-189 (pointcloud_to_voxel_grid) ---------------------------
  * d_out: grid_size^3 float32, bit for bit the reference's volume for the resident (n, 3) list d_pts (float32 rows, or float64 with
  * pts_f64 = 1; any 4- / 8-byte aligned base):

@@ -11,13 +11,9 @@
 //                     the bounding box that RANGE is decided from)
 //   k_voxel_number    inverse[i] = rank[first[slot[i]]]; a first point also writes index, counts and, for reduce = first, its row
 // reduce = centroid adds each voxel's points in ascending position, which no atomic can do.  The (voxel, position) pairs, in position
-// order to begin with, go through a stable LSD radix sort on the voxel number (8-bit digits over the bits m - 1 needs: one pass for up
-// to 256 voxels, four at most), which leaves every voxel's positions ascending and the voxels in order, with no per-voxel state: a
-// voxel that holds the whole cloud is sorted like any other.
-//   k_sort_hist       per tile of 2048 pairs, the digit histogram (LDS integer atomics) -> hist[digit][tile]
-//   pb3d_scan_counts  that table in digit-major order = where each (digit, tile) run starts
-//   k_sort_scatter    the tile again, 256 pairs a round in input order: a pair's place is its run's start + same-digit pairs of earlier
-//                     rounds + of earlier waves + of lower lanes (ballot matching), which is what makes the pass stable
+// order to begin with, go through a stable LSD radix sort on the voxel number (pb3d_sort_pairs, csrc/sort_pairs.hip: 8-bit digits over
+// the bits m - 1 needs, one pass for up to 256 voxels, four at most), which leaves every voxel's positions ascending and the voxels in
+// order, with no per-voxel state: a voxel that holds the whole cloud is sorted like any other.
 //   k_voxel_centroid  one wavefront per voxel: 64 positions a time are gathered (the next 64 are in flight meanwhile), then every lane adds
 //                     the same 64 values in order from 0.0 by readlane, one rounded addition each; one correctly rounded division
 // No floating-point atomic anywhere, and -ffp-contract=off (Makefile) keeps the additions apart.
@@ -29,7 +25,7 @@ namespace {
 
 constexpr double kCells = 2097152.0;                // 2^21 cells per axis
 constexpr u64 kEmpty = ~0ull;                       // no key has bit 63
-constexpr int kTile = 2048, kRounds = kTile / 256;  // pairs per workgroup of a sort pass
+constexpr int kTile = pb3d_sort_tile;               // pairs per workgroup of a sort pass (csrc/sort_pairs.hip)
 
 struct Vox { double o[3], size; };
 // one slot of the table: the three words a point touches share a 16-byte record, so an insertion lands in one cache line
@@ -113,55 +109,6 @@ __global__ __launch_bounds__(256) void k_voxel_number(const T* __restrict__ pts,
     }
 }
 
-// ---- the stable radix pass --------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_sort_hist(const u32* __restrict__ key, i64 n, int shift, i64 ntiles, u32* __restrict__ hist) {
-    __shared__ u32 h[256];
-    h[threadIdx.x] = 0;
-    __syncthreads();
-    const i64 base = (i64)blockIdx.x * kTile;
-    for (int r = 0; r < kRounds; ++r) {
-        const i64 i = base + r * 256 + threadIdx.x;
-        if (i < n) atomicAdd(&h[(key[i] >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    hist[(i64)threadIdx.x * ntiles + blockIdx.x] = h[threadIdx.x];
-}
-
-__global__ __launch_bounds__(256) void k_sort_scatter(const u32* __restrict__ key, const u32* __restrict__ val, i64 n, int shift, i64 ntiles,
-                                                      const i64* __restrict__ start, u32* __restrict__ key_out, u32* __restrict__ val_out) {
-    __shared__ u32 before[256];        // pairs of each digit in the tile's earlier rounds
-    __shared__ u32 wave[4][256];       // ... in each wavefront of this round
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    before[t] = 0;
-    for (int k = 0; k < 4; ++k) wave[k][t] = 0;
-    __syncthreads();
-    const i64 base = (i64)blockIdx.x * kTile;
-    for (int r = 0; r < kRounds; ++r) {
-        const i64 i = base + r * 256 + t;
-        const bool valid = i < n;
-        const u32 k = valid ? key[i] : 0u;
-        const u32 d = (k >> shift) & 255u;
-        unsigned long long match = __ballot(valid);     // the lanes of this wavefront that hold digit d
-        for (int b = 0; b < 8; ++b) {
-            const unsigned long long bal = __ballot((d >> b) & 1u);
-            match &= ((d >> b) & 1u) ? bal : ~bal;
-        }
-        const u32 below = (u32)__popcll(match & ((1ull << lane) - 1ull));
-        if (valid && below == 0) wave[w][d] = (u32)__popcll(match);
-        __syncthreads();
-        if (valid) {
-            u32 ahead = before[d] + below;
-            for (int k2 = 0; k2 < w; ++k2) ahead += wave[k2][d];
-            const i64 dst = start[(i64)d * ntiles + blockIdx.x] + ahead;
-            key_out[dst] = k;
-            val_out[dst] = val[i];
-        }
-        __syncthreads();
-        for (int k2 = 0; k2 < 4; ++k2) { before[t] += wave[k2][t]; wave[k2][t] = 0; }
-        __syncthreads();
-    }
-}
-
 // ---- centroids --------------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ double from_lane(double x, int j) {      // lane j's x in every lane (j is the same in all of them)
     const int lo = __builtin_amdgcn_readlane(__double2loint(x), j), hi = __builtin_amdgcn_readlane(__double2hiint(x), j);
@@ -203,30 +150,6 @@ __global__ __launch_bounds__(256) void k_voxel_centroid(const void* __restrict__
 
 // ---- host side --------------------------------------------------------------------------------------------------------------------------
 double host_cell(double p, double o, double size) { return std::floor((p - o) / size); }
-
-// the pairs in keyval (4 arrays of n u32: key, val, key', val') sorted stably by key < m; *sorted = the val array that holds the result
-int sort_pairs(pb3d_ctx* ctx, u32* keyval, i64 n, i64 m, const u32** sorted) {
-    const i64 ntiles = (n + kTile - 1) / kTile, nruns = 256 * ntiles;
-    int bits = 1;
-    while (bits < 32 && ((u64)(m - 1) >> bits) != 0) ++bits;
-    void* hist;
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_DOWNSAMPLE_SORT_HIST, (size_t)(nruns + 1) * sizeof(i64) + (size_t)nruns * sizeof(u32), &hist));
-    i64* starts = (i64*)hist;
-    u32* counts = (u32*)(starts + nruns + 1);
-    u32 *key = keyval, *val = keyval + n, *key2 = keyval + 2 * n, *val2 = keyval + 3 * n;
-    for (int shift = 0; shift < bits; shift += 8) {
-        hipLaunchKernelGGL(k_sort_hist, dim3((unsigned)ntiles), dim3(256), 0, ctx->stream, (const u32*)key, n, shift, ntiles, counts);
-        PB3D_CHECK_LAUNCH();
-        PB3D_TRY(pb3d_scan_counts(ctx, counts, nruns, starts, PB3D_SLOT_DOWNSAMPLE_SCAN_LOCAL, PB3D_SLOT_DOWNSAMPLE_SCAN_SEGS));
-        hipLaunchKernelGGL(k_sort_scatter, dim3((unsigned)ntiles), dim3(256), 0, ctx->stream, (const u32*)key, (const u32*)val, n, shift, ntiles,
-                           (const i64*)starts, key2, val2);
-        PB3D_CHECK_LAUNCH();
-        u32* t = key; key = key2; key2 = t;
-        t = val; val = val2; val2 = t;
-    }
-    *sorted = val;
-    return PB3D_OK;
-}
 
 template <class T>
 int launch_number(pb3d_ctx* ctx, const void* d_pts, i64 n, const u32* slot_of, const Slot* table, const i64* rank, int* index, int* inverse,
@@ -320,7 +243,8 @@ extern "C" int pb3d_voxel_downsample_resident(pb3d_ctx* ctx, const void* d_pts, 
         // the ranks are spent too: the list starts (m + 1 <= n + 1 int64) take their place
         PB3D_TRY(pb3d_scan_counts(ctx, counts, m, (i64*)ranks, PB3D_SLOT_DOWNSAMPLE_SCAN_LOCAL, PB3D_SLOT_DOWNSAMPLE_SCAN_SEGS));
         const u32* sorted;
-        PB3D_TRY(sort_pairs(ctx, pairs, n, m, &sorted));
+        PB3D_TRY(pb3d_sort_pairs(ctx, pairs, pairs + n, pairs + 2 * n, pairs + 3 * n, n, m, PB3D_SLOT_DOWNSAMPLE_SORT_HIST,
+                                 PB3D_SLOT_DOWNSAMPLE_SCAN_LOCAL, PB3D_SLOT_DOWNSAMPLE_SCAN_SEGS, nullptr, &sorted));
         hipLaunchKernelGGL((pts_f64 ? k_voxel_centroid<true> : k_voxel_centroid<false>), dim3((unsigned)((m + 3) / 4)), dim3(256), 0, ctx->stream, d_pts,
                            sorted, (const i64*)ranks, m, d_out);
         PB3D_CHECK_LAUNCH();

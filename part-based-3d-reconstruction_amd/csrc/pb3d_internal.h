@@ -202,8 +202,28 @@ enum pb3d_slot : int {
     PB3D_SLOT_DOWNSAMPLE_SCAN_SEGS = 107,
     PB3D_SLOT_DOWNSAMPLE_SORT_PAIRS = 108,
     PB3D_SLOT_DOWNSAMPLE_SORT_HIST = 109,
+    // call-local, csrc/smooth.hip, all of them (P = 6 nf directed pairs): the pairs of the two stable sorts (key, val and their
+    // ping-pong twins, P u32 each; the sorted (i, j) columns are read until the adjacency is complete) and the sorts' run table; the
+    // "new pair" flags (P + 1 u32; once scanned, the position of every unique pair's first copy takes their place); their ranks
+    // (P + 1 int64) and the two slots of every pb3d_scan_counts of the call; starts (nv + 1 int64), neighbours (P int32) and the
+    // boundary bytes (nv, then ORed with the caller's fixed mask) of pb3d_mesh_smooth_resident, which pb3d_mesh_adjacency_resident
+    // writes into its caller's buffers instead (it takes BOUNDARY only when it needs the bytes for nobody); the vertices above the
+    // lane cutoff (a counter, then their numbers) and the two float64 position buffers (nv x 3 each) of the steps.  The index check
+    // in front uses SURF_FLAG
+    PB3D_SLOT_SMOOTH_PAIRS = 110,
+    PB3D_SLOT_SMOOTH_SORT_HIST = 111,
+    PB3D_SLOT_SMOOTH_FLAGS = 112,
+    PB3D_SLOT_SMOOTH_RANKS = 113,
+    PB3D_SLOT_SMOOTH_SCAN_LOCAL = 114,
+    PB3D_SLOT_SMOOTH_SCAN_SEGS = 115,
+    PB3D_SLOT_SMOOTH_STARTS = 116,
+    PB3D_SLOT_SMOOTH_NEIGHBOURS = 117,
+    PB3D_SLOT_SMOOTH_BOUNDARY = 118,
+    PB3D_SLOT_SMOOTH_HUBS = 119,
+    PB3D_SLOT_SMOOTH_POS_A = 120,
+    PB3D_SLOT_SMOOTH_POS_B = 121,
 
-    PB3D_SLOT_COUNT = 110
+    PB3D_SLOT_COUNT = 122
 };
 
 // ---- the cell index of the exact nearest-neighbour search (csrc/nn.hip) -----------------------------------
@@ -440,6 +460,13 @@ int pb3d_ccl_label_on_device(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, i
 // ---- kernels' host launchers used across translation units ---------------------------------
 // exclusive scan of n u32 counts into n + 1 int64 offsets (the last = total) with points.hip's scan kernels; scratch slots local_slot, seg_slot
 int pb3d_scan_counts(pb3d_ctx* ctx, const u32* d_counts, i64 n, i64* d_offsets, pb3d_slot local_slot, pb3d_slot seg_slot);
+// csrc/sort_pairs.hip for csrc/downsample.hip and csrc/smooth.hip: the n >= 1 pairs (key[i], val[i]) sorted stably by key < m, through
+// the ping-pong twins key2 / val2 (four arrays of n u32, none overlapping).  *key_sorted (unless null) and *val_sorted = the two of
+// the four that hold the result.  hist_slot takes the run table (256 runs per tile of pb3d_sort_tile pairs: int64 starts, then u32
+// counts); the scans inside use scan_local_slot and scan_segs_slot, for 256 * tiles counts each.  Enqueued
+constexpr int pb3d_sort_tile = 2048;
+int pb3d_sort_pairs(pb3d_ctx* ctx, u32* key, u32* val, u32* key2, u32* val2, i64 n, i64 m, pb3d_slot hist_slot, pb3d_slot scan_local_slot,
+                    pb3d_slot scan_segs_slot, const u32** key_sorted, const u32** val_sorted);
 // csrc/nn.hip for csrc/icp.hip: bin the nr >= 1 reference points (one host wait for the exact box) into the three given slots; then,
 // any number of times, the position in the reference list of the nearest point ((d2, position) smallest: pb3d_knn_dev with k = 1) of
 // each of nq float64 queries -> d_idx (enqueued; only the query binning is redone)

@@ -33,6 +33,7 @@ from .preprocess_helpers import (crop_to_box, crop_to_box_resident, fit_plane_ra
 from .cluster import (cluster_points, cluster_points_resident, keep_largest_clusters, keep_largest_clusters_resident,  # noqa: F401
                       radius_neighbor_counts, radius_neighbor_counts_resident, select_points, select_points_resident)
 from .downsample import voxel_downsample, voxel_downsample_resident  # noqa: F401
+from .smooth import mesh_vertex_adjacency, mesh_vertex_adjacency_resident, smooth_mesh, smooth_mesh_resident  # noqa: F401
 from .eval_helpers_intra import (color_presence, compute_binary_gt, compute_global_depth_buffer, grid_depth_buffer, grid_visible_bits,  # noqa: F401
                                  points_visible_bits, project_part_visible, run_minaret_iou_evaluation, run_minaret_kp_evaluation,
                                  run_part_minaret_binary_iou)

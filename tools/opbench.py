@@ -1,5 +1,5 @@
 """Device-resident timing of every op of the path (M1..M8 of SURVEY.md 8(d), plus the N1/N2 kernels of the notebook-1 chain) on
-synthetic inputs.  Development/measurement tool: python tools/opbench.py [--size 1024] [--shape WxHxD] [--ops M1,M3,...,N2,overlays,ICP,PLANE,MESHD,CLUSTER,DOWNSAMPLE]; one JSON
+synthetic inputs.  Development/measurement tool: python tools/opbench.py [--size 1024] [--shape WxHxD] [--ops M1,M3,...,N2,overlays,ICP,PLANE,MESHD,CLUSTER,DOWNSAMPLE,SMOOTH]; one JSON
 line per op.  Pricing: `alg_B_per_voxel` is SURVEY 8(d)'s algorithmic figure for the sweeps that are EXECUTED (a folded 0-degree step
 moves nothing and is not priced); ops whose intermediates are not bytes (the bit-sliced chains) also carry `moved_B_per_voxel`, the
 bytes that cross the HBM by design, and their `frac_of_8TBs` is computed from THAT (never from bytes that are not moved)."""
@@ -260,6 +260,8 @@ def main():
         cluster(a.reps, res, cpu_ref=not a.no_cpu_ref)
     if "DOWNSAMPLE" in ops:
         downsample(a.reps, res, cpu_ref=not a.no_cpu_ref)
+    if "SMOOTH" in ops:
+        smooth(a.reps, res, cpu_ref=not a.no_cpu_ref)
     if "MESH" in ops:
         meshify(a.reps, res)
     if "DENS" in ops:
@@ -915,6 +917,69 @@ def downsample(reps, res, cpu_ref=True):
         print(json.dumps(r), flush=True)
         res.append(r)
     d_sfm.free(); d_tp.free()
+
+
+def smooth(reps, res, cpu_ref=True):
+    """SMOOTH, mesh_vertex_adjacency and smooth_mesh (csrc/smooth.hip) on the stride-1 mesh of the stored Taj grid (float32 vertices, int32
+    faces).  Resident, by device events (best mean of reps, host waits inside): the adjacency build alone, then 10 Taubin rounds and 1
+    Taubin round, each with its own adjacency build -- their difference over 18 is one step.  Beside a step, the time a plain
+    device-to-device copy of its bytes takes (positions read once per neighbour and once per vertex, the lists once, positions written
+    once), measured here with pb3d_d2d.  Then both through the NumPy API (upload, call, download; host wall clock, best of reps) and,
+    with cpu_ref, the restatement of tests/smooth_restate.py in NumPy on this host and whether the device's arrays equal it."""
+    import smooth_restate as sr
+    lib, L = pb3d._lib.load(), pb3d._lib
+    taj = np.load(os.path.join(ROOT, "tests", "golden", "stored_Taj_voxel_grid.npz"))["voxel_grid"]
+    v, f = pb3d.meshify_colored_voxel_grid(taj, stride=1)[:2]
+    nv, nf = len(v), len(f)
+    d_v, d_f = dev.from_numpy(v), dev.from_numpy(f)
+    bufs = [dev.DeviceBuffer((nv + 1) * 8), dev.DeviceBuffer(6 * nf * 4), dev.DeviceBuffer(6 * nf * 4), dev.DeviceBuffer(nv), dev.DeviceBuffer(nv * 12)]
+    d_st, d_nb, d_mu, d_bd, d_out = (C.c_void_p(b.ptr) for b in bufs)
+    total = C.c_int64(0)
+
+    def adjacency():
+        L.check(lib.pb3d_mesh_adjacency_resident(L.ctx(), C.c_void_p(d_f.ptr), 0, nv, nf, d_st, d_nb, d_mu, d_bd, C.byref(total)))
+
+    def taubin(iterations):
+        return lambda: L.check(lib.pb3d_mesh_smooth_resident(L.ctx(), C.c_void_p(d_v.ptr), 0, nv, C.c_void_p(d_f.ptr), 0, nf, iterations, 0.5, -0.53,
+                                                             None, 0, d_out))
+
+    def best(fn):
+        return min(timeit(fn, reps, warm=1) for _ in range(2))
+
+    t_adj, t10, t1 = best(adjacency), best(taubin(10)), best(taubin(1))
+    starts = bufs[0].download((nv + 1,), np.int64)
+    step_bytes = int(total.value) * (24 + 4) + nv * (24 + 24) + (nv + 1) * 8
+    d_a, d_b = dev.DeviceBuffer(step_bytes // 2), dev.DeviceBuffer(step_bytes // 2)       # a copy reads and writes: half the bytes each way
+    t_copy = best(lambda: L.check(lib.pb3d_d2d(L.ctx(), C.c_void_p(d_b.ptr), C.c_void_p(d_a.ptr), step_bytes // 2)))
+    d_a.free(); d_b.free()
+    step = (t10 - t1) / 18.0
+    r = {"op": "SMOOTH", "name": "mesh smoothing: stored Taj, stride 1", "nverts": nv, "nfaces": nf, "pairs": 6 * nf, "unique_pairs": int(total.value),
+         "max_degree": int(np.diff(starts).max()), "adjacency_ms": round(t_adj, 4), "taubin10_ms": round(t10, 4), "taubin1_ms": round(t1, 4),
+         "step_ms": round(step, 4), "step_bytes": step_bytes, "step_GB_s": round(step_bytes / step / 1e6, 1), "copy_of_step_bytes_ms": round(t_copy, 4),
+         "step_over_copy": round(step / t_copy, 2), "adjacency_share_of_taubin10": round(t_adj / t10, 3)}
+    wall = {"adjacency": [], "taubin10": []}
+    for _ in range(reps + 1):
+        t0 = time.perf_counter()
+        got_adj = pb3d.mesh_vertex_adjacency(f, nv, return_multiplicity=True, return_boundary=True)
+        wall["adjacency"].append(time.perf_counter() - t0)
+        t0 = time.perf_counter()
+        got = pb3d.smooth_mesh(v, f)
+        wall["taubin10"].append(time.perf_counter() - t0)
+    r["numpy_api_adjacency_ms"] = round(1e3 * min(wall["adjacency"][1:]), 2)
+    r["numpy_api_taubin10_ms"] = round(1e3 * min(wall["taubin10"][1:]), 2)
+    if cpu_ref:
+        t0 = time.perf_counter()
+        ref_adj = sr.adjacency(f, nv)
+        r["numpy_restatement_adjacency_ms"] = round(1e3 * (time.perf_counter() - t0), 1)
+        t0 = time.perf_counter()
+        ref = sr.restate(v, f)
+        r["numpy_restatement_taubin10_ms"] = round(1e3 * (time.perf_counter() - t0), 1)
+        r["adjacency_equal"] = bool(all(np.array_equal(g, w) for g, w in zip(got_adj, ref_adj)))
+        r["taubin10_equal"] = bool(got.tobytes() == ref.tobytes())
+    for b in bufs + [d_v, d_f]:
+        b.free()
+    print(json.dumps(r), flush=True)
+    res.append(r)
 
 
 def meshify(reps, res):
