@@ -872,8 +872,8 @@ static int label_colors_impl(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, i
     // the component counts and -- optimistically -- the statistics of the first kFirst components of every colour come back in ONE copy
     struct Rec { int bb[8]; unsigned long long cs[4]; };
     static_assert(sizeof(Rec) == 64, "the statistics block is 64-byte records");
-    char* hb = (char*)ctx->pinned + 1024;
-    static_assert(64 + (size_t)kMaxColors * kFirst * 64 + 1024 + 64 <= (1 << 16), "the pinned area holds the read-back block");
+    char* hb = (char*)ctx->pinned + pb3d_pinned_ccl;
+    static_assert(pb3d_pinned_ccl + 64 + (size_t)kMaxColors * kFirst * 64 + pb3d_pinned_flag <= pb3d_pinned_bytes, "the pinned area holds the read-back block");
     PB3D_HIP(hipMemcpyAsync(hb, sblk, stats ? head_bytes : 64, hipMemcpyDeviceToHost, ctx->stream));
     PB3D_TRY(pb3d_stream_sync(ctx));
     const i64* nroots = (const i64*)hb;

@@ -286,9 +286,8 @@ int pb3d_cluster_points_resident(pb3d_ctx* ctx, const void* d_pts, int pts_f64, 
     PB3D_CHECK_LAUNCH();
     PB3D_TRY(t.mark(ctx));
     PB3D_TRY(pb3d_scan_counts(ctx, (const u32*)flags, n, (i64*)ranks, PB3D_SLOT_CLUSTER_SCAN_LOCAL, PB3D_SLOT_CLUSTER_SCAN_SEGS));
-    PB3D_HIP(hipMemcpyAsync(ctx->pinned, (const i64*)ranks + n, sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
-    PB3D_TRY(pb3d_stream_sync(ctx));
-    const i64 nc = *(const i64*)ctx->pinned;
+    i64 nc;
+    PB3D_TRY(pb3d_read_back(ctx, &nc, (const i64*)ranks + n, sizeof(i64)));
     PB3D_TRY(t.mark(ctx));
     if (nc > 0) PB3D_HIP(hipMemsetAsync(d_sizes, 0, (size_t)nc * sizeof(int64_t), ctx->stream));
     hipLaunchKernelGGL((pts_f64 ? k_cluster_labels<true> : k_cluster_labels<false>), grid, dim3(256), 0, ctx->stream, d_pts, (i64)n, order, ix, eps2,

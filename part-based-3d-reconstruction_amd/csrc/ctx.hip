@@ -87,7 +87,7 @@ int pb3d_create(int device, pb3d_ctx** out) {
         const char* v = getenv("PB3D_DEVICE_POOL_MB");
         ctx->pool_cap = v ? (size_t)(atoll(v) < 0 ? 0 : atoll(v)) << 20 : (size_t)prop.totalGlobalMem / 4;
     }
-    ctx->pinned_bytes = 1 << 16;
+    ctx->pinned_bytes = pb3d_pinned_bytes;
     e = hipHostMalloc(&ctx->pinned, ctx->pinned_bytes, hipHostMallocDefault);
     if (e != hipSuccess) {
         (void)hipEventDestroy(ctx->s32_ev);
@@ -396,6 +396,14 @@ int pb3d_stream_sync(pb3d_ctx* ctx) {
     PB3D_HIP(hipStreamSynchronize(ctx->stream));
     ctx->stage_head = 0;
     ++ctx->sync_count;
+    return PB3D_OK;
+}
+
+int pb3d_read_back(pb3d_ctx* ctx, void* host_dst, const void* d_src, size_t bytes) {
+    PB3D_REQUIRE(bytes <= pb3d_pinned_head, "pb3d_read_back: %zu bytes exceed the %zu-byte head of the pinned area", bytes, pb3d_pinned_head);
+    PB3D_HIP(hipMemcpyAsync(ctx->pinned, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    PB3D_TRY(pb3d_stream_sync(ctx));
+    memcpy(host_dst, ctx->pinned, bytes);
     return PB3D_OK;
 }
 

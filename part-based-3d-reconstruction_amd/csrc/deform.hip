@@ -172,9 +172,8 @@ int centers(pb3d_ctx* ctx, const float* d_pts, i64 n, double sxz, double sy, dou
     hipLaunchKernelGGL(k_deform_sum, dim3(pb3d_stream_blocks(ctx, n, 256, 4)), dim3(256), 0, ctx->stream, d_pts, n,
                        (unsigned long long*)acc);
     PB3D_CHECK_LAUNCH();
-    PB3D_HIP(hipMemcpyAsync(ctx->pinned, acc, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    PB3D_TRY(pb3d_stream_sync(ctx));
-    const long long* h = (const long long*)ctx->pinned;
+    long long h[4];
+    PB3D_TRY(pb3d_read_back(ctx, h, acc, sizeof(h)));
     if (h[3] != 0) {
         pb3d_set_error("pb3d_deform: %lld point coordinates are not voxel indices (integer-valued, |v| < 2^22)", h[3]);
         return PB3D_EUNSUPPORTED;
@@ -226,9 +225,8 @@ int pb3d_deform_count_dev(pb3d_ctx* ctx, const float* d_pts, int64_t n, double s
     const unsigned blocks = pb3d_stream_blocks(ctx, 7 * n, 256, 8);
     hipLaunchKernelGGL(k_deform_bbox, dim3(blocks), dim3(256), 0, ctx->stream, d_pts, n, P, (int*)bbv);
     PB3D_CHECK_LAUNCH();
-    PB3D_HIP(hipMemcpyAsync(ctx->pinned, bbv, sizeof(init), hipMemcpyDeviceToHost, ctx->stream));
-    PB3D_TRY(pb3d_stream_sync(ctx));
-    const int* bb = (const int*)ctx->pinned;
+    int bb[8];
+    PB3D_TRY(pb3d_read_back(ctx, bb, bbv, sizeof(bb)));
     if (bb[6]) {
         pb3d_set_error("pb3d_deform: deformed coordinates exceed +-2^30");
         return PB3D_EUNSUPPORTED;
@@ -292,9 +290,9 @@ int pb3d_scatter_colors_dev(pb3d_ctx* ctx, const int64_t* d_coords, const uint8_
     hipLaunchKernelGGL(k_scatter_colors, dim3(pb3d_stream_blocks(ctx, m, 256, 8)), dim3(256), 0, ctx->stream, (const i64*)d_coords,
                        d_cols, m, A0, A1, A2, d_grid, (int*)flag);
     PB3D_CHECK_LAUNCH();
-    PB3D_HIP(hipMemcpyAsync(ctx->pinned, flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    PB3D_TRY(pb3d_stream_sync(ctx));
-    if (*(const int*)ctx->pinned) {
+    int bad;
+    PB3D_TRY(pb3d_read_back(ctx, &bad, flag, sizeof(bad)));
+    if (bad) {
         pb3d_set_error("index out of bounds in pb3d_scatter_colors (NumPy would raise IndexError)");
         return PB3D_EINVAL;
     }

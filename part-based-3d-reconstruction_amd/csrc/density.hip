@@ -157,16 +157,14 @@ extern "C" int pb3d_density_grid_resident(pb3d_ctx* ctx, const void* d_pts, int 
 
     const int G = grid_size;
     const size_t vol_bytes = (size_t)G * G * G * sizeof(u32);
-    void *bb, *vol, *wtab;
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_DENSITY_BOUNDS, 6 * sizeof(double), &bb));
+    void *vol, *wtab;
     PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_DENSITY_COUNTS, vol_bytes, &vol));
     PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_DENSITY_WEIGHTS, (size_t)(kMaxRadius + 1) * sizeof(double), &wtab));
-    PB3D_TRY(pb3d_points_bounds_dev(ctx, d_pts, pts_f64, n, (double*)bb));
-    PB3D_HIP(hipMemcpyAsync(ctx->pinned, bb, 6 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    // in front of the box, so that it is done under the box's host wait and not after it.  The bounds kernel right behind the fill runs
+    // some 6 us longer than behind anything else (53 -> 59 us on 12 M points, profiles/onecopy_bounds_after_fill.txt)
     PB3D_HIP(hipMemsetAsync(vol, 0, vol_bytes, ctx->stream));
-    PB3D_TRY(pb3d_stream_sync(ctx));
     double b[6];
-    memcpy(b, ctx->pinned, sizeof(b));
+    PB3D_TRY(pb3d_points_box(ctx, d_pts, pts_f64, n, PB3D_SLOT_DENSITY_BOUNDS, b));
     for (int k = 0; k < 6; ++k)
         PB3D_REQUIRE(std::isfinite(b[k]), "pb3d_density_grid: the points' bounds are not finite (NaN or infinite coordinates)");
 

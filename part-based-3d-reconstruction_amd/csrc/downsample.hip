@@ -14,18 +14,19 @@
 // order to begin with, go through a stable LSD radix sort on the voxel number (pb3d_sort_pairs, csrc/sort_pairs.hip: 8-bit digits over
 // the bits m - 1 needs, one pass for up to 256 voxels, four at most), which leaves every voxel's positions ascending and the voxels in
 // order, with no per-voxel state: a voxel that holds the whole cloud is sorted like any other.
-//   k_voxel_centroid  one wavefront per voxel: 64 positions a time are gathered (the next 64 are in flight meanwhile), then every lane adds
-//                     the same 64 values in order from 0.0 by readlane, one rounded addition each; one correctly rounded division
+//   k_voxel_centroid  one wavefront per voxel: the ordered wavefront sum of csrc/ordered_sum.h (which states the order of the additions)
+//                     over the voxel's positions, then one correctly rounded division
 // No floating-point atomic anywhere, and -ffp-contract=off (Makefile) keeps the additions apart.
+#include <algorithm>
 #include <cmath>
 
+#include "ordered_sum.h"
 #include "pb3d_internal.h"
 
 namespace {
 
 constexpr double kCells = 2097152.0;                // 2^21 cells per axis
 constexpr u64 kEmpty = ~0ull;                       // no key has bit 63
-constexpr int kTile = pb3d_sort_tile;               // pairs per workgroup of a sort pass (csrc/sort_pairs.hip)
 
 struct Vox { double o[3], size; };
 // one slot of the table: the three words a point touches share a 16-byte record, so an insertion lands in one cache line
@@ -40,12 +41,6 @@ __device__ __forceinline__ u64 cell_of(double p, double o, double size) {
     return (u64)c;
 }
 
-__device__ __forceinline__ u64 mix(u64 k) {         // splitmix64's finaliser
-    k ^= k >> 30; k *= 0xbf58476d1ce4e5b9ull;
-    k ^= k >> 27; k *= 0x94d049bb133111ebull;
-    return k ^ (k >> 31);
-}
-
 __global__ __launch_bounds__(256) void k_table_clear(Slot* table, u64 cap) {
     for (u64 s = (u64)blockIdx.x * 256 + threadIdx.x; s < cap; s += (u64)gridDim.x * 256) table[s] = {kEmpty, 0xffffffffu, 0u};
 }
@@ -58,7 +53,7 @@ __global__ __launch_bounds__(256) void k_voxel_insert(const void* __restrict__ p
     double p[3];
     pb3d_load3<F64>(pts, i, p);
     const u64 key = (cell_of(p[0], vx.o[0], vx.size) << 42) | (cell_of(p[1], vx.o[1], vx.size) << 21) | cell_of(p[2], vx.o[2], vx.size);
-    u64 s = mix(key) & (cap - 1);
+    u64 s = pb3d_mix64(key) & (cap - 1);
     while (true) {
         u64 cur = __hip_atomic_load(&table[s].key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (cur == kEmpty) cur = atomicCAS((unsigned long long*)&table[s].key, (unsigned long long)kEmpty, (unsigned long long)key);
@@ -110,17 +105,6 @@ __global__ __launch_bounds__(256) void k_voxel_number(const T* __restrict__ pts,
 }
 
 // ---- centroids --------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double from_lane(double x, int j) {      // lane j's x in every lane (j is the same in all of them)
-    const int lo = __builtin_amdgcn_readlane(__double2loint(x), j), hi = __builtin_amdgcn_readlane(__double2hiint(x), j);
-    return __hiloint2double(hi, lo);
-}
-
-template <bool F64>
-__device__ __forceinline__ void gather(const void* pts, const u32* pos, i64 p, i64 e, double v[3]) {
-    v[0] = v[1] = v[2] = 0.0;
-    if (p < e) pb3d_load3<F64>(pts, (i64)pos[p], v);
-}
-
 // start[v] .. start[v + 1]: voxel v's run of pos[], ascending positions.  However long the run, the wavefront walks it 64 a time
 template <bool F64>
 __global__ __launch_bounds__(256) void k_voxel_centroid(const void* __restrict__ pts, const u32* __restrict__ pos, const i64* __restrict__ start, i64 m,
@@ -129,18 +113,8 @@ __global__ __launch_bounds__(256) void k_voxel_centroid(const void* __restrict__
     const i64 v = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) + (i64)blockIdx.x * 4;
     if (v >= m) return;
     const i64 s = start[v], e = start[v + 1];
-    double sum[3] = {0.0, 0.0, 0.0}, cur[3], nxt[3];
-    gather<F64>(pts, pos, s + lane, e, cur);
-    for (i64 p = s; p < e; p += 64) {
-        gather<F64>(pts, pos, p + 64 + lane, e, nxt);
-        const int c = (int)(e - p < 64 ? e - p : 64);
-        for (int j = 0; j < c; ++j) {
-            sum[0] = sum[0] + from_lane(cur[0], j);
-            sum[1] = sum[1] + from_lane(cur[1], j);
-            sum[2] = sum[2] + from_lane(cur[2], j);
-        }
-        for (int a = 0; a < 3; ++a) cur[a] = nxt[a];
-    }
+    double sum[3];
+    ordered_sum(s, e, [&](i64 p, double* row) { pb3d_load3<F64>(pts, (i64)pos[p], row); }, sum);
     if (lane < 3) {
         const double q = __ddiv_rn(sum[lane], (double)(e - s));
         if (F64) ((double*)out)[3 * v + lane] = q;
@@ -179,13 +153,8 @@ extern "C" int pb3d_voxel_downsample_resident(pb3d_ctx* ctx, const void* d_pts, 
 
     // the exact bounds (first host wait) decide ORIGIN and RANGE: subtraction, division and floor are monotone, so the cells of lo and
     // hi enclose every point's
-    void* bb;
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_DOWNSAMPLE_BOUNDS, 6 * sizeof(double), &bb));
-    PB3D_TRY(pb3d_points_bounds_dev(ctx, d_pts, pts_f64, n, (double*)bb));
-    PB3D_HIP(hipMemcpyAsync(ctx->pinned, bb, 6 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    PB3D_TRY(pb3d_stream_sync(ctx));
     double b[6];
-    memcpy(b, ctx->pinned, sizeof(b));
+    PB3D_TRY(pb3d_points_box(ctx, d_pts, pts_f64, n, PB3D_SLOT_DOWNSAMPLE_BOUNDS, b));
     Vox vx;
     vx.size = voxel_size;
     const double h = 0.5 * voxel_size;
@@ -200,16 +169,13 @@ extern "C" int pb3d_voxel_downsample_resident(pb3d_ctx* ctx, const void* d_pts, 
     u64 cap = 64;
     while (cap < 2 * (u64)n) cap <<= 1;
     const bool centroid = reduce == PB3D_DOWNSAMPLE_CENTROID;
-    void *tab, *slot_of, *flags, *ranks, *local;
+    void *tab, *slot_of, *flags, *ranks;
     PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_DOWNSAMPLE_TABLE, (size_t)cap * sizeof(Slot), &tab));
     PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_DOWNSAMPLE_POINT_SLOT, (size_t)n * sizeof(u32), &slot_of));
     PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_DOWNSAMPLE_FLAGS, (size_t)n * sizeof(u32), &flags));
     PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_DOWNSAMPLE_RANKS, (size_t)(n + 1) * sizeof(i64), &ranks));
-    if (centroid) {     // the largest scan of the call may be the sort's: size both scan slots for it now, so none regrows (and waits) midway
-        const i64 nruns = 256 * ((n + kTile - 1) / kTile), most = nruns > n ? nruns : n;
-        PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_DOWNSAMPLE_SCAN_LOCAL, (size_t)most * sizeof(u32), &local));
-        PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_DOWNSAMPLE_SCAN_SEGS, (size_t)(most / 1024 + 1) * (sizeof(u32) + sizeof(i64)), &local));
-    }
+    if (centroid)       // the largest scan of the call may be the sort's: size both scan slots for it now, so none regrows (and waits) midway
+        PB3D_TRY(pb3d_scan_reserve(ctx, std::max<i64>(n, pb3d_sort_scan_items(n)), PB3D_SLOT_DOWNSAMPLE_SCAN_LOCAL, PB3D_SLOT_DOWNSAMPLE_SCAN_SEGS));
     Slot* table = (Slot*)tab;
     hipLaunchKernelGGL(k_table_clear, dim3(pb3d_stream_blocks(ctx, (i64)cap, 256, 8)), dim3(256), 0, ctx->stream, table, cap);
     PB3D_CHECK_LAUNCH();
@@ -220,9 +186,8 @@ extern "C" int pb3d_voxel_downsample_resident(pb3d_ctx* ctx, const void* d_pts, 
     hipLaunchKernelGGL(k_voxel_flags, grid, dim3(256), 0, ctx->stream, (i64)n, (const u32*)slot_of, (const Slot*)table, (u32*)flags);
     PB3D_CHECK_LAUNCH();
     PB3D_TRY(pb3d_scan_counts(ctx, (const u32*)flags, n, (i64*)ranks, PB3D_SLOT_DOWNSAMPLE_SCAN_LOCAL, PB3D_SLOT_DOWNSAMPLE_SCAN_SEGS));
-    PB3D_HIP(hipMemcpyAsync(ctx->pinned, (const i64*)ranks + n, sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
-    PB3D_TRY(pb3d_stream_sync(ctx));
-    const i64 m = *(const i64*)ctx->pinned;
+    i64 m;
+    PB3D_TRY(pb3d_read_back(ctx, &m, (const i64*)ranks + n, sizeof(i64)));
 
     // the flags are spent: a centroid call without d_counts keeps its counts there
     u32* counts = d_counts ? d_counts : centroid ? (u32*)flags : nullptr;

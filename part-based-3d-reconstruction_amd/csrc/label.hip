@@ -240,13 +240,6 @@ __global__ __launch_bounds__(256) void k_label_final(const u8* __restrict__ labe
     }
 }
 
-int read_flag(pb3d_ctx* ctx, const int* d_flag, int* out) {
-    PB3D_HIP(hipMemcpyAsync(ctx->pinned, d_flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    PB3D_TRY(pb3d_stream_sync(ctx));
-    *out = *(const int*)ctx->pinned;
-    return PB3D_OK;
-}
-
 int palette_words(const u8* palette, int npal, u32* pal) {
     PB3D_REQUIRE(npal >= 0 && npal <= 254 && (npal == 0 || palette), "pb3d label ops: palette of 0..254 colours");
     for (int k = 0; k < 256; ++k) pal[k] = 0;
@@ -273,7 +266,7 @@ int pb3d_rgb_to_label_dev(pb3d_ctx* ctx, const uint8_t* d_rgb, int64_t nvox, con
                        (int*)flag);
     PB3D_CHECK_LAUNCH();
     int bad = 0;
-    PB3D_TRY(read_flag(ctx, (const int*)flag, &bad));
+    PB3D_TRY(pb3d_read_back(ctx, &bad, flag, sizeof(bad)));
     PB3D_REQUIRE(!bad, "pb3d_rgb_to_label: the grid holds a colour that is neither black nor in the palette");
     return PB3D_OK;
 }
@@ -300,7 +293,7 @@ int pb3d_label_to_rgb_dev(pb3d_ctx* ctx, const uint8_t* d_label, int64_t nvox, c
     int* flag;
     PB3D_TRY(label_to_rgb_launch(ctx, d_label, nvox, palette, npal, d_rgb, &flag));
     int bad = 0;
-    PB3D_TRY(read_flag(ctx, flag, &bad));
+    PB3D_TRY(pb3d_read_back(ctx, &bad, flag, sizeof(bad)));
     PB3D_REQUIRE(!bad, "pb3d_label_to_rgb: a label exceeds the palette size");
     return PB3D_OK;
 }

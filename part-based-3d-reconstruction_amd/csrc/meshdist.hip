@@ -55,6 +55,7 @@
 // sample and one weighted sum per coordinate.  Nothing depends on the launch shape: two runs give the same bytes.
 #include <cmath>
 
+#include "mesh_index.h"
 #include "pb3d_internal.h"
 #include "ring_walk.h"
 
@@ -64,27 +65,11 @@ constexpr i64 kEntryCap = 8;            // (cell, face) entries per face the ind
 constexpr int kPrefixBlock = 1024;      // faces per block of the cumulative area sum (include/pb3d.h)
 constexpr int kNoFace = 0x7fffffff;
 
-template <bool I64>
-__device__ __forceinline__ i64 load_index(const void* p, i64 e) {
-    return I64 ? ((const i64*)p)[e] : (i64)((const int*)p)[e];
-}
-// a checked index in [-nv, nv) as NumPy reads it
-__device__ __forceinline__ i64 wrap(i64 v, i64 nv) { return v < 0 ? v + nv : v; }
-
 // the corners of face f, widened: t[0..3) = a, t[3..6) = b, t[6..9) = c
 template <bool VF64, bool I64>
 __device__ __forceinline__ void load_face(const void* verts, i64 nv, const void* faces, i64 f, double t[9]) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) pb3d_load3<VF64>(verts, wrap(load_index<I64>(faces, 3 * f + c), nv), t + 3 * c);
-}
-
-// fn(VF64, I64) with the mesh's vertex and index widths as compile-time constants
-template <class Fn>
-void with_mesh_types(int verts_f64, int faces_i64, Fn fn) {
-    if (verts_f64 && faces_i64) fn(std::true_type{}, std::true_type{});
-    else if (verts_f64) fn(std::true_type{}, std::false_type{});
-    else if (faces_i64) fn(std::false_type{}, std::true_type{});
-    else fn(std::false_type{}, std::false_type{});
 }
 
 // ---- d2(q, face) and the closest point ----------------------------------------------------------------------------------------------
@@ -294,20 +279,19 @@ struct MeshIndex { Grid g; const i64* starts; const int* ids; const double* tri;
 
 // faces checked; nv, nf >= 1
 int build_index(pb3d_ctx* ctx, const void* d_verts, int verts_f64, i64 nv, const void* d_faces, int faces_i64, i64 nf, MeshIndex* ix) {
-    void *tri, *rb, *cnt, *st, *ids;
+    void *tri, *cnt, *st, *ids;
     PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESHD_CORNERS, (size_t)nf * 9 * sizeof(double), &tri));
     with_mesh_types(verts_f64, faces_i64, [&](auto V, auto I) {
         hipLaunchKernelGGL((k_face_corners<decltype(V)::value, decltype(I)::value>), dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, ctx->stream,
                            d_verts, nv, d_faces, nf, (double*)tri);
     });
     PB3D_CHECK_LAUNCH();
-    // the exact box of ALL vertices (k_bounds_* of csrc/nn.hip): an unreferenced vertex only enlarges it
+    // the exact box of ALL vertices (k_bounds_* of csrc/nn.hip): an unreferenced vertex only enlarges it.  The slot holds 8 doubles:
+    // the box, then the entry total at + 6
+    void* rb;
     PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESHD_READBACK, 8 * sizeof(double), &rb));
-    PB3D_TRY(pb3d_points_bounds_dev(ctx, d_verts, verts_f64, nv, (double*)rb));
-    PB3D_HIP(hipMemcpyAsync(ctx->pinned, rb, 6 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    PB3D_TRY(pb3d_stream_sync(ctx));
     double b[6];
-    memcpy(b, ctx->pinned, sizeof(b));
+    PB3D_TRY(pb3d_points_box(ctx, d_verts, verts_f64, nv, PB3D_SLOT_MESHD_READBACK, b));
     for (int a = 0; a < 6; ++a) PB3D_REQUIRE(std::isfinite(b[a]), "pb3d_mesh_dist: the vertices must be finite");
     Grid g = make_grid(b, nf);
     unsigned long long* d_total = (unsigned long long*)rb + 6;
@@ -318,9 +302,7 @@ int build_index(pb3d_ctx* ctx, const void* d_verts, int verts_f64, i64 nv, const
         PB3D_HIP(hipMemsetAsync(d_total, 0, sizeof(unsigned long long), ctx->stream));
         hipLaunchKernelGGL(k_face_entries, dim3(nb), dim3(256), 0, ctx->stream, (const double*)tri, nf, g, d_total);
         PB3D_CHECK_LAUNCH();
-        PB3D_HIP(hipMemcpyAsync(ctx->pinned, d_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-        PB3D_TRY(pb3d_stream_sync(ctx));
-        memcpy(&total, ctx->pinned, sizeof(total));
+        PB3D_TRY(pb3d_read_back(ctx, &total, d_total, sizeof(total)));
         if (total <= (unsigned long long)(kEntryCap * nf) || g.ncells == 1) break;
         g = coarsen(g);
         ++coarsenings;
@@ -345,12 +327,7 @@ int build_index(pb3d_ctx* ctx, const void* d_verts, int verts_f64, i64 nv, const
 }
 
 // ---- sampling ---------------------------------------------------------------------------------------------------------------------------
-__host__ __device__ __forceinline__ u64 mix64(u64 x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
+__host__ __device__ __forceinline__ u64 mix64(u64 x) { return pb3d_mix64(x + 0x9e3779b97f4a7c15ull); }
 // r_j(i) in [0, 1): 53 bits
 __device__ __forceinline__ double unit_random(u64 key, u64 i, u64 j) { return (double)(mix64(key + 3 * i + j) >> 11) * 0x1p-53; }
 
@@ -485,10 +462,8 @@ int pb3d_mesh_sample_resident(pb3d_ctx* ctx, const void* d_verts, int verts_f64,
     PB3D_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_prefix_add, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, ctx->stream, (double*)cum, (i64)nf, (const double*)blk);
     PB3D_CHECK_LAUNCH();
-    PB3D_HIP(hipMemcpyAsync(ctx->pinned, (const double*)cum + (nf - 1), sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    PB3D_TRY(pb3d_stream_sync(ctx));
     double total;
-    memcpy(&total, ctx->pinned, sizeof(total));
+    PB3D_TRY(pb3d_read_back(ctx, &total, (const double*)cum + (nf - 1), sizeof(total)));
     PB3D_REQUIRE(std::isfinite(total) && total > 0.0, "pb3d_mesh_sample: the mesh's total area must be finite and positive (got %g)", total);
     with_mesh_types(verts_f64, faces_i64, [&](auto V, auto I) {
         hipLaunchKernelGGL((k_mesh_sample<decltype(V)::value, decltype(I)::value>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,

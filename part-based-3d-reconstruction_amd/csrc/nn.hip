@@ -313,13 +313,8 @@ int bin_points(pb3d_ctx* ctx, const void* d_pts, i64 n, const Grid& g, pb3d_slot
 
 // the reference set's exact box, read back once, and the cell grid made from it
 int grid_of(pb3d_ctx* ctx, const void* d_r, int r_f64, i64 nr, Grid* g) {
-    void* bb;
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_NN_BOUNDS, 6 * sizeof(double), &bb));
-    PB3D_TRY(launch_bounds(ctx, d_r, r_f64, nr, (double*)bb));
-    PB3D_HIP(hipMemcpyAsync(ctx->pinned, bb, 6 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    PB3D_TRY(pb3d_stream_sync(ctx));
     double b[6];
-    memcpy(b, ctx->pinned, sizeof(b));
+    PB3D_TRY(pb3d_points_box(ctx, d_r, r_f64, nr, PB3D_SLOT_NN_BOUNDS, b));
     *g = make_grid(b, nr);
     return PB3D_OK;
 }
@@ -387,6 +382,13 @@ int launch_knn(pb3d_ctx* ctx, const pb3d_nn_index& ix, const void* d_q, int q_f6
 }
 
 }  // namespace
+
+int pb3d_points_box(pb3d_ctx* ctx, const void* d_pts, int f64, i64 n, pb3d_slot slot, double b[6]) {
+    void* bb;
+    PB3D_TRY(pb3d_scratch(ctx, slot, 6 * sizeof(double), &bb));
+    PB3D_TRY(launch_bounds(ctx, d_pts, f64, n, (double*)bb));
+    return pb3d_read_back(ctx, b, bb, 6 * sizeof(double));
+}
 
 // ---- the index kept between calls (csrc/icp.hip): pb3d_knn_dev's two halves, the reference half into the caller's slots ------------
 int pb3d_nn_index_build(pb3d_ctx* ctx, const void* d_r, int r_f64, i64 nr, pb3d_slot starts_slot, pb3d_slot coords_slot, pb3d_slot ids_slot,

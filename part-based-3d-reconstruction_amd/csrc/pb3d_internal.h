@@ -311,7 +311,7 @@ struct pb3d_ctx {
     // Growable device scratch slots, named by enum pb3d_slot (no hipMalloc / hipFree per call once warm).
     void* scratch[PB3D_SLOT_COUNT];
     size_t scratch_bytes[PB3D_SLOT_COUNT];
-    // small pinned host area for counters read back from the device
+    // small pinned host area for counters read back from the device; who owns which bytes: pb3d_pinned_* below
     void* pinned;
     size_t pinned_bytes;
     // pinned staging ring of pb3d_h2d_async: small host inputs (2-D masks, descriptors) go up without a host wait
@@ -411,6 +411,17 @@ static inline pb3d_ctx::PointsArgs pb3d_points_args(const void* grid, i64 A0, i6
 }
 // hipStreamSynchronize(ctx->stream) + bookkeeping (the staging ring is empty afterwards)
 int pb3d_stream_sync(pb3d_ctx* ctx);
+// ---- the pinned read-back area (pb3d_ctx::pinned), three disjoint regions:
+//   [0, pb3d_pinned_head)                  pb3d_read_back: complete when the call returns, so free again for the next one
+//   [pb3d_pinned_ccl, ... - flag)          csrc/ccl.hip's counts and statistics block (it static_asserts that it ends before the flag)
+//   the last pb3d_pinned_flag bytes        csrc/sliced.hip's "not 0/1" word: its copy completes behind an event (s32_ev), not behind
+//                                          the caller's next wait, so nothing else may ever be written there
+constexpr size_t pb3d_pinned_bytes = 1 << 16;
+constexpr size_t pb3d_pinned_ccl = 1024;
+constexpr size_t pb3d_pinned_head = pb3d_pinned_ccl;
+constexpr size_t pb3d_pinned_flag = 64;
+// d_src[0, bytes) -> host_dst through the head of the pinned area: one copy, one host wait (pb3d_stream_sync), one memcpy out
+int pb3d_read_back(pb3d_ctx* ctx, void* host_dst, const void* d_src, size_t bytes);
 
 // grid size for grid-stride streaming kernels: enough blocks to fill 256 CUs, capped
 // blocks_per_cu <= 0: no cap -- one workgroup per tile of the stream.  For write-heavy or latency-heavy streams the dispatcher balances
@@ -451,6 +462,14 @@ __device__ __forceinline__ u32 pb3d_div(u32 n, const pb3d_magic g) {
     return (t + ((n - t) >> g.sa)) >> g.sb;
 }
 
+// splitmix64's finaliser.  The generator's step is pb3d_mix64(z + 0x9e3779b97f4a7c15) (csrc/synth.hip, the sampler of csrc/meshdist.hip);
+// csrc/downsample.hip hashes its voxel keys with the finaliser alone
+__host__ __device__ inline u64 pb3d_mix64(u64 z) {
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+
 // what a labelling leaves on the device (csrc/ccl.hip): total[k] = components of colour k, records[(k * dcap + c) * 64] = 64-byte statistics
 // record of component c + 1 {int lo[3], hi[3] (inclusive), pad[2]; u64 count, sum[3]}, valid for c < min(total[k], dcap)
 struct pb3d_ccl_dev { const i64* total; const char* records; int dcap; };
@@ -460,13 +479,19 @@ int pb3d_ccl_label_on_device(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, i
 // ---- kernels' host launchers used across translation units ---------------------------------
 // exclusive scan of n u32 counts into n + 1 int64 offsets (the last = total) with points.hip's scan kernels; scratch slots local_slot, seg_slot
 int pb3d_scan_counts(pb3d_ctx* ctx, const u32* d_counts, i64 n, i64* d_offsets, pb3d_slot local_slot, pb3d_slot seg_slot);
+// the two slots grown for a scan of n counts (pb3d_scan_counts does it itself): a caller with several scans ahead reserves for the
+// largest first, so that no slot regrows (and waits) midway
+int pb3d_scan_reserve(pb3d_ctx* ctx, i64 n, pb3d_slot local_slot, pb3d_slot seg_slot);
 // csrc/sort_pairs.hip for csrc/downsample.hip and csrc/smooth.hip: the n >= 1 pairs (key[i], val[i]) sorted stably by key < m, through
 // the ping-pong twins key2 / val2 (four arrays of n u32, none overlapping).  *key_sorted (unless null) and *val_sorted = the two of
 // the four that hold the result.  hist_slot takes the run table (256 runs per tile of pb3d_sort_tile pairs: int64 starts, then u32
-// counts); the scans inside use scan_local_slot and scan_segs_slot, for 256 * tiles counts each.  Enqueued
+// counts); the scans inside use scan_local_slot and scan_segs_slot, for pb3d_sort_scan_items(n) counts each.  Enqueued
 constexpr int pb3d_sort_tile = 2048;
+inline i64 pb3d_sort_scan_items(i64 n) { return 256 * ((n + pb3d_sort_tile - 1) / pb3d_sort_tile); }   // the counts one pass of n pairs scans
 int pb3d_sort_pairs(pb3d_ctx* ctx, u32* key, u32* val, u32* key2, u32* val2, i64 n, i64 m, pb3d_slot hist_slot, pb3d_slot scan_local_slot,
                     pb3d_slot scan_segs_slot, const u32** key_sorted, const u32** val_sorted);
+// csrc/nn.hip: the exact bounding box of n >= 1 points on the host: bounds kernel into `slot` (>= 6 doubles), pb3d_read_back; one host wait
+int pb3d_points_box(pb3d_ctx* ctx, const void* d_pts, int f64, i64 n, pb3d_slot slot, double b[6]);
 // csrc/nn.hip for csrc/icp.hip: bin the nr >= 1 reference points (one host wait for the exact box) into the three given slots; then,
 // any number of times, the position in the reference list of the nearest point ((d2, position) smallest: pb3d_knn_dev with k = 1) of
 // each of nq float64 queries -> d_idx (enqueued; only the query binning is redone)

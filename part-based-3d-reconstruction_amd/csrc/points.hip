@@ -506,26 +506,8 @@ int count_pass(pb3d_ctx* ctx, const u8* d_grid, const SelParams& p, bool fast16,
     else if (fast16) hipLaunchKernelGGL(k_points_count16<1>, dim3((unsigned)nb), dim3(256), 0, ctx->stream, d_grid, p, (u32*)counts, (unsigned short*)masks);
     else hipLaunchKernelGGL(k_points_count, dim3((unsigned)nb), dim3(256), 0, ctx->stream, d_grid, p, (u32*)counts);
     PB3D_CHECK_LAUNCH();
-    i64* total = (i64*)offsets + nb;
-    {
-        const i64 nseg = (nb + kSeg - 1) / kSeg;
-        void *local, *segs;
-        PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_SCAN_LOCAL, (size_t)nb * sizeof(u32), &local));
-        PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_SCAN_SEGS, 64 + (size_t)nseg * (sizeof(u32) + sizeof(i64)), &segs));
-        i64* seg_base = (i64*)((u8*)segs + 64);                    // [0,64): unused (it held the rotate kernels' flag word once)
-        u32* seg_total = (u32*)(seg_base + nseg);
-        hipLaunchKernelGGL(k_scan_local, dim3((unsigned)nseg), dim3(256), 0, ctx->stream, (const u32*)counts, nb, (u32*)local, seg_total);
-        PB3D_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_scan_totals, dim3(1), dim3(1024), 0, ctx->stream, (const u32*)seg_total, nseg, seg_base, total);
-        PB3D_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_scan_add, dim3(pb3d_stream_blocks(ctx, nb, 256, 8)), dim3(256), 0, ctx->stream, (const u32*)local,
-                           (const i64*)seg_base, nb, (i64*)offsets);
-        PB3D_CHECK_LAUNCH();
-    }
-    PB3D_HIP(hipMemcpyAsync(ctx->pinned, total, sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
-    PB3D_TRY(pb3d_stream_sync(ctx));
-    *n = *(i64*)ctx->pinned;
-    return PB3D_OK;
+    PB3D_TRY(pb3d_scan_counts(ctx, (const u32*)counts, nb, (i64*)offsets, PB3D_SLOT_SCAN_LOCAL, PB3D_SLOT_SCAN_SEGS));
+    return pb3d_read_back(ctx, n, (const i64*)offsets + nb, sizeof(i64));
 }
 
 // The fill pass after count_pass(off_slot, mask_slot) on the same grid and selection.  d_pts: n*3 floats, d_cols: n*C bytes.
@@ -547,12 +529,18 @@ int fill_pass(pb3d_ctx* ctx, const u8* d_grid, const SelParams& p, bool fast16, 
 }  // namespace
 
 // The exclusive scan of count_pass on any u32 count array (the cell index of csrc/nn.hip): offsets[0..n) and offsets[n] = total.
-// Slot local_slot holds n u32 in-segment offsets, slot seg_slot the segment totals and bases.  Enqueue only.
+// Slot local_slot holds n u32 in-segment offsets, slot seg_slot the segment bases (int64) and then the segment totals (u32).
+int pb3d_scan_reserve(pb3d_ctx* ctx, i64 n, pb3d_slot local_slot, pb3d_slot seg_slot) {
+    void* p;
+    PB3D_TRY(pb3d_scratch(ctx, local_slot, (size_t)n * sizeof(u32), &p));
+    return pb3d_scratch(ctx, seg_slot, (size_t)((n + kSeg - 1) / kSeg) * (sizeof(u32) + sizeof(i64)), &p);
+}
+
+// Enqueue only.
 int pb3d_scan_counts(pb3d_ctx* ctx, const u32* d_counts, i64 n, i64* d_offsets, pb3d_slot local_slot, pb3d_slot seg_slot) {
     const i64 nseg = (n + kSeg - 1) / kSeg;
-    void *local, *segs;
-    PB3D_TRY(pb3d_scratch(ctx, local_slot, (size_t)n * sizeof(u32), &local));
-    PB3D_TRY(pb3d_scratch(ctx, seg_slot, (size_t)nseg * (sizeof(u32) + sizeof(i64)), &segs));
+    PB3D_TRY(pb3d_scan_reserve(ctx, n, local_slot, seg_slot));
+    void *local = ctx->scratch[local_slot], *segs = ctx->scratch[seg_slot];
     i64* seg_base = (i64*)segs;
     u32* seg_total = (u32*)(seg_base + nseg);
     hipLaunchKernelGGL(k_scan_local, dim3((unsigned)nseg), dim3(256), 0, ctx->stream, d_counts, n, (u32*)local, seg_total);

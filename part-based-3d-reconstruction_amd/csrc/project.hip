@@ -442,9 +442,8 @@ int pb3d_partwise_iou_dev(pb3d_ctx* ctx, const uint8_t* d_a, const uint8_t* d_b,
     hipLaunchKernelGGL(k_partwise_iou, dim3(pb3d_stream_blocks(ctx, npix, 256, 4)), dim3(256), 0, ctx->stream, d_a, d_b, npix, P,
                        (unsigned long long*)counts);
     PB3D_CHECK_LAUNCH();
-    PB3D_HIP(hipMemcpyAsync(ctx->pinned, counts, 64 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    PB3D_TRY(pb3d_stream_sync(ctx));
-    const unsigned long long* h = (const unsigned long long*)ctx->pinned;
+    unsigned long long h[64];
+    PB3D_TRY(pb3d_read_back(ctx, h, counts, sizeof(h)));
     for (int k = 0; k < ncolors; ++k) { inter[k] = (int64_t)h[2 * k]; uni[k] = (int64_t)h[2 * k + 1]; }
     return PB3D_OK;
 }

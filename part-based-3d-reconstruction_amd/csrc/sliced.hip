@@ -646,7 +646,7 @@ static int s32_chain(pb3d_ctx* ctx, const u8* d_occ, i64 W, i64 H, i64 D, const 
             hipLaunchKernelGGL(k_s32_fill, dim3((tq + 255u) / 256u), dim3(256), 0, ctx->stream, (u32*)A, (const u32*)mb, D, Dp, pb3d_make_magic((u32)(Dp / 4)), tq);
         }
         PB3D_CHECK_LAUNCH();
-        int* hflag = (int*)((char*)ctx->pinned + ctx->pinned_bytes - 64);
+        int* hflag = (int*)((char*)ctx->pinned + pb3d_pinned_bytes - pb3d_pinned_flag);
         if (!known_binary) {
             PB3D_HIP(hipMemcpyAsync(hflag, flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
             PB3D_HIP(hipEventRecord(ctx->s32_ev, ctx->stream));

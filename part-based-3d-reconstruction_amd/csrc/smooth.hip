@@ -16,12 +16,15 @@
 // A step reads one float64 position buffer and writes the other:
 //   k_smooth_step     one lane per vertex walks its ascending list: s = 0.0, s = s + x_j; m = s / deg; d = m - x; x + f * d -- one
 //                     rounded operation each (-ffp-contract=off, __ddiv_rn).  Fixed vertices and vertices without a neighbour copy
-//   k_smooth_hubs     the vertices whose degree exceeds kLaneDegree (listed once, k_hub_list), one wavefront each: 64 neighbours a time
-//                     are gathered, then every lane adds the same 64 values in order by readlane -- the same additions in the same
-//                     order as the lane form, so the cutoff changes the time and never the bits
+//   k_smooth_hubs     the vertices whose degree exceeds kLaneDegree (listed once, k_hub_list), one wavefront each: the ordered
+//                     wavefront sum of csrc/ordered_sum.h -- the same additions in the same order as the lane form, so the cutoff
+//                     changes the time and never the bits
 // The last step stores in the caller's dtype: the one rounding to float32.
+#include <algorithm>
 #include <cmath>
 
+#include "mesh_index.h"
+#include "ordered_sum.h"
 #include "pb3d_internal.h"
 
 namespace {
@@ -29,20 +32,13 @@ namespace {
 constexpr i64 kMaxVerts = (1ll << 31) - 1, kMaxPairs = (1ll << 31) - 1;
 constexpr int kLaneDegree = 32;                     // above it a vertex is summed by a wavefront
 
-template <bool I64>
-__device__ __forceinline__ i64 load_index(const void* p, i64 e) {
-    return I64 ? ((const i64*)p)[e] : (i64)((const int*)p)[e];
-}
-// a checked index in [-nv, nv) as NumPy reads it
-__device__ __forceinline__ u32 wrap(i64 v, i64 nv) { return (u32)(v < 0 ? v + nv : v); }
-
 // ---- adjacency ------------------------------------------------------------------------------------------------------------------------
 template <bool I64>
 __global__ __launch_bounds__(256) void k_emit_pairs(const void* __restrict__ faces, i64 nf, i64 nv, u32* __restrict__ key, u32* __restrict__ val) {
     const i64 f = (i64)blockIdx.x * 256 + threadIdx.x;
     if (f >= nf) return;
-    const u32 c[3] = {wrap(load_index<I64>(faces, 3 * f), nv), wrap(load_index<I64>(faces, 3 * f + 1), nv),
-                      wrap(load_index<I64>(faces, 3 * f + 2), nv)};
+    const u32 c[3] = {(u32)wrap(load_index<I64>(faces, 3 * f), nv), (u32)wrap(load_index<I64>(faces, 3 * f + 1), nv),
+                      (u32)wrap(load_index<I64>(faces, 3 * f + 2), nv)};
     const u32 none = (u32)nv;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -155,19 +151,6 @@ __global__ __launch_bounds__(256) void k_smooth_step(const double* __restrict__ 
     for (int a = 0; a < 3; ++a) store_coord<F32OUT>(out, 3 * i + a, x[a]);
 }
 
-__device__ __forceinline__ double from_lane(double x, int j) {      // lane j's x in every lane (j is the same in all of them)
-    const int lo = __builtin_amdgcn_readlane(__double2loint(x), j), hi = __builtin_amdgcn_readlane(__double2hiint(x), j);
-    return __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ void gather(const double* pos, const int* neighbours, i64 p, i64 e, double v[3]) {
-    v[0] = v[1] = v[2] = 0.0;
-    if (p < e) {
-        const double* q = pos + 3 * (i64)neighbours[p];
-        v[0] = q[0]; v[1] = q[1]; v[2] = q[2];
-    }
-}
-
 // the same STEP for the listed vertices, one wavefront each: however long the list, it is walked 64 a time
 template <bool F32OUT>
 __global__ __launch_bounds__(256) void k_smooth_hubs(const double* __restrict__ pos, const u32* __restrict__ hubs, const i64* __restrict__ starts,
@@ -179,18 +162,11 @@ __global__ __launch_bounds__(256) void k_smooth_hubs(const double* __restrict__ 
         const i64 v = __builtin_amdgcn_readfirstlane((int)hubs[1 + h]);
         if (fixed && fixed[v]) continue;            // k_smooth_step has copied it
         const i64 s = starts[v], e = starts[v + 1];
-        double sum[3] = {0.0, 0.0, 0.0}, cur[3], nxt[3];
-        gather(pos, neighbours, s + lane, e, cur);
-        for (i64 p = s; p < e; p += 64) {
-            gather(pos, neighbours, p + 64 + lane, e, nxt);
-            const int c = (int)(e - p < 64 ? e - p : 64);
-            for (int j = 0; j < c; ++j) {
-                sum[0] = sum[0] + from_lane(cur[0], j);
-                sum[1] = sum[1] + from_lane(cur[1], j);
-                sum[2] = sum[2] + from_lane(cur[2], j);
-            }
-            for (int a = 0; a < 3; ++a) cur[a] = nxt[a];
-        }
+        double sum[3];
+        ordered_sum(s, e, [&](i64 p, double* row) {
+            const double* q = pos + 3 * (i64)neighbours[p];
+            row[0] = q[0]; row[1] = q[1]; row[2] = q[2];
+        }, sum);
         if (lane < 3) {
             const double x = pos[3 * v + lane];
             const double m = __ddiv_rn(lane == 0 ? sum[0] : lane == 1 ? sum[1] : sum[2], (double)(e - s));
@@ -210,19 +186,16 @@ struct AdjOut { i64* starts; int* neighbours; u32* mult; u8* boundary; };
 int build_adjacency(pb3d_ctx* ctx, const void* d_faces, int faces_i64, i64 nv, i64 nf, const AdjOut& o, const i64** d_total) {
     const i64 P = 6 * nf;
     const u32 none = (u32)nv;
-    void *kv, *fl, *rk, *tmp;
+    void *kv, *fl, *rk;
     PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_SMOOTH_PAIRS, (size_t)P * 4 * sizeof(u32), &kv));
     PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_SMOOTH_FLAGS, (size_t)(P + 1) * sizeof(u32), &fl));
     PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_SMOOTH_RANKS, (size_t)(P + 1) * sizeof(i64), &rk));
     // the scans of the call are the sorts' run tables and the flags': size both scan slots for the largest now, so that none regrows
     // (and waits) midway
-    const i64 nruns = 256 * ((P + pb3d_sort_tile - 1) / pb3d_sort_tile), most = nruns > P ? nruns : P;
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_SMOOTH_SCAN_LOCAL, (size_t)most * sizeof(u32), &tmp));
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_SMOOTH_SCAN_SEGS, (size_t)(most / 1024 + 1) * (sizeof(u32) + sizeof(i64)), &tmp));
+    PB3D_TRY(pb3d_scan_reserve(ctx, std::max<i64>(P, pb3d_sort_scan_items(P)), PB3D_SLOT_SMOOTH_SCAN_LOCAL, PB3D_SLOT_SMOOTH_SCAN_SEGS));
     u32* a = (u32*)kv;
     u32 *key = a, *val = a + P, *key2 = a + 2 * P, *val2 = a + 3 * P;
-    if (faces_i64) hipLaunchKernelGGL(k_emit_pairs<true>, grid_for(nf), dim3(256), 0, ctx->stream, d_faces, nf, nv, key, val);
-    else hipLaunchKernelGGL(k_emit_pairs<false>, grid_for(nf), dim3(256), 0, ctx->stream, d_faces, nf, nv, key, val);
+    hipLaunchKernelGGL((faces_i64 ? k_emit_pairs<true> : k_emit_pairs<false>), grid_for(nf), dim3(256), 0, ctx->stream, d_faces, nf, nv, key, val);
     PB3D_CHECK_LAUNCH();
     const u32 *by_j, *ends_i;       // sorted by the second end: that column and the first ends beside it
     PB3D_TRY(pb3d_sort_pairs(ctx, key, val, key2, val2, P, nv + 1, PB3D_SLOT_SMOOTH_SORT_HIST, PB3D_SLOT_SMOOTH_SCAN_LOCAL,
@@ -290,10 +263,7 @@ int pb3d_mesh_adjacency_resident(pb3d_ctx* ctx, const void* d_faces, int faces_i
     }
     const i64* d_total;
     PB3D_TRY(build_adjacency(ctx, d_faces, faces_i64, nv, nf, AdjOut{d_starts, d_neighbours, d_mult, d_boundary}, &d_total));
-    PB3D_HIP(hipMemcpyAsync(ctx->pinned, d_total, sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
-    PB3D_TRY(pb3d_stream_sync(ctx));
-    *total = *(const i64*)ctx->pinned;
-    return PB3D_OK;
+    return pb3d_read_back(ctx, total, d_total, sizeof(i64));
 }
 
 int pb3d_mesh_smooth_resident(pb3d_ctx* ctx, const void* d_verts, int verts_f64, int64_t nv, const void* d_faces, int faces_i64, int64_t nf,
@@ -336,8 +306,7 @@ int pb3d_mesh_smooth_resident(pb3d_ctx* ctx, const void* d_verts, int verts_f64,
         PB3D_CHECK_LAUNCH();
     }
     const unsigned wb = pb3d_stream_blocks(ctx, 3 * nv, 256, 8);
-    if (verts_f64) hipLaunchKernelGGL(k_widen<true>, dim3(wb), dim3(256), 0, ctx->stream, d_verts, 3 * (i64)nv, (double*)pa);
-    else hipLaunchKernelGGL(k_widen<false>, dim3(wb), dim3(256), 0, ctx->stream, d_verts, 3 * (i64)nv, (double*)pa);
+    hipLaunchKernelGGL((verts_f64 ? k_widen<true> : k_widen<false>), dim3(wb), dim3(256), 0, ctx->stream, d_verts, 3 * (i64)nv, (double*)pa);
     PB3D_CHECK_LAUNCH();
 
     const bool taubin = !std::isnan(mu);

@@ -64,7 +64,7 @@ __global__ __launch_bounds__(256) void k_sort_scatter(const u32* __restrict__ ke
 
 int pb3d_sort_pairs(pb3d_ctx* ctx, u32* key, u32* val, u32* key2, u32* val2, i64 n, i64 m, pb3d_slot hist_slot, pb3d_slot scan_local_slot,
                     pb3d_slot scan_segs_slot, const u32** key_sorted, const u32** val_sorted) {
-    const i64 ntiles = (n + kTile - 1) / kTile, nruns = 256 * ntiles;
+    const i64 ntiles = (n + kTile - 1) / kTile, nruns = pb3d_sort_scan_items(n);
     int bits = 1;
     while (bits < 32 && ((u64)(m - 1) >> bits) != 0) ++bits;
     void* hist;

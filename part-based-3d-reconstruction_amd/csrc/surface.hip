@@ -17,17 +17,13 @@
 #include <cmath>
 
 #include "jacobi3.h"
+#include "mesh_index.h"
 #include "pb3d_internal.h"
 
 namespace {
 
 constexpr i64 kMaxElems = (1ll << 31) - 1;      // vertices, faces: positions are 32-bit
 constexpr int kFrames = 3;                      // covariance solves per vertex: the input frame, then twice its own eigenvector frame
-
-template <bool I64>
-__device__ __forceinline__ i64 load_index(const void* p, i64 e) {
-    return I64 ? ((const i64*)p)[e] : (i64)((const int*)p)[e];
-}
 
 // ---- index check: flag = 1 if any of the n entries is outside [lo, hi) ---------------------------------------------------------------
 template <bool I64>
@@ -46,13 +42,10 @@ int check_indices(pb3d_ctx* ctx, const void* d_idx, int i64_entries, i64 n, i64 
     PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_SURF_FLAG, sizeof(u32), &f));
     PB3D_HIP(hipMemsetAsync(f, 0, sizeof(u32), ctx->stream));
     const unsigned nb = pb3d_stream_blocks(ctx, n, 256, 8);
-    if (i64_entries) hipLaunchKernelGGL(k_check_indices<true>, dim3(nb), dim3(256), 0, ctx->stream, d_idx, n, lo, hi, (u32*)f);
-    else hipLaunchKernelGGL(k_check_indices<false>, dim3(nb), dim3(256), 0, ctx->stream, d_idx, n, lo, hi, (u32*)f);
+    hipLaunchKernelGGL((i64_entries ? k_check_indices<true> : k_check_indices<false>), dim3(nb), dim3(256), 0, ctx->stream, d_idx, n, lo, hi, (u32*)f);
     PB3D_CHECK_LAUNCH();
-    PB3D_HIP(hipMemcpyAsync(ctx->pinned, f, sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-    PB3D_TRY(pb3d_stream_sync(ctx));
     u32 bad;
-    memcpy(&bad, ctx->pinned, sizeof(bad));
+    PB3D_TRY(pb3d_read_back(ctx, &bad, f, sizeof(bad)));
     if (bad) {
         pb3d_set_error("%s: index out of bounds for %lld entries", what, (long long)hi);
         return PB3D_EINDEX;
@@ -73,9 +66,6 @@ __device__ __forceinline__ void normalize3(T x, T y, T z, T* out) {
     const T d = np_sqrt((x * x + y * y) + z * z) + (T)1e-8;
     out[0] = np_div(x, d); out[1] = np_div(y, d); out[2] = np_div(z, d);
 }
-
-// a checked index in [-nv, nv) as NumPy reads it
-__device__ __forceinline__ i64 wrap(i64 v, i64 nv) { return v < 0 ? v + nv : v; }
 
 template <class T, bool I64>
 __global__ __launch_bounds__(256) void k_triangle_normals(const T* __restrict__ verts, i64 nv, const void* __restrict__ faces, i64 nf,
@@ -285,18 +275,13 @@ __global__ __launch_bounds__(256) void k_surface_metrics(const void* __restrict_
     roughness[i] = fmax(lam, 0.0) / (kk - 1.0);
 }
 
-template <class T, bool I64>
-void launch_triangle_normals(pb3d_ctx* ctx, const void* d_verts, i64 nv, const void* d_faces, i64 nf, void* d_out) {
-    hipLaunchKernelGGL((k_triangle_normals<T, I64>), dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, ctx->stream, (const T*)d_verts, nv,
-                       d_faces, nf, (T*)d_out);
-}
-
 int triangle_normals(pb3d_ctx* ctx, const void* d_verts, int verts_f64, i64 nv, const void* d_faces, int faces_i64, i64 nf, void* d_out) {
     if (nf == 0) return PB3D_OK;
-    if (verts_f64 && faces_i64) launch_triangle_normals<double, true>(ctx, d_verts, nv, d_faces, nf, d_out);
-    else if (verts_f64) launch_triangle_normals<double, false>(ctx, d_verts, nv, d_faces, nf, d_out);
-    else if (faces_i64) launch_triangle_normals<float, true>(ctx, d_verts, nv, d_faces, nf, d_out);
-    else launch_triangle_normals<float, false>(ctx, d_verts, nv, d_faces, nf, d_out);
+    with_mesh_types(verts_f64, faces_i64, [&](auto V, auto I) {
+        using T = std::conditional_t<decltype(V)::value, double, float>;
+        hipLaunchKernelGGL((k_triangle_normals<T, decltype(I)::value>), dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, ctx->stream,
+                           (const T*)d_verts, nv, d_faces, nf, (T*)d_out);
+    });
     PB3D_CHECK_LAUNCH();
     return PB3D_OK;
 }
@@ -340,17 +325,14 @@ int pb3d_vertex_normals_dev(pb3d_ctx* ctx, const void* d_verts, int verts_f64, i
     const unsigned nb = pb3d_stream_blocks(ctx, nc, 256, 8);
     PB3D_HIP(hipMemsetAsync(cnt, 0, (size_t)nv * sizeof(u32), ctx->stream));
     if (nc > 0) {
-        if (faces_i64) hipLaunchKernelGGL(k_incident_count<true>, dim3(nb), dim3(256), 0, ctx->stream, d_faces, (i64)nv, nc, (u32*)cnt);
-        else hipLaunchKernelGGL(k_incident_count<false>, dim3(nb), dim3(256), 0, ctx->stream, d_faces, (i64)nv, nc, (u32*)cnt);
+        hipLaunchKernelGGL((faces_i64 ? k_incident_count<true> : k_incident_count<false>), dim3(nb), dim3(256), 0, ctx->stream, d_faces, (i64)nv, nc, (u32*)cnt);
         PB3D_CHECK_LAUNCH();
     }
     PB3D_TRY(pb3d_scan_counts(ctx, (const u32*)cnt, nv, (i64*)st, PB3D_SLOT_SURF_SCAN_LOCAL, PB3D_SLOT_SURF_SCAN_SEGS));
     PB3D_HIP(hipMemsetAsync(cnt, 0, (size_t)nv * sizeof(u32), ctx->stream));      // the fill's cursors
     if (nc > 0) {
-        if (faces_i64) hipLaunchKernelGGL(k_incident_fill<true>, dim3(nb), dim3(256), 0, ctx->stream, d_faces, (i64)nv, nc, (const i64*)st,
-                                          (u32*)cnt, (u32*)inc);
-        else hipLaunchKernelGGL(k_incident_fill<false>, dim3(nb), dim3(256), 0, ctx->stream, d_faces, (i64)nv, nc, (const i64*)st, (u32*)cnt,
-                                (u32*)inc);
+        hipLaunchKernelGGL((faces_i64 ? k_incident_fill<true> : k_incident_fill<false>), dim3(nb), dim3(256), 0, ctx->stream, d_faces, (i64)nv, nc,
+                           (const i64*)st, (u32*)cnt, (u32*)inc);
         PB3D_CHECK_LAUNCH();
     }
     const dim3 grid((unsigned)((nv + 255) / 256));

@@ -4,12 +4,7 @@
 
 namespace {
 
-__host__ __device__ inline u64 splitmix64(u64 z) {
-    z += 0x9e3779b97f4a7c15ull;
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
-}
+__host__ __device__ inline u64 splitmix64(u64 z) { return pb3d_mix64(z + 0x9e3779b97f4a7c15ull); }
 
 struct Palette16 {
     u8 rgb[48];

@@ -276,6 +276,13 @@ def reset():
             _ctx = None
 
 
+def _ptr(b):
+    """the device address of a DeviceBuffer, or of a place inside one (DeviceBuffer.at gives a c_void_p); None stays None"""
+    if b is None or isinstance(b, C.c_void_p):
+        return b
+    return C.c_void_p(b.ptr)
+
+
 def p_u8(a):
     return a.ctypes.data_as(u8p)
 

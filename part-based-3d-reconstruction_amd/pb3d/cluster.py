@@ -19,17 +19,12 @@ import math
 import numpy as np
 
 from . import _lib
+from ._lib import _ptr
 
 __all__ = ["radius_neighbor_counts", "radius_neighbor_counts_resident", "cluster_points", "cluster_points_resident", "select_points",
            "select_points_resident", "keep_largest_clusters", "keep_largest_clusters_resident"]
 
 MAX_POINTS = 2 ** 31 - 1
-
-
-def _ptr(b):
-    if b is None or isinstance(b, C.c_void_p):
-        return b
-    return C.c_void_p(b.ptr)
 
 
 def _count(n):

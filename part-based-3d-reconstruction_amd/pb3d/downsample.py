@@ -17,7 +17,8 @@ import math
 import numpy as np
 
 from . import _lib
-from .cluster import _cloud, _count, _ptr
+from ._lib import _ptr
+from .cluster import _cloud, _count
 
 __all__ = ["voxel_downsample", "voxel_downsample_resident"]
 

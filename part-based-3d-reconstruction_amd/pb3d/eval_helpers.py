@@ -36,6 +36,7 @@ import operator
 import numpy as np
 
 from . import _lib
+from ._lib import _ptr
 
 __all__ = ["filter_mesh", "chamfer_distance", "fscore_with_threshold", "pca_shape_similarity", "voxel_iou", "compute_nn_stats",
            "compute_nn_distances", "f1_curve_from_distances", "compute_f1_curve", "nn_distances", "nn_distances_resident",
@@ -70,10 +71,6 @@ def _cloud(P, what="points"):
     if a.dtype.kind not in "fiu" or a.dtype.itemsize > 8:
         raise TypeError(f"{what}: unsupported dtype {a.dtype}")
     return np.ascontiguousarray(a, dtype=np.float64), 1
-
-
-def _ptr(b):
-    return None if b is None else C.c_void_p(b.ptr)
 
 
 def nn_distances_resident(d_A, nA, d_B, nB, k=1, a_f64=True, b_f64=True, out=None):

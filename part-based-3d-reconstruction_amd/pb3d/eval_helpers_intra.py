@@ -16,6 +16,7 @@ import warnings
 import numpy as np
 
 from . import _lib
+from ._lib import _ptr
 from .projection_utils import _promotes_to_f64, camera_args
 
 __all__ = ["compute_global_depth_buffer", "project_part_visible", "load_voxel_grid", "load_mask", "resize_mask_to_voxel_grid",
@@ -161,10 +162,6 @@ def _colour_table(colors, C):
     if t.size and (t.min() < 0 or t.max() > 255):
         raise ValueError("colours are uint8 values")
     return np.ascontiguousarray(t.astype(np.uint8))
-
-
-def _ptr(b):
-    return None if b is None else C.c_void_p(b.ptr)
 
 
 def depth_buffer_resident(d_grid, shape, cam, H, W, out=None):

@@ -25,12 +25,13 @@ float64 sums in the ICP step's fixed order; the host draws the triplets, picks t
 refit (plane_from_moments).  Segmenting the SfM cloud, step 1, is pb3d/cluster.py (cluster_points, keep_largest_clusters: exact DBSCAN
 on the device).  Thinning a cloud to an even density before registration is pb3d/downsample.py (voxel_downsample: a voxel-grid filter
 on the device).  What is still not mirrored: loading the SfM cloud, and the CAD model."""
-import ctypes as C
 import math
 
 import numpy as np
 
 from . import _lib
+from ._lib import _ptr
+from .eval_helpers import _cloud
 
 __all__ = ["normalize_preserve_aspect", "flip_y_axis", "transform_points", "transform_points_resident", "best_fit_transform_from_sums",
            "best_fit_similarity_from_sums", "icp_align", "icp_align_resident", "icp_index_resident", "icp_step_resident",
@@ -58,21 +59,9 @@ def flip_y_axis(coords):
 
 
 # ---- rigid ICP ---------------------------------------------------------------------------------------------------------------------------
-def _cloud(P, what):
-    from .eval_helpers import _cloud as cloud
-    return cloud(P, what)
-
-
 def _finite(a, what):
     if not np.isfinite(a).all():
         raise ValueError(f"Input {what} contains NaN or infinity.")
-
-
-def _ptr(b):
-    """the device address of a DeviceBuffer, or of a place inside one (DeviceBuffer.at)"""
-    if b is None or isinstance(b, C.c_void_p):
-        return b
-    return C.c_void_p(b.ptr)
 
 
 def _transform(T, what="T"):

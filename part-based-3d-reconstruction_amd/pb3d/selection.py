@@ -1,19 +1,12 @@
 """Exact order statistics of a float64 list on the device (csrc/select.hip; include/pb3d.h has the contract): the element at a given
 0-based rank in IEEE totalOrder, found by a radix selection over the ordered keys with integer counters only -- no sort, no host
 round trip, and the same bytes on every call.  The trimmed ICP step (pb3d.preprocess_helpers) is its first user."""
-import ctypes as C
-
 import numpy as np
 
 from . import _lib
+from ._lib import _ptr
 
 __all__ = ["kth_smallest", "kth_smallest_resident"]
-
-
-def _ptr(b):
-    if b is None or isinstance(b, C.c_void_p):
-        return b
-    return C.c_void_p(b.ptr)
 
 
 def kth_smallest_resident(d_vals, n, rank, out=None):

@@ -24,7 +24,7 @@ import math
 import numpy as np
 
 from . import _lib
-from .cluster import _ptr
+from ._lib import _ptr
 
 __all__ = ["mesh_vertex_adjacency", "mesh_vertex_adjacency_resident", "smooth_mesh", "smooth_mesh_resident"]
 

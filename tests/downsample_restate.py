@@ -129,6 +129,19 @@ def all_distinct(layout, n=2 ** 17 + 3):
     return p
 
 
+RUN_LENGTHS = (1, 2, 63, 64, 65, 127, 128, 129, 193)       # voxel populations on both sides of the centroid kernel's 64-row rounds
+
+
+def run_boundaries(seed=7):
+    """772 points: voxel k (cell k on x, voxel_size 1e5, origin 0) holds RUN_LENGTHS[k] of them, interleaved by a seeded permutation.
+    Inside a voxel the offsets span seven decades, so the order of the additions shows in the centroid's bits."""
+    rng = np.random.default_rng(seed)
+    voxel = np.repeat(np.arange(len(RUN_LENGTHS)), RUN_LENGTHS)
+    p = rng.random((len(voxel), 3)) * 10.0 ** rng.integers(-3, 4, (len(voxel), 3))
+    p[:, 0] += voxel * 1e5
+    return p[rng.permutation(len(voxel))]
+
+
 def constructed_cases():
     cases = {"faces/lattice": (face_lattice(), 0.5, (0.0, 0.0, 0.0))}
     for a in range(3):
@@ -140,4 +153,5 @@ def constructed_cases():
     cases["onevoxel/70001"] = (rng.random((70001, 3)) * 3.0 + 10.0, 8.0, (8.0, 8.0, 8.0))
     for layout in ("cx", "cz", "random"):
         cases[f"distinct/{layout}"] = (all_distinct(layout), 1.0, (0.0, 0.0, 0.0))
+    cases["runs/boundaries"] = (run_boundaries(), 1e5, (0.0, 0.0, 0.0))
     return cases

@@ -94,6 +94,26 @@ def test_restatement_on_the_constructed_clouds():
             assert len(want(f"distinct/{layout}", dt)[1]) == 2 ** 17 + 3
 
 
+def test_run_boundaries_case_tells_orders_apart():
+    """the populations are dr.RUN_LENGTHS (as a multiset: voxels are numbered by first appearance), and in float64 the centroid of some
+    voxel of 65 or more points changes bits when its points are added in reversed order -- else the case could not catch a wrong order"""
+    pts, vs, origin = CASES["runs/boundaries"]
+    out, index, inverse, counts = want("runs/boundaries", np.float64)
+    assert len(pts) == 772 and sorted(counts.tolist()) == sorted(dr.RUN_LENGTHS)
+    differing = 0
+    for v in np.flatnonzero(counts >= 65):
+        rows = pts[inverse == v].tolist()
+        fwd, rev = [0.0, 0.0, 0.0], [0.0, 0.0, 0.0]
+        for r, q in zip(rows, rows[::-1]):
+            for a in range(3):
+                fwd[a] = fwd[a] + r[a]
+                rev[a] = rev[a] + q[a]
+        k = float(counts[v])
+        assert np.array([s / k for s in fwd]).tobytes() == out[v].tobytes()
+        differing += [s / k for s in fwd] != [s / k for s in rev]
+    assert differing >= 1
+
+
 def test_pinned_counts_on_the_sfm_sample():
     for vs, m, largest in ((0.5, 127, 743), (0.05, 5217, 22)):
         counts = want(f"sfm/forward/{vs}", np.float64)[3]
@@ -255,6 +275,12 @@ def test_one_voxel(pb3d_gpu):
     same((out, index, inverse, counts), dr.restate(sfm(), 100.0), "sfm/100")
     assert counts.tolist() == [20000] and index.tolist() == [0] and not inverse.any()
     check(pb3d_gpu, "onevoxel/70001", *CASES["onevoxel/70001"])
+
+
+@gpu
+def test_run_boundaries(pb3d_gpu):
+    """voxels of 1, 2, 63, 64, 65, 127, 128, 129 and 193 points: every tail length of the ordered wavefront sum (csrc/ordered_sum.h)"""
+    check(pb3d_gpu, "runs/boundaries", *CASES["runs/boundaries"])
 
 
 @gpu
