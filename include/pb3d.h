@@ -63,7 +63,9 @@ int pb3d_sync(pb3d_ctx* ctx);
 /* Development knobs (results never depend on them; they select between kernels that are all bit-exact, and the parity tests use them to
  * run both forms of a kernel on the same grids).  Every knob has a name -- "sliced", "rot90_wide", "rot90_flat", "rot90_fill",
  * "rot90_mask_block", "global_composed", "per_job", "orient_tile", "ccl_*", "s32_*", "no_table_cache",
- * "uncap", "crop_ablate" (csrc/ctx.hip lists them with their ranges); an unknown name or a value out of range is PB3D_EINVAL.  Initial
+ * "uncap", "crop_ablate" (csrc/ctx.hip lists them with their ranges); an unknown name or a value out of range is PB3D_EINVAL.
+ * "per_job" = 1: pb3d_part_carve_dev and pb3d_part_carve_label_dev run every job through the job-by-job passes (no fused sweep of the
+ * 90-degree jobs, no merged pass of the others), pb3d_global_carve_label_dev its composed pipeline at 90 degrees too.  Initial
  * values come from the environment, read ONCE in pb3d_create: PB3D_KNOBS="name=value,name=value" (any knob), and PB3D_SLICED,
  * PB3D_ROT90_WIDE, PB3D_S32_GPW, PB3D_UNCAP. */
 int pb3d_set_tuning(pb3d_ctx* ctx, const char* name, int value);

@@ -88,20 +88,6 @@ __global__ __launch_bounds__(256) void k_carve_bytes(const u8* __restrict__ in, 
 // two, in which case its bytes are masked on both sides of the boundary.  Column of a piece: one exact multiply-high
 // division of its tile-relative byte offset.  Dropped pieces are never read.
 // ------------------------------------------------------------------------------------------------
-struct Magic32 { u32 m; int sa, sb; };
-inline Magic32 make_magic32(u32 d) {     // exact u32 division, 1 <= d < 2^31 (Granlund-Montgomery round-up form)
-    int L = 0;
-    while ((1ull << L) < d) ++L;
-    Magic32 g;
-    g.m = (u32)(((1ull << 32) * ((1ull << L) - d)) / d + 1);
-    g.sa = L < 1 ? L : 1;
-    g.sb = L > 1 ? L - 1 : 0;
-    return g;
-}
-__device__ __forceinline__ u32 magic_div32(u32 n, Magic32 g) {
-    const u32 t = __umulhi(g.m, n);
-    return (t + ((n - t) >> g.sa)) >> g.sb;
-}
 // dword j of a 16-byte mask whose bytes below position b (0..16) are 0xff
 __device__ __forceinline__ u32 below_mask(int b, int j) {
     const int n = b - 4 * j;
@@ -109,14 +95,15 @@ __device__ __forceinline__ u32 below_mask(int b, int j) {
 }
 
 __global__ __launch_bounds__(kTileThreads) void k_carve_flat(const u8* __restrict__ in, u8* __restrict__ out, const u8* __restrict__ mask,
-                                                             i64 nbytes, i64 ncols, u32 col, Magic32 mg) {
+                                                             i64 nbytes, i64 ncols, pb3d_magic mg) {
     __shared__ u8 smask[kTileVec + 4];
+    const u32 col = mg.d;
     const i64 b_begin = (i64)blockIdx.x * (kTileVec * 16);
     const i64 first_col = b_begin / col;                        // block-uniform
     const u32 rem0 = (u32)(b_begin - first_col * col);
     const i64 left = nbytes - b_begin;
     const u32 n_here = left < kTileVec * 16 ? (u32)left : (u32)(kTileVec * 16);       // bytes of this tile
-    const u32 ncol_here = magic_div32(rem0 + n_here - 1, mg) + 1;
+    const u32 ncol_here = pb3d_div(rem0 + n_here - 1, mg) + 1;
     for (u32 c = threadIdx.x; c < ncol_here; c += kTileThreads) smask[c] = first_col + c < ncols ? mask[first_col + c] : (u8)0;
     __syncthreads();
 #pragma unroll
@@ -126,7 +113,7 @@ __global__ __launch_bounds__(kTileThreads) void k_carve_flat(const u8* __restric
         bool k0 = false, k1 = false, keep = false;
         int bnd = 16;                                            // bytes of the piece that belong to its first column
         if (live) {
-            const u32 q = rem0 + bo, c0 = magic_div32(q, mg);
+            const u32 q = rem0 + bo, c0 = pb3d_div(q, mg);
             const u32 to_end = col - (q - c0 * col);             // >= 1
             k0 = smask[c0] != 0;
             if (to_end < 16 && bo + to_end < n_here) { bnd = (int)to_end; k1 = smask[c0 + 1] != 0; }
@@ -188,7 +175,8 @@ __global__ __launch_bounds__(256) void k_occupancy_tail(const u8* __restrict__ r
 }
 
 // ------------------------------------------------------------------------------------------------
-// apply_colored_mask_to_voxel_grid: out[x,y,z,:] = rgb[y,x,:] if carved[x,y,z] == 1 else 0.
+// apply_colored_mask_to_voxel_grid: out[x,y,z,:] = img[y,x,:] if carved[x,y,z] == 1 else 0, for an (H,W,C) image: RGB (C == 3) or
+// 1-byte labels (C == 1).
 // Fast path (D % 16 == 0): 16 voxels of one column per thread -> 16 bytes in, 48 bytes out.
 // ------------------------------------------------------------------------------------------------
 // FLAT = false: D % 16 == 0, a group of 16 voxels lies in one column.  FLAT = true: any D >= 16 -- groups are cut from the
@@ -232,33 +220,67 @@ __global__ __launch_bounds__(256) void k_color_apply16(const u8* __restrict__ ca
     }
 }
 
+// The same for a 1-byte label image, FLAT or not (fewer than 2^32 voxels, D >= 16, 16-byte aligned output).  A kernel of its own, not
+// k_color_apply16 with one byte per voxel: that one waits for the group's carved bytes before it asks for the pixel, which costs the
+// 32-bytes-per-lane label stream up to 9 % of global_carve_label(45) at odd D (profiles/onejobloop_ab_templated_apply.jsonl); here
+// the one or two label bytes are on their way first, and two labels are blended per byte instead of in a divergent branch.
+__global__ __launch_bounds__(256) void k_label_apply16(const u8* __restrict__ carved, const u8* __restrict__ label_hw, i64 W, i64 H, i64 ngroups,
+                                                       pb3d_magic mD, pb3d_magic mH, u8* __restrict__ out) {
+    for (i64 g = (i64)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += (i64)gridDim.x * blockDim.x) {
+        const u32 v0 = (u32)(16 * g);
+        const u32 col = pb3d_div(v0, mD), x = pb3d_div(col, mH), y = col - x * mH.d;
+        const u32 bnd = (col + 1) * mD.d - v0;                      // voxels of the group in column `col` (>= 1)
+        const u32 L0 = label_hw[(i64)y * W + x];
+        u32 L1 = L0;
+        if (bnd < 16u) { const u32 x1 = y + 1 < mH.d ? x : x + 1, y1 = y + 1 < mH.d ? y + 1 : 0u; L1 = label_hw[(i64)y1 * W + x1]; }
+        const u32x4 cv = *(const u32x4*)(carved + 16 * g);
+        const u32 cw[4] = {cv.x, cv.y, cv.z, cv.w};
+        u32 o[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            u32 lab = 0;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) lab |= ((u32)(4 * j + b) < bnd ? L0 : L1) << (8 * b);
+            o[j] = (one_bytes(cw[j]) * 0xffu) & lab;
+        }
+        u32x4 r; r.x = o[0]; r.y = o[1]; r.z = o[2]; r.w = o[3];
+        *(u32x4*)(out + 16 * g) = r;
+    }
+}
+
+template <int C>
 __global__ __launch_bounds__(256) void k_color_apply_generic(const u8* __restrict__ carved, const u8* __restrict__ rgb_hw3,
                                                              u8* __restrict__ out, i64 W, i64 H, i64 D, i64 v_first) {
     const i64 nvox = W * H * D;
     for (i64 v = v_first + (i64)blockIdx.x * blockDim.x + threadIdx.x; v < nvox; v += (i64)gridDim.x * blockDim.x) {
         const i64 xy = v / D;
         const i64 x = xy / H, y = xy - x * H;
-        const u8* px = rgb_hw3 + (y * W + x) * 3;
+        const u8* px = rgb_hw3 + (y * W + x) * C;
         const bool on = carved[v] == 1;
-        out[3 * v] = on ? px[0] : (u8)0;
-        out[3 * v + 1] = on ? px[1] : (u8)0;
-        out[3 * v + 2] = on ? px[2] : (u8)0;
+#pragma unroll
+        for (int c = 0; c < C; ++c) out[C * v + c] = on ? px[c] : (u8)0;
     }
 }
 
 // ------------------------------------------------------------------------------------------------
-// part_carve helpers.
+// part_carve helpers, for voxels of C bytes: RGB (C == 3) or a 1-byte label (C == 1, reference :139-160 with the colour grid in label form).
 //   k_part_occ   : occ[v] = mask_sub[xy] && any(colored[v] > 0)            (reference :152-154)
 //   k_keep_or    : keep[v] |= carved[v] && mask_sub[xy]                    (part = sub * carved, :156)
 //   k_part_final : out[v] = keep[v] ? colored[v] : 0                       (:158; every job writes
 //                  colored[v] itself, so the overlay is the union of the jobs' keep sets)
 // ------------------------------------------------------------------------------------------------
+template <int C>
 __global__ __launch_bounds__(256) void k_part_occ(const u8* __restrict__ colored, const u8* __restrict__ mask_sub,
                                                   u8* __restrict__ occ, i64 nvox, i64 D, i64 v_first = 0) {
     for (i64 v = v_first + (i64)blockIdx.x * blockDim.x + threadIdx.x; v < nvox; v += (i64)gridDim.x * blockDim.x) {
         const i64 xy = v / D;
         u8 r = 0;
-        if (mask_sub[xy]) r = (colored[3 * v] | colored[3 * v + 1] | colored[3 * v + 2]) ? 1 : 0;
+        if (mask_sub[xy]) {
+            u8 any = 0;
+#pragma unroll
+            for (int c = 0; c < C; ++c) any |= colored[C * v + c];
+            r = any ? 1 : 0;
+        }
         occ[v] = r;
     }
 }
@@ -273,13 +295,13 @@ __global__ __launch_bounds__(256) void k_keep_or(const u8* __restrict__ carved, 
     }
 }
 
+template <int C>
 __global__ __launch_bounds__(256) void k_part_final(const u8* __restrict__ colored, const u8* __restrict__ keep,
                                                     u8* __restrict__ out, i64 nvox, i64 v_first = 0) {
     for (i64 v = v_first + (i64)blockIdx.x * blockDim.x + threadIdx.x; v < nvox; v += (i64)gridDim.x * blockDim.x) {
         const bool k = keep[v] != 0;
-        out[3 * v] = k ? colored[3 * v] : (u8)0;
-        out[3 * v + 1] = k ? colored[3 * v + 1] : (u8)0;
-        out[3 * v + 2] = k ? colored[3 * v + 2] : (u8)0;
+#pragma unroll
+        for (int c = 0; c < C; ++c) out[C * v + c] = k ? colored[C * v + c] : (u8)0;
     }
 }
 
@@ -295,19 +317,25 @@ __device__ __forceinline__ u32 group_sel16(const u8* __restrict__ mask_sub, i64 
     return sel;
 }
 
+template <int C>
 __global__ __launch_bounds__(256) void k_part_occ16(const u32x4* __restrict__ colored, const u8* __restrict__ mask_sub,
                                                     u32x4* __restrict__ occ, i64 ngroups, pb3d_magic mD) {
     for (i64 g = (i64)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += (i64)gridDim.x * blockDim.x) {
         u32 o[4] = {0, 0, 0, 0};
         const u32 sel = group_sel16(mask_sub, g, mD);
         if (sel) {
-            u32 w[12];
+            u32 w[4 * C];
 #pragma unroll
-            for (int k = 0; k < 3; ++k) { const u32x4 t = ld_s(colored + 3 * g + k); w[4 * k] = t.x; w[4 * k + 1] = t.y; w[4 * k + 2] = t.z; w[4 * k + 3] = t.w; }
+            for (int k = 0; k < C; ++k) { const u32x4 t = ld_s(colored + C * g + k); w[4 * k] = t.x; w[4 * k + 1] = t.y; w[4 * k + 2] = t.z; w[4 * k + 3] = t.w; }
+            if constexpr (C == 1) {
 #pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const u32 any = byte_of(w, 3 * i) | byte_of(w, 3 * i + 1) | byte_of(w, 3 * i + 2);
-                o[i >> 2] |= (any ? 1u : 0u) << ((i & 3) * 8);
+                for (int j = 0; j < 4; ++j) o[j] = nonzero_bytes(w[j]);
+            } else {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const u32 any = byte_of(w, 3 * i) | byte_of(w, 3 * i + 1) | byte_of(w, 3 * i + 2);
+                    o[i >> 2] |= (any ? 1u : 0u) << ((i & 3) * 8);
+                }
             }
             if (sel != 0xffffu) {
 #pragma unroll
@@ -342,13 +370,23 @@ __global__ __launch_bounds__(256) void k_keep_or16(const u32x4* __restrict__ car
     }
 }
 
+// vector k of group g: colored where the mask m (mask16) keeps, `under` elsewhere
+template <int C>
+__device__ __forceinline__ u32x4 keep_vec(const u32x4* __restrict__ colored, i64 g, int k, const u32* m, const u32x4 under) {
+    const u32x4 c = ld_s(colored + C * g + k);
+    u32x4 r;
+    r.x = (c.x & m[4 * k]) | (under.x & ~m[4 * k]); r.y = (c.y & m[4 * k + 1]) | (under.y & ~m[4 * k + 1]);
+    r.z = (c.z & m[4 * k + 2]) | (under.z & ~m[4 * k + 2]); r.w = (c.w & m[4 * k + 3]) | (under.w & ~m[4 * k + 3]);
+    return r;
+}
+
+template <int C>
 __global__ __launch_bounds__(256) void k_part_final16(const u32x4* __restrict__ colored, const u32x4* __restrict__ keep,
                                                       u32x4* __restrict__ out, i64 ngroups) {
-    __shared__ u32x4 stage[4][192];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     for (i64 gw0 = (i64)blockIdx.x * blockDim.x + 64 * wv; gw0 < ngroups; gw0 += (i64)gridDim.x * blockDim.x) {   // wave-uniform
         const i64 g = gw0 + lane;
-        u32x4 r[3] = {(u32x4)(0u), (u32x4)(0u), (u32x4)(0u)};
+        u32x4 r[C] = {};
         if (g < ngroups) {
             const u32x4 kv = ld_nt(keep + g);
             const u32 kw[4] = {kv.x, kv.y, kv.z, kv.w};
@@ -356,26 +394,28 @@ __global__ __launch_bounds__(256) void k_part_final16(const u32x4* __restrict__ 
 #pragma unroll
             for (int i = 0; i < 16; ++i) keep16 |= (byte_of(kw, i) ? 1u : 0u) << i;
             if (keep16) {
-                u32 m[12];
-                expand16(keep16, 0xffu, 0xffu, 0xffu, m);
+                u32 m[4 * C];
+                mask16<C>(keep16, m);
 #pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    const u32x4 c = ld_s(colored + 3 * g + k);
-                    r[k].x = c.x & m[4 * k]; r[k].y = c.y & m[4 * k + 1]; r[k].z = c.z & m[4 * k + 2]; r[k].w = c.w & m[4 * k + 3];
-                }
+                for (int k = 0; k < C; ++k) r[k] = keep_vec<C>(colored, g, k, m, (u32x4)(0u));
             }
         }
-        store48_wave(out, gw0, ngroups, r, stage[wv]);
+        store_groups<C>(out, gw0, ngroups, r);
     }
 }
 
 // out[v] = colored[v] where keep[v] (the rest of `out` -- the overlay of the fused 90-degree jobs -- stays)
+template <int C>
 __global__ __launch_bounds__(256) void k_part_merge(const u8* __restrict__ colored, const u8* __restrict__ keep, u8* __restrict__ out, i64 nvox,
                                                     i64 v_first = 0) {
     for (i64 v = v_first + (i64)blockIdx.x * blockDim.x + threadIdx.x; v < nvox; v += (i64)gridDim.x * blockDim.x)
-        if (keep[v]) { out[3 * v] = colored[3 * v]; out[3 * v + 1] = colored[3 * v + 1]; out[3 * v + 2] = colored[3 * v + 2]; }
+        if (keep[v]) {
+#pragma unroll
+            for (int c = 0; c < C; ++c) out[C * v + c] = colored[C * v + c];
+        }
 }
 
+template <int C>
 __global__ __launch_bounds__(256) void k_part_merge16(const u32x4* __restrict__ colored, const u32x4* __restrict__ keep, u32x4* __restrict__ out,
                                                       i64 ngroups) {
     for (i64 g = (i64)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += (i64)gridDim.x * blockDim.x) {
@@ -385,16 +425,10 @@ __global__ __launch_bounds__(256) void k_part_merge16(const u32x4* __restrict__ 
 #pragma unroll
         for (int i = 0; i < 16; ++i) keep16 |= (byte_of(kw, i) ? 1u : 0u) << i;
         if (!keep16) continue;                               // untouched groups cost 16 bytes of keep
-        u32 m[12];
-        expand16(keep16, 0xffu, 0xffu, 0xffu, m);
+        u32 m[4 * C];
+        mask16<C>(keep16, m);
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const u32x4 c = ld_s(colored + 3 * g + k), o = ld_s(out + 3 * g + k);
-            u32x4 r;
-            r.x = (c.x & m[4 * k]) | (o.x & ~m[4 * k]); r.y = (c.y & m[4 * k + 1]) | (o.y & ~m[4 * k + 1]);
-            r.z = (c.z & m[4 * k + 2]) | (o.z & ~m[4 * k + 2]); r.w = (c.w & m[4 * k + 3]) | (o.w & ~m[4 * k + 3]);
-            st_s(out + 3 * g + k, r);
-        }
+        for (int k = 0; k < C; ++k) st_s(out + C * g + k, keep_vec<C>(colored, g, k, m, ld_s(out + C * g + k)));
     }
 }
 
@@ -434,33 +468,25 @@ __device__ __forceinline__ u32 multi_keep16(const u32x4* __restrict__ carvedN, i
     return keep16;
 }
 
-template <bool MERGE>
+template <bool MERGE, int C>
 __global__ __launch_bounds__(256) void k_part_multi16(const u32x4* __restrict__ colored, const u32x4* __restrict__ carvedN, i64 ngroups_stride, int nk,
                                                       const u32* __restrict__ S, pb3d_magic mD, u32x4* __restrict__ out, i64 ngroups) {
-    __shared__ u32x4 stage[4][192];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     for (i64 gw0 = (i64)blockIdx.x * blockDim.x + 64 * wv; gw0 < ngroups; gw0 += (i64)gridDim.x * blockDim.x) {   // wave-uniform
         const i64 g = gw0 + lane;
-        u32x4 r[3] = {(u32x4)(0u), (u32x4)(0u), (u32x4)(0u)};
+        u32x4 r[C] = {};
         u32 keep16 = 0;
         if (g < ngroups) keep16 = multi_keep16(carvedN, ngroups_stride, nk, S, g, mD);
         if (keep16) {
-            u32 m[12];
-            expand16(keep16, 0xffu, 0xffu, 0xffu, m);
+            u32 m[4 * C];
+            mask16<C>(keep16, m);
 #pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const u32x4 c = ld_s(colored + 3 * g + k);
-                if (MERGE) {
-                    const u32x4 o = ld_s(out + 3 * g + k);
-                    r[k].x = (c.x & m[4 * k]) | (o.x & ~m[4 * k]); r[k].y = (c.y & m[4 * k + 1]) | (o.y & ~m[4 * k + 1]);
-                    r[k].z = (c.z & m[4 * k + 2]) | (o.z & ~m[4 * k + 2]); r[k].w = (c.w & m[4 * k + 3]) | (o.w & ~m[4 * k + 3]);
-                    st_s(out + 3 * g + k, r[k]);
-                } else {
-                    r[k].x = c.x & m[4 * k]; r[k].y = c.y & m[4 * k + 1]; r[k].z = c.z & m[4 * k + 2]; r[k].w = c.w & m[4 * k + 3];
-                }
+            for (int k = 0; k < C; ++k) {
+                if (MERGE) st_s(out + C * g + k, keep_vec<C>(colored, g, k, m, ld_s(out + C * g + k)));
+                else r[k] = keep_vec<C>(colored, g, k, m, (u32x4)(0u));
             }
         }
-        if (!MERGE) store48_wave(out, gw0, ngroups, r, stage[wv]);
+        if (!MERGE) store_groups<C>(out, gw0, ngroups, r);
     }
 }
 
@@ -492,8 +518,8 @@ int pb3d_carve_mask_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t W, int64_t
                            (u32x4*)d_out, d_mask_wh, nvec, ncols, vpc, magic);
     } else if (col >= 16 && col < (1ll << 31) - kTileVec * 16 && (nbytes + kTileVec * 16 - 1) / (kTileVec * 16) < (1ll << 31)) {
         const unsigned blocks = (unsigned)((nbytes + kTileVec * 16 - 1) / (kTileVec * 16));
-        hipLaunchKernelGGL(k_carve_flat, dim3(blocks), dim3(kTileThreads), 0, ctx->stream, d_grid, d_out, d_mask_wh, nbytes, ncols, (u32)col,
-                           make_magic32((u32)col));
+        hipLaunchKernelGGL(k_carve_flat, dim3(blocks), dim3(kTileThreads), 0, ctx->stream, d_grid, d_out, d_mask_wh, nbytes, ncols,
+                           pb3d_make_magic((u32)col));
     } else {
         const unsigned blocks = pb3d_stream_blocks(ctx, (nbytes + 15) / 16, 256, 8);
         hipLaunchKernelGGL(k_carve_bytes, dim3(blocks), dim3(256), 0, ctx->stream, d_grid, d_out, d_mask_wh, nbytes, col);
@@ -525,40 +551,33 @@ int pb3d_occupancy_dev(pb3d_ctx* ctx, const uint8_t* d_grid_rgb, int64_t nvox, u
 int pb3d_color_apply_dev(pb3d_ctx* ctx, const uint8_t* d_carved, int64_t W, int64_t H, int64_t D,
                          const uint8_t* d_rgb_hw3, uint8_t* d_out) {
     PB3D_REQUIRE(ctx != nullptr && W >= 0 && H >= 0 && D >= 0, "pb3d_color_apply: bad shape");
-    const i64 nvox = W * H * D;
-    if (nvox == 0) return PB3D_OK;
+    if (W * H * D == 0) return PB3D_OK;
     PB3D_REQUIRE(d_carved && d_rgb_hw3 && d_out, "pb3d_color_apply: null buffer");
-    const i64 ngroups = D >= 16 ? nvox / 16 : 0;      // whole groups of 16 voxels of the flat stream; the rest goes voxel by voxel
-    // one workgroup per 256 groups, not a persistent grid-stride loop: the dispatcher balances a write-heavy stream better (0.84 -> 0.70 ms)
-    const unsigned ca_blocks = pb3d_stream_blocks(ctx, ngroups, 256, 0);
-    if (ngroups) {
-        if (D % 16 == 0)
-            hipLaunchKernelGGL(k_color_apply16<false>, dim3(ca_blocks), dim3(256), 0, ctx->stream, d_carved,
-                               d_rgb_hw3, d_out, W, H, D, ngroups, pb3d_make_magic((u32)(D < (1ll << 31) ? D : 1)), pb3d_make_magic((u32)(H < (1ll << 31) ? H : 1)),
-                               (nvox < (1ll << 32) && D < (1ll << 31) && H < (1ll << 31)) ? 1 : 0);
-        else
-            hipLaunchKernelGGL(k_color_apply16<true>, dim3(ca_blocks), dim3(256), 0, ctx->stream, d_carved,
-                               d_rgb_hw3, d_out, W, H, D, ngroups, pb3d_make_magic((u32)(D < (1ll << 31) ? D : 1)), pb3d_make_magic((u32)(H < (1ll << 31) ? H : 1)),
-                               (nvox < (1ll << 32) && D < (1ll << 31) && H < (1ll << 31)) ? 1 : 0);
-        PB3D_CHECK_LAUNCH();
-    }
-    if (16 * ngroups < nvox)
-        hipLaunchKernelGGL(k_color_apply_generic, dim3(pb3d_stream_blocks(ctx, nvox - 16 * ngroups, 256, 8)), dim3(256), 0, ctx->stream,
-                           d_carved, d_rgb_hw3, d_out, W, H, D, 16 * ngroups);
-    PB3D_CHECK_LAUNCH();
-    return PB3D_OK;
+    return pb3d_image_apply_dev(ctx, d_carved, W, H, D, d_rgb_hw3, 3, d_out);
 }
 
 int pb3d_part_carve_dev(pb3d_ctx* ctx, const uint8_t* d_colored, int64_t W, int64_t H, int64_t D,
                         const uint8_t* d_mask_sub, const uint8_t* d_mask_carve, const int* job_angle,
                         const int* job_skip, int njobs, uint8_t* d_out) {
     PB3D_REQUIRE(ctx != nullptr && W >= 0 && H >= 0 && D >= 0 && njobs >= 0, "pb3d_part_carve: bad shape");
-    const i64 nvox = W * H * D;
-    if (nvox == 0) return PB3D_OK;
+    if (W * H * D == 0) return PB3D_OK;
     PB3D_REQUIRE(d_colored && d_out && (njobs == 0 || (d_mask_sub && d_mask_carve && job_angle && job_skip)),
                  "pb3d_part_carve: null buffer");
     for (int j = 0; j < njobs; ++j)
         PB3D_REQUIRE(job_skip[j] || job_angle[j] > 0, "pb3d_part_carve: job %d has angle %d (must be > 0)", j, job_angle[j]);
+    return pb3d_part_carve_jobs(ctx, d_colored, 3, W, H, D, d_mask_sub, d_mask_carve, job_angle, job_skip, njobs, d_out);
+}
+
+}  // extern "C"
+
+namespace {
+
+// part_carve behind the entries' argument checks (nvox > 0), on voxels of C bytes.  Knob per_job = 1: every job goes through the
+// job-by-job passes at the end -- no fused 90-degree sweep, no merged pass (the parity tests compare the two that way).
+template <int C>
+int part_carve_jobs(pb3d_ctx* ctx, const u8* d_colored, i64 W, i64 H, i64 D, const u8* d_mask_sub, const u8* d_mask_carve, const int* job_angle,
+                    const int* job_skip, int njobs, u8* d_out) {
+    const i64 nvox = W * H * D;
     // Every job overlays colored[v] where it keeps, so the result is the union of the jobs' keep sets in any order: all
     // 90-degree jobs go through ONE fused sweep (csrc/rotate_tiled.hip, K5); jobs with other angles follow one by one and are
     // merged into that overlay.
@@ -567,10 +586,10 @@ int pb3d_part_carve_dev(pb3d_ctx* ctx, const uint8_t* d_colored, int64_t W, int6
         if (!job_skip[j]) { if (job_angle[j] == 90) ++n90; else ++nother; }
     bool base90 = false;                // d_out already holds the overlay of the 90-degree jobs
     std::vector<int> skip_rest(job_skip, job_skip + njobs);
-    if (n90 > 0 && njobs <= 32) {
+    if (n90 > 0 && njobs <= 32 && ctx->tune_per_job != 1) {
         std::vector<int> skip90(njobs);
         for (int j = 0; j < njobs; ++j) skip90[j] = job_skip[j] || job_angle[j] != 90;
-        const int rc = pb3d_try_part_carve90(ctx, d_colored, 3, W, H, D, d_mask_sub, d_mask_carve, job_angle, skip90.data(), njobs, d_out);
+        const int rc = pb3d_try_part_carve90(ctx, d_colored, C, W, H, D, d_mask_sub, d_mask_carve, job_angle, skip90.data(), njobs, d_out);
         if (rc != PB3D_EUNSUPPORTED) {
             if (rc != PB3D_OK || nother == 0) return rc;
             base90 = true;
@@ -593,8 +612,7 @@ int pb3d_part_carve_dev(pb3d_ctx* ctx, const uint8_t* d_colored, int64_t W, int6
     const i64 ngroups = nvox / 16, vtail = 16 * ngroups;                    // the last nvox % 16 voxels: scalar kernels from vtail on
     const pb3d_magic mD = pb3d_make_magic((u32)(D > 0 ? D : 1));
     const unsigned gblocks = pb3d_stream_blocks(ctx, ngroups > 0 ? ngroups : 1, 256, 8);
-    // up to eight such jobs: each leaves its carved occupancy in its own volume and ONE pass merges them (k_part_multi16); knob per_job = 1
-    // keeps the job-by-job keep-OR passes
+    // up to eight such jobs: each leaves its carved occupancy in its own volume and ONE pass merges them (k_part_multi16)
     JobList jl; jl.n = 0;
     for (int j = 0; j < njobs; ++j)
         if (!job_skip[j] && jl.n < 8) jl.j[jl.n++] = j;
@@ -604,17 +622,17 @@ int pb3d_part_carve_dev(pb3d_ctx* ctx, const uint8_t* d_colored, int64_t W, int6
             const int j = jl.j[k];
             const u8* ms = d_mask_sub + (i64)j * W * H;
             const u8* mc = d_mask_carve + (i64)j * W * H;
-            hipLaunchKernelGGL(k_part_occ16, dim3(gblocks), dim3(256), 0, ctx->stream, (const u32x4*)d_colored, ms, (u32x4*)occ, ngroups, mD);
+            hipLaunchKernelGGL(k_part_occ16<C>, dim3(gblocks), dim3(256), 0, ctx->stream, (const u32x4*)d_colored, ms, (u32x4*)occ, ngroups, mD);
             PB3D_CHECK_LAUNCH();
             PB3D_TRY(pb3d_process_grid_binary_dev(ctx, (const u8*)occ, W, H, D, mc, job_angle[j], (u8*)carvedN + (i64)k * nvox, (u8*)tmp));
         }
         hipLaunchKernelGGL(k_sub_bitset, dim3(pb3d_stream_blocks(ctx, W * H, 256, 8)), dim3(256), 0, ctx->stream, d_mask_sub, jl, W * H, (u32*)S);
         PB3D_CHECK_LAUNCH();
         if (base90)
-            hipLaunchKernelGGL(k_part_multi16<true>, dim3(gblocks), dim3(256), 0, ctx->stream, (const u32x4*)d_colored, (const u32x4*)carvedN, ngroups, jl.n,
+            hipLaunchKernelGGL((k_part_multi16<true, C>), dim3(gblocks), dim3(256), 0, ctx->stream, (const u32x4*)d_colored, (const u32x4*)carvedN, ngroups, jl.n,
                                (const u32*)S, mD, (u32x4*)d_out, ngroups);
         else
-            hipLaunchKernelGGL(k_part_multi16<false>, dim3(gblocks), dim3(256), 0, ctx->stream, (const u32x4*)d_colored, (const u32x4*)carvedN, ngroups, jl.n,
+            hipLaunchKernelGGL((k_part_multi16<false, C>), dim3(gblocks), dim3(256), 0, ctx->stream, (const u32x4*)d_colored, (const u32x4*)carvedN, ngroups, jl.n,
                                (const u32*)S, mD, (u32x4*)d_out, ngroups);
         PB3D_CHECK_LAUNCH();
         return PB3D_OK;
@@ -625,10 +643,10 @@ int pb3d_part_carve_dev(pb3d_ctx* ctx, const uint8_t* d_colored, int64_t W, int6
         const u8* ms = d_mask_sub + (i64)j * W * H;
         const u8* mc = d_mask_carve + (i64)j * W * H;
         if (wide) {
-            hipLaunchKernelGGL(k_part_occ16, dim3(gblocks), dim3(256), 0, ctx->stream, (const u32x4*)d_colored, ms, (u32x4*)occ, ngroups, mD);
-            if (vtail < nvox) hipLaunchKernelGGL(k_part_occ, dim3(1), dim3(256), 0, ctx->stream, d_colored, ms, (u8*)occ, nvox, D, vtail);
+            hipLaunchKernelGGL(k_part_occ16<C>, dim3(gblocks), dim3(256), 0, ctx->stream, (const u32x4*)d_colored, ms, (u32x4*)occ, ngroups, mD);
+            if (vtail < nvox) hipLaunchKernelGGL(k_part_occ<C>, dim3(1), dim3(256), 0, ctx->stream, d_colored, ms, (u8*)occ, nvox, D, vtail);
         } else
-            hipLaunchKernelGGL(k_part_occ, dim3(blocks), dim3(256), 0, ctx->stream, d_colored, ms, (u8*)occ, nvox, D);
+            hipLaunchKernelGGL(k_part_occ<C>, dim3(blocks), dim3(256), 0, ctx->stream, d_colored, ms, (u8*)occ, nvox, D);
         PB3D_CHECK_LAUNCH();
         PB3D_TRY(pb3d_process_grid_binary_dev(ctx, (const u8*)occ, W, H, D, mc, job_angle[j], (u8*)carved, (u8*)tmp));
         if (wide) {
@@ -640,27 +658,60 @@ int pb3d_part_carve_dev(pb3d_ctx* ctx, const uint8_t* d_colored, int64_t W, int6
         any = true;
     }
     if (!any) {
-        if (!base90) PB3D_HIP(hipMemsetAsync(d_out, 0, (size_t)nvox * 3, ctx->stream));
+        if (!base90) PB3D_HIP(hipMemsetAsync(d_out, 0, (size_t)nvox * C, ctx->stream));
         return PB3D_OK;
     }
     if (base90) {
         if (wide) {
-            hipLaunchKernelGGL(k_part_merge16, dim3(gblocks), dim3(256), 0, ctx->stream, (const u32x4*)d_colored, (const u32x4*)keep, (u32x4*)d_out,
+            hipLaunchKernelGGL(k_part_merge16<C>, dim3(gblocks), dim3(256), 0, ctx->stream, (const u32x4*)d_colored, (const u32x4*)keep, (u32x4*)d_out,
                                ngroups);
-            if (vtail < nvox) hipLaunchKernelGGL(k_part_merge, dim3(1), dim3(256), 0, ctx->stream, d_colored, (const u8*)keep, d_out, nvox, vtail);
+            if (vtail < nvox) hipLaunchKernelGGL(k_part_merge<C>, dim3(1), dim3(256), 0, ctx->stream, d_colored, (const u8*)keep, d_out, nvox, vtail);
         } else
-            hipLaunchKernelGGL(k_part_merge, dim3(blocks), dim3(256), 0, ctx->stream, d_colored, (const u8*)keep, d_out, nvox);
+            hipLaunchKernelGGL(k_part_merge<C>, dim3(blocks), dim3(256), 0, ctx->stream, d_colored, (const u8*)keep, d_out, nvox);
         PB3D_CHECK_LAUNCH();
         return PB3D_OK;
     }
     if (wide) {
-        hipLaunchKernelGGL(k_part_final16, dim3(gblocks), dim3(256), 0, ctx->stream, (const u32x4*)d_colored, (const u32x4*)keep, (u32x4*)d_out,
+        hipLaunchKernelGGL(k_part_final16<C>, dim3(gblocks), dim3(256), 0, ctx->stream, (const u32x4*)d_colored, (const u32x4*)keep, (u32x4*)d_out,
                            ngroups);
-        if (vtail < nvox) hipLaunchKernelGGL(k_part_final, dim3(1), dim3(256), 0, ctx->stream, d_colored, (const u8*)keep, d_out, nvox, vtail);
+        if (vtail < nvox) hipLaunchKernelGGL(k_part_final<C>, dim3(1), dim3(256), 0, ctx->stream, d_colored, (const u8*)keep, d_out, nvox, vtail);
     } else
-        hipLaunchKernelGGL(k_part_final, dim3(blocks), dim3(256), 0, ctx->stream, d_colored, (const u8*)keep, d_out, nvox);
+        hipLaunchKernelGGL(k_part_final<C>, dim3(blocks), dim3(256), 0, ctx->stream, d_colored, (const u8*)keep, d_out, nvox);
     PB3D_CHECK_LAUNCH();
     return PB3D_OK;
 }
 
-}  // extern "C"
+}  // namespace
+
+int pb3d_image_apply_dev(pb3d_ctx* ctx, const u8* d_carved, i64 W, i64 H, i64 D, const u8* d_img_hwc, int C, u8* d_out) {
+    const i64 nvox = W * H * D;
+    const int small = (nvox < (1ll << 32) && D < (1ll << 31) && H < (1ll << 31)) ? 1 : 0;      // exact u32 divisions
+    i64 ngroups = D >= 16 ? nvox / 16 : 0;            // whole groups of 16 voxels of the flat stream; the rest goes voxel by voxel
+    if (C == 1 && !(small && aligned16(d_carved) && aligned16(d_out))) ngroups = 0;          // k_label_apply16's conditions
+    if (ngroups) {
+        const pb3d_magic mD = pb3d_make_magic((u32)(D < (1ll << 31) ? D : 1)), mH = pb3d_make_magic((u32)(H < (1ll << 31) ? H : 1));
+        // RGB: one workgroup per 256 groups, not a persistent grid-stride loop: the dispatcher balances a write-heavy stream better (0.84 -> 0.70 ms)
+        const unsigned ca_blocks = pb3d_stream_blocks(ctx, ngroups, 256, 0);
+        if (C == 1)
+            hipLaunchKernelGGL(k_label_apply16, dim3(pb3d_stream_blocks(ctx, ngroups, 256, 16)), dim3(256), 0, ctx->stream, d_carved, d_img_hwc, W, H, ngroups,
+                               mD, mH, d_out);
+        else if (D % 16 == 0)
+            hipLaunchKernelGGL(k_color_apply16<false>, dim3(ca_blocks), dim3(256), 0, ctx->stream, d_carved, d_img_hwc, d_out, W, H, D, ngroups, mD, mH, small);
+        else
+            hipLaunchKernelGGL(k_color_apply16<true>, dim3(ca_blocks), dim3(256), 0, ctx->stream, d_carved, d_img_hwc, d_out, W, H, D, ngroups, mD, mH, small);
+        PB3D_CHECK_LAUNCH();
+    }
+    if (16 * ngroups < nvox) {
+        const unsigned blocks = pb3d_stream_blocks(ctx, nvox - 16 * ngroups, 256, 8);
+        if (C == 1) hipLaunchKernelGGL(k_color_apply_generic<1>, dim3(blocks), dim3(256), 0, ctx->stream, d_carved, d_img_hwc, d_out, W, H, D, 16 * ngroups);
+        else hipLaunchKernelGGL(k_color_apply_generic<3>, dim3(blocks), dim3(256), 0, ctx->stream, d_carved, d_img_hwc, d_out, W, H, D, 16 * ngroups);
+    }
+    PB3D_CHECK_LAUNCH();
+    return PB3D_OK;
+}
+
+int pb3d_part_carve_jobs(pb3d_ctx* ctx, const u8* d_colored, int C, i64 W, i64 H, i64 D, const u8* d_mask_sub, const u8* d_mask_carve,
+                         const int* job_angle, const int* job_skip, int njobs, u8* d_out) {
+    return C == 1 ? part_carve_jobs<1>(ctx, d_colored, W, H, D, d_mask_sub, d_mask_carve, job_angle, job_skip, njobs, d_out)
+                  : part_carve_jobs<3>(ctx, d_colored, W, H, D, d_mask_sub, d_mask_carve, job_angle, job_skip, njobs, d_out);
+}

@@ -54,14 +54,19 @@ int pb3d_global_carve_dev(pb3d_ctx* ctx, const uint8_t* d_bin_hw, const uint8_t*
         PB3D_TRY(pb3d_global_carve_sliced(ctx, (const u8*)mwh, d_rgb_hw3, W, H, D, angle_interval, d_out_slab, &took));
         if (took) return PB3D_OK;
     }
-    // composed pipeline: ones -> process_voxel_grid -> colour
+    return pb3d_global_carve_composed(ctx, (const u8*)mwh, d_rgb_hw3, 3, W, H, D, angle_interval, d_out_slab);
+}
+
+}  // extern "C"
+
+// composed pipeline: ones -> process_voxel_grid -> colour (C == 3) or label (C == 1) of the column's pixel
+int pb3d_global_carve_composed(pb3d_ctx* ctx, const u8* d_mask_wh, const u8* d_img_hwc, int C, i64 W, i64 H, i64 D, int angle_interval, u8* d_out) {
+    const i64 nvox = W * H * D;
     void *ones, *carved, *tmp;
     PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_VOL_OCC, (size_t)nvox, &ones));
     PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_VOL_CARVED, (size_t)nvox, &carved));
     PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_VOL_TMP, (size_t)nvox, &tmp));
     PB3D_HIP(hipMemsetAsync(ones, 1, (size_t)nvox, ctx->stream));
-    PB3D_TRY(pb3d_process_grid_binary_dev(ctx, (const u8*)ones, W, H, D, (const u8*)mwh, angle_interval, (u8*)carved, (u8*)tmp));
-    return pb3d_color_apply_dev(ctx, (const u8*)carved, W, H, D, d_rgb_hw3, d_out_slab);
+    PB3D_TRY(pb3d_process_grid_binary_dev(ctx, (const u8*)ones, W, H, D, d_mask_wh, angle_interval, (u8*)carved, (u8*)tmp));
+    return pb3d_image_apply_dev(ctx, (const u8*)carved, W, H, D, d_img_hwc, C, d_out);
 }
-
-}  // extern "C"

@@ -6,8 +6,9 @@
 // The carve ops act on labels exactly as on colours (zero where the mask drops, the column's own value elsewhere), at a third
 // of the traffic; the label volume is also what a multi-GPU run should reassemble (1 B/voxel over xGMI instead of 3) -- every
 // rank expands to RGB locally, and only if a consumer needs RGB at all.
-#include <vector>
-
+// This file holds the conversions and the label entries' argument checks.  The carving itself is the RGB forms' code with one byte
+// per voxel: part_carve's job loop and kernels (csrc/carve.hip, pb3d_part_carve_jobs), global_carve's composed pipeline and its apply
+// pass (csrc/global.hip, pb3d_global_carve_composed), the fused 90-degree paths (csrc/rotate_tiled.hip, csrc/bits90.hip).
 #include "pb3d_internal.h"
 
 #include "lane48.h"      // u32x4, and u32x4_u: the conversions take caller pointers at any byte address
@@ -130,116 +131,6 @@ __global__ __launch_bounds__(256) void k_label_to_rgb(const u8* __restrict__ lab
     if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(unknown, 1);
 }
 
-// apply_colored_mask_to_voxel_grid on labels: out[x,y,z] = carved[x,y,z] == 1 ? label_hw[y,x] : 0
-__global__ __launch_bounds__(256) void k_label_apply(const u8* __restrict__ carved, const u8* __restrict__ label_hw, i64 W, i64 H, i64 D,
-                                                     u8* __restrict__ out, i64 v_first = 0) {
-    const i64 nvox = W * H * D;
-    for (i64 i = v_first + (i64)blockIdx.x * blockDim.x + threadIdx.x; i < nvox; i += (i64)gridDim.x * blockDim.x) {
-        const i64 col = i / D, x = col / H, y = col - x * H;
-        out[i] = carved[i] == 1 ? label_hw[y * W + x] : (u8)0;
-    }
-}
-
-
-// the same, 16 voxels of the flat stream per thread (fewer than 2^32 voxels, D >= 16, 16-byte aligned output): a group lies in one
-// (x,y) column or straddles two; exact u32 divisions (the per-voxel form spends two 64-bit divisions per BYTE)
-__global__ __launch_bounds__(256) void k_label_apply16(const u8* __restrict__ carved, const u8* __restrict__ label_hw, i64 W, i64 H, i64 ngroups,
-                                                       pb3d_magic mD, pb3d_magic mH, u8* __restrict__ out) {
-    for (i64 g = (i64)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += (i64)gridDim.x * blockDim.x) {
-        const u32 v0 = (u32)(16 * g);
-        const u32 col = pb3d_div(v0, mD), x = pb3d_div(col, mH), y = col - x * mH.d;
-        const u32 bnd = (col + 1) * mD.d - v0;                      // voxels of the group in column `col` (>= 1)
-        const u32 L0 = label_hw[(i64)y * W + x];
-        u32 L1 = L0;
-        if (bnd < 16u) { const u32 x1 = y + 1 < mH.d ? x : x + 1, y1 = y + 1 < mH.d ? y + 1 : 0u; L1 = label_hw[(i64)y1 * W + x1]; }
-        const u32x4 cv = *(const u32x4*)(carved + 16 * g);
-        const u32 cw[4] = {cv.x, cv.y, cv.z, cv.w};
-        u32 o[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const u32 t = cw[j] ^ 0x01010101u;                                          // a byte equal to 1 becomes 0
-            const u32 z = (((t & 0x7f7f7f7fu) + 0x7f7f7f7fu) | t) & 0x80808080u;          // bit 7 set <=> the byte is non-zero
-            const u32 e = ((~z & 0x80808080u) >> 7) * 0xffu;                             // 0xff where carved == 1
-            u32 lab = 0;
-#pragma unroll
-            for (int b = 0; b < 4; ++b) lab |= ((u32)(4 * j + b) < bnd ? L0 : L1) << (8 * b);
-            o[j] = e & lab;
-        }
-        u32x4 r; r.x = o[0]; r.y = o[1]; r.z = o[2]; r.w = o[3];
-        *(u32x4*)(out + 16 * g) = r;
-    }
-}
-
-// part_carve on labels (reference utils/voxel_carving_utils.py:139-160 with the colour grid in label form), per job:
-//   occ[v]  = mask_sub[xy] && label[v] != 0 ; carved = process_voxel_grid(occ, mask_carve, angle) ; keep[v] |= mask_sub[xy] && carved[v]
-//   out[v]  = keep[v] ? label[v] : 0
-// G = 16 voxels per thread when a column is a whole number of 16-byte groups, else 1.
-template <int G>
-__global__ __launch_bounds__(256) void k_label_occ(const u8* __restrict__ label, const u8* __restrict__ mask_sub, u8* __restrict__ occ, i64 nvox, i64 D,
-                                                   pb3d_magic mD, int small) {
-    const i64 ngroups = nvox / G;
-    for (i64 g = (i64)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += (i64)gridDim.x * blockDim.x) {
-        const bool m = mask_sub[small ? (i64)pb3d_div((u32)(g * G), mD) : (g * G) / D] != 0;
-        if (G == 16) {
-            u32x4 r = (u32x4)(0u);
-            if (m) {
-                const u32x4 t = *(const u32x4*)(label + 16 * g);
-                const u32 w[4] = {t.x, t.y, t.z, t.w};
-                u32 o[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) { u32 v = w[k]; v |= v >> 4; v |= v >> 2; v |= v >> 1; o[k] = v & 0x01010101u; }
-                r.x = o[0]; r.y = o[1]; r.z = o[2]; r.w = o[3];
-            }
-            *(u32x4*)(occ + 16 * g) = r;
-        } else {
-            occ[g] = (m && label[g]) ? 1 : 0;
-        }
-    }
-}
-
-template <int G>
-__global__ __launch_bounds__(256) void k_label_keep_or(const u8* __restrict__ carved, const u8* __restrict__ mask_sub, u8* __restrict__ keep, i64 nvox,
-                                                       i64 D, int first, pb3d_magic mD, int small) {
-    const i64 ngroups = nvox / G;
-    for (i64 g = (i64)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += (i64)gridDim.x * blockDim.x) {
-        const bool m = mask_sub[small ? (i64)pb3d_div((u32)(g * G), mD) : (g * G) / D] != 0;
-        if (G == 16) {
-            u32x4 r = (u32x4)(0u);
-            if (m) {
-                const u32x4 t = *(const u32x4*)(carved + 16 * g);
-                const u32 w[4] = {t.x, t.y, t.z, t.w};
-                u32 o[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) { u32 v = w[k]; v |= v >> 4; v |= v >> 2; v |= v >> 1; o[k] = v & 0x01010101u; }
-                r.x = o[0]; r.y = o[1]; r.z = o[2]; r.w = o[3];
-            }
-            if (!first) { const u32x4 k0 = *(const u32x4*)(keep + 16 * g); r.x |= k0.x; r.y |= k0.y; r.z |= k0.z; r.w |= k0.w; }
-            *(u32x4*)(keep + 16 * g) = r;
-        } else {
-            const u8 k = (m && carved[g]) ? 1 : 0;
-            keep[g] = first ? k : (u8)(keep[g] | k);
-        }
-    }
-}
-
-template <int G>
-__global__ __launch_bounds__(256) void k_label_final(const u8* __restrict__ label, const u8* __restrict__ keep, u8* __restrict__ out, i64 nvox) {
-    const i64 ngroups = nvox / G;
-    for (i64 g = (i64)blockIdx.x * blockDim.x + threadIdx.x; g < ngroups; g += (i64)gridDim.x * blockDim.x) {
-        if (G == 16) {
-            const u32x4 k = *(const u32x4*)(keep + 16 * g);
-            u32x4 r = (u32x4)(0u);
-            if (k.x | k.y | k.z | k.w) {
-                const u32x4 t = *(const u32x4*)(label + 16 * g);
-                r.x = t.x & (k.x * 0xffu); r.y = t.y & (k.y * 0xffu); r.z = t.z & (k.z * 0xffu); r.w = t.w & (k.w * 0xffu);   // keep bytes are 0/1
-            }
-            *(u32x4*)(out + 16 * g) = r;
-        } else {
-            out[g] = keep[g] ? label[g] : (u8)0;
-        }
-    }
-}
-
 int palette_words(const u8* palette, int npal, u32* pal) {
     PB3D_REQUIRE(npal >= 0 && npal <= 254 && (npal == 0 || palette), "pb3d label ops: palette of 0..254 colours");
     for (int k = 0; k < 256; ++k) pal[k] = 0;
@@ -312,75 +203,21 @@ int pb3d_global_carve_label_dev(pb3d_ctx* ctx, const uint8_t* d_bin_hw, const ui
         PB3D_TRY(pb3d_offset(M, shape, off));
         if (pb3d_is_perm_step(M, off, W, D)) return pb3d_launch_global_carve90(ctx, d_bin_hw, d_label_hw, 1, h, w, M, off, 0, W, d_out);
     }
-    void *ones, *carved, *tmp, *mwh;
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_VOL_OCC, (size_t)nvox, &ones));
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_VOL_CARVED, (size_t)nvox, &carved));
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_VOL_TMP, (size_t)nvox, &tmp));
+    void* mwh;
     PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MASK_WH, (size_t)(W * H), &mwh));
-    PB3D_HIP(hipMemsetAsync(ones, 1, (size_t)nvox, ctx->stream));
     PB3D_TRY(pb3d_transpose_mask_dev(ctx, d_bin_hw, H, W, (u8*)mwh));
-    PB3D_TRY(pb3d_process_grid_binary_dev(ctx, (const u8*)ones, W, H, D, (const u8*)mwh, angle_interval, (u8*)carved, (u8*)tmp));
-    if (nvox < (1ll << 32) && D >= 16 && (((uintptr_t)d_out) & 15u) == 0) {
-        const i64 ngroups = nvox / 16;
-        hipLaunchKernelGGL(k_label_apply16, dim3(pb3d_stream_blocks(ctx, ngroups, 256, 16)), dim3(256), 0, ctx->stream, (const u8*)carved, d_label_hw, W, H,
-                           ngroups, pb3d_make_magic((u32)D), pb3d_make_magic((u32)H), d_out);
-        if (16 * ngroups < nvox)
-            hipLaunchKernelGGL(k_label_apply, dim3(1), dim3(256), 0, ctx->stream, (const u8*)carved, d_label_hw, W, H, D, d_out, 16 * ngroups);
-    } else
-        hipLaunchKernelGGL(k_label_apply, dim3(pb3d_stream_blocks(ctx, nvox, 256, 16)), dim3(256), 0, ctx->stream, (const u8*)carved, d_label_hw, W, H, D,
-                           d_out);
-    PB3D_CHECK_LAUNCH();
-    return PB3D_OK;
+    return pb3d_global_carve_composed(ctx, (const u8*)mwh, d_label_hw, 1, W, H, D, angle_interval, d_out);
 }
 
 int pb3d_part_carve_label_dev(pb3d_ctx* ctx, const uint8_t* d_label, int64_t W, int64_t H, int64_t D, const uint8_t* d_mask_sub,
                               const uint8_t* d_mask_carve, const int* job_angle, const int* job_skip, int njobs, uint8_t* d_out) {
     PB3D_REQUIRE(ctx != nullptr && W >= 0 && H >= 0 && D >= 0 && njobs >= 0, "pb3d_part_carve_label: bad shape");
-    const i64 nvox = W * H * D;
-    if (nvox == 0) return PB3D_OK;
+    if (W * H * D == 0) return PB3D_OK;
     PB3D_REQUIRE(d_label && d_out && d_label != d_out && (njobs == 0 || (d_mask_sub && d_mask_carve && job_angle && job_skip)),
                  "pb3d_part_carve_label: null or aliased buffer");
     for (int j = 0; j < njobs; ++j)
         PB3D_REQUIRE(job_skip[j] || job_angle[j] > 0, "pb3d_part_carve_label: job %d has angle %d (must be > 0)", j, job_angle[j]);
-    // all live jobs at 90 degrees (the notebook's group_jobs): ONE launch of the plane-local kernel on the label bytes (csrc/bits90.hip,
-    // k_part90_plane<1>: occupancy = label != 0) instead of occupancy / process / keep passes per job
-    {
-        bool all90 = njobs > 0 && njobs <= 32, any_live = false;
-        for (int j = 0; j < njobs; ++j)
-            if (!job_skip[j]) { any_live = true; all90 = all90 && job_angle[j] == 90; }
-        if (all90 && any_live && ctx->tune_per_job != 1) {
-            const int rc = pb3d_try_part_carve90(ctx, d_label, 1, W, H, D, d_mask_sub, d_mask_carve, job_angle, job_skip, njobs, d_out);
-            if (rc != PB3D_EUNSUPPORTED) return rc;
-        }
-    }
-    void *occ, *carved, *tmp, *keep;
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_VOL_OCC, (size_t)nvox, &occ));
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_VOL_CARVED, (size_t)nvox, &carved));
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_VOL_TMP, (size_t)nvox, &tmp));
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_VOL_KEEP, (size_t)nvox, &keep));
-    const bool wide = D % 16 == 0 && ((((uintptr_t)d_label) | ((uintptr_t)d_out)) & 15u) == 0;
-    const unsigned blocks = pb3d_stream_blocks(ctx, wide ? nvox / 16 : nvox, 256, 8);
-    bool any = false;
-    const pb3d_magic mDl = pb3d_make_magic((u32)(D > 0 && D < (1ll << 31) ? D : 1));
-    const int smalll = (nvox < (1ll << 32) && D < (1ll << 31)) ? 1 : 0;
-    for (int j = 0; j < njobs; ++j) {
-        if (job_skip[j]) continue;
-        const u8* ms = d_mask_sub + (i64)j * W * H;
-        const u8* mc = d_mask_carve + (i64)j * W * H;
-        if (wide) hipLaunchKernelGGL(k_label_occ<16>, dim3(blocks), dim3(256), 0, ctx->stream, d_label, ms, (u8*)occ, nvox, D, mDl, smalll);
-        else hipLaunchKernelGGL(k_label_occ<1>, dim3(blocks), dim3(256), 0, ctx->stream, d_label, ms, (u8*)occ, nvox, D, mDl, smalll);
-        PB3D_CHECK_LAUNCH();
-        PB3D_TRY(pb3d_process_grid_binary_dev(ctx, (const u8*)occ, W, H, D, mc, job_angle[j], (u8*)carved, (u8*)tmp));
-        if (wide) hipLaunchKernelGGL(k_label_keep_or<16>, dim3(blocks), dim3(256), 0, ctx->stream, (const u8*)carved, ms, (u8*)keep, nvox, D, any ? 0 : 1, mDl, smalll);
-        else hipLaunchKernelGGL(k_label_keep_or<1>, dim3(blocks), dim3(256), 0, ctx->stream, (const u8*)carved, ms, (u8*)keep, nvox, D, any ? 0 : 1, mDl, smalll);
-        PB3D_CHECK_LAUNCH();
-        any = true;
-    }
-    if (!any) { PB3D_HIP(hipMemsetAsync(d_out, 0, (size_t)nvox, ctx->stream)); return PB3D_OK; }
-    if (wide) hipLaunchKernelGGL(k_label_final<16>, dim3(blocks), dim3(256), 0, ctx->stream, d_label, (const u8*)keep, d_out, nvox);
-    else hipLaunchKernelGGL(k_label_final<1>, dim3(blocks), dim3(256), 0, ctx->stream, d_label, (const u8*)keep, d_out, nvox);
-    PB3D_CHECK_LAUNCH();
-    return PB3D_OK;
+    return pb3d_part_carve_jobs(ctx, d_label, 1, W, H, D, d_mask_sub, d_mask_carve, job_angle, job_skip, njobs, d_out);
 }
 
 // ---- sharded forms: one process per GPU, communicator from pb3d_comm_init; rank r of n owns the X-planes [r W/n, (r+1) W/n) ----------

@@ -76,29 +76,51 @@ __device__ __forceinline__ void expand16(const u32 keep16, const u32 r, const u3
     }
 }
 
+__device__ __forceinline__ u32 one_bytes(u32 c) {                // byte j = (byte j of c == 1) ? 1 : 0
+    const u32 t = c ^ 0x01010101u;                                           // a byte equal to 1 becomes 0
+    const u32 z = (((t & 0x7f7f7f7fu) + 0x7f7f7f7fu) | t) & 0x80808080u;       // bit 7 of a byte set <=> the byte is non-zero
+    return (~z & 0x80808080u) >> 7;
+}
 // bit i = (byte i of the 16 bytes == 1)
 __device__ __forceinline__ u32 ones16(const u32 cw[4]) {
     u32 bits = 0;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const u32 t = cw[j] ^ 0x01010101u;                                     // a byte equal to 1 becomes 0
-        const u32 z = ((t & 0x7f7f7f7fu) + 0x7f7f7f7fu | t) & 0x80808080u;       // bit 7 of a byte set <=> the byte is non-zero
-        const u32 e = (~z & 0x80808080u) >> 7;                                  // bit 0 of a byte set <=> the byte was 1
-        bits |= ((e * 0x01020408u) >> 24) << (4 * j);                            // gather bits 0, 8, 16, 24 into 4 bits
-    }
+    for (int j = 0; j < 4; ++j) bits |= ((one_bytes(cw[j]) * 0x01020408u) >> 24) << (4 * j);      // gather bits 0, 8, 16, 24 into 4 bits
     return bits;
 }
 
 __device__ __forceinline__ u32 spread4(u32 b4) { return ((b4 * 0x00204081u) & 0x01010101u) * 0xffu; }      // bit j -> byte j = 0xff
+__device__ __forceinline__ u32 nonzero_bytes(u32 t) {            // byte j = (byte j of t != 0) ? 1 : 0
+    return ((((t & 0x7f7f7f7fu) + 0x7f7f7f7fu) | t) & 0x80808080u) >> 7;
+}
 __device__ __forceinline__ u32 nonzero16(const u32 cw[4]) {      // bit i = (byte i of the 16 bytes != 0)
     u32 bits = 0;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const u32 t = cw[j];
-        const u32 z = (((t & 0x7f7f7f7fu) + 0x7f7f7f7fu) | t) & 0x80808080u;
-        bits |= (((z >> 7) * 0x01020408u) >> 24) << (4 * j);
-    }
+    for (int j = 0; j < 4; ++j) bits |= ((nonzero_bytes(cw[j]) * 0x01020408u) >> 24) << (4 * j);
     return bits;
+}
+
+// ---- voxels of C bytes, 16 per lane: RGB grids (C == 3) and 1-byte label grids (C == 1) run the same kernels (csrc/carve.hip) ----
+// m[0 .. 4 C) = the AND mask of the 16 voxels' bytes: 0xff where the voxel's bit of keep16 is set
+template <int C>
+__device__ __forceinline__ void mask16(const u32 keep16, u32* m) {
+    if constexpr (C == 3) expand16(keep16, 0xffu, 0xffu, 0xffu, m);
+    else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) m[j] = spread4((keep16 >> (4 * j)) & 15u);
+    }
+}
+// The wave's 64 groups from gw0 on go out, r = this lane's C vectors; called by all 64 lanes.  With C == 1 a lane's 16 bytes follow its
+// neighbour's, so the plain store already writes whole lines: only the 48-byte lanes of C == 3 take the LDS window.
+template <int C>
+__device__ __forceinline__ void store_groups(u32x4_u* __restrict__ out, i64 gw0, i64 ngroups, const u32x4* r) {
+    if constexpr (C == 3) {
+        __shared__ u32x4 stage[4][192];
+        store48_wave(out, gw0, ngroups, r, stage[threadIdx.x >> 6]);
+    } else {
+        const i64 g = gw0 + (threadIdx.x & 63);
+        if (g < ngroups) st_nt(out + g, r[0]);
+    }
 }
 
 }  // namespace

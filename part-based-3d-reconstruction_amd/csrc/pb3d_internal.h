@@ -286,7 +286,7 @@ struct pb3d_ctx {
     int tune_rot90_mask_block;  // knob "rot90_mask_block": 1 = the 90-degree kernels fetch their mask bytes per plane / segment instead of once into LDS
     int tune_orient_tile;       // knob "orient_tile": 1 = pb3d_orient_dev without its 128-pixel tile kernel
     int tune_global_composed;   // knob "global_composed": 1 = global_carve with other angle steps as ones -> process -> colour (parity tests run both)
-    int tune_per_job;           // knob "per_job": 1 = part_carve's non-90 jobs one by one (no merged pass); label forms of global_carve / part_carve by their per-job passes
+    int tune_per_job;           // knob "per_job": 1 = part_carve's jobs one by one, RGB and label form alike (no fused 90-degree sweep, no merged pass); label form of global_carve(90) by the composed pipeline
     int tune_no_table_cache;    // knob "no_table_cache": 1 = validity tables and tile programs are rebuilt on every call
     int tune_part90_inflight;   // knob "part90_inflight": 10 UA + UE, items in flight per thread in the source / output pass of k_part90_plane (0 = 2 / 4)
     int tune_crop_ablate;       // knob "crop_ablate": ablation switches of k_crop_chain (tools/cropabl.py)
@@ -532,6 +532,14 @@ int pb3d_launch_rotate_perm(pb3d_ctx* ctx, const u8* d_in, i64 W, i64 H, i64 D, 
 int pb3d_try_part_carve90(pb3d_ctx* ctx, const u8* d_colored, int C, i64 W, i64 H, i64 D, const u8* d_mask_sub, const u8* d_mask_carve,
                           const int* job_angle, const int* job_skip, int njobs, u8* d_out);
 int pb3d_transpose_mask_dev(pb3d_ctx* ctx, const u8* d_hw, i64 h, i64 w, u8* d_wh);
+// The RGB (C == 3) and label (C == 1) forms of an op behind their entries' argument checks (nvox > 0, no null buffer):
+// csrc/carve.hip: part_carve's jobs on a (W,H,D,C) grid -- the fused 90-degree sweep, then the other jobs merged or one by one
+int pb3d_part_carve_jobs(pb3d_ctx* ctx, const u8* d_colored, int C, i64 W, i64 H, i64 D, const u8* d_mask_sub, const u8* d_mask_carve,
+                         const int* job_angle, const int* job_skip, int njobs, u8* d_out);
+// csrc/carve.hip: out[x,y,z,:] = img[y,x,:] where carved[x,y,z] == 1, else 0, for an (H,W,C) image
+int pb3d_image_apply_dev(pb3d_ctx* ctx, const u8* d_carved, i64 W, i64 H, i64 D, const u8* d_img_hwc, int C, u8* d_out);
+// csrc/global.hip: global_carve as ones -> process_voxel_grid -> image apply, with the transposed (W,H) mask already in d_mask_wh
+int pb3d_global_carve_composed(pb3d_ctx* ctx, const u8* d_mask_wh, const u8* d_img_hwc, int C, i64 W, i64 H, i64 D, int angle_interval, u8* d_out);
 int pb3d_part_carve90_planes(pb3d_ctx* ctx, const u8* d_colored, int C, i64 W, i64 H, i64 D, const u32* d_A, const u32* d_AT, int njobs, const u32* d_vbits,
                              int nwv, int c0, int c2, u8* d_out, int* took);
 int pb3d_launch_gc90_stream(pb3d_ctx* ctx, const u8* d_bin_hw, const u8* d_rgb_hw3, int C, const u32* d_vbits, int nw, int c0, i64 W, i64 H, i64 D, i64 x0,

@@ -16,9 +16,9 @@ but not 128, 64), one and three elements for 4- and 8-byte element buffers.
 
 What the kernels need, per pointer argument, from reading them (csrc/ = part-based-3d-reconstruction_amd/csrc/):
 
-  carve_mask        grid / out: k_carve_tiles casts to 16-byte vectors -> only behind the aligned16 test (carve.hip:482); k_carve_flat
+  carve_mask        grid / out: k_carve_tiles casts to 16-byte vectors -> only behind the aligned16 test (carve.hip:508); k_carve_flat
                     uses align-1 vector types, k_carve_bytes bytes.  mask: bytes.
-  occupancy         k_occupancy16 behind carve.hip:510, else the byte kernel.
+  occupancy         k_occupancy16 behind carve.hip:536, else the byte kernel.
   color_apply       carved through align-1 vectors, out through store48_wave (align-1), rgb_hw3 bytes: any base.
   rotate_carve      90 degrees: every form reads through load_piece (align-1); WF / FLAT store aligned 16-byte pieces relative
                     to `out` and are chosen only for a 128-byte aligned out (rotate_tiled.hip:780); WIDE loads and stores aligned
@@ -28,10 +28,11 @@ What the kernels need, per pointer argument, from reading them (csrc/ = part-bas
                     otherwise); rotate_carve then takes the bit-sliced step (0/1 data) or k_rotate_generic (rotate.hip:122-129).
   process_grid      slice pass reads align-1 vectors, un-slice stores align-1; the sliced volume is scratch.  d_tmp: as out.
   global_carve      bin_hw / rgb_hw3 bytes; the colour stream stores align-1 vectors (bits90.hip) or bytes: any slab pointer.
-  part_carve        the 16-voxel forms behind carve.hip:581 (aligned16 of colored | out), else byte kernels; masks bytes.
+  part_carve        the 16-voxel forms behind carve.hip:600 (aligned16 of colored | out), else byte kernels; masks bytes.
   label form        k_rgb_to_label / k_label_to_rgb moved 16-byte vectors through ALIGNED vector types on the caller's pointers
-                    with no test in front: they now use the align-1 type like every other sweep (label.hip).  global_carve_label:
-                    k_label_apply16 behind label.hip:330; part_carve_label: the <16> forms behind :368; orient_label bytes.
+                    with no test in front: they now use the align-1 type like every other sweep (label.hip).  global_carve_label and
+                    part_carve_label: the rows above with one byte per voxel (one apply routine, one job loop for both forms;
+                    k_label_apply16 behind the aligned16 test of carve.hip:690); orient_label bytes.
   orient            k_orient128 behind components.hip:706, k_orient4 (dword casts) behind :716, else k_orient (bytes).
   points count/fill grid: 16-voxel forms behind points.hip:493; d_pts (float aligned) and d_cols (any byte): the wave-private fill
                     derives head and shift from the address (points.hip:336,341).  points_extract refuses a grid that is not
@@ -70,11 +71,11 @@ COMBOS = [(0, 0)] + [c for i, k in enumerate(BYTE_OFFS) for c in ((0, k), (k, 0)
 # ---- the case table: entry -> (test function, rows of (shape, offset argument(s), branch the row is there for)) -----------------
 CASES = {
     "pb3d_carve_mask_dev": ("test_carve_mask", [
-        ("64x9x64 C=1,3", "grid, mask, out", "carve.hip:482 k_carve_tiles <-> k_carve_flat"),
-        ("33x5x37 C=3", "grid, mask, out", "carve.hip:493 k_carve_flat (odd column)"),
-        ("20x7x5 C=1,3", "grid, mask, out", "carve.hip:497 k_carve_bytes (col < 16)")]),
-    "pb3d_occupancy_dev": ("test_occupancy", [("nvox 4096, 4099, 7", "rgb, occ", "carve.hip:510 k_occupancy16 + tail <-> tail only")]),
-    "pb3d_color_apply_dev": ("test_color_apply", [("12x7x32, 12x7x37, 12x7x5", "carved, rgb, out", "carve.hip:535 (no pointer test: align-1 vectors)")]),
+        ("64x9x64 C=1,3", "grid, mask, out", "carve.hip:508 k_carve_tiles <-> k_carve_flat"),
+        ("33x5x37 C=3", "grid, mask, out", "carve.hip:519 k_carve_flat (odd column)"),
+        ("20x7x5 C=1,3", "grid, mask, out", "carve.hip:523 k_carve_bytes (col < 16)")]),
+    "pb3d_occupancy_dev": ("test_occupancy", [("nvox 4096, 4099, 7", "rgb, occ", "carve.hip:536 k_occupancy16 + tail <-> tail only")]),
+    "pb3d_color_apply_dev": ("test_color_apply", [("12x7x32, 12x7x37, 12x7x5", "carved, rgb, out", "carve.hip:686 pb3d_image_apply_dev (no pointer test: align-1 vectors)")]),
     "pb3d_rotate_carve_dev": ("test_rotate90_forms / test_rotate_generic_and_180", [
         ("355x128x355", "in, mask, out", "rotate_tiled.hip:780-781 WF <-> TILE_RAGGED"),
         ("131x256x131", "in, mask, out", "rotate_tiled.hip:780,782 FLAT <-> TILE_RAGGED"),
@@ -89,11 +90,11 @@ CASES = {
     "pb3d_global_carve_dev": ("test_global_carve", [
         ("h 37, w 131 whole", "bin, rgb, out", "bits90.hip colour stream / sliced chain colour stores"),
         ("slabs [5,9) [4,20) [16,131)", "out (slab residue 1, 4, 0 mod 16)", "bits90.hip:303 slab pointer = start of the slab (90); global.hip:47 refusal of a slab at 45")]),
-    "pb3d_part_carve_dev": ("test_part_carve", [("40x24x56, 41x24x56", "colored, masks, out", "carve.hip:581 16-voxel forms <-> byte kernels; rotate_tiled.hip:887 fused 90")]),
-    "pb3d_rgb_to_label_dev": ("test_label_conversions", [("nvox 4096, 4099, 7", "rgb, label", "label.hip:66,87 (align-1 vectors)")]),
-    "pb3d_label_to_rgb_dev": ("test_label_conversions", [("nvox 4096, 4099, 7", "label, rgb", "label.hip:105,123 (align-1 vectors)")]),
-    "pb3d_global_carve_label_dev": ("test_global_carve_label", [("h 37, w 131 at 90 and 45", "bin, label_hw, out", "label.hip:330 k_label_apply16 <-> k_label_apply")]),
-    "pb3d_part_carve_label_dev": ("test_part_carve_label", [("40x24x48 mixed jobs", "label, masks, out", "label.hip:368 <16> <-> <1>")]),
+    "pb3d_part_carve_dev": ("test_part_carve", [("40x24x56, 41x24x56", "colored, masks, out", "carve.hip:600 16-voxel forms <-> byte kernels; rotate_tiled.hip:887 fused 90")]),
+    "pb3d_rgb_to_label_dev": ("test_label_conversions", [("nvox 4096, 4099, 7", "rgb, label", "label.hip:67,88 (align-1 vectors)")]),
+    "pb3d_label_to_rgb_dev": ("test_label_conversions", [("nvox 4096, 4099, 7", "label, rgb", "label.hip:106,124 (align-1 vectors)")]),
+    "pb3d_global_carve_label_dev": ("test_global_carve_label", [("h 37, w 131 at 90 and 45", "bin, label_hw, out", "carve.hip:690 k_label_apply16 <-> k_color_apply_generic<1>")]),
+    "pb3d_part_carve_label_dev": ("test_part_carve_label", [("40x24x48 mixed jobs", "label, masks, out", "carve.hip part_carve_jobs<1>: 16-voxel forms <-> byte kernels; rotate_tiled.hip fused 90")]),
     "pb3d_orient_label_dev": ("test_orient", [("70x5x66", "grid, out", "components.hip:696 (bytes)")]),
     "pb3d_orient_dev": ("test_orient", [
         ("128x3x128", "grid, out", "components.hip:706 k_orient128 <-> :716 k_orient4 <-> k_orient"),

@@ -68,6 +68,16 @@ def main():
         ang2 = (C.c_int * 6)(90, 45, 90, 60, 90, 90)
         rows0["part_carve(4 x 90, 45, 60 deg)"] = (timeit(lambda: L.check(lib.pb3d_part_carve_dev(L.ctx(), C.c_void_p(d_col.ptr), W, H, D, C.c_void_p(d_ms.ptr),
                                                                                                  C.c_void_p(d_mc.ptr), ang2, skip, 6, C.c_void_p(d_pout.ptr))), 5), 6)
+        # the label forms (1 byte per voxel) of the same job lists: d_occ's 0 / 1 bytes are labels 0 and 1, the 0 / 1 mask a label image
+        def part_label(angles, n=6):
+            a, s = (C.c_int * n)(*angles), (C.c_int * n)(*([0] * n))
+            return lambda: L.check(lib.pb3d_part_carve_label_dev(L.ctx(), C.c_void_p(d_occ.ptr), W, H, D, C.c_void_p(d_ms.ptr), C.c_void_p(d_mc.ptr), a, s, n,
+                                                                 C.c_void_p(d_o.ptr)))
+        rows0["part_carve_label(6 x 90 deg)"] = (timeit(part_label([90] * 6), 10), 2)
+        rows0["part_carve_label(4 x 90, 45, 60 deg)"] = (timeit(part_label([90, 45, 90, 60, 90, 90]), 5), 2)
+        rows0["part_carve_label(45, 60 deg)"] = (timeit(part_label([45, 60], 2), 5), 2)
+        rows0["global_carve_label(45)"] = (timeit(lambda: L.check(lib.pb3d_global_carve_label_dev(L.ctx(), C.c_void_p(d_bhw.ptr), C.c_void_p(d_bhw.ptr), H, W, 45,
+                                                                                                 C.c_void_p(d_o.ptr))), 5), 1)
         d_ms.free(); d_mc.free(); d_pout.free()
         rows.update(rows0)
         for name, (ms, bpv) in rows.items():
