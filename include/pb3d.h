@@ -442,6 +442,67 @@ int pb3d_mesh_smooth_resident(pb3d_ctx* ctx, const void* d_verts, int verts_f64,
                               int iterations, double lambda, double mu /* NaN: Laplacian */, const uint8_t* d_fixed /* or NULL */,
                               int fix_boundary, void* d_out /* nv x 3 in the input dtype; may not alias d_verts */);
 
+/* ---- mesh -> grid: exact solid voxelization of a triangle mesh by crossing parity, and the overlap of two grids (csrc/voxelize.hip) ------
+ * The one conversion the other sections lack: a mesh (a CAD model, a smoothed marching-cubes mesh) becomes an occupancy, label or RGB grid
+ * that the carve, paint, points and labelling entries take as it is.  Solid voxelization by crossing parity (Schwarz & Seidel 2010) with a
+ * symbolic tie rule.  There is no upstream text, so the rules below are the specification, and the result is a function of the input
+ * alone, to the bit: the only shared writes are integer XORs of single bits, which commute.
+ *   INPUT      verts: (nv, 3) rows of float32 (verts_f64 = 0) or float64 (1); faces: (nf, 3) rows of int32 (faces_i64 = 0) or int64 (1)
+ *              with entries in [-nv, nv), wrapping as NumPy's do.  Anything else is PB3D_EINDEX; a vertex coordinate that is not finite
+ *              (of any vertex, used or not) is PB3D_EINVAL.  Both are checked on the device in one sweep before any kernel gathers, at the
+ *              price of one host wait, and d_out is untouched when they fail.  Grid n0 x n1 x n2, each >= 1, n0 * n1 * n2 <= 2^31 - 1
+ *              (the labelling entries' limit); nv <= 2^31 - 1, 3 * nf <= 2^31 - 1.  origin[3] finite, voxel_size finite and > 0.
+ *              Voxel (i, j, k) is the SAMPLE POINT origin + voxel_size * (i, j, k); a caller who means cell centres shifts origin by half
+ *              a voxel.
+ *   ARITHMETIC all float64; float32 is widened first, which is exact.  Every product, sum, difference and quotient below is one rounded
+ *              IEEE operation, no FMA.  As for mesh_dist, coordinates must be small enough that no product overflows.
+ *   LATTICE    frame = 0 ("lattice"): L = (v - origin) / voxel_size per axis, the vertex's columns in order (a0, a1, a2).
+ *              frame = 1 ("meshify"): first v' = (depth - v[2], v[1], v[0]), one subtraction, then as above: the inverse of the frame
+ *              pb3d_mesh_fill_dev hands out (its vertices are (a2, a1, A2 - a0)); depth = n2 is right for stride 1, origin 0, voxel_size 1.
+ *   FACE       (A, B, C) in lattice coordinates, rays along a2:
+ *              1. area = (B0-A0)*(C1-A1) - (B1-A1)*(C0-A0); area == 0: the face contributes nothing (two equal projected corners give
+ *                 exactly 0 by this formula).
+ *              2. columns i = max(0, ceil(min(A0,B0,C0))) .. min(n0-1, floor(max(A0,B0,C0))), j likewise on axis 1, both clamped in
+ *                 float64 before the conversion to integer.
+ *              3. each directed edge (P, Q) of (A,B), (B,C), (C,A): flipped = (Q0, Q1) < (P0, P1) lexicographically; lo, hi = its ends in
+ *                 ascending lexicographic order; E = (hi0-lo0)*(j-lo1) - (hi1-lo1)*(i-lo0); pos = (area > 0) != flipped; the edge accepts
+ *                 the column if pos ? E >= 0 : E < 0.  The face crosses the column if all three edges accept it.  The two faces of a
+ *                 shared edge evaluate the same E bit for bit and exactly one of them owns a column on it: the rule is the sample moved
+ *                 by the infinitesimal (-eps^2, +eps), so it is consistent at vertices too, and independent of the faces' winding.
+ *              4. nx = (B1-A1)*(C2-A2) - (B2-A2)*(C1-A1); ny = (B2-A2)*(C0-A0) - (B0-A0)*(C2-A2);
+ *                 z = A2 - (nx*(i-A0) + ny*(j-A1)) / area; k = ceil(z).  k <= n2-1: the crossing flips bit (i, j, max(k, 0)); otherwise
+ *                 (above the grid; also a z that is NaN) it flips the column's overflow bit.
+ *   RESULT     occ[i,j,k] = parity of the crossings of column (i, j) at bits 0 .. k.  A sample exactly on the surface is inside where the
+ *              ray enters and outside where it leaves.  For a closed mesh in exact arithmetic this is the point-in-solid test of the
+ *              displaced samples; for any other input (an open mesh, one that intersects itself, coordinates whose products round) it is
+ *              still exactly this function of the input, and nothing more is claimed.  Every operation above is exact when the lattice
+ *              coordinates are small multiples of a power of two -- half-integer coordinates, marching-cubes output at unit or
+ *              power-of-two voxel_size -- and the round trip voxelize(marching_cubes(mask)) == mask (tests) rests on that.
+ *              Pinned: the box with corners (2,3,1) and (6,7,5), 12 triangles, in a 9 x 10 x 8 grid fills i 3..6, j 3..6, k 1..4.
+ *   OUTPUT     d_out: n0*n1*n2*channels uint8, channels 1 or 3, written whole: inside voxels take value[0 .. channels), outside 0.
+ *   STATS      stats[4] int64 or NULL (not NULL: one more host wait, one download): crossings; occupied voxels; open columns (total
+ *              parity, overflow bit included, is odd: the mesh leaks there or leaves the grid's side); faces with area == 0.
+ * nf = 0 gives an all-zero grid.  PB3D_EINVAL: a grid axis < 1 or too many voxels, origin / voxel_size / depth not finite,
+ * voxel_size <= 0, frame not 0 or 1, channels not 1 or 3.
+ * Two passes over a bit volume of n0 * n1 * (ceil(n2 / 32) + 1) dwords (32 planes per dword, one more dword per column for the overflow
+ * bit).  Crossings: one lane per face computes the set-up once; a face of at most 16 columns is walked by its lane, a wider one is listed
+ * and walked by a workgroup; a crossing is one atomicXor of one bit.  Scan: per column the prefix XOR (shifts inside a dword, a ballot of
+ * the dwords' parities across them), then the bytes along a2 (16 voxels per lane in 16-byte stores when n2 is a multiple of 16 and d_out is
+ * 16-byte aligned, 64 consecutive bytes per store instruction otherwise: only speed depends on it); the same pass counts the occupied
+ * voxels and the open columns.  No floating-point atomics.  Scratch: the bit volume (n2 = 512: 17/128 of a byte per voxel), 4 bytes per face
+ * and 40 bytes of counters.  Knob "voxelize_timing" (pb3d_set_tuning; one more host wait) times the two passes with events:
+ * pb3d_voxelize_last gives the milliseconds of the crossing pass (the bit volume's clear included) and of the scan pass of the last
+ * call, PB3D_EINVAL if it was not timed. */
+int pb3d_voxelize_mesh_resident(pb3d_ctx* ctx, const void* d_verts, int verts_f64, int64_t nv, const void* d_faces, int faces_i64, int64_t nf,
+                                int64_t n0, int64_t n1, int64_t n2, const double origin[3], double voxel_size, int frame, double depth,
+                                int channels, const uint8_t* value /* channels bytes */, uint8_t* d_out /* n0*n1*n2*channels */,
+                                int64_t stats[4] /* or NULL */);
+int pb3d_voxelize_last(pb3d_ctx* ctx, double pass_ms[2]);
+/* Volume overlap of two resident grids of nvox voxels: out = {voxels non-zero in both, in a, in b}, where non-zero means any channel > 0
+ * (_occupancy's reading; channels 1 or 3 per grid, the two may differ).  Exact integers; one sweep and one download (one host wait). */
+int pb3d_grid_overlap_resident(pb3d_ctx* ctx, const uint8_t* d_a, int channels_a, const uint8_t* d_b, int channels_b, int64_t nvox,
+                               int64_t out[3]);
+
 /* ---- density volume of a point cloud, reference utils/eval_helpers.py:178-189 (pointcloud_to_voxel_grid) ---------------------------
  * d_out: grid_size^3 float32, bit for bit the reference's volume for the resident (n, 3) list d_pts (float32 rows, or float64 with
  * pts_f64 = 1; any 4- / 8-byte aligned base):

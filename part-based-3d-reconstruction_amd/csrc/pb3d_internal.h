@@ -222,8 +222,16 @@ enum pb3d_slot : int {
     PB3D_SLOT_SMOOTH_HUBS = 119,
     PB3D_SLOT_SMOOTH_POS_A = 120,
     PB3D_SLOT_SMOOTH_POS_B = 121,
+    // call-local, csrc/voxelize.hip: the bit volume of pb3d_voxelize_mesh_resident (n0 * n1 columns of ceil(n2 / 32) + 1 dwords: 32
+    // planes per dword and the column's overflow bit), the faces too wide for a lane (a counter, then their numbers: nf + 1 u32) and
+    // five 64-bit words: the four stats and the flag of the index / finiteness check in front.  The three counts of
+    // pb3d_grid_overlap_resident have a slot of their own: mesh_grid_iou runs the two back to back
+    PB3D_SLOT_VOXELIZE_BITS = 122,
+    PB3D_SLOT_VOXELIZE_LARGE = 123,
+    PB3D_SLOT_VOXELIZE_COUNTS = 124,
+    PB3D_SLOT_OVERLAP_COUNTS = 125,
 
-    PB3D_SLOT_COUNT = 122
+    PB3D_SLOT_COUNT = 126
 };
 
 // ---- the cell index of the exact nearest-neighbour search (csrc/nn.hip) -----------------------------------
@@ -308,6 +316,10 @@ struct pb3d_ctx {
     // the last pb3d_cluster_points_resident / pb3d_radius_count_resident (csrc/cluster.hip) for pb3d_cluster_last: cells per axis of its
     // index, and with cluster_timing the milliseconds of its passes (index, count, union + flatten, ranks, labels)
     struct ClusterLast { bool valid, timed; float ms[5]; i64 cells[3]; } cluster_last;
+    int tune_voxelize_timing;   // knob "voxelize_timing": 1 = pb3d_voxelize_mesh_resident times its two passes with events (one more host wait)
+    // the last pb3d_voxelize_mesh_resident (csrc/voxelize.hip) for pb3d_voxelize_last: with voxelize_timing the milliseconds of the
+    // crossing pass (bit-volume clear included) and of the scan pass
+    struct VoxelizeLast { bool valid, timed; float ms[2]; } voxelize_last;
     // Growable device scratch slots, named by enum pb3d_slot (no hipMalloc / hipFree per call once warm).
     void* scratch[PB3D_SLOT_COUNT];
     size_t scratch_bytes[PB3D_SLOT_COUNT];

@@ -1,5 +1,5 @@
 """Device-resident timing of every op of the path (M1..M8 of SURVEY.md 8(d), plus the N1/N2 kernels of the notebook-1 chain) on
-synthetic inputs.  Development/measurement tool: python tools/opbench.py [--size 1024] [--shape WxHxD] [--ops M1,M3,...,N2,overlays,ICP,PLANE,MESHD,CLUSTER,DOWNSAMPLE,SMOOTH]; one JSON
+synthetic inputs.  Development/measurement tool: python tools/opbench.py [--size 1024] [--shape WxHxD] [--ops M1,M3,...,N2,overlays,ICP,PLANE,MESHD,CLUSTER,DOWNSAMPLE,SMOOTH,VOXELIZE]; one JSON
 line per op.  Pricing: `alg_B_per_voxel` is SURVEY 8(d)'s algorithmic figure for the sweeps that are EXECUTED (a folded 0-degree step
 moves nothing and is not priced); ops whose intermediates are not bytes (the bit-sliced chains) also carry `moved_B_per_voxel`, the
 bytes that cross the HBM by design, and their `frac_of_8TBs` is computed from THAT (never from bytes that are not moved)."""
@@ -262,6 +262,8 @@ def main():
         downsample(a.reps, res, cpu_ref=not a.no_cpu_ref)
     if "SMOOTH" in ops:
         smooth(a.reps, res, cpu_ref=not a.no_cpu_ref)
+    if "VOXELIZE" in ops:
+        voxelize(a.reps, res, cpu_ref=not a.no_cpu_ref)
     if "MESH" in ops:
         meshify(a.reps, res)
     if "DENS" in ops:
@@ -977,6 +979,60 @@ def smooth(reps, res, cpu_ref=True):
         r["adjacency_equal"] = bool(all(np.array_equal(g, w) for g, w in zip(got_adj, ref_adj)))
         r["taubin10_equal"] = bool(got.tobytes() == ref.tobytes())
     for b in bufs + [d_v, d_f]:
+        b.free()
+    print(json.dumps(r), flush=True)
+    res.append(r)
+
+
+def voxelize(reps, res, cpu_ref=True):
+    """VOXELIZE, voxelize_mesh (csrc/voxelize.hip): the stride-1 mesh of the stored Taj grid (float32 vertices, int32 faces, meshify's frame)
+    back into its 512 x 278 x 512 grid.  Resident, by device events (best mean of reps, the check's host wait inside): the whole call;
+    under knob voxelize_timing the call's own events give the crossing pass (the bit volume's clear included) and the scan pass.  Beside
+    the scan pass the time of a plain fill of the same output bytes (pb3d_dev_memset), the only roof it has; for the crossing pass the
+    crossings per second.  Then whether the bytes equal the grid's occupancy and, with cpu_ref, the restatement of
+    tests/voxelize_restate.py in NumPy on this host and whether the device's bytes equal it."""
+    import voxelize_restate as vr
+    lib, L = pb3d._lib.load(), pb3d._lib
+    taj = np.load(os.path.join(ROOT, "tests", "golden", "stored_Taj_voxel_grid.npz"))["voxel_grid"]
+    shape = taj.shape[:3]
+    nvox = int(np.prod(shape))
+    occ = np.any(taj > 0, axis=-1)
+    v, f = pb3d.meshify_colored_voxel_grid(taj, stride=1)[:2]
+    nv, nf = len(v), len(f)
+    d_v, d_f, d_out = dev.from_numpy(v), dev.from_numpy(f), dev.DeviceBuffer(nvox)
+
+    def call(**kw):
+        return pb3d.voxelize_mesh_resident(d_v, nv, d_f, nf, shape, frame="meshify", out=d_out, **kw)
+
+    def best(fn):
+        return min(timeit(fn, reps, warm=1) for _ in range(2))
+
+    t_all = best(call)
+    t_fill = best(lambda: L.check(lib.pb3d_dev_memset(L.ctx(), C.c_void_p(d_out.ptr), 0, nvox)))
+    L.set_tuning("voxelize_timing", 1)
+    passes = []
+    try:
+        for _ in range(reps + 1):
+            call()
+            pm = (C.c_double * 2)()
+            L.check(lib.pb3d_voxelize_last(L.ctx(), pm))
+            passes.append((pm[0], pm[1]))
+    finally:
+        L.set_tuning("voxelize_timing", 0)
+    t_cross, t_scan = min(p[0] for p in passes[1:]), min(p[1] for p in passes[1:])
+    _, stats = call(return_stats=True)
+    got = d_out.download(shape)
+    r = {"op": "VOXELIZE", "name": "voxelize_mesh: stored Taj, stride-1 mesh back into its grid", "shape": list(shape), "nverts": nv, "nfaces": nf,
+         "ms": round(t_all, 4), "crossing_pass_ms": round(t_cross, 4), "scan_pass_ms": round(t_scan, 4), "fill_of_output_bytes_ms": round(t_fill, 4),
+         "scan_over_fill": round(t_scan / t_fill, 2), "output_GB_s_of_scan": round(nvox / t_scan / 1e6, 1),
+         "Mcrossings_s": round(stats["crossings"] / t_cross / 1e3, 1), **stats,
+         "equals_occupancy": bool(np.array_equal(got, occ.view(np.uint8))), "voxels_differing_from_occupancy": int(np.count_nonzero(got != occ))}
+    if cpu_ref:
+        t0 = time.perf_counter()
+        ref, ref_stats = vr.restate(v, f, shape, frame="meshify")
+        r["numpy_restatement_ms"] = round(1e3 * (time.perf_counter() - t0), 1)
+        r["equals_restatement"] = bool(np.array_equal(got, ref) and stats == ref_stats)
+    for b in (d_v, d_f, d_out):
         b.free()
     print(json.dumps(r), flush=True)
     res.append(r)
