@@ -503,6 +503,62 @@ int pb3d_voxelize_last(pb3d_ctx* ctx, double pass_ms[2]);
 int pb3d_grid_overlap_resident(pb3d_ctx* ctx, const uint8_t* d_a, int channels_a, const uint8_t* d_b, int channels_b, int64_t nvox,
                                int64_t out[3]);
 
+/* ---- grid -> distance: the exact Euclidean distance transform with its feature transform (csrc/edt.hip) ------------------------------
+ * Squared distances on a lattice are integers, so the transform is stated to the bit; there is no upstream text and the rules below are
+ * the specification.  scipy.ndimage.distance_transform_edt(x) equals sqrt((double)sq) of PB3D_EDT_TO_BACKGROUND bit for bit (tests).
+ *   GRID       (n0, n1, n2) voxels of `channels` (1 or 3) uint8 each, every axis in [1, 16384] (so 3 * 16383^2 < 2^31: every squared
+ *              distance fits int32), at most 2^31 - 1 voxels; anything else is PB3D_EINVAL.  A voxel is OCCUPIED when any of its
+ *              channels is non-zero (pb3d_grid_overlap_resident's rule).
+ *   TARGETS    target = PB3D_EDT_TO_BACKGROUND (0): the voxels that are not occupied (SciPy's convention);
+ *              PB3D_EDT_TO_OCCUPIED (1): the occupied voxels;
+ *              PB3D_EDT_TO_SURFACE (2): the occupied voxels with at least one of their 6 neighbours not occupied or outside the grid.
+ *   SQ         d_sq[v] = min over the targets t of (v0-t0)^2 + (v1-t1)^2 + (v2-t2)^2, int32; 0 on a target.  With border_is_target != 0
+ *              the six planes just outside the grid are targets too: sq[v] = min(sq[v], (v_a + 1)^2, (n_a - v_a)^2) over the axes a
+ *              (border_value = 0 of SciPy's morphology).  With no target and no border every sq is PB3D_EDT_NONE = INT32_MAX.
+ *   NONE       PB3D_EDT_NONE never enters a sum: neither widened nor saturated.  A pass tests a partial result for PB3D_EDT_NONE before
+ *              it uses it and leaves such a voxel out of the minimisation (it is no parabola of the envelope); what remains is at most
+ *              3 * 16383^2 and no sum or difference of the passes leaves int32.
+ *   INDEX      d_index[v] (int32, or NULL: not written) = the linear index (t0 * n1 + t1) * n2 + t2 of a nearest target, -1 where sq is
+ *              PB3D_EDT_NONE.  TIE RULE: among the targets at the minimum squared distance, the smallest linear index, which is the
+ *              lexicographic minimum of (t0, t1, t2).  The rule is separable: the row pass (axis 2) gives every voxel (i, j, k) the
+ *              nearest target of its row, the smaller t2 of an equidistant left / right pair, so R(i, j, k) holds, for row (i, j), the
+ *              least (distance, t2).  The axis-1 pass minimises R(i, j', k) + (j - j')^2 over j' and keeps the smallest j' among equal
+ *              totals: a target (t1, t2) of plane i at the plane's minimum distance from (j, k) with the smallest t1 is found at
+ *              j' = t1, and within row t1 the row pass already kept the smallest t2 at that distance.  The axis-0 pass does the same
+ *              with i' and keeps the smallest t0.  So the result is the minimum of (distance, t0, t1, t2) in that order.  SciPy's
+ *              return_indices follows no such rule (tests); it serves only to check that an index is A nearest target.
+ *              d_index with border_is_target != 0 is PB3D_EINVAL: a border plane has no index.
+ *   NO FLOATS  No floating-point operation computes sq or index.  The column passes build the lower envelope of the parabolas
+ *              g(j') + (j - j')^2 with Meijster's integer Sep(i, u) = (u^2 - i^2 + g(u) - g(i)) div (2 (u - i)), i < u: the largest x
+ *              at which parabola i is not above parabola u, so a tie goes to the smaller index.  The numerator is never negative where
+ *              it is evaluated (parabola i is not above u at some x >= 0), so the division is that of non-negative integers.
+ *   STATS      stats (host, or NULL) = {number of target voxels (border planes not counted), the largest sq that is not PB3D_EDT_NONE
+ *              or -1 when there is none}.  Not NULL: one download and one host wait; NULL: the entry only enqueues.
+ * Scratch: 8 bytes per voxel (the other half of the passes' ping-pong and the envelope stacks), 4 more with d_index.
+ *
+ * pb3d_edt_distances_resident: out[v] = sqrt((double)sq[v]) * voxel_size for n values, one correctly rounded square root and one rounded
+ *   product, float64 (out_f64 != 0) or that rounded once more to float32; PB3D_EDT_NONE gives +inf.  voxel_size finite and > 0.
+ * pb3d_edt_apply_resident: mode PB3D_EDT_FILL: an occupied voxel keeps its bytes, an empty one with sq[v] <= r_sq takes the bytes of
+ *   voxel index[v] (d_sq, d_index: PB3D_EDT_TO_OCCUPIED output), every other voxel becomes zero: dilation by the Euclidean ball of
+ *   squared radius r_sq, coloured by the nearest voxel.  mode PB3D_EDT_KEEP: a voxel keeps its bytes when sq[v] > r_sq and becomes zero
+ *   otherwise (d_index unused, may be NULL); with PB3D_EDT_TO_BACKGROUND output this is erosion by the ball.  d_out may be d_grid (FILL
+ *   gathers only from occupied voxels, which keep their bytes).  r_sq >= 0.
+ * pb3d_grid_surface_stats_resident: over the surface voxels v of grid a (PB3D_EDT_TO_SURFACE's rule) with s = d_sq_to_b_surface[v]:
+ *   out = {their number, max s (-1 without a surface voxel), sum of s, and per k < nthr the number with s <= thresholds_sq[k]}.  int64
+ *   atomic max and add only, one per workgroup of a capped grid: independent of order.  0 <= nthr <= 8.  One download, one host wait. */
+#define PB3D_EDT_NONE 2147483647
+#define PB3D_EDT_MAX_AXIS 16384
+enum { PB3D_EDT_TO_BACKGROUND = 0, PB3D_EDT_TO_OCCUPIED = 1, PB3D_EDT_TO_SURFACE = 2 };
+enum { PB3D_EDT_FILL = 0, PB3D_EDT_KEEP = 1 };
+int pb3d_edt_resident(pb3d_ctx* ctx, const uint8_t* d_grid, int channels, int64_t n0, int64_t n1, int64_t n2, int target, int border_is_target,
+                      int32_t* d_sq, int32_t* d_index /* may be NULL */, int64_t* stats /* host, may be NULL: [0] targets, [1] max finite sq or -1 */);
+int pb3d_edt_distances_resident(pb3d_ctx* ctx, const int32_t* d_sq, int64_t n, double voxel_size, int out_f64, void* d_out);
+int pb3d_edt_apply_resident(pb3d_ctx* ctx, const uint8_t* d_grid, int channels, int64_t nvox, const int32_t* d_sq, const int32_t* d_index, int mode,
+                            int64_t r_sq, uint8_t* d_out);
+int pb3d_grid_surface_stats_resident(pb3d_ctx* ctx, const uint8_t* d_a, int channels_a, int64_t n0, int64_t n1, int64_t n2,
+                                     const int32_t* d_sq_to_b_surface, const int64_t* thresholds_sq, int nthr /* <= 8 */,
+                                     int64_t* out /* host: [0] surface voxels of a, [1] max sq, [2] sum sq, [3+k] #(sq <= thresholds_sq[k]) */);
+
 /* ---- density volume of a point cloud, reference utils/eval_helpers.py:178-189 (pointcloud_to_voxel_grid) ---------------------------
  * d_out: grid_size^3 float32, bit for bit the reference's volume for the resident (n, 3) list d_pts (float32 rows, or float64 with
  * pts_f64 = 1; any 4- / 8-byte aligned base):

@@ -230,8 +230,16 @@ enum pb3d_slot : int {
     PB3D_SLOT_VOXELIZE_LARGE = 123,
     PB3D_SLOT_VOXELIZE_COUNTS = 124,
     PB3D_SLOT_OVERLAP_COUNTS = 125,
+    // call-local, csrc/edt.hip: the other half of the passes' ping-pong (the axis-1 pass writes it, the axis-0 pass reads it: one int32
+    // per voxel for sq, one more for the partial index when d_index is given), the g values of the envelope stacks (one int32 per
+    // voxel, level l of a column at the column's l-th voxel) and the counters (pb3d_edt_resident: targets, max sq + 1;
+    // pb3d_grid_surface_stats_resident: its 3 + 8 words)
+    PB3D_SLOT_EDT_SQ_TMP = 126,
+    PB3D_SLOT_EDT_INDEX_TMP = 127,
+    PB3D_SLOT_EDT_STACK = 128,
+    PB3D_SLOT_EDT_COUNTS = 129,
 
-    PB3D_SLOT_COUNT = 126
+    PB3D_SLOT_COUNT = 130
 };
 
 // ---- the cell index of the exact nearest-neighbour search (csrc/nn.hip) -----------------------------------

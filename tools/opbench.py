@@ -1,5 +1,5 @@
 """Device-resident timing of every op of the path (M1..M8 of SURVEY.md 8(d), plus the N1/N2 kernels of the notebook-1 chain) on
-synthetic inputs.  Development/measurement tool: python tools/opbench.py [--size 1024] [--shape WxHxD] [--ops M1,M3,...,N2,overlays,ICP,PLANE,MESHD,CLUSTER,DOWNSAMPLE,SMOOTH,VOXELIZE]; one JSON
+synthetic inputs.  Development/measurement tool: python tools/opbench.py [--size 1024] [--shape WxHxD] [--ops M1,M3,...,N2,overlays,ICP,PLANE,MESHD,CLUSTER,DOWNSAMPLE,SMOOTH,VOXELIZE,EDT]; one JSON
 line per op.  Pricing: `alg_B_per_voxel` is SURVEY 8(d)'s algorithmic figure for the sweeps that are EXECUTED (a folded 0-degree step
 moves nothing and is not priced); ops whose intermediates are not bytes (the bit-sliced chains) also carry `moved_B_per_voxel`, the
 bytes that cross the HBM by design, and their `frac_of_8TBs` is computed from THAT (never from bytes that are not moved)."""
@@ -264,6 +264,8 @@ def main():
         smooth(a.reps, res, cpu_ref=not a.no_cpu_ref)
     if "VOXELIZE" in ops:
         voxelize(a.reps, res, cpu_ref=not a.no_cpu_ref)
+    if "EDT" in ops:
+        edt(a.reps, res, cpu_ref=not a.no_cpu_ref)
     if "MESH" in ops:
         meshify(a.reps, res)
     if "DENS" in ops:
@@ -1036,6 +1038,96 @@ def voxelize(reps, res, cpu_ref=True):
         b.free()
     print(json.dumps(r), flush=True)
     res.append(r)
+
+
+def edt(reps, res, cpu_ref=True):
+    """EDT, distance_transform (csrc/edt.hip) on the stored Taj grid (512 x 278 x 512 RGB), resident, by device events (best mean of reps):
+    to="background" without and with indices, to="surface", close_grid at radius 2, and grid_surface_metrics of the grid against
+    voxelize_mesh of its own smoothed mesh (wall clock: it has four host waits).  Then to="background" on two adversarial contents of
+    the same shape and channel count: a full grid with one empty corner voxel (one target: the longest distances, every column's
+    envelope a single parabola found late) and a 3-D checkerboard (every other voxel a parabola vertex), with their ratio to the Taj
+    content.  Yardsticks: the time a plain device copy (pb3d_d2d) needs for the bytes the three passes must move -- the grid's bytes and
+    4 (sq) or 8 (sq and index) bytes per voxel written by every pass and read by the next -- from the rate of a copy of 4 bytes per
+    voxel; and, with cpu_ref, scipy.ndimage.distance_transform_edt of the same occupancy on this host's CPU (and whether the device's
+    distances equal it bit for bit)."""
+    import scipy.ndimage as ndi
+    import pb3d.distance as pd
+    lib, L = pb3d._lib.load(), pb3d._lib
+    taj = np.ascontiguousarray(np.load(os.path.join(ROOT, "tests", "golden", "stored_Taj_voxel_grid.npz"))["voxel_grid"])
+    shape, ch = taj.shape[:3], taj.shape[3]
+    nvox = int(np.prod(shape))
+    d_grid, d_sq, d_ix, d_tmp = dev.from_numpy(taj), dev.DeviceBuffer(4 * nvox), dev.DeviceBuffer(4 * nvox), dev.DeviceBuffer(4 * nvox)
+
+    def best(fn):
+        return min(timeit(fn, reps, warm=1) for _ in range(2))
+
+    def transform(target, index, grid=None):
+        L.check(lib.pb3d_edt_resident(L.ctx(), C.c_void_p((grid or d_grid).ptr), ch, *shape, target, 0, C.c_void_p(d_sq.ptr),
+                                      C.c_void_p(d_ix.ptr) if index else None, None))
+
+    t_copy = best(lambda: L.check(lib.pb3d_d2d(L.ctx(), C.c_void_p(d_tmp.ptr), C.c_void_p(d_sq.ptr), 4 * nvox)))
+    copy_GB_s = 8 * nvox / t_copy / 1e6                   # a copy of n bytes moves 2 n
+    moved = {False: ch + 4 + 8 + 8, True: ch + 8 + 16 + 16}  # bytes per voxel the three passes read and write, without / with index
+
+    def row(name, ms, index):
+        yard = moved[index] * nvox / copy_GB_s / 1e6
+        return {name + "_ms": round(ms, 4), name + "_copy_yardstick_ms": round(yard, 4), name + "_over_copy": round(ms / yard, 2)}
+
+    r = {"op": "EDT", "name": "distance_transform: stored Taj grid, resident", "shape": list(shape), "channels": ch,
+         "copy_GB_s": round(copy_GB_s, 1), "moved_B_per_voxel": [moved[False], moved[True]]}
+    t_bg = best(lambda: transform(0, False))
+    r.update(row("background", t_bg, False))
+    r.update(row("background_indices", best(lambda: transform(0, True)), True))
+    r.update(row("surface", best(lambda: transform(2, False)), False))
+    g = dev.DeviceGrid(d_grid, taj.shape)
+    out = dev.DeviceGrid(dev.DeviceBuffer(nvox * ch), taj.shape)
+    r["close_radius2_ms"] = round(best(lambda: pb3d.close_grid_resident(g, 2, out=out)), 4)
+    v, f = pb3d.meshify_colored_voxel_grid(taj, stride=1)[:2]
+    vs = pb3d.smooth_mesh(v, f)
+    d_v, d_f = dev.from_numpy(vs), dev.from_numpy(f)
+    d_m = pb3d.voxelize_mesh_resident(d_v, len(vs), d_f, len(f), shape, frame="meshify")
+    gm = dev.DeviceGrid(d_m, shape)
+    walls = []
+    for _ in range(reps + 1):
+        dev.sync()
+        t0 = time.perf_counter()
+        m = pb3d.grid_surface_metrics(g, gm, thresholds=(1.0, 2.0))
+        walls.append(1e3 * (time.perf_counter() - t0))
+    r["surface_metrics_vs_smoothed_mesh_wall_ms"] = round(min(walls[1:]), 3)
+    r["surface_metrics"] = m
+    transform(0, False)
+    got = d_sq.download(shape, np.int32)
+    if cpu_ref:
+        occ = np.any(taj > 0, axis=-1)
+        t0 = time.perf_counter()
+        ref = ndi.distance_transform_edt(occ)
+        r["scipy_edt_ms"] = round(1e3 * (time.perf_counter() - t0), 1)
+        r["scipy_over_device"] = round(r["scipy_edt_ms"] / t_bg, 1)
+        r["equals_scipy_bitwise"] = bool(np.array_equal(np.sqrt(got.astype(np.float64)), ref))
+    print(json.dumps(r), flush=True)
+    res.append(r)
+    adversarial = {"full_but_one_corner": np.ones(shape, bool), "checkerboard": np.indices(shape).sum(axis=0) % 2 == 0}
+    adversarial["full_but_one_corner"][0, 0, 0] = False
+    for name, occ in adversarial.items():
+        d_a = dev.from_numpy(np.repeat(occ.view(np.uint8)[..., None], ch, axis=-1))
+        ra = {"op": "EDT", "name": "distance_transform: adversarial content " + name, "shape": list(shape), "channels": ch}
+        for index in (False, True):
+            key = "background_indices" if index else "background"
+            ms = best(lambda: transform(0, index, d_a))
+            ra.update(row(key, ms, index))
+            ra[key + "_over_taj"] = round(ms / r[key + "_ms"], 2)
+        if cpu_ref:
+            transform(0, False, d_a)
+            got = d_sq.download(shape, np.int32)
+            t0 = time.perf_counter()
+            ref = ndi.distance_transform_edt(occ)
+            ra["scipy_edt_ms"] = round(1e3 * (time.perf_counter() - t0), 1)
+            ra["equals_scipy_bitwise"] = bool(np.array_equal(np.sqrt(got.astype(np.float64)), ref))
+        d_a.free()
+        print(json.dumps(ra), flush=True)
+        res.append(ra)
+    for b in (d_grid, d_sq, d_ix, d_tmp, out, d_v, d_f, d_m):
+        b.free()
 
 
 def meshify(reps, res):
