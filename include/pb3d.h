@@ -559,6 +559,82 @@ int pb3d_grid_surface_stats_resident(pb3d_ctx* ctx, const uint8_t* d_a, int chan
                                      const int32_t* d_sq_to_b_surface, const int64_t* thresholds_sq, int nthr /* <= 8 */,
                                      int64_t* out /* host: [0] surface voxels of a, [1] max sq, [2] sum sq, [3+k] #(sq <= thresholds_sq[k]) */);
 
+/* ---- mesh -> image: depth, face and colour images of a triangle mesh under a pinhole camera (csrc/render.hip) --------------------------
+ * The pair the other sections lack: a mesh (the smoothed marching-cubes mesh, a CAD model) seen by the camera the projection entries use,
+ * as a z-buffer, a face image and a part-colour image that pb3d_partwise_iou_dev and the carve entries take as they are.  There is no
+ * upstream text, so the rules below are the specification, and the result is a function of the input alone, to the bit: the only shared
+ * writes are integer minima, which commute.  The ray test is Woop, Benthin and Wald 2013 ("Watertight ray/triangle intersection")
+ * without their float fallback, because everything here is already double.
+ *   ARITHMETIC all float64; float32 input is widened first, which is exact.  Every product, sum, difference and quotient below is one
+ *              correctly rounded IEEE operation, no FMA (the build has -ffp-contract=off on host and device).
+ *   INPUT      verts: (nv, 3) rows of float32 (verts_f64 = 0) or float64 (1); faces: (nf, 3) rows of int32 (faces_i64 = 0) or int64 (1)
+ *              with entries in [-nv, nv), those in [-nv, -1] wrapping as NumPy's do.  Any other index is PB3D_EINDEX; a vertex (used or
+ *              not) with a coordinate that is not finite is PB3D_EINVAL.  Both are checked on the device before any kernel gathers
+ *              through the indices: the call's one host wait besides the job count below, and no output is written when they fail.
+ *              Limits: nv, nf <= 2^31 - 1; Himg, Wimg > 0, Himg * Wimg <= 2^31 - 1; f finite and > 0; cx, cy, cam, R finite; near
+ *              finite and > 0; frame 0 or 1 (depth finite with 1); d_depth not NULL and 8-byte aligned.  Anything else is PB3D_EINVAL
+ *              before any device work.
+ *   FRAME      frame = 0 ("points"): p = v, the (x, y, z) frame pb3d_project_dev sees, where voxel (a0, a1, a2) is (a2, a1, a0).
+ *              frame = 1 ("meshify"): p = (v0, v1, depth - v2), one subtraction: the inverse of the frame pb3d_mesh_fill_dev hands out
+ *              (its vertices are (a2, a1, A2 - a0); depth = A2), the convention of pb3d_voxelize_mesh_resident's frame = 1.
+ *   CAMERA     R[9] row-major, rows x, y, z (the host's look_at_rotation taken in float64); cam[3], f, cx, cy float64.  Once per vertex:
+ *              q = p - cam; X = (R0*q0 + R1*q1) + R2*q2; Y = (R3*q0 + R4*q1) + R5*q2; Z = (R6*q0 + R7*q1) + R8*q2.
+ *   PIXEL      (u, v) integers, 0 <= u < Wimg, 0 <= v < Himg.  The pixel's ray goes through its integer centre, the pixel
+ *              pb3d_project_dev rounds to: sx = ((double)u - cx) / f; sy = -(((double)v - cy) / f).
+ *   FACE against PIXEL, corners a, b, c with camera coordinates (Xa, Ya, Za) ...:
+ *              sheared corners xa = Xa - sx*Za, ya = Ya - sy*Za (a product, then a difference), b and c likewise;
+ *              U = xc*yb - yc*xb; V = xa*yc - ya*xc; W = xb*ya - yb*xa; det = (U + V) + W; T = (U*Za + V*Zb) + W*Zc; t = T / det.
+ *              The face HITS the pixel iff it is not the case that some of U, V, W is < 0 while another is > 0, and det != 0, and
+ *              t >= near, every comparison IEEE (a NaN fails t >= near).  Both windings hit: no culling by orientation.
+ *   RESULT     each pixel takes the hitting face with the smallest (t as computed, face number), compared lexicographically.
+ *              depth[v,u] = that t as float64, +inf when nothing hits; face[v,u] = its number as int32, -1 when nothing hits;
+ *              bary[v,u] = (U/det, V/det, W/det) of that face, (0, 0, 0) when nothing hits.  t is the camera-space Z of the hit, the
+ *              quantity the z-buffers (pb3d_depth_buffer_dev, pb3d_grid_depth_buffer_dev) store.
+ *   SHADE      a pass of its own (pb3d_render_shade_resident) on face and bary, a per-vertex attribute of C = 1 or 3 bytes and a
+ *              background of C bytes: the corner m is the first of (a, b, c) with the largest weight -- a later corner replaces an
+ *              earlier one only if its weight is strictly larger -- and image[v,u] = attr[faces[face][m]], the background where
+ *              face is -1.  No blending: part colours and labels stay part colours and labels.  The pass only enqueues; a face
+ *              number outside [0, nf) or a corner index outside [-nv, nv) is never followed, the pixel takes the background.
+ * Two properties the tests lean on:
+ *   SHARED EDGES  The value on an edge (U for edge b-c, V for c-a, W for a-b) is computed from the same two sheared vertices in both
+ *              faces that share the edge, so it is the same number up to sign (a*b - c*d and c*d - a*b round to negatives of each
+ *              other), and the zero case is inclusive: a ray cannot pass between two faces that share an edge, and a ray exactly on
+ *              the edge hits both.  A closed mesh is hit an even number of times by a ray from outside.
+ *   NO CLIPPING   A face that crosses the camera plane needs no clipping step: the test is on the ray's line, and t >= near discards
+ *              what lies behind.
+ *   PRUNE      A face is tested only against the pixels of a box, by exactly these rules (h = near / 2, exact):
+ *              1. all three Z < h: the face is dropped.  Where U, V, W do not disagree in sign, the computed t is a quotient of
+ *                 same-signed sums bounded by the largest Z up to a few roundings, far below the factor 2, so it cannot reach near.
+ *              2. all three Z >= h: the box of the projected corners px = (X/Z)*f + cx, py = (-(Y/Z))*f + cy, from floor(min) - 1 to
+ *                 ceil(max) + 1, clamped to the image; a face whose box misses the image is dropped.  With every Z positive the sheared
+ *                 corners are Z/f times the pixel offsets, and the sign of a computed U, V or W is the sign of the exact one or zero
+ *                 (rounding is monotone), so a pixel a whole pixel outside the corners' box sees them disagree.
+ *              3. otherwise (corners on both sides of h, or a NaN among the projected corners): the whole image.  Rare, and correct.
+ *              Every double -> int conversion of a box edge happens after the clamp to the image in double: a corner at Z = h projects
+ *              to about 1e12 pixels, and converting that, or a NaN, directly is undefined.
+ * Passes: camera coordinates and the check in one sweep (24 bytes of scratch per vertex); one lane per face classifies, walks a box of at
+ * most 64 pixels itself and counts 8 x 8-pixel tile jobs for any other face; pb3d_scan_counts gives the job offsets, whose total (with
+ * the three face counts) is the second host wait; one wavefront per (face, tile) job, one pixel per lane, finds its face by a binary
+ * search of the offsets -- a triangle that fills the image is thousands of independent jobs, never one loop.  Depth: atomicMin on the
+ * uint64 pattern of t (t >= near > 0, so the patterns order as the doubles do) into d_depth, pre-filled with the pattern of +inf.  Face:
+ * the same walk again, a face whose t equals the pixel's depth bit for bit does atomicMin on its number into d_face, pre-filled with
+ * 0xffffffff; skipped when neither d_face nor d_bary is asked for.  Resolve (d_bary only): one lane per pixel recomputes U, V, W of the
+ * winner.  No floating-point atomics.  Scratch: 24 bytes per vertex, 16 per face (jobs 4, offsets 8, scan 4 and a little), 4 per pixel
+ * when d_face is NULL and d_bary is not.
+ * pb3d_render_last: of the last completed pb3d_render_mesh_resident of the context, {faces dropped by PRUNE 1 or 2, faces on the small
+ * path, faces on the large path, tile jobs}.  Knob "render_timing" (pb3d_set_tuning; one more host wait) times the passes with events:
+ * pb3d_render_last_ms gives the milliseconds of {small-path depth with the classification, the scan and its wait; tile depth;
+ * small-path face; tile face; resolve} of a call with nf > 0 and a face or bary image, PB3D_EINVAL if the last call was not timed. */
+int pb3d_render_mesh_resident(pb3d_ctx* ctx, const void* d_verts, int verts_f64, int64_t nv, const void* d_faces, int faces_i64, int64_t nf,
+                              int frame, double depth, const double R[9], const double cam[3], double f, double cx, double cy, int Himg,
+                              int Wimg, double near, double* d_depth /* Himg*Wimg */, int32_t* d_face /* Himg*Wimg, or NULL */,
+                              double* d_bary /* Himg*Wimg*3, or NULL */);
+int pb3d_render_shade_resident(pb3d_ctx* ctx, const int32_t* d_face, const double* d_bary, int64_t npix, const void* d_faces, int faces_i64,
+                               int64_t nf, int64_t nv, const uint8_t* d_attr /* nv*C */, int C, const uint8_t* bg /* host, C bytes */,
+                               uint8_t* d_image /* npix*C */);
+int pb3d_render_last(const pb3d_ctx* ctx, int64_t stats[4]);
+int pb3d_render_last_ms(const pb3d_ctx* ctx, double pass_ms[5]);
+
 /* ---- density volume of a point cloud, reference utils/eval_helpers.py:178-189 (pointcloud_to_voxel_grid) ---------------------------
  * d_out: grid_size^3 float32, bit for bit the reference's volume for the resident (n, 3) list d_pts (float32 rows, or float64 with
  * pts_f64 = 1; any 4- / 8-byte aligned base):

@@ -238,8 +238,19 @@ enum pb3d_slot : int {
     PB3D_SLOT_EDT_INDEX_TMP = 127,
     PB3D_SLOT_EDT_STACK = 128,
     PB3D_SLOT_EDT_COUNTS = 129,
+    // call-local, csrc/render.hip: the camera coordinates of pb3d_render_mesh_resident (24 bytes per vertex), four 64-bit words (faces
+    // pruned, on the small path, on the large path; then the flag of the index / finiteness check, later the tile-job total), the
+    // winner image when the caller gave no d_face (one u32 per pixel), the tile jobs per face (nf u32), their offsets (nf + 1 int64)
+    // and the two slots of that pb3d_scan_counts
+    PB3D_SLOT_RENDER_CAMERA = 130,
+    PB3D_SLOT_RENDER_COUNTS = 131,
+    PB3D_SLOT_RENDER_WINNER = 132,
+    PB3D_SLOT_RENDER_JOBS = 133,
+    PB3D_SLOT_RENDER_OFFSETS = 134,
+    PB3D_SLOT_RENDER_SCAN_LOCAL = 135,
+    PB3D_SLOT_RENDER_SCAN_SEGS = 136,
 
-    PB3D_SLOT_COUNT = 130
+    PB3D_SLOT_COUNT = 137
 };
 
 // ---- the cell index of the exact nearest-neighbour search (csrc/nn.hip) -----------------------------------
@@ -328,6 +339,10 @@ struct pb3d_ctx {
     // the last pb3d_voxelize_mesh_resident (csrc/voxelize.hip) for pb3d_voxelize_last: with voxelize_timing the milliseconds of the
     // crossing pass (bit-volume clear included) and of the scan pass
     struct VoxelizeLast { bool valid, timed; float ms[2]; } voxelize_last;
+    int tune_render_timing;     // knob "render_timing": 1 = pb3d_render_mesh_resident times its passes with events (one more host wait)
+    // the last pb3d_render_mesh_resident (csrc/render.hip) for pb3d_render_last: faces pruned, on the small path, on the large path and
+    // tile jobs; with render_timing the milliseconds of its passes (faces depth + scan, tiles depth, faces face, tiles face, resolve)
+    struct RenderLast { bool valid, timed; float ms[5]; i64 stats[4]; } render_last;
     // Growable device scratch slots, named by enum pb3d_slot (no hipMalloc / hipFree per call once warm).
     void* scratch[PB3D_SLOT_COUNT];
     size_t scratch_bytes[PB3D_SLOT_COUNT];

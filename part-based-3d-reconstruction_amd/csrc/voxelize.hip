@@ -21,6 +21,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "group_sum.h"
 #include "mesh_index.h"
 #include "pb3d_internal.h"
 
@@ -124,26 +125,6 @@ __device__ __forceinline__ u32 cross_column(const Face& f, int i, int j, const V
         atomicXor(col + (v.W - 1), 1u);         // above the grid (or no height at all: a NaN compares false)
     }
     return 1;
-}
-
-__device__ __forceinline__ u64 wave_sum(u64 c) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d);
-    return c;
-}
-
-// *dst += the sum of c over a 256-thread workgroup, by one atomic (every thread of the workgroup calls it).  One per workgroup of a
-// capped grid, not one per wavefront: tens of thousands of atomics on one address were what the passes waited for
-__device__ __forceinline__ void group_add(u64 c, u64* dst) {
-    __shared__ u64 part[4];
-    c = wave_sum(c);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const u64 t = (part[0] + part[1]) + (part[2] + part[3]);
-        if (t) atomicAdd((unsigned long long*)dst, (unsigned long long)t);
-    }
-    __syncthreads();
 }
 
 // stats: crossings, occupied, open columns, flat faces.  large[0] = listed faces (zeroed before), large[1 ...] = their numbers, in

@@ -38,6 +38,7 @@ from .voxelize import grid_overlap_counts, grid_overlap_counts_resident, mesh_gr
 from .distance import (close_grid, close_grid_resident, dilate_grid, dilate_grid_resident, distance_transform,  # noqa: F401
                        distance_transform_resident, erode_grid, erode_grid_resident, grid_surface_metrics, grid_surface_metrics_resident,
                        open_grid, open_grid_resident)
+from .render import mesh_projection_iou, render_mesh, render_mesh_resident, render_shade_resident  # noqa: F401
 from .eval_helpers_intra import (color_presence, compute_binary_gt, compute_global_depth_buffer, grid_depth_buffer, grid_visible_bits,  # noqa: F401
                                  points_visible_bits, project_part_visible, run_minaret_iou_evaluation, run_minaret_kp_evaluation,
                                  run_part_minaret_binary_iou)

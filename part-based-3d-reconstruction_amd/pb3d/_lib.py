@@ -185,6 +185,11 @@ _SIGNATURES = {
     "pb3d_edt_distances_resident": [vp, vp, i64, C.c_double, C.c_int, vp],
     "pb3d_edt_apply_resident": [vp, vp, C.c_int, i64, vp, vp, C.c_int, i64, vp],
     "pb3d_grid_surface_stats_resident": [vp, vp, C.c_int, i64, i64, i64, vp, i64p, C.c_int, i64p],
+    "pb3d_render_mesh_resident": [vp, vp, C.c_int, i64, vp, C.c_int, i64, C.c_int, C.c_double, dblp, dblp, C.c_double, C.c_double, C.c_double,
+                                  C.c_int, C.c_int, C.c_double, vp, vp, vp],
+    "pb3d_render_shade_resident": [vp, vp, vp, i64, vp, C.c_int, i64, i64, vp, C.c_int, u8p, vp],
+    "pb3d_render_last": [vp, i64p],
+    "pb3d_render_last_ms": [vp, dblp],
 }
 class IouRow(C.Structure):
     """pb3d_iou_row (include/pb3d.h)"""

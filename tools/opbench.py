@@ -1,5 +1,5 @@
 """Device-resident timing of every op of the path (M1..M8 of SURVEY.md 8(d), plus the N1/N2 kernels of the notebook-1 chain) on
-synthetic inputs.  Development/measurement tool: python tools/opbench.py [--size 1024] [--shape WxHxD] [--ops M1,M3,...,N2,overlays,ICP,PLANE,MESHD,CLUSTER,DOWNSAMPLE,SMOOTH,VOXELIZE,EDT]; one JSON
+synthetic inputs.  Development/measurement tool: python tools/opbench.py [--size 1024] [--shape WxHxD] [--ops M1,M3,...,N2,overlays,ICP,PLANE,MESHD,CLUSTER,DOWNSAMPLE,SMOOTH,VOXELIZE,EDT,RENDER]; one JSON
 line per op.  Pricing: `alg_B_per_voxel` is SURVEY 8(d)'s algorithmic figure for the sweeps that are EXECUTED (a folded 0-degree step
 moves nothing and is not priced); ops whose intermediates are not bytes (the bit-sliced chains) also carry `moved_B_per_voxel`, the
 bytes that cross the HBM by design, and their `frac_of_8TBs` is computed from THAT (never from bytes that are not moved)."""
@@ -266,6 +266,8 @@ def main():
         voxelize(a.reps, res, cpu_ref=not a.no_cpu_ref)
     if "EDT" in ops:
         edt(a.reps, res, cpu_ref=not a.no_cpu_ref)
+    if "RENDER" in ops:
+        render(a.reps, res, cpu_ref=not a.no_cpu_ref)
     if "MESH" in ops:
         meshify(a.reps, res)
     if "DENS" in ops:
@@ -1128,6 +1130,108 @@ def edt(reps, res, cpu_ref=True):
         res.append(ra)
     for b in (d_grid, d_sq, d_ix, d_tmp, out, d_v, d_f, d_m):
         b.free()
+
+
+def render(reps, res, cpu_ref=True):
+    """RENDER, render_mesh (csrc/render.hip), resident, by device events (best mean of reps, the two host waits inside).  (a) The
+    stride-1 mesh of the stored Taj grid as pb3d.device.meshify(download=False) hands it out (float32 vertices, int32 faces,
+    nearest-voxel bytes, meshify's frame) under the stored final front camera at the size of that camera's mask: depth, face and colour
+    image; depth alone; and under knob render_timing the call's own events per pass.  (b) One triangle that fills a 1024 x 768 image.
+    (c) For context: a plain fill (pb3d_dev_memset) of 20 bytes per pixel (the depth image written twice, by the pre-fill and by the
+    walk, and the face image once) and of the 36 of all three images (8 + 4 + 24), the grid-direct z-buffer of the same grid under the same camera, and with
+    cpu_ref the NumPy restatement of tests/render_restate.py on a 64 x 48 crop of (a) on this host, and whether the device's crop equals it."""
+    import render_restate as rr
+    import pb3d.eval_helpers_intra as ev
+    import pb3d.render as rd
+    lib, L = pb3d._lib.load(), pb3d._lib
+    g = os.path.join(ROOT, "tests", "golden")
+    taj = np.ascontiguousarray(np.load(os.path.join(g, "stored_Taj_voxel_grid.npz"))["voxel_grid"])
+    cam = ev.load_camera_json(os.path.join(g, "stored_Taj_camera_params_final.json"), "front")
+    H, W = ev.resize_mask_to_voxel_grid(ev.load_mask(os.path.join(g, "data_Taj_front_mask.png")), taj).shape[:2]
+    d_g = dev.from_numpy(taj)
+    (dv, df, dn, dc), (nv, nf) = dev.meshify(d_g, taj.shape, stride=1, download=False)
+    view = (cam["cam_pos"], cam["target"], cam["f"], cam["cx"], cam["cy"])
+
+    def best(fn):
+        return min(timeit(fn, reps, warm=1) for _ in range(2))
+
+    def free(bufs):
+        for b in bufs:
+            b.free()
+
+    def taj_call(colors=True, **kw):
+        return rd.render_mesh_resident(dv, nv, df, nf, *view, H, W, dc if colors else None, 3, frame="meshify", depth=taj.shape[2], **kw)
+
+    def passes(fn):
+        L.set_tuning("render_timing", 1)
+        rows = []
+        try:
+            for _ in range(reps + 1):
+                free(fn())
+                pm = (C.c_double * 5)()
+                L.check(lib.pb3d_render_last_ms(L.ctx(), pm))
+                rows.append(list(pm))
+        finally:
+            L.set_tuning("render_timing", 0)
+        return dict(zip(("faces_depth_scan_wait_ms", "tiles_depth_ms", "faces_face_ms", "tiles_face_ms", "resolve_ms"),
+                        (round(min(r[k] for r in rows[1:]), 4) for k in range(5))))
+
+    def fill_ms(npix, bytes_per_pixel):
+        d = dev.DeviceBuffer(npix * bytes_per_pixel)
+        t = best(lambda: L.check(lib.pb3d_dev_memset(L.ctx(), C.c_void_p(d.ptr), 0, d.nbytes)))
+        d.free()
+        return round(t, 4)
+
+    r = {"op": "RENDER", "name": "render_mesh: stored Taj, stride-1 mesh, final front camera", "image": [H, W], "nverts": int(nv), "nfaces": int(nf),
+         "depth_face_image_ms": round(best(lambda: free(taj_call())), 4), "depth_face_ms": round(best(lambda: free(taj_call(False))), 4),
+         **passes(lambda: taj_call(False, return_bary=True)), **rd.render_last(), "fill_20B_per_pixel_ms": fill_ms(H * W, 20),
+         "fill_36B_per_pixel_ms": fill_ms(H * W, 36)}
+    d_z = dev.DeviceBuffer(H * W * 4)
+    r["grid_zbuffer_ms"] = round(best(lambda: ev.depth_buffer_resident(d_g, taj.shape, cam, H, W, out=d_z)), 4)
+    res_d = taj_call()
+    depth, face = res_d[0].download((H, W), np.float64), res_d[1].download((H, W), np.int32)
+    free(res_d)
+    zb = d_z.download((H, W), np.float32)
+    both = np.isfinite(depth) & np.isfinite(zb)
+    r.update(covered_pixels=int((face >= 0).sum()), zbuffer_pixels=int(np.isfinite(zb).sum()), covered_by_both=int(both.sum()),
+             max_abs_depth_minus_zbuffer=round(float(np.abs(depth[both] - zb[both]).max()), 4))
+    if cpu_ref:
+        y0, x0 = int(np.argmax((face >= 0).any(axis=1))) + 40, W // 2 - 32        # a 64 x 48 window on the monument
+        v, f = dv.download((nv, 3), np.float32), df.download((nf, 3), np.int32)
+        R, c = rr.look_at(cam["cam_pos"], cam["target"])
+        t0 = time.perf_counter()
+        ref = rr.restate(v, f, R, c, cam["f"], cam["cx"] - x0, cam["cy"] - y0, 48, 64, frame=1, depth=float(taj.shape[2]))
+        r["numpy_restatement_64x48_crop_ms"] = round(1e3 * (time.perf_counter() - t0), 1)
+        crop = rd.render_mesh_resident(dv, nv, df, nf, cam["cam_pos"], cam["target"], cam["f"], cam["cx"] - x0, cam["cy"] - y0, 48, 64,
+                                       frame="meshify", depth=taj.shape[2], return_bary=True)
+        got = (crop[0].download((48, 64), np.float64), crop[1].download((48, 64), np.int32), crop[2].download((48, 64, 3), np.float64))
+        free(crop)
+        r["crop_covered_pixels"] = int((ref[1] >= 0).sum())
+        r["crop_equals_restatement"] = bool(np.array_equal(rr.bits(got[0]), rr.bits(ref[0])) and np.array_equal(got[1], ref[1])
+                                            and np.array_equal(got[2], ref[2]))
+    print(json.dumps(r), flush=True)
+    res.append(r)
+    free((d_g, dv, df, dn, dc, d_z))
+
+    Hb, Wb = 768, 1024
+    tri = np.array([(-3.0, 3.0, 1.0), (9.0, 3.0, 1.0), (-3.0, -9.0, 1.0)], np.float32)       # covers u in [0, 1024), v in [0, 768) at f = 512
+    d_t, d_i = dev.from_numpy(tri), dev.from_numpy(np.array([(0, 1, 2)], np.int32))
+    d_c = dev.from_numpy(np.array([(255, 0, 0), (0, 255, 0), (0, 0, 255)], np.uint8))
+    origin = ((0.0, 0.0, 0.0), (0.0, 0.0, 1.0), 512.0, 511.5, 383.5)
+
+    def tri_call(colors=True, **kw):
+        return rd.render_mesh_resident(d_t, 3, d_i, 1, *origin, Hb, Wb, d_c if colors else None, 3, **kw)
+
+    rb = {"op": "RENDER", "name": "render_mesh: one triangle filling the image", "image": [Hb, Wb], "nverts": 3, "nfaces": 1,
+          "depth_face_image_ms": round(best(lambda: free(tri_call())), 4), "depth_face_ms": round(best(lambda: free(tri_call(False))), 4),
+          **passes(lambda: tri_call(False, return_bary=True)), **rd.render_last(), "fill_20B_per_pixel_ms": fill_ms(Hb * Wb, 20),
+          "fill_36B_per_pixel_ms": fill_ms(Hb * Wb, 36)}
+    out = tri_call(False)
+    rb["covered_pixels"] = int((out[1].download((Hb, Wb), np.int32) == 0).sum())
+    free(out)
+    free((d_t, d_i, d_c))
+    print(json.dumps(rb), flush=True)
+    res.append(rb)
 
 
 def meshify(reps, res):
