@@ -5,7 +5,9 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, device as dev, eval_helpers_intra as ev, projection_utils
+from ._args import _cam, _colour_table, _grid, _on_device
+from ._lib import _ptr
 from .minarets import (extract_minaret_kps_for_view, extract_minaret_masks_by_label, extract_minaret_voxels_by_label,  # noqa: F401
                        extract_top_bottom_image_points, extract_top_bottom_voxel_points)
 
@@ -58,7 +60,6 @@ class CameraObjective:
     """
 
     def __init__(self, voxel_pts, voxel_colors, seg_img, selected_labels):
-        from . import device as dev
         from .projection_utils import points_f64
         self._dev = dev
         pts = np.asarray(voxel_pts)
@@ -77,10 +78,12 @@ class CameraObjective:
         self._colors = np.ascontiguousarray(np.array([selected_labels[k] for k in self.names], np.uint8).reshape(-1, 3))
         if len(self._colors) > 32:
             raise ValueError("at most 32 parts")
-        self._d_pts = dev.from_numpy(self._pts_host) if self.n else None
-        self._d_cols = dev.from_numpy(cols) if self.n else None
-        self._d_seg = dev.from_numpy(seg)
-        self._d_img = dev.DeviceBuffer(self.H * self.W * 3)
+        with dev.Scope() as sc:         # (all four or none: close() frees them)
+            self._d_pts, self._d_cols = sc.upload(self._pts_host), sc.upload(cols)
+            self._d_seg = sc.upload(seg) or sc.alloc(0)
+            self._d_img = sc.alloc(self.H * self.W * 3)
+            for b in (self._d_pts, self._d_cols, self._d_seg, self._d_img):
+                sc.keep(b)
 
     def __call__(self, p):
         from .projection_utils import camera_args
@@ -108,7 +111,6 @@ class CameraObjective:
         (the random / coordinate stages of the aligner evaluate dozens of cameras around the current one).  Exactly the values
         of the one-at-a-time path: the same point kernel per camera, the same integer counts, the same float64 mean."""
         from .camera_geometry import look_at_rotation_batch
-        from .projection_utils import _promotion_flags
         params = list(params)
         K = len(params)
         if K == 0:
@@ -132,7 +134,7 @@ class CameraObjective:
                 _, _, R, cam, prec = camera_args(np.zeros((1, 3), self._pts_dtype), p["cam_pos"], p["target"], p["f"], p["cx"], p["cy"])
                 cams["R"][k] = R.reshape(9); cams["cam"][k] = cam; t0s.append(int(prec[0]))
         for k, p in enumerate(params):
-            cams["prec"][k] = _promotion_flags(t0s[k], p["f"], p["cx"], p["cy"])
+            cams["prec"][k] = projection_utils._promotion_flags(t0s[k], p["f"], p["cx"], p["cy"])
             cams["f"][k] = float(p["f"]); cams["cx"][k] = float(p["cx"]); cams["cy"][k] = float(p["cy"])
         P = len(self._colors)
         inter = np.zeros((K, P), np.int64); uni = np.zeros((K, P), np.int64)
@@ -164,18 +166,16 @@ def projection_iou_by_part(voxel_grid, part_colors, image, cam_params):
     part its points are extracted, projected with the camera and compared with the part's pixels of `image`; the
     combined binary IoU compares the union of the projections with every non-background pixel.
     Returns ({part: IoU}, combined_binary_IoU).  The grid is uploaded once and all parts are processed on the device."""
-    from . import device as dev
     from .projection_utils import camera_args
     grid = _lib.as_u8(voxel_grid, "voxel_grid")
     img = _lib.as_u8(image, "image")
     H, W = img.shape[:2]
     A0, A1, A2 = grid.shape[:3]
     lib, ctx = _lib.load(), _lib.ctx()
-    d_grid = dev.from_numpy(grid); d_img = dev.from_numpy(img); d_proj = dev.DeviceBuffer(H * W * 3)
-    bufs = [d_grid, d_img, d_proj]
     per = {}
     union_prj = np.zeros((H, W), bool)
-    try:
+    with dev.Scope() as sc:
+        d_grid = sc.upload(grid) or sc.alloc(0); d_img = sc.upload(img) or sc.alloc(0); d_proj = sc.alloc(H * W * 3)
         _, _, R, cam, prec = camera_args(np.zeros((1, 3), np.float32), cam_params["cam_pos"], cam_params["target"], cam_params["f"],
                                          cam_params["cx"], cam_params["cy"])
         for part, color in part_colors.items():
@@ -187,8 +187,8 @@ def projection_iou_by_part(voxel_grid, part_colors, image, cam_params):
             _lib.check(lib.pb3d_points_count_dev(ctx, C.c_void_p(d_grid.ptr), A0, A1, A2, 3, _lib.p_u8(c8), 1, 1, C.byref(n)))
             if n.value == 0:
                 continue
-            d_pts = dev.DeviceBuffer(n.value * 12); d_pc = dev.DeviceBuffer(n.value * 3)
-            try:
+            with dev.Scope() as part_sc:
+                d_pts = part_sc.alloc(n.value * 12); d_pc = part_sc.alloc(n.value * 3)
                 _lib.check(lib.pb3d_points_fill_dev(ctx, C.c_void_p(d_grid.ptr), A0, A1, A2, 3, _lib.p_u8(c8), 1, 1, n.value,
                                                     C.c_void_p(d_pts.ptr), C.c_void_p(d_pc.ptr)))
                 _lib.check(lib.pb3d_project_dev(ctx, C.c_void_p(d_pts.ptr), 0, C.c_void_p(d_pc.ptr), n.value, _lib.p_dbl(R), _lib.p_dbl(cam),
@@ -199,15 +199,10 @@ def projection_iou_by_part(voxel_grid, part_colors, image, cam_params):
                                                      inter.ctypes.data_as(_lib.i64p), uni.ctypes.data_as(_lib.i64p)))
                 per[part] = (inter[0] / uni[0]) if uni[0] > 0 else 0.0
                 union_prj |= np.all(d_proj.download((H, W, 3)) == c8, axis=-1)
-            finally:
-                d_pts.free(); d_pc.free()
         bg = np.array(part_colors.get("background", (0, 0, 0)), dtype=np.uint8)
         gt = np.any(img != bg, axis=-1)
         u = np.logical_or(gt, union_prj).sum()
         return per, ((np.logical_and(gt, union_prj).sum() / u) if u > 0 else 0.0)
-    finally:
-        for b in bufs:
-            b.free()
 
 
 # =====================================================================================================
@@ -312,17 +307,14 @@ def grid_bounds(voxel_grid, colors=None):
     """(count, lo, hi): the number of voxels whose colour (RGB grid) or label ((A0,A1,A2) grid) is in `colors` (None or empty: any
     non-zero voxel; at most 31, none of them zero) and their inclusive int64 bounds (a0, a1, a2) -- np.where(mask) reduced on the
     device in one read of the grid (pb3d_grid_bounds_resident).  count 0: lo and hi are None."""
-    from . import device as dev
-    from . import eval_helpers_intra as ev
-    d_g, shape, owned = ev._grid(voxel_grid)
+    g, shape = _grid(voxel_grid)
     A0, A1, A2, Cc = shape
-    tab = ev._colour_table(colors if colors is not None else [], Cc)
-    d_o = dev.DeviceBuffer(7 * 8)
-    try:
-        _lib.check(_lib.load().pb3d_grid_bounds_resident(_lib.ctx(), ev._ptr(d_g), A0, A1, A2, Cc, _lib.p_u8(tab), len(tab), C.c_void_p(d_o.ptr)))
+    with dev.Scope() as sc:
+        d_g = _on_device(sc, g)
+        tab = _colour_table(colors if colors is not None else [], Cc)
+        d_o = sc.alloc(7 * 8)
+        _lib.check(_lib.load().pb3d_grid_bounds_resident(_lib.ctx(), _ptr(d_g), A0, A1, A2, Cc, _lib.p_u8(tab), len(tab), C.c_void_p(d_o.ptr)))
         out = d_o.download((7,), np.int64)
-    finally:
-        ev._free(d_o, d_g if owned else None)
     if out[0] == 0:
         return 0, None, None
     return int(out[0]), out[1:4].copy(), out[4:7].copy()
@@ -330,29 +322,24 @@ def grid_bounds(voxel_grid, colors=None):
 
 def hit_bits_resident(d_grid, shape, colors, cam_params, H, W, out=None):
     """pb3d_grid_hit_bits_resident into a (H, W) uint32 image: `out` (a DeviceBuffer or a ctypes pointer into one) or a new DeviceBuffer"""
-    from . import device as dev
-    from . import eval_helpers_intra as ev
     A0, A1, A2, Cc = shape
-    R, cp, prec = ev._cam(cam_params, np.float32)
-    tab = ev._colour_table(colors, Cc)
-    d_b = out if out is not None else dev.DeviceBuffer(max(1, int(H) * int(W)) * 4)
-    _lib.check(_lib.load().pb3d_grid_hit_bits_resident(_lib.ctx(), ev._ptr(d_grid), A0, A1, A2, Cc, _lib.p_u8(tab), len(tab), _lib.p_dbl(R),
-                                                  _lib.p_dbl(cp), float(cam_params["f"]), float(cam_params["cx"]), float(cam_params["cy"]),
-                                                  prec, int(H), int(W), d_b if isinstance(d_b, C.c_void_p) else C.c_void_p(d_b.ptr)))
-    return d_b
+    R, cp, prec = _cam(cam_params, np.float32)
+    tab = _colour_table(colors, Cc)
+    with dev.Scope() as sc:
+        d_b = sc.result(out, max(1, int(H) * int(W)) * 4)
+        _lib.check(_lib.load().pb3d_grid_hit_bits_resident(_lib.ctx(), _ptr(d_grid), A0, A1, A2, Cc, _lib.p_u8(tab), len(tab), _lib.p_dbl(R),
+                                                           _lib.p_dbl(cp), float(cam_params["f"]), float(cam_params["cx"]), float(cam_params["cy"]),
+                                                           prec, int(H), int(W), _ptr(d_b)))
+        return d_b
 
 
 def grid_hit_bits(voxel_grid, colors, cam_params, H, W):
     """(H, W) uint32: bit k = some voxel of colors[k] (at most 31) projects onto the pixel, i.e.
     np.all(project_colored_voxels(*get_voxel_points_by_parts(grid, .., [part k]), ...) == colors[k], axis=-1) for every k in one sweep"""
-    from . import eval_helpers_intra as ev
-    d_g, shape, owned = ev._grid(voxel_grid)
-    d_b = None
-    try:
-        d_b = hit_bits_resident(d_g, shape, colors, cam_params, H, W)
+    g, shape = _grid(voxel_grid)
+    with dev.Scope() as sc:
+        d_b = sc.adopt(hit_bits_resident(_on_device(sc, g), shape, colors, cam_params, H, W))
         return d_b.download((int(H), int(W)), np.uint32)
-    finally:
-        ev._free(d_b, d_g if owned else None)
 
 
 def bbox_init_from_bounds(lo, hi, img_bbox_min, img_bbox_max, H_img, W_img, fov_deg=30):
@@ -474,11 +461,9 @@ def _outline_host(vis, gt, prj):
 
 def _overlays(voxel_grid, part_colors, image, cam_params, mode):
     """[(part or None, title, vis, iou)] of projection_overlays"""
-    from . import device as dev
-    from . import eval_helpers_intra as ev
-    d_g, shape, owned = ev._grid(voxel_grid)
-    bufs = [d_g] if owned else []
-    try:
+    g, shape = _grid(voxel_grid)
+    with dev.Scope() as sc:
+        d_g = _on_device(sc, g)
         if shape[3] != 3:
             raise ValueError("voxel_grid must be (A0,A1,A2,3) RGB")
         img = _lib.as_u8(image, "image")
@@ -496,8 +481,8 @@ def _overlays(voxel_grid, part_colors, image, cam_params, mode):
                 continue                                    # never equals a uint8 voxel: no points upstream
             (cand if np.any(c != 0) else black).append((part, np.ascontiguousarray(c.astype(np.uint8))))
         live = []
-        d_present = dev.DeviceBuffer(8); bufs.append(d_present)
-        d_bm = dev.DeviceBuffer(_lib.PRESENCE_BYTES); bufs.append(d_bm)
+        d_present = sc.alloc(8)
+        d_bm = sc.alloc(_lib.PRESENCE_BYTES)
         for s in range(0, len(cand), _SWEEP):
             chunk = cand[s:s + _SWEEP]
             ev.presence_resident(d_g, shape, [c for _, c in chunk], d_present, out=d_bm)
@@ -523,26 +508,25 @@ def _overlays(voxel_grid, part_colors, image, cam_params, mode):
         if len(live) > 8 * _SWEEP:
             raise ValueError(f"at most {8 * _SWEEP} parts with voxels")
         nplanes = (len(live) + _SWEEP - 1) // _SWEEP
-        d_bits = dev.DeviceBuffer(max(1, nplanes * npix) * 4); bufs.append(d_bits)
+        d_bits = sc.alloc(max(1, nplanes * npix) * 4)
         for s in range(nplanes):
             hit_bits_resident(d_g, shape, [c for _, c in live[s * _SWEEP:(s + 1) * _SWEEP]], cam_params, H, W, out=d_bits.at(s * npix * 4))
-        d_img = dev.from_numpy(img) if npix else dev.DeviceBuffer(1)
-        bufs.append(d_img)
+        d_img = sc.upload(img) or sc.alloc(1)
         tab = np.ascontiguousarray(np.array([c for _, c in live], np.uint8).reshape(-1, 3))
         bg = np.array(part_colors.get("background", (0, 0, 0)), dtype=np.uint8)
         m = OVERLAY_MODES[mode]
         nimg = len(live) if m == 0 else 1
         ncnt = 2 * len(live) if m == 0 else 2
-        d_vis = dev.DeviceBuffer(max(1, nimg * npix * 3)); bufs.append(d_vis)
-        d_cnt = dev.DeviceBuffer(max(1, ncnt) * 8); bufs.append(d_cnt)
+        d_vis = sc.alloc(max(1, nimg * npix * 3))
+        d_cnt = sc.alloc(max(1, ncnt) * 8)
         d_extra = None
         if m == 1 and host:
             extra = np.zeros((H, W), bool)
             for _, _, prj in host.values():
                 extra |= prj
-            d_extra = dev.from_numpy(extra.view(np.uint8)); bufs.append(d_extra)
+            d_extra = sc.upload(extra.view(np.uint8))
         _lib.check(_lib.load().pb3d_overlay_compose_resident(_lib.ctx(), C.c_void_p(d_bits.ptr), nplanes, C.c_void_p(d_img.ptr), H, W, _lib.p_u8(tab),
-                                                        len(live), _lib.p_u8(bg), ev._ptr(d_extra), m, C.c_void_p(d_vis.ptr),
+                                                        len(live), _lib.p_u8(bg), _ptr(d_extra), m, C.c_void_p(d_vis.ptr),
                                                         C.c_void_p(d_cnt.ptr)))
         vis = d_vis.download((nimg, H, W, 3)) if nimg else np.zeros((0, H, W, 3), np.uint8)
         cnt = d_cnt.download((max(1, ncnt),), np.int64)
@@ -556,8 +540,6 @@ def _overlays(voxel_grid, part_colors, image, cam_params, mode):
             v = _outline_host((0.7 * proj + 0.3 * img).astype(np.uint8), gt, prj)
             done[part] = (v, _iou(np.logical_and(gt, prj).sum(), np.logical_or(gt, prj).sum()))
         return [(part, f"{part} | IoU: {done[part][1]:.3f}", done[part][0], done[part][1]) for part in part_colors if part in done]
-    finally:
-        ev._free(*bufs)
 
 
 def projection_overlays(voxel_grid, part_colors, image, cam_params, mode):

@@ -18,21 +18,12 @@ import math
 
 import numpy as np
 
-from . import _lib
+from . import _lib, device as dev
+from ._args import MAX_POINTS, _count, _finite_cloud, _sized_cloud  # noqa: F401
 from ._lib import _ptr
 
 __all__ = ["radius_neighbor_counts", "radius_neighbor_counts_resident", "cluster_points", "cluster_points_resident", "select_points",
            "select_points_resident", "keep_largest_clusters", "keep_largest_clusters_resident"]
-
-MAX_POINTS = 2 ** 31 - 1
-
-
-def _count(n):
-    n = int(n)
-    if not 0 <= n <= MAX_POINTS:
-        raise ValueError(f"a point list holds at most 2^31 - 1 points (got {n})")
-    return n
-
 
 def _eps(eps):
     e = float(eps)
@@ -47,75 +38,43 @@ def _at_least_one(v, name):
     return int(v)
 
 
-def _cloud(points):
-    """(contiguous (n, 3) float32 / float64 array, f64 flag) of a finite cloud; the size is checked on the shape, before any copy"""
-    from .eval_helpers import _cloud as cloud
-    shape = np.shape(points)
-    if len(shape) == 2 and shape[1] == 3:
-        _count(shape[0])
-    p, pf = cloud(points, "points")
-    if not np.isfinite(p).all():
-        raise ValueError("Input points contains NaN or infinity.")
-    return p, pf
-
-
 # ---- resident forms ----------------------------------------------------------------------------------------------------------------------
 def radius_neighbor_counts_resident(d_P, n, eps, f64=True, out=None):
     """pb3d_radius_count_resident: a DeviceBuffer of n uint32 -- for every point of the resident (n, 3) list (float64 rows, or float32
     with f64 False; finite) the number of points within eps of it, itself included"""
-    from . import device as dev
     n, eps = _count(n), _eps(eps)
-    d_out = out if out is not None else dev.DeviceBuffer(max(1, n) * 4)
-    try:
+    with dev.Scope() as sc:
+        d_out = sc.result(out, max(1, n) * 4)
         _lib.check(_lib.load().pb3d_radius_count_resident(_lib.ctx(), _ptr(d_P), int(bool(f64)), n, eps, _ptr(d_out)))
-    except BaseException:
-        if out is None:
-            d_out.free()
-        raise
-    return d_out
+        return d_out
 
 
 def cluster_points_resident(d_P, n, eps, min_samples, f64=True):
     """pb3d_cluster_points_resident: (d_labels, d_core, d_counts, d_sizes, nclusters) -- DeviceBuffers of n int32 labels (-1 = noise),
     n core bytes (0 / 1), n uint32 neighbour counts and int64 cluster sizes (the first nclusters of n entries are written).  The
     number of clusters is the call's one download.  The caller frees the four buffers."""
-    from . import device as dev
     n, eps, min_samples = _count(n), _eps(eps), _at_least_one(min_samples, "min_samples")
-    bufs = [dev.DeviceBuffer(max(1, n) * w) for w in (4, 1, 4, 8)]
     nc = C.c_int64(0)
-    try:
+    with dev.Scope() as sc:
+        bufs = [sc.result(None, max(1, n) * w) for w in (4, 1, 4, 8)]
         _lib.check(_lib.load().pb3d_cluster_points_resident(_lib.ctx(), _ptr(d_P), int(bool(f64)), n, eps, min_samples, _ptr(bufs[0]),
                                                             _ptr(bufs[1]), _ptr(bufs[2]), _ptr(bufs[3]), C.byref(nc)))
-    except BaseException:
-        for b in bufs:
-            b.free()
-        raise
-    return bufs[0], bufs[1], bufs[2], bufs[3], int(nc.value)
+        return bufs[0], bufs[1], bufs[2], bufs[3], int(nc.value)
 
 
 def select_points_resident(d_P, n, d_keep, f64=True, out=None, index=None):
     """pb3d_points_select_resident: (d_out, d_idx, count) -- the rows of the resident (n, 3) list whose byte in d_keep (n bytes on the
     device) is not 0, in their order and dtype, at the front of d_out (n rows), and their positions in the input at the front of d_idx
     (n int32).  Both are allocated unless given.  The count is downloaded (the one host wait)."""
-    from . import device as dev
     n = _count(n)
     row = 24 if f64 else 12
-    d_out = out if out is not None else dev.DeviceBuffer(max(1, n) * row)
-    d_idx = index if index is not None else dev.DeviceBuffer(max(1, n) * 4)
-    d_count = dev.DeviceBuffer(8)
-    try:
+    with dev.Scope() as sc:
+        d_out = sc.result(out, max(1, n) * row)
+        d_idx = sc.result(index, max(1, n) * 4)
+        d_count = sc.alloc(8)
         _lib.check(_lib.load().pb3d_points_select_resident(_lib.ctx(), _ptr(d_P), int(bool(f64)), n, _ptr(d_keep), _ptr(d_out), _ptr(d_idx),
                                                            _ptr(d_count)))
-        count = int(d_count.download((1,), np.int64)[0])
-    except BaseException:
-        if out is None:
-            d_out.free()
-        if index is None:
-            d_idx.free()
-        raise
-    finally:
-        d_count.free()
-    return d_out, d_idx, count
+        return d_out, d_idx, int(d_count.download((1,), np.int64)[0])
 
 
 def _largest(sizes, k):
@@ -128,69 +87,51 @@ def _largest(sizes, k):
 def keep_largest_clusters_resident(d_P, n, eps, min_samples, k=1, f64=True):
     """cluster_points_resident, the k largest sizes picked on the host (ties to the lower label), and select_points_resident on the
     device's flags `label is one of them`: (d_out, d_idx, count, chosen labels).  Only the sizes and two counts leave the device."""
-    from . import device as dev
     k = _at_least_one(k, "k")
     n = _count(n)
-    d_lab, d_core, d_cnt, d_sizes, nc = cluster_points_resident(d_P, n, eps, min_samples, f64)
-    d_keep = None
-    try:
+    with dev.Scope() as sc:
+        *bufs, nc = cluster_points_resident(d_P, n, eps, min_samples, f64)
+        d_lab, _, _, d_sizes = sc.adopt(bufs)
         sizes = d_sizes.download((nc,), np.int64) if nc else np.zeros(0, np.int64)
         chosen = _largest(sizes, k)
         table = np.zeros(max(1, nc), np.uint8)
         table[chosen] = 1
-        d_keep = dev.DeviceBuffer(max(1, n))
+        d_keep = sc.alloc(max(1, n))
         _lib.check(_lib.load().pb3d_labels_member_resident(_lib.ctx(), _ptr(d_lab), n, _lib.p_u8(table), nc, _ptr(d_keep)))
         d_out, d_idx, count = select_points_resident(d_P, n, d_keep, f64)
         return d_out, d_idx, count, chosen
-    finally:
-        for b in (d_lab, d_core, d_cnt, d_sizes, d_keep):
-            if b is not None:
-                b.free()
 
 
 # ---- NumPy forms ------------------------------------------------------------------------------------------------------------------------
 def radius_neighbor_counts(points, eps):
     """int64 (n,): the number of points within eps of each point, itself included (d2 <= eps*eps as in the module text).  Radius outlier
     removal is points[radius_neighbor_counts(points, eps) >= m]."""
-    from . import device as dev
     eps = _eps(eps)
-    p, pf = _cloud(points)
+    p, pf = _finite_cloud(points)
     n = len(p)
     if n == 0:
         return np.zeros(0, np.int64)
-    d_p = dev.from_numpy(p)
-    d_out = None
-    try:
-        d_out = radius_neighbor_counts_resident(d_p, n, eps, pf)
+    with dev.Scope() as sc:
+        d_out = sc.adopt(radius_neighbor_counts_resident(sc.upload(p), n, eps, pf))
         return d_out.download((n,), np.uint32).astype(np.int64)
-    finally:
-        d_p.free()
-        if d_out is not None:
-            d_out.free()
 
 
 def cluster_points(points, eps, min_samples):
     """(labels int64 (n,), core bool (n,), counts int64 (n,), sizes int64 (clusters,)): DBSCAN of an (n, 3) cloud, float32 (widened) or
     any other real dtype (as float64).  labels == sklearn.cluster.DBSCAN(eps=eps, min_samples=min_samples).fit(points).labels_."""
-    from . import device as dev
     eps, min_samples = _eps(eps), _at_least_one(min_samples, "min_samples")
-    p, pf = _cloud(points)
+    p, pf = _finite_cloud(points)
     n = len(p)
     if n == 0:
         return np.zeros(0, np.int64), np.zeros(0, bool), np.zeros(0, np.int64), np.zeros(0, np.int64)
-    d_p = dev.from_numpy(p)
-    bufs = ()
-    try:
-        *bufs, nc = cluster_points_resident(d_p, n, eps, min_samples, pf)
+    with dev.Scope() as sc:
+        *bufs, nc = cluster_points_resident(sc.upload(p), n, eps, min_samples, pf)
+        sc.adopt(bufs)
         labels = bufs[0].download((n,), np.int32).astype(np.int64)
         core = bufs[1].download((n,), np.uint8) != 0
         counts = bufs[2].download((n,), np.uint32).astype(np.int64)
         sizes = bufs[3].download((nc,), np.int64).copy() if nc else np.zeros(0, np.int64)
         return labels, core, counts, sizes
-    finally:
-        d_p.free()
-        for b in bufs:
-            b.free()
 
 
 def _keep_flags(keep, n):
@@ -203,25 +144,15 @@ def _keep_flags(keep, n):
 def select_points(points, keep):
     """(points[keep != 0], np.flatnonzero(keep)) compacted on the device, in input order; float32 clouds stay float32, other real
     dtypes become float64.  keep: one boolean or integer per point."""
-    from . import device as dev
-    from .eval_helpers import _cloud as cloud
-    shape = np.shape(points)
-    if len(shape) == 2 and shape[1] == 3:
-        _count(shape[0])
-    p, pf = cloud(points, "points")
+    p, pf = _sized_cloud(points)
     n = len(p)
     flags = _keep_flags(keep, n)
     if n == 0:
         return p.copy(), np.zeros(0, np.intp)
-    d_p, d_k = dev.from_numpy(p), dev.from_numpy(flags)
-    d_out = d_idx = None
-    try:
-        d_out, d_idx, count = select_points_resident(d_p, n, d_k, pf)
+    with dev.Scope() as sc:
+        d_out, d_idx, count = select_points_resident(sc.upload(p), n, sc.upload(flags), pf)
+        sc.adopt((d_out, d_idx))
         return _download_selection(d_out, d_idx, count, p.dtype)
-    finally:
-        for b in (d_p, d_k, d_out, d_idx):
-            if b is not None:
-                b.free()
 
 
 def _download_selection(d_out, d_idx, count, dtype):
@@ -233,19 +164,13 @@ def _download_selection(d_out, d_idx, count, dtype):
 def keep_largest_clusters(points, eps, min_samples, k=1, return_index=False):
     """The points of the k largest DBSCAN clusters (core and border points; ties in size go to the lower label; all clusters when k
     exceeds their number), in input order.  return_index=True: (kept, their positions in the input)."""
-    from . import device as dev
     eps, min_samples, k = _eps(eps), _at_least_one(min_samples, "min_samples"), _at_least_one(k, "k")
-    p, pf = _cloud(points)
+    p, pf = _finite_cloud(points)
     n = len(p)
     if n == 0:
         return (p.copy(), np.zeros(0, np.intp)) if return_index else p.copy()
-    d_p = dev.from_numpy(p)
-    d_out = d_idx = None
-    try:
-        d_out, d_idx, count, _ = keep_largest_clusters_resident(d_p, n, eps, min_samples, k, pf)
+    with dev.Scope() as sc:
+        d_out, d_idx, count, _ = keep_largest_clusters_resident(sc.upload(p), n, eps, min_samples, k, pf)
+        sc.adopt((d_out, d_idx))
         out, idx = _download_selection(d_out, d_idx, count, p.dtype)
         return (out, idx) if return_index else out
-    finally:
-        for b in (d_p, d_out, d_idx):
-            if b is not None:
-                b.free()

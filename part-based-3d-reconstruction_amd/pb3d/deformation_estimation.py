@@ -10,7 +10,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, device as dev
 from .camera_estimation import compute_partwise_iou
 from .projection_utils import project_colored_voxels
 from .voxel_utils import get_voxel_points_by_parts
@@ -76,7 +76,6 @@ def evaluate_part_deform_batch(voxel_grid, part_labels, part, deforms, image, ca
     resident and ONE pair of launches for the whole list.  Returns (ious, nvalid): ious[k] is the float the one-at-a-time
     path returns; nvalid[k] == 0 marks tuples whose deformed voxels all leave the grid (upstream prints a notice and has no
     IoU; the entry is 0.0)."""
-    from . import device as dev
     from .camera_estimation import CameraObjective
     from .projection_utils import camera_args
     grid = _lib.as_u8(voxel_grid, "voxel_grid")
@@ -100,14 +99,12 @@ def evaluate_part_deform_batch(voxel_grid, part_labels, part, deforms, image, ca
     c["cy"][0] = float(cam_params["cy"]); c["prec"][0] = list(prec)
     color = np.ascontiguousarray(np.asarray(part_labels[part]).astype(np.uint8))
     inter = np.zeros(K, np.int64); uni = np.zeros(K, np.int64); nvalid = np.zeros(K, np.int64)
-    d_pts = dev.from_numpy(coords); d_img = dev.from_numpy(img)
-    try:
+    with dev.Scope() as sc:
+        d_pts = sc.upload(coords); d_img = sc.upload(img) or sc.alloc(0)
         _lib.check(_lib.load().pb3d_deform_iou_batch_dev(_lib.ctx(), C.c_void_p(d_pts.ptr), len(coords), _lib.p_dbl(d5), K, A0, A1, A2,
                                                          c.ctypes.data_as(C.c_void_p), H, W, C.c_void_p(d_img.ptr), _lib.p_u8(color),
                                                          inter.ctypes.data_as(_lib.i64p), uni.ctypes.data_as(_lib.i64p),
                                                          nvalid.ctypes.data_as(_lib.i64p)))
-    finally:
-        d_pts.free(); d_img.free()
     return [float(i / u) if (u > 0 and v > 0) else 0.0 for i, u, v in zip(inter, uni, nvalid)], nvalid
 
 
@@ -115,15 +112,14 @@ def build_deformed_grid(voxel_grid, part_labels, saved_params, image_shape):
     """Every saved part painted into a zero grid, in part_labels order (save_deformed_grid, :288-313).
     A part's points all carry the part colour, so the grid[z,y,x] = colour assignment is done by one
     device kernel per part straight from the jittered evaluation (no sort / dedup needed)."""
-    from . import device as dev
     grid = _lib.as_u8(voxel_grid, "voxel_grid")
     if grid.ndim != 4 or grid.shape[3] != 3:
         raise ValueError("voxel_grid must be (A0,A1,A2,3)")
     A0, A1, A2 = grid.shape[:3]
     lib, ctx = _lib.load(), _lib.ctx()
-    d_out = dev.DeviceBuffer(grid.size)
-    d_out.zero()
-    try:
+    with dev.Scope() as sc:
+        d_out = sc.alloc(grid.size)
+        d_out.zero()
         for part in part_labels:
             if part not in saved_params:
                 continue
@@ -131,12 +127,10 @@ def build_deformed_grid(voxel_grid, part_labels, saved_params, image_shape):
             if len(coords) == 0:
                 continue
             sxz, sy, kx, ky, kz = _scalars(image_shape, (A0, A1, A2), saved_params[part]["deform"])
-            d_pts = dev.from_numpy(coords)
+            d_pts = sc.upload(coords)
             rgb = np.ascontiguousarray(colors[0], np.uint8)
             _lib.check(lib.pb3d_deform_paint_dev(ctx, C.c_void_p(d_pts.ptr), len(coords), sxz, sy, kx, ky, kz, A0, A1, A2,
                                                  _lib.p_u8(rgb), C.c_void_p(d_out.ptr)))
             dev.sync()
-            d_pts.free()
+            sc.free(d_pts)
         return d_out.download(grid.shape)
-    finally:
-        d_out.free()

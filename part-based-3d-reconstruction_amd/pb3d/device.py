@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import _hostmem, _lib
+from ._lib import _ptr
 
 
 class DeviceBuffer:
@@ -104,6 +105,68 @@ def from_numpy_async(array):
     return DeviceBuffer(a.nbytes).upload_async(a)
 
 
+class Scope:
+    """Owner of a wrapper's temporary device buffers: `with Scope() as sc:` frees on exit, newest first, whatever upload(), alloc()
+    and adopt() handed out and neither keep() nor free() took back -- with or without an exception in flight.  result() is a resident
+    form's output: the caller's `out`, else a new buffer that survives a normal exit and is freed when an exception leaves the scope.
+    A buffer the scope was never given (a caller's `out`, a DeviceGrid's) is never touched.  No device work beyond those calls."""
+
+    def __init__(self):
+        self._held = []         # (buffer, is a result) in order of acquisition
+
+    def __enter__(self):
+        return self
+
+    def adopt(self, b):
+        """own what something else allocated: anything with a free(), or a tuple of them (None passes through)"""
+        if isinstance(b, (tuple, list)):
+            for x in b:
+                self.adopt(x)
+        elif b is not None:
+            self._held.append((b, False))
+        return b
+
+    def alloc(self, nbytes):
+        return self.adopt(DeviceBuffer(nbytes))
+
+    def upload(self, array, wait=True):
+        """the array in a buffer of its size (wait=False: staged through upload_async); None for an empty array"""
+        a = np.ascontiguousarray(array)
+        if a.size == 0:
+            return None
+        b = self.alloc(a.nbytes)
+        return b.upload(a) if wait else b.upload_async(a)
+
+    def result(self, out, nbytes):
+        if out is None:
+            out = DeviceBuffer(nbytes)
+            self._held.append((out, True))
+        return out
+
+    def keep(self, b):
+        """b outlives the scope (what a resident form returns, what a DeviceGrid wraps)"""
+        self._held = [h for h in self._held if h[0] is not b]
+        return b
+
+    def free(self, b):
+        """free b now; the exit does not free it again"""
+        self.keep(b).free()
+
+    def __exit__(self, exc_type, exc, tb):
+        held, self._held = self._held, []
+        failed = None
+        for b, is_result in reversed(held):
+            if is_result and exc_type is None:
+                continue
+            try:
+                b.free()
+            except BaseException as e:      # the other buffers are still freed; an exception already in flight stays the one raised
+                failed = failed or e
+        if failed is not None and exc_type is None:
+            raise failed
+        return False
+
+
 def sync_count():
     """how often the host has waited for the context's stream so far"""
     return int(_lib.load().pb3d_sync_count(_lib.ctx()))
@@ -141,14 +204,6 @@ def device_info():
     mem = C.c_int64(0)
     _lib.check(_lib.load().pb3d_device_info(_lib.ctx(), name, 128, C.byref(cus), C.byref(mem)))
     return {"name": name.value.decode(), "compute_units": cus.value, "hbm_bytes": mem.value}
-
-
-def _ptr(x):
-    if x is None:
-        return None
-    if isinstance(x, DeviceBuffer):
-        return C.c_void_p(x.ptr)
-    return x  # already a c_void_p (buffer.at(offset))
 
 
 # ---- device-resident ops (enqueue only; call sync() or an Event to wait) --------------------------
@@ -228,14 +283,11 @@ def meshify(d_grid, shape, stride=1, download=True):
     if nv.value == 0:
         raise ValueError("Surface level must be within volume data range.")
     n, m = nv.value, nf.value
-    dv, df, dn, dc = DeviceBuffer(n * 12), DeviceBuffer(m * 12), DeviceBuffer(n * 12), DeviceBuffer(n * ch)
-    _lib.check(lib.pb3d_mesh_fill_dev(ctx, _ptr(buf), shape[0], shape[1], shape[2], ch, stride, n, m, _ptr(dv), _ptr(df), _ptr(dn),
-                                      _ptr(dc)))
-    if not download:
-        return (dv, df, dn, dc), (n, m)
-    try:
+    with Scope() as sc:
+        dv, df, dn, dc = sc.alloc(n * 12), sc.alloc(m * 12), sc.alloc(n * 12), sc.alloc(n * ch)
+        _lib.check(lib.pb3d_mesh_fill_dev(ctx, _ptr(buf), shape[0], shape[1], shape[2], ch, stride, n, m, _ptr(dv), _ptr(df), _ptr(dn),
+                                          _ptr(dc)))
+        if not download:
+            return tuple(sc.keep(b) for b in (dv, df, dn, dc)), (n, m)
         return (dv.download((n, 3), np.float32), df.download((m, 3), np.int32), mesh_colors(dc.download((n, ch))),
                 dn.download((n, 3), np.float32))
-    finally:
-        for b in (dv, df, dn, dc):
-            b.free()

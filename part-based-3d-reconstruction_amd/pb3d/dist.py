@@ -11,7 +11,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, device as dev
+from ._lib import _ptr
 
 
 def slab_bounds(n_planes, rank, nranks):
@@ -84,19 +85,16 @@ def comm_info():
 
 def allgather(d_send, d_recv, bytes_per_rank):
     """Enqueue the slab all-gather on the context stream (d_send may be the rank's slot of d_recv)."""
-    from .device import _ptr
     _lib.check(_lib.load().pb3d_allgather_dev(_lib.ctx(), _ptr(d_send), _ptr(d_recv), int(bytes_per_rank)))
 
 
 def carve_mask_sharded(d_grid_slab, W, H, D, channels, d_mask_wh, d_out_full):
     """This rank's slab carved into its slot of d_out_full + ONE in-place all-gather (pb3d_carve_mask_sharded_dev); enqueue only."""
-    from .device import _ptr
     _lib.check(_lib.load().pb3d_carve_mask_sharded_dev(_lib.ctx(), _ptr(d_grid_slab), int(W), int(H), int(D), int(channels), _ptr(d_mask_wh),
                                                        _ptr(d_out_full)))
 
 
 def global_carve_sharded(d_bin_hw, d_rgb_hw3, h, w, angle_interval, d_out_full):
-    from .device import _ptr
     _lib.check(_lib.load().pb3d_global_carve_sharded_dev(_lib.ctx(), _ptr(d_bin_hw), _ptr(d_rgb_hw3), int(h), int(w), int(angle_interval),
                                                          _ptr(d_out_full)))
 
@@ -105,7 +103,6 @@ def carve_labels_sharded(d_label_slab, W, H, D, d_mask_wh, d_label_full, palette
     """The compact form of the reassembly: the slab is carved as LABELS (1 B/voxel), ONE all-gather moves a
     third of the bytes of the RGB form, and -- only if d_rgb_full is given -- the reassembled label volume is expanded to RGB
     locally.  palette_colors: (n,3) uint8 (label k <-> palette_colors[k-1])."""
-    from .device import _ptr
     pal = np.zeros((0, 3), np.uint8) if palette_colors is None else np.ascontiguousarray(palette_colors, np.uint8)
     _lib.check(_lib.load().pb3d_carve_labels_sharded_dev(_lib.ctx(), _ptr(d_label_slab), int(W), int(H), int(D), _ptr(d_mask_wh), _ptr(d_label_full),
                                                          _lib.p_u8(pal), len(pal), _ptr(d_rgb_full)))
@@ -128,17 +125,15 @@ def project_colored_voxels_sharded(pts_shard, colors_shard, index_base, cam_pos,
     that merges key images itself) and returns (image, keys)."""
     import ctypes as C
     import numpy as np
-    from . import device as dev
     from .projection_utils import camera_args
     p, pf64, R, cam, prec = camera_args(pts_shard, cam_pos, target, f, cx, cy)
     cols = np.ascontiguousarray(np.asarray(colors_shard).astype(np.uint8, copy=False))
     if cols.shape != (len(p), 3):
         raise ValueError("colors must be (N,3)")
     lib, ctx = _lib.load(), _lib.ctx()
-    d_p = dev.from_numpy(p) if len(p) else None
-    d_c = dev.from_numpy(cols) if len(p) else None
-    d_keys = dev.DeviceBuffer(int(H) * int(W) * 8); d_img = dev.DeviceBuffer(int(H) * int(W) * 3)
-    try:
+    with dev.Scope() as sc:
+        d_p, d_c = sc.upload(p), sc.upload(cols)
+        d_keys = sc.alloc(int(H) * int(W) * 8); d_img = sc.alloc(int(H) * int(W) * 3)
         _lib.check(lib.pb3d_project_keys_dev(ctx, None if d_p is None else C.c_void_p(d_p.ptr), pf64, None if d_c is None else C.c_void_p(d_c.ptr),
                                              len(p), int(index_base), _lib.p_dbl(R), _lib.p_dbl(cam), float(f), float(cx), float(cy), prec,
                                              int(H), int(W), C.c_void_p(d_keys.ptr)))
@@ -147,10 +142,6 @@ def project_colored_voxels_sharded(pts_shard, colors_shard, index_base, cam_pos,
         _lib.check(lib.pb3d_project_resolve_keys_dev(ctx, C.c_void_p(d_keys.ptr), int(H), int(W), C.c_void_p(d_img.ptr)))
         img = d_img.download((int(H), int(W), 3))
         return img if reduce else (img, d_keys.download((int(H), int(W)), np.uint64))
-    finally:
-        for b in (d_p, d_c, d_keys, d_img):
-            if b is not None:
-                b.free()
 
 
 def resolve_keys(keys):

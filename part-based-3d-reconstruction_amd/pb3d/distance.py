@@ -16,9 +16,9 @@ import math
 
 import numpy as np
 
-from . import _lib
+from . import _lib, device as dev
+from ._args import _grid_channels, _on_device, _voxel_size
 from ._lib import _ptr
-from .voxelize import _grid, _grid_shape
 
 __all__ = ["distance_transform", "distance_transform_resident", "dilate_grid", "dilate_grid_resident", "erode_grid", "erode_grid_resident",
            "close_grid", "close_grid_resident", "open_grid", "open_grid_resident", "grid_surface_metrics", "grid_surface_metrics_resident"]
@@ -59,13 +59,6 @@ def _radius_sq(radius, what="radius"):
     return min(int(math.floor(r * r)), 2 ** 62)
 
 
-def _voxel_size(voxel_size):
-    vs = float(voxel_size)
-    if not math.isfinite(vs) or vs <= 0.0:
-        raise ValueError(f"voxel_size must be finite and > 0 (got {voxel_size!r})")
-    return vs
-
-
 def _out_dtype(dtype):
     dt = np.dtype(dtype)
     if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
@@ -89,26 +82,20 @@ def _thresholds_sq(thresholds, vs):
 
 def _edt(d_grid, ch, s, target, border, want_index, want_stats=False):
     """pb3d_edt_resident into fresh buffers: (d_sq, d_index or None[, stats])"""
-    from . import device as dev
     n = s[0] * s[1] * s[2]
-    d_sq, d_ix = dev.DeviceBuffer(4 * n), None
-    try:
-        d_ix = dev.DeviceBuffer(4 * n) if want_index else None
+    with dev.Scope() as sc:
+        d_sq = sc.result(None, 4 * n)
+        d_ix = sc.result(None, 4 * n) if want_index else None
         stats = (C.c_int64 * 2)() if want_stats else None
         _lib.check(_lib.load().pb3d_edt_resident(_lib.ctx(), _ptr(d_grid), ch, s[0], s[1], s[2], target, int(bool(border)), _ptr(d_sq), _ptr(d_ix),
                                                  stats))
-    except BaseException:
-        d_sq.free()
-        if d_ix is not None:
-            d_ix.free()
-        raise
-    if want_stats:
-        return d_sq, d_ix, {"targets": int(stats[0]), "max_sq": int(stats[1])}
-    return d_sq, d_ix
+        if want_stats:
+            return d_sq, d_ix, {"targets": int(stats[0]), "max_sq": int(stats[1])}
+        return d_sq, d_ix
 
 
 def _check_transform(grid, to, border, return_distances, return_indices, voxel_size, dtype):
-    ch, shape = _grid_shape(grid, "grid")
+    ch, shape = _grid_channels(grid, "grid")
     s = _lattice(shape, "grid")
     target = _target(to)
     if not return_distances and not return_indices:
@@ -123,34 +110,24 @@ def distance_transform_resident(grid, to="background", border=False, return_dist
     """distance_transform of a DeviceGrid with the results left on the device: DeviceBuffers of n0 * n1 * n2 values -- distances
     (float64 / float32, or the int32 sq with squared=True), indices (int32), in that order, one or a tuple as asked for.  With
     return_stats also the dict of targets (their number) and max_sq (the largest sq, -1 when there is no target): one host wait."""
-    from . import device as dev
     if not isinstance(grid, dev.DeviceGrid):
         raise TypeError(f"grid must be a DeviceGrid (got {type(grid).__name__})")
     ch, s, target, vs, dt = _check_transform(grid, to, border, return_distances, return_indices, voxel_size, dtype)
     n = s[0] * s[1] * s[2]
-    res = _edt(grid.buf, ch, s, target, border, return_indices, return_stats)
-    d_sq, d_ix = res[0], res[1]
     out = []
-    try:
+    with dev.Scope() as sc:
+        res = _edt(grid.buf, ch, s, target, border, return_indices, return_stats)
+        d_sq, d_ix = sc.adopt(res[:2])
         if return_distances and not squared:
-            d_d = dev.DeviceBuffer(n * dt.itemsize)
-            try:
-                _lib.check(_lib.load().pb3d_edt_distances_resident(_lib.ctx(), _ptr(d_sq), n, vs, int(dt.itemsize == 8), _ptr(d_d)))
-            except BaseException:
-                d_d.free()
-                raise
+            d_d = sc.alloc(n * dt.itemsize)
+            _lib.check(_lib.load().pb3d_edt_distances_resident(_lib.ctx(), _ptr(d_sq), n, vs, int(dt.itemsize == 8), _ptr(d_d)))
             out.append(d_d)
         elif return_distances:
             out.append(d_sq)
-    except BaseException:
-        d_sq.free()
-        if d_ix is not None:
-            d_ix.free()
-        raise
-    if not (return_distances and squared):
-        d_sq.free()
-    if return_indices:
-        out.append(d_ix)
+        if return_indices:
+            out.append(d_ix)
+        for b in out:
+            sc.keep(b)
     if return_stats:
         out.append(res[2])
     return out[0] if len(out) == 1 else tuple(out)
@@ -167,25 +144,18 @@ def distance_transform(grid, to="background", border=False, return_distances=Tru
     of a nearest target -- among equidistant ones the smallest index -- and -1 where there is none; np.unravel_index(index, shape) gives
     coordinates.  With voxel_size 1 and float64 the distances are SciPy's ndimage.distance_transform_edt's bit for bit."""
     _check_transform(grid, to, border, return_distances, return_indices, voxel_size, dtype)
-    from . import device as dev
-    g, bufs = None, []
-    try:
-        g = _grid(grid, "grid")
-        s = g[2]
-        res = distance_transform_resident(dev.DeviceGrid(g[0], s + ((3,) if g[1] == 3 else ())), to, border, return_distances, return_indices, squared,
-                                          voxel_size, dtype)
-        bufs = list(res) if isinstance(res, tuple) else [res]
+    ch, s = _grid_channels(grid, "grid")
+    with dev.Scope() as sc:
+        d_g = _on_device(sc, grid)
+        res = sc.adopt(distance_transform_resident(dev.DeviceGrid(d_g, s + ((3,) if ch == 3 else ())), to, border, return_distances, return_indices,
+                                                   squared, voxel_size, dtype))
+        bufs = res if isinstance(res, tuple) else (res,)
         out = []
         if return_distances:
             out.append(bufs[0].download(s, np.int32 if squared else np.dtype(dtype)))
         if return_indices:
             out.append(bufs[-1].download(s, np.int32))
         return out[0] if len(out) == 1 else tuple(out)
-    finally:
-        if g is not None and g[3] and g[0] is not None:
-            g[0].free()
-        for b in bufs:
-            b.free()
 
 
 def _apply(d_grid, ch, n, d_sq, d_ix, mode, r_sq, d_out):
@@ -194,31 +164,22 @@ def _apply(d_grid, ch, n, d_sq, d_ix, mode, r_sq, d_out):
 
 def _morph(grid, steps, out=None):
     """steps: (FILL or KEEP, r_sq, border) in turn on a DeviceGrid; a new DeviceGrid (or `out`, which may be `grid`)"""
-    from . import device as dev
     if not isinstance(grid, dev.DeviceGrid):
         raise TypeError(f"grid must be a DeviceGrid (got {type(grid).__name__})")
-    ch, shape = _grid_shape(grid, "grid")
+    ch, shape = _grid_channels(grid, "grid")
     s = _lattice(shape, "grid")
     n = s[0] * s[1] * s[2]
     if out is not None and (not isinstance(out, dev.DeviceGrid) or out.shape != grid.shape):
         raise ValueError("out must be a DeviceGrid of the grid's shape")
-    res = out if out is not None else dev.DeviceGrid(dev.DeviceBuffer(n * ch), grid.shape)
-    src = grid.buf
-    try:
+    with dev.Scope() as sc:
+        d_res = sc.result(None if out is None else out.buf, n * ch)
+        src = grid.buf
         for mode, r_sq, border in steps:
-            d_sq, d_ix = _edt(src, ch, s, 1 if mode == FILL else 0, border, mode == FILL)
-            try:
-                _apply(src, ch, n, d_sq, d_ix, mode, r_sq, res.buf)
-            finally:
-                d_sq.free()
-                if d_ix is not None:
-                    d_ix.free()
-            src = res.buf                                   # the next step runs in place on the result
-    except BaseException:
-        if out is None:
-            res.free()
-        raise
-    return res
+            with dev.Scope() as step:
+                d_sq, d_ix = step.adopt(_edt(src, ch, s, 1 if mode == FILL else 0, border, mode == FILL))
+                _apply(src, ch, n, d_sq, d_ix, mode, r_sq, d_res)
+            src = d_res                                     # the next step runs in place on the result
+        return out if out is not None else dev.DeviceGrid(d_res, grid.shape)
 
 
 def dilate_grid_resident(grid, radius, out=None):
@@ -244,20 +205,11 @@ def open_grid_resident(grid, radius, out=None):
 
 
 def _host_form(resident, grid, *args):
-    from . import device as dev
-    _lattice(_grid_shape(grid, "grid")[1], "grid")
+    _lattice(_grid_channels(grid, "grid")[1], "grid")
     if isinstance(grid, dev.DeviceGrid):
         return resident(grid, *args)
-    g, res = None, None
-    try:
-        g = _grid(grid, "grid")
-        res = resident(dev.DeviceGrid(g[0], np.shape(grid)), *args)
-        return res.numpy()
-    finally:
-        if g is not None and g[0] is not None:
-            g[0].free()
-        if res is not None:
-            res.free()
+    with dev.Scope() as sc:
+        return sc.adopt(resident(dev.DeviceGrid(_on_device(sc, grid), np.shape(grid)), *args)).numpy()
 
 
 def dilate_grid(grid, radius):
@@ -292,13 +244,12 @@ def open_grid(grid, radius):
 
 def _directed(d_a, ch_a, d_b, ch_b, s, thr_sq):
     """surface of a against the surface of b: (surface voxels of a, max sq, sum sq, counts per threshold), surface voxels of b"""
-    d_sq, _, st = _edt(d_b, ch_b, s, 2, False, False, True)
-    try:
+    with dev.Scope() as sc:
+        d_sq, _, st = _edt(d_b, ch_b, s, 2, False, False, True)
+        sc.adopt(d_sq)
         out = (C.c_int64 * (3 + MAX_THRESHOLDS))()
         thr = (C.c_int64 * MAX_THRESHOLDS)(*thr_sq)
         _lib.check(_lib.load().pb3d_grid_surface_stats_resident(_lib.ctx(), _ptr(d_a), ch_a, s[0], s[1], s[2], _ptr(d_sq), thr, len(thr_sq), out))
-    finally:
-        d_sq.free()
     return [int(v) for v in out[:3 + len(thr_sq)]], st["targets"]
 
 
@@ -332,7 +283,6 @@ def _metrics_from_sums(ab, ba, thresholds, voxel_size):
 
 def grid_surface_metrics_resident(a, b, thresholds=(1.0,), voxel_size=1.0):
     """grid_surface_metrics of two DeviceGrids (what it does for grids that are already resident)"""
-    from . import device as dev
     for g, what in ((a, "a"), (b, "b")):
         if not isinstance(g, dev.DeviceGrid):
             raise TypeError(f"{what} must be a DeviceGrid (got {type(g).__name__})")
@@ -350,24 +300,16 @@ def grid_surface_metrics(a, b, thresholds=(1.0,), voxel_size=1.0):
     recall and fscore are 0.0, the distances from the empty surface are 0.0 and those to it are inf (both empty: all 0.0).
     The mean (non-squared) surface distance is left out on purpose: a sum of square roots has no order-free exact form on the device;
     take it from distance_transform(b, to="surface") on the host if it is needed."""
-    ca, sa = _grid_shape(a, "a")
-    cb, sb = _grid_shape(b, "b")
+    ca, sa = _grid_channels(a, "a")
+    cb, sb = _grid_channels(b, "b")
     if sa != sb:
         raise ValueError(f"the grids differ in shape: {sa} and {sb}")
     s = _lattice(sa, "a")
     vs = _voxel_size(voxel_size)
     ts, thr_sq = _thresholds_sq(thresholds, vs)
-    bufs = []
-    try:
-        da = _grid(a, "a")
-        bufs.append(da)
-        db = _grid(b, "b")
-        bufs.append(db)
-        ab, nb = _directed(da[0], ca, db[0], cb, s, thr_sq)
-        ba, na = _directed(db[0], cb, da[0], ca, s, thr_sq)
+    with dev.Scope() as sc:
+        d_a, d_b = _on_device(sc, a), _on_device(sc, b)
+        ab, nb = _directed(d_a, ca, d_b, cb, s, thr_sq)
+        ba, na = _directed(d_b, cb, d_a, ca, s, thr_sq)
         assert ab[0] == na and ba[0] == nb, "the two surface counts of a grid differ"
         return _metrics_from_sums(ab, ba, ts, vs)
-    finally:
-        for buf, _, _, ours in bufs:
-            if ours and buf is not None:
-                buf.free()

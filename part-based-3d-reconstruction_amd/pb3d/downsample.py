@@ -12,24 +12,16 @@ csrc/downsample.hip: a hash table of 63-bit cell keys finds the voxels, a scan o
 radix sort of (voxel, position) pairs puts every voxel's points in input order for the sums -- no floating-point atomics.  The NumPy
 form uploads the cloud and downloads the arrays; the *_resident twin takes and returns device handles (pb3d.device.DeviceBuffer)."""
 import ctypes as C
-import math
 
 import numpy as np
 
-from . import _lib
+from . import _lib, device as dev
+from ._args import _count, _finite_cloud, _voxel_size
 from ._lib import _ptr
-from .cluster import _cloud, _count
 
 __all__ = ["voxel_downsample", "voxel_downsample_resident"]
 
 REDUCE = {"centroid": 0, "first": 1}
-
-
-def _voxel_size(v):
-    s = float(v)
-    if not (math.isfinite(s) and s > 0.0):
-        raise ValueError(f"voxel_size must be finite and > 0 (got {v!r})")
-    return s
 
 
 def _origin(origin):
@@ -52,19 +44,14 @@ def voxel_downsample_resident(d_P, n, voxel_size, origin=None, reduce="centroid"
     or float32 with f64 False), n int32 first positions, n int32 voxel numbers and n uint32 counts; the first m entries of d_out, d_index
     and d_counts are written.  m is the call's one download.  The caller frees the four buffers.  ValueError when a point's cell leaves
     [0, 2^21) on an axis (voxel_size too small for the extent, or an origin above the cloud)."""
-    from . import device as dev
     n, voxel_size, o, r = _count(n), _voxel_size(voxel_size), _origin(origin), _reduce(reduce)
-    bufs = [dev.DeviceBuffer(max(1, n) * w) for w in (24 if f64 else 12, 4, 4, 4)]
     m = C.c_int64(0)
-    try:
+    with dev.Scope() as sc:
+        bufs = [sc.result(None, max(1, n) * w) for w in (24 if f64 else 12, 4, 4, 4)]
         _lib.check(_lib.load().pb3d_voxel_downsample_resident(_lib.ctx(), _ptr(d_P), int(bool(f64)), n, voxel_size,
                                                               None if o is None else _lib.p_dbl(o), r, _ptr(bufs[0]), _ptr(bufs[1]),
                                                               _ptr(bufs[2]), _ptr(bufs[3]), C.byref(m)))
-    except BaseException:
-        for b in bufs:
-            b.free()
-        raise
-    return bufs[0], bufs[1], bufs[2], bufs[3], int(m.value)
+        return bufs[0], bufs[1], bufs[2], bufs[3], int(m.value)
 
 
 def voxel_downsample(points, voxel_size, origin=None, reduce="centroid", return_index=False, return_inverse=False, return_counts=False):
@@ -72,9 +59,8 @@ def voxel_downsample(points, voxel_size, origin=None, reduce="centroid", return_
     reduce="first" its first point.  float32 clouds stay float32 (sums and quotient in float64, rounded once), other real dtypes become
     float64.  Extras in np.unique's order: index (intp, the first position of each voxel), inverse (intp, the voxel of each point),
     counts (int64)."""
-    from . import device as dev
     voxel_size, o, _ = _voxel_size(voxel_size), _origin(origin), _reduce(reduce)
-    p, pf = _cloud(points)
+    p, pf = _finite_cloud(points)
     n = len(p)
 
     def pack(out, index, inverse, counts):
@@ -83,16 +69,11 @@ def voxel_downsample(points, voxel_size, origin=None, reduce="centroid", return_
 
     if n == 0:
         return pack(p.copy(), np.zeros(0, np.intp), np.zeros(0, np.intp), np.zeros(0, np.int64))
-    d_p = dev.from_numpy(p)
-    bufs = ()
-    try:
-        *bufs, m = voxel_downsample_resident(d_p, n, voxel_size, o, reduce, pf)
+    with dev.Scope() as sc:
+        *bufs, m = voxel_downsample_resident(sc.upload(p), n, voxel_size, o, reduce, pf)
+        sc.adopt(bufs)
         out = bufs[0].download((m, 3), p.dtype)
         index = bufs[1].download((m,), np.int32).astype(np.intp) if return_index else None
         inverse = bufs[2].download((n,), np.int32).astype(np.intp) if return_inverse else None
         counts = bufs[3].download((m,), np.uint32).astype(np.int64) if return_counts else None
         return pack(out, index, inverse, counts)
-    finally:
-        d_p.free()
-        for b in bufs:
-            b.free()

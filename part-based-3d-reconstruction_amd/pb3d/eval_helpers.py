@@ -35,7 +35,8 @@ import operator
 
 import numpy as np
 
-from . import _lib
+from . import _lib, device as dev
+from ._args import _cloud  # noqa: F401  (the cloud check; tests and tools take it from here)
 from ._lib import _ptr
 
 __all__ = ["filter_mesh", "chamfer_distance", "fscore_with_threshold", "pca_shape_similarity", "voxel_iou", "compute_nn_stats",
@@ -60,69 +61,48 @@ def filter_mesh(vertices, faces, y_thresh=0.2):
 
 
 # ---- point lists on the device -----------------------------------------------------------------------------------------------------------
-def _cloud(P, what="points"):
-    """(n, 3) array the kernels read: float32 stays float32 (widened on the device), anything else real becomes float64 -- what the
-    trees do with it.  Integer coordinates must satisfy |v| < 2^53 to convert exactly."""
-    a = np.asarray(P)
-    if a.ndim != 2 or a.shape[1] != 3:
-        raise ValueError(f"{what} must be an (n, 3) array (got shape {a.shape})")
-    if a.dtype == np.float32:
-        return np.ascontiguousarray(a), 0
-    if a.dtype.kind not in "fiu" or a.dtype.itemsize > 8:
-        raise TypeError(f"{what}: unsupported dtype {a.dtype}")
-    return np.ascontiguousarray(a, dtype=np.float64), 1
-
-
 def nn_distances_resident(d_A, nA, d_B, nB, k=1, a_f64=True, b_f64=True, out=None):
     """pb3d_nn_dist_dev: a DeviceBuffer of nA float64 -- the k-th smallest distance (k = 1 or 2) from each point of the resident
     (nA, 3) list d_A to the resident (nB, 3) list d_B (float64 rows, or float32 with a_f64 / b_f64 False).  With k = 2 and d_A the
     same list as d_B a point's own copy counts (distance 0), as NearestNeighbors(2).kneighbors(X) of X itself does."""
-    from . import device as dev
-    d_out = out if out is not None else dev.DeviceBuffer(max(1, int(nA)) * 8)
-    _lib.check(_lib.load().pb3d_nn_dist_dev(_lib.ctx(), _ptr(d_A), int(bool(a_f64)), int(nA), _ptr(d_B), int(bool(b_f64)), int(nB), int(k),
-                                            _ptr(d_out)))
-    return d_out
+    with dev.Scope() as sc:
+        d_out = sc.result(out, max(1, int(nA)) * 8)
+        _lib.check(_lib.load().pb3d_nn_dist_dev(_lib.ctx(), _ptr(d_A), int(bool(a_f64)), int(nA), _ptr(d_B), int(bool(b_f64)), int(nB), int(k),
+                                                _ptr(d_out)))
+        return d_out
 
 
 def points_bounds_resident(d_P, n, f64=True, out=None):
     """pb3d_points_bounds_dev: a DeviceBuffer of 6 float64, the exact min (3) and max (3) of a resident (n, 3) list"""
-    from . import device as dev
-    d_out = out if out is not None else dev.DeviceBuffer(6 * 8)
-    _lib.check(_lib.load().pb3d_points_bounds_dev(_lib.ctx(), _ptr(d_P), int(bool(f64)), int(n), _ptr(d_out)))
-    return d_out
+    with dev.Scope() as sc:
+        d_out = sc.result(out, 6 * 8)
+        _lib.check(_lib.load().pb3d_points_bounds_dev(_lib.ctx(), _ptr(d_P), int(bool(f64)), int(n), _ptr(d_out)))
+        return d_out
 
 
 def voxel_iou_counts_resident(d_A, nA, d_B, nB, bounds_min, step, resolution, iters, a_f64=True, b_f64=True, calc_f32=False, out=None):
     """pb3d_voxel_iou_counts_dev: a DeviceBuffer of 2 int64, (#(occA & occB), #(occA | occB)) of voxel_iou's dilated occupancies"""
-    from . import device as dev
-    d_out = out if out is not None else dev.DeviceBuffer(2 * 8)
     lo = np.ascontiguousarray(np.asarray(bounds_min, dtype=np.float64).reshape(3))
-    _lib.check(_lib.load().pb3d_voxel_iou_counts_dev(_lib.ctx(), _ptr(d_A), int(bool(a_f64)), int(nA), _ptr(d_B), int(bool(b_f64)), int(nB),
-                                                     _lib.p_dbl(lo), float(step), int(bool(calc_f32)), int(resolution), int(iters),
-                                                     _ptr(d_out)))
-    return d_out
+    with dev.Scope() as sc:
+        d_out = sc.result(out, 2 * 8)
+        _lib.check(_lib.load().pb3d_voxel_iou_counts_dev(_lib.ctx(), _ptr(d_A), int(bool(a_f64)), int(nA), _ptr(d_B), int(bool(b_f64)), int(nB),
+                                                         _lib.p_dbl(lo), float(step), int(bool(calc_f32)), int(resolution), int(iters),
+                                                         _ptr(d_out)))
+        return d_out
 
 
 def nn_distances(A, B, k=1):
     """float64 (len(A),) array: the k-th nearest distance (k = 1 or 2) from each point of A to B, bit for bit
     cKDTree(B).query(A, k)[0] (its last column when k = 2)."""
-    from . import device as dev
     a, af = _cloud(A, "A")
     b, bf = _cloud(B, "B")
     if len(a) == 0:
         return np.zeros(0, np.float64)
-    d_a = dev.from_numpy(a)
-    d_b = d_a if B is A else dev.from_numpy(b)
-    try:
-        d_out = nn_distances_resident(d_a, len(a), d_b, len(b), k, af, bf)
-        try:
-            return d_out.download((len(a),), np.float64)
-        finally:
-            d_out.free()
-    finally:
-        d_a.free()
-        if d_b is not d_a:
-            d_b.free()
+    with dev.Scope() as sc:
+        d_a = sc.upload(a)
+        d_b = d_a if B is A else sc.upload(b)
+        d_out = sc.adopt(nn_distances_resident(d_a, len(a), d_b, len(b), k, af, bf))
+        return d_out.download((len(a),), np.float64)
 
 
 # ---- accuracy metrics (:29-70) ---------------------------------------------------------------------------------------------------------
@@ -202,21 +182,16 @@ def _iou_inputs(A, B):
 def voxel_iou_counts(A, B, resolution=96, dilate_frac=0.01):
     """(inter, union) of voxel_iou: the occupancy of both clouds in resolution^3 voxels of their joint box, each dilated `iters`
     times; bounds, step and iters are the reference's expressions (:84-102) on the exact device bounds."""
-    from . import device as dev
     a, b, f64, dt = _iou_inputs(A, B)
     if len(a) + len(b) == 0:
         np.vstack([np.asarray(A), np.asarray(B)]).min(0)        # the reference's error on two empty clouds
-    bufs = []
-    try:
+    with dev.Scope() as sc:
         d_pts, bb = [], []
         for P in (a, b):
-            d_p = dev.from_numpy(P) if len(P) else None
+            d_p = sc.upload(P)
             d_pts.append(d_p)
             if d_p is not None:
-                bufs.append(d_p)
-                d_bb = points_bounds_resident(d_p, len(P), f64)
-                bufs.append(d_bb)
-                bb.append(d_bb.download((6,), np.float64))
+                bb.append(sc.adopt(points_bounds_resident(d_p, len(P), f64)).download((6,), np.float64))
         bb = np.array(bb)
         bounds_min = bb[:, :3].min(0).astype(dt)
         bounds_max = bb[:, 3:].max(0).astype(dt)
@@ -226,14 +201,10 @@ def voxel_iou_counts(A, B, resolution=96, dilate_frac=0.01):
             iters = max(1, int(round(
                 (dilate_frac * np.linalg.norm(bounds_max - bounds_min)) / step
             )))
-        d_c = voxel_iou_counts_resident(d_pts[0], len(a), d_pts[1], len(b), bounds_min, step, resolution, iters, f64, f64,
-                                        calc_f32=not f64)
-        bufs.append(d_c)
+        d_c = sc.adopt(voxel_iou_counts_resident(d_pts[0], len(a), d_pts[1], len(b), bounds_min, step, resolution, iters, f64, f64,
+                                                 calc_f32=not f64))
         inter, union = (int(v) for v in d_c.download((2,), np.int64))
         return inter, union
-    finally:
-        for buf in bufs:
-            buf.free()
 
 
 def voxel_iou(A, B, resolution=96, dilate_frac=0.01):
@@ -263,17 +234,12 @@ def _density_args(grid_size, sigma):
 def density_grid_resident(d_pts, n, grid_size=128, sigma=1.0, f64=True, out=None):
     """pb3d_density_grid_resident: a DeviceBuffer of grid_size^3 float32, pointcloud_to_voxel_grid of the resident (n, 3) list d_pts
     (float64 rows, or float32 with f64 False), bit for bit the reference's volume.  The coordinates must be finite."""
-    from . import device as dev
     G, radius, w = _density_args(grid_size, sigma)
-    d_out = out if out is not None else dev.DeviceBuffer(G ** 3 * 4)
-    try:
+    with dev.Scope() as sc:
+        d_out = sc.result(out, G ** 3 * 4)
         _lib.check(_lib.load().pb3d_density_grid_resident(_lib.ctx(), _ptr(d_pts), int(bool(f64)), int(n), G,
                                                           None if w is None else _lib.p_dbl(w), radius, _ptr(d_out)))
-    except BaseException:
-        if out is None:
-            d_out.free()
-        raise
-    return d_out
+        return d_out
 
 
 def pointcloud_to_voxel_grid(points, grid_size=128, sigma=1.0):
@@ -281,21 +247,14 @@ def pointcloud_to_voxel_grid(points, grid_size=128, sigma=1.0):
     pb3d.preprocess_helpers.normalize_preserve_aspect in its own dtype (float32 stays float32, other reals become float64), the points
     counted per voxel trunc(norm * (grid_size - 1)) -- the y indices are <= 0 and wrap to the far planes, as NumPy's do -- smoothed by
     the reference's Gaussian filter when sigma > 0, and the six faces set to 0."""
-    from . import device as dev
     p, f64 = _cloud(points)
     G, _, _ = _density_args(grid_size, sigma)
     if len(p) == 0:
         raise ValueError("zero-size array to reduction operation minimum which has no identity")
     _finite(p, "points")
-    d_p = dev.from_numpy(p)
-    d_out = None
-    try:
-        d_out = density_grid_resident(d_p, len(p), G, sigma, f64)
+    with dev.Scope() as sc:
+        d_out = sc.adopt(density_grid_resident(sc.upload(p), len(p), G, sigma, f64))
         return d_out.download((G, G, G), np.float32)
-    finally:
-        d_p.free()
-        if d_out is not None:
-            d_out.free()
 
 
 # ---- regularity metrics (:118-130) -----------------------------------------------------------------------------------------------------
@@ -338,26 +297,19 @@ def _finite(a, what):
 def knn_resident(d_A, nA, d_B, nB, k, a_f64=True, b_f64=True, dist=True):
     """pb3d_knn_dev: (DeviceBuffer of nA x k float64 distances or None, DeviceBuffer of nA x k int32 positions in d_B), each row
     ascending by (squared distance, position)."""
-    from . import device as dev
     k = _check_k(k, int(nB))
-    d_idx = dev.DeviceBuffer(max(1, int(nA) * k) * 4)
-    d_dist = dev.DeviceBuffer(max(1, int(nA) * k) * 8) if dist else None
-    try:
+    with dev.Scope() as sc:
+        d_idx = sc.result(None, max(1, int(nA) * k) * 4)
+        d_dist = sc.result(None, max(1, int(nA) * k) * 8) if dist else None
         _lib.check(_lib.load().pb3d_knn_dev(_lib.ctx(), _ptr(d_A), int(bool(a_f64)), int(nA), _ptr(d_B), int(bool(b_f64)), int(nB), k,
                                             _ptr(d_dist), _ptr(d_idx)))
-    except BaseException:
-        d_idx.free()
-        if d_dist is not None:
-            d_dist.free()
-        raise
-    return d_dist, d_idx
+        return d_dist, d_idx
 
 
 def knn(A, B, k):
     """(dist float64 (len(A), k), idx int32 (len(A), k)): the k nearest points of B for each point of A, nearest first; equal
     distances in ascending index order, which also decides who is in the row.  The distances are bit for bit
     NearestNeighbors(n_neighbors=k).fit(B).kneighbors(A)[0]; the indices are too wherever no two candidates tie."""
-    from . import device as dev
     a, af = _cloud(A, "A")
     b, bf = _cloud(B, "B")
     k = _check_k(k, len(b))
@@ -365,16 +317,11 @@ def knn(A, B, k):
     _finite(b, "B")
     if len(a) == 0:
         return np.zeros((0, k), np.float64), np.zeros((0, k), np.int32)
-    d_a = dev.from_numpy(a)
-    d_b = d_a if B is A else dev.from_numpy(b)
-    bufs = [d_a] + ([] if d_b is d_a else [d_b])
-    try:
-        d_dist, d_idx = knn_resident(d_a, len(a), d_b, len(b), k, af, bf)
-        bufs += [d_dist, d_idx]
+    with dev.Scope() as sc:
+        d_a = sc.upload(a)
+        d_b = d_a if B is A else sc.upload(b)
+        d_dist, d_idx = sc.adopt(knn_resident(d_a, len(a), d_b, len(b), k, af, bf))
         return d_dist.download((len(a), k), np.float64), d_idx.download((len(a), k), np.int32)
-    finally:
-        for buf in bufs:
-            buf.free()
 
 
 # ---- mesh regularity (:198-245) --------------------------------------------------------------------------------------------------------
@@ -393,25 +340,20 @@ def _mesh_arrays(vertices, faces):
 
 def triangle_normals_resident(d_verts, nv, d_faces, nf, verts_f64=False, faces_i64=False, out=None):
     """pb3d_triangle_normals_dev: a DeviceBuffer of nf x 3 face normals in the vertex dtype (IndexError on a bad face index)"""
-    from . import device as dev
-    d_out = out if out is not None else dev.DeviceBuffer(max(1, int(nf)) * 3 * (8 if verts_f64 else 4))
-    _lib.check(_lib.load().pb3d_triangle_normals_dev(_lib.ctx(), _ptr(d_verts), int(bool(verts_f64)), int(nv), _ptr(d_faces),
-                                                     int(bool(faces_i64)), int(nf), _ptr(d_out)))
-    return d_out
+    with dev.Scope() as sc:
+        d_out = sc.result(out, max(1, int(nf)) * 3 * (8 if verts_f64 else 4))
+        _lib.check(_lib.load().pb3d_triangle_normals_dev(_lib.ctx(), _ptr(d_verts), int(bool(verts_f64)), int(nv), _ptr(d_faces),
+                                                         int(bool(faces_i64)), int(nf), _ptr(d_out)))
+        return d_out
 
 
 def vertex_normals_resident(d_verts, nv, d_faces, nf, verts_f64=False, faces_i64=False, out=None):
     """pb3d_vertex_normals_dev: a DeviceBuffer of nv x 3 vertex normals in the vertex dtype (IndexError on a bad face index)"""
-    from . import device as dev
-    d_out = out if out is not None else dev.DeviceBuffer(max(1, int(nv)) * 3 * (8 if verts_f64 else 4))
-    try:
+    with dev.Scope() as sc:
+        d_out = sc.result(out, max(1, int(nv)) * 3 * (8 if verts_f64 else 4))
         _lib.check(_lib.load().pb3d_vertex_normals_dev(_lib.ctx(), _ptr(d_verts), int(bool(verts_f64)), int(nv), _ptr(d_faces),
                                                        int(bool(faces_i64)), int(nf), _ptr(d_out)))
-    except BaseException:
-        if out is None:
-            d_out.free()
-        raise
-    return d_out
+        return d_out
 
 
 def surface_metrics_resident(d_verts, nv, d_faces, nf, k=20, verts_f64=False, faces_i64=False):
@@ -419,46 +361,29 @@ def surface_metrics_resident(d_verts, nv, d_faces, nf, k=20, verts_f64=False, fa
     float32 vertices and int32 faces): a DeviceBuffer of 3 x nv float64 -- normal angle spread (degrees), smallest PCA eigenvalue,
     |neighbour mean - vertex| -- from pb3d_vertex_normals_dev, pb3d_knn_dev on the vertices themselves and pb3d_surface_metrics_dev.
     The vertices must be finite."""
-    from . import device as dev
     nv = int(nv)
     k = _check_k_metrics(k, nv)
-    bufs = []
-    try:
-        d_n = vertex_normals_resident(d_verts, nv, d_faces, nf, verts_f64, faces_i64)
-        bufs.append(d_n)
-        _, d_idx = knn_resident(d_verts, nv, d_verts, nv, k, verts_f64, verts_f64, dist=False)
-        bufs.append(d_idx)
-        d_out = dev.DeviceBuffer(max(1, nv) * 3 * 8)
-        try:
-            _lib.check(_lib.load().pb3d_surface_metrics_dev(_lib.ctx(), _ptr(d_verts), _ptr(d_n), int(bool(verts_f64)), nv, _ptr(d_idx), k,
-                                                            d_out.at(0), d_out.at(nv * 8), d_out.at(2 * nv * 8)))
-        except BaseException:
-            d_out.free()
-            raise
+    with dev.Scope() as sc:
+        d_n = sc.adopt(vertex_normals_resident(d_verts, nv, d_faces, nf, verts_f64, faces_i64))
+        _, d_idx = sc.adopt(knn_resident(d_verts, nv, d_verts, nv, k, verts_f64, verts_f64, dist=False))
+        d_out = sc.result(None, max(1, nv) * 3 * 8)
+        _lib.check(_lib.load().pb3d_surface_metrics_dev(_lib.ctx(), _ptr(d_verts), _ptr(d_n), int(bool(verts_f64)), nv, _ptr(d_idx), k,
+                                                        d_out.at(0), d_out.at(nv * 8), d_out.at(2 * nv * 8)))
         return d_out
-    finally:
-        for buf in bufs:
-            buf.free()
 
 
 def _normals(vertices, faces, per_vertex):
-    from . import device as dev
     v, vf, f = _mesh_arrays(vertices, faces)
     n = len(v) if per_vertex else len(f)
     if len(v) == 0 and len(f):
         v[f[:, 0]]                                                      # the reference's IndexError
     if n == 0:
         return np.zeros((0, 3), v.dtype)
-    d_v, d_f = dev.from_numpy(v), dev.from_numpy(f if len(f) else np.zeros((1, 3), np.int64))
-    d_out = None
-    try:
+    with dev.Scope() as sc:
+        d_v, d_f = sc.upload(v), sc.upload(f if len(f) else np.zeros((1, 3), np.int64))
         fn = vertex_normals_resident if per_vertex else triangle_normals_resident
-        d_out = fn(d_v, len(v), d_f, len(f), vf, True)
+        d_out = sc.adopt(fn(d_v, len(v), d_f, len(f), vf, True))
         return d_out.download((n, 3), v.dtype)
-    finally:
-        for buf in (d_v, d_f, d_out):
-            if buf is not None:
-                buf.free()
 
 
 def compute_triangle_normals(vertices, faces):
@@ -474,20 +399,14 @@ def compute_vertex_normals(vertices, faces):
 
 def surface_metrics_per_vertex(vertices, faces, k=20):
     """(normal_stds, roughness_vals, mean_curvatures): the three per-vertex lists of compute_surface_metrics as float64 arrays"""
-    from . import device as dev
     v, vf, f = _mesh_arrays(vertices, faces)
     k = _check_k_metrics(k, len(v))
     _finite(v, "X")
-    d_v, d_f = dev.from_numpy(v), dev.from_numpy(f if len(f) else np.zeros((1, 3), np.int64))
-    d_out = None
-    try:
-        d_out = surface_metrics_resident(d_v, len(v), d_f, len(f), k, vf, True)
+    with dev.Scope() as sc:
+        d_v, d_f = sc.upload(v), sc.upload(f if len(f) else np.zeros((1, 3), np.int64))
+        d_out = sc.adopt(surface_metrics_resident(d_v, len(v), d_f, len(f), k, vf, True))
         out = d_out.download((3, len(v)), np.float64)
         return out[0], out[1], out[2]
-    finally:
-        for buf in (d_v, d_f, d_out):
-            if buf is not None:
-                buf.free()
 
 
 def compute_surface_metrics(vertices, faces, k=20):
@@ -505,19 +424,13 @@ def point_to_mesh_distances_resident(d_P, nP, d_verts, nv, d_faces, nf, p_f64=Tr
     """pb3d_mesh_dist_resident: (DeviceBuffer of nP float64 distances, DeviceBuffer of nP int32 nearest faces or None, DeviceBuffer of
     nP x 3 float64 closest points or None) of the resident (nP, 3) list d_P against the resident mesh (IndexError on a bad face index).
     Points and vertices must be finite."""
-    from . import device as dev
     nP = int(nP)
-    bufs = [dev.DeviceBuffer(max(1, nP) * 8), dev.DeviceBuffer(max(1, nP) * 4) if return_faces else None,
-            dev.DeviceBuffer(max(1, nP) * 24) if return_closest else None]
-    try:
+    with dev.Scope() as sc:
+        bufs = [sc.result(None, max(1, nP) * 8), sc.result(None, max(1, nP) * 4) if return_faces else None,
+                sc.result(None, max(1, nP) * 24) if return_closest else None]
         _lib.check(_lib.load().pb3d_mesh_dist_resident(_lib.ctx(), _ptr(d_P), int(bool(p_f64)), nP, _ptr(d_verts), int(bool(verts_f64)), int(nv),
                                                        _ptr(d_faces), int(bool(faces_i64)), int(nf), *[_ptr(b) for b in bufs]))
-    except BaseException:
-        for b in bufs:
-            if b is not None:
-                b.free()
-        raise
-    return tuple(bufs)
+        return tuple(bufs)
 
 
 def mesh_grid_shape():
@@ -543,7 +456,6 @@ def point_to_mesh_distances(P, vertices, faces, return_faces=False, return_close
     include/pb3d.h (Ericson's closest point on every candidate face in float64, the minimum over ALL faces, ties to the lowest face).
     With return_faces also the int32 face index of each point, with return_closest also the (len(P), 3) float64 closest points, in
     that order."""
-    from . import device as dev
     p, pf = _cloud(P, "P")
     _finite(p, "P")
     if len(p) == 0:
@@ -551,19 +463,15 @@ def point_to_mesh_distances(P, vertices, faces, return_faces=False, return_close
             ((np.zeros((0, 3), np.float64),) if return_closest else ())
         return out if len(out) > 1 else out[0]
     v, vf, f = _mesh_on_device(vertices, faces, "point_to_mesh_distances")
-    bufs = [dev.from_numpy(p), dev.from_numpy(v), dev.from_numpy(f)]
-    try:
-        outs = point_to_mesh_distances_resident(bufs[0], len(p), bufs[1], len(v), bufs[2], len(f), pf, vf, True, return_faces, return_closest)
-        bufs += [b for b in outs if b is not None]
+    with dev.Scope() as sc:
+        outs = sc.adopt(point_to_mesh_distances_resident(sc.upload(p), len(p), sc.upload(v), len(v), sc.upload(f), len(f), pf, vf, True,
+                                                         return_faces, return_closest))
         res = [outs[0].download((len(p),), np.float64)]
         if return_faces:
             res.append(outs[1].download((len(p),), np.int32))
         if return_closest:
             res.append(outs[2].download((len(p), 3), np.float64))
         return tuple(res) if len(res) > 1 else res[0]
-    finally:
-        for b in bufs:
-            b.free()
 
 
 def _sample_args(n, seed):
@@ -578,39 +486,27 @@ def _sample_args(n, seed):
 def sample_mesh_points_resident(d_verts, nv, d_faces, nf, n, seed=0, verts_f64=False, faces_i64=False, return_faces=True):
     """pb3d_mesh_sample_resident: (DeviceBuffer of n x 3 float64 surface points, DeviceBuffer of n int32 faces or None), stratified by
     area and a function of (mesh, n, seed) alone (ValueError if the mesh's area is 0, IndexError on a bad face index)"""
-    from . import device as dev
     n, seed = _sample_args(n, seed)
-    d_pts = dev.DeviceBuffer(max(1, n) * 24)
-    d_face = dev.DeviceBuffer(max(1, n) * 4) if return_faces else None
-    try:
+    with dev.Scope() as sc:
+        d_pts = sc.result(None, max(1, n) * 24)
+        d_face = sc.result(None, max(1, n) * 4) if return_faces else None
         _lib.check(_lib.load().pb3d_mesh_sample_resident(_lib.ctx(), _ptr(d_verts), int(bool(verts_f64)), int(nv), _ptr(d_faces),
                                                          int(bool(faces_i64)), int(nf), n, seed, _ptr(d_pts), _ptr(d_face)))
-    except BaseException:
-        d_pts.free()
-        if d_face is not None:
-            d_face.free()
-        raise
-    return d_pts, d_face
+        return d_pts, d_face
 
 
 def sample_mesh_points(vertices, faces, n, seed=0, return_faces=False):
     """(n, 3) float64 points of the mesh surface, area-weighted and stratified: sample i falls in the i-th of n equal slices of the
     cumulative face area, so consecutive samples lie on consecutive faces and every face gets its share to within 2 samples.  The
     same (mesh, n, seed) gives the same bytes.  With return_faces also the int32 face of each sample."""
-    from . import device as dev
     n, seed = _sample_args(n, seed)
     if n == 0:
         return (np.zeros((0, 3), np.float64), np.zeros(0, np.int32)) if return_faces else np.zeros((0, 3), np.float64)
     v, vf, f = _mesh_on_device(vertices, faces, "sample_mesh_points")
-    bufs = [dev.from_numpy(v), dev.from_numpy(f)]
-    try:
-        d_pts, d_face = sample_mesh_points_resident(bufs[0], len(v), bufs[1], len(f), n, seed, vf, True, return_faces)
-        bufs += [b for b in (d_pts, d_face) if b is not None]
+    with dev.Scope() as sc:
+        d_pts, d_face = sc.adopt(sample_mesh_points_resident(sc.upload(v), len(v), sc.upload(f), len(f), n, seed, vf, True, return_faces))
         pts = d_pts.download((n, 3), np.float64)
         return (pts, d_face.download((n,), np.int32)) if return_faces else pts
-    finally:
-        for b in bufs:
-            b.free()
 
 
 def cloud_to_mesh_metrics(P, vertices, faces, tau, n_samples=None, seed=0):

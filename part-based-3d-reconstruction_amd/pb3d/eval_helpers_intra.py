@@ -15,9 +15,10 @@ import warnings
 
 import numpy as np
 
-from . import _lib
+from . import _lib, device as dev, mask_utils
+from ._args import _cam, _colour_table, _eps_f32, _grid, _on_device
 from ._lib import _ptr
-from .projection_utils import _promotes_to_f64, camera_args
+from .projection_utils import camera_args
 
 __all__ = ["compute_global_depth_buffer", "project_part_visible", "load_voxel_grid", "load_mask", "resize_mask_to_voxel_grid",
            "load_camera_json", "project_keypoints", "compute_binary_gt", "run_minaret_kp_evaluation", "run_minaret_iou_evaluation",
@@ -27,50 +28,38 @@ __all__ = ["compute_global_depth_buffer", "project_part_visible", "load_voxel_gr
 
 def compute_global_depth_buffer(voxel_grid, cam, H, W):
     """(H,W) float32 depth of the nearest occupied voxel per pixel, +inf where none."""
-    from . import device as dev
     grid = _lib.as_u8(voxel_grid, "voxel_grid")
     if grid.ndim != 4:
         raise ValueError("voxel_grid must be (A0,A1,A2,3)")
     A0, A1, A2, Cc = grid.shape
     lib, ctx = _lib.load(), _lib.ctx()
-    d_grid = dev.from_numpy(grid)
-    d_z = dev.DeviceBuffer(int(H) * int(W) * 4)
-    bufs = [d_grid, d_z]
-    try:
+    with dev.Scope() as sc:
+        d_grid = sc.upload(grid) or sc.alloc(0)
+        d_z = sc.alloc(int(H) * int(W) * 4)
         n = C.c_int64(0)
         _lib.check(lib.pb3d_points_count_dev(ctx, C.c_void_p(d_grid.ptr), A0, A1, A2, Cc, None, 0, 1, C.byref(n)))
-        d_pts = dev.DeviceBuffer(max(1, n.value) * 12); d_pc = dev.DeviceBuffer(max(1, n.value) * Cc)
-        bufs += [d_pts, d_pc]
+        d_pts = sc.alloc(max(1, n.value) * 12); d_pc = sc.alloc(max(1, n.value) * Cc)
         _lib.check(lib.pb3d_points_fill_dev(ctx, C.c_void_p(d_grid.ptr), A0, A1, A2, Cc, None, 0, 1, n.value, C.c_void_p(d_pts.ptr),
                                             C.c_void_p(d_pc.ptr)))
         _, _, R, cp, prec = camera_args(np.zeros((1, 3), np.float32), cam["cam_pos"], cam["target"], cam["f"], cam["cx"], cam["cy"])
         _lib.check(lib.pb3d_depth_buffer_dev(ctx, C.c_void_p(d_pts.ptr), 0, n.value, _lib.p_dbl(R), _lib.p_dbl(cp), float(cam["f"]),
                                              float(cam["cx"]), float(cam["cy"]), prec, int(H), int(W), C.c_void_p(d_z.ptr)))
         return d_z.download((int(H), int(W)), np.float32)
-    finally:
-        for b in bufs:
-            b.free()
 
 
 def project_part_visible(pts3d, cam, zbuf, H, W, eps=1e-3):
     """(H,W) bool: pixels where some point of the part lies on the depth buffer (within eps)."""
-    from . import device as dev
     p, pf64, R, cp, prec = camera_args(pts3d, cam["cam_pos"], cam["target"], cam["f"], cam["cx"], cam["cy"])
     zb = np.ascontiguousarray(zbuf, np.float32)
     if zb.shape != (int(H), int(W)):
         raise IndexError("zbuf shape does not match (H, W)")
-    eps_f32 = int((not prec[0]) and not _promotes_to_f64(eps))
-    d_p = dev.from_numpy(p) if len(p) else None
-    d_zb = dev.from_numpy(zb); d_m = dev.DeviceBuffer(int(H) * int(W))
-    try:
+    with dev.Scope() as sc:
+        d_p = sc.upload(p)
+        d_zb = sc.upload(zb) or sc.alloc(0); d_m = sc.alloc(int(H) * int(W))
         _lib.check(_lib.load().pb3d_visible_mask_dev(_lib.ctx(), None if d_p is None else C.c_void_p(d_p.ptr), pf64, len(p), _lib.p_dbl(R),
                                                      _lib.p_dbl(cp), float(cam["f"]), float(cam["cx"]), float(cam["cy"]), prec,
-                                                     C.c_void_p(d_zb.ptr), int(H), int(W), float(eps), eps_f32, C.c_void_p(d_m.ptr)))
+                                                     C.c_void_p(d_zb.ptr), int(H), int(W), float(eps), _eps_f32(prec, eps), C.c_void_p(d_m.ptr)))
         return d_m.download((int(H), int(W))).astype(bool)
-    finally:
-        for b in (d_p, d_zb, d_m):
-            if b is not None:
-                b.free()
 
 
 # ---- loaders and small helpers (reference :19-84, :269-285) -------------------------------------------------------------------------
@@ -88,18 +77,16 @@ def load_voxel_grid(npz_path):
 
 def load_mask(mask_path):
     """(H, W, 3) uint8 RGB of a mask file (not pb3d.load_mask, which is utils/mask_utils.py's)"""
-    from .mask_utils import _read_rgb
-    return _read_rgb(mask_path)
+    return mask_utils._read_rgb(mask_path)
 
 
 def resize_mask_to_voxel_grid(mask_img, voxel_grid):
     """nearest resize so the mask's longer side is the grid's largest dimension; prints upstream's line.  voxel_grid: anything with
     the grid's .shape (a NumPy grid or a DeviceGrid)"""
-    from .mask_utils import resize_nearest
     H, W = mask_img.shape[:2]
     scale = max(voxel_grid.shape[:3]) / max(H, W)
     new_W, new_H = int(round(W * scale)), int(round(H * scale))
-    resized = resize_nearest(mask_img, new_W, new_H)
+    resized = mask_utils.resize_nearest(mask_img, new_W, new_H)
     print(f"Mask resized: ({H},{W}) → ({new_H},{new_W}) | scale={scale:.3f}")
     return resized
 
@@ -133,66 +120,34 @@ def _iou_counts(inter, union):
 
 
 # ---- device passes ----------------------------------------------------------------------------------------------------------------
-def _cam(cam, pts_dtype):
-    _, _, R, cp, prec = camera_args(np.zeros((1, 3), pts_dtype), cam["cam_pos"], cam["target"], cam["f"], cam["cx"], cam["cy"])
-    return R, cp, prec
-
-
-def _eps_f32(prec, eps):
-    return int((not prec[0]) and not _promotes_to_f64(eps))
-
-
-def _grid(voxel_grid):
-    """(device buffer or None, (A0, A1, A2, C), owned) of a NumPy grid ((A0,A1,A2,3) RGB or (A0,A1,A2) labels) or a DeviceGrid"""
-    from . import device as dev
-    if isinstance(voxel_grid, dev.DeviceGrid):
-        shape, buf, owned = voxel_grid.shape, voxel_grid.buf, False
-    else:
-        g = _lib.as_u8(voxel_grid, "voxel_grid")
-        shape, buf, owned = g.shape, (dev.from_numpy(g) if g.size else None), True
-    if len(shape) == 3:
-        shape = tuple(shape) + (1,)
-    if len(shape) != 4 or shape[3] not in (1, 3):
-        raise ValueError("voxel_grid must be (A0,A1,A2,3) RGB or (A0,A1,A2) labels")
-    return buf, tuple(int(v) for v in shape), owned
-
-
-def _colour_table(colors, C):
-    t = np.ascontiguousarray(np.asarray(colors, dtype=np.int64).reshape(-1, C) if len(colors) else np.zeros((0, C), np.int64))
-    if t.size and (t.min() < 0 or t.max() > 255):
-        raise ValueError("colours are uint8 values")
-    return np.ascontiguousarray(t.astype(np.uint8))
-
-
 def depth_buffer_resident(d_grid, shape, cam, H, W, out=None):
     """pb3d_grid_depth_buffer_dev: the float32 (H, W) z-buffer of a resident grid in a DeviceBuffer"""
-    from . import device as dev
     A0, A1, A2, Cc = shape
     R, cp, prec = _cam(cam, np.float32)
-    d_z = out if out is not None else dev.DeviceBuffer(max(1, int(H) * int(W)) * 4)
-    _lib.check(_lib.load().pb3d_grid_depth_buffer_dev(_lib.ctx(), _ptr(d_grid), A0, A1, A2, Cc, _lib.p_dbl(R), _lib.p_dbl(cp), float(cam["f"]),
-                                                      float(cam["cx"]), float(cam["cy"]), prec, int(H), int(W), C.c_void_p(d_z.ptr)))
-    return d_z
+    with dev.Scope() as sc:
+        d_z = sc.result(out, max(1, int(H) * int(W)) * 4)
+        _lib.check(_lib.load().pb3d_grid_depth_buffer_dev(_lib.ctx(), _ptr(d_grid), A0, A1, A2, Cc, _lib.p_dbl(R), _lib.p_dbl(cp), float(cam["f"]),
+                                                          float(cam["cx"]), float(cam["cy"]), prec, int(H), int(W), C.c_void_p(d_z.ptr)))
+        return d_z
 
 
 def visible_bits_resident(d_grid, shape, colors, cam, d_zbuf, zshape, H, W, eps=1e-3, out=None):
     """pb3d_grid_visible_bits_dev into a (H, W) uint32 DeviceBuffer"""
-    from . import device as dev
     A0, A1, A2, Cc = shape
     R, cp, prec = _cam(cam, np.float32)
     tab = _colour_table(colors, Cc)
-    d_b = out if out is not None else dev.DeviceBuffer(max(1, int(H) * int(W)) * 4)
-    _lib.check(_lib.load().pb3d_grid_visible_bits_dev(_lib.ctx(), _ptr(d_grid), A0, A1, A2, Cc, _lib.p_u8(tab), len(tab), _lib.p_dbl(R),
-                                                      _lib.p_dbl(cp), float(cam["f"]), float(cam["cx"]), float(cam["cy"]), prec,
-                                                      C.c_void_p(d_zbuf.ptr), int(zshape[0]), int(zshape[1]), int(H), int(W), float(eps),
-                                                      _eps_f32(prec, eps), C.c_void_p(d_b.ptr)))
-    return d_b
+    with dev.Scope() as sc:
+        d_b = sc.result(out, max(1, int(H) * int(W)) * 4)
+        _lib.check(_lib.load().pb3d_grid_visible_bits_dev(_lib.ctx(), _ptr(d_grid), A0, A1, A2, Cc, _lib.p_u8(tab), len(tab), _lib.p_dbl(R),
+                                                          _lib.p_dbl(cp), float(cam["f"]), float(cam["cx"]), float(cam["cy"]), prec,
+                                                          C.c_void_p(d_zbuf.ptr), int(zshape[0]), int(zshape[1]), int(H), int(W), float(eps),
+                                                          _eps_f32(prec, eps), C.c_void_p(d_b.ptr)))
+        return d_b
 
 
 def points_visible_bits_resident(lists, cam, d_zbuf, zshape, H, W, eps=1e-3, out=None):
     """pb3d_points_visible_bits_dev: bit k = some point of lists[k] ((n, 3) arrays of one dtype: float32, float64 or int64) is visible.
     The camera's precision follows NumPy's promotion of the points' dtype (int64 - float32 is float64)."""
-    from . import device as dev
     arrs = [np.asarray(a) for a in lists]
     dt = np.result_type(*arrs) if arrs else np.dtype(np.float32)
     kinds = {np.dtype(np.float32): 0, np.dtype(np.float64): 1, np.dtype(np.int64): 2}
@@ -202,42 +157,38 @@ def points_visible_bits_resident(lists, cam, d_zbuf, zshape, H, W, eps=1e-3, out
         if a.ndim != 2 or a.shape[1] != 3:
             raise ValueError("point lists must be (n, 3)")
     R, cp, prec = _cam(cam, dt)
-    bufs = [dev.from_numpy(a) if len(a) else None for a in arrs]
-    ptrs = (C.c_void_p * max(1, len(arrs)))(*[None if b is None else b.ptr for b in bufs])
     counts = np.array([len(a) for a in arrs] or [0], np.int64)
-    d_b = out if out is not None else dev.DeviceBuffer(max(1, int(H) * int(W)) * 4)
-    try:
+    with dev.Scope() as sc:     # (the context's pool hands a freed block out again only behind this stream's work)
+        bufs = [sc.upload(a) for a in arrs]
+        ptrs = (C.c_void_p * max(1, len(arrs)))(*[None if b is None else b.ptr for b in bufs])
+        d_b = sc.result(out, max(1, int(H) * int(W)) * 4)
         _lib.check(_lib.load().pb3d_points_visible_bits_dev(_lib.ctx(), ptrs, counts.ctypes.data_as(_lib.i64p), len(arrs), kinds[dt],
                                                             _lib.p_dbl(R), _lib.p_dbl(cp), float(cam["f"]), float(cam["cx"]), float(cam["cy"]),
                                                             prec, C.c_void_p(d_zbuf.ptr), int(zshape[0]), int(zshape[1]), int(H), int(W),
                                                             float(eps), _eps_f32(prec, eps), C.c_void_p(d_b.ptr)))
-    finally:
-        for b in bufs:      # the context's pool hands a freed block out again only behind this stream's work
-            if b is not None:
-                b.free()
-    return d_b
+        return d_b
 
 
 def presence_resident(d_grid, shape, colors, d_present=None, out=None):
     """pb3d_color_presence_dev: the 2^24-bit colour bitmap of a resident grid (a DeviceBuffer); d_present (8 bytes) gets the bits
     of the table's colours that occur"""
-    from . import device as dev
     A0, A1, A2, Cc = shape
     tab = _colour_table(colors, Cc)
-    d_bm = out if out is not None else dev.DeviceBuffer(_lib.PRESENCE_BYTES)
-    _lib.check(_lib.load().pb3d_color_presence_dev(_lib.ctx(), _ptr(d_grid), A0 * A1 * A2, Cc, C.c_void_p(d_bm.ptr), _lib.p_u8(tab), len(tab),
-                                                   d_present if isinstance(d_present, C.c_void_p) else _ptr(d_present)))
-    return d_bm
+    with dev.Scope() as sc:
+        d_bm = sc.result(out, _lib.PRESENCE_BYTES)
+        _lib.check(_lib.load().pb3d_color_presence_dev(_lib.ctx(), _ptr(d_grid), A0 * A1 * A2, Cc, C.c_void_p(d_bm.ptr), _lib.p_u8(tab), len(tab),
+                                                       _ptr(d_present)))
+        return d_bm
 
 
 def mask_bits_resident(d_mask, npix, colors, d_bitmap=None, out=None):
     """pb3d_mask_bits_dev of a resident (H, W, 3) RGB mask"""
-    from . import device as dev
     tab = _colour_table(colors, 3)
-    d_b = out if out is not None else dev.DeviceBuffer(max(1, int(npix)) * 4)
-    _lib.check(_lib.load().pb3d_mask_bits_dev(_lib.ctx(), C.c_void_p(d_mask.ptr), int(npix), _lib.p_u8(tab), len(tab), _ptr(d_bitmap),
-                                              C.c_void_p(d_b.ptr)))
-    return d_b
+    with dev.Scope() as sc:
+        d_b = sc.result(out, max(1, int(npix)) * 4)
+        _lib.check(_lib.load().pb3d_mask_bits_dev(_lib.ctx(), C.c_void_p(d_mask.ptr), int(npix), _lib.p_u8(tab), len(tab), _ptr(d_bitmap),
+                                                  C.c_void_p(d_b.ptr)))
+        return d_b
 
 
 def iou_rows_resident(rows, npix, d_counts, byte_offset=0):
@@ -250,58 +201,40 @@ def iou_rows_resident(rows, npix, d_counts, byte_offset=0):
     _lib.check(_lib.load().pb3d_iou_rows_dev(_lib.ctx(), C.cast(arr, C.c_void_p), len(rows), int(npix), C.c_void_p(d_counts.ptr + byte_offset)))
 
 
-def _free(*bufs):
-    for b in bufs:
-        if b is not None:
-            b.free()
-
-
 def grid_depth_buffer(voxel_grid, cam, H, W):
     """compute_global_depth_buffer read straight from the grid (NumPy (A0,A1,A2,3) / (A0,A1,A2) labels or DeviceGrid): (H, W) float32"""
-    d_g, shape, owned = _grid(voxel_grid)
-    d_z = depth_buffer_resident(d_g, shape, cam, H, W)
-    try:
+    g, shape = _grid(voxel_grid)
+    with dev.Scope() as sc:
+        d_z = sc.adopt(depth_buffer_resident(_on_device(sc, g), shape, cam, H, W))
         return d_z.download((int(H), int(W)), np.float32)
-    finally:
-        _free(d_z, d_g if owned else None)
 
 
 def grid_visible_bits(voxel_grid, colors, cam, zbuf, H, W, eps=1e-3):
     """(H, W) uint32: bit k = project_part_visible of the voxels of colors[k] against zbuf (which may come from another grid), bit 31
     = of every occupied voxel"""
-    from . import device as dev
     zb = np.ascontiguousarray(zbuf, np.float32)
-    d_g, shape, owned = _grid(voxel_grid)
-    d_zb = dev.from_numpy(zb)
-    d_b = None
-    try:
-        d_b = visible_bits_resident(d_g, shape, colors, cam, d_zb, zb.shape if zb.ndim == 2 else (-1, -1), H, W, eps)
+    g, shape = _grid(voxel_grid)
+    with dev.Scope() as sc:
+        d_g, d_zb = _on_device(sc, g), sc.upload(zb) or sc.alloc(0)
+        d_b = sc.adopt(visible_bits_resident(d_g, shape, colors, cam, d_zb, zb.shape if zb.ndim == 2 else (-1, -1), H, W, eps))
         return d_b.download((int(H), int(W)), np.uint32)
-    finally:
-        _free(d_b, d_zb, d_g if owned else None)
 
 
 def points_visible_bits(lists, cam, zbuf, H, W, eps=1e-3):
     """(H, W) uint32: bit k = project_part_visible(lists[k], cam, zbuf, H, W, eps)"""
-    from . import device as dev
     zb = np.ascontiguousarray(zbuf, np.float32)
-    d_zb = dev.from_numpy(zb)
-    d_b = None
-    try:
-        d_b = points_visible_bits_resident(lists, cam, d_zb, zb.shape if zb.ndim == 2 else (-1, -1), H, W, eps)
+    with dev.Scope() as sc:
+        d_zb = sc.upload(zb) or sc.alloc(0)
+        d_b = sc.adopt(points_visible_bits_resident(lists, cam, d_zb, zb.shape if zb.ndim == 2 else (-1, -1), H, W, eps))
         return d_b.download((int(H), int(W)), np.uint32)
-    finally:
-        _free(d_b, d_zb)
 
 
 def color_presence(voxel_grid):
     """the distinct non-zero values of a grid, as np.unique(axis=0) orders them ((n, 3) uint8 colours, or (n,) labels)"""
-    d_g, shape, owned = _grid(voxel_grid)
-    d_bm = presence_resident(d_g, shape, [])
-    try:
+    g, shape = _grid(voxel_grid)
+    with dev.Scope() as sc:
+        d_bm = sc.adopt(presence_resident(_on_device(sc, g), shape, []))
         words = d_bm.download((_lib.PRESENCE_BYTES // 4,), np.uint32)
-    finally:
-        _free(d_bm, d_g if owned else None)
     keys = np.flatnonzero(np.unpackbits(words.view(np.uint8), bitorder="little"))
     if shape[3] == 1:
         return keys.astype(np.uint8)
@@ -311,22 +244,18 @@ def color_presence(voxel_grid):
 
 def compute_binary_gt(mask_img, voxel_grid):
     """mask pixels whose colour occurs (non-black) in the grid (reference :274-284): the grid's colour set is a device bitmap"""
-    from . import device as dev
     m = np.ascontiguousarray(np.asarray(mask_img)[:, :, :3], np.uint8)
     H, W = m.shape[:2]
-    d_g, shape, owned = _grid(voxel_grid)
+    g, shape = _grid(voxel_grid)
     if shape[3] != 3:
         raise ValueError("compute_binary_gt takes an RGB grid")
-    d_m = dev.from_numpy(m) if m.size else None
-    d_bm = d_b = None
-    try:
-        d_bm = presence_resident(d_g, shape, [])
+    with dev.Scope() as sc:
+        d_g, d_m = _on_device(sc, g), sc.upload(m)
+        d_bm = sc.adopt(presence_resident(d_g, shape, []))
         if d_m is None:
             return np.zeros((H, W), bool)
-        d_b = mask_bits_resident(d_m, H * W, [], d_bm)
+        d_b = sc.adopt(mask_bits_resident(d_m, H * W, [], d_bm))
         return d_b.download((H, W), np.uint32) != 0
-    finally:
-        _free(d_b, d_bm, d_m, d_g if owned else None)
 
 
 # ---- the three evaluations, per monument (plain dicts of table cells) -----------------------------------------------------------------
@@ -362,15 +291,13 @@ def minaret_kp_cells(monument, view, root_voxels, root_masks, cam_dir, part_colo
     from .minarets import (extract_minaret_masks_by_label, extract_minaret_voxels_by_label, extract_top_bottom_image_points,
                            extract_top_bottom_voxel_points)
     print(f"\n🏛️ {monument}")
-    grid = _resident_grid(_paths(root_voxels, f"{monument}_voxel_grid.npz"))
-    try:
+    with dev.Scope() as sc:
+        grid = sc.adopt(_resident_grid(_paths(root_voxels, f"{monument}_voxel_grid.npz")))
         mask_img = _load_mask_for(root_masks, monument, view, grid)
         cams = {tag: load_camera_json(_paths(cam_dir, f"{monument}_camera_params_{tag}.json"), view) for tag in ("init", "kp")}
         cams = {"init": cams["init"], "rep": cams["kp"]}
         colours = [part_colors["front_minarets"], part_colors["back_minarets"]]
         vox_parts = extract_minaret_voxels_by_label(grid, colours)
-    finally:
-        grid.free()
     msk_parts = extract_minaret_masks_by_label(mask_img, colours)
     voxel_kps = extract_top_bottom_voxel_points(vox_parts)
     image_kps = extract_top_bottom_image_points(msk_parts)
@@ -392,12 +319,10 @@ def minaret_kp_cells(monument, view, root_voxels, root_masks, cam_dir, part_colo
 def minaret_iou_cells(monument, view, root_voxels, root_masks, cam_dir, part_colors, visualize=False):
     """{minaret or "Average": "init→kp→final" IoU} of one monument (reference :471-532).  Per camera: the init grid's z-buffer, the
     visible bits of the four int64 minaret sets, and four gated rows; the twelve rows come back in one download."""
-    from . import device as dev
     from .minarets import extract_minaret_masks_by_label, extract_minaret_voxels_by_label
     print(f"\n🏛️ {monument}")
-    grid = _resident_grid(_paths(root_voxels, f"{monument}_voxel_grid.npz"))
-    bufs = []
-    try:
+    with dev.Scope() as sc:
+        grid = sc.adopt(_resident_grid(_paths(root_voxels, f"{monument}_voxel_grid.npz")))
         mask_img = _load_mask_for(root_masks, monument, view, grid)
         H, W = mask_img.shape[:2]
         cams = {"init": load_camera_json(_paths(cam_dir, f"{monument}_camera_params_init.json"), view),
@@ -411,19 +336,16 @@ def minaret_iou_cells(monument, view, root_voxels, root_masks, cam_dir, part_col
         gt = np.zeros((H, W), np.uint32)
         for j, m in enumerate(MINARETS):
             gt |= msk_parts[m].astype(bool).astype(np.uint32) << j
-        d_gt = dev.from_numpy(gt); bufs.append(d_gt)
+        d_gt = sc.upload(gt) or sc.alloc(0)
         shape = grid.shape + (() if len(grid.shape) == 4 else (1,))
         rows = []
         for cam in cams.values():
-            d_z = depth_buffer_resident(grid.buf, shape, cam, H, W); bufs.append(d_z)
-            d_v = points_visible_bits_resident([vox_parts[m] for m in MINARETS], cam, d_z, (H, W), H, W); bufs.append(d_v)
+            d_z = sc.adopt(depth_buffer_resident(grid.buf, shape, cam, H, W))
+            d_v = sc.adopt(points_visible_bits_resident([vox_parts[m] for m in MINARETS], cam, d_z, (H, W), H, W))
             rows += [(d_v, 1 << j, d_gt, 1 << j, d_v, 0xF) for j in range(len(MINARETS))]
-        d_c = dev.DeviceBuffer(len(rows) * 16); bufs.append(d_c)
+        d_c = sc.alloc(len(rows) * 16)
         iou_rows_resident(rows, H * W, d_c)
         counts = d_c.download((len(rows), 2), np.int64)
-    finally:
-        _free(*bufs)
-        grid.free()
     iou = {m: {} for m in MINARETS}
     for c, tag in enumerate(cams):
         for j, m in enumerate(MINARETS):
@@ -438,19 +360,14 @@ def part_minaret_binary_cells(monument, view, root_voxels, deformed_voxels, root
     """{part, "minarets", "whole": "init→deformed" IoU or "--"} of one monument under its final camera (reference :605-738): two grid
     z-buffers, three visible-bit passes (init and deformed grid against their own z-buffer, the init grid against the deformed one for the
     minarets row), the colour set of the init grid, one ground-truth bit image and one row pass; one download."""
-    from . import device as dev
     print(f"\n🏛️ {monument}")
-    g_i = _resident_grid(_paths(root_voxels, f"{monument}_voxel_grid.npz"))
-    g_d = _resident_grid(_paths(deformed_voxels, f"{monument}_deformed_voxel_grid.npz"))
-    bufs = []
-    try:
+    with dev.Scope() as sc:
+        g_i = sc.adopt(_resident_grid(_paths(root_voxels, f"{monument}_voxel_grid.npz")))
+        g_d = sc.adopt(_resident_grid(_paths(deformed_voxels, f"{monument}_deformed_voxel_grid.npz")))
         mask_img = _load_mask_for(root_masks, monument, view, g_i)
         H, W = mask_img.shape[:2]
         cam = load_camera_json(_paths(cam_dir, f"{monument}_camera_params_final.json"), view)
-        counts, present, images = _part_rows(g_i, g_d, mask_img, cam, part_colors, bufs, want_images=visualize)
-    finally:
-        _free(*bufs)
-        g_i.free(); g_d.free()
+        counts, present, images = _part_rows(g_i, g_d, mask_img, cam, part_colors, want_images=visualize)
     cells, r = {}, 0
     for k, part in enumerate(PARTS):
         (i0n, i0u), (i1n, i1u), (_, gt_sum) = counts[r:r + 3]
@@ -472,38 +389,39 @@ def part_minaret_binary_cells(monument, view, root_voxels, deformed_voxels, root
     return cells
 
 
-def _part_rows(g_i, g_d, mask_img, cam, part_colors, bufs, want_images=False):
-    """the device half of part_minaret_binary_cells: counts (rows, 2) int64 and the init grid's part-presence bits"""
-    from . import device as dev
-    H, W = mask_img.shape[:2]
-    colours = [part_colors[p] for p in PARTS] + [part_colors["front_minarets"], part_colors["back_minarets"]]
-    sh_i = g_i.shape + (() if len(g_i.shape) == 4 else (1,))
-    sh_d = g_d.shape + (() if len(g_d.shape) == 4 else (1,))
-    d_m = dev.from_numpy(np.ascontiguousarray(mask_img[:, :, :3])); bufs.append(d_m)
-    nrows = 3 * len(PARTS) + 4
-    d_c = dev.DeviceBuffer(nrows * 16 + 8); bufs.append(d_c)
-    d_present = d_c.at(nrows * 16)
-    d_bm = presence_resident(g_i.buf, sh_i, colours, d_present); bufs.append(d_bm)
-    d_gt = mask_bits_resident(d_m, H * W, colours, d_bm); bufs.append(d_gt)
-    z_i = depth_buffer_resident(g_i.buf, sh_i, cam, H, W); bufs.append(z_i)
-    z_d = depth_buffer_resident(g_d.buf, sh_d, cam, H, W); bufs.append(z_d)
-    v_ii = visible_bits_resident(g_i.buf, sh_i, colours, cam, z_i, (H, W), H, W); bufs.append(v_ii)
-    v_dd = visible_bits_resident(g_d.buf, sh_d, colours, cam, z_d, (H, W), H, W); bufs.append(v_dd)
-    v_id = visible_bits_resident(g_i.buf, sh_i, colours[len(PARTS):], cam, z_d, (H, W), H, W); bufs.append(v_id)
-    rows = []
-    for k in range(len(PARTS)):
-        rows += [(v_ii, 1 << k, d_gt, 1 << k, None, 0), (v_dd, 1 << k, d_gt, 1 << k, None, 0), (None, 0, d_gt, 1 << k, None, 0)]
-    rows += [(v_ii, 3 << 5, d_gt, 3 << 5, None, 0), (v_id, 3, d_gt, 3 << 5, None, 0)]
-    rows += [(v_ii, _ANY, d_gt, _ANY, None, 0), (v_dd, _ANY, d_gt, _ANY, None, 0)]
-    iou_rows_resident(rows, H * W, d_c)
-    raw = d_c.download((nrows * 2 + 1,), np.int64)
-    images = None
-    if want_images:
-        host = {k: b.download((H, W), np.uint32) for k, b in (("gt", d_gt), ("ii", v_ii), ("dd", v_dd), ("id", v_id))}
+def _part_rows(g_i, g_d, mask_img, cam, part_colors, bufs=None, want_images=False):
+    """the device half of part_minaret_binary_cells: counts (rows, 2) int64 and the init grid's part-presence bits.  `bufs` is not read:
+    the buffers live in a scope of this call."""
+    with dev.Scope() as sc:
+        H, W = mask_img.shape[:2]
+        colours = [part_colors[p] for p in PARTS] + [part_colors["front_minarets"], part_colors["back_minarets"]]
+        sh_i = g_i.shape + (() if len(g_i.shape) == 4 else (1,))
+        sh_d = g_d.shape + (() if len(g_d.shape) == 4 else (1,))
+        d_m = sc.upload(mask_img[:, :, :3]) or sc.alloc(0)
+        nrows = 3 * len(PARTS) + 4
+        d_c = sc.alloc(nrows * 16 + 8)
+        d_present = d_c.at(nrows * 16)
+        d_bm = sc.adopt(presence_resident(g_i.buf, sh_i, colours, d_present))
+        d_gt = sc.adopt(mask_bits_resident(d_m, H * W, colours, d_bm))
+        z_i = sc.adopt(depth_buffer_resident(g_i.buf, sh_i, cam, H, W))
+        z_d = sc.adopt(depth_buffer_resident(g_d.buf, sh_d, cam, H, W))
+        v_ii = sc.adopt(visible_bits_resident(g_i.buf, sh_i, colours, cam, z_i, (H, W), H, W))
+        v_dd = sc.adopt(visible_bits_resident(g_d.buf, sh_d, colours, cam, z_d, (H, W), H, W))
+        v_id = sc.adopt(visible_bits_resident(g_i.buf, sh_i, colours[len(PARTS):], cam, z_d, (H, W), H, W))
+        rows = []
+        for k in range(len(PARTS)):
+            rows += [(v_ii, 1 << k, d_gt, 1 << k, None, 0), (v_dd, 1 << k, d_gt, 1 << k, None, 0), (None, 0, d_gt, 1 << k, None, 0)]
+        rows += [(v_ii, 3 << 5, d_gt, 3 << 5, None, 0), (v_id, 3, d_gt, 3 << 5, None, 0)]
+        rows += [(v_ii, _ANY, d_gt, _ANY, None, 0), (v_dd, _ANY, d_gt, _ANY, None, 0)]
+        iou_rows_resident(rows, H * W, d_c)
+        raw = d_c.download((nrows * 2 + 1,), np.int64)
+        images = None
+        if want_images:
+            host = {k: b.download((H, W), np.uint32) for k, b in (("gt", d_gt), ("ii", v_ii), ("dd", v_dd), ("id", v_id))}
 
-        def images(gm, pm_i, pm_d, minarets):
-            return (host["gt"] & gm) != 0, (host["ii"] & pm_i) != 0, (host["id" if minarets else "dd"] & (3 if minarets else pm_d)) != 0
-    return raw[:-1].reshape(nrows, 2), int(raw[-1]), images
+            def images(gm, pm_i, pm_d, minarets):
+                return (host["gt"] & gm) != 0, (host["ii"] & pm_i) != 0, (host["id" if minarets else "dd"] & (3 if minarets else pm_d)) != 0
+        return raw[:-1].reshape(nrows, 2), int(raw[-1]), images
 
 
 # ---- the notebook entry points -------------------------------------------------------------------------------------------------------

@@ -15,7 +15,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _hostmem, _lib
+from . import _hostmem, _lib, device as dev, voxel_carving_utils as vcu, voxel_utils as vu
 
 __all__ = ["Palette", "rgb_to_label", "label_to_rgb", "global_carve_labels", "part_carve_labels", "left_right_guided_carve_labels",
            "extrude_from_surface_labels", "recolor_backward_components_labels", "extract_top_k_components_labels", "partwise_carve_labels", "get_voxel_points_by_parts_labels",
@@ -68,7 +68,6 @@ def _pal(palette):
 
 def rgb_to_label(grid_rgb, palette):
     """(..., 3) uint8 colours -> (...) uint8 labels; ValueError if a colour is neither black nor in the palette."""
-    from . import device as dev
     pal = _pal(palette)
     g = _lib.as_u8(grid_rgb, "grid")
     if g.ndim < 1 or g.shape[-1] != 3:
@@ -77,33 +76,27 @@ def rgb_to_label(grid_rgb, palette):
     out = _hostmem.empty(g.shape[:-1], np.uint8)
     if nvox == 0:
         return out
-    d_in = dev.from_numpy(g); d_out = dev.DeviceBuffer(nvox)
-    try:
+    with dev.Scope() as sc:
+        d_in = sc.upload(g); d_out = sc.alloc(nvox)
         _lib.check(_lib.load().pb3d_rgb_to_label_dev(_lib.ctx(), C.c_void_p(d_in.ptr), nvox, _lib.p_u8(pal.colors), len(pal), C.c_void_p(d_out.ptr)))
         return d_out.download(g.shape[:-1])
-    finally:
-        d_in.free(); d_out.free()
 
 
 def label_to_rgb(labels, palette):
     """(...) uint8 labels -> (..., 3) uint8 colours."""
-    from . import device as dev
     pal = _pal(palette)
     lab = _lib.as_u8(labels, "labels")
     if lab.size == 0:
         return np.zeros(lab.shape + (3,), np.uint8)
-    d_in = dev.from_numpy(lab); d_out = dev.DeviceBuffer(lab.size * 3)
-    try:
+    with dev.Scope() as sc:
+        d_in = sc.upload(lab); d_out = sc.alloc(lab.size * 3)
         _lib.check(_lib.load().pb3d_label_to_rgb_dev(_lib.ctx(), C.c_void_p(d_in.ptr), lab.size, _lib.p_u8(pal.colors), len(pal), C.c_void_p(d_out.ptr)))
         return d_out.download(lab.shape + (3,))
-    finally:
-        d_in.free(); d_out.free()
 
 
 def global_carve_labels(binary_mask, label_mask, angle_interval=90):
     """global_carve (reference utils/voxel_carving_utils.py:269-298) on labels: (w,h,w) uint8 whose expansion with the
     palette is global_carve(binary_mask, palette_image_of(label_mask), angle_interval)."""
-    from . import device as dev
     b = np.asarray(binary_mask)
     if b.ndim != 2:
         raise ValueError("binary_mask must be (h,w)")
@@ -113,21 +106,16 @@ def global_carve_labels(binary_mask, label_mask, angle_interval=90):
         raise ValueError(f"label mask shape {lm.shape} does not match (h,w)=({h},{w})")
     if isinstance(angle_interval, (bool, np.bool_)) or not isinstance(angle_interval, (int, np.integer)) or angle_interval <= 0:
         raise ValueError("angle_interval must be a positive integer")
-    d_b = dev.from_numpy(_lib.truth_u8(b)); d_l = dev.from_numpy(lm); d_out = dev.DeviceBuffer(max(1, w * h * w))
-    try:
+    with dev.Scope() as sc:
+        d_b = sc.upload(_lib.truth_u8(b)) or sc.alloc(0); d_l = sc.upload(lm) or sc.alloc(0); d_out = sc.alloc(max(1, w * h * w))
         _lib.check(_lib.load().pb3d_global_carve_label_dev(_lib.ctx(), C.c_void_p(d_b.ptr), C.c_void_p(d_l.ptr), h, w, int(min(angle_interval, 91)),
                                                            C.c_void_p(d_out.ptr)))
         return d_out.download((w, h, w))
-    finally:
-        for d in (d_b, d_l, d_out):
-            d.free()
 
 
 def part_carve_labels(label_grid, label_mask, group_jobs, palette):
     """part_carve (reference utils/voxel_carving_utils.py:139-160) on labels.  group_jobs as upstream: [(part names, angle)];
     the names are looked up in the palette."""
-    from . import device as dev
-    from .voxel_carving_utils import _mask_to_wh
     pal = _pal(palette)
     g = _lib.as_u8(label_grid, "label_grid")
     if g.ndim != 3:
@@ -147,23 +135,18 @@ def part_carve_labels(label_grid, label_mask, group_jobs, palette):
         if m.shape != (W, H):
             raise ValueError(f"operands could not be broadcast together: mask {m.shape} vs grid ({W},{H})")
         msub[j] = m
-        mcarve[j] = _mask_to_wh(m, W, H)
+        mcarve[j] = vcu._mask_to_wh(m, W, H)
     if g.size == 0:
         return np.zeros_like(g)
-    d_g = dev.from_numpy(g); d_ms = dev.from_numpy(msub); d_mc = dev.from_numpy(mcarve); d_out = dev.DeviceBuffer(g.size)
-    try:
+    with dev.Scope() as sc:
+        d_g = sc.upload(g); d_ms = sc.upload(msub); d_mc = sc.upload(mcarve); d_out = sc.alloc(g.size)
         _lib.check(_lib.load().pb3d_part_carve_label_dev(_lib.ctx(), C.c_void_p(d_g.ptr), W, H, D, C.c_void_p(d_ms.ptr), C.c_void_p(d_mc.ptr), angles,
                                                          skip, nj, C.c_void_p(d_out.ptr)))
         return d_out.download(g.shape)
-    finally:
-        for d in (d_g, d_ms, d_mc, d_out):
-            d.free()
 
 
 # ---- the rest of the notebook-1 chain and the point extraction on label volumes (row N3: "a 1-byte label volume end to end") --------
 def _part_carve_labels_dev(d_g, shape3, label_mask, group_jobs, pal, d_out):
-    from . import device as dev
-    from .voxel_carving_utils import _mask_to_wh
     W, H, D = shape3
     lm = _lib.as_u8(label_mask, "label_mask")
     nj = len(group_jobs)
@@ -179,22 +162,18 @@ def _part_carve_labels_dev(d_g, shape3, label_mask, group_jobs, pal, d_out):
         if m.shape != (W, H):
             raise ValueError(f"operands could not be broadcast together: mask {m.shape} vs grid ({W},{H})")
         msub[j] = m
-        mcarve[j] = _mask_to_wh(m, W, H)
-    d_ms = dev.from_numpy(msub); d_mc = dev.from_numpy(mcarve)
-    try:
+        mcarve[j] = vcu._mask_to_wh(m, W, H)
+    with dev.Scope() as sc:
+        d_ms = sc.upload(msub) or sc.alloc(0); d_mc = sc.upload(mcarve) or sc.alloc(0)
         _lib.check(_lib.load().pb3d_part_carve_label_dev(_lib.ctx(), C.c_void_p(d_g.ptr), W, H, D, C.c_void_p(d_ms.ptr), C.c_void_p(d_mc.ptr), angles,
                                                          skip, nj, C.c_void_p(d_out.ptr)))
         dev.sync()
-    finally:
-        d_ms.free(); d_mc.free()
 
 
 def left_right_guided_carve_labels(label_grid, label_mask, target_label, angle=60, log_color=None):
     """left_right_guided_carve (reference utils/voxel_carving_utils.py:163-210) on a (W,H,D) label volume: the components of
     `target_label`, each carved against label_mask == target_label.  Prints upstream's log (log_color: what to print in the
     "[colour]" place, default the label)."""
-    from . import device as dev
-    from .voxel_carving_utils import _lrgc_dev
     g = _lib.as_u8(label_grid, "label_grid")
     if g.ndim != 3:
         raise ValueError("label_grid must be (W,H,D)")
@@ -204,54 +183,44 @@ def left_right_guided_carve_labels(label_grid, label_mask, target_label, angle=6
     if not np.any(mask2d):
         print(f"[SKIP] No mask for color {shown}")
         return g.copy()
-    d_g = dev.from_numpy(g)
-    try:
-        d_r = _lrgc_dev(d_g, g.shape, mask2d, shown, angle, label=int(target_label))
+    with dev.Scope() as sc:
+        d_g = sc.upload(g) or sc.alloc(0)
+        d_r = vcu._lrgc_dev(d_g, g.shape, mask2d, shown, angle, label=int(target_label))
+        if d_r is not d_g:
+            sc.adopt(d_r)
         return d_r.download(g.shape)
-    finally:
-        d_g.free()
 
 
 def extrude_from_surface_labels(label_grid, mask_2d, axis, direction="+", depth=5, fill_label=None):
     """extrude_from_surface (reference :213-248) on a label volume; fill_label None clears."""
-    from . import device as dev
-    from .voxel_carving_utils import _extrude_args, _extrude_dev
     g = _lib.as_u8(label_grid, "label_grid")
     if g.ndim != 3:
         raise ValueError("label_grid must be (W,H,D)")
     if axis not in (0, 2) or int(depth) <= 0:
         return g.copy()
-    vt, vw = _extrude_args(g.shape, mask_2d, axis, direction)
-    d_in = dev.from_numpy(g); d_out = dev.DeviceBuffer(g.size)
-    try:
-        _extrude_dev(d_in, d_out, g.shape, vt, vw, axis, direction, depth, fill_label, label=True)
+    vt, vw = vcu._extrude_args(g.shape, mask_2d, axis, direction)
+    with dev.Scope() as sc:
+        d_in = sc.upload(g) or sc.alloc(0); d_out = sc.alloc(g.size)
+        vcu._extrude_dev(d_in, d_out, g.shape, vt, vw, axis, direction, depth, fill_label, label=True)
         return d_out.download(g.shape)
-    finally:
-        d_in.free(); d_out.free()
 
 
 def recolor_backward_components_labels(label_grid, label, new_label, k=4, sort_axis=2):
     """recolor_backward_components (reference :252-266) on a label volume (any axis order; returns a C-contiguous copy)."""
-    from . import device as dev
-    from .voxel_carving_utils import _recolor_dev
     g = np.ascontiguousarray(_lib.as_u8(label_grid, "label_grid"))
     if g.ndim != 3:
         raise ValueError("label_grid must be 3-D")
     if g.size == 0:
         return g.copy()
-    d_g = dev.from_numpy(g)
-    try:
-        _recolor_dev(d_g, g.shape, int(label), int(new_label), k, sort_axis, label=True)
+    with dev.Scope() as sc:
+        d_g = sc.upload(g)
+        vcu._recolor_dev(d_g, g.shape, int(label), int(new_label), k, sort_axis, label=True)
         return d_g.download(g.shape)
-    finally:
-        d_g.free()
 
 
 def extract_top_k_components_labels(label_grid, label, k=4):
     """extract_top_k_components (reference utils/voxel_utils.py:24-33) on a label volume: the k tallest 26-connected components of
     `label` are kept, the other voxels of that label become 0 (returns a C-contiguous copy)."""
-    from . import device as dev
-    from .voxel_utils import _top_k_dev
     g = _lib.as_u8(label_grid, "label_grid")
     if g.ndim != 3:
         raise ValueError("label_grid must be 3-D")
@@ -260,12 +229,10 @@ def extract_top_k_components_labels(label_grid, label, k=4):
     lv = np.asarray(label).reshape(-1)
     if g.size == 0 or lv.size != 1 or not (0 <= lv[0] <= 255) or lv[0] != np.round(lv[0]):
         return np.ascontiguousarray(g).copy()
-    d_g = dev.from_numpy(g)
-    try:
-        _top_k_dev(d_g, g.shape, int(lv[0]), k, 1)
+    with dev.Scope() as sc:
+        d_g = sc.upload(g)
+        vu._top_k_dev(d_g, g.shape, int(lv[0]), k, 1)
         return d_g.download(g.shape)
-    finally:
-        d_g.free()
 
 
 def partwise_carve_labels(label_grid, label_mask_exterior, label_mask_full, palette, group_jobs, part_symmetry, extrusion_depths,
@@ -273,31 +240,26 @@ def partwise_carve_labels(label_grid, label_mask_exterior, label_mask_full, pale
     """partwise_carve (reference utils/voxel_carving_utils.py:302-400) on a (W,H,D) label volume, resident from the first stage to
     the last at ONE byte per voxel.  Returns (D,H,W) labels (transposed + flipped, as upstream) when the back-minaret recolouring
     runs, else (W,H,D); label_to_rgb of it is partwise_carve of the RGB grid, byte for byte (the printed log names the colours)."""
-    from . import device as dev
-    from .voxel_carving_utils import _extrude_args, _extrude_dev, _GuidedParts, _recolor_dev, _recolor_queue
     pal = _pal(palette)
     g = _lib.as_u8(label_grid, "label_grid")
     if g.ndim != 3:
         raise ValueError("label_grid must be (W,H,D)")
     W, H, D = g.shape
     lme = _lib.as_u8(label_mask_exterior, "label_mask_exterior"); lmf = _lib.as_u8(label_mask_full, "label_mask_full")
-    d_in = dev.from_numpy(g); d_a = dev.DeviceBuffer(g.size)
-    live = [d_in, d_a]
-    guided = None
-    try:
+    with dev.Scope() as sc:
+        d_in = sc.upload(g) or sc.alloc(0); d_a = sc.alloc(g.size)
         _part_carve_labels_dev(d_in, (W, H, D), lme, group_jobs, pal, d_a)
         # all part labels in ONE labelling, their component loops queued behind it (voxel_carving_utils._GuidedParts)
-        d_lab = dev.DeviceBuffer(W * H * D * 4)
-        live.append(d_lab)
+        d_lab = sc.alloc(W * H * D * 4)
         parts = []
         for part, angle in part_symmetry.items():
             lab = pal.label_of(part)
             parts.append((pal.colors[lab - 1], lme == lab, angle, int(lab)))
-        guided = _GuidedParts(d_a, (W, H, D), parts, d_lab, channels=1)
+        guided = sc.adopt(vcu._GuidedParts(d_a, (W, H, D), parts, d_lab, channels=1))
         d_b = guided.run()
         if d_b is not d_a:
-            live.append(d_b)
-            d_a.free(); live.remove(d_a)
+            sc.adopt(d_b)
+            sc.free(d_a)
             d_a = d_b
         for part, depth in extrusion_depths.items():
             if int(depth) <= 0:
@@ -305,57 +267,46 @@ def partwise_carve_labels(label_grid, label_mask_exterior, label_mask_full, pale
             lab = pal.label_of(part)
             mask = lmf == lab
             for axis in (2, 0):
-                vt, vw = _extrude_args((W, H, D), mask, axis, "+")
-                d_v = dev.from_numpy_async(vt)
-                try:
-                    for direction in ("+", "-"):
-                        _extrude_dev(d_a, d_a, (W, H, D), vt, vw, axis, direction, depth, lab, d_valid=d_v, label=True)
-                finally:
-                    d_v.free()
+                vt, vw = vcu._extrude_args((W, H, D), mask, axis, "+")
+                d_v = sc.upload(vt, wait=False) or sc.alloc(0)
+                for direction in ("+", "-"):
+                    vcu._extrude_dev(d_a, d_a, (W, H, D), vt, vw, axis, direction, depth, lab, d_valid=d_v, label=True)
+                sc.free(d_v)
         if recolor_back_minarets:
             _lib.check(_lib.load().pb3d_orient_label_dev(_lib.ctx(), C.c_void_p(d_a.ptr), W, H, D, C.c_void_p(d_in.ptr)))
             fm, bm = pal.label_of("front_minarets"), pal.label_of("back_minarets")
-            queued = _recolor_queue(d_in, (D, H, W), fm, bm, 2, 0, d_lab, guided.status_ptr(), label=True)
+            queued = vcu._recolor_queue(d_in, (D, H, W), fm, bm, 2, 0, d_lab, guided.status_ptr(), label=True)
             status = guided.finish(with_status=queued)
             if queued and status[1]:
-                _recolor_dev(d_in, (D, H, W), fm, bm, 2, 0, label=True)
+                vcu._recolor_dev(d_in, (D, H, W), fm, bm, 2, 0, label=True)
             return d_in.download((D, H, W))
         guided.finish()
         return d_a.download(g.shape)
-    finally:
-        if guided is not None:
-            guided.free()
-        for b in live:
-            b.free()
 
 
 def _points_labels(label_grid, labels_sel, stride, pal):
-    from . import device as dev
+    """(points, palette colours) of the voxels whose label is in labels_sel; None selects every occupied voxel"""
     g = _lib.as_u8(label_grid, "label_grid")
     if g.ndim != 3:
         raise ValueError("label_grid must be 3-D")
     A0, A1, A2 = g.shape
-    sel = np.ascontiguousarray(np.asarray(labels_sel, np.uint8))
-    if g.size == 0 or sel.size == 0:
+    sel = None if labels_sel is None else np.ascontiguousarray(np.asarray(labels_sel, np.uint8))
+    if g.size == 0 or (sel is not None and sel.size == 0):
         return np.zeros((0, 3), np.float32), np.zeros((0, 3), np.uint8)
     lib, ctx = _lib.load(), _lib.ctx()
-    d_g = dev.from_numpy(g)
+    p_sel, n_sel = (None, 0) if sel is None else (_lib.p_u8(sel), int(sel.size))
     n = C.c_int64(0)
-    try:
-        _lib.check(lib.pb3d_points_count_dev(ctx, C.c_void_p(d_g.ptr), A0, A1, A2, 1, _lib.p_u8(sel) if sel.size else None, int(sel.size), int(stride), C.byref(n)))
+    with dev.Scope() as sc:
+        d_g = sc.upload(g)
+        _lib.check(lib.pb3d_points_count_dev(ctx, C.c_void_p(d_g.ptr), A0, A1, A2, 1, p_sel, n_sel, int(stride), C.byref(n)))
         if n.value == 0:
             return np.zeros((0, 3), np.float32), np.zeros((0, 3), np.uint8)
-        d_p = dev.DeviceBuffer(n.value * 12); d_l = dev.DeviceBuffer(n.value); d_c = dev.DeviceBuffer(n.value * 3)
-        try:
-            _lib.check(lib.pb3d_points_fill_dev(ctx, C.c_void_p(d_g.ptr), A0, A1, A2, 1, _lib.p_u8(sel) if sel.size else None, int(sel.size), int(stride),
-                                                n.value, C.c_void_p(d_p.ptr), C.c_void_p(d_l.ptr)))
-            # the points' colours: their labels expanded with the palette, on the device
-            _lib.check(lib.pb3d_label_to_rgb_dev(ctx, C.c_void_p(d_l.ptr), n.value, _lib.p_u8(pal.colors), len(pal), C.c_void_p(d_c.ptr)))
-            return d_p.download((n.value, 3), np.float32), d_c.download((n.value, 3))
-        finally:
-            d_p.free(); d_l.free(); d_c.free()
-    finally:
-        d_g.free()
+        d_p = sc.alloc(n.value * 12); d_l = sc.alloc(n.value); d_c = sc.alloc(n.value * 3)
+        _lib.check(lib.pb3d_points_fill_dev(ctx, C.c_void_p(d_g.ptr), A0, A1, A2, 1, p_sel, n_sel, int(stride), n.value, C.c_void_p(d_p.ptr),
+                                            C.c_void_p(d_l.ptr)))
+        # the points' colours: their labels expanded with the palette, on the device
+        _lib.check(lib.pb3d_label_to_rgb_dev(ctx, C.c_void_p(d_l.ptr), n.value, _lib.p_u8(pal.colors), len(pal), C.c_void_p(d_c.ptr)))
+        return d_p.download((n.value, 3), np.float32), d_c.download((n.value, 3))
 
 
 def get_voxel_points_by_parts_labels(label_grid, palette, part_names):
@@ -371,47 +322,22 @@ def voxel_grid_to_points_labels(label_grid, palette, stride=2):
     points scaled by the stride.  Returns (pts, colours, shape) like upstream."""
     pal = _pal(palette)
     g = _lib.as_u8(label_grid, "label_grid")
-    pts, cols = _points_labels_occ(g, stride, pal)
     W, H, D = g.shape
+    pts, cols = _points_labels(g, None, stride, pal)
     return pts, cols, (H, W, D)          # (upstream unpacks W, H, D = shape[:3] and returns them in this order, :37 / :51)
-
-
-def _points_labels_occ(g, stride, pal):
-    from . import device as dev
-    A0, A1, A2 = g.shape
-    if g.size == 0:
-        return np.zeros((0, 3), np.float32), np.zeros((0, 3), np.uint8)
-    lib, ctx = _lib.load(), _lib.ctx()
-    d_g = dev.from_numpy(g)
-    n = C.c_int64(0)
-    try:
-        _lib.check(lib.pb3d_points_count_dev(ctx, C.c_void_p(d_g.ptr), A0, A1, A2, 1, None, 0, int(stride), C.byref(n)))
-        if n.value == 0:
-            return np.zeros((0, 3), np.float32), np.zeros((0, 3), np.uint8)
-        d_p = dev.DeviceBuffer(n.value * 12); d_l = dev.DeviceBuffer(n.value); d_c = dev.DeviceBuffer(n.value * 3)
-        try:
-            _lib.check(lib.pb3d_points_fill_dev(ctx, C.c_void_p(d_g.ptr), A0, A1, A2, 1, None, 0, int(stride), n.value, C.c_void_p(d_p.ptr),
-                                                C.c_void_p(d_l.ptr)))
-            _lib.check(lib.pb3d_label_to_rgb_dev(ctx, C.c_void_p(d_l.ptr), n.value, _lib.p_u8(pal.colors), len(pal), C.c_void_p(d_c.ptr)))
-            return d_p.download((n.value, 3), np.float32), d_c.download((n.value, 3))
-        finally:
-            d_p.free(); d_l.free(); d_c.free()
-    finally:
-        d_g.free()
 
 
 def meshify_colored_voxel_grid_labels(label_grid, palette, stride=1):
     """meshify_colored_voxel_grid of a 1-byte label volume (label 0 empty, label k = palette colour k-1): the same mesh from a
     third of the bytes, equal to meshify_colored_voxel_grid(label_to_rgb(label_grid, palette), stride)."""
-    from .voxel_utils import _mesh_host, mesh_check, mesh_colors
     pal = _pal(palette)
     lab = np.asarray(label_grid)
     if lab.ndim != 3:
         raise ValueError("label_grid must be (A0, A1, A2)")
-    stride = mesh_check(lab.shape, stride)
+    stride = vu.mesh_check(lab.shape, stride)
     lab = _lib.as_u8(lab, "label_grid")
-    verts, faces, normals, labs = _mesh_host(lab, 1, stride)
+    verts, faces, normals, labs = vu._mesh_host(lab, 1, stride)
     table = np.concatenate([np.zeros((1, 3), np.uint8), np.asarray(pal.colors, np.uint8).reshape(-1, 3)])
     if int(labs.max(initial=0)) >= len(table):
         raise ValueError("label_grid holds labels beyond the palette")
-    return verts, faces, mesh_colors(table[labs[:, 0]]), normals
+    return verts, faces, vu.mesh_colors(table[labs[:, 0]]), normals

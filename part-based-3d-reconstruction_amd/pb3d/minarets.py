@@ -8,7 +8,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, device as dev, voxel_carving_utils as vcu, voxel_utils as vu
+from ._args import _on_device
 
 __all__ = ["extract_minaret_voxels_by_label", "extract_minaret_masks_by_label", "extract_top_bottom_voxel_points",
            "extract_top_bottom_image_points", "extract_minaret_kps_for_view"]
@@ -23,14 +24,12 @@ class _Labelling:
     and current() re-makes that volume when a later call has overwritten it (labels are numbered per colour, deterministically)."""
 
     def __init__(self, d_g, shape3, cols, d_lab, connectivity, cap):
-        from .voxel_utils import _RECORDS_MAX, _label_stats_conn
-        from .voxel_carving_utils import _component_stats
         self.d_g, self.shape3, self.cols, self.d_lab, self.conn = d_g, shape3, cols, d_lab, connectivity
         self.recs = [None] * len(cols)
         self.cur = None
         for s in range(0, len(cols), _MAX_SEL):
             chunk = list(range(s, min(s + _MAX_SEL, len(cols))))
-            st = _label_stats_conn(d_g, shape3, [cols[i] for i in chunk], d_lab, connectivity, cap=cap, members_only=True)
+            st = vu._label_stats_conn(d_g, shape3, [cols[i] for i in chunk], d_lab, connectivity, cap=cap, members_only=True)
             self.cur = ("chunk", s)
             for i, (n, bbox, cnt, sums) in zip(chunk, st):
                 self.recs[i] = (int(n), bbox, cnt, sums, self.cur)
@@ -38,27 +37,25 @@ class _Labelling:
                 if bbox is not None:
                     continue
                 # more components than the records hold: this colour alone, a full label volume, then the statistics pass if still needed
-                n, bbox, cnt, sums = _label_stats_conn(d_g, shape3, [cols[i]], d_lab, connectivity, cap=min(int(n), _RECORDS_MAX))[0]
+                n, bbox, cnt, sums = vu._label_stats_conn(d_g, shape3, [cols[i]], d_lab, connectivity, cap=min(int(n), vu._RECORDS_MAX))[0]
                 if bbox is None:
-                    bbox, cnt, sums = _component_stats(d_lab, shape3, int(n))
+                    bbox, cnt, sums = vcu._component_stats(d_lab, shape3, int(n))
                 self.cur = ("solo", i)
                 self.recs[i] = (int(n), bbox, cnt, sums, self.cur)
 
     def current(self, group):
-        from .voxel_utils import _label_stats_conn
         if group != self.cur:
             kind, i = group
             idx = list(range(i, min(i + _MAX_SEL, len(self.cols)))) if kind == "chunk" else [i]
-            _label_stats_conn(self.d_g, self.shape3, [self.cols[j] for j in idx], self.d_lab, self.conn, cap=1, members_only=kind == "chunk")
+            vu._label_stats_conn(self.d_g, self.shape3, [self.cols[j] for j in idx], self.d_lab, self.conn, cap=1, members_only=kind == "chunk")
             self.cur = group
 
 
 def _distinct(colors):
     """per given colour the index of its distinct uint8 colour (None: a colour no uint8 voxel can equal), and the distinct colours"""
-    from .voxel_carving_utils import _color_u8
     cols, index, where = [], {}, []
     for c in colors:
-        cu8 = _color_u8(c)
+        cu8 = vcu._color_u8(c)
         if cu8 is None:
             where.append(None)
             continue
@@ -73,7 +70,6 @@ def _distinct(colors):
 def _members(lab, sel, outputs):
     """pb3d_component_members_dev for the selections sel = [(colour index, label, bbox row, count)], grouped by the labelling that holds
     them.  Returns per selection a dict with "coords" (int64 (n, 3)), "rows" (int64 (2, 4)) and / or "mask" (uint8 (A0, A1, A2))."""
-    from . import device as dev
     A0, A1, A2 = lab.shape3
     nvox = A0 * A1 * A2
     out = [dict() for _ in sel]
@@ -90,14 +86,10 @@ def _members(lab, sel, outputs):
         bbox = np.ascontiguousarray(np.stack([sel[j][2] for j in js]), np.int64)
         counts = np.ascontiguousarray([sel[j][3] for j in js], np.int64)
         ntot = int(counts.sum())
-        bufs = []
-        try:
-            d_coords = dev.DeviceBuffer(max(ntot, 1) * 24) if outputs & _COORDS else None
-            bufs.append(d_coords)
-            d_rows = dev.DeviceBuffer(k * 64) if outputs & _ROWS else None
-            bufs.append(d_rows)
-            d_masks = dev.DeviceBuffer(max(k * nvox, 1)) if outputs & _MASK else None
-            bufs.append(d_masks)
+        with dev.Scope() as sc:
+            d_coords = sc.alloc(max(ntot, 1) * 24) if outputs & _COORDS else None
+            d_rows = sc.alloc(k * 64) if outputs & _ROWS else None
+            d_masks = sc.alloc(max(k * nvox, 1)) if outputs & _MASK else None
             ptr = lambda b: None if b is None else C.c_void_p(b.ptr)
             _lib.check(_lib.load().pb3d_component_members_dev(
                 _lib.ctx(), C.c_void_p(lab.d_g.ptr), A0, A1, A2, 3, C.c_void_p(lab.d_lab.ptr), k, _lib.p_u8(cols),
@@ -116,26 +108,15 @@ def _members(lab, sel, outputs):
                 m = d_masks.download((k, A0, A1, A2), np.uint8)
                 for q, j in enumerate(js):
                     out[j]["mask"] = m[q]
-        finally:
-            for b in bufs:
-                if b is not None:
-                    b.free()
     return out
 
 
-def _resident(grid, what):
-    """(device buffer, shape, owned) of a NumPy (A0, A1, A2, 3) uint8 grid or a pb3d.device.DeviceGrid"""
-    from . import device as dev
-    if isinstance(grid, dev.DeviceGrid):
-        g, owned = grid, False
-    else:
-        g, owned = _lib.as_u8(grid, what), True
+def _rgb_grid(grid, what):
+    """(the DeviceGrid or the uint8 array to upload, lattice shape) of a NumPy (A0, A1, A2, 3) uint8 grid or a pb3d.device.DeviceGrid"""
+    g = grid if isinstance(grid, dev.DeviceGrid) else _lib.as_u8(grid, what)
     if len(g.shape) != 4 or g.shape[3] != 3:
         raise ValueError(f"{what} must be (A0,A1,A2,3)")
-    shape3 = tuple(int(v) for v in g.shape[:3])
-    if not owned:
-        return g.buf, shape3, False
-    return (dev.from_numpy(g) if g.size else None), shape3, True
+    return g, tuple(int(v) for v in g.shape[:3])
 
 
 def _four_minarets(lab, where):
@@ -159,20 +140,15 @@ def _four_minarets(lab, where):
 
 def _minaret_voxels(voxel_grid, minaret_colors, outputs):
     """the four minarets of extract_minaret_voxels_by_label: {"LM1", "LM2", "RM1", "RM2": _members' outputs for that component}"""
-    from . import device as dev
-    d_g, shape3, owned = _resident(voxel_grid, "voxel_grid")
-    cols, where = _distinct(minaret_colors)
-    nvox = int(np.prod(shape3, dtype=np.int64))
-    d_lab = dev.DeviceBuffer(max(nvox, 1) * 4) if nvox and cols else None
-    try:
+    g, shape3 = _rgb_grid(voxel_grid, "voxel_grid")
+    with dev.Scope() as sc:
+        d_g = _on_device(sc, g)
+        cols, where = _distinct(minaret_colors)
+        nvox = int(np.prod(shape3, dtype=np.int64))
+        d_lab = sc.alloc(max(nvox, 1) * 4) if nvox and cols else None
         lab = _Labelling(d_g, shape3, cols, d_lab, 6, 1024) if d_lab is not None else None
         got = _members(lab, _four_minarets(lab, where), outputs)
         return dict(zip(("LM1", "LM2", "RM1", "RM2"), got))
-    finally:
-        if d_lab is not None:
-            d_lab.free()
-        if owned and d_g is not None:
-            d_g.free()
 
 
 def extract_minaret_voxels_by_label(voxel_grid, minaret_colors):
@@ -191,7 +167,6 @@ def extract_minaret_voxels_by_label(voxel_grid, minaret_colors):
 
 def _mask_regions(image, minaret_colors, min_area):
     """the chosen regions of extract_minaret_masks_by_label: [(name, region)], region = (colour index, label, bbox, count)"""
-    from . import device as dev
     img = _lib.as_u8(image, "image")
     if img.ndim != 3 or img.shape[2] < 3:
         raise ValueError("image must be (H, W, 3) or (H, W, 4)")
@@ -199,9 +174,9 @@ def _mask_regions(image, minaret_colors, min_area):
     H, W = rgb.shape[:2]
     shape3 = (1, H, W)
     cols, where = _distinct(minaret_colors)
-    d_g = dev.from_numpy(rgb) if H * W and cols else None
-    d_lab = dev.DeviceBuffer(H * W * 4) if d_g is not None else None
-    try:
+    with dev.Scope() as sc:
+        d_g = sc.upload(rgb) if cols else None
+        d_lab = sc.alloc(H * W * 4) if d_g is not None else None
         # skimage.measure.label's default connectivity is ndim (8 neighbours in 2-D): the 26-connected labelling of the (1, H, W) view
         lab = _Labelling(d_g, shape3, cols, d_lab, 26, 4096) if d_g is not None else None
         regions = []
@@ -230,10 +205,6 @@ def _mask_regions(image, minaret_colors, min_area):
         chosen = [(name, r) for name, r in (("LM1", lm1), ("RM1", rm1), ("LM2", lm2), ("RM2", rm2)) if r is not None]
         got = _members(lab, [r["sel"] for _, r in chosen], _MASK)
         return {name: g["mask"].reshape(H, W) for (name, _), g in zip(chosen, got)}
-    finally:
-        for b in (d_lab, d_g):
-            if b is not None:
-                b.free()
 
 
 def extract_minaret_masks_by_label(image, minaret_colors, min_area=50):

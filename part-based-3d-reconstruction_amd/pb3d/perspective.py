@@ -12,9 +12,10 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
-from .device import _ptr
-from .eval_helpers_intra import _cam, _colour_table, _eps_f32, _free, _grid, depth_buffer_resident
+from . import _lib, device as dev
+from ._args import _cam, _colour_table, _eps_f32, _grid, _grid_shape, _on_device
+from ._lib import _ptr
+from .eval_helpers_intra import depth_buffer_resident
 
 __all__ = ["perspective_carve", "perspective_carve_resident", "pack_mask_bits", "perspective_paint", "perspective_paint_resident"]
 
@@ -46,7 +47,6 @@ class _DeviceMaskBits:
     the same masks again and again (tools/pcarvebench.py) makes them once and passes them in place of the masks."""
 
     def __init__(self, mask):
-        from . import device as dev
         bits = pack_mask_bits(mask)
         self.H, self.W = int(bits.shape[0]), int(np.asarray(mask).shape[1])
         self.buf = dev.from_numpy_async(bits)
@@ -84,31 +84,20 @@ def _fill_view(rec, cam):
     return prec
 
 
-def _grid_shape(voxel_grid):
-    from . import device as dev
-    grid_shape = tuple(voxel_grid.shape if isinstance(voxel_grid, dev.DeviceGrid) else np.shape(voxel_grid))
-    if len(grid_shape) not in (3, 4) or (len(grid_shape) == 4 and grid_shape[3] != 3):
-        raise ValueError("voxel_grid must be (A0,A1,A2,3) RGB or (A0,A1,A2) labels")
-    return grid_shape
-
-
 def _rewritten(voxel_grid, grid_shape, nviews, return_counts, run):
     """The tail of perspective_carve / perspective_paint, once every argument is checked: run(d_grid, shape, d_out, d_counts) rewrites
     the resident grid into a new buffer; the result is downloaded, or wrapped as a DeviceGrid for a DeviceGrid."""
-    from . import device as dev
-    d_g, shape, owned = _grid(voxel_grid)
-    d_out = d_cnt = None
-    try:
-        d_out = dev.DeviceBuffer(max(1, int(np.prod(shape, dtype=np.int64))))
-        d_cnt = dev.DeviceBuffer(8 * max(1, nviews)) if return_counts else None
+    g, shape = _grid(voxel_grid)
+    with dev.Scope() as sc:
+        d_g = _on_device(sc, g)
+        d_out = sc.alloc(max(1, int(np.prod(shape, dtype=np.int64))))
+        d_cnt = sc.alloc(8 * max(1, nviews)) if return_counts else None
         run(d_g, shape, d_out, d_cnt if nviews else None)
         counts = d_cnt.download((nviews,), np.int64) if return_counts else None
         if isinstance(voxel_grid, dev.DeviceGrid):
-            res, d_out = dev.DeviceGrid(d_out, grid_shape), None
+            res = dev.DeviceGrid(sc.keep(d_out), grid_shape)
         else:
             res = d_out.download(grid_shape)
-    finally:
-        _free(d_out, d_cnt, d_g if owned else None)
     return (res, counts) if return_counts else res
 
 
@@ -123,21 +112,15 @@ def perspective_carve_resident(d_grid, shape, views, colors=None, outside="carve
     tab, ncol = _subject_table(colors, Cc)
     views = list(views)
     arr = (_lib.CarveView * max(1, len(views)))()
-    owned = []
-    try:
+    with dev.Scope() as sc:     # (the context's pool hands a freed block out again only behind this stream's work)
         for k, (mask, cam) in enumerate(views):
-            mb = mask if isinstance(mask, _DeviceMaskBits) else _DeviceMaskBits(mask)
-            if mb is not mask:
-                owned.append(mb)
+            mb = mask if isinstance(mask, _DeviceMaskBits) else sc.adopt(_DeviceMaskBits(mask))
             _fill_view(arr[k], cam)
             arr[k].Himg, arr[k].Wimg, arr[k].d_maskbits = mb.H, mb.W, mb.buf.ptr
         dst = d_grid if out is None else out
         _lib.check(_lib.load().pb3d_perspective_carve_resident(_lib.ctx(), _ptr(d_grid), A0, A1, A2, Cc, _lib.p_u8(tab) if ncol else None, ncol,
                                                                C.cast(arr, C.c_void_p), len(views), keep, _ptr(dst), _ptr(d_removed)))
         return dst
-    finally:
-        for mb in owned:        # the context's pool hands a freed block out again only behind this stream's work
-            mb.free()
 
 
 def perspective_carve(voxel_grid, views, colors=None, outside="carve", return_counts=False):
@@ -170,7 +153,6 @@ class _DeviceImage:
     caller whose image is resident already wraps it: _DeviceImage(DeviceBuffer or pointer into one, H, W)."""
 
     def __init__(self, image, H=None, W=None):
-        from . import device as dev
         if H is None:
             img = _lib.as_u8(image, "a view's image")
             self.H, self.W = int(img.shape[0]), int(img.shape[1])
@@ -228,21 +210,15 @@ def perspective_paint_resident(d_grid, shape, views, d_zbufs, colors=None, skip=
         raise ValueError(f"{len(views)} views but {len(d_zbufs)} z-buffers")
     arr = (_lib.PaintView * max(1, len(views)))()
     eps_f32 = max([_eps_f32(_fill_view(arr[k], cam), eps) for k, (_, cam) in enumerate(views)], default=0)     # read by float32 cameras only
-    owned = []
-    try:
+    with dev.Scope() as sc:     # (the context's pool hands a freed block out again only behind this stream's work)
         for k, ((image, _), (H, W)) in enumerate(zip(views, sizes)):
-            im = image if isinstance(image, _DeviceImage) else _DeviceImage(image)
-            if im is not image:
-                owned.append(im)
+            im = image if isinstance(image, _DeviceImage) else sc.adopt(_DeviceImage(image))
             arr[k].Himg, arr[k].Wimg, arr[k].d_image, arr[k].d_zbuf = H, W, _ptr(im.buf), _ptr(d_zbufs[k])
         dst = d_grid if out is None else out
         _lib.check(_lib.load().pb3d_perspective_paint_resident(_lib.ctx(), _ptr(d_grid), A0, A1, A2, Cc, _lib.p_u8(tab) if ncol else None, ncol,
                                                                C.cast(arr, C.c_void_p), len(views), _lib.p_u8(sk) if len(sk) else None, len(sk),
                                                                float(eps), eps_f32, _ptr(dst), _ptr(d_painted)))
         return dst
-    finally:
-        for im in owned:        # the context's pool hands a freed block out again only behind this stream's work
-            im.free()
 
 
 def perspective_paint(voxel_grid, views, colors=None, skip=(), eps=1e-3, zbufs=None, return_counts=False):
@@ -259,7 +235,6 @@ def perspective_paint(voxel_grid, views, colors=None, skip=(), eps=1e-3, zbufs=N
     A view sees a subject voxel whose pixel is inside the image (Z > 1e-6) with |Z - zbuf[v,u]| < eps, and paints it when the pixel is
     neither black nor in skip.  Views are tried in order, the first that paints a voxel decides its colour, a voxel no view paints
     keeps its own.  return_counts=True also returns the int64 (K,) array of voxels decided per view."""
-    from . import device as dev
     grid_shape = _grid_shape(voxel_grid)
     views, sizes, _, _, _ = _paint_args(3 if len(grid_shape) == 4 else 1, views, colors, skip)      # every argument is checked before anything is uploaded
     for _, cam in views:
@@ -278,17 +253,15 @@ def perspective_paint(voxel_grid, views, colors=None, skip=(), eps=1e-3, zbufs=N
                 raise ValueError(f"the z-buffer of view {k} holds {zb.nbytes} bytes, its {hw[0]} x {hw[1]} image needs {4 * hw[0] * hw[1]}")
 
     def paint(d_g, shape, d_out, d_cnt):
-        mine = []
-        try:
+        with dev.Scope() as sc:         # (the context's pool hands a freed block out again only behind this stream's work)
             d_z = []
             for k, ((_, cam), (H, W)) in enumerate(zip(views, sizes)):
                 if zbufs is None:
-                    mine.append(depth_buffer_resident(d_g, shape, cam, H, W))
+                    d_z.append(sc.adopt(depth_buffer_resident(d_g, shape, cam, H, W)))
                 elif host_z[k] is not None:
-                    mine.append(dev.from_numpy_async(host_z[k]))
-                d_z.append(mine[-1] if zbufs is None or host_z[k] is not None else zbufs[k])
+                    d_z.append(sc.upload(host_z[k], wait=False))
+                else:
+                    d_z.append(zbufs[k])
             perspective_paint_resident(d_g, shape, views, d_z, colors, skip, eps, out=d_out, d_painted=d_cnt)
-        finally:
-            _free(*mine)        # the context's pool hands a freed block out again only behind this stream's work
 
     return _rewritten(voxel_grid, grid_shape, len(views), return_counts, paint)

@@ -29,9 +29,9 @@ import math
 
 import numpy as np
 
-from . import _lib
+from . import _lib, device as dev
 from ._lib import _ptr
-from .eval_helpers import _cloud
+from ._args import _cloud
 
 __all__ = ["normalize_preserve_aspect", "flip_y_axis", "transform_points", "transform_points_resident", "best_fit_transform_from_sums",
            "best_fit_similarity_from_sums", "icp_align", "icp_align_resident", "icp_index_resident", "icp_step_resident",
@@ -85,29 +85,22 @@ def _t12(T):
 def transform_points_resident(d_P, n, T, f64=True, out=None):
     """pb3d_transform_points_resident: a DeviceBuffer of n x 3 float64, T applied to the resident (n, 3) list d_P (float64 rows, or
     float32 with f64 False)"""
-    from . import device as dev
     t = _t12(_transform(T))
-    d_out = out if out is not None else dev.DeviceBuffer(max(1, int(n)) * 24)
-    _lib.check(_lib.load().pb3d_transform_points_resident(_lib.ctx(), _ptr(d_P), int(bool(f64)), int(n), _lib.p_dbl(t), _ptr(d_out)))
-    return d_out
+    with dev.Scope() as sc:
+        d_out = sc.result(out, max(1, int(n)) * 24)
+        _lib.check(_lib.load().pb3d_transform_points_resident(_lib.ctx(), _ptr(d_P), int(bool(f64)), int(n), _lib.p_dbl(t), _ptr(d_out)))
+        return d_out
 
 
 def transform_points(P, T):
     """float64 (n, 3): row i = ((T[h,0]*x + T[h,1]*y) + T[h,2]*z) + T[h,3] of point i, for a 3 x 4 or 4 x 4 T, on the device"""
-    from . import device as dev
     p, pf = _cloud(P, "P")
     t = _transform(T)
     if len(p) == 0:
         return np.zeros((0, 3), np.float64)
-    d_p = dev.from_numpy(p)
-    try:
-        d_out = transform_points_resident(d_p, len(p), t, pf)
-        try:
-            return d_out.download((len(p), 3), np.float64)
-        finally:
-            d_out.free()
-    finally:
-        d_p.free()
+    with dev.Scope() as sc:
+        d_out = sc.adopt(transform_points_resident(sc.upload(p), len(p), t, pf))
+        return d_out.download((len(p), 3), np.float64)
 
 
 def best_fit_transform_from_sums(count, sums, cp, cq):
@@ -175,29 +168,29 @@ def icp_index_resident(d_target, nt, f64=True):
 def icp_step_resident(d_source, ns, d_target, nt, T, max_dist2, cp, cq, s_f64=True, t_f64=True, out=None):
     """pb3d_icp_step_resident: a DeviceBuffer of 17 x 8 bytes -- the int64 count of used pairs and the 16 float64 sums of one step with
     the 4 x 4 (or 3 x 4) T against the index icp_index_resident built for this target.  max_dist2 < 0: no gate."""
-    from . import device as dev
     t = _t12(np.asarray(T, np.float64))
     cp = np.ascontiguousarray(cp, dtype=np.float64).reshape(3)
     cq = np.ascontiguousarray(cq, dtype=np.float64).reshape(3)
-    d_out = out if out is not None else dev.DeviceBuffer(17 * 8)
-    _lib.check(_lib.load().pb3d_icp_step_resident(_lib.ctx(), _ptr(d_source), int(bool(s_f64)), int(ns), _ptr(d_target), int(bool(t_f64)),
-                                                  int(nt), _lib.p_dbl(t), float(max_dist2), _lib.p_dbl(cp), _lib.p_dbl(cq), _ptr(d_out)))
-    return d_out
+    with dev.Scope() as sc:
+        d_out = sc.result(out, 17 * 8)
+        _lib.check(_lib.load().pb3d_icp_step_resident(_lib.ctx(), _ptr(d_source), int(bool(s_f64)), int(ns), _ptr(d_target), int(bool(t_f64)),
+                                                      int(nt), _lib.p_dbl(t), float(max_dist2), _lib.p_dbl(cp), _lib.p_dbl(cq), _ptr(d_out)))
+        return d_out
 
 
 def icp_step_trimmed_resident(d_source, ns, d_target, nt, T, max_dist2, trim_fraction, cp, cq, s_f64=True, t_f64=True, out=None):
     """pb3d_icp_step_trimmed_resident: a DeviceBuffer of 20 x 8 bytes -- the int64 count of used pairs, 17 float64 sums (the 16 of
     icp_step_resident and sum |p - cp|^2), the int64 number of candidate pairs m and the float64 tau, the k-th smallest candidate
     squared distance with k = ceil(trim_fraction * m): the pairs with d2 <= tau are used.  The 4 x 4 (or 3 x 4) T need not be rigid."""
-    from . import device as dev
     t = _t12(np.asarray(T, np.float64))
     cp = np.ascontiguousarray(cp, dtype=np.float64).reshape(3)
     cq = np.ascontiguousarray(cq, dtype=np.float64).reshape(3)
-    d_out = out if out is not None else dev.DeviceBuffer(20 * 8)
-    _lib.check(_lib.load().pb3d_icp_step_trimmed_resident(_lib.ctx(), _ptr(d_source), int(bool(s_f64)), int(ns), _ptr(d_target),
-                                                          int(bool(t_f64)), int(nt), _lib.p_dbl(t), float(max_dist2), float(trim_fraction),
-                                                          _lib.p_dbl(cp), _lib.p_dbl(cq), _ptr(d_out)))
-    return d_out
+    with dev.Scope() as sc:
+        d_out = sc.result(out, 20 * 8)
+        _lib.check(_lib.load().pb3d_icp_step_trimmed_resident(_lib.ctx(), _ptr(d_source), int(bool(s_f64)), int(ns), _ptr(d_target),
+                                                              int(bool(t_f64)), int(nt), _lib.p_dbl(t), float(max_dist2), float(trim_fraction),
+                                                              _lib.p_dbl(cp), _lib.p_dbl(cq), _ptr(d_out)))
+        return d_out
 
 
 def icp_step_plane_resident(d_source, ns, d_target, nt, d_normals, T, max_dist2, trim_fraction, c, s_f64=True, t_f64=True, out=None):
@@ -205,15 +198,15 @@ def icp_step_plane_resident(d_source, ns, d_target, nt, d_normals, T, max_dist2,
     point-to-plane step (the upper triangle of sum J J^T, sum J r, sum r r, sum d2) against the index of icp_index_resident and the
     resident (nt, 3) float64 target normals, the int64 number of candidate pairs m and the float64 tau.  trim_fraction < 0 (or None):
     untrimmed, m and tau are 0.  c: the pivot of the rotation."""
-    from . import device as dev
     t = _t12(np.asarray(T, np.float64))
     c = np.ascontiguousarray(c, dtype=np.float64).reshape(3)
     rho = -1.0 if trim_fraction is None else float(trim_fraction)
-    d_out = out if out is not None else dev.DeviceBuffer(32 * 8)
-    _lib.check(_lib.load().pb3d_icp_step_plane_resident(_lib.ctx(), _ptr(d_source), int(bool(s_f64)), int(ns), _ptr(d_target),
-                                                        int(bool(t_f64)), int(nt), _ptr(d_normals), _lib.p_dbl(t), float(max_dist2), rho,
-                                                        _lib.p_dbl(c), _ptr(d_out)))
-    return d_out
+    with dev.Scope() as sc:
+        d_out = sc.result(out, 32 * 8)
+        _lib.check(_lib.load().pb3d_icp_step_plane_resident(_lib.ctx(), _ptr(d_source), int(bool(s_f64)), int(ns), _ptr(d_target),
+                                                            int(bool(t_f64)), int(nt), _ptr(d_normals), _lib.p_dbl(t), float(max_dist2), rho,
+                                                            _lib.p_dbl(c), _ptr(d_out)))
+        return d_out
 
 
 def plane_step_from_sums(count, sums, c, cutoff=1e-12):
@@ -280,24 +273,16 @@ def _viewpoint(orient_towards):
 def estimate_normals_resident(d_points, n, k=20, orient_towards=None, f64=True, out=None):
     """pb3d_point_normals_resident on the rows of pb3d_knn_dev: a DeviceBuffer of n x 3 float64 unit normals of the resident (n, 3) list
     (float64 rows, or float32 with f64 False; finite).  Two host waits: the search's box and the index check."""
-    from . import device as dev
     from .eval_helpers import knn_resident
     n = int(n)
     k = _normals_k(k, n)
     v = _viewpoint(orient_towards)
-    _, d_idx = knn_resident(d_points, n, d_points, n, k, f64, f64, dist=False)
-    try:
-        d_out = out if out is not None else dev.DeviceBuffer(n * 24)
-        try:
-            _lib.check(_lib.load().pb3d_point_normals_resident(_lib.ctx(), _ptr(d_points), int(bool(f64)), n, _ptr(d_idx), k,
-                                                               None if v is None else _lib.p_dbl(v), _ptr(d_out)))
-        except BaseException:
-            if out is None:
-                d_out.free()
-            raise
+    with dev.Scope() as sc:
+        _, d_idx = sc.adopt(knn_resident(d_points, n, d_points, n, k, f64, f64, dist=False))
+        d_out = sc.result(out, n * 24)
+        _lib.check(_lib.load().pb3d_point_normals_resident(_lib.ctx(), _ptr(d_points), int(bool(f64)), n, _ptr(d_idx), k,
+                                                           None if v is None else _lib.p_dbl(v), _ptr(d_out)))
         return d_out
-    finally:
-        d_idx.free()
 
 
 def estimate_normals(points, k=20, orient_towards=None):
@@ -305,20 +290,13 @@ def estimate_normals(points, k=20, orient_towards=None):
     exact search, ties to the lowest index), on the device.  include/pb3d.h states the arithmetic to the bit.  orient_towards=None: the
     component of largest magnitude is positive; orient_towards=v: the normal points into the half space of the viewpoint v.
     ValueError for k < 3, k > KNN_MAX_K, fewer than k points or non-finite input.  float32 clouds stay float32 on the device."""
-    from . import device as dev
     p, pf = _cloud(points, "points")
     _normals_k(k, len(p))
     _viewpoint(orient_towards)
     _finite(p, "points")
-    d_p = dev.from_numpy(p)
-    try:
-        d_out = estimate_normals_resident(d_p, len(p), k, orient_towards, pf)
-        try:
-            return d_out.download((len(p), 3), np.float64)
-        finally:
-            d_out.free()
-    finally:
-        d_p.free()
+    with dev.Scope() as sc:
+        d_out = sc.adopt(estimate_normals_resident(sc.upload(p), len(p), k, orient_towards, pf))
+        return d_out.download((len(p), 3), np.float64)
 
 
 METHODS = ("point_to_point", "point_to_plane")
@@ -381,7 +359,6 @@ def icp_align_resident(d_source, ns, d_target, nt, max_iterations=50, tolerance=
     is binned once; every iteration enqueues one step and downloads its 17 values (20 with trim_fraction or with_scale: the trimmed
     step, whose history entries are (count, rmse, candidates, tau)).  method="point_to_plane": target_normals is a DeviceBuffer of nt x 3
     float64, or None to estimate them here from the normals_k nearest neighbours; an iteration downloads 32 values."""
-    from . import device as dev
     max_iterations, tolerance, md2, T = _icp_args(int(ns), int(nt), max_iterations, tolerance, max_distance, init)
     rho, with_scale = _trim_args(trim_fraction, with_scale)
     if _method_args(method, with_scale, normals_k, int(nt), target_normals is not None):
@@ -391,9 +368,9 @@ def icp_align_resident(d_source, ns, d_target, nt, max_iterations=50, tolerance=
     box = icp_index_resident(d_target, nt, t_f64)               # the only index build of the alignment
     c = 0.5 * (box[:3] + box[3:])
     words = 20 if trimmed else 17
-    d_out = dev.DeviceBuffer(words * 8)
     history, Ts, prev = [], [], None
-    try:
+    with dev.Scope() as sc:
+        d_out = sc.alloc(words * 8)
         for _ in range(max_iterations):
             if trimmed:
                 icp_step_trimmed_resident(d_source, ns, d_target, nt, T, md2, 1.0 if rho is None else rho, c, c, s_f64, t_f64, out=d_out)
@@ -414,23 +391,18 @@ def icp_align_resident(d_source, ns, d_target, nt, max_iterations=50, tolerance=
             if prev is not None and abs(prev - rmse) < tolerance:
                 break
             prev = rmse
-    finally:
-        d_out.free()
     return (T, history, Ts) if return_history else T
 
 
 def _icp_plane(d_source, ns, d_target, nt, max_iterations, tolerance, md2, T, return_history, s_f64, t_f64, rho, d_normals, normals_k):
     """the point-to-plane loop of icp_align_resident, its arguments checked"""
-    from . import device as dev
-    own = d_normals is None
-    if own:
-        d_normals = estimate_normals_resident(d_target, nt, normals_k, None, t_f64)     # once per alignment
-    d_out = None
     history, Ts, prev = [], [], None
-    try:
+    with dev.Scope() as sc:
+        if d_normals is None:
+            d_normals = sc.adopt(estimate_normals_resident(d_target, nt, normals_k, None, t_f64))     # once per alignment
         box = icp_index_resident(d_target, nt, t_f64)
         c = 0.5 * (box[:3] + box[3:])
-        d_out = dev.DeviceBuffer(32 * 8)
+        d_out = sc.alloc(32 * 8)
         for _ in range(max_iterations):
             icp_step_plane_resident(d_source, ns, d_target, nt, d_normals, T, md2, rho, c, s_f64, t_f64, out=d_out)
             raw = d_out.download((32,), np.float64)
@@ -446,11 +418,6 @@ def _icp_plane(d_source, ns, d_target, nt, max_iterations, tolerance, md2, T, re
             if prev is not None and abs(prev - rmse_plane) < tolerance:
                 break
             prev = rmse_plane
-    finally:
-        if d_out is not None:
-            d_out.free()
-        if own:
-            d_normals.free()
     return (T, history, Ts) if return_history else T
 
 
@@ -492,7 +459,6 @@ def icp_align(source, target, max_iterations=50, tolerance=1e-9, max_distance=No
     and the source is moved into the plane, not along it) and stops once the RMS plane distance changed by less than `tolerance`.
     History entries are (count, rmse_plane, rmse_point, rank), with (candidates, tau) appended under trim_fraction.  The method is
     rigid: with_scale=True is a ValueError.  An iteration needs 6 pairs."""
-    from . import device as dev
     s, sf = _cloud(source, "source")
     t, tf = _cloud(target, "target")
     _finite(s, "source")
@@ -501,20 +467,12 @@ def icp_align(source, target, max_iterations=50, tolerance=1e-9, max_distance=No
     _, scaled = _trim_args(trim_fraction, with_scale)
     _method_args(method, scaled, normals_k, len(t), target_normals is not None)
     nrm = _target_normals(target_normals, len(t))
-    d_s = dev.from_numpy(s)
-    d_t = d_s if target is source else dev.from_numpy(t)
-    d_n = None
-    try:
-        if nrm is not None:
-            d_n = dev.from_numpy(nrm)
+    with dev.Scope() as sc:
+        d_s = sc.upload(s)
+        d_t = d_s if target is source else sc.upload(t)
+        d_n = None if nrm is None else sc.upload(nrm)
         return icp_align_resident(d_s, len(s), d_t, len(t), max_iterations, tolerance, max_distance, init, return_history, sf, tf,
                                   trim_fraction, with_scale, method, d_n, normals_k)
-    finally:
-        d_s.free()
-        if d_t is not d_s:
-            d_t.free()
-        if d_n is not None:
-            d_n.free()
 
 
 # ---- facade plane, box crop, four-way completion ---------------------------------------------------------------------------------------
@@ -524,30 +482,30 @@ MAX_HYPOTHESES = 4096
 def plane_hypotheses_resident(d_P, n, d_triplets, K, f64=True, out=None):
     """pb3d_plane_hypotheses_resident: a DeviceBuffer of K x 4 float64, row k the plane (unit normal, d) through the three points of the
     resident (n, 3) list that the resident int64 triplet k names; four NaNs for a degenerate or out-of-range triplet"""
-    from . import device as dev
-    d_out = out if out is not None else dev.DeviceBuffer(max(1, int(K)) * 32)
-    _lib.check(_lib.load().pb3d_plane_hypotheses_resident(_lib.ctx(), _ptr(d_P), int(bool(f64)), int(n), _ptr(d_triplets), int(K), _ptr(d_out)))
-    return d_out
+    with dev.Scope() as sc:
+        d_out = sc.result(out, max(1, int(K)) * 32)
+        _lib.check(_lib.load().pb3d_plane_hypotheses_resident(_lib.ctx(), _ptr(d_P), int(bool(f64)), int(n), _ptr(d_triplets), int(K), _ptr(d_out)))
+        return d_out
 
 
 def plane_score_resident(d_P, n, d_planes, K, tau, f64=True, out=None):
     """pb3d_plane_score_resident: a DeviceBuffer of K int64, the number of points within tau of each of the K resident plane rows"""
-    from . import device as dev
-    d_out = out if out is not None else dev.DeviceBuffer(max(1, int(K)) * 8)
-    _lib.check(_lib.load().pb3d_plane_score_resident(_lib.ctx(), _ptr(d_P), int(bool(f64)), int(n), _ptr(d_planes), int(K), float(tau), _ptr(d_out)))
-    return d_out
+    with dev.Scope() as sc:
+        d_out = sc.result(out, max(1, int(K)) * 8)
+        _lib.check(_lib.load().pb3d_plane_score_resident(_lib.ctx(), _ptr(d_P), int(bool(f64)), int(n), _ptr(d_planes), int(K), float(tau), _ptr(d_out)))
+        return d_out
 
 
 def plane_moments_resident(d_P, n, plane, tau, pivot, f64=True, out=None):
     """pb3d_plane_moments_resident: a DeviceBuffer of 12 x 8 bytes -- the int64 count of the points within tau of `plane` (a, b, c, d)
     and the 11 float64 sums of a refit about `pivot`"""
-    from . import device as dev
     plane = np.ascontiguousarray(plane, dtype=np.float64).reshape(4)
     pivot = np.ascontiguousarray(pivot, dtype=np.float64).reshape(3)
-    d_out = out if out is not None else dev.DeviceBuffer(12 * 8)
-    _lib.check(_lib.load().pb3d_plane_moments_resident(_lib.ctx(), _ptr(d_P), int(bool(f64)), int(n), _lib.p_dbl(plane), float(tau),
-                                                       _lib.p_dbl(pivot), _ptr(d_out)))
-    return d_out
+    with dev.Scope() as sc:
+        d_out = sc.result(out, 12 * 8)
+        _lib.check(_lib.load().pb3d_plane_moments_resident(_lib.ctx(), _ptr(d_P), int(bool(f64)), int(n), _lib.p_dbl(plane), float(tau),
+                                                           _lib.p_dbl(pivot), _ptr(d_out)))
+        return d_out
 
 
 def _box(lo, hi):
@@ -562,49 +520,34 @@ def crop_to_box_resident(d_P, n, lo, hi, f64=True, out=None, index=None):
     """pb3d_points_crop_box_resident: (d_out, count) -- the rows of the resident (n, 3) list inside the closed box [lo, hi], in their
     order and dtype, at the front of d_out (a DeviceBuffer of n rows; allocated when `out` is None).  index: a DeviceBuffer of n int32
     that receives the surviving rows' positions, or None.  The count is downloaded (the one host wait)."""
-    from . import device as dev
     lo, hi = _box(lo, hi)
     row = 24 if f64 else 12
-    d_out = out if out is not None else dev.DeviceBuffer(max(1, int(n)) * row)
-    d_count = dev.DeviceBuffer(8)
-    try:
+    with dev.Scope() as sc:
+        d_out = sc.result(out, max(1, int(n)) * row)
+        d_count = sc.alloc(8)
         _lib.check(_lib.load().pb3d_points_crop_box_resident(_lib.ctx(), _ptr(d_P), int(bool(f64)), int(n), _lib.p_dbl(lo), _lib.p_dbl(hi),
                                                              _ptr(d_out), _ptr(index), _ptr(d_count)))
-        count = int(d_count.download((1,), np.int64)[0])
-    except BaseException:
-        if out is None:
-            d_out.free()
-        raise
-    finally:
-        d_count.free()
-    return d_out, count
+        return d_out, int(d_count.download((1,), np.int64)[0])
 
 
 def crop_to_box(points, lo, hi, return_index=False):
     """points[mask] for mask = all(lo <= p) & all(p <= hi) per row (the box is closed, a NaN coordinate fails), compacted on the device;
     float32 clouds stay float32, other real dtypes become float64.  return_index=True: (cropped, np.flatnonzero(mask))."""
-    from . import device as dev
     p, pf = _cloud(points, "points")
     lo, hi = _box(lo, hi)
     n = len(p)
     if n == 0:
         return (p.copy(), np.zeros(0, np.intp)) if return_index else p.copy()
-    d_p = dev.from_numpy(p)
-    d_idx = dev.DeviceBuffer(n * 4) if return_index else None
-    d_out = None
-    try:
+    with dev.Scope() as sc:
+        d_p = sc.upload(p)
+        d_idx = sc.alloc(n * 4) if return_index else None
         d_out, count = crop_to_box_resident(d_p, n, lo, hi, pf, index=d_idx)
+        sc.adopt(d_out)
         out = d_out.download((count, 3), p.dtype) if count else np.zeros((0, 3), p.dtype)
         if not return_index:
             return out
         idx = d_idx.download((count,), np.int32) if count else np.zeros(0, np.int32)
         return out, idx.astype(np.intp)
-    finally:
-        d_p.free()
-        if d_idx is not None:
-            d_idx.free()
-        if d_out is not None:
-            d_out.free()
 
 
 def plane_from_moments(count, sums, pivot):
@@ -649,19 +592,12 @@ def fit_plane_ransac_resident(d_P, n, inlier_threshold, num_hypotheses=1024, see
     """fit_plane_ransac on a resident (n, 3) list (a DeviceBuffer; float64 rows, or float32 with f64 False).  One upload of the
     triplets, the hypotheses and score entries, one download of K planes and K counts; then per refit one moments call about the box
     centre (pb3d_points_bounds_dev, once) and a download of its 12 numbers.  The coordinates must be finite (not checked here)."""
-    from . import device as dev
     n = int(n)
     tau, K, refits = _ransac_args(n, inlier_threshold, num_hypotheses, refine_iterations)
     triplets = np.random.default_rng(seed).integers(0, n, size=(K, 3), dtype=np.int64)
-    bufs = []
-
-    def buf(b):
-        bufs.append(b)
-        return b
-
-    try:
-        d_trip = buf(dev.from_numpy(triplets))
-        d_pc = buf(dev.DeviceBuffer(K * 40))                        # K x 4 planes, then K counts: one download
+    with dev.Scope() as sc:
+        d_trip = sc.upload(triplets)
+        d_pc = sc.alloc(K * 40)                                     # K x 4 planes, then K counts: one download
         plane_hypotheses_resident(d_P, n, d_trip, K, f64, out=d_pc.at(0))
         plane_score_resident(d_P, n, d_pc.at(0), K, tau, f64, out=d_pc.at(K * 32))
         raw = d_pc.download((K * 5,), np.float64)
@@ -672,11 +608,11 @@ def fit_plane_ransac_resident(d_P, n, inlier_threshold, num_hypotheses=1024, see
         normal, d, inliers = planes[best, :3].copy(), float(planes[best, 3]), int(counts[best])
         refit_log = []
         if refits:
-            d_box = buf(dev.DeviceBuffer(48))
+            d_box = sc.alloc(48)
             _lib.check(_lib.load().pb3d_points_bounds_dev(_lib.ctx(), _ptr(d_P), int(bool(f64)), n, _ptr(d_box)))
             box = d_box.download((6,), np.float64)
             pivot = 0.5 * (box[:3] + box[3:])
-            d_mom = buf(dev.DeviceBuffer(12 * 8))
+            d_mom = sc.alloc(12 * 8)
             for _ in range(refits):
                 plane_moments_resident(d_P, n, (normal[0], normal[1], normal[2], d), tau, pivot, f64, out=d_mom)
                 raw = d_mom.download((12,), np.float64)
@@ -686,12 +622,9 @@ def fit_plane_ransac_resident(d_P, n, inlier_threshold, num_hypotheses=1024, see
                 normal, d, _ = plane_from_moments(count, sums, pivot)
                 refit_log.append((count, sums, normal, d))
             # the inliers of the plane that is returned: one more sweep, of one plane
-            d_one = buf(dev.from_numpy(np.array([normal[0], normal[1], normal[2], d], np.float64)))
+            d_one = sc.upload(np.array([normal[0], normal[1], normal[2], d], np.float64))
             plane_score_resident(d_P, n, d_one, 1, tau, f64, out=d_pc.at(K * 32))
             inliers = int(d_pc.download((1,), np.int64, K * 32)[0])
-    finally:
-        for b in bufs:
-            b.free()
     if return_history:
         return normal, d, inliers, {"triplets": triplets, "planes": planes, "counts": counts, "best": best, "refits": refit_log}
     return normal, d, inliers
@@ -707,15 +640,11 @@ def fit_plane_ransac(points, inlier_threshold, num_hypotheses=1024, seed=0, refi
     plane that is returned.  return_history=True adds a dict: triplets, planes (K x 4, NaN rows for degenerate triplets), counts, best
     and refits = [(count, sums, normal, d) per refit].  ValueError for fewer than 3 points, a threshold that is negative or not finite,
     K outside [1, 4096], points that are not finite, or fewer than 3 inliers at any stage.  float32 clouds stay float32 on the device."""
-    from . import device as dev
     p, pf = _cloud(points, "points")
     _ransac_args(len(p), inlier_threshold, num_hypotheses, refine_iterations)
     _finite(p, "points")
-    d_p = dev.from_numpy(p)
-    try:
-        return fit_plane_ransac_resident(d_p, len(p), inlier_threshold, num_hypotheses, seed, refine_iterations, return_history, pf)
-    finally:
-        d_p.free()
+    with dev.Scope() as sc:
+        return fit_plane_ransac_resident(sc.upload(p), len(p), inlier_threshold, num_hypotheses, seed, refine_iterations, return_history, pf)
 
 
 def plane_alignment_transform(normal, d):
@@ -762,45 +691,32 @@ def quarter_turn_transforms(centre):
 
 def symmetric_completion_resident(d_P, n, centre=None, f64=True):
     """symmetric_completion on a resident (n, 3) list: a DeviceBuffer of 4n x 3 float64 (four transform_points_resident calls)"""
-    from . import device as dev
     n = int(n)
     if centre is None:
         if n < 1:
             raise ValueError("symmetric_completion: an empty cloud has no box; give a centre")
-        d_box = dev.DeviceBuffer(48)
-        try:
+        with dev.Scope() as sc:
+            d_box = sc.alloc(48)
             _lib.check(_lib.load().pb3d_points_bounds_dev(_lib.ctx(), _ptr(d_P), int(bool(f64)), n, _ptr(d_box)))
             box = d_box.download((6,), np.float64)
-        finally:
-            d_box.free()
         centre = (0.5 * (box[0] + box[3]), 0.5 * (box[2] + box[5]))
     Ts = quarter_turn_transforms(centre)
-    d_out = dev.DeviceBuffer(max(1, 4 * n) * 24)
-    try:
+    with dev.Scope() as sc:
+        d_out = sc.result(None, max(1, 4 * n) * 24)
         for q, T in enumerate(Ts):
             transform_points_resident(d_P, n, T, f64, out=d_out.at(q * n * 24))
-    except BaseException:
-        d_out.free()
-        raise
-    return d_out
+        return d_out
 
 
 def symmetric_completion(points, centre=None):
     """The naive four-way completion of a facade cloud: float64 (4n, 3), rows [q n, (q + 1) n) the cloud turned by q quarter turns about
     the axis parallel to Y through centre = (cx, cz) (default: the x / z centre of the cloud's box).  Copy 0 is the input widened to
     float64 (a -0.0 coordinate comes out as +0.0)."""
-    from . import device as dev
     p, pf = _cloud(points, "points")
     _finite(p, "points")
     n = len(p)
     if n == 0:
         return np.zeros((0, 3), np.float64)
-    d_p = dev.from_numpy(p)
-    try:
-        d_out = symmetric_completion_resident(d_p, n, centre, pf)
-        try:
-            return d_out.download((4 * n, 3), np.float64)
-        finally:
-            d_out.free()
-    finally:
-        d_p.free()
+    with dev.Scope() as sc:
+        d_out = sc.adopt(symmetric_completion_resident(sc.upload(p), n, centre, pf))
+        return d_out.download((4 * n, 3), np.float64)

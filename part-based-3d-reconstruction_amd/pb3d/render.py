@@ -17,7 +17,8 @@ import math
 
 import numpy as np
 
-from . import _lib
+from . import _lib, device as dev
+from ._args import _counts, _mesh
 from ._lib import _ptr
 
 __all__ = ["render_mesh", "render_mesh_resident", "render_shade_resident", "mesh_projection_iou", "render_last"]
@@ -111,20 +112,15 @@ def render_shade_resident(d_face, d_bary, n_pixels, d_faces, n_faces, n_vertices
     """pb3d_render_shade_resident: a DeviceBuffer of n_pixels * channels bytes -- per pixel the `channels` (1 or 3) bytes that the
     resident (n_vertices, channels) uint8 list d_colors holds for the dominant corner of the pixel's face, `background` where the face
     image holds -1.  Enqueued."""
-    from . import device as dev
     channels = int(channels)
     if channels not in (1, 3):
         raise ValueError(f"channels must be 1 or 3 (got {channels})")
     bg = _background(background, channels)
-    d_out = out if out is not None else dev.DeviceBuffer(max(1, int(n_pixels) * channels))
-    try:
+    with dev.Scope() as sc:
+        d_out = sc.result(out, max(1, int(n_pixels) * channels))
         _lib.check(_lib.load().pb3d_render_shade_resident(_lib.ctx(), _ptr(d_face), _ptr(d_bary), int(n_pixels), _ptr(d_faces), int(bool(faces_i64)),
                                                           int(n_faces), int(n_vertices), _ptr(d_colors), channels, _lib.p_u8(bg), _ptr(d_out)))
-    except BaseException:
-        if out is None:
-            d_out.free()
-        raise
-    return d_out
+        return d_out
 
 
 def render_mesh_resident(d_verts, n_vertices, d_faces, n_faces, cam_pos, target, f, cx, cy, H, W, d_colors=None, channels=3, background=0,
@@ -133,8 +129,6 @@ def render_mesh_resident(d_verts, n_vertices, d_faces, n_faces, cam_pos, target,
     (with d_colors, the resident (n_vertices, channels) uint8 attribute) and H * W * 3 float64 (with return_bary).  It takes what
     pb3d.device.meshify(..., download=False) hands out as it is: float32 vertices, int32 faces, nearest-voxel bytes, frame="meshify".
     Two host waits (the index / finiteness check: IndexError, ValueError; the tile-job count); nothing is returned when it fails."""
-    from . import device as dev
-    from .smooth import _counts
     nv, nf = _counts(n_vertices, n_faces)
     R, cam, f, cx, cy, H, W, near = _camera(cam_pos, target, f, cx, cy, H, W, near)
     fr, d = _frame(frame, depth)
@@ -144,33 +138,19 @@ def render_mesh_resident(d_verts, n_vertices, d_faces, n_faces, cam_pos, target,
             raise ValueError(f"channels must be 1 or 3 (got {channels})")
         _background(background, channels)
     npix = H * W
-    bufs = []
-    try:
-        d_depth = dev.DeviceBuffer(npix * 8)
-        bufs.append(d_depth)
-        d_face = dev.DeviceBuffer(npix * 4)
-        bufs.append(d_face)
+    with dev.Scope() as sc:
+        d_depth, d_face = sc.result(None, npix * 8), sc.result(None, npix * 4)
         want_bary = return_bary or d_colors is not None
-        d_bary = dev.DeviceBuffer(npix * 24) if want_bary else None
-        bufs.append(d_bary)
+        d_bary = (sc.result(None, npix * 24) if return_bary else sc.alloc(npix * 24)) if want_bary else None
         _lib.check(_lib.load().pb3d_render_mesh_resident(_lib.ctx(), _ptr(d_verts), int(bool(verts_f64)), nv, _ptr(d_faces), int(bool(faces_i64)), nf,
                                                          fr, d, _lib.p_dbl(R), _lib.p_dbl(cam), f, cx, cy, H, W, near, _ptr(d_depth), _ptr(d_face),
                                                          _ptr(d_bary)))
         out = [d_depth, d_face]
         if d_colors is not None:
-            d_image = render_shade_resident(d_face, d_bary, npix, d_faces, nf, nv, d_colors, channels, background, faces_i64)
-            bufs.append(d_image)
-            out.append(d_image)
+            out.append(render_shade_resident(d_face, d_bary, npix, d_faces, nf, nv, d_colors, channels, background, faces_i64))
         if return_bary:
             out.append(d_bary)
-        elif d_bary is not None:
-            d_bary.free()
         return tuple(out)
-    except BaseException:
-        for b in bufs:
-            if b is not None:
-                b.free()
-        raise
 
 
 def render_mesh(vertices, faces, cam_pos, target, f, cx, cy, H, W, vertex_colors=None, background=0, near=1e-6, frame="points", depth=None,
@@ -183,8 +163,6 @@ def render_mesh(vertices, faces, cam_pos, target, f, cx, cy, H, W, vertex_colors
     face's corners.  float32 vertices stay float32 (the arithmetic is float64), other real dtypes become float64; negative face indices
     wrap as NumPy's do.  frame="meshify" takes the vertices as meshify_colored_voxel_grid returns them and needs `depth`, the grid's last
     axis; frame="points" is the (x, y, z) frame of voxel_grid_to_points.  Faces nearer than `near` along the camera axis are not seen."""
-    from . import device as dev
-    from .voxelize import _mesh
     _camera(cam_pos, target, f, cx, cy, H, W, near)
     _frame(frame, depth)
     v, vf, fc, fi = _mesh(vertices, faces)
@@ -192,20 +170,11 @@ def render_mesh(vertices, faces, cam_pos, target, f, cx, cy, H, W, vertex_colors
     if cols is not None:
         _background(background, cols.shape[1])
     H, W = int(H), int(W)
-    bufs = []
-    try:
-        d_v = dev.from_numpy(v) if len(v) else None
-        bufs.append(d_v)
-        d_f = dev.from_numpy(fc) if len(fc) else None
-        bufs.append(d_f)
-        d_c = dev.from_numpy(cols) if cols is not None and len(cols) else None
-        bufs.append(d_c)
-        if cols is not None and d_c is None:
-            d_c = dev.DeviceBuffer(1)                # no vertex: nothing is read, but the handle says "shade"
-            bufs.append(d_c)
-        res = render_mesh_resident(d_v, len(v), d_f, len(fc), cam_pos, target, f, cx, cy, H, W, d_c, 3 if cols is None else cols.shape[1],
-                                   background, near, frame, depth, return_bary, vf, fi)
-        bufs.extend(res)
+    with dev.Scope() as sc:
+        d_v, d_f = sc.upload(v), sc.upload(fc)
+        d_c = None if cols is None else sc.upload(cols) or sc.alloc(1)      # no vertex: nothing is read, but the handle says "shade"
+        res = sc.adopt(render_mesh_resident(d_v, len(v), d_f, len(fc), cam_pos, target, f, cx, cy, H, W, d_c, 3 if cols is None else cols.shape[1],
+                                            background, near, frame, depth, return_bary, vf, fi))
         out = [res[0].download((H, W), np.float64), res[1].download((H, W), np.int32)]
         k = 2
         if cols is not None:
@@ -214,10 +183,6 @@ def render_mesh(vertices, faces, cam_pos, target, f, cx, cy, H, W, vertex_colors
         if return_bary:
             out.append(res[k].download((H, W, 3), np.float64))
         return tuple(out)
-    finally:
-        for b in bufs:
-            if b is not None:
-                b.free()
 
 
 def mesh_projection_iou(vertices, faces, vertex_colors, seg_image, part_colors, cam_pos, target, f, cx, cy, background=0, near=1e-6,
@@ -225,8 +190,6 @@ def mesh_projection_iou(vertices, faces, vertex_colors, seg_image, part_colors, 
     """compute_partwise_iou of the rendered mesh against an (H, W, 3) uint8 part image, what it returns: ({part: inter / union, or 0.0
     when the union is empty}, mean over parts).  The mesh is rendered and shaded with its (n, 3) vertex_colors at the image's size and
     compared by pb3d_partwise_iou_dev where it lies: nothing is downloaded but the counts."""
-    from . import device as dev
-    from .voxelize import _mesh
     seg = _lib.as_u8(seg_image, "seg_image")
     if seg.ndim != 3 or seg.shape[2] != 3:
         raise ValueError(f"seg_image must be an (H, W, 3) image (got shape {seg.shape})")
@@ -240,26 +203,15 @@ def mesh_projection_iou(vertices, faces, vertex_colors, seg_image, part_colors, 
     ok = np.all((pc >= 0) & (pc <= 255), axis=1)
     c8 = np.ascontiguousarray(pc[ok].astype(np.uint8))
     inter, uni = np.zeros(len(pc), np.int64), np.zeros(len(pc), np.int64)
-    bufs = []
-    try:
-        for a in (v, fc, cols, seg):
-            bufs.append(dev.from_numpy(a) if a.size else None)
-        d_v, d_f, d_c, d_seg = bufs
-        if d_c is None:
-            d_c = dev.DeviceBuffer(1)
-            bufs.append(d_c)
-        res = render_mesh_resident(d_v, len(v), d_f, len(fc), cam_pos, target, f, cx, cy, H, W, d_c, 3, background, near, frame, depth, False,
-                                   vf, fi)
-        bufs.extend(res)
+    with dev.Scope() as sc:
+        d_v, d_f, d_c, d_seg = (sc.upload(a) for a in (v, fc, cols, seg))
+        res = sc.adopt(render_mesh_resident(d_v, len(v), d_f, len(fc), cam_pos, target, f, cx, cy, H, W, d_c or sc.alloc(1), 3, background, near,
+                                            frame, depth, False, vf, fi))
         i8, u8 = np.zeros(len(c8), np.int64), np.zeros(len(c8), np.int64)
         for s in range(0, len(c8), 32):
             chunk = np.ascontiguousarray(c8[s:s + 32])
             _lib.check(_lib.load().pb3d_partwise_iou_dev(_lib.ctx(), _ptr(res[2]), _ptr(d_seg), H * W, _lib.p_u8(chunk), len(chunk),
                                                          i8[s:].ctypes.data_as(_lib.i64p), u8[s:].ctypes.data_as(_lib.i64p)))
         inter[ok], uni[ok] = i8, u8
-    finally:
-        for b in bufs:
-            if b is not None:
-                b.free()
     per_part = {name: ((i / u) if u > 0 else 0.0) for name, i, u in zip(names, inter, uni)}
     return per_part, np.mean(list(per_part.values()))

@@ -23,38 +23,13 @@ import math
 
 import numpy as np
 
-from . import _lib
+from . import _lib, device as dev
+from ._args import MAX_FACES, MAX_VERTICES, _cloud, _counts, _faces  # noqa: F401
 from ._lib import _ptr
 
 __all__ = ["mesh_vertex_adjacency", "mesh_vertex_adjacency_resident", "smooth_mesh", "smooth_mesh_resident"]
 
-MAX_VERTICES = 2 ** 31 - 1
-MAX_FACES = (2 ** 31 - 1) // 6
 METHODS = ("taubin", "laplacian")
-
-
-def _counts(nv, nf):
-    nv, nf = int(nv), int(nf)
-    if not 0 <= nv <= MAX_VERTICES:
-        raise ValueError(f"a mesh holds at most 2^31 - 1 vertices (got {nv})")
-    if not 0 <= nf <= MAX_FACES:
-        raise ValueError(f"a mesh holds at most (2^31 - 1) / 6 faces (got {nf})")
-    return nv, nf
-
-
-def _faces(faces, nv):
-    """(contiguous (nf, 3) int32 or int64 array, i64 flag); int32 and int64 go as they are, other integer types become int64"""
-    f = np.asarray(faces)
-    if f.dtype.kind not in "iu":
-        raise IndexError("arrays used as indices must be of integer (or boolean) type")
-    if f.ndim != 2 or f.shape[1] != 3:
-        raise ValueError(f"faces must be an (m, 3) array (got shape {f.shape})")
-    _counts(nv, f.shape[0])
-    if f.dtype.kind == "u" and f.size and int(f.max()) >= nv:           # before the cast to int64 could wrap it
-        raise IndexError(f"index {int(f.max())} is out of bounds for axis 0 with size {nv}")
-    if f.dtype == np.int32:
-        return np.ascontiguousarray(f), 0
-    return np.ascontiguousarray(f, dtype=np.int64), 1
 
 
 def _iterations(iterations):
@@ -83,21 +58,15 @@ def mesh_vertex_adjacency_resident(d_faces, n_vertices, n_faces, faces_i64=False
     6 * n_faces int32 of which the first `total` are written, the same of uint32 (None unless `multiplicity`) and n_vertices bytes (None
     unless `boundary`).  total is the call's one download.  The caller frees the buffers.  IndexError on a face index outside
     [-n_vertices, n_vertices)."""
-    from . import device as dev
     nv, nf = _counts(n_vertices, n_faces)
     room = max(1, 6 * nf) * 4
-    bufs = [dev.DeviceBuffer((nv + 1) * 8), dev.DeviceBuffer(room), dev.DeviceBuffer(room) if multiplicity else None,
-            dev.DeviceBuffer(max(1, nv)) if boundary else None]
     total = C.c_int64(0)
-    try:
+    with dev.Scope() as sc:
+        bufs = [sc.result(None, (nv + 1) * 8), sc.result(None, room), sc.result(None, room) if multiplicity else None,
+                sc.result(None, max(1, nv)) if boundary else None]
         _lib.check(_lib.load().pb3d_mesh_adjacency_resident(_lib.ctx(), _ptr(d_faces), int(bool(faces_i64)), nv, nf, _ptr(bufs[0]), _ptr(bufs[1]),
                                                             _ptr(bufs[2]), _ptr(bufs[3]), C.byref(total)))
-    except BaseException:
-        for b in bufs:
-            if b is not None:
-                b.free()
-        raise
-    return bufs[0], bufs[1], bufs[2], bufs[3], int(total.value)
+        return bufs[0], bufs[1], bufs[2], bufs[3], int(total.value)
 
 
 def mesh_vertex_adjacency(faces, n_vertices, return_multiplicity=False, return_boundary=False):
@@ -106,24 +75,18 @@ def mesh_vertex_adjacency(faces, n_vertices, return_multiplicity=False, return_b
     Negative indices wrap as NumPy's do; one outside [-n_vertices, n_vertices) is an IndexError.  Degenerate faces contribute the pairs
     of their distinct corners.  Extras, in this order: multiplicity (int64, beside neighbours: the number of face corners pairs that
     give the directed pair; 1 = an edge of one face), boundary (bool per vertex: it is an end of a pair of multiplicity 1)."""
-    from . import device as dev
     nv = _counts(n_vertices, 0)[0]
     f, fi = _faces(faces, nv)
     nf = len(f)
-    d_f = dev.from_numpy(f) if nf else None
-    bufs = ()
-    try:
-        *bufs, total = mesh_vertex_adjacency_resident(d_f, nv, nf, fi, return_multiplicity, return_boundary)
+    with dev.Scope() as sc:
+        *bufs, total = mesh_vertex_adjacency_resident(sc.upload(f), nv, nf, fi, return_multiplicity, return_boundary)
+        sc.adopt(bufs)
         out = [bufs[0].download((nv + 1,), np.int64), bufs[1].download((total,), np.int32)]
         if return_multiplicity:
             out.append(bufs[2].download((total,), np.uint32).astype(np.int64))
         if return_boundary:
             out.append(bufs[3].download((nv,), np.uint8).astype(bool))
         return tuple(out)
-    finally:
-        for b in (d_f, *bufs):
-            if b is not None:
-                b.free()
 
 
 def smooth_mesh_resident(d_verts, n_vertices, d_faces, n_faces, iterations=10, method="taubin", lamb=0.5, mu=-0.53, d_fixed=None,
@@ -131,19 +94,14 @@ def smooth_mesh_resident(d_verts, n_vertices, d_faces, n_faces, iterations=10, m
     """pb3d_mesh_smooth_resident: a DeviceBuffer of n_vertices x 3 smoothed vertices in the input dtype (float32, or float64 with verts_f64)
     -- pb3d.device.meshify(..., download=False) hands out float32 vertices and int32 faces.  d_fixed: n_vertices bytes, non-zero = the
     vertex stays, or None.  Everything is enqueued behind the index check (IndexError on a bad face index).  `out` may not be d_verts."""
-    from . import device as dev
     nv, nf = _counts(n_vertices, n_faces)
     iterations = _iterations(iterations)
     lamb, mu = _factors(method, lamb, mu)
-    d_out = out if out is not None else dev.DeviceBuffer(max(1, nv) * 3 * (8 if verts_f64 else 4))
-    try:
+    with dev.Scope() as sc:
+        d_out = sc.result(out, max(1, nv) * 3 * (8 if verts_f64 else 4))
         _lib.check(_lib.load().pb3d_mesh_smooth_resident(_lib.ctx(), _ptr(d_verts), int(bool(verts_f64)), nv, _ptr(d_faces), int(bool(faces_i64)), nf,
                                                          iterations, lamb, mu, _ptr(d_fixed), int(bool(fix_boundary)), _ptr(d_out)))
-    except BaseException:
-        if out is None:
-            d_out.free()
-        raise
-    return d_out
+        return d_out
 
 
 def smooth_mesh(vertices, faces, iterations=10, method="taubin", lamb=0.5, mu=-0.53, fixed=None, fix_boundary=False):
@@ -153,8 +111,6 @@ def smooth_mesh(vertices, faces, iterations=10, method="taubin", lamb=0.5, mu=-0
     fixed: a mask of n entries, true = the vertex stays; fix_boundary also keeps every vertex on an edge of a single face.
     The faces and the colours of the mesh are untouched by smoothing: meshify_colored_voxel_grid's other outputs stay valid beside the
     new vertices."""
-    from . import device as dev
-    from .eval_helpers import _cloud
     iterations = _iterations(iterations)
     _factors(method, lamb, mu)
     v, vf = _cloud(vertices, "vertices")
@@ -171,18 +127,8 @@ def smooth_mesh(vertices, faces, iterations=10, method="taubin", lamb=0.5, mu=-0
         if nf:
             raise IndexError(f"index {int(f.reshape(-1)[0])} is out of bounds for axis 0 with size 0")
         return v.copy()
-    bufs = []
-    try:
-        d_v = dev.from_numpy(v)
-        bufs.append(d_v)
-        d_f = dev.from_numpy(f) if nf else None
-        bufs.append(d_f)
-        d_x = dev.from_numpy(fx) if fx is not None else None
-        bufs.append(d_x)
-        d_out = smooth_mesh_resident(d_v, nv, d_f, nf, iterations, method, lamb, mu, d_x, fix_boundary, vf, fi)
-        bufs.append(d_out)
+    with dev.Scope() as sc:
+        d_v, d_f = sc.upload(v), sc.upload(f)
+        d_x = sc.upload(fx) if fx is not None else None
+        d_out = sc.adopt(smooth_mesh_resident(d_v, nv, d_f, nf, iterations, method, lamb, mu, d_x, fix_boundary, vf, fi))
         return d_out.download((nv, 3), v.dtype)
-    finally:
-        for b in bufs:
-            if b is not None:
-                b.free()

@@ -9,7 +9,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _hostmem, _lib
+from . import _hostmem, _lib, device as dev
 from .config import PART_COLORS, PART_COLORS_NP  # noqa: F401  (re-exported like upstream)
 
 __all__ = ["carve_voxel_grid_with_masks", "process_voxel_grid", "apply_colored_mask_to_voxel_grid", "part_carve",
@@ -113,18 +113,14 @@ def process_voxel_grid(voxel_grid, combined_mask, angle_interval=90):
     m = _lib.truth_u8(mask)
     if typed is not None:
         # any other dtype SciPy's interpolation takes (the reference's loop never looks at it): csrc/rotate_typed.hip
-        from . import device as dev
         if g.size == 0:
             return g.copy()
-        d_g = dev.from_numpy(g.view(np.uint8).reshape(-1)); d_m = dev.from_numpy(m)
-        d_o = dev.DeviceBuffer(g.nbytes); d_t = dev.DeviceBuffer(g.nbytes)
-        try:
+        with dev.Scope() as sc:
+            d_g = sc.upload(g.view(np.uint8).reshape(-1)); d_m = sc.upload(m)
+            d_o = sc.alloc(g.nbytes); d_t = sc.alloc(g.nbytes)
             _lib.check(_lib.load().pb3d_process_grid_typed_dev(_lib.ctx(), C.c_void_p(d_g.ptr), typed, W, H, D, C.c_void_p(d_m.ptr),
                                                                int(min(angle_interval, 91)), C.c_void_p(d_o.ptr), C.c_void_p(d_t.ptr)))
             return d_o.download((g.nbytes,)).view(g.dtype).reshape(g.shape)
-        finally:
-            for b in (d_g, d_m, d_o, d_t):
-                b.free()
     out = _hostmem.empty_like(g)
     _lib.check(_lib.load().pb3d_process_grid(_lib.ctx(), _lib.p_u8(g), W, H, D, _lib.p_u8(m), int(min(angle_interval, 91)),
                                              _lib.p_u8(out)))
@@ -251,7 +247,6 @@ def _job_masks(semantic_mask, group_jobs, W, H, part_colors):
 def part_carve(colored_grid, semantic_mask, group_jobs, visualize=False):
     """Per part group: select its pixels, carve the group's occupancy with its own symmetry
     angle, overlay the survivors; reference :139-160."""
-    from . import device as dev
     resident = isinstance(colored_grid, dev.DeviceGrid)          # device-resident chain: no upload, no download
     g = colored_grid if resident else _lib.as_u8(colored_grid, "colored_grid")
     if len(g.shape) != 4 or g.shape[3] != 3:
@@ -263,18 +258,13 @@ def part_carve(colored_grid, semantic_mask, group_jobs, visualize=False):
             raise ValueError("range() arg 3 must not be zero" if angles[j] == 0 else "negative angle steps are not supported")
         angles[j] = min(angles[j], 91) if angles[j] > 0 else angles[j]
     if resident:
-        d_ms = dev.from_numpy(msub); d_mc = dev.from_numpy(mcarve)
-        d_out = dev.DeviceBuffer(g.nbytes)
-        try:
+        with dev.Scope() as sc:
+            d_ms = sc.upload(msub) or sc.alloc(0); d_mc = sc.upload(mcarve) or sc.alloc(0)
+            d_out = sc.result(None, g.nbytes)
             _lib.check(_lib.load().pb3d_part_carve_dev(_lib.ctx(), C.c_void_p(g.buf.ptr), W, H, D, C.c_void_p(d_ms.ptr), C.c_void_p(d_mc.ptr),
                                                        angles, skip, len(group_jobs), C.c_void_p(d_out.ptr)))
             dev.sync()
-        except Exception:
-            d_out.free()
-            raise
-        finally:
-            d_ms.free(); d_mc.free()
-        return dev.DeviceGrid(d_out, g.shape)
+            return dev.DeviceGrid(d_out, g.shape)
     out = _hostmem.empty_like(g)
     _lib.check(_lib.load().pb3d_part_carve(_lib.ctx(), _lib.p_u8(g), W, H, D, _lib.p_u8(msub), _lib.p_u8(mcarve), angles, skip,
                                            len(group_jobs), _lib.p_u8(out)))
@@ -300,18 +290,12 @@ def global_carve(binary_mask, semantic_mask_exterior, angle_interval=90, stride=
         return apply_colored_mask_to_voxel_grid(np.ones((w, h, w), np.uint8), rgb)
     bt = _lib.truth_u8(b)
     if on_device:
-        from . import device as dev
-        d_b = dev.from_numpy(bt); d_rgb = dev.from_numpy(rgb)
-        d_out = dev.DeviceBuffer(w * h * w * 3)
-        try:
+        with dev.Scope() as sc:
+            d_b = sc.upload(bt) or sc.alloc(0); d_rgb = sc.upload(rgb) or sc.alloc(0)
+            d_out = sc.result(None, w * h * w * 3)
             dev.global_carve(d_b, d_rgb, h, w, int(min(angle_interval, 91)), d_out)
             dev.sync()
-        except Exception:
-            d_out.free()
-            raise
-        finally:
-            d_b.free(); d_rgb.free()
-        return dev.DeviceGrid(d_out, (w, h, w, 3))
+            return dev.DeviceGrid(d_out, (w, h, w, 3))
     out = _hostmem.empty((w, h, w, 3), np.uint8)
     _lib.check(_lib.load().pb3d_global_carve(_lib.ctx(), _lib.p_u8(bt), _lib.p_u8(rgb), h, w, int(min(angle_interval, 91)),
                                              _lib.p_u8(out)))
@@ -406,16 +390,13 @@ def _check_angle_step(angle):
 def _lrgc_dev(d_col, shape3, mask2d, target_color, angle, label=None, d_lab=None):
     """left_right_guided_carve on a device-resident grid.  Returns the DeviceBuffer that holds the result: d_col itself when the
     fused component loop ran (csrc/guided.hip: in place, one launch pair per batch of components), else a new buffer."""
-    from . import device as dev
     W, H, D = shape3
     lib, ctx = _lib.load(), _lib.ctx()
     nbytes = W * H * D * (3 if label is None else 1)      # label: d_col is a 1-byte label volume and `label` the part's label value
-    own_lab = d_lab is None
-    if own_lab:
-        d_lab = dev.DeviceBuffer(W * H * D * 4)
-    d_carved = None
-    tmp = []
-    try:
+    with dev.Scope() as sc:
+        if d_lab is None:
+            d_lab = sc.alloc(W * H * D * 4)
+        d_carved = None
         cu8 = _color_u8(target_color) if label is None else int(label)
         # (labels written at the component voxels only: the fused loop below consults the labelling's membership bits)
         num, bbox, _, _ = _label_stats(d_col, (W, H, D), cu8, d_lab, members_only=True) if cu8 is not None else (0, None, None, None)
@@ -425,21 +406,14 @@ def _lrgc_dev(d_col, shape3, mask2d, target_color, angle, label=None, d_lab=None
         _check_angle_step(angle)
         # every component's 2-D crop mask goes up in ONE transfer and the "carved voxels" counts come back in one (upstream prints
         # between the steps; the text is the same, it is emitted after the loop)
-        masks, offs, o = [], [], 0
-        for i in range(1, num + 1):
-            x0, y0, z0, x1, y1, z1 = (int(v) for v in bbox[i - 1])
-            m = _lib.truth_u8(_mask_to_wh(mask2d[y0:y1, x0:x1], x1 - x0, y1 - y0))
-            masks.append(np.ascontiguousarray(m).reshape(-1)); offs.append(o); o += (m.size + 15) & ~15
-        packed = np.zeros(max(o, 16), np.uint8)
-        for m, off in zip(masks, offs):
-            packed[off:off + m.size] = m
+        packed, offs = _pack_crop_masks(mask2d, bbox)
         counts = None
         if angle > 0:
-            bb = np.ascontiguousarray(bbox, np.int64); mo = np.asarray(offs, np.int64); cn = np.zeros(num, np.int64)
+            bb = np.ascontiguousarray(bbox, np.int64); cn = np.zeros(num, np.int64)
             took = C.c_int(0)
             fn = lib.pb3d_guided_carve_dev if label is None else lib.pb3d_guided_carve_label_dev
             _lib.check(fn(ctx, C.c_void_p(d_col.ptr), C.c_void_p(d_lab.ptr), W, H, D, num, bb.ctypes.data_as(_lib.i64p),
-                                                 _lib.p_u8(packed), mo.ctypes.data_as(_lib.i64p), packed.size, int(min(angle, 91)),
+                                                 _lib.p_u8(packed), offs.ctypes.data_as(_lib.i64p), packed.size, int(min(angle, 91)),
                                                  cn.ctypes.data_as(_lib.i64p), C.byref(took)))
             if took.value:
                 counts = cn
@@ -452,13 +426,12 @@ def _lrgc_dev(d_col, shape3, mask2d, target_color, angle, label=None, d_lab=None
                 _label_stats(d_col, (W, H, D), cu8, d_lab, cap=1024, members_only=False)
             crop_fn = lib.pb3d_crop_occupancy_dev if label is None else lib.pb3d_crop_occupancy_label_dev
             paste_fn = lib.pb3d_component_paste_dev if label is None else lib.pb3d_component_paste_label_dev
-            d_carved = dev.DeviceBuffer(nbytes)
+            d_carved = sc.result(None, nbytes)
             _lib.check(lib.pb3d_d2d(ctx, C.c_void_p(d_carved.ptr), C.c_void_p(d_col.ptr), nbytes))
             vmax = int(max((b[3] - b[0]) * (b[4] - b[1]) * (b[5] - b[2]) for b in bbox))
-            d_m = dev.from_numpy(packed)
-            d_occ = dev.DeviceBuffer(vmax); d_out = dev.DeviceBuffer(vmax); d_tmp = dev.DeviceBuffer(vmax)
-            d_cnt = dev.DeviceBuffer(8 * num); d_cnt.zero()
-            tmp = [d_occ, d_out, d_tmp, d_m, d_cnt]
+            d_m = sc.upload(packed)
+            d_occ = sc.alloc(vmax); d_out = sc.alloc(vmax); d_tmp = sc.alloc(vmax)
+            d_cnt = sc.alloc(8 * num); d_cnt.zero()
             for i in range(1, num + 1):
                 x0, y0, z0, x1, y1, z1 = (int(v) for v in bbox[i - 1])
                 Wc, Hc, Dc = x1 - x0, y1 - y0, z1 - z0
@@ -467,27 +440,14 @@ def _lrgc_dev(d_col, shape3, mask2d, target_color, angle, label=None, d_lab=None
                 if angle < 0:
                     src = d_occ     # empty angle loop: the crop's occupancy is returned as is
                 else:
-                    dev.process_grid(d_occ, Wc, Hc, Dc, d_m.at(offs[i - 1]), int(min(angle, 91)), d_out, d_tmp)
+                    dev.process_grid(d_occ, Wc, Hc, Dc, d_m.at(int(offs[i - 1])), int(min(angle, 91)), d_out, d_tmp)
                     src = d_out
                 _lib.check(lib.pb3d_count_nonzero_dev(ctx, C.c_void_p(src.ptr), Wc * Hc * Dc, d_cnt.at(8 * (i - 1))))
                 _lib.check(paste_fn(ctx, C.c_void_p(d_col.ptr), C.c_void_p(d_lab.ptr), i, C.c_void_p(src.ptr), W, H, D, lo, hi, C.c_void_p(d_carved.ptr)))
             counts = d_cnt.download((num,), np.int64)
-        lines = []
-        for i in range(1, num + 1):
-            x0, y0, z0, x1, y1, z1 = (int(v) for v in bbox[i - 1])
-            lines.append(f"  - Component {i}: bbox ({x0},{y0},{z0}) → ({x1},{y1},{z1})")
-            lines.append(f"    carved voxels: {int(counts[i - 1])}")
-        print("\n".join(lines))
+        print("\n".join(_component_log(num, bbox, counts)))
         dev.sync()
-        res, d_carved = (d_carved if d_carved is not None else d_col), None
-        return res
-    finally:
-        if d_carved is not None:
-            d_carved.free()
-        if own_lab:
-            d_lab.free()
-        for b in tmp:
-            b.free()
+        return d_carved if d_carved is not None else d_col
 
 
 def _pack_crop_masks(mask2d, bbox):
@@ -527,7 +487,6 @@ class _GuidedParts:
     def __init__(self, d_grid, shape3, parts, d_lab, channels=3):
         """parts: list of (printed colour, mask2d (H,W) bool, angle, key) -- key = 3 uint8 (colour grid) or an int label value
         (label volume), None if the colour cannot occur in a uint8 grid."""
-        from . import device as dev
         self.dev, self.d_grid, self.shape3, self.d_lab, self.channels = dev, d_grid, shape3, d_lab, channels
         self.items = []           # ("text", line) | ("part", printed colour, num, bbox, offset into the counts)
         self.d_log = dev.DeviceBuffer(8 * (self.CAP + 2))
@@ -638,7 +597,6 @@ def left_right_guided_carve(colored_grid, semantic_mask, target_color, angle=60,
     """Per 3-D connected component of `target_color`: crop its bounding box, rotate-and-carve the crop's
     occupancy with the part's own angle step against the cropped 2-D mask, clear the component and paste
     what survives; reference :163-210 (prints kept: they are notebook output)."""
-    from . import device as dev
     g = _lib.as_u8(colored_grid, "colored_grid")
     if g.ndim != 4 or g.shape[3] != 3:
         raise ValueError("not enough values to unpack (expected 4, got %d)" % g.ndim)
@@ -648,16 +606,12 @@ def left_right_guided_carve(colored_grid, semantic_mask, target_color, angle=60,
     if not np.any(mask2d):
         print(f"[SKIP] No mask for color {target_color}")
         return g.copy()
-    d_col = dev.from_numpy(g)
-    try:
+    with dev.Scope() as sc:
+        d_col = sc.upload(g) or sc.alloc(0)
         d_carved = _lrgc_dev(d_col, (W, H, D), mask2d, target_color, angle)
-        try:
-            return d_carved.download(g.shape)
-        finally:
-            if d_carved is not d_col:
-                d_carved.free()
-    finally:
-        d_col.free()
+        if d_carved is not d_col:
+            sc.adopt(d_carved)
+        return d_carved.download(g.shape)
 
 
 def _extrude_args(shape3, mask_2d, axis, direction):
@@ -679,11 +633,10 @@ def _extrude_args(shape3, mask_2d, axis, direction):
 def _extrude_dev(d_in, d_out, shape3, valid_u8, vw, axis, direction, depth, fill_color, d_valid=None, label=False):
     """one extrusion on device buffers; d_out may be d_in (in place).  d_valid: the mask already on the device (a chain of calls
     with one mask uploads it once); the call only queues work."""
-    from . import device as dev
     W, H, D = shape3
     fc = None if (fill_color is None or label) else np.ascontiguousarray(np.asarray(fill_color).astype(np.uint8).reshape(3))
-    d_v = d_valid if d_valid is not None else dev.from_numpy(valid_u8)
-    try:
+    with dev.Scope() as sc:     # (a mask uploaded here goes back to the context's pool; the stream is in order)
+        d_v = d_valid if d_valid is not None else sc.upload(valid_u8) or sc.alloc(0)
         if label:       # 1-byte label volume: fill_color is the label value (None clears)
             _lib.check(_lib.load().pb3d_extrude_label_dev(_lib.ctx(), C.c_void_p(d_in.ptr), W, H, D, C.c_void_p(d_v.ptr), vw, int(axis),
                                                           1 if direction == "+" else 0, int(depth), -1 if fill_color is None else int(fill_color),
@@ -692,15 +645,11 @@ def _extrude_dev(d_in, d_out, shape3, valid_u8, vw, axis, direction, depth, fill
         _lib.check(_lib.load().pb3d_extrude_dev(_lib.ctx(), C.c_void_p(d_in.ptr), W, H, D, C.c_void_p(d_v.ptr), vw, int(axis),
                                                 1 if direction == "+" else 0, int(depth), None if fc is None else _lib.p_u8(fc),
                                                 C.c_void_p(d_out.ptr)))
-    finally:
-        if d_valid is None:
-            d_v.free()      # (the block goes back to the context's pool; the stream is in order)
 
 
 def extrude_from_surface(grid, mask_2d, axis, direction="+", depth=5, fill_color=None):
     """From the first occupied voxel along `axis` (seen from the `direction` side) paint `depth` cells
     where the 2-D mask allows; reference :213-248 (an empty column starts at index 0, like np.argmax)."""
-    from . import device as dev
     g = _lib.as_u8(grid, "grid")
     if g.ndim != 4 or g.shape[3] != 3:
         raise ValueError("extrude_from_surface expects a (W,H,D,3) grid")
@@ -708,23 +657,20 @@ def extrude_from_surface(grid, mask_2d, axis, direction="+", depth=5, fill_color
     if axis not in (0, 2) or int(depth) <= 0:
         return g.copy()
     vt, vw = _extrude_args((W, H, D), mask_2d, axis, direction)
-    d_in = dev.from_numpy(g); d_out = dev.DeviceBuffer(g.size)
-    try:
+    with dev.Scope() as sc:
+        d_in = sc.upload(g) or sc.alloc(0); d_out = sc.alloc(g.size)
         _extrude_dev(d_in, d_out, (W, H, D), vt, vw, axis, direction, depth, fill_color)
         return d_out.download(g.shape)
-    finally:
-        d_in.free(); d_out.free()
 
 
 def _recolor_dev(d_g, shape3, color, new_color, k, sort_axis, label=False):
     """recolor_backward_components in place on a device-resident (A0,A1,A2,3) grid."""
-    from . import device as dev
     A0, A1, A2 = shape3
     cu8 = int(color) if label else _color_u8(color)
     if cu8 is None or A0 * A1 * A2 == 0:
         return
-    d_lab = dev.DeviceBuffer(A0 * A1 * A2 * 4)
-    try:
+    with dev.Scope() as sc:
+        d_lab = sc.alloc(A0 * A1 * A2 * 4)
         n, _, cnt, sums = _label_stats(d_g, (A0, A1, A2), cu8, d_lab, members_only=True)
         if n == 0:
             return
@@ -736,29 +682,24 @@ def _recolor_dev(d_g, shape3, color, new_color, k, sort_axis, label=False):
         _lib.check(_lib.load().pb3d_recolor_last_labelled_dev(_lib.ctx(), C.c_void_p(d_lab.ptr), A0 * A1 * A2, _lib.p_u8(flags), n,
                                                               _lib.p_u8(nc), C.c_void_p(d_g.ptr), 1 if label else 3))
         dev.sync()
-    finally:
-        d_lab.free()
 
 
 def recolor_backward_components(voxel_grid, color, new_color, k=4, sort_axis=2):
     """Keep the k components of `color` with the smallest mean coordinate on sort_axis, recolour the rest;
     reference :252-266.  Returns a C-contiguous copy (the input is usually a transposed/flipped view)."""
-    from . import device as dev
     g = np.ascontiguousarray(_lib.as_u8(voxel_grid, "voxel_grid"))
     if g.ndim != 4 or g.shape[3] != 3:
         raise ValueError("recolor_backward_components expects an (A0,A1,A2,3) grid")
     if g.size == 0:
         return g.copy()
-    d_g = dev.from_numpy(g)
-    d_lab = dev.DeviceBuffer(g.size // 3 * 4); d_st = dev.DeviceBuffer(16)
-    try:
+    with dev.Scope() as sc:
+        d_g = sc.upload(g)
+        d_lab = sc.alloc(g.size // 3 * 4); d_st = sc.alloc(16)
         # labelling, keep decision and painting on the device (pb3d_recolor_backward_dev); the host decides for scenes with more
         # components than that entry takes
         if _recolor_queue(d_g, g.shape[:3], color, new_color, k, sort_axis, d_lab, C.c_void_p(d_st.ptr)) and d_st.download((2,), np.int64)[1]:
             _recolor_dev(d_g, g.shape[:3], color, new_color, k, sort_axis)
         return d_g.download(g.shape)
-    finally:
-        d_g.free(); d_lab.free(); d_st.free()
 
 
 def _recolor_queue(d_g, shape3, color, new_color, k, sort_axis, d_lab, d_status, label=False):
@@ -781,7 +722,6 @@ def partwise_carve(colored_voxel_grid, semantic_mask_exterior, semantic_mask_ful
     The grid stays resident in HBM from the first stage to the last (one upload, one download) and the host waits for the device
     TWICE: for the component boxes of all part colours (one labelling) and for the finished grid -- the printed log (upstream's text,
     line for line) is emitted at the end.  Only with visualize=True are intermediate grids brought back for plotting."""
-    from . import device as dev
     resident = isinstance(colored_voxel_grid, dev.DeviceGrid)     # then the result is a DeviceGrid too (the input stays the caller's)
     g = colored_voxel_grid if resident else _lib.as_u8(colored_voxel_grid, "colored_voxel_grid")
     if len(g.shape) != 4 or g.shape[3] != 3:
@@ -803,30 +743,26 @@ def partwise_carve(colored_voxel_grid, semantic_mask_exterior, semantic_mask_ful
             raise ValueError("range() arg 3 must not be zero" if angles[j] == 0 else "negative angle steps are not supported")
         angles[j] = min(angles[j], 91) if angles[j] > 0 else angles[j]
     nb = int(np.prod(g.shape, dtype=np.int64))
-    d_in = dev.DeviceBuffer(nb) if resident else dev.from_numpy(g)       # scratch later on; a resident input is only read
-    d_a = dev.DeviceBuffer(nb)
-    live = [d_in, d_a]
-    guided = None
-    try:
-        d_ms = dev.from_numpy_async(msub); d_mc = dev.from_numpy_async(mcarve)
-        live += [d_ms, d_mc]
+    with dev.Scope() as sc:
+        d_in = sc.alloc(nb) if resident else sc.upload(g) or sc.alloc(0)       # scratch later on; a resident input is only read
+        d_a = sc.alloc(nb)
+        d_ms = sc.upload(msub, wait=False) or sc.alloc(0); d_mc = sc.upload(mcarve, wait=False) or sc.alloc(0)
         _lib.check(lib.pb3d_part_carve_dev(ctx, C.c_void_p(g.buf.ptr if resident else d_in.ptr), W, H, D, C.c_void_p(d_ms.ptr), C.c_void_p(d_mc.ptr), angles, skip,
                                            len(group_jobs), C.c_void_p(d_a.ptr)))
         show(d_a, tuple(g.shape), "After part-wise symmetric carving (global symmetry on each part)")
         # 2. component-guided symmetry: ONE labelling for all part colours, the component loops queued behind it
         sm_ext = np.asarray(semantic_mask_exterior)
         key_ext = _color_key(sm_ext)
-        d_lab = dev.DeviceBuffer(W * H * D * 4)
-        live.append(d_lab)
+        d_lab = sc.alloc(W * H * D * 4)
         parts = []
         for part, angle in part_symmetry.items():
             target = part_colors_np[part]
             parts.append((target, _is_color(sm_ext, key_ext, target), angle, _color_u8(target)))
-        guided = _GuidedParts(d_a, (W, H, D), parts, d_lab)
+        guided = sc.adopt(_GuidedParts(d_a, (W, H, D), parts, d_lab))
         d_b = guided.run()
         if d_b is not d_a:          # (a part that went component by component works on a copy)
-            live.append(d_b)
-            d_a.free(); live.remove(d_a)
+            sc.adopt(d_b)
+            sc.free(d_a)
             d_a = d_b
         show(d_a, g.shape, "After part-wise symmetric carving (local symmetry on each part)")
         # 3. interior extrusion: four directions per part, IN PLACE (a column is scanned and painted by one wavefront / thread), the
@@ -840,12 +776,10 @@ def partwise_carve(colored_voxel_grid, semantic_mask_exterior, semantic_mask_ful
             mask = _is_color(sm_full, key_full, part_colors_np[part])
             for axis in (2, 0):
                 vt, vw = _extrude_args((W, H, D), mask, axis, "+")
-                d_v = dev.from_numpy_async(vt)
-                try:
-                    for direction in ("+", "-"):
-                        _extrude_dev(d_a, d_a, (W, H, D), vt, vw, axis, direction, depth, part_colors_np[part], d_valid=d_v)
-                finally:
-                    d_v.free()
+                d_v = sc.upload(vt, wait=False) or sc.alloc(0)
+                for direction in ("+", "-"):
+                    _extrude_dev(d_a, d_a, (W, H, D), vt, vw, axis, direction, depth, part_colors_np[part], d_valid=d_v)
+                sc.free(d_v)
         show(d_a, g.shape, "After interior extrusion")
         # 4. orientation + back-minaret recolouring (labelling, keep decision and painting all on the device)
         if recolor_back_minarets:
@@ -857,16 +791,9 @@ def partwise_carve(colored_voxel_grid, semantic_mask_exterior, semantic_mask_ful
                 _recolor_dev(d_b, (D, H, W), part_colors_np["front_minarets"], part_colors_np["back_minarets"], 2, 0)
             show(d_b, (D, H, W, 3), "After back-minaret recoloring")
             if resident:
-                live.remove(d_b)
-                return dev.DeviceGrid(d_b, (D, H, W, 3))
+                return dev.DeviceGrid(sc.keep(d_b), (D, H, W, 3))
             return d_b.download((D, H, W, 3))
         guided.finish()
         if resident:
-            live.remove(d_a)
-            return dev.DeviceGrid(d_a, tuple(g.shape))
+            return dev.DeviceGrid(sc.keep(d_a), tuple(g.shape))
         return d_a.download(g.shape)
-    finally:
-        if guided is not None:
-            guided.free()
-        for b in live:
-            b.free()

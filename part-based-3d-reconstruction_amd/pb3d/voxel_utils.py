@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _hostmem, _lib
+from . import _hostmem, _lib, device as dev, voxel_carving_utils as vcu
 
 __all__ = ["get_voxel_points_by_parts", "extract_top_k_components", "voxel_grid_to_points", "meshify_colored_voxel_grid"]
 
@@ -87,16 +87,14 @@ def _label_stats_conn(d_grid, shape3, colors, d_labels, connectivity, cap=1024, 
 
 def _top_k_dev(d_g, shape3, value, k, channels):
     """extract_top_k_components in place on a device buffer; value: 3 uint8 (channels = 3) or a label value (channels = 1)."""
-    from . import device as dev
-    from .voxel_carving_utils import _component_stats
     A0, A1, A2 = shape3
     if A0 * A1 * A2 == 0:
         return
     c3 = np.array([value, 0, 0], np.uint8) if channels == 1 else np.ascontiguousarray(value)
     kk = max(min(int(k), 1 << 62), -(1 << 62))           # any Python int: [:k] of fewer than 2^31 components
     lib, ctx = _lib.load(), _lib.ctx()
-    d_lab = dev.DeviceBuffer(A0 * A1 * A2 * 4); d_st = dev.DeviceBuffer(16)
-    try:
+    with dev.Scope() as sc:
+        d_lab = sc.alloc(A0 * A1 * A2 * 4); d_st = sc.alloc(16)
         # labelling, ranking and zeroing on the device (pb3d_top_k_components_dev); the host decides when the records overflow
         _lib.check(lib.pb3d_top_k_components_dev(ctx, C.c_void_p(d_g.ptr), A0, A1, A2, _lib.p_u8(c3), channels, kk, 26, C.c_void_p(d_lab.ptr),
                                                  C.c_void_p(d_st.ptr)))
@@ -107,7 +105,7 @@ def _top_k_dev(d_g, shape3, value, k, channels):
         col = [value] if channels == 1 else [c3]
         n, bbox, _, _ = _label_stats_conn(d_g, shape3, col, d_lab, 26, cap=min(n, _RECORDS_MAX), members_only=False, channels=channels)[0]
         if bbox is None:
-            bbox = _component_stats(d_lab, shape3, n)[0]
+            bbox = vcu._component_stats(d_lab, shape3, n)[0]
         heights = bbox[:, 4] - 1 - bbox[:, 1]
         top = sorted(range(n), key=lambda i: -heights[i])[:kk]
         flags = np.ones(n, np.uint8)
@@ -116,44 +114,34 @@ def _top_k_dev(d_g, shape3, value, k, channels):
         _lib.check(lib.pb3d_recolor_last_labelled_dev(ctx, C.c_void_p(d_lab.ptr), A0 * A1 * A2, _lib.p_u8(flags), n, _lib.p_u8(zero),
                                                       C.c_void_p(d_g.ptr), channels))
         dev.sync()
-    finally:
-        d_lab.free(); d_st.free()
 
 
 def extract_top_k_components(voxel_grid, color, k=4):
     """Keep the k tallest 26-connected components of `color` (height = extent along axis 1; equal heights in label order), zero the
     other voxels of that colour; reference :24-33.  Returns a new C-contiguous uint8 array (the input is not changed), or a new
     pb3d.device.DeviceGrid for a resident grid (the input stays the caller's)."""
-    from . import device as dev
-    from .voxel_carving_utils import _color_u8
     resident = isinstance(voxel_grid, dev.DeviceGrid)
     g = voxel_grid if resident else _lib.as_u8(voxel_grid, "voxel_grid")
     if len(g.shape) != 4 or g.shape[3] != 3:
         raise ValueError("extract_top_k_components expects an (A0,A1,A2,3) grid")
     if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)):
         raise TypeError("k must be an integer")
-    cu8 = _color_u8(color)
+    cu8 = vcu._color_u8(color)
     shape3 = tuple(int(v) for v in g.shape[:3])
     nbytes = int(np.prod(g.shape, dtype=np.int64))
-    if resident:
-        d_out = dev.DeviceBuffer(nbytes)
-        try:
+    if not resident and (cu8 is None or g.size == 0):       # a colour that no uint8 voxel can equal: nothing is a member
+        return np.ascontiguousarray(g).copy()
+    with dev.Scope() as sc:
+        if resident:
+            d_out = sc.result(None, nbytes)
             if nbytes:
                 _lib.check(_lib.load().pb3d_d2d(_lib.ctx(), C.c_void_p(d_out.ptr), C.c_void_p(g.buf.ptr), nbytes))
             if cu8 is not None:
                 _top_k_dev(d_out, shape3, cu8, k, 3)
-        except BaseException:
-            d_out.free()
-            raise
-        return dev.DeviceGrid(d_out, g.shape)
-    if cu8 is None or g.size == 0:      # a colour that no uint8 voxel can equal: nothing is a member
-        return np.ascontiguousarray(g).copy()
-    d_g = dev.from_numpy(g)
-    try:
+            return dev.DeviceGrid(d_out, g.shape)
+        d_g = sc.upload(g)
         _top_k_dev(d_g, shape3, cu8, k, 3)
         return d_g.download(g.shape)
-    finally:
-        d_g.free()
 
 
 # ---- meshify_colored_voxel_grid (reference :53-96): binary marching cubes + nearest-filled-voxel colours (csrc/mesh.hip) ----------

@@ -18,7 +18,8 @@ import math
 
 import numpy as np
 
-from . import _lib
+from . import _lib, device as dev
+from ._args import _counts, _grid_channels, _mesh, _on_device
 from ._lib import _ptr
 
 __all__ = ["voxelize_mesh", "voxelize_mesh_resident", "grid_overlap_counts", "grid_overlap_counts_resident", "mesh_grid_iou"]
@@ -76,35 +77,19 @@ def voxelize_mesh_resident(d_verts, n_vertices, d_faces, n_faces, shape, origin=
     pb3d.device.meshify(..., download=False) hands out float32 vertices and int32 faces in frame="meshify".  With return_stats also the
     dict of crossings, occupied, open_columns and flat_faces (one more download).  Everything is enqueued behind the check of the indices
     (IndexError) and of the coordinates (ValueError on one that is not finite); `out` is untouched when it fails."""
-    from . import device as dev
-    from .smooth import _counts
     nv, nf = _counts(n_vertices, n_faces)
     s = _shape(shape)
     o, vs, fr, d = _placement(origin, voxel_size, frame, depth, s)
     val = _value(value)
-    d_out = out if out is not None else dev.DeviceBuffer(s[0] * s[1] * s[2] * len(val))
     stats = (C.c_int64 * 4)() if return_stats else None
-    try:
+    with dev.Scope() as sc:
+        d_out = sc.result(out, s[0] * s[1] * s[2] * len(val))
         _lib.check(_lib.load().pb3d_voxelize_mesh_resident(_lib.ctx(), _ptr(d_verts), int(bool(verts_f64)), nv, _ptr(d_faces), int(bool(faces_i64)),
                                                            nf, s[0], s[1], s[2], _lib.p_dbl(o), vs, fr, d, len(val), _lib.p_u8(val), _ptr(d_out),
                                                            stats))
-    except BaseException:
-        if out is None:
-            d_out.free()
-        raise
-    if return_stats:
-        return d_out, dict(zip(STATS, (int(v) for v in stats)))
-    return d_out
-
-
-def _mesh(vertices, faces):
-    from .eval_helpers import _cloud
-    from .smooth import _faces
-    v, vf = _cloud(vertices, "vertices")
-    f, fi = _faces(faces, len(v))
-    if len(v) == 0 and len(f):
-        raise IndexError(f"index {int(f.reshape(-1)[0])} is out of bounds for axis 0 with size 0")
-    return v, vf, f, fi
+        if return_stats:
+            return d_out, dict(zip(STATS, (int(v) for v in stats)))
+        return d_out
 
 
 def voxelize_mesh(vertices, faces, shape, origin=(0, 0, 0), voxel_size=1.0, frame="lattice", depth=None, value=1, return_stats=False):
@@ -114,26 +99,15 @@ def voxelize_mesh(vertices, faces, shape, origin=(0, 0, 0), voxel_size=1.0, fram
     do.  frame="meshify" takes the vertices as meshify_colored_voxel_grid returns them (`depth` = the grid's last axis, default
     shape[2]).  return_stats adds the dict of crossings, occupied voxels, open_columns (columns whose crossings do not pair up: the mesh
     leaks there or leaves the grid's side) and flat_faces (faces the rays run parallel to)."""
-    from . import device as dev
     s = _shape(shape)
     _placement(origin, voxel_size, frame, depth, s)
     val = _value(value)
     v, vf, f, fi = _mesh(vertices, faces)
-    bufs = []
-    try:
-        d_v = dev.from_numpy(v) if len(v) else None
-        bufs.append(d_v)
-        d_f = dev.from_numpy(f) if len(f) else None
-        bufs.append(d_f)
-        res = voxelize_mesh_resident(d_v, len(v), d_f, len(f), s, origin, voxel_size, frame, depth, value, return_stats, vf, fi)
+    with dev.Scope() as sc:
+        res = voxelize_mesh_resident(sc.upload(v), len(v), sc.upload(f), len(f), s, origin, voxel_size, frame, depth, value, return_stats, vf, fi)
         d_out, stats = res if return_stats else (res, None)
-        bufs.append(d_out)
-        grid = d_out.download(s if len(val) == 1 else s + (3,))
+        grid = sc.adopt(d_out).download(s if len(val) == 1 else s + (3,))
         return (grid, stats) if return_stats else grid
-    finally:
-        for b in bufs:
-            if b is not None:
-                b.free()
 
 
 def grid_overlap_counts_resident(d_a, channels_a, d_b, channels_b, n_voxels):
@@ -143,68 +117,26 @@ def grid_overlap_counts_resident(d_a, channels_a, d_b, channels_b, n_voxels):
     return int(out[0]), int(out[1]), int(out[2])
 
 
-def _grid_shape(g, what):
-    """(channels, lattice shape) of a uint8 (n0, n1, n2[, 3]) array or DeviceGrid"""
-    from . import device as dev
-    if not isinstance(g, dev.DeviceGrid) and np.asarray(g).dtype != np.uint8:
-        raise TypeError(f"{what} must be a uint8 array (got {np.asarray(g).dtype})")
-    shape = tuple(g.shape if isinstance(g, dev.DeviceGrid) else np.shape(g))
-    if len(shape) not in (3, 4) or (len(shape) == 4 and shape[3] not in (1, 3)):
-        raise ValueError(f"{what} must have shape (n0, n1, n2) or (n0, n1, n2, 3) (got {shape})")
-    return (shape[3] if len(shape) == 4 else 1), shape[:3]
-
-
-def _grid(g, what):
-    """(device buffer, channels, lattice shape, whether the buffer is ours to free) of such a grid"""
-    from . import device as dev
-    ch, shape = _grid_shape(g, what)
-    if isinstance(g, dev.DeviceGrid):
-        return g.buf, ch, shape, False
-    g = np.asarray(g)
-    return (dev.from_numpy(g) if g.size else None), ch, shape, True
-
-
 def grid_overlap_counts(a, b):
     """(inter, count_a, count_b): the voxels non-zero in both grids, in a and in b, where non-zero means any channel > 0.  a, b: uint8
     arrays or DeviceGrids of one lattice shape, each (n0, n1, n2) or (n0, n1, n2, 3)."""
-    sa, sb = _grid_shape(a, "a")[1], _grid_shape(b, "b")[1]
+    (ca, sa), (cb, sb) = _grid_channels(a, "a"), _grid_channels(b, "b")
     if sa != sb:
         raise ValueError(f"the grids differ in shape: {sa} and {sb}")
-    bufs = []
-    try:
-        da = _grid(a, "a")
-        bufs.append(da)
-        db = _grid(b, "b")
-        bufs.append(db)
-        return grid_overlap_counts_resident(da[0], da[1], db[0], db[1], da[2][0] * da[2][1] * da[2][2])
-    finally:
-        for buf, _, _, ours in bufs:
-            if ours and buf is not None:
-                buf.free()
+    with dev.Scope() as sc:
+        return grid_overlap_counts_resident(_on_device(sc, a), ca, _on_device(sc, b), cb, sa[0] * sa[1] * sa[2])
 
 
 def mesh_grid_iou(vertices, faces, grid, origin=(0, 0, 0), voxel_size=1.0, frame="lattice"):
     """Intersection over union of the solid a mesh encloses and the occupied voxels of `grid` (a uint8 array or DeviceGrid, (n0, n1, n2) or
     (n0, n1, n2, 3)), on the grid's lattice: voxelize_mesh and grid_overlap_counts composed, the voxelized mesh never leaving the
     device.  inter / union as one float64 division; 0.0 for an empty union."""
-    from . import device as dev
     v, vf, f, fi = _mesh(vertices, faces)
-    bufs, g = [], None
-    try:
-        g = _grid(grid, "grid")
-        s = _shape(g[2])
-        d_v = dev.from_numpy(v) if len(v) else None
-        bufs.append(d_v)
-        d_f = dev.from_numpy(f) if len(f) else None
-        bufs.append(d_f)
-        d_m = voxelize_mesh_resident(d_v, len(v), d_f, len(f), s, origin, voxel_size, frame, None, 1, False, vf, fi)
-        bufs.append(d_m)
-        inter, na, nb = grid_overlap_counts_resident(d_m, 1, g[0], g[1], s[0] * s[1] * s[2])
+    ch, shape = _grid_channels(grid, "grid")
+    with dev.Scope() as sc:
+        d_g = _on_device(sc, grid)
+        s = _shape(shape)
+        d_m = sc.adopt(voxelize_mesh_resident(sc.upload(v), len(v), sc.upload(f), len(f), s, origin, voxel_size, frame, None, 1, False, vf, fi))
+        inter, na, nb = grid_overlap_counts_resident(d_m, 1, d_g, ch, s[0] * s[1] * s[2])
         union = na + nb - inter
         return float(np.float64(inter) / np.float64(union)) if union else 0.0
-    finally:
-        if g is not None and g[3] and g[0] is not None:
-            g[0].free()
-        for b in bufs:
-            if b is not None:
-                b.free()
