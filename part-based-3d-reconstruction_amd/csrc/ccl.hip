@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "pb3d_internal.h"
+#include "wave.h"
 
 namespace {
 
@@ -450,37 +451,13 @@ __global__ __launch_bounds__(256) void k_ccl_roots(const u64* __restrict__ bits_
         if (lane == 0) rootflag[(i64)blockIdx.x * (kWinPerBlock / 64) + 4 * q + wv] = fl;
         cnt += (u32)__popcll(roots);
     }
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
-    if (lane == 0) wsum[wv] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) chunk_count[(i64)blockIdx.y * gridDim.x + blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    group_total<4>(wave_sum(cnt), wsum, [&](u32 tot) { chunk_count[(i64)blockIdx.y * gridDim.x + blockIdx.x] = tot; });
 }
 
 // exclusive scan of a colour's chunk counts, one block per colour (16 384 chunks at 1024^3); total[colour] = number of components
 __global__ __launch_bounds__(1024) void k_ccl_scan(const u32* __restrict__ counts_all, i64 nchunks, u32* __restrict__ chunk_base_all, i64* __restrict__ total) {
     __shared__ u32 part[1024];
-    const u32* __restrict__ counts = counts_all + (i64)blockIdx.x * nchunks;
-    u32* __restrict__ chunk_base = chunk_base_all + (i64)blockIdx.x * nchunks;
-    const i64 per = (nchunks + 1023) / 1024;
-    const i64 b = (i64)threadIdx.x * per, e = b + per < nchunks ? b + per : nchunks;
-    u32 s = 0;
-    for (i64 i = b; i < e; ++i) s += counts[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x < 64) {                                      // one wavefront scans the 1024 partial sums, 16 per lane
-        u32 loc[16], sum = 0;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) { loc[k] = part[16 * threadIdx.x + k]; sum += loc[k]; }
-        u32 inc = sum;
-        for (int off = 1; off < 64; off <<= 1) { const u32 t = __shfl_up(inc, off); if ((int)threadIdx.x >= off) inc += t; }
-        u32 run = inc - sum;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) { part[16 * threadIdx.x + k] = run; run += loc[k]; }
-        if (threadIdx.x == 63) total[blockIdx.x] = (i64)run;
-    }
-    __syncthreads();
-    u32 run = part[threadIdx.x];
-    for (i64 i = b; i < e; ++i) { chunk_base[i] = run; run += counts[i]; }
+    group_scan_array(counts_all + (i64)blockIdx.x * nchunks, nchunks, chunk_base_all + (i64)blockIdx.x * nchunks, &total[blockIdx.x], part);
 }
 
 // parent[root] = its 1-based rank among the roots of its colour, in raster order (positive: from here on the entry is a finished label)
@@ -489,7 +466,6 @@ __global__ __launch_bounds__(256) void k_ccl_number(i64 nwords, pb3d_magic mP, i
     __shared__ u32 wsum[4];
     const u64* __restrict__ rootbits = rootbits_all + (i64)blockIdx.y * nwords;
     const u64* __restrict__ rootflag = rootflag_all + (i64)blockIdx.y * gridDim.x * (kWinPerBlock / 64);
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     // thread i takes the four consecutive windows 4 i .. 4 i + 3 of the chunk (raster order = thread order): one nibble of a flag word
     const u32 nib = (u32)(rootflag[(i64)blockIdx.x * (kWinPerBlock / 64) + (threadIdx.x >> 4)] >> (4 * (threadIdx.x & 15))) & 15u;
     u64 r[4];
@@ -500,12 +476,7 @@ __global__ __launch_bounds__(256) void k_ccl_number(i64 nwords, pb3d_magic mP, i
         r[q] = ((nib >> q) & 1u) ? rootbits[idx] : 0ull;
         mine += (u32)__popcll(r[q]);
     }
-    u32 inc = mine;
-    for (int off = 1; off < 64; off <<= 1) { const u32 t = __shfl_up(inc, off); if (lane >= off) inc += t; }
-    if (lane == 63) wsum[wv] = inc;
-    __syncthreads();
-    u32 label = chunk_base[(i64)blockIdx.y * gridDim.x + blockIdx.x] + inc - mine;
-    for (int k = 0; k < wv; ++k) label += wsum[k];
+    u32 label = chunk_base[(i64)blockIdx.y * gridDim.x + blockIdx.x] + group_excl_scan<256>(mine, wsum);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         u64 m = r[q];
@@ -730,10 +701,8 @@ __global__ __launch_bounds__(256) void k_ccl_fold(int K, int dcap, const i64* __
             for (int a = 0; a < 3; ++a) { lo[a] = bb[a]; hi[a] = bb[3 + a]; }
             for (int a = 0; a < 4; ++a) cs[a] = sp[a];
         }
-        for (int off = 32; off > 0; off >>= 1) {
-            for (int a = 0; a < 3; ++a) { lo[a] = min(lo[a], __shfl_xor(lo[a], off)); hi[a] = max(hi[a], __shfl_xor(hi[a], off)); }
-            for (int a = 0; a < 4; ++a) cs[a] += __shfl_xor(cs[a], off);
-        }
+        for (int a = 0; a < 3; ++a) { lo[a] = wave_min(lo[a]); hi[a] = wave_max(hi[a]); }
+        for (int a = 0; a < 4; ++a) cs[a] = wave_sum(cs[a]);
         if (lane < 2 && (lane == 0 || c < kFirst)) {
             char* out = lane == 0 ? fin + ((i64)k * dcap + c) * 64 : head + ((i64)k * kFirst + c) * 64;
             int* ob = (int*)out;

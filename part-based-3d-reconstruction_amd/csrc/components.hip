@@ -1,6 +1,7 @@
 // N1/N2: per-component statistics, the crop / paste steps of left_right_guided_carve, surface extrusion and component
 // recolouring.  The connected-component labelling itself (pb3d_label_color_dev) is csrc/ccl.hip.
 #include "pb3d_internal.h"
+#include "wave.h"
 
 namespace {
 
@@ -200,20 +201,6 @@ __global__ __launch_bounds__(1024) void k_recolor_select(const i64* __restrict__
 // ordered count).  O(n + A1), no cap of its own below dcap.  status[0] = number of components, status[1] = 1 when the records do not
 // hold them all or A1 exceeds the histogram (nothing is flagged then: the caller's host path decides).
 constexpr int kTopkBins = 8192;
-__device__ __forceinline__ u32 block_excl_scan1024(u32 v, u32* part) {
-    const int tid = (int)threadIdx.x;
-    part[tid] = v;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        const u32 t = tid >= off ? part[tid - off] : 0u;
-        __syncthreads();
-        part[tid] += t;
-        __syncthreads();
-    }
-    const u32 inc = part[tid];
-    __syncthreads();
-    return inc - v;
-}
 __device__ __forceinline__ int rec_height(const char* records, int i) {
     const int* bb = (const int*)(records + (i64)i * 64);
     return bb[4] - bb[1];
@@ -221,7 +208,7 @@ __device__ __forceinline__ int rec_height(const char* records, int i) {
 __global__ __launch_bounds__(1024) void k_topk_select(const i64* __restrict__ total, const char* __restrict__ records, int dcap, int A1, i64 k,
                                                       u8* __restrict__ flags, i64* __restrict__ status) {
     __shared__ u32 hist[kTopkBins];
-    __shared__ u32 part[1024];
+    __shared__ u32 wsum[16];
     __shared__ int s_thr;
     __shared__ u32 s_take;
     const int tid = (int)threadIdx.x;
@@ -241,7 +228,7 @@ __global__ __launch_bounds__(1024) void k_topk_select(const i64* __restrict__ to
     u32 mine = 0;
 #pragma unroll
     for (int j = 0; j < kPer; ++j) mine += hist[btop - j];
-    u32 above = block_excl_scan1024(mine, part);
+    u32 above = group_excl_scan<1024>(mine, wsum);
 #pragma unroll
     for (int j = 0; j < kPer; ++j) {
         const u32 h = hist[btop - j];
@@ -255,7 +242,7 @@ __global__ __launch_bounds__(1024) void k_topk_select(const i64* __restrict__ to
     const int per = (m + 1023) / 1024, i0 = tid * per, i1 = i0 + per < m ? i0 + per : m;
     u32 eq = 0;
     for (int i = i0; i < i1; ++i) eq += rec_height(records, i) == thr;
-    u32 ord = block_excl_scan1024(eq, part);
+    u32 ord = group_excl_scan<1024>(eq, wsum);
     for (int i = i0; i < i1; ++i) {
         const int h = rec_height(records, i);
         bool kept = h > thr;
@@ -486,7 +473,7 @@ __global__ __launch_bounds__(256) void k_orient128(const u8* __restrict__ grid, 
 __global__ __launch_bounds__(256) void k_count_nonzero(const u8* __restrict__ b, i64 n, unsigned long long* __restrict__ count) {
     unsigned long long c = 0;
     for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (i64)gridDim.x * blockDim.x) c += b[i] != 0;
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    c = wave_sum(c);
     if ((threadIdx.x & 63) == 0 && c) atomicAdd(count, c);
 }
 

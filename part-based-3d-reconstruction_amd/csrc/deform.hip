@@ -11,6 +11,7 @@
 #include <cmath>
 
 #include "pb3d_internal.h"
+#include "wave.h"
 #include "project_point.h"
 
 namespace {
@@ -144,7 +145,7 @@ __global__ __launch_bounds__(256) void k_deform_project_batch(const float* __res
         int ui, vi;
         if (pb3d_proj::project_xyz<0>(P, q, &ui, &vi)) mark[(i64)vi * P.Wimg + ui] = 1;
     }
-    for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o);
+    mine = wave_sum(mine);
     if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&nvalid[blockIdx.y], mine);
 }
 
@@ -158,7 +159,7 @@ __global__ __launch_bounds__(256) void k_deform_iou_batch(const u8* __restrict__
         const bool b = seg[3 * px] == c0 && seg[3 * px + 1] == c1 && seg[3 * px + 2] == c2;
         ni += (a && b); nu += (a || b);
     }
-    for (int o = 32; o > 0; o >>= 1) { ni += __shfl_xor(ni, o); nu += __shfl_xor(nu, o); }
+    ni = wave_sum(ni); nu = wave_sum(nu);
     if ((threadIdx.x & 63) == 0) {
         if (ni) atomicAdd(&counts[2 * blockIdx.y], ni);
         if (nu) atomicAdd(&counts[2 * blockIdx.y + 1], nu);

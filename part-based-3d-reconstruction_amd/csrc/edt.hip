@@ -25,6 +25,7 @@
 #include <cmath>
 
 #include "pb3d_internal.h"
+#include "wave.h"
 
 namespace {
 
@@ -42,36 +43,6 @@ __device__ __forceinline__ bool occupied(const u8* g, i64 v) {
     if (CH == 1) return g[v] != 0;
     const u8* p = g + 3 * v;
     return (p[0] | p[1] | p[2]) != 0;
-}
-
-__device__ __forceinline__ u64 wave_sum(u64 c) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d);
-    return c;
-}
-__device__ __forceinline__ u64 wave_max(u64 c) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) c = max(c, (u64)__shfl_xor(c, d));
-    return c;
-}
-
-// *dst += the sum (MAX: = the maximum with the maximum) of c over a 256-thread workgroup, by one atomic; every thread calls it
-template <bool MAX>
-__device__ __forceinline__ void group_reduce(u64 c, u64* dst) {
-    __shared__ u64 part[4];
-    c = MAX ? wave_max(c) : wave_sum(c);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        if (MAX) {
-            const u64 t = max(max(part[0], part[1]), max(part[2], part[3]));
-            if (t) atomicMax((unsigned long long*)dst, (unsigned long long)t);
-        } else {
-            const u64 t = (part[0] + part[1]) + (part[2] + part[3]);
-            if (t) atomicAdd((unsigned long long*)dst, (unsigned long long)t);
-        }
-    }
-    __syncthreads();
 }
 
 // the largest w' < w (smallest w' > w) whose bit is set in the masks nz[0 .. kRowGroups), or -1
@@ -174,7 +145,7 @@ __global__ __launch_bounds__(256) void k_edt_rows(const u8* __restrict__ grid, i
         }
         __syncthreads();
     }
-    group_reduce<false>(ntargets, &counts[0]);
+    group_add(ntargets, &counts[0]);
 }
 
 struct Cols {
@@ -324,12 +295,12 @@ __global__ __launch_bounds__(256) void k_surface_stats(const u8* __restrict__ a,
 #pragma unroll
         for (int t = 0; t < 8; ++t) within[t] += (t < th.n && s <= th.t[t]) ? 1 : 0;
     }
-    group_reduce<false>(cnt, &counts[0]);
-    group_reduce<true>(best, &counts[1]);
-    group_reduce<false>(sum, &counts[2]);
+    group_add(cnt, &counts[0]);
+    group_max(best, &counts[1]);
+    group_add(sum, &counts[2]);
 #pragma unroll
     for (int t = 0; t < 8; ++t)
-        if (t < th.n) group_reduce<false>(within[t], &counts[3 + t]);
+        if (t < th.n) group_add(within[t], &counts[3 + t]);
 }
 
 bool grid_ok(i64 n0, i64 n1, i64 n2) {

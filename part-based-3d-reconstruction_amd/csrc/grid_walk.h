@@ -6,6 +6,7 @@
 // voxels with dword loads where the rows allow it (lanes of a wave take consecutive a2).  Voxel (a0, a1, a2) is the point (x = a2, y = a1, z = a0).
 #pragma once
 #include "pb3d_internal.h"
+#include "wave.h"
 #include "project_point.h"
 
 namespace pb3d_walk {
@@ -173,9 +174,7 @@ __device__ __forceinline__ void rewrite_walk(const Walk& w, const Colours& cols,
     }
     if (!counts) return;                  // wave-uniform; below, every lane of the wave takes part in the shuffles
     for (int j = 0; j < nviews; ++j) {
-        int c = (int)((tally[j >> 2] >> (16 * (j & 3))) & 0xffffu);
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d);
+        const int c = wave_sum((int)((tally[j >> 2] >> (16 * (j & 3))) & 0xffffu));
         if (__lane_id() == 0 && c) atomicAdd(&counts[j], (unsigned long long)c);
     }
 }

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "rot_common.h"
+#include "wave.h"
 
 namespace {
 
@@ -211,8 +212,7 @@ __global__ __launch_bounds__(GTHREADS) void k_crop_chain(const u8* src_rgb, u8* 
             xs += dx; zs += dz; if (zs >= Dc) { zs -= Dc; ++xs; }
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+    cnt = wave_sum(cnt);
     if ((tid & 63) == 0 && cnt) atomicAdd(&counts[d.id - 1], cnt);
 }
 

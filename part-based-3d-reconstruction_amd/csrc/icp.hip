@@ -25,6 +25,7 @@
 #include <cmath>
 
 #include "pb3d_internal.h"
+#include "wave.h"
 #include "reduce_rows.h"
 
 namespace {
@@ -85,13 +86,9 @@ __global__ __launch_bounds__(256) void k_icp_keys(const double* __restrict__ mov
         cand = icp_pair<TF64, true>(moved, nearest, i, tgt, nt, max_dist2, p, q, &d2);
         keys[i] = cand ? (u64)__double_as_longlong(d2) : kNotCandidate;
     }
-    const int c = __popcll(__ballot(cand));
-    if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int tot = wc[0] + wc[1] + wc[2] + wc[3];
+    group_total<4>((int)__popcll(__ballot(cand)), wc, [&](int tot) {
         if (tot) atomicAdd((unsigned long long*)&hdr->m, (unsigned long long)tot);      // integer: exact in any order
-    }
+    });
 }
 
 // k = (rho >= 1) ? m : min(m, ceil(rho * m)): one rounded product, then ceil; the selection's rank is k - 1

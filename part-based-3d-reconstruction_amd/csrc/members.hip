@@ -8,6 +8,7 @@
 // counts -> one-workgroup exclusive scan -> fill at the block's offset + in-block rank.  The row sums and the mask are written by the
 // count pass, so a call that wants only those is one launch.
 #include "pb3d_internal.h"
+#include "wave.h"
 
 namespace {
 
@@ -53,17 +54,12 @@ __device__ __forceinline__ bool member_at(const MemParams& p, const MemSel& s, c
     return c == s.color && labels[v] == s.label;
 }
 
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
 // pass 1: per-block member counts (COUNTS), bottom / top row sums (ROWS), mask bytes (MASK)
 template <int C, bool COUNTS, bool ROWS, bool MASK>
 __global__ __launch_bounds__(256) void k_members_count(const u8* __restrict__ grid, const int* __restrict__ labels, MemParams p,
                                                        u32* __restrict__ block_counts, unsigned long long* __restrict__ rows, u8* __restrict__ masks) {
     __shared__ u32 wsum[4];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
     const int k = sel_of_block(p, blockIdx.x);
     const MemSel& s = p.s[k];
     const u32 base = (blockIdx.x - s.blk0) * (u32)kBlockVox;
@@ -88,30 +84,14 @@ __global__ __launch_bounds__(256) void k_members_count(const u8* __restrict__ gr
             for (int q = 0; q < 8; ++q)
                 if (rs[q]) atomicAdd(&rows[8 * k + q], rs[q]);
     }
-    if (COUNTS) {
-        if (lane == 0) wsum[w] = cnt;
-        __syncthreads();
-        if (threadIdx.x == 0) block_counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    }
+    if (COUNTS) group_total<4>(cnt, wsum, [&](u32 tot) { block_counts[blockIdx.x] = tot; });
 }
 
 // exclusive scan of the block counts of the whole launch in one workgroup (a few hundred blocks for minaret boxes; a full 1024^3 box is
 // 262144).  offsets[b] - offsets[blk0 of its selection] is the block's first row inside its selection.
 __global__ __launch_bounds__(1024) void k_members_scan(const u32* __restrict__ counts, int nb, i64* __restrict__ offsets) {
     __shared__ i64 part[1024];
-    const int per = (nb + 1023) / 1024;
-    const int b = threadIdx.x * per, e = b + per < nb ? b + per : nb;
-    i64 s = 0;
-    for (int i = b; i < e; ++i) s += counts[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        i64 run = 0;
-        for (int i = 0; i < 1024; ++i) { const i64 v = part[i]; part[i] = run; run += v; }
-    }
-    __syncthreads();
-    i64 run = part[threadIdx.x];
-    for (int i = b; i < e; ++i) { offsets[i] = run; run += counts[i]; }
+    group_scan_array(counts, (i64)nb, offsets, (i64*)nullptr, part);
 }
 
 // pass 2: coordinates (int64 a0, a1, a2) of the members at their rank inside the selection; never more than its `cap` rows

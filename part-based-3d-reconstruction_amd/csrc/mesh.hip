@@ -18,6 +18,7 @@
 // Passes: occupancy bitmask of the lattice (rows padded to 64 bits) -> per-block vertex / face counts ->
 // exclusive scans (points.hip's scan) -> vertices + per-cube vertex base -> faces -> colours.
 #include "pb3d_internal.h"
+#include "wave.h"
 
 namespace {
 
@@ -140,20 +141,6 @@ __device__ __forceinline__ void cube_coords(const MeshParams& p, i64 t, i64* c0,
     *c0 = r / p.m1;
 }
 
-// exclusive block scan (256 threads) of v; *total = block sum
-__device__ __forceinline__ u32 block_scan(u32 v, u32* wsum, u32* total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    u32 inc = v;
-    for (int off = 1; off < 64; off <<= 1) { const u32 t = __shfl_up(inc, off); if (lane >= off) inc += t; }
-    if (lane == 63) wsum[wv] = inc;
-    __syncthreads();
-    u32 before = inc - v;
-    for (int k = 0; k < wv; ++k) before += wsum[k];
-    *total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    __syncthreads();
-    return before;
-}
-
 
 // occupancy bitmask of the lattice: one wave per 64-bit word, bit k of row (i, j) = any channel of grid[i*s, j*s, k*s] > 0
 __global__ __launch_bounds__(256) void k_mesh_bits(MeshParams p, u64* __restrict__ bits) {
@@ -185,8 +172,8 @@ __global__ __launch_bounds__(256) void k_mesh_count(MeshParams p, const u64* __r
         if (nf) nv = owned_count(cs, zbits_of(c0, c1, c2));
     }
     u32 tv, tf;
-    (void)block_scan(nv, wsum, &tv);
-    (void)block_scan(nf, wsum, &tf);
+    (void)group_excl_scan<256>(nv, wsum, &tv);
+    (void)group_excl_scan<256>(nf, wsum, &tf);
     if (threadIdx.x == 0) { vcount[blockIdx.x] = tv; fcount[blockIdx.x] = tf; }
 }
 
@@ -205,7 +192,7 @@ __global__ __launch_bounds__(256) void k_mesh_verts(MeshParams p, const u64* __r
         if (MC_NTRI[cs]) nv = owned_count(cs, zb);
     }
     u32 tot;
-    const u32 before = block_scan(nv, wsum, &tot);
+    const u32 before = group_excl_scan<256>(nv, wsum, &tot);
     if (t >= p.ncubes) return;
     const i64 base = voff[blockIdx.x] + before;
     vbase[t] = (int)base;
@@ -278,7 +265,7 @@ __global__ __launch_bounds__(256) void k_mesh_faces(MeshParams p, const u64* __r
         nf = MC_NTRI[cs];
     }
     u32 tot;
-    const u32 before = block_scan(nf, wsum, &tot);
+    const u32 before = group_excl_scan<256>(nf, wsum, &tot);
     if (!nf) return;
     const int zb = zbits_of(c[0], c[1], c[2]);
     const int mybase = vbase[t];

@@ -57,6 +57,7 @@
 
 #include "mesh_index.h"
 #include "pb3d_internal.h"
+#include "wave.h"
 #include "ring_walk.h"
 
 namespace {
@@ -188,7 +189,7 @@ __global__ __launch_bounds__(256) void k_face_entries(const double* __restrict__
         face_cells(g, tri + 9 * f, lo, hi);
         n += (unsigned long long)(hi[0] - lo[0] + 1) * (unsigned long long)(hi[1] - lo[1] + 1) * (unsigned long long)(hi[2] - lo[2] + 1);
     }
-    for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off);
+    n = wave_sum(n);
     if ((threadIdx.x & 63) == 0 && n) atomicAdd(total, n);
 }
 

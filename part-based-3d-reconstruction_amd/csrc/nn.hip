@@ -18,6 +18,7 @@
 #include <cmath>
 
 #include "pb3d_internal.h"
+#include "wave.h"
 #include "ring_walk.h"      // the cell grid (Grid, make_grid, cell_of, cell_index) and ring_walk with its bounds
 
 namespace {
@@ -39,11 +40,7 @@ __global__ __launch_bounds__(256) void k_bounds_partial(const void* __restrict__
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
     for (int c = 0; c < 6; ++c) {
-        double v = m[c];
-        for (int off = 32; off > 0; off >>= 1) {
-            const double o = __shfl_xor(v, off);
-            v = c < 3 ? fmin(v, o) : fmax(v, o);
-        }
+        const double v = c < 3 ? wave_min(m[c]) : wave_max(m[c]);
         if (lane == 0) red[c][w] = v;
     }
     __syncthreads();
@@ -276,7 +273,7 @@ __global__ __launch_bounds__(256) void k_iou_count(const u32* __restrict__ a, co
         ci += __popc(x & y);
         cu += __popc(x | y);
     }
-    for (int off = 32; off > 0; off >>= 1) { ci += __shfl_xor(ci, off); cu += __shfl_xor(cu, off); }
+    ci = wave_sum(ci); cu = wave_sum(cu);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     if (lane == 0) { red[0][w] = ci; red[1][w] = cu; }
     __syncthreads();

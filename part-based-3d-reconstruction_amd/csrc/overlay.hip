@@ -10,6 +10,7 @@
 // The blend (0.7 * proj + 0.3 * image).astype(np.uint8) is float64 in NumPy: two multiplies, one add, truncation.  It is evaluated
 // here with __dmul_rn / __dadd_rn (and the build has -ffp-contract=off), so every byte is NumPy's.
 #include "pb3d_internal.h"
+#include "wave.h"
 #include "grid_walk.h"
 
 namespace {
@@ -54,12 +55,9 @@ __global__ __launch_bounds__(256) void k_grid_bounds(Walk w, Colours cols, long 
             hi2 = (int)a2 + (31 - __clz(cols_hit));
         }
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        cnt += __shfl_xor(cnt, d);
-        lo0 = min(lo0, __shfl_xor(lo0, d)); lo1 = min(lo1, __shfl_xor(lo1, d)); lo2 = min(lo2, __shfl_xor(lo2, d));
-        hi0 = max(hi0, __shfl_xor(hi0, d)); hi1 = max(hi1, __shfl_xor(hi1, d)); hi2 = max(hi2, __shfl_xor(hi2, d));
-    }
+    cnt = wave_sum(cnt);
+    lo0 = wave_min(lo0); lo1 = wave_min(lo1); lo2 = wave_min(lo2);
+    hi0 = wave_max(hi0); hi1 = wave_max(hi1); hi2 = wave_max(hi2);
     const int wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) {
         s_box[wave][0] = cnt;

@@ -18,6 +18,7 @@
 #include <cmath>
 
 #include "pb3d_internal.h"
+#include "wave.h"
 #include "reduce_rows.h"
 
 namespace {
@@ -147,9 +148,7 @@ __global__ __launch_bounds__(256) void k_crop_count(i64 n, Keep pred, u32* __res
     const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
     const bool keep = i < n && pred(i);
     const u32 c = (u32)__popcll(__ballot(keep));
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    group_total<4>(c, wsum, [&](u32 tot) { counts[blockIdx.x] = tot; });
 }
 
 template <bool F64, class Keep>

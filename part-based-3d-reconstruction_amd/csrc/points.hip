@@ -5,6 +5,7 @@
 // atomic append would break that, so compaction is a three-launch ordered scan: per-block popcounts
 // (wave64 ballots) -> exclusive scan of the block counts -> fill at base + in-block rank.
 #include "pb3d_internal.h"
+#include "wave.h"
 
 namespace {
 
@@ -57,7 +58,6 @@ __device__ __forceinline__ bool selected(const SelParams& p, const u8* __restric
 
 __global__ __launch_bounds__(256) void k_points_count(const u8* __restrict__ grid, SelParams p, u32* __restrict__ block_counts) {
     __shared__ u32 wsum[4];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const i64 base = (i64)blockIdx.x * kBlockVox;
     u32 cnt = 0;
     for (int it = 0; it < kItems; ++it) {
@@ -69,9 +69,7 @@ __global__ __launch_bounds__(256) void k_points_count(const u8* __restrict__ gri
         }
         cnt += (u32)__popcll(__ballot(sel));
     }
-    if (lane == 0) wsum[w] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) block_counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    group_total<4>(cnt, wsum, [&](u32 tot) { block_counts[blockIdx.x] = tot; });
 }
 
 // Exclusive scan of the nb block counts into 64-bit offsets, three small launches:
@@ -82,18 +80,11 @@ constexpr int kSeg = 1024;
 
 __global__ __launch_bounds__(256) void k_scan_local(const u32* __restrict__ counts, i64 nb, u32* __restrict__ local, u32* __restrict__ seg_total) {
     __shared__ u32 wsum[4];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const i64 i0 = (i64)blockIdx.x * kSeg + 4 * threadIdx.x;
     u32 c[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) c[k] = i0 + k < nb ? counts[i0 + k] : 0u;
-    const u32 mine = c[0] + c[1] + c[2] + c[3];
-    u32 inc = mine;
-    for (int off = 1; off < 64; off <<= 1) { const u32 t = __shfl_up(inc, off); if (lane >= off) inc += t; }
-    if (lane == 63) wsum[wv] = inc;
-    __syncthreads();
-    u32 before = inc - mine;
-    for (int k = 0; k < wv; ++k) before += wsum[k];
+    u32 before = group_excl_scan<256>(c[0] + c[1] + c[2] + c[3], wsum);
 #pragma unroll
     for (int k = 0; k < 4; ++k) { if (i0 + k < nb) local[i0 + k] = before; before += c[k]; }
     if (threadIdx.x == 255) seg_total[blockIdx.x] = before;
@@ -101,20 +92,7 @@ __global__ __launch_bounds__(256) void k_scan_local(const u32* __restrict__ coun
 
 __global__ __launch_bounds__(1024) void k_scan_totals(const u32* __restrict__ seg_total, i64 nseg, i64* __restrict__ seg_base, i64* __restrict__ total) {
     __shared__ i64 part[1024];
-    const i64 per = (nseg + 1023) / 1024;
-    const i64 b = (i64)threadIdx.x * per, e = b + per < nseg ? b + per : nseg;
-    i64 s = 0;
-    for (i64 i = b; i < e; ++i) s += seg_total[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        i64 run = 0;
-        for (int i = 0; i < 1024; ++i) { const i64 v = part[i]; part[i] = run; run += v; }
-        *total = run;
-    }
-    __syncthreads();
-    i64 run = part[threadIdx.x];
-    for (i64 i = b; i < e; ++i) { seg_base[i] = run; run += seg_total[i]; }
+    group_scan_array(seg_total, nseg, seg_base, total, part);
 }
 
 __global__ __launch_bounds__(256) void k_scan_add(const u32* __restrict__ local, const i64* __restrict__ seg_base, i64 nb, i64* __restrict__ offsets) {
@@ -256,11 +234,7 @@ __global__ __launch_bounds__(256) void k_points_count16(const u8* __restrict__ g
     u32 w[12];
     const u32 sel = v0 < p.nlat ? (C == 3 ? select16(p, htab, grid, v0, p.nlat, w) : select16_occ(grid, v0, p.nlat, w, p.labelsel ? htab : nullptr)) : 0u;
     masks[(i64)blockIdx.x * 256 + threadIdx.x] = (unsigned short)sel;
-    u32 c = (u32)__popc(sel);
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) block_counts[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    group_total<4>(wave_sum((u32)__popc(sel)), wsum, [&](u32 tot) { block_counts[blockIdx.x] = tot; });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -300,9 +274,8 @@ __global__ __launch_bounds__(256) void k_points_fillw(const u8* __restrict__ gri
     const u32 mymask = bm[64 * wv + lane];                // selection of voxels wbase + 16 lane .. + 15 (bits past the grid's end are zero)
     u32 pre = 0;
     for (int q = 0; q < wv; ++q) pre += (u32)__popc((u32)bm[64 * q + lane]);
-    u32 tot = (u32)__popc(mymask);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { pre += __shfl_xor(pre, o); tot += __shfl_xor(tot, o); }
+    pre = wave_sum(pre);
+    const u32 tot = wave_sum((u32)__popc(mymask));
     if (tot == 0) return;
     const i64 out0 = block_off[bid] + pre;
     float* fw = fwin[wv];
@@ -353,9 +326,7 @@ __global__ __launch_bounds__(256) void k_points_fillw(const u8* __restrict__ gri
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const u32 c = (u32)__popc(sel[r]);
-        u32 inc = c;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) { const u32 t = __shfl_up(inc, off); if (lane >= off) inc += t; }
+        const u32 inc = wave_incl_scan(c);
         const u32 n = (u32)__builtin_amdgcn_readlane((int)inc, 63);
         if (n == 0) continue;
         // ---- scatter: coordinates and colour records of this lane's selected voxels

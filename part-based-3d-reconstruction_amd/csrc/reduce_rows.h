@@ -5,17 +5,17 @@
 // No floating-point atomics; the Makefile's -ffp-contract=off keeps every addition one rounded operation.
 #pragma once
 #include "pb3d_internal.h"
+#include "wave.h"
 
 // The workgroup's 256 (count, W values) -> row[0] = count, row[1 + c] = sum c: per wave the butterfly v += shfl_xor(v, off) for
-// off = 32 ... 1 (every lane ends with the same bits: IEEE addition commutes), then the four wave sums added left to right.
+// off = 32 ... 1 (wave.h's wave_sum; every lane ends with the same bits: IEEE addition commutes), then the four wave sums added left to right.
 template <int W>
 __device__ __forceinline__ void pb3d_reduce_row(double v[W], i64 cnt, double* __restrict__ row) {
     __shared__ double red[4][W];
     __shared__ i64 redc[4];
+    cnt = wave_sum(cnt);
 #pragma unroll
-    for (int c = 0; c < W; ++c)
-        for (int off = 32; off > 0; off >>= 1) v[c] += __shfl_xor(v[c], off);
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
+    for (int c = 0; c < W; ++c) v[c] = wave_sum(v[c]);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     if (lane == 0) {
 #pragma unroll

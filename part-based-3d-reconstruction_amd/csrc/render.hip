@@ -21,7 +21,7 @@
 #include <algorithm>
 #include <cmath>
 
-#include "group_sum.h"
+#include "wave.h"
 #include "mesh_index.h"
 #include "pb3d_internal.h"
 

@@ -14,6 +14,7 @@
 #include <cstddef>
 
 #include "pb3d_internal.h"
+#include "wave.h"
 
 namespace {
 
@@ -81,19 +82,12 @@ __global__ __launch_bounds__(256) void k_select_hist(const double* __restrict__ 
 
 __global__ __launch_bounds__(256) void k_select_scan(SelState* __restrict__ st, const i64* __restrict__ rank0, int pass, double* __restrict__ out) {
     __shared__ i64 wsum[4];
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int t = threadIdx.x;
     const i64 c = st->hist[pass][t];
-    i64 incl = c;
-    for (int off = 1; off < 64; off <<= 1) {
-        const i64 up = __shfl_up(incl, off);
-        if (lane >= off) incl += up;
-    }
-    if (lane == 63) wsum[w] = incl;
     const i64 rank = pass ? st->rank : *rank0;
     const u64 prefix = pass ? st->prefix : 0;
-    __syncthreads();                                        // every thread has read the state before the one below rewrites it
-    for (int k = 0; k < w; ++k) incl += wsum[k];
-    const i64 excl = incl - c;
+    const i64 excl = group_excl_scan<256>(c, wsum);         // (its barriers: every thread has read the state before the one below rewrites it)
+    const i64 incl = excl + c;
     if (excl <= rank && rank < incl) {                      // exactly one bin: 0 <= rank < the total
         const u64 p = prefix | ((u64)t << (56 - 8 * pass));
         st->prefix = p;

@@ -14,6 +14,7 @@
 // the list of 16-byte units of its rotated footprint) from SciPy's f64 arithmetic.  The programs depend on (angles, W, D) only and
 // are cached across calls.  Data that is not 0/1 raises a flag in k_s32_slice: the caller then runs the byte chain (rotate.hip).
 #include "rot_common.h"
+#include "wave.h"
 
 namespace {
 
@@ -287,9 +288,7 @@ __global__ __launch_bounds__(256) void k_s32_unslice_rgb(const u32* __restrict__
     const bool whole = live && z + 16 <= D;
     // planes this WAVE walks: its lanes may sit in two plane groups (rows of different g), one of them the short last group -- walk the
     // longest, predicate per lane.  The plane loop is unrolled (static indices into v[][]); planes past npmax are skipped wave-uniformly.
-    int npmax = live ? np : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) npmax = max(npmax, __shfl_xor(npmax, o));
+    const int npmax = wave_max(live ? np : 0);
 #pragma unroll
     for (int q = 0; q < 32; ++q) {
         if (q >= npmax) continue;
@@ -449,11 +448,7 @@ __global__ __launch_bounds__(STHREADS) void k_s32_prep(StepParams sp, i64 W, i64
                 }
             }
         }
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) {
-        mn0 = min(mn0, __shfl_xor(mn0, s)); mx0 = max(mx0, __shfl_xor(mx0, s));
-        mn2 = min(mn2, __shfl_xor(mn2, s)); mx2 = max(mx2, __shfl_xor(mx2, s));
-    }
+    mn0 = wave_min(mn0); mx0 = wave_max(mx0); mn2 = wave_min(mn2); mx2 = wave_max(mx2);
     if ((tid & 63) == 0 && mx0 >= 0) { atomicMin(&bb[0], mn0); atomicMax(&bb[1], mx0); atomicMin(&bb[2], mn2); atomicMax(&bb[3], mx2); }
     __syncthreads();
     const int bx0 = bb[0], bx1 = bb[1], bz0 = bb[2] & ~3, bz1 = bb[3];      // columns start on a 16-byte boundary
@@ -485,12 +480,7 @@ __global__ __launch_bounds__(STHREADS) void k_s32_prep(StepParams sp, i64 W, i64
                 }
             }
         }
-        int inc0 = n[0], inc1 = n[1];
-#pragma unroll
-        for (int s = 1; s < 64; s <<= 1) {
-            const int a = __shfl_up(inc0, s), b2 = __shfl_up(inc1, s);
-            if (tid >= s) { inc0 += a; inc1 += b2; }
-        }
+        const int inc0 = wave_incl_scan(n[0]), inc1 = wave_incl_scan(n[1]);
         const int tot0 = __shfl(inc0, 63);
         ustart[tid] = inc0 - n[0];
         if (tid + 64 <= SROWS) ustart[tid + 64] = tot0 + inc1 - n[1];

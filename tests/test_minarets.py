@@ -255,6 +255,51 @@ def test_device_grid_and_many_colours(pb3d_gpu):
     _same_parts(pb3d_gpu.extract_minaret_voxels_by_label(g[:, :, :53], cols), ref_voxels(g[:, :, :53], cols))
 
 
+def _box_filling_component(shape):
+    """One 6-connected component whose bounding box is the whole grid, with 4096-voxel blocks of its box that hold every voxel, none,
+    and something in between: a spine along axis 0 with three lines from the origin, ten full slices, twenty comb slices (a wall at
+    a2 = 0 and every third row to a varying length) and a full last slice behind a slice that holds the spine alone."""
+    A0, A1, A2 = shape
+    m = np.zeros(shape, bool)
+    m[:, 0, 0] = m[0, :, 0] = m[0, 0, :] = True
+    m[10:20] = True
+    a1 = np.arange(0, A1, 3)
+    for a0 in range(40, 60):
+        m[a0, :, 0] = True
+        m[a0, a1] |= np.arange(A2)[None, :] < ((a0 * 7 + a1 * 13) % A2)[:, None]
+    m[A0 - 1] = True
+    return m
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape, nblocks", [((168, 168, 168), 1158), ((128, 128, 256), 1024)])
+def test_members_of_a_box_of_many_blocks(pb3d_gpu, shape, nblocks):
+    """The member pass scans its per-block counts in one 1024-thread workgroup (k_members_scan, csrc/wave.h's group_scan_array).  A box
+    of 168^3 voxels is 1158 blocks of 4096 -- two per thread with a ragged last thread and a ragged last block -- and one of
+    128 x 128 x 256 is exactly 1024, one per thread with no slack.  The big component's colour is labelled in the first chunk of eight
+    colours and the three small ones in the second, so its box is a launch of its own.  Coordinates in np.argwhere order, exactly."""
+    big = (250, 7, 9)
+    small = [(i * 20, 7, 9) for i in (8, 9, 10)]
+    colours = [big] + [(i * 20, 7, 9) for i in range(1, 8)] + small          # 1 .. 7 colour nothing
+    m = _box_filling_component(shape)
+    per_block = np.add.reduceat(m.ravel().astype(np.int64), np.arange(0, m.size, 4096))          # the box is the grid: box raster = grid raster
+    assert len(per_block) == nblocks and per_block.min() == 0 and per_block.max() == 4096 and ((per_block > 0) & (per_block < 4096)).any()
+    g = np.zeros(shape + (3,), np.uint8)
+    g[m] = big
+    for i, c in enumerate(small):
+        g[100:102, 50:55 + i, 60 + 10 * i:62 + 10 * i] = c
+    assert ndimage.label(np.all(g == big, axis=-1))[1] == 1
+    got = pb3d_gpu.extract_minaret_voxels_by_label(g, colours)
+    assert list(got) == ["LM1", "LM2", "RM1", "RM2"]
+    seen = set()
+    for name, v in got.items():
+        colour = tuple(int(x) for x in g[tuple(v[0])])
+        seen.add(colour)
+        want = np.argwhere(np.all(g == colour, axis=-1))
+        assert v.dtype == np.int64 and v.shape == want.shape and np.array_equal(v, want), (name, colour)
+    assert seen == {big, *small}
+
+
 # ---- GPU: masks ----------------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
 @pytest.mark.parametrize("view", ["front", "drone"])

@@ -316,6 +316,30 @@ def test_seams(pb3d_gpu, n):
     check(pb3d_gpu, f"seams/{n}", *CASES[f"seams/{n}"])
 
 
+def scan_segments_cloud(n):
+    """n points whose first-appearance flags differ from one 1024-flag segment of the rank scan to the next: 3 * 1024 points in cells of
+    their own (segments of all ones), 5 * 1024 copies of them (segments of all zeros), then a random mix of new and seen cells; the two
+    small sizes get half and half"""
+    rng = np.random.default_rng(1026)
+    cell = rng.integers(0, 96, (n, 3))
+    k = min(n // 2, 3 * 1024)
+    cell[:k] = np.stack([np.arange(k) % 96, np.arange(k) // 96, np.full(k, 200)], axis=1)
+    copies = min(n - k - 1, 5 * 1024)                   # (the last point is always a random one)
+    cell[k:k + copies] = cell[np.arange(copies) % k]
+    return cell + rng.choice([0.25, 0.5, 0.75], (n, 3))
+
+
+@gpu
+@pytest.mark.parametrize("n", (1024, 1025, 1024 * 1024 + 1025))
+def test_scan_segments(pb3d_gpu, n):
+    """The rank scan (pb3d_scan_counts) is given the n first-appearance flags, so its one-workgroup pass over the segment totals
+    (k_scan_totals, csrc/wave.h's group_scan_array) sees ceil(n / 1024) of them: one, two, and 1026 -- two per thread of its 1024
+    threads with a ragged last thread, the only size at which a thread's run is longer than one.  Both reductions, to the bit."""
+    pts = scan_segments_cloud(n)
+    for reduce in REDUCES:
+        same(via_numpy(pb3d_gpu, pts, 1.0, (0.0, 0.0, 0.0), reduce), dr.restate(pts, 1.0, (0.0, 0.0, 0.0), reduce), (n, reduce))
+
+
 # ---- buffers that do not start where the allocator put them, and the optional outputs ---------------------------------------------------
 GUARD = 256
 IN_FILL, OUT_FILL = 0xFF, 0xA5
