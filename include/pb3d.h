@@ -217,6 +217,48 @@ int pb3d_mesh_count(pb3d_ctx* ctx, const uint8_t* grid, int64_t A0, int64_t A1, 
 int pb3d_mesh_fill(pb3d_ctx* ctx, int64_t nverts, int64_t nfaces, float* verts, int32_t* faces, float* normals,
                    uint8_t* cols); /* after pb3d_mesh_count on the same ctx; cols may be null */
 
+/* ---- get_marching_cubes_mesh, reference utils/eval_helpers.py:191-195: the isosurface of a float32 volume ----------
+ * The reference calls skimage's marching_cubes(volume, level) and divides the vertices by grid_size.  This is a rule of the project's
+ * own on the binary case table of meshify_colored_voxel_grid (csrc/mc_binary_table.inc), stated to the bit; on a 0/1 volume at level
+ * 0.5 it gives meshify's lattice mesh (skimage's) byte for byte.
+ *   Input     a C-contiguous float32 volume (n0, n1, n2), every n >= 2 and < 2^24, all values finite (the caller's business: a NaN
+ *             counts as outside, and a non-finite end of a crossed edge gives a non-finite vertex); level, a finite float64; divisor, a finite float32 > 0
+ *             (1 = lattice units).
+ *   Inside    a lattice point is inside iff (double)v > level.  A value equal to the level is outside.  The level is never
+ *             rounded to float32: float32(0.1) > 0.1, so a voxel holding float32(0.1) is inside at level 0.1.
+ *   Cases, ownership, order   meshify's at stride 1: case bit a0*4 + a1*2 + a2 = corner (c0+a0, c1+a1, c2+a2) inside; a cube's
+ *             triangles are the table's for that case, in table order; an edge vertex belongs to the lowest-scan-order cube that
+ *             holds the edge, the centre vertex (id 12) to its cube; a cube creates the vertices it owns in the order its triangle
+ *             list first names them; vertices and faces follow cube scan order (a2 fastest).  The triangles depend on the 8 signs
+ *             alone, and the table resolves ambiguous faces the same way from both sides: the mesh is closed and consistently
+ *             oriented wherever the volume's border is outside.
+ *   Edge vertex   between lattice points a (the lower index on the edge's axis, value va) and b (value vb):
+ *             t = (level - (double)va) / ((double)vb - (double)va), three float64 operations, each rounded once, no FMA;
+ *             0 <= t <= 1.  Its coordinate on the edge's axis is (float)((double)ia + t): one float64 addition, one rounding to
+ *             float32.  The other two coordinates are the float32 lattice indices.
+ *   Centre vertex   c + 0.5 on every axis, whatever the values.
+ *   Output    every coordinate is then divided by the divisor in float32, one correctly rounded division (x / 1.0f is x).
+ *             verts: nverts x 3 float32 in (a0, a1, a2) order; faces: nfaces x 3 int32.  No normals, no values.
+ *   Allowed   a vertex exactly on a lattice point (t = 0 where va == level), several vertices at one position, zero-area faces
+ *             (kept, so the mesh stays closed).  A level outside the data range, or a volume all inside, gives 0 vertices and faces.
+ *   Not claimed   equality with skimage on float input: its Lewiner variant decides ambiguous faces and interiors from the values and
+ *             places the extra vertex elsewhere, so vertex and face counts can differ on ambiguous cubes.
+ * count: the inside bitmask (the one full read of the volume), meshify's count and scans, one host wait; returns nverts / nfaces (an
+ * error if either reaches 2^31).  fill: must follow count with identical arguments (the level and the divisor bit for bit) and the
+ * counted sizes on the same context; enqueue only.  The pair keeps its state in the scratch slots of pb3d_mesh_count_dev /
+ * pb3d_mesh_fill_dev: a count of either ends the other's pending pair, whose fill then refuses (PB3D_EINVAL).  The host forms stage
+ * the volume; pb3d_iso_fill waits.  Arguments are checked before the context is looked at.
+ * Knob "iso_timing" (pb3d_set_tuning; the fill then waits once) times the passes with events: pb3d_iso_last gives the milliseconds
+ * of {bits pass, count and scans, vertex pass, faces} of the last count and fill. */
+int pb3d_iso_count_resident(pb3d_ctx* ctx, const float* d_vol, int64_t n0, int64_t n1, int64_t n2, double level, float divisor,
+                       int64_t* nverts, int64_t* nfaces);
+int pb3d_iso_fill_resident(pb3d_ctx* ctx, const float* d_vol, int64_t n0, int64_t n1, int64_t n2, double level, float divisor,
+                      int64_t nverts, int64_t nfaces, float* d_verts, int32_t* d_faces);
+int pb3d_iso_count(pb3d_ctx* ctx, const float* vol, int64_t n0, int64_t n1, int64_t n2, double level, float divisor,
+                   int64_t* nverts, int64_t* nfaces);
+int pb3d_iso_fill(pb3d_ctx* ctx, int64_t nverts, int64_t nfaces, float* verts, int32_t* faces); /* after pb3d_iso_count on the same ctx */
+int pb3d_iso_last(pb3d_ctx* ctx, double pass_ms[4]);
+
 /* ---- project_colored_voxels, reference utils/projection_utils.py:5-23 ---------------------
  * R = look_at_rotation(cam, target) (host, reference utils/camera_geometry.py:3-14) is
  * passed in.  pts: (n,3) float32 (pts_f64 = 0) or float64 (1); cols (n,3) uint8.

@@ -17,6 +17,13 @@
 //
 // Passes: occupancy bitmask of the lattice (rows padded to 64 bits) -> per-block vertex / face counts ->
 // exclusive scans (points.hip's scan) -> vertices + per-cube vertex base -> faces -> colours.
+//
+// The isosurface of a float32 volume (pb3d_iso_*, reference utils/eval_helpers.py:191-195; include/pb3d.h states the rule) runs on
+// the same table, ownership and order: the triangles of a cube depend only on which corners are above the level, so only the bits
+// pass (k_iso_bits) and the vertex pass (k_iso_verts: interpolated edge vertices, no normals) are its own; counts, scans and faces
+// are the kernels above, launched on the LatticeParams half of either parameter block.
+#include <cmath>
+
 #include "pb3d_internal.h"
 #include "wave.h"
 
@@ -24,21 +31,33 @@ namespace {
 
 #include "mc_binary_table.inc"
 
-struct MeshParams {
-    const u8* grid;
-    i64 A1, A2;          // full-resolution dims (axis 1, 2)
+// the bit lattice: all the topology passes (counts, vertex base, faces) read
+struct LatticeParams {
     i64 n0, n1, n2;      // lattice dims
     i64 m1, m2;          // cubes per axis 1, 2 (n - 1)
     i64 ncubes;
     i64 W;               // 64-bit words per lattice row
+};
+
+// ... and the uint8 grid it was taken from (meshify's bits, vertex and colour passes)
+struct MeshParams : LatticeParams {
+    const u8* grid;
+    i64 A1, A2;          // full-resolution dims (axis 1, 2)
     int C, stride;
     float S2;            // full-resolution shape[2]
+};
+
+// ... or the float32 volume (the isosurface's bits and vertex passes)
+struct IsoParams : LatticeParams {
+    const float* vol;    // C-contiguous (n0, n1, n2)
+    double level;
+    float divisor;
 };
 
 __device__ __forceinline__ int lat_bit_row(const u64* __restrict__ row, i64 k) { return (int)((row[k >> 6] >> (k & 63)) & 1ull); }
 
 // case bit a0*4 + a1*2 + a2 = corner (c0+a0, c1+a1, c2+a2) occupied
-__device__ __forceinline__ int cube_case(const u64* __restrict__ bits, const MeshParams& p, i64 c0, i64 c1, i64 c2) {
+__device__ __forceinline__ int cube_case(const u64* __restrict__ bits, const LatticeParams& p, i64 c0, i64 c1, i64 c2) {
     int c = 0;
 #pragma unroll
     for (int a0 = 0; a0 < 2; ++a0)
@@ -134,7 +153,7 @@ __device__ __forceinline__ int refcount(int cs, int id) {
     return n;
 }
 
-__device__ __forceinline__ void cube_coords(const MeshParams& p, i64 t, i64* c0, i64* c1, i64* c2) {
+__device__ __forceinline__ void cube_coords(const LatticeParams& p, i64 t, i64* c0, i64* c1, i64* c2) {
     *c2 = t % p.m2;
     const i64 r = t / p.m2;
     *c1 = r % p.m1;
@@ -158,8 +177,37 @@ __global__ __launch_bounds__(256) void k_mesh_bits(MeshParams p, u64* __restrict
     if ((threadIdx.x & 63) == 0 && row < p.n0 * p.n1) bits[row * p.W + (k >> 6)] = m;
 }
 
+// inside bitmask of a float32 volume: one wave per lattice row, one lattice point per lane and 64-bit word; bit k of row (i, j) =
+// (double)vol[i, j, k] > level.  Rows are padded as k_mesh_bits pads them.  The only full read of the volume
+__global__ __launch_bounds__(256) void k_iso_bits(IsoParams p, u64* __restrict__ bits) {
+    const int lane = threadIdx.x & 63;
+    const i64 rows = p.n0 * p.n1;
+    // a capped grid whose waves stride over the rows
+    for (i64 row = (i64)blockIdx.x * 4 + (threadIdx.x >> 6); row < rows; row += (i64)gridDim.x * 4) {
+        const float* __restrict__ v = p.vol + row * p.n2;
+        u64* __restrict__ out = bits + row * p.W;
+        // eight words per round, so that their loads are in flight together
+        for (i64 w0 = 0; w0 < p.W; w0 += 8) {
+            bool in[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                // k >= n2 in the row's padding and in the words past the row's last: those lanes load the row's last value, so that no
+                // load sits behind a branch and all eight are issued before the first is waited for
+                const i64 k = (w0 + u) * 64 + lane;
+                const float x = v[k < p.n2 ? k : p.n2 - 1];
+                in[u] = k < p.n2 && (double)x > p.level;
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const u64 m = __ballot(in[u]);
+                if (lane == 0 && w0 + u < p.W) out[w0 + u] = m;
+            }
+        }
+    }
+}
+
 // per block of 256 cubes: owned vertices and triangles
-__global__ __launch_bounds__(256) void k_mesh_count(MeshParams p, const u64* __restrict__ bits, u32* __restrict__ vcount,
+__global__ __launch_bounds__(256) void k_mesh_count(LatticeParams p, const u64* __restrict__ bits, u32* __restrict__ vcount,
                                                     u32* __restrict__ fcount) {
     __shared__ u32 wsum[4];
     const i64 t = (i64)blockIdx.x * 256 + threadIdx.x;
@@ -251,8 +299,64 @@ __global__ __launch_bounds__(256) void k_mesh_verts(MeshParams p, const u64* __r
     }
 }
 
+// the isosurface's owned vertices and each cube's first vertex index: k_mesh_verts' ownership walk.  An edge vertex between lattice
+// points a (the lower index on the edge's axis) and b sits at ia + t on that axis, t = (level - va) / (vb - va) in float64 (three
+// operations, each rounded once; this file is built without contraction), rounded to float32 once; the centre vertex stays at the
+// cube centre.  Every coordinate is then divided by the divisor in float32, correctly rounded (include/pb3d.h states the rule)
+__global__ __launch_bounds__(256) void k_iso_verts(IsoParams p, const u64* __restrict__ bits, const i64* __restrict__ voff,
+                                                   int* __restrict__ vbase, float* __restrict__ verts) {
+    __shared__ u32 wsum[4];
+    const i64 t = (i64)blockIdx.x * 256 + threadIdx.x;
+    i64 c0 = 0, c1 = 0, c2 = 0;
+    int cs = 0, zb = 0;
+    u32 nv = 0;
+    if (t < p.ncubes) {
+        cube_coords(p, t, &c0, &c1, &c2);
+        cs = cube_case(bits, p, c0, c1, c2);
+        zb = zbits_of(c0, c1, c2);
+        if (MC_NTRI[cs]) nv = owned_count(cs, zb);
+    }
+    u32 tot;
+    const u32 before = group_excl_scan<256>(nv, wsum, &tot);
+    if (!nv) return;        // the cubes past the last one too
+    // k_mesh_faces uses the base of a cube only for a vertex that cube owns (its own, or the owner's of a shared edge): the cubes that own
+    // nothing, nearly all of a density volume, write none
+    const i64 base = voff[blockIdx.x] + before;
+    vbase[t] = (int)base;
+    i64 vi = base;
+    for (int k = 0; k < 13; ++k) {
+        const int id = MC_ORDER[cs][k];
+        if (id == 15) break;
+        if (!owns(id, zb)) continue;
+        float x0, x1, x2;   // (a0, a1, a2) in lattice units
+        if (id == 12) {
+            x0 = (float)c0 + 0.5f; x1 = (float)c1 + 0.5f; x2 = (float)c2 + 0.5f;
+        } else {
+            const int ax = id >> 2, p1 = (id >> 1) & 1, q1 = id & 1;
+            // the edge's low end; its high end is one step further on axis ax
+            const i64 a0 = ax == 0 ? c0 : c0 + p1;
+            const i64 a1 = ax == 1 ? c1 : c1 + (ax == 0 ? p1 : q1);
+            const i64 a2 = ax == 2 ? c2 : c2 + q1;
+            const i64 ia = (a0 * p.n1 + a1) * p.n2 + a2;
+            const i64 step = ax == 0 ? p.n1 * p.n2 : ax == 1 ? p.n2 : 1;
+            const double va = (double)p.vol[ia], vb = (double)p.vol[ia + step];
+            const double num = p.level - va, den = vb - va;
+            const double tt = num / den;
+            const float along = (float)((double)(ax == 0 ? a0 : ax == 1 ? a1 : a2) + tt);
+            x0 = ax == 0 ? along : (float)a0;
+            x1 = ax == 1 ? along : (float)a1;
+            x2 = ax == 2 ? along : (float)a2;
+        }
+        float* v = verts + 3 * vi;
+        v[0] = __fdiv_rn(x0, p.divisor);
+        v[1] = __fdiv_rn(x1, p.divisor);
+        v[2] = __fdiv_rn(x2, p.divisor);
+        ++vi;
+    }
+}
+
 // triangles: a reference to a vertex of an earlier cube resolves to that cube's vertex base + the vertex's rank there
-__global__ __launch_bounds__(256) void k_mesh_faces(MeshParams p, const u64* __restrict__ bits, const i64* __restrict__ foff,
+__global__ __launch_bounds__(256) void k_mesh_faces(LatticeParams p, const u64* __restrict__ bits, const i64* __restrict__ foff,
                                                     const int* __restrict__ vbase, int* __restrict__ faces) {
     __shared__ u32 wsum[4];
     const i64 t = (i64)blockIdx.x * 256 + threadIdx.x;
@@ -379,6 +483,13 @@ __global__ __launch_bounds__(256) void k_mesh_colors(MeshParams p, const u64* __
     for (int ch = 0; ch < p.C; ++ch) cols[v * p.C + ch] = g[ch];
 }
 
+// cubes and words of a lattice whose n0, n1, n2 are set
+void finish_lattice(LatticeParams* p) {
+    p->m1 = p->n1 - 1; p->m2 = p->n2 - 1;
+    p->ncubes = (p->n0 - 1) * p->m1 * p->m2;
+    p->W = (p->n2 + 63) / 64;
+}
+
 int make_mesh_params(const u8* d_grid, i64 A0, i64 A1, i64 A2, int C, int stride, MeshParams* p) {
     PB3D_REQUIRE(A0 >= 0 && A1 >= 0 && A2 >= 0 && (C == 1 || C == 3), "pb3d_mesh: bad shape");
     PB3D_REQUIRE(stride >= 1, "pb3d_mesh: stride must be >= 1");
@@ -389,13 +500,54 @@ int make_mesh_params(const u8* d_grid, i64 A0, i64 A1, i64 A2, int C, int stride
     p->n2 = (A2 + stride - 1) / stride;
     PB3D_REQUIRE(p->n0 >= 2 && p->n1 >= 2 && p->n2 >= 2, "pb3d_mesh: Input array must be at least 2x2x2.");
     PB3D_REQUIRE(A2 < (1 << 24), "pb3d_mesh: shape[2] must be < 2^24");
-    p->m1 = p->n1 - 1; p->m2 = p->n2 - 1;
-    p->ncubes = (p->n0 - 1) * p->m1 * p->m2;
-    p->W = (p->n2 + 63) / 64;
+    finish_lattice(p);
     p->S2 = (float)A2;
     PB3D_REQUIRE(d_grid != nullptr, "pb3d_mesh: null grid");
     return PB3D_OK;
 }
+
+int make_iso_params(const float* d_vol, i64 n0, i64 n1, i64 n2, double level, float divisor, IsoParams* p) {
+    PB3D_REQUIRE(n0 >= 2 && n1 >= 2 && n2 >= 2, "pb3d_iso: Input array must be at least 2x2x2.");
+    PB3D_REQUIRE(n0 < (1 << 24) && n1 < (1 << 24) && n2 < (1 << 24), "pb3d_iso: every axis must be < 2^24");
+    PB3D_REQUIRE(std::isfinite(level), "pb3d_iso: level must be finite");
+    PB3D_REQUIRE(std::isfinite(divisor) && divisor > 0.0f, "pb3d_iso: divisor must be finite and > 0 (got %g)", (double)divisor);
+    PB3D_REQUIRE(d_vol != nullptr, "pb3d_iso: null volume");
+    p->n0 = n0; p->n1 = n1; p->n2 = n2;
+    finish_lattice(p);
+    p->vol = d_vol; p->level = level; p->divisor = divisor;
+    return PB3D_OK;
+}
+
+pb3d_ctx::IsoArgs iso_args(const void* vol, i64 n0, i64 n1, i64 n2, double level, float divisor, i64 nv, i64 nf) {
+    u64 lb;
+    u32 db;
+    memcpy(&lb, &level, sizeof lb);
+    memcpy(&db, &divisor, sizeof db);
+    return pb3d_ctx::IsoArgs{vol, n0, n1, n2, nv, nf, lb, db};
+}
+
+// the passes' time stamps of an isosurface count or fill (knob "iso_timing"): three events, created per call; read() wants the
+// stream waited for
+struct IsoStamps {
+    bool on;
+    int k;
+    hipEvent_t ev[3];
+    int mark(pb3d_ctx* ctx) {
+        if (!on) return PB3D_OK;
+        PB3D_HIP(hipEventCreate(&ev[k]));
+        PB3D_HIP(hipEventRecord(ev[k], ctx->stream));
+        ++k;
+        return PB3D_OK;
+    }
+    int read(float ms[2], bool* timed) {
+        *timed = false;
+        if (!on || k != 3) return PB3D_OK;
+        for (int i = 0; i < 2; ++i) PB3D_HIP(hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
+        *timed = true;
+        return PB3D_OK;
+    }
+    ~IsoStamps() { for (int i = 0; i < k; ++i) (void)hipEventDestroy(ev[i]); }
+};
 
 // bitmask of the lattice into PB3D_SLOT_MESH_BITS
 int build_bits(pb3d_ctx* ctx, const MeshParams& p, u64** bits) {
@@ -406,6 +558,48 @@ int build_bits(pb3d_ctx* ctx, const MeshParams& p, u64** bits) {
     hipLaunchKernelGGL(k_mesh_bits, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream, p, (u64*)b);
     PB3D_CHECK_LAUNCH();
     *bits = (u64*)b;
+    return PB3D_OK;
+}
+
+// The topology of a bit lattice, shared by meshify and the isosurface: per-block vertex and face counts, their two scans into
+// PB3D_SLOT_MESH_VERT_OFFSETS / _FACE_OFFSETS, and the two totals after the call's one host wait
+int count_lattice(pb3d_ctx* ctx, const LatticeParams& p, const u64* bits, const char* who, i64 tot[2], IsoStamps* stamps = nullptr) {
+    const i64 nb = (p.ncubes + 255) / 256;
+    void *vc, *fc, *vo, *fo;
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESH_VERT_COUNTS, (size_t)nb * sizeof(u32), &vc));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESH_FACE_COUNTS, (size_t)nb * sizeof(u32), &fc));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESH_VERT_OFFSETS, (size_t)(nb + 1) * sizeof(i64), &vo));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESH_FACE_OFFSETS, (size_t)(nb + 1) * sizeof(i64), &fo));
+    hipLaunchKernelGGL(k_mesh_count, dim3((unsigned)nb), dim3(256), 0, ctx->stream, p, bits, (u32*)vc, (u32*)fc);
+    PB3D_CHECK_LAUNCH();
+    PB3D_TRY(pb3d_scan_counts(ctx, (const u32*)vc, nb, (i64*)vo, PB3D_SLOT_MESH_VSCAN_LOCAL, PB3D_SLOT_MESH_VSCAN_SEGS));
+    PB3D_TRY(pb3d_scan_counts(ctx, (const u32*)fc, nb, (i64*)fo, PB3D_SLOT_MESH_FSCAN_LOCAL, PB3D_SLOT_MESH_FSCAN_SEGS));
+    if (stamps) PB3D_TRY(stamps->mark(ctx));
+    PB3D_HIP(hipMemcpyAsync(&tot[0], (i64*)vo + nb, sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
+    PB3D_HIP(hipMemcpyAsync(&tot[1], (i64*)fo + nb, sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
+    PB3D_TRY(pb3d_stream_sync(ctx));
+    PB3D_REQUIRE(tot[0] < (1ll << 31) && tot[1] < (1ll << 31), "%s: %lld vertices / %lld faces: int32 faces need < 2^31", who,
+                 (long long)tot[0], (long long)tot[1]);
+    return PB3D_OK;
+}
+
+// what a fill reads of its count: the bit lattice and the two offset arrays, still at least as large as this lattice needs
+int counted_lattice(const pb3d_ctx* ctx, const LatticeParams& p, const char* fill, const char* count, const u64** bits) {
+    const i64 nb = (p.ncubes + 255) / 256;
+    const size_t bits_bytes = (size_t)(p.n0 * p.n1 * p.W) * sizeof(u64);
+    PB3D_REQUIRE(ctx->scratch[PB3D_SLOT_MESH_BITS] && ctx->scratch_bytes[PB3D_SLOT_MESH_BITS] >= bits_bytes &&
+                     ctx->scratch[PB3D_SLOT_MESH_VERT_OFFSETS] && ctx->scratch_bytes[PB3D_SLOT_MESH_VERT_OFFSETS] >= (size_t)(nb + 1) * sizeof(i64) &&
+                     ctx->scratch[PB3D_SLOT_MESH_FACE_OFFSETS] && ctx->scratch_bytes[PB3D_SLOT_MESH_FACE_OFFSETS] >= (size_t)(nb + 1) * sizeof(i64),
+                 "%s: call %s on the same grid first", fill, count);
+    *bits = (const u64*)ctx->scratch[PB3D_SLOT_MESH_BITS];
+    return PB3D_OK;
+}
+
+// the faces of a counted lattice whose vertex pass has written the per-cube vertex base
+int fill_faces(pb3d_ctx* ctx, const LatticeParams& p, const u64* bits, const int* vbase, int32_t* d_faces) {
+    hipLaunchKernelGGL(k_mesh_faces, dim3((unsigned)((p.ncubes + 255) / 256)), dim3(256), 0, ctx->stream, p, bits,
+                       (const i64*)ctx->scratch[PB3D_SLOT_MESH_FACE_OFFSETS], vbase, (int*)d_faces);
+    PB3D_CHECK_LAUNCH();
     return PB3D_OK;
 }
 
@@ -424,21 +618,8 @@ int pb3d_mesh_count_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64_
     PB3D_REQUIRE(nb < (1ll << 31) && (p.n0 * p.n1 * p.W * 64 + 255) / 256 < (1ll << 31), "pb3d_mesh_count: grid too large");
     u64* bits;
     PB3D_TRY(build_bits(ctx, p, &bits));
-    void *vc, *fc, *vo, *fo;
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESH_VERT_COUNTS, (size_t)nb * sizeof(u32), &vc));
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESH_FACE_COUNTS, (size_t)nb * sizeof(u32), &fc));
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESH_VERT_OFFSETS, (size_t)(nb + 1) * sizeof(i64), &vo));
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESH_FACE_OFFSETS, (size_t)(nb + 1) * sizeof(i64), &fo));
-    hipLaunchKernelGGL(k_mesh_count, dim3((unsigned)nb), dim3(256), 0, ctx->stream, p, (const u64*)bits, (u32*)vc, (u32*)fc);
-    PB3D_CHECK_LAUNCH();
-    PB3D_TRY(pb3d_scan_counts(ctx, (const u32*)vc, nb, (i64*)vo, PB3D_SLOT_MESH_VSCAN_LOCAL, PB3D_SLOT_MESH_VSCAN_SEGS));
-    PB3D_TRY(pb3d_scan_counts(ctx, (const u32*)fc, nb, (i64*)fo, PB3D_SLOT_MESH_FSCAN_LOCAL, PB3D_SLOT_MESH_FSCAN_SEGS));
     i64 tot[2];
-    PB3D_HIP(hipMemcpyAsync(&tot[0], (i64*)vo + nb, sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
-    PB3D_HIP(hipMemcpyAsync(&tot[1], (i64*)fo + nb, sizeof(i64), hipMemcpyDeviceToHost, ctx->stream));
-    PB3D_TRY(pb3d_stream_sync(ctx));
-    PB3D_REQUIRE(tot[0] < (1ll << 31) && tot[1] < (1ll << 31), "pb3d_mesh_count: %lld vertices / %lld faces: int32 faces need < 2^31",
-                 (long long)tot[0], (long long)tot[1]);
+    PB3D_TRY(count_lattice(ctx, p, bits, "pb3d_mesh_count", tot));
     *nverts = tot[0];
     *nfaces = tot[1];
     ctx->mesh_dev.a = pb3d_ctx::MeshArgs{d_grid, A0, A1, A2, tot[0], tot[1], C, stride};
@@ -473,20 +654,14 @@ int pb3d_mesh_fill_dev(pb3d_ctx* ctx, const uint8_t* d_grid, int64_t A0, int64_t
                              pb3d_same_args(ctx->mesh_dev.a, pb3d_ctx::MeshArgs{d_grid, A0, A1, A2, nverts, nfaces, C, stride}),
                              "pb3d_mesh_fill", "pb3d_mesh_count"));
     const i64 nb = (p.ncubes + 255) / 256;
-    const size_t bits_bytes = (size_t)(p.n0 * p.n1 * p.W) * sizeof(u64);
-    PB3D_REQUIRE(ctx->scratch[PB3D_SLOT_MESH_BITS] && ctx->scratch_bytes[PB3D_SLOT_MESH_BITS] >= bits_bytes &&
-                     ctx->scratch[PB3D_SLOT_MESH_VERT_OFFSETS] && ctx->scratch_bytes[PB3D_SLOT_MESH_VERT_OFFSETS] >= (size_t)(nb + 1) * sizeof(i64) &&
-                     ctx->scratch[PB3D_SLOT_MESH_FACE_OFFSETS] && ctx->scratch_bytes[PB3D_SLOT_MESH_FACE_OFFSETS] >= (size_t)(nb + 1) * sizeof(i64),
-                 "pb3d_mesh_fill: call pb3d_mesh_count_dev on the same grid first");
-    const u64* bits = (const u64*)ctx->scratch[PB3D_SLOT_MESH_BITS];
+    const u64* bits;
+    PB3D_TRY(counted_lattice(ctx, p, "pb3d_mesh_fill", "pb3d_mesh_count_dev", &bits));
     void* vb;
     PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESH_VERT_BASE, (size_t)p.ncubes * sizeof(int), &vb));
     hipLaunchKernelGGL(k_mesh_verts, dim3((unsigned)nb), dim3(256), 0, ctx->stream, p, bits, (const i64*)ctx->scratch[PB3D_SLOT_MESH_VERT_OFFSETS],
                        (int*)vb, d_verts, d_normals);
     PB3D_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_mesh_faces, dim3((unsigned)nb), dim3(256), 0, ctx->stream, p, bits, (const i64*)ctx->scratch[PB3D_SLOT_MESH_FACE_OFFSETS],
-                       (const int*)vb, (int*)d_faces);
-    PB3D_CHECK_LAUNCH();
+    PB3D_TRY(fill_faces(ctx, p, bits, (const int*)vb, d_faces));
     (void)nfaces;
     if (d_cols) {
         hipLaunchKernelGGL(k_mesh_colors, dim3((unsigned)((nverts + 255) / 256)), dim3(256), 0, ctx->stream, p, bits,
@@ -537,6 +712,115 @@ int pb3d_mesh_fill(pb3d_ctx* ctx, int64_t nverts, int64_t nfaces, float* verts, 
     PB3D_HIP(hipMemcpyAsync(faces, df, (size_t)nfaces * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     PB3D_HIP(hipMemcpyAsync(normals, dn, (size_t)nverts * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     if (cols) PB3D_HIP(hipMemcpyAsync(cols, dc, (size_t)nverts * C, hipMemcpyDeviceToHost, ctx->stream));
+    return pb3d_stream_sync(ctx);
+}
+
+}  // extern "C"
+
+// ---- isosurface of a float32 volume (include/pb3d.h states the rule): the bits and vertex passes of its own, meshify's topology ----
+extern "C" {
+
+int pb3d_iso_count_resident(pb3d_ctx* ctx, const float* d_vol, int64_t n0, int64_t n1, int64_t n2, double level, float divisor,
+                       int64_t* nverts, int64_t* nfaces) {
+    PB3D_REQUIRE(nverts != nullptr && nfaces != nullptr, "pb3d_iso_count: null argument");
+    *nverts = *nfaces = 0;
+    IsoParams p;
+    PB3D_TRY(make_iso_params(d_vol, n0, n1, n2, level, divisor, &p));
+    PB3D_REQUIRE(ctx != nullptr, "pb3d_iso_count: null context");
+    ctx->iso_dev.pair.valid = false;
+    ctx->iso_last.count_timed = ctx->iso_last.fill_timed = false;
+    const i64 nb = (p.ncubes + 255) / 256, rows = p.n0 * p.n1;
+    PB3D_REQUIRE(nb < (1ll << 31), "pb3d_iso_count: volume too large");
+    void* b;
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESH_BITS, (size_t)(rows * p.W) * sizeof(u64), &b));
+    IsoStamps st = {ctx->tune_iso_timing != 0, 0, {}};
+    PB3D_TRY(st.mark(ctx));
+    hipLaunchKernelGGL(k_iso_bits, dim3(pb3d_stream_blocks(ctx, rows, 4, 16)), dim3(256), 0, ctx->stream, p, (u64*)b);
+    PB3D_CHECK_LAUNCH();
+    PB3D_TRY(st.mark(ctx));
+    i64 tot[2];
+    PB3D_TRY(count_lattice(ctx, p, (const u64*)b, "pb3d_iso_count", tot, &st));
+    PB3D_TRY(st.read(&ctx->iso_last.ms[0], &ctx->iso_last.count_timed));
+    *nverts = tot[0];
+    *nfaces = tot[1];
+    ctx->iso_dev.a = iso_args(d_vol, n0, n1, n2, level, divisor, tot[0], tot[1]);
+    pb3d_pair_record(ctx, &ctx->iso_dev.pair, {PB3D_SLOT_MESH_BITS, PB3D_SLOT_MESH_VERT_OFFSETS, PB3D_SLOT_MESH_FACE_OFFSETS});
+    return PB3D_OK;
+}
+
+int pb3d_iso_fill_resident(pb3d_ctx* ctx, const float* d_vol, int64_t n0, int64_t n1, int64_t n2, double level, float divisor,
+                      int64_t nverts, int64_t nfaces, float* d_verts, int32_t* d_faces) {
+    IsoParams p;
+    PB3D_TRY(make_iso_params(d_vol, n0, n1, n2, level, divisor, &p));
+    PB3D_REQUIRE(nverts >= 0 && nfaces >= 0, "pb3d_iso_fill: negative size");
+    PB3D_REQUIRE(ctx != nullptr, "pb3d_iso_fill: null context");
+    PB3D_TRY(pb3d_pair_check(ctx, ctx->iso_dev.pair, pb3d_same_args(ctx->iso_dev.a, iso_args(d_vol, n0, n1, n2, level, divisor, nverts, nfaces)),
+                             "pb3d_iso_fill", "pb3d_iso_count"));
+    if (nverts == 0) return PB3D_OK;      // a counted mesh without vertices has no faces
+    PB3D_REQUIRE(d_verts && d_faces, "pb3d_iso_fill: null buffer");
+    const i64 nb = (p.ncubes + 255) / 256;
+    const u64* bits;
+    PB3D_TRY(counted_lattice(ctx, p, "pb3d_iso_fill", "pb3d_iso_count_resident", &bits));
+    void* vb;
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESH_VERT_BASE, (size_t)p.ncubes * sizeof(int), &vb));
+    IsoStamps st = {ctx->tune_iso_timing != 0, 0, {}};
+    PB3D_TRY(st.mark(ctx));
+    hipLaunchKernelGGL(k_iso_verts, dim3((unsigned)nb), dim3(256), 0, ctx->stream, p, bits, (const i64*)ctx->scratch[PB3D_SLOT_MESH_VERT_OFFSETS],
+                       (int*)vb, d_verts);
+    PB3D_CHECK_LAUNCH();
+    PB3D_TRY(st.mark(ctx));
+    PB3D_TRY(fill_faces(ctx, p, bits, (const int*)vb, d_faces));
+    PB3D_TRY(st.mark(ctx));
+    if (st.on) PB3D_TRY(pb3d_stream_sync(ctx));
+    return st.read(&ctx->iso_last.ms[2], &ctx->iso_last.fill_timed);
+}
+
+int pb3d_iso_last(pb3d_ctx* ctx, double pass_ms[4]) {
+    PB3D_REQUIRE(ctx != nullptr && pass_ms != nullptr, "pb3d_iso_last: null argument");
+    PB3D_REQUIRE(ctx->iso_last.count_timed && ctx->iso_last.fill_timed,
+                 "pb3d_iso_last: the last isosurface count and fill were not both timed (knob iso_timing)");
+    for (int i = 0; i < 4; ++i) pass_ms[i] = ctx->iso_last.ms[i];
+    return PB3D_OK;
+}
+
+int pb3d_iso_count(pb3d_ctx* ctx, const float* vol, int64_t n0, int64_t n1, int64_t n2, double level, float divisor, int64_t* nverts,
+                   int64_t* nfaces) {
+    PB3D_REQUIRE(nverts != nullptr && nfaces != nullptr, "pb3d_iso_count: null argument");
+    *nverts = *nfaces = 0;
+    IsoParams p;
+    PB3D_TRY(make_iso_params(vol, n0, n1, n2, level, divisor, &p));
+    PB3D_REQUIRE(ctx != nullptr, "pb3d_iso_count: null context");
+    ctx->iso.pair.valid = false;
+    const size_t bytes = (size_t)(n0 * n1 * n2) * sizeof(float);
+    void* dv = nullptr;
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_HOST_IN0, bytes, &dv));
+    PB3D_HIP(hipMemcpyAsync(dv, vol, bytes, hipMemcpyHostToDevice, ctx->stream));
+    PB3D_TRY(pb3d_iso_count_resident(ctx, (const float*)dv, n0, n1, n2, level, divisor, nverts, nfaces));
+    ctx->iso.a = iso_args(dv, n0, n1, n2, level, divisor, *nverts, *nfaces);
+    pb3d_pair_record(ctx, &ctx->iso.pair, {PB3D_SLOT_HOST_IN0});
+    return PB3D_OK;
+}
+
+// the device fill checks the device pair that pb3d_iso_count ran
+int pb3d_iso_fill(pb3d_ctx* ctx, int64_t nverts, int64_t nfaces, float* verts, int32_t* faces) {
+    PB3D_REQUIRE(ctx != nullptr, "pb3d_iso_fill: null context");
+    const pb3d_ctx::IsoArgs& a = ctx->iso.a;
+    PB3D_TRY(pb3d_pair_check(ctx, ctx->iso.pair, true, "pb3d_iso_fill", "pb3d_iso_count"));
+    PB3D_REQUIRE(nverts == a.nv && nfaces == a.nf, "pb3d_iso_fill: sizes do not match the count");
+    ctx->iso.pair.valid = false;
+    if (nverts == 0) return PB3D_OK;
+    PB3D_REQUIRE(verts && faces, "pb3d_iso_fill: null buffer");
+    double level;
+    float divisor;
+    const u32 db = (u32)a.divisor_bits;
+    memcpy(&level, &a.level_bits, sizeof level);
+    memcpy(&divisor, &db, sizeof divisor);
+    void *dv, *df;
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_HOST_OUT0, (size_t)nverts * 3 * sizeof(float), &dv));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_HOST_OUT1, (size_t)nfaces * 3 * sizeof(int32_t), &df));
+    PB3D_TRY(pb3d_iso_fill_resident(ctx, (const float*)a.vol, a.n0, a.n1, a.n2, level, divisor, nverts, nfaces, (float*)dv, (int32_t*)df));
+    PB3D_HIP(hipMemcpyAsync(verts, dv, (size_t)nverts * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    PB3D_HIP(hipMemcpyAsync(faces, df, (size_t)nfaces * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     return pb3d_stream_sync(ctx);
 }
 

@@ -109,7 +109,8 @@ enum pb3d_slot : int {
     PB3D_SLOT_CCL_RECORDS = 40,
     // cache, csrc/ccl.hip: the membership bits of the last labelled volume (ccl_last)
     PB3D_SLOT_CCL_MEMBER_BITS = 42,
-    // pair state, csrc/mesh.hip: pb3d_mesh_count_dev -> pb3d_mesh_fill_dev (pb3d_mesh_colors_dev rebuilds MESH_BITS)
+    // pair state, csrc/mesh.hip: pb3d_mesh_count_dev -> pb3d_mesh_fill_dev (pb3d_mesh_colors_dev rebuilds MESH_BITS), and
+    // pb3d_iso_count_resident -> pb3d_iso_fill_resident on the same slots: a count of either requests them, which ends the other's pending pair
     PB3D_SLOT_MESH_BITS = 48,
     PB3D_SLOT_MESH_VERT_OFFSETS = 51,
     PB3D_SLOT_MESH_FACE_OFFSETS = 52,
@@ -343,6 +344,10 @@ struct pb3d_ctx {
     // the last pb3d_render_mesh_resident (csrc/render.hip) for pb3d_render_last: faces pruned, on the small path, on the large path and
     // tile jobs; with render_timing the milliseconds of its passes (faces depth + scan, tiles depth, faces face, tiles face, resolve)
     struct RenderLast { bool valid, timed; float ms[5]; i64 stats[4]; } render_last;
+    int tune_iso_timing;        // knob "iso_timing": 1 = pb3d_iso_count_resident / pb3d_iso_fill_resident time their passes with events (the fill waits once more)
+    // the last isosurface pair (csrc/mesh.hip) for pb3d_iso_last: with iso_timing the milliseconds of the bits pass, of the count and
+    // its two scans (both stamped by the count), of the vertex pass and of the faces (both stamped by the fill)
+    struct IsoLast { bool count_timed, fill_timed; float ms[4]; } iso_last;
     // Growable device scratch slots, named by enum pb3d_slot (no hipMalloc / hipFree per call once warm).
     void* scratch[PB3D_SLOT_COUNT];
     size_t scratch_bytes[PB3D_SLOT_COUNT];
@@ -360,6 +365,9 @@ struct pb3d_ctx {
     struct { pb3d_pair pair; PointsArgs a; } pts_dev, pts;
     struct MeshArgs { const void* grid; i64 A0, A1, A2, nv, nf, C, stride; };
     struct { pb3d_pair pair; MeshArgs a; } mesh_dev, mesh;
+    // level and divisor by their bits (float64, float32): a record compared byte for byte holds no floating-point member
+    struct IsoArgs { const void* vol; i64 n0, n1, n2, nv, nf; u64 level_bits, divisor_bits; };
+    struct { pb3d_pair pair; IsoArgs a; } iso_dev, iso;
     struct { pb3d_pair pair; int ox, oy, oz; i64 X, Y, Z, n; } deform;
     struct ValidCache { void* buf; u64 gen; i64 W, D; double p[8]; } valid_cache;   // validity bit table of the last 90-degree step (PB3D_SLOT_ROT_VALID_TABLE)
     // Tile programs of the bit-sliced chain (csrc/sliced.hip, PB3D_SLOT_S32_TILE_PROGRAMS): valid for these steps on this (W, D)

@@ -20,6 +20,7 @@ from .eval_helpers import (chamfer_distance, compute_f1_curve, compute_nn_distan
 from .eval_helpers import (compute_surface_metrics, compute_triangle_normals, compute_vertex_normals, knn,  # noqa: F401
                            surface_metrics_per_vertex)
 from .eval_helpers import density_grid_resident, pointcloud_to_voxel_grid  # noqa: F401
+from .eval_helpers import get_marching_cubes_mesh, isosurface, marching_cubes_mesh_resident  # noqa: F401
 from .eval_helpers import cloud_to_mesh_metrics, point_to_mesh_distances, sample_mesh_points  # noqa: F401
 from .preprocess_helpers import (best_fit_transform_from_sums, flip_y_axis, icp_align, icp_align_resident, normalize_preserve_aspect,  # noqa: F401
                                  transform_points, transform_points_resident)
@@ -72,7 +73,7 @@ _PATCH = {
                            "run_minaret_iou_evaluation", "run_part_minaret_binary_iou"],
     "eval_helpers": ["filter_mesh", "_downsample", "chamfer_distance", "fscore_with_threshold", "pca_shape_similarity", "voxel_iou",
                      "compute_nn_stats", "compute_nn_distances", "f1_curve_from_distances", "compute_f1_curve", "compute_triangle_normals",
-                     "compute_vertex_normals", "compute_surface_metrics", "pointcloud_to_voxel_grid"],
+                     "compute_vertex_normals", "compute_surface_metrics", "pointcloud_to_voxel_grid", "get_marching_cubes_mesh"],
 }
 
 

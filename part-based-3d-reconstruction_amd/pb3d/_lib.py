@@ -70,6 +70,11 @@ _SIGNATURES = {
     "pb3d_mesh_colors_dev": [vp, vp, i64, i64, i64, C.c_int, C.c_int, vp, i64, vp],
     "pb3d_mesh_count": [vp, u8p, i64, i64, i64, C.c_int, C.c_int, i64p, i64p],
     "pb3d_mesh_fill": [vp, i64, i64, vp, vp, vp, vp],
+    "pb3d_iso_count_resident": [vp, vp, i64, i64, i64, C.c_double, C.c_float, i64p, i64p],
+    "pb3d_iso_fill_resident": [vp, vp, i64, i64, i64, C.c_double, C.c_float, i64, i64, vp, vp],
+    "pb3d_iso_count": [vp, vp, i64, i64, i64, C.c_double, C.c_float, i64p, i64p],
+    "pb3d_iso_fill": [vp, i64, i64, vp, vp],
+    "pb3d_iso_last": [vp, dblp],
     "pb3d_project_dev": [vp, vp, C.c_int, vp, i64, dblp, dblp, C.c_double, C.c_double, C.c_double, intp, C.c_int, C.c_int, vp],
     "pb3d_project": [vp, vp, C.c_int, u8p, i64, dblp, dblp, C.c_double, C.c_double, C.c_double, intp, C.c_int, C.c_int, u8p],
     "pb3d_partwise_iou_dev": [vp, vp, vp, i64, u8p, C.c_int, i64p, i64p],

@@ -291,3 +291,42 @@ def meshify(d_grid, shape, stride=1, download=True):
             return tuple(sc.keep(b) for b in (dv, df, dn, dc)), (n, m)
         return (dv.download((n, 3), np.float32), df.download((m, 3), np.int32), mesh_colors(dc.download((n, ch))),
                 dn.download((n, 3), np.float32))
+
+
+def iso_check(shape, level, divisor):
+    """(shape, level, divisor) of an isosurface call, refused before any device work: three axes of at least 2, a finite level, a
+    finite divisor > 0 that float32 holds (the vertices are float32)"""
+    shape = tuple(int(v) for v in shape)
+    if len(shape) != 3:
+        raise ValueError(f"the volume must be (n0, n1, n2) (got shape {shape})")
+    if any(n < 2 for n in shape):
+        raise ValueError("Input array must be at least 2x2x2.")
+    with np.errstate(over="ignore"):
+        level, divisor = float(level), float(np.float32(divisor))
+    if not np.isfinite(level):
+        raise ValueError(f"level must be finite (got {level})")
+    if not (np.isfinite(divisor) and divisor > 0):
+        raise ValueError(f"divisor must be finite and > 0 in float32 (got {divisor})")
+    return shape, level, divisor
+
+
+def isosurface(d_volume, shape, level, divisor=1.0, download=True):
+    """The isosurface of a float32 volume already in HBM (a DeviceBuffer of shape = (n0, n1, n2) C-contiguous values, all finite) at
+    `level`, by the rule of include/pb3d.h: inside iff float64(v) > level, meshify's case table and order, edge vertices interpolated
+    in float64, every coordinate divided by float32(divisor).  One synchronisation for the counts; download=True returns (verts (n, 3)
+    float32 in (a0, a1, a2) order, faces (m, 3) int32), one download of each; download=False returns the two as DeviceBuffers -- the
+    layout meshify(download=False) uses for them; of one byte each when the surface is empty -- plus (n, m).  An empty surface (a
+    level outside the data range) is (0, 3) and (0, 3), not an error."""
+    shape, level, divisor = iso_check(shape, level, divisor)
+    lib, ctx = _lib.load(), _lib.ctx()
+    nv, nf = C.c_int64(0), C.c_int64(0)
+    _lib.check(lib.pb3d_iso_count_resident(ctx, _ptr(d_volume), *shape, level, divisor, C.byref(nv), C.byref(nf)))
+    n, m = nv.value, nf.value
+    with Scope() as sc:
+        dv, df = sc.alloc(max(1, n * 12)), sc.alloc(max(1, m * 12))
+        _lib.check(lib.pb3d_iso_fill_resident(ctx, _ptr(d_volume), *shape, level, divisor, n, m, _ptr(dv), _ptr(df)))
+        if not download:
+            return (sc.keep(dv), sc.keep(df)), (n, m)
+        if n == 0:
+            return np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32)
+        return dv.download((n, 3), np.float32), df.download((m, 3), np.int32)

@@ -29,13 +29,18 @@ the exact nearest point of the surface for every point of a cloud on the cell in
 draws stratified area-weighted samples that turn a mesh into a cloud for every metric above and for icp_align; include/pb3d.h states
 both to the bit.
 
-Not mirrored: get_marching_cubes_mesh (no scikit-image here to take float-level marching-cubes fixtures from)."""
+get_marching_cubes_mesh (:191-195) runs on the device too: the resident density volume, then the isosurface of csrc/mesh.hip
+(pb3d_iso_*), whose rule -- inside iff float64(v) > level, meshify's binary case table, ownership and order, edge vertices
+interpolated in float64, the centre vertex at the cube centre -- is the project's own and is stated to the bit in include/pb3d.h.
+There is no scikit-image here to compare float-level meshes with, and none is claimed equal: skimage's Lewiner variant decides
+ambiguous faces and interiors from the values, so vertex and face counts can differ on ambiguous cubes.  On a 0/1 volume at level
+0.5 the rule gives meshify_colored_voxel_grid's lattice mesh, which is skimage's, byte for byte."""
 import ctypes as C
 import operator
 
 import numpy as np
 
-from . import _lib, device as dev
+from . import _hostmem, _lib, device as dev
 from ._args import _cloud  # noqa: F401  (the cloud check; tests and tools take it from here)
 from ._lib import _ptr
 
@@ -45,7 +50,8 @@ __all__ = ["filter_mesh", "chamfer_distance", "fscore_with_threshold", "pca_shap
            "compute_vertex_normals", "compute_surface_metrics", "surface_metrics_per_vertex", "triangle_normals_resident",
            "vertex_normals_resident", "surface_metrics_resident", "KNN_MAX_K", "pointcloud_to_voxel_grid", "density_grid_resident",
            "point_to_mesh_distances", "point_to_mesh_distances_resident", "mesh_grid_shape", "sample_mesh_points",
-           "sample_mesh_points_resident", "cloud_to_mesh_metrics"]
+           "sample_mesh_points_resident", "cloud_to_mesh_metrics", "isosurface", "get_marching_cubes_mesh",
+           "marching_cubes_mesh_resident"]
 
 KNN_MAX_K = 32      # PB3D_KNN_MAX_K
 DENSITY_MAX_GRID = 1024     # the limits of pb3d_density_grid_resident
@@ -255,6 +261,61 @@ def pointcloud_to_voxel_grid(points, grid_size=128, sigma=1.0):
     with dev.Scope() as sc:
         d_out = sc.adopt(density_grid_resident(sc.upload(p), len(p), G, sigma, f64))
         return d_out.download((G, G, G), np.float32)
+
+
+# ---- isosurface of the density volume (:191-195; csrc/mesh.hip, include/pb3d.h states the rule) -----------------------------------------
+def isosurface(volume, level, divisor=1.0):
+    """(verts (n, 3) float32 in (a0, a1, a2) order, faces (m, 3) int32): the isosurface of a float32 (n0, n1, n2) volume at `level`
+    by the rule of include/pb3d.h -- a lattice point is inside iff float64(v) > level; cases, vertex ownership and order are
+    meshify_colored_voxel_grid's; an edge vertex sits at ia + (level - va) / (vb - va), in float64, rounded to float32 once; the
+    centre vertex of the cases that have one stays at the cube centre; every coordinate is divided by float32(divisor).  A 0/1 volume
+    at level 0.5 gives the lattice mesh of meshify_colored_voxel_grid byte for byte.  The mesh is closed and consistently oriented
+    wherever the volume's border is outside; zero-area faces (values equal to the level) are kept.  A level outside the data range
+    gives empty (0, 3) arrays.  Not skimage's Lewiner mesh on float input: on ambiguous cubes vertex and face counts can differ.
+    Other real dtypes are converted to float32; non-finite values are refused (ValueError)."""
+    v = np.asarray(volume)
+    if v.dtype.kind not in "fiub":
+        raise TypeError(f"isosurface takes a real-valued volume (got {v.dtype})")
+    v = np.ascontiguousarray(v, dtype=np.float32)
+    shape, level, divisor = dev.iso_check(v.shape, level, divisor)
+    _finite(v, "volume")
+    lib, ctx = _lib.load(), _lib.ctx()
+    nv, nf = C.c_int64(0), C.c_int64(0)
+    _lib.check(lib.pb3d_iso_count(ctx, v.ctypes.data_as(C.c_void_p), *shape, level, divisor, C.byref(nv), C.byref(nf)))
+    verts = _hostmem.empty((nv.value, 3), np.float32)
+    faces = _hostmem.empty((nf.value, 3), np.int32)
+    _lib.check(lib.pb3d_iso_fill(ctx, nv.value, nf.value, verts.ctypes.data_as(C.c_void_p), faces.ctypes.data_as(C.c_void_p)))
+    return verts, faces
+
+
+def marching_cubes_mesh_resident(d_pts, n, grid_size=128, sigma=1.0, level=0.1, f64=True):
+    """get_marching_cubes_mesh of a resident (n, 3) cloud, the mesh left on the device: ((DeviceBuffer of nv x 3 float32 vertices,
+    DeviceBuffer of nf x 3 int32 faces), (nv, nf)) as pb3d.device.isosurface(download=False) hands them out -- the density volume
+    (density_grid_resident) never leaves the device and is freed before the call returns."""
+    with dev.Scope() as sc:
+        d_vol = sc.adopt(density_grid_resident(d_pts, n, grid_size, sigma, f64))
+        G = operator.index(grid_size)
+        return dev.isosurface(d_vol, (G, G, G), level, divisor=G, download=False)
+
+
+def get_marching_cubes_mesh(points, grid_size=128, sigma=1.0, level=0.1):
+    """(verts, faces) of the reference (:191-195): pointcloud_to_voxel_grid's density volume (bit for bit the reference's), its
+    isosurface at `level` by the rule of isosurface() -- this project's own, not skimage's Lewiner mesh on float input -- and the
+    vertices divided by grid_size in float32, as the reference's verts /= grid_size does.  The cloud goes up once, the volume stays on
+    the device, the two arrays come down.  A level outside the volume's range gives empty (0, 3) arrays (skimage raises there)."""
+    p, f64 = _cloud(points)
+    G, _, _ = _density_args(grid_size, sigma)
+    if len(p) == 0:
+        raise ValueError("zero-size array to reduction operation minimum which has no identity")
+    _finite(p, "points")
+    if G < 2:
+        raise ValueError("Input array must be at least 2x2x2.")
+    with dev.Scope() as sc:
+        bufs, (nv, nf) = marching_cubes_mesh_resident(sc.upload(p), len(p), G, sigma, level, f64)
+        d_v, d_f = sc.adopt(bufs)
+        if nv == 0:
+            return np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32)
+        return d_v.download((nv, 3), np.float32), d_f.download((nf, 3), np.int32)
 
 
 # ---- regularity metrics (:118-130) -----------------------------------------------------------------------------------------------------

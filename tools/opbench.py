@@ -1,5 +1,5 @@
 """Device-resident timing of every op of the path (M1..M8 of SURVEY.md 8(d), plus the N1/N2 kernels of the notebook-1 chain) on
-synthetic inputs.  Development/measurement tool: python tools/opbench.py [--size 1024] [--shape WxHxD] [--ops M1,M3,...,N2,overlays,ICP,PLANE,MESHD,CLUSTER,DOWNSAMPLE,SMOOTH,VOXELIZE,EDT,RENDER]; one JSON
+synthetic inputs.  Development/measurement tool: python tools/opbench.py [--size 1024] [--shape WxHxD] [--ops M1,M3,...,N2,overlays,ICP,PLANE,MESHD,CLUSTER,DOWNSAMPLE,SMOOTH,VOXELIZE,EDT,RENDER,ISO]; one JSON
 line per op.  Pricing: `alg_B_per_voxel` is SURVEY 8(d)'s algorithmic figure for the sweeps that are EXECUTED (a folded 0-degree step
 moves nothing and is not priced); ops whose intermediates are not bytes (the bit-sliced chains) also carry `moved_B_per_voxel`, the
 bytes that cross the HBM by design, and their `frac_of_8TBs` is computed from THAT (never from bytes that are not moved)."""
@@ -272,6 +272,8 @@ def main():
         meshify(a.reps, res)
     if "DENS" in ops:
         density(a.reps, res, cpu_ref=not a.no_cpu_ref)
+    if "ISO" in ops:
+        isosurface(a.reps, res)
     if "MESHD" in ops:
         mesh_target(a.reps, res)
     if "overlays" in ops:
@@ -1380,6 +1382,86 @@ def density(reps, res, cpu_ref=True):
         res.append(r)
     for b in (d_g, d_tp, d_tc):
         b.free()
+
+
+def isosurface(reps, res):
+    """ISO, the isosurface of a resident density volume (pb3d_iso_*, csrc/mesh.hip) at level 0.1, divisor grid_size: (a) the default
+    case of get_marching_cubes_mesh, the 128^3 volume of the 20 k SfM sample; (b) the 512^3 volume of every point of the stored Taj
+    grid.  resident_ms: count with its one host wait + fill into new device buffers, by device events (mean of reps after two warm
+    calls).  passes_ms: under knob iso_timing the calls' own events -- bits pass, count and its two scans, vertex pass, faces (median
+    of reps; the fill then waits once more, so these runs are not the ones resident_ms times).  Two yardsticks that are not the code
+    under test, in the same run: device.meshify(download=False) on a uint8 (G, G, G, 1) grid holding the same sign mask (the same
+    topology passes on 1 B per voxel, plus normals and colours), and the plain sweep A2 (_occupancy: 3 B read + 1 B written per
+    element) over G^3 elements, the floor of a pass that reads 4 B per voxel once."""
+    from pb3d.eval_helpers import density_grid_resident
+    lib, L = pb3d._lib.load(), pb3d._lib
+    sfm = np.ascontiguousarray(np.load(os.path.join(ROOT, "tests", "golden", "inter_sfm20k.npz"))["sfm"])
+    taj = np.load(os.path.join(ROOT, "tests", "golden", "stored_Taj_voxel_grid.npz"))["voxel_grid"]
+    nvox = int(np.prod(taj.shape[:3]))
+    d_g = dev.from_numpy(taj)
+    d_tp, d_tc = dev.DeviceBuffer(nvox * 12), dev.DeviceBuffer(nvox * 3)
+    n = C.c_int64(0)
+    L.check(lib.pb3d_points_extract_dev(L.ctx(), C.c_void_p(d_g.ptr), *taj.shape[:3], 3, None, 0, nvox, C.c_void_p(d_tp.ptr),
+                                        C.c_void_p(d_tc.ptr), C.byref(n)))
+    d_g.free(); d_tc.free()
+    d_sfm = dev.from_numpy(sfm)
+    for name, d_p, npts, f64, G in (("20 k SfM sample", d_sfm, len(sfm), True, 128), ("every point of the stored Taj grid", d_tp, n.value, False, 512)):
+        d_vol = density_grid_resident(d_p, npts, G, 1.0, f64=f64)
+        shape = (G, G, G)
+        keep = []
+
+        def run():
+            keep.append(dev.isosurface(d_vol, shape, 0.1, G, download=False))
+
+        def drop():
+            for bufs, _ in keep:
+                for b in bufs:
+                    b.free()
+            del keep[:]
+        ms = timeit(run, reps)
+        nv, nf = keep[-1][1]
+        drop()
+        L.set_tuning("iso_timing", 1)
+        passes = []
+        try:
+            for _ in range(max(3, reps)):
+                run()
+                pm = (C.c_double * 4)()
+                L.check(lib.pb3d_iso_last(L.ctx(), pm))
+                passes.append(list(pm))
+                drop()
+        finally:
+            L.set_tuning("iso_timing", 0)
+        bits_ms, count_ms, verts_ms, faces_ms = (float(x) for x in np.median(np.array(passes), axis=0))
+        # yardstick 1: meshify on the same sign mask
+        mask = (d_vol.download(shape, np.float32).astype(np.float64) > 0.1).astype(np.uint8)[..., None] * np.uint8(255)
+        d_m = dev.from_numpy(mask)
+        mkeep = []
+
+        def mrun():
+            mkeep.append(dev.meshify(d_m, mask.shape, stride=1, download=False))
+        mesh_ms = timeit(mrun, reps)
+        mnv, mnf = mkeep[-1][1]
+        for bufs, _ in mkeep:
+            for b in bufs:
+                b.free()
+        d_m.free()
+        # yardstick 2: the plain sweep over G^3 elements of 4 B
+        d_c, d_o = dev.DeviceBuffer(G ** 3 * 3), dev.DeviceBuffer(G ** 3)
+        d_c.zero()
+        sweep_ms = timeit(lambda: dev.occupancy(d_c, G ** 3, d_o), 20)
+        d_c.free(); d_o.free()
+        r = {"op": "ISO", "name": f"isosurface of the density volume, {name}", "points": int(npts), "grid_size": G, "sigma": 1.0, "level": 0.1,
+             "nverts": int(nv), "nfaces": int(nf), "resident_ms": round(ms, 4),
+             "passes_ms": {"bits": round(bits_ms, 4), "count_and_scans": round(count_ms, 4), "verts": round(verts_ms, 4), "faces": round(faces_ms, 4)},
+             "bits_GB_s": round(4 * G ** 3 / bits_ms / 1e6, 1),
+             "yardstick_meshify_same_mask_resident_ms": round(mesh_ms, 4), "meshify_same_counts": bool((mnv, mnf) == (nv, nf)),
+             "yardstick_sweep_4B_per_voxel_ms": round(sweep_ms, 4), "sweep_GB_s": round(4 * G ** 3 / sweep_ms / 1e6, 1),
+             "ratio_iso_to_meshify": round(ms / mesh_ms, 3), "ratio_bits_to_sweep": round(bits_ms / sweep_ms, 3)}
+        print(json.dumps(r), flush=True)
+        res.append(r)
+        d_vol.free()
+    d_sfm.free(); d_tp.free()
 
 
 def overlays(reps, res):
