@@ -484,6 +484,70 @@ int pb3d_mesh_smooth_resident(pb3d_ctx* ctx, const void* d_verts, int verts_f64,
                               int iterations, double lambda, double mu /* NaN: Laplacian */, const uint8_t* d_fixed /* or NULL */,
                               int fix_boundary, void* d_out /* nv x 3 in the input dtype; may not alias d_verts */);
 
+/* ---- mesh simplification by vertex clustering, and the compaction of a mesh (csrc/simplify.hip) ------------------------------------------
+ * The one mesh -> mesh step that changes the faces (Rossignac & Borrel 1993; Open3D's simplify_vertex_clustering): the vertices of a
+ * voxel become one vertex, and the faces are mapped, thinned and renumbered.  There is no upstream text, so the rules below are the
+ * specification, and the result is a function of the input and its order alone, to the bit: two runs give the same bytes.
+ *   INPUT      verts: (nv, 3) rows of float32 (verts_f64 = 0) or float64 (1); faces: (nf, 3) rows of int32 (faces_i64 = 0) or int64 (1)
+ *              with entries in [-nv, nv); entries in [-nv, -1] wrap as NumPy's do.  Anything else is PB3D_EINDEX, checked on the device
+ *              before any kernel gathers through them (one host wait), with nothing written.  Limits: 0 <= nv, nf <= 2^31 - 1.
+ *              voxel_size, origin (or NULL) and reduce are voxel_downsample's; duplicate_faces is one of the two below.
+ *   CLUSTERS   ORIGIN, CELL, RANGE, VOXELS, INDEX, CENTROID and FIRST of the voxel_downsample section, applied to the whole vertex list:
+ *              vertices that no face names are included.  c[0 .. m) are those voxels in their numbering by first appearance, inv[i] the
+ *              cluster of vertex i, first[k] the first vertex of cluster k.  A RANGE failure is that section's PB3D_EINVAL.
+ *   MAP        face j becomes g_j = (inv[w0], inv[w1], inv[w2]) of its wrapped corners, in the caller's corner order.
+ *   COLLAPSED  face j is dropped iff two of its three clusters are equal.
+ *   REPEATED   (duplicate_faces = PB3D_FACES_DROP) g_j is rotated cyclically so that its smallest cluster comes first; the three are
+ *              distinct, so the rotation is unique.  Two surviving faces are repeats iff their rotated triples are equal: the same three
+ *              clusters in the opposite orientation are NOT a repeat.  Of each set of repeats the face with the smallest j stays.
+ *              With PB3D_FACES_KEEP this step is skipped.
+ *   ORDER      the faces that stay keep the caller's order; face_index[t] = the input position of output face t, strictly increasing.
+ *   VERTICES   a cluster stays iff a face that stays names it.  The clusters that stay keep their relative order (first appearance) and
+ *              are renumbered 0 .. m' - 1.  out_verts[k'] = the CENTROID or FIRST row of that cluster, taken over all its vertices,
+ *              named by a face or not, in the input dtype (float32 rounded once, as voxel_downsample does); index[k'] = first[k];
+ *              inverse[i] = the new number of vertex i's cluster, -1 when that cluster was dropped.
+ *   FACES OUT  the new numbers in the caller's corner order (not the rotated order), in the caller's index dtype.
+ *   ATTRIBUTES with d_colors ((nv, channels) uint8, channels 1 or 3): out_colors[k'] = colors[index[k']] byte for byte -- the colour or
+ *              label of a cluster is that of its first vertex; nothing is blended.
+ *   EMPTY      nf = 0, or every face collapsed: counts = (0, 0), inverse all -1; not an error.  nf = 0 skips CLUSTERS altogether (no
+ *              RANGE failure, no host wait).  nv = 0 with nf > 0 is PB3D_EINDEX.
+ * CLOSEDNESS.  With PB3D_FACES_KEEP: if every directed edge (a, b) of the input occurs as often as (b, a) -- a closed, consistently
+ * oriented mesh, as meshify and the isosurface produce away from the volume border -- then the same holds for the output (MAP sends
+ * a balanced multiset of directed edges to a balanced one, and a collapsed face removes either an edge and its reverse, or nothing
+ * but loops).  So the crossing parity that pb3d_voxelize_mesh_resident relies on survives.  With PB3D_FACES_DROP the property can be
+ * lost wherever a thin part folds onto itself: of two sheets that land on the same triple in the same orientation one is removed and
+ * its neighbours keep an edge without a partner.
+ * mesh_compact is MAP .. ATTRIBUTES with every vertex its own cluster (inv[i] = i, m = nv) and no arithmetic: vertices are copied byte
+ *   for byte.  It removes faces with a repeated corner, repeated faces (the same option) and the vertices no remaining face names.
+ * Neither is quadric-error simplification, neither moves a representative to a quadric optimum, and neither welds vertices by
+ * coordinate equality (two vertices are merged only by sharing a voxel).  Beyond the cluster membership that the voxel_downsample
+ * section documents, no equality with Open3D is claimed.
+ * Outputs: d_out_verts room for nv rows and d_out_faces room for nf rows, of which the first counts[0] and counts[1] are written;
+ *   d_out_colors (given iff d_colors is) nv x channels; d_index (nv int32, or NULL), d_face_index (nf int32, or NULL) likewise;
+ *   d_inverse (nv int32, or NULL) whole.  No output may alias an input.  Host waits: the index check, the two of the cluster pass
+ *   (mesh_simplify only) and one read-back of the two counts; everything else is enqueued.
+ * The face half keeps no state per cluster or per triple: the rotated triples go through three stable radix sorts of (key, position)
+ * pairs, last cluster first, and a face is a repeat iff it equals its predecessor in that order.  Scratch: 46 bytes per face with
+ * PB3D_FACES_DROP (clusters 12, pairs 16, flags 4, ranks 8, scan 4, run table 2), 28 with PB3D_FACES_KEEP; 12 bytes per cluster and,
+ * for mesh_simplify, 8 + one row per vertex on top of voxel_downsample's own.
+ * simplify_last: of the last of the two on this context, counts = (clusters m, vertices out, faces out) and, with pass_ms not NULL, the
+ *   milliseconds its passes took (clusters, map, sorts + repeats, scans, gathers) -- recorded only under the development knob
+ *   "simplify_timing" (pb3d_set_tuning; one more host wait), else PB3D_EINVAL.  No result depends on the knob. */
+#define PB3D_FACES_DROP 0
+#define PB3D_FACES_KEEP 1
+int pb3d_mesh_simplify_resident(pb3d_ctx* ctx, const void* d_verts, int verts_f64, int64_t nv, const void* d_faces, int faces_i64, int64_t nf,
+                                double voxel_size, const double origin[3] /* or NULL */, int reduce /* PB3D_DOWNSAMPLE_* */,
+                                int duplicate_faces, const uint8_t* d_colors /* nv x channels, or NULL */, int channels,
+                                void* d_out_verts /* nv rows */, void* d_out_faces /* nf rows */, uint8_t* d_out_colors /* or NULL */,
+                                int32_t* d_index /* nv, or NULL */, int32_t* d_inverse /* nv, or NULL */,
+                                int32_t* d_face_index /* nf, or NULL */, int64_t counts[2] /* vertices, faces written */);
+int pb3d_mesh_compact_resident(pb3d_ctx* ctx, const void* d_verts, int verts_f64, int64_t nv, const void* d_faces, int faces_i64, int64_t nf,
+                               int duplicate_faces, const uint8_t* d_colors /* nv x channels, or NULL */, int channels,
+                               void* d_out_verts /* nv rows */, void* d_out_faces /* nf rows */, uint8_t* d_out_colors /* or NULL */,
+                               int32_t* d_index /* nv, or NULL */, int32_t* d_inverse /* nv, or NULL */,
+                               int32_t* d_face_index /* nf, or NULL */, int64_t counts[2] /* vertices, faces written */);
+int pb3d_simplify_last(pb3d_ctx* ctx, int64_t counts[3], double pass_ms[5] /* or NULL */);
+
 /* ---- mesh -> grid: exact solid voxelization of a triangle mesh by crossing parity, and the overlap of two grids (csrc/voxelize.hip) ------
  * The one conversion the other sections lack: a mesh (a CAD model, a smoothed marching-cubes mesh) becomes an occupancy, label or RGB grid
  * that the carve, paint, points and labelling entries take as it is.  Solid voxelization by crossing parity (Schwarz & Seidel 2010) with a

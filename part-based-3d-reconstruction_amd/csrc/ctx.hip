@@ -143,6 +143,7 @@ const Knob kKnobs[] = {
     {"voxelize_timing", &pb3d_ctx::tune_voxelize_timing, 0, 1, "0 or 1 (time the two passes of a voxelization with events)"},
     {"render_timing", &pb3d_ctx::tune_render_timing, 0, 1, "0 or 1 (time the passes of a mesh rendering with events)"},
     {"iso_timing", &pb3d_ctx::tune_iso_timing, 0, 1, "0 or 1 (time the passes of an isosurface count and fill with events)"},
+    {"simplify_timing", &pb3d_ctx::tune_simplify_timing, 0, 1, "0 or 1 (time the passes of a mesh simplification with events)"},
     {"orient_tile", &pb3d_ctx::tune_orient_tile, 0, 1, "0 (128-pixel tiles where they apply) or 1 (never)"},
     {"global_composed", &pb3d_ctx::tune_global_composed, 0, 1, "0 (mask bits -> sliced chain -> colours) or 1 (ones -> process -> colour)"},
     {"per_job", &pb3d_ctx::tune_per_job, 0, 1, "0 (merged / fused forms) or 1 (job by job)"},

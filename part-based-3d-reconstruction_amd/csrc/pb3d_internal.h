@@ -250,8 +250,27 @@ enum pb3d_slot : int {
     PB3D_SLOT_RENDER_OFFSETS = 134,
     PB3D_SLOT_RENDER_SCAN_LOCAL = 135,
     PB3D_SLOT_RENDER_SCAN_SEGS = 136,
+    // call-local, csrc/simplify.hip, all of them.  What pb3d_voxel_downsample_resident leaves of the clusters (pb3d_mesh_simplify_resident
+    // only: nv rows in the vertex dtype, nv int32 first vertices, nv int32 cluster numbers); each face's three clusters in the caller's
+    // corner order (nf x 3 u32, read by every pass behind the map); the (key, position) pairs of the three stable sorts (key, val and
+    // their ping-pong twins, nf u32 each; PB3D_FACES_DROP only) and the sorts' run table; the "face stays" flags (nf u32) and the
+    // "cluster is named" flags (m u32), their ranks (nf + 1 and m + 1 int64) and the two slots of every pb3d_scan_counts of the call;
+    // the two totals the host reads back.  The cluster pass inside uses the DOWNSAMPLE_* slots, the index check in front SURF_FLAG
+    PB3D_SLOT_SIMPLIFY_CLUSTER_ROWS = 137,
+    PB3D_SLOT_SIMPLIFY_CLUSTER_FIRST = 138,
+    PB3D_SLOT_SIMPLIFY_CLUSTER_INVERSE = 139,
+    PB3D_SLOT_SIMPLIFY_CORNERS = 140,
+    PB3D_SLOT_SIMPLIFY_PAIRS = 141,
+    PB3D_SLOT_SIMPLIFY_SORT_HIST = 142,
+    PB3D_SLOT_SIMPLIFY_KEEP = 143,
+    PB3D_SLOT_SIMPLIFY_USED = 144,
+    PB3D_SLOT_SIMPLIFY_FACE_RANKS = 145,
+    PB3D_SLOT_SIMPLIFY_VERTEX_RANKS = 146,
+    PB3D_SLOT_SIMPLIFY_SCAN_LOCAL = 147,
+    PB3D_SLOT_SIMPLIFY_SCAN_SEGS = 148,
+    PB3D_SLOT_SIMPLIFY_COUNTS = 149,
 
-    PB3D_SLOT_COUNT = 137
+    PB3D_SLOT_COUNT = 150
 };
 
 // ---- the cell index of the exact nearest-neighbour search (csrc/nn.hip) -----------------------------------
@@ -348,6 +367,10 @@ struct pb3d_ctx {
     // the last isosurface pair (csrc/mesh.hip) for pb3d_iso_last: with iso_timing the milliseconds of the bits pass, of the count and
     // its two scans (both stamped by the count), of the vertex pass and of the faces (both stamped by the fill)
     struct IsoLast { bool count_timed, fill_timed; float ms[4]; } iso_last;
+    int tune_simplify_timing;   // knob "simplify_timing": 1 = pb3d_mesh_simplify_resident / pb3d_mesh_compact_resident time their passes with events (one more host wait)
+    // the last of the two (csrc/simplify.hip) for pb3d_simplify_last: clusters, vertices out, faces out; with simplify_timing the
+    // milliseconds of its passes (clusters, map, sorts + repeats, scans, gathers)
+    struct SimplifyLast { bool valid, timed; float ms[5]; i64 counts[3]; } simplify_last;
     // Growable device scratch slots, named by enum pb3d_slot (no hipMalloc / hipFree per call once warm).
     void* scratch[PB3D_SLOT_COUNT];
     size_t scratch_bytes[PB3D_SLOT_COUNT];

@@ -182,6 +182,10 @@ _SIGNATURES = {
     "pb3d_voxel_downsample_resident": [vp, vp, C.c_int, i64, C.c_double, dblp, C.c_int, vp, vp, vp, vp, i64p],
     "pb3d_mesh_adjacency_resident": [vp, vp, C.c_int, i64, i64, vp, vp, vp, vp, i64p],
     "pb3d_mesh_smooth_resident": [vp, vp, C.c_int, i64, vp, C.c_int, i64, C.c_int, C.c_double, C.c_double, vp, C.c_int, vp],
+    "pb3d_mesh_simplify_resident": [vp, vp, C.c_int, i64, vp, C.c_int, i64, C.c_double, dblp, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp,
+                                    vp, i64p],
+    "pb3d_mesh_compact_resident": [vp, vp, C.c_int, i64, vp, C.c_int, i64, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, i64p],
+    "pb3d_simplify_last": [vp, i64p, dblp],
     "pb3d_voxelize_mesh_resident": [vp, vp, C.c_int, i64, vp, C.c_int, i64, i64, i64, i64, dblp, C.c_double, C.c_int, C.c_double, C.c_int, u8p,
                                     vp, i64p],
     "pb3d_voxelize_last": [vp, dblp],

@@ -1,5 +1,5 @@
 """Device-resident timing of every op of the path (M1..M8 of SURVEY.md 8(d), plus the N1/N2 kernels of the notebook-1 chain) on
-synthetic inputs.  Development/measurement tool: python tools/opbench.py [--size 1024] [--shape WxHxD] [--ops M1,M3,...,N2,overlays,ICP,PLANE,MESHD,CLUSTER,DOWNSAMPLE,SMOOTH,VOXELIZE,EDT,RENDER,ISO]; one JSON
+synthetic inputs.  Development/measurement tool: python tools/opbench.py [--size 1024] [--shape WxHxD] [--ops M1,M3,...,N2,overlays,ICP,PLANE,MESHD,CLUSTER,DOWNSAMPLE,SMOOTH,SIMPLIFY,VOXELIZE,EDT,RENDER,ISO]; one JSON
 line per op.  Pricing: `alg_B_per_voxel` is SURVEY 8(d)'s algorithmic figure for the sweeps that are EXECUTED (a folded 0-degree step
 moves nothing and is not priced); ops whose intermediates are not bytes (the bit-sliced chains) also carry `moved_B_per_voxel`, the
 bytes that cross the HBM by design, and their `frac_of_8TBs` is computed from THAT (never from bytes that are not moved)."""
@@ -262,6 +262,8 @@ def main():
         downsample(a.reps, res, cpu_ref=not a.no_cpu_ref)
     if "SMOOTH" in ops:
         smooth(a.reps, res, cpu_ref=not a.no_cpu_ref)
+    if "SIMPLIFY" in ops:
+        simplify(a.reps, res, cpu_ref=not a.no_cpu_ref)
     if "VOXELIZE" in ops:
         voxelize(a.reps, res, cpu_ref=not a.no_cpu_ref)
     if "EDT" in ops:
@@ -988,6 +990,90 @@ def smooth(reps, res, cpu_ref=True):
         b.free()
     print(json.dumps(r), flush=True)
     res.append(r)
+
+
+def simplify(reps, res, cpu_ref=True):
+    """SIMPLIFY, simplify_mesh and compact_mesh (csrc/simplify.hip) on the stride-1 mesh of the stored Taj grid as
+    pb3d.device.meshify(download=False) leaves it (float32 vertices, int32 faces, nearest-voxel bytes).  Resident, by device events (best
+    mean of reps, host waits inside): simplify_mesh at voxel_size 2 and 4 and compact_mesh, each with duplicate_faces drop and keep.
+    Per row the five passes from the call's own events under knob simplify_timing (clusters, map, sorts + repeats, scans, gathers) and
+    pb3d_simplify_last's counts.  The yardsticks are the same library's own operations on the same data: (a) voxel_downsample of the same
+    vertex list at the same voxel_size (the call contains it), (b) the adjacency build of smooth_mesh on the same faces (two sorts of
+    6 nf pairs), (c) a plain device-to-device copy of the bytes the face half must move (faces, cluster numbers and rows in; faces,
+    positions, rows, index, inverse and colours out).  With cpu_ref, the restatement of tests/simplify_restate.py in NumPy on this host
+    and whether the device's six arrays equal it."""
+    import simplify_restate as sr
+    from pb3d import simplify as sm
+    lib, L = pb3d._lib.load(), pb3d._lib
+    taj = np.load(os.path.join(ROOT, "tests", "golden", "stored_Taj_voxel_grid.npz"))["voxel_grid"]
+    d_g = dev.from_numpy(taj)
+    (d_v, d_f, d_n, d_c), (nv, nf) = dev.meshify(d_g, taj.shape, download=False)
+    d_g.free(); d_n.free()
+    host = (d_v.download((nv, 3), np.float32), d_f.download((nf, 3), np.int32), d_c.download((nv, 3))) if cpu_ref else None
+    outs = [dev.DeviceBuffer(n) for n in (nv * 12, nf * 12, nv * 3, nv * 4, nv * 4, nf * 4)]
+    po = [C.c_void_p(b.ptr) for b in outs]
+    counts, last, ms = (C.c_int64 * 2)(), (C.c_int64 * 3)(), (C.c_double * 5)()
+    head = (C.c_void_p(d_v.ptr), 0, nv, C.c_void_p(d_f.ptr), 0, nf)
+
+    def best(fn):
+        return min(timeit(fn, reps, warm=1) for _ in range(2))
+
+    # (b): the adjacency build on the same faces
+    adj = [dev.DeviceBuffer((nv + 1) * 8), dev.DeviceBuffer(6 * nf * 4)]
+    total = C.c_int64(0)
+    t_adj = best(lambda: L.check(lib.pb3d_mesh_adjacency_resident(L.ctx(), C.c_void_p(d_f.ptr), 0, nv, nf, C.c_void_p(adj[0].ptr),
+                                                                  C.c_void_p(adj[1].ptr), None, None, C.byref(total))))
+    for b in adj:
+        b.free()
+    ds_bufs = [dev.DeviceBuffer(nv * w) for w in (12, 4, 4)]
+    t_down = {}
+    for vs, dup in [(2.0, "drop"), (2.0, "keep"), (4.0, "drop"), (4.0, "keep"), (None, "drop"), (None, "keep")]:
+        d = sm.DUPLICATE_FACES[dup]
+        if vs is None:
+            call = lambda: L.check(lib.pb3d_mesh_compact_resident(L.ctx(), *head, d, C.c_void_p(d_c.ptr), 3, *po, counts))
+        else:
+            call = lambda: L.check(lib.pb3d_mesh_simplify_resident(L.ctx(), *head, vs, None, 0, d, C.c_void_p(d_c.ptr), 3, *po, counts))
+            if vs not in t_down:        # (a): voxel_downsample of the same list
+                m = C.c_int64(0)
+                t_down[vs] = best(lambda: L.check(lib.pb3d_voxel_downsample_resident(L.ctx(), C.c_void_p(d_v.ptr), 0, nv, vs, None, 0,
+                                                                                     *(C.c_void_p(b.ptr) for b in ds_bufs), None, C.byref(m))))
+        r = {"op": "SIMPLIFY", "name": ("compact_mesh" if vs is None else "simplify_mesh") + ": stored Taj, stride 1", "nverts": nv, "nfaces": nf,
+             "voxel_size": vs, "duplicate_faces": dup, "call_ms": round(best(call), 4)}
+        L.set_tuning("simplify_timing", 1)
+        try:
+            passes = []
+            for _ in range(max(2, reps)):
+                call()
+                L.check(lib.pb3d_simplify_last(L.ctx(), last, ms))
+                passes.append(list(ms))
+        finally:
+            L.set_tuning("simplify_timing", 0)
+        p = min(passes, key=sum)
+        n_out, m_out, clusters = int(last[1]), int(last[2]), int(last[0])
+        face_half = sum(p[1:])
+        moved = (12 * nf + 4 * nv + 12 * clusters + 3 * nv) + (16 * m_out + 16 * n_out + 4 * nv + 3 * n_out)
+        d_a, d_b = dev.DeviceBuffer(moved // 2), dev.DeviceBuffer(moved // 2)           # a copy reads and writes: half the bytes each way
+        t_copy = best(lambda: L.check(lib.pb3d_d2d(L.ctx(), C.c_void_p(d_b.ptr), C.c_void_p(d_a.ptr), moved // 2)))
+        d_a.free(); d_b.free()
+        r.update({"clusters": clusters, "nverts_out": n_out, "nfaces_out": m_out,
+                  "pass_ms": {k: round(t, 4) for k, t in zip(("clusters", "map", "sorts_repeats", "scans", "gathers"), p)},
+                  "face_half_ms": round(face_half, 4), "adjacency_ms": round(t_adj, 4), "face_half_over_adjacency": round(face_half / t_adj, 2),
+                  "face_half_bytes": moved, "copy_of_face_half_bytes_ms": round(t_copy, 4), "face_half_over_copy": round(face_half / t_copy, 2)})
+        if vs is not None:
+            r.update({"voxel_downsample_ms": round(t_down[vs], 4), "call_over_voxel_downsample": round(r["call_ms"] / t_down[vs], 2)})
+        if cpu_ref:
+            call()
+            got = (outs[0].download((n_out, 3), np.float32), outs[1].download((m_out, 3), np.int32), outs[2].download((n_out, 3)),
+                   outs[3].download((n_out,), np.int32), outs[4].download((nv,), np.int32), outs[5].download((m_out,), np.int32))
+            t0 = time.perf_counter()
+            ref = sr.restate(host[0], host[1], vs, None, "centroid", dup, host[2])
+            r["numpy_restatement_ms"] = round(1e3 * (time.perf_counter() - t0), 1)
+            r["numpy_equal"] = bool((int(counts[0]), int(counts[1])) == (len(ref[0]), len(ref[1]))
+                                    and all(np.array_equal(g, w) for g, w in zip(got, ref)) and got[0].tobytes() == ref[0].tobytes())
+        print(json.dumps(r), flush=True)
+        res.append(r)
+    for b in outs + ds_bufs + [d_v, d_f, d_c]:
+        b.free()
 
 
 def voxelize(reps, res, cpu_ref=True):
