@@ -548,6 +548,65 @@ int pb3d_mesh_compact_resident(pb3d_ctx* ctx, const void* d_verts, int verts_f64
                                int32_t* d_face_index /* nf, or NULL */, int64_t counts[2] /* vertices, faces written */);
 int pb3d_simplify_last(pb3d_ctx* ctx, int64_t counts[3], double pass_ms[5] /* or NULL */);
 
+/* ---- mesh components: connected components, edge counts and ordered measures of a triangle mesh (csrc/meshcomp.hip), and the mesh of
+ * a face mask (csrc/simplify.hip) ------------------------------------------------------------------------------------------------------
+ * The segmentation step for the third shape of data (cluster_points has the clouds, the labelling the grids): Open3D's
+ * cluster_connected_triangles + remove_triangles_by_mask, trimesh's split / is_watertight.  There is no upstream text, so the rules
+ * below are the specification, and the result is a function of the input and its order alone, to the bit.
+ *   INPUT      faces: (nf, 3) rows of int32 (faces_i64 = 0) or int64 (1) with entries in [-nv, nv); entries in [-nv, -1] wrap as NumPy's
+ *              do.  Anything else is PB3D_EINDEX, checked on the device before any kernel gathers through them (one host wait), with
+ *              nothing written; nv = 0 with nf > 0 is PB3D_EINDEX.  verts (or NULL): (nv, 3) rows of float32 (verts_f64 = 0; widened)
+ *              or float64 (1), read only for the measures; they must be finite (the caller's promise: pb3d.mesh_components checks it
+ *              on the host), else area and volume are whatever IEEE arithmetic makes of them.  Limits: nv <= 2^31 - 1,
+ *              nf <= (2^31 - 1) / 6.
+ *   RECORDS    face j with wrapped corners (w0, w1, w2) gives the records 3j, 3j + 1, 3j + 2 for the directed edges (w0, w1), (w1, w2),
+ *              (w2, w0).  A record with equal ends is a LOOP and takes no further part.  A record's undirected edge is (lo, hi); the
+ *              record is FORWARD iff its source is lo.
+ *   EDGES      an undirected edge with c records of which f are forward is BOUNDARY iff c == 1, NON-MANIFOLD iff c > 2, UNBALANCED iff
+ *              2 f != c.  Unbalanced includes every boundary edge and every pair traversed twice the same way; no unbalanced edge is
+ *              exactly "every directed edge has its reverse", what pb3d_voxelize_mesh_resident's crossing parity needs.
+ *   CONNECT    PB3D_MESH_CONNECT_VERTEX: two faces are connected when they name a common vertex.  PB3D_MESH_CONNECT_EDGE: when an
+ *              undirected edge has a record of each (Open3D's rule; an edge of many faces connects all of them).  Components are the
+ *              classes of the transitive closure.  A face all of whose records are loops is a component of its own under EDGE and in
+ *              the component of its vertex under VERTEX.
+ *   NUMBERS    components are numbered 0 .. nc - 1 by their smallest face position.  face_labels[j] = the number of face j's component;
+ *              vertex_labels[i] = the smallest label among the faces that name vertex i, -1 when none does.
+ *   COUNTS     d_counts (or NULL; room for 5 nf int64) holds five arrays of nc, one behind the other: faces, edges, boundary edges,
+ *              non-manifold edges, unbalanced edges of every component.  An edge belongs to the component of its faces, which is the
+ *              same for all of them under both rules.
+ *   MEASURES   d_measures (or NULL; needs verts; room for 2 nf float64) holds two arrays of nc: area, volume.  Per face, with the
+ *              corners a, b, c as float64 and every operation below one rounded float64 operation (no FMA):
+ *                e1 = b - a, e2 = c - a;  nx = e1y*e2z - e1z*e2y, ny = e1z*e2x - e1x*e2z, nz = e1x*e2y - e1y*e2x;
+ *                A_j = 0.5 * sqrt((nx*nx + ny*ny) + nz*nz) with the correctly rounded square root;
+ *                m = b x c formed like n;  S_j = (a.x*m.x + a.y*m.y) + a.z*m.z.
+ *              A component's faces in ascending position are cut into blocks of 256, counted within the component's own list; a block
+ *              sum starts at 0.0 and takes its faces in order; the total starts at 0.0 and takes the block sums in order.
+ *              area = the total of A, volume = the total of S divided by 6.0: signed, and meaningful when the component has no
+ *              unbalanced edge.
+ *   TOTALS     totals[8] = components nc, vertices some face names V, undirected edges E, faces F = nf, boundary, non-manifold and
+ *              unbalanced edges, loops.  The Euler characteristic is V - E + F.  Read back once, the call's one host wait behind the
+ *              index check; everything else is enqueued.
+ *   EMPTY      nf = 0: totals all 0, vertex_labels all -1, no host wait.
+ * Nothing is kept per edge and no lane walks along a run of records: the 3 nf records go through two stable radix sorts of (key, record)
+ * pairs, by hi and then by lo; run heads and forward bits are flagged and scanned, so c and f are differences at consecutive heads; the
+ * components are a lock-free union-find whose roots are minima by construction (csrc/union_find.h); the counts are integer atomics; the
+ * measures use no atomics: a stable sort of (label, face), one wavefront per block, one per component.  Scratch: about 170 bytes per
+ * face (corners 12; pairs 48, flags 24, ranks 48 and edge starts 12 for its three records; the components' parent, flags and ranks 16;
+ * scans and run table), 56 more with measures, 40 more without d_counts, 4 - 12 per vertex.
+ * mesh_select_faces is mesh_compact's VERTICES, FACES OUT, ATTRIBUTES and outputs with the caller's flags in place of COLLAPSED and
+ *   REPEATED: face j stays iff d_keep[j] != 0 (nf bytes), degenerate and repeated faces included, in order and in corner order; the
+ *   vertices no kept face names go, the rest are renumbered in order and copied byte for byte.  Host waits: the index check and counts. */
+#define PB3D_MESH_CONNECT_EDGE 0
+#define PB3D_MESH_CONNECT_VERTEX 1
+int pb3d_mesh_components_resident(pb3d_ctx* ctx, const void* d_verts /* or NULL */, int verts_f64, int64_t nv, const void* d_faces, int faces_i64,
+                                  int64_t nf, int connectivity, int32_t* d_face_labels /* nf */, int32_t* d_vertex_labels /* nv, or NULL */,
+                                  int64_t* d_counts /* 5 nf, or NULL */, double* d_measures /* 2 nf, or NULL */, int64_t totals[8]);
+int pb3d_mesh_select_faces_resident(pb3d_ctx* ctx, const void* d_verts, int verts_f64, int64_t nv, const void* d_faces, int faces_i64, int64_t nf,
+                                    const uint8_t* d_keep /* nf */, const uint8_t* d_colors /* nv x channels, or NULL */, int channels,
+                                    void* d_out_verts /* nv rows */, void* d_out_faces /* nf rows */, uint8_t* d_out_colors /* or NULL */,
+                                    int32_t* d_index /* nv, or NULL */, int32_t* d_inverse /* nv, or NULL */,
+                                    int32_t* d_face_index /* nf, or NULL */, int64_t counts[2] /* vertices, faces written */);
+
 /* ---- mesh -> grid: exact solid voxelization of a triangle mesh by crossing parity, and the overlap of two grids (csrc/voxelize.hip) ------
  * The one conversion the other sections lack: a mesh (a CAD model, a smoothed marching-cubes mesh) becomes an occupancy, label or RGB grid
  * that the carve, paint, points and labelling entries take as it is.  Solid voxelization by crossing parity (Schwarz & Seidel 2010) with a

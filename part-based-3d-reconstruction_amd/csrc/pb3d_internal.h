@@ -269,8 +269,32 @@ enum pb3d_slot : int {
     PB3D_SLOT_SIMPLIFY_SCAN_LOCAL = 147,
     PB3D_SLOT_SIMPLIFY_SCAN_SEGS = 148,
     PB3D_SLOT_SIMPLIFY_COUNTS = 149,
+    // call-local, csrc/meshcomp.hip, all of them (R = 3 nf edge records): each face's wrapped corners (nf x 3 u32); the (key, record)
+    // pairs of the two stable sorts (key, val and their ping-pong twins, R u32 each; the measures' (label, face) sort takes the front
+    // of them once the edges are counted) and the sorts' run table; the run-head flags and the forward bits (R u32 each), their ranks
+    // (R + 1 int64 each) and the position of every edge's first record (R + 1 u32); the union-find's parent (per face under "edge",
+    // per vertex under "vertex") and, under "vertex", each root's smallest face; the "first face of a component" flags (nf u32) and
+    // their ranks (nf + 1 int64); the vertex labels before -1 is written (nv int32); the u32 face count and block count of every
+    // component with their two scans (nf + 1 int64 each); A_j, S_j per face and the block sums (nf x 2 float64 each); the eight totals;
+    // the two slots of every pb3d_scan_counts of the call.  The index check in front uses SURF_FLAG
+    PB3D_SLOT_MESHCOMP_CORNERS = 150,
+    PB3D_SLOT_MESHCOMP_PAIRS = 151,
+    PB3D_SLOT_MESHCOMP_SORT_HIST = 152,
+    PB3D_SLOT_MESHCOMP_FLAGS = 153,
+    PB3D_SLOT_MESHCOMP_RANKS = 154,
+    PB3D_SLOT_MESHCOMP_HEADS = 155,
+    PB3D_SLOT_MESHCOMP_PARENT = 156,
+    PB3D_SLOT_MESHCOMP_MIN_FACE = 157,
+    PB3D_SLOT_MESHCOMP_ROOT_FLAGS = 158,
+    PB3D_SLOT_MESHCOMP_ROOT_RANKS = 159,
+    PB3D_SLOT_MESHCOMP_VERTEX_LABELS = 160,
+    PB3D_SLOT_MESHCOMP_SEGMENTS = 161,
+    PB3D_SLOT_MESHCOMP_MEASURES = 162,
+    PB3D_SLOT_MESHCOMP_TOTALS = 163,
+    PB3D_SLOT_MESHCOMP_SCAN_LOCAL = 164,
+    PB3D_SLOT_MESHCOMP_SCAN_SEGS = 165,
 
-    PB3D_SLOT_COUNT = 150
+    PB3D_SLOT_COUNT = 166
 };
 
 // ---- the cell index of the exact nearest-neighbour search (csrc/nn.hip) -----------------------------------

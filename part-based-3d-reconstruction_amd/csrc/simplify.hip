@@ -40,10 +40,12 @@ __device__ __forceinline__ Tri rotated(const Tri& t) {
 }
 __device__ __forceinline__ void mark(u32* __restrict__ used, const Tri& t) { used[t.g[0]] = 1u; used[t.g[1]] = 1u; used[t.g[2]] = 1u; }
 
-// inv null: every vertex its own cluster.  DROP: key / val are the sort's first pairs, keep and used are written by k_face_repeats
+// inv null: every vertex its own cluster.  DROP: key / val are the sort's first pairs, keep and used are written by k_face_repeats.
+// given (not with DROP): the caller's flags decide what stays, collapsed faces included
 template <bool I64, bool DROP>
-__global__ __launch_bounds__(256) void k_face_map(const void* __restrict__ faces, i64 nf, i64 nv, const int* __restrict__ inv, u32 m, u32* __restrict__ G,
-                                                  u32* __restrict__ keep, u32* __restrict__ used, u32* __restrict__ key, u32* __restrict__ val) {
+__global__ __launch_bounds__(256) void k_face_map(const void* __restrict__ faces, i64 nf, i64 nv, const int* __restrict__ inv, u32 m, const u8* __restrict__ given,
+                                                  u32* __restrict__ G, u32* __restrict__ keep, u32* __restrict__ used, u32* __restrict__ key,
+                                                  u32* __restrict__ val) {
     const i64 j = (i64)blockIdx.x * 256 + threadIdx.x;
     if (j >= nf) return;
     Tri t;
@@ -58,8 +60,9 @@ __global__ __launch_bounds__(256) void k_face_map(const void* __restrict__ faces
         key[j] = dead ? m : rotated(t).g[2];
         val[j] = (u32)j;
     } else {
-        keep[j] = dead ? 0u : 1u;
-        if (!dead) mark(used, t);
+        const bool stays = given ? given[j] != 0 : !dead;
+        keep[j] = stays ? 1u : 0u;
+        if (stays) mark(used, t);
     }
 }
 
@@ -161,6 +164,7 @@ struct Mesh {
     void *out_verts, *out_faces;
     u8* out_colors;
     int *index, *inverse, *face_index;
+    const u8* given;           // pb3d_mesh_select_faces_resident: one flag per face (with PB3D_FACES_KEEP), else null
 };
 
 int require_mesh(const char* what, const Mesh& s, const int64_t* counts) {
@@ -199,7 +203,7 @@ int face_tail(pb3d_ctx* ctx, const Mesh& s, const int* inv, const int* first, co
         u32* a = (u32*)kv;
         u32 *key = a, *val = a + nf, *key2 = a + 2 * nf, *val2 = a + 3 * nf;
         hipLaunchKernelGGL((s.faces_i64 ? k_face_map<true, true> : k_face_map<false, true>), grid_for(nf), dim3(256), 0, ctx->stream, s.faces, nf, nv, inv,
-                           (u32)m, G, keep, used, key, val);
+                           (u32)m, (const u8*)nullptr, G, keep, used, key, val);
         PB3D_CHECK_LAUNCH();
         PB3D_TRY(t.mark(ctx));
         for (int which = 2; which >= 0; --which) {
@@ -216,7 +220,7 @@ int face_tail(pb3d_ctx* ctx, const Mesh& s, const int* inv, const int* first, co
         PB3D_CHECK_LAUNCH();
     } else {
         hipLaunchKernelGGL((s.faces_i64 ? k_face_map<true, false> : k_face_map<false, false>), grid_for(nf), dim3(256), 0, ctx->stream, s.faces, nf, nv,
-                           inv, (u32)m, G, keep, used, (u32*)nullptr, (u32*)nullptr);
+                           inv, (u32)m, s.given, G, keep, used, (u32*)nullptr, (u32*)nullptr);
         PB3D_CHECK_LAUNCH();
         PB3D_TRY(t.mark(ctx));
     }
@@ -310,6 +314,19 @@ int pb3d_mesh_compact_resident(pb3d_ctx* ctx, const void* d_verts, int verts_f64
     PB3D_TRY(require_mesh("pb3d_mesh_compact", s, counts));
     PB3D_REQUIRE(ctx != nullptr, "pb3d_mesh_compact: null context");
     return run(ctx, "pb3d_mesh_compact", s, false, 0.0, nullptr, 0, counts);
+}
+
+int pb3d_mesh_select_faces_resident(pb3d_ctx* ctx, const void* d_verts, int verts_f64, int64_t nv, const void* d_faces, int faces_i64, int64_t nf,
+                                    const uint8_t* d_keep, const uint8_t* d_colors, int channels, void* d_out_verts, void* d_out_faces,
+                                    uint8_t* d_out_colors, int32_t* d_index, int32_t* d_inverse, int32_t* d_face_index, int64_t counts[2]) {
+    const Mesh s = {d_verts, verts_f64, nv, d_faces, faces_i64, nf, PB3D_FACES_KEEP, d_colors, channels, d_out_verts, d_out_faces, d_out_colors,
+                    d_index, d_inverse, d_face_index, d_keep};
+    PB3D_TRY(require_mesh("pb3d_mesh_select_faces", s, counts));
+    PB3D_REQUIRE(nf == 0 || d_keep != nullptr, "pb3d_mesh_select_faces: null buffer");
+    PB3D_REQUIRE(nv == 0 || nf == 0 || ((const void*)d_keep != d_out_verts && (const void*)d_keep != d_out_faces),
+                 "pb3d_mesh_select_faces: an output may not alias an input");
+    PB3D_REQUIRE(ctx != nullptr, "pb3d_mesh_select_faces: null context");
+    return run(ctx, "pb3d_mesh_select_faces", s, false, 0.0, nullptr, 0, counts);
 }
 
 int pb3d_simplify_last(pb3d_ctx* ctx, int64_t counts[3], double pass_ms[5]) {

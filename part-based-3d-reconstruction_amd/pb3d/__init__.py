@@ -36,6 +36,8 @@ from .cluster import (cluster_points, cluster_points_resident, keep_largest_clus
 from .downsample import voxel_downsample, voxel_downsample_resident  # noqa: F401
 from .smooth import mesh_vertex_adjacency, mesh_vertex_adjacency_resident, smooth_mesh, smooth_mesh_resident  # noqa: F401
 from .simplify import compact_mesh, compact_mesh_resident, simplify_mesh, simplify_mesh_resident  # noqa: F401
+from .meshcomp import (keep_mesh_components, keep_mesh_components_resident, mesh_components, mesh_components_resident,  # noqa: F401
+                       mesh_topology, mesh_topology_resident, select_faces, select_faces_resident)
 from .voxelize import grid_overlap_counts, grid_overlap_counts_resident, mesh_grid_iou, voxelize_mesh, voxelize_mesh_resident  # noqa: F401
 from .distance import (close_grid, close_grid_resident, dilate_grid, dilate_grid_resident, distance_transform,  # noqa: F401
                        distance_transform_resident, erode_grid, erode_grid_resident, grid_surface_metrics, grid_surface_metrics_resident,

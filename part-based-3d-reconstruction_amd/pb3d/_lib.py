@@ -186,6 +186,8 @@ _SIGNATURES = {
                                     vp, i64p],
     "pb3d_mesh_compact_resident": [vp, vp, C.c_int, i64, vp, C.c_int, i64, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, i64p],
     "pb3d_simplify_last": [vp, i64p, dblp],
+    "pb3d_mesh_components_resident": [vp, vp, C.c_int, i64, vp, C.c_int, i64, C.c_int, vp, vp, vp, vp, i64p],
+    "pb3d_mesh_select_faces_resident": [vp, vp, C.c_int, i64, vp, C.c_int, i64, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, i64p],
     "pb3d_voxelize_mesh_resident": [vp, vp, C.c_int, i64, vp, C.c_int, i64, i64, i64, i64, dblp, C.c_double, C.c_int, C.c_double, C.c_int, u8p,
                                     vp, i64p],
     "pb3d_voxelize_last": [vp, dblp],

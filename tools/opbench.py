@@ -1,5 +1,5 @@
 """Device-resident timing of every op of the path (M1..M8 of SURVEY.md 8(d), plus the N1/N2 kernels of the notebook-1 chain) on
-synthetic inputs.  Development/measurement tool: python tools/opbench.py [--size 1024] [--shape WxHxD] [--ops M1,M3,...,N2,overlays,ICP,PLANE,MESHD,CLUSTER,DOWNSAMPLE,SMOOTH,SIMPLIFY,VOXELIZE,EDT,RENDER,ISO]; one JSON
+synthetic inputs.  Development/measurement tool: python tools/opbench.py [--size 1024] [--shape WxHxD] [--ops M1,M3,...,N2,overlays,ICP,PLANE,MESHD,CLUSTER,DOWNSAMPLE,SMOOTH,SIMPLIFY,VOXELIZE,EDT,RENDER,ISO,MESHCOMP]; one JSON
 line per op.  Pricing: `alg_B_per_voxel` is SURVEY 8(d)'s algorithmic figure for the sweeps that are EXECUTED (a folded 0-degree step
 moves nothing and is not priced); ops whose intermediates are not bytes (the bit-sliced chains) also carry `moved_B_per_voxel`, the
 bytes that cross the HBM by design, and their `frac_of_8TBs` is computed from THAT (never from bytes that are not moved)."""
@@ -278,6 +278,8 @@ def main():
         isosurface(a.reps, res)
     if "MESHD" in ops:
         mesh_target(a.reps, res)
+    if "MESHCOMP" in ops:
+        mesh_components(a.reps, res)
     if "overlays" in ops:
         overlays(a.reps, res)
     if d_col is not None:
@@ -1548,6 +1550,80 @@ def isosurface(reps, res):
         res.append(r)
         d_vol.free()
     d_sfm.free(); d_tp.free()
+
+
+def mesh_components(reps, res):
+    """MESHCOMP, mesh_components, select_faces and keep_mesh_components (csrc/meshcomp.hip, csrc/simplify.hip) on the meshes of the
+    SIMPLIFY and ISO rows: the stride-1 mesh of the stored Taj grid and the 512^3 isosurface of the density volume of its points at level
+    0.1.  Resident, by device events (best mean of reps, host waits inside): the labelling under both connectivities, without and with
+    the measures; mesh_topology; keep_mesh_components(k=1) by faces; select_faces on keep's own mask.  Two yardsticks that are not the
+    code under test, on the same mesh in the same run: mesh_vertex_adjacency_resident (it sorts 6 m pairs by two keys where the
+    labelling sorts 3 m records) and compact_mesh_resident with duplicate_faces="keep" (the select tail's passes on every face)."""
+    from pb3d import meshcomp as mcp, simplify as sm, smooth as smo
+    from pb3d.eval_helpers import density_grid_resident
+    lib, L = pb3d._lib.load(), pb3d._lib
+    taj = np.load(os.path.join(ROOT, "tests", "golden", "stored_Taj_voxel_grid.npz"))["voxel_grid"]
+    nvox = int(np.prod(taj.shape[:3]))
+    d_g = dev.from_numpy(taj)
+
+    def best(fn):
+        return min(timeit(fn, reps, warm=1) for _ in range(2))
+
+    def free(bufs):
+        for b in bufs:
+            if hasattr(b, "free"):
+                b.free()
+
+    def taj_mesh():
+        (d_v, d_f, d_n, d_c), (nv, nf) = dev.meshify(d_g, taj.shape, download=False)
+        free((d_n, d_c))
+        return d_v, d_f, nv, nf
+
+    def iso_mesh():
+        d_tp, d_tc = dev.DeviceBuffer(nvox * 12), dev.DeviceBuffer(nvox * 3)
+        n = C.c_int64(0)
+        L.check(lib.pb3d_points_extract_dev(L.ctx(), C.c_void_p(d_g.ptr), *taj.shape[:3], 3, None, 0, nvox, C.c_void_p(d_tp.ptr),
+                                            C.c_void_p(d_tc.ptr), C.byref(n)))
+        d_vol = density_grid_resident(d_tp, n.value, 512, 1.0, f64=False)
+        (d_v, d_f), (nv, nf) = dev.isosurface(d_vol, (512, 512, 512), 0.1, 512, download=False)
+        free((d_tp, d_tc, d_vol))
+        return d_v, d_f, nv, nf
+
+    for name, make in (("stored Taj, stride-1 mesh", taj_mesh), ("512^3 isosurface of the Taj density volume, level 0.1", iso_mesh)):
+        d_v, d_f, nv, nf = make()
+        r = {"op": "MESHCOMP", "name": f"mesh_components: {name}", "nverts": int(nv), "nfaces": int(nf), "records": 3 * int(nf), "reps": reps}
+        for conn in ("edge", "vertex"):
+            for measured in (False, True):
+                def call():
+                    *bufs, t = mcp.mesh_components_resident(d_f, nf, nv, d_v if measured else None, conn)
+                    free(bufs)
+                    return t
+                r[f"{conn}{'_measured' if measured else ''}_ms"] = round(best(call), 4)
+            r[f"{conn}_components"] = call()["components"]
+        t = mcp.mesh_topology_resident(d_f, nf, nv)
+        r.update({"topology_ms": round(best(lambda: mcp.mesh_topology_resident(d_f, nf, nv)), 4),
+                  "topology": {k: t[k] for k in mcp.TOTALS + ("euler", "closed", "edge_manifold", "watertight")}})
+
+        def keep():
+            out, d_lab, chosen = mcp.keep_mesh_components_resident(d_v, nv, d_f, nf, k=1)
+            free(out[:6] + (d_lab,))
+            return out[6]
+        r["keep_k1_ms"] = round(best(keep), 4)
+        r["keep_k1_counts"] = list(keep())
+        d_keep = dev.from_numpy(np.ones(nf, np.uint8))
+        r["select_all_ms"] = round(best(lambda: free(mcp.select_faces_resident(d_v, nv, d_f, nf, d_keep)[:6])), 4)
+        # the yardsticks
+        r["yardstick_adjacency_ms"] = round(best(lambda: free(smo.mesh_vertex_adjacency_resident(d_f, nv, nf)[:4])), 4)
+        r["yardstick_compact_keep_ms"] = round(best(lambda: free(sm.compact_mesh_resident(d_v, nv, d_f, nf, duplicate_faces="keep")[:6])), 4)
+        r.update({"edge_over_adjacency": round(r["edge_ms"] / r["yardstick_adjacency_ms"], 3),
+                  "vertex_over_adjacency": round(r["vertex_ms"] / r["yardstick_adjacency_ms"], 3),
+                  "edge_measured_over_adjacency": round(r["edge_measured_ms"] / r["yardstick_adjacency_ms"], 3),
+                  "select_over_compact_keep": round(r["select_all_ms"] / r["yardstick_compact_keep_ms"], 3),
+                  "keep_k1_over_edge_plus_compact": round(r["keep_k1_ms"] / (r["edge_ms"] + r["yardstick_compact_keep_ms"]), 3)})
+        print(json.dumps(r), flush=True)
+        res.append(r)
+        free((d_v, d_f, d_keep))
+    d_g.free()
 
 
 def overlays(reps, res):
