@@ -668,6 +668,60 @@ int pb3d_voxelize_last(pb3d_ctx* ctx, double pass_ms[2]);
 int pb3d_grid_overlap_resident(pb3d_ctx* ctx, const uint8_t* d_a, int channels_a, const uint8_t* d_b, int channels_b, int64_t nvox,
                                int64_t out[3]);
 
+/* ---- containment: which points of a cloud lie inside a triangle mesh, and signed mesh distances (csrc/inside.hip) --------------------
+ * The relation the other sections lack: mesh_dist says how far a point is from the surface, not on which side.  The rule is the
+ * voxelization's above -- its FACE and RESULT rules with the column (i, j) replaced by the query's (q0, q1), from the same text
+ * (csrc/cross_rule.h) -- so at a lattice point the byte is the voxel's, and as there the result is a function of the input alone, to the
+ * bit.  There is no upstream text: the rules below are the specification.
+ *   INPUT      d_P: (nP, 3) rows of float32 (p_f64 = 0) or float64 (1).  verts, faces: as for the voxelization, with its checks: an
+ *              index outside [-nv, nv) is PB3D_EINDEX, a vertex coordinate that is not finite (of any vertex, used or not)
+ *              PB3D_EINVAL, both found in one sweep before any kernel gathers (one host wait), and nothing is written when they
+ *              fail.  nP, nv and 3 * nf <= 2^31 - 1.  No frame, origin or voxel size is applied: vertices and queries are used as given.
+ *   ARITHMETIC all float64; float32 is widened first, which is exact.  Every product, sum, difference and quotient below is one rounded
+ *              IEEE operation, no FMA.  Rays run along the third coordinate.
+ *   FACE       query q against face (A, B, C):
+ *              1. area as in the voxelization's step 1; area == 0: the face contributes nothing.
+ *              2. box: the face is considered only if min(A0,B0,C0) <= q0 <= max(A0,B0,C0), and likewise on axis 1.  At integer q this is
+ *                 the voxelization's step 2.
+ *              3. the three edges as in the voxelization's step 3 with i -> q0, j -> q1: flipped, lo, hi, E, pos and the accept condition
+ *                 pos ? E >= 0 : E < 0 unchanged.  The face COVERS the query if the box holds it and all three edges accept it.
+ *              4. z = A2 - (nx*(q0-A0) + ny*(q1-A1)) / area with nx, ny as in the voxelization's step 4.
+ *   RESULT     total = the number of covering faces; below = the number of covering faces with z <= q2 (a NaN z counts in total only, as
+ *              the voxelization's overflow bit does); inside = below & 1.  An odd total means the mesh is open over this query (the
+ *              voxelization's open column); the answer is still exactly this function of the input.  As there, nothing more is claimed
+ *              for an open mesh, one that intersects itself, or coordinates whose products round.  Pinned: the box with corners (2,3,1)
+ *              and (6,7,5), 12 triangles, queried at the 720 lattice points of a 9 x 10 x 8 grid, is inside at i 3..6, j 3..6, k 1..4.
+ *   QUERIES    A query with a NaN coordinate compares false everywhere: it is outside with below = total = 0, and counts among the
+ *              queries outside the box.  An infinite q2 is a coordinate like any other (+inf: below = total).  The NumPy form refuses
+ *              queries that are not finite; a resident caller gets the above.
+ *   OUTPUT     d_inside: nP bytes, 0 or 1.  d_counts (or NULL): nP x 2 int32, (below, total) per query.
+ *   STATS      stats[4] int64 or NULL (not NULL: one more host wait, one download): queries inside; queries with an odd total; faces
+ *              with area == 0; queries outside the (a0, a1) box of the vertices (they are outside, with no face looked at).
+ * nP = 0 does nothing beyond the check (stats: four zeros).  nf = 0 gives all outside: zero counts, stats {0, 0, 0, nP}.
+ * Index: a 2-D cell grid over the exact (a0, a1) box of ALL vertices, sized from nf by the rule of nn_dist's grid; a face with
+ * area != 0 is listed in every cell of cell(min corner) .. cell(max corner) per axis, and because that cell function is monotone a face
+ * whose box holds (q0, q1) is listed in the query's cell.  While the (cell, face) entries exceed 8 * nf and the grid has more than one
+ * cell, the cells per axis are halved (mesh_dist's defence against one giant face among small ones).  One lane per query walks the list
+ * of its one cell; no atomics on the query side, no floating-point atomics anywhere.  Host waits: the check, the box, 1 + (number of
+ * halvings) for the entry counts; the query itself is enqueued.  Scratch: 72 bytes per face, 4 bytes per entry, 12 bytes per cell, 12
+ * bytes per 256 queries with stats.
+ * points_in_mesh_last: info = {cells along a0, cells along a1, (cell, face) entries, halvings} of the index the last call with nP > 0
+ *   on this context built (four zeros after nf = 0), PB3D_EINVAL before the first.  pass_ms (or NULL): the milliseconds of the index
+ *   build and of the query from the call's own events under knob "inside_timing" (pb3d_set_tuning; one more host wait), PB3D_EINVAL if
+ *   the last call was not timed.  Knob "inside_order" = 1 walks the queries in the index's cell order instead of the caller's, knob
+ *   "inside_table" = 1 reads each face's finished set-up from a table (184 more bytes of scratch per face) instead of computing it
+ *   from the corners; no byte depends on any of the three.
+ * mesh_dist_sign: d_out[i] = (d_inside[i] != 0 && d_dist[i] > 0) ? -d_dist[i] : d_dist[i] for i < n -- mesh_dist's distances, signed
+ *   by the bytes above: negative inside, and a point on the surface keeps +0.0.  d_out may be d_dist.  Enqueued.
+ * flags_not: d_out[i] = d_flags[i] == 0 for i < n, what pb3d_points_select_resident needs to keep the points OUTSIDE a mesh.  d_out may
+ *   be d_flags.  Enqueued. */
+int pb3d_points_in_mesh_resident(pb3d_ctx* ctx, const void* d_P, int p_f64, int64_t nP, const void* d_verts, int verts_f64, int64_t nv,
+                                 const void* d_faces, int faces_i64, int64_t nf, uint8_t* d_inside /* nP */,
+                                 int32_t* d_counts /* nP x 2: below, total; or NULL */, int64_t stats[4] /* or NULL */);
+int pb3d_points_in_mesh_last(pb3d_ctx* ctx, int64_t info[4], double pass_ms[2] /* or NULL */);
+int pb3d_mesh_dist_sign_resident(pb3d_ctx* ctx, const double* d_dist, const uint8_t* d_inside, int64_t n, double* d_out);
+int pb3d_flags_not_resident(pb3d_ctx* ctx, const uint8_t* d_flags, int64_t n, uint8_t* d_out);
+
 /* ---- grid -> distance: the exact Euclidean distance transform with its feature transform (csrc/edt.hip) ------------------------------
  * Squared distances on a lattice are integers, so the transform is stated to the bit; there is no upstream text and the rules below are
  * the specification.  scipy.ndimage.distance_transform_edt(x) equals sqrt((double)sq) of PB3D_EDT_TO_BACKGROUND bit for bit (tests).

@@ -293,8 +293,23 @@ enum pb3d_slot : int {
     PB3D_SLOT_MESHCOMP_TOTALS = 163,
     PB3D_SLOT_MESHCOMP_SCAN_LOCAL = 164,
     PB3D_SLOT_MESHCOMP_SCAN_SEGS = 165,
+    // call-local, csrc/inside.hip, all of them: the nf x 9 float64 corner table; eight 64-bit words the host reads back (the vertex box,
+    // the entry total, the flag of the index / finiteness check in front); per-cell counts (then the scatter's cursors), cell starts,
+    // face ids in cell order and the two slots of its pb3d_scan_counts; four 64-bit words (queries inside, with an odd total, faces
+    // with area == 0, queries outside the box) and the three u32 partial counts of every workgroup of the query kernel.  The box
+    // pass inside uses NN_BOUNDS_PARTIALS, and under knob "inside_order" = 1 the query order uses NN_QUERY_*, NN_ORDER and NN_SCAN_*
+    PB3D_SLOT_INSIDE_CORNERS = 166,
+    PB3D_SLOT_INSIDE_READBACK = 167,
+    PB3D_SLOT_INSIDE_COUNTS = 168,
+    PB3D_SLOT_INSIDE_STARTS = 169,
+    PB3D_SLOT_INSIDE_IDS = 170,
+    PB3D_SLOT_INSIDE_SCAN_LOCAL = 171,
+    PB3D_SLOT_INSIDE_SCAN_SEGS = 172,
+    PB3D_SLOT_INSIDE_STATS = 173,
+    PB3D_SLOT_INSIDE_PARTIALS = 174,
+    PB3D_SLOT_INSIDE_SETUP = 175,                       // knob "inside_table" = 1 only: 184 bytes of finished set-up per face
 
-    PB3D_SLOT_COUNT = 166
+    PB3D_SLOT_COUNT = 176
 };
 
 // ---- the cell index of the exact nearest-neighbour search (csrc/nn.hip) -----------------------------------
@@ -395,6 +410,12 @@ struct pb3d_ctx {
     // the last of the two (csrc/simplify.hip) for pb3d_simplify_last: clusters, vertices out, faces out; with simplify_timing the
     // milliseconds of its passes (clusters, map, sorts + repeats, scans, gathers)
     struct SimplifyLast { bool valid, timed; float ms[5]; i64 counts[3]; } simplify_last;
+    int tune_inside_timing;     // knob "inside_timing": 1 = pb3d_points_in_mesh_resident times its index build and its query with events (one more host wait)
+    int tune_inside_order;      // knob "inside_order": 0 = queries in input order, 1 = in the cell order of the index (csrc/nn.hip's query binning)
+    int tune_inside_table;      // knob "inside_table": 0 = the query recomputes a face's set-up from its 72-byte corner row, 1 = it reads a 184-byte row of finished set-ups (development A/B)
+    // the last pb3d_points_in_mesh_resident (csrc/inside.hip) for pb3d_points_in_mesh_last: cells per axis of its index, (cell, face)
+    // entries and halvings; with inside_timing the milliseconds of the index build and of the query
+    struct InsideLast { bool valid, timed; float ms[2]; i64 info[4]; } inside_last;
     // Growable device scratch slots, named by enum pb3d_slot (no hipMalloc / hipFree per call once warm).
     void* scratch[PB3D_SLOT_COUNT];
     size_t scratch_bytes[PB3D_SLOT_COUNT];

@@ -3,7 +3,8 @@
 //
 // The bit volume holds, per column (i, j) of the grid, W = ceil(n2 / 32) + 1 dwords: bit k of the column is bit k & 31 of dword k >> 5,
 // and bit 0 of the last dword is the column's overflow bit (crossings above the grid).
-//   k_check_mesh      one sweep over the face indices and the vertex coordinates: bit 0 of the flag = an index outside [-nv, nv),
+//   k_check_mesh      (csrc/cross_rule.h, with the rule itself: csrc/inside.hip asks the same of arbitrary query points) one sweep
+//                     over the face indices and the vertex coordinates: bit 0 of the flag = an index outside [-nv, nv),
 //                     bit 1 = a coordinate that is not finite.  The entry's one host wait in front of everything that gathers
 //   k_cross_lanes     one lane per face: lattice coordinates, area, column box, the three edge set-ups and the plane, in registers.
 //                     A face of at most kLaneCols columns (every marching-cubes face) is walked by its lane; a larger one is listed
@@ -22,6 +23,7 @@
 #include <cmath>
 
 #include "wave.h"
+#include "cross_rule.h"
 #include "mesh_index.h"
 #include "pb3d_internal.h"
 
@@ -33,29 +35,10 @@ constexpr int kLaneCols = 16;                       // above it a face's columns
 struct Vol { u32* bits; i64 n0, n1, n2, W; };
 struct Frame { double o[3], vs, depth; int meshify; };
 
-// what a face needs per column: edge e accepts where ex * (j - ly) - ey * (i - lx) is >= 0 (bit e of pos) or < 0
-struct Face {
-    double ex[3], ey[3], lx[3], ly[3];
-    double a0, a1, a2, nx, ny, area;
+// what a face needs per column: the shared record of csrc/cross_rule.h and the face's columns
+struct Face : CrossFace {
     int i0, i1, j0, j1;                             // the column box, inclusive; i1 < i0 or j1 < j0: no column
-    u32 pos;
 };
-
-template <bool VF64, bool I64>
-__global__ __launch_bounds__(256) void k_check_mesh(const void* __restrict__ verts, i64 nv, const void* __restrict__ faces, i64 nf,
-                                                    u32* __restrict__ flag) {
-    u32 bad = 0;
-    const i64 t0 = (i64)blockIdx.x * 256 + threadIdx.x, step = (i64)gridDim.x * 256;
-    for (i64 e = t0; e < 3 * nf; e += step) {
-        const i64 v = load_index<I64>(faces, e);
-        if (v < -nv || v >= nv) bad |= 1u;
-    }
-    for (i64 e = t0; e < 3 * nv; e += step) {
-        const double x = VF64 ? ((const double*)verts)[e] : (double)((const float*)verts)[e];
-        if (!isfinite(x)) bad |= 2u;
-    }
-    if (bad) atomicOr(flag, bad);
-}
 
 template <bool VF64>
 __device__ __forceinline__ void lattice(const void* verts, i64 v, const Frame& fr, double L[3]) {
@@ -67,16 +50,6 @@ __device__ __forceinline__ void lattice(const void* verts, i64 v, const Frame& f
     L[2] = __ddiv_rn(a2 - fr.o[2], fr.vs);
 }
 
-__device__ __forceinline__ void set_edge(Face* f, int e, const double* P, const double* Q, bool up) {
-    const bool flipped = Q[0] < P[0] || (Q[0] == P[0] && Q[1] < P[1]);
-    const double lo0 = flipped ? Q[0] : P[0], lo1 = flipped ? Q[1] : P[1], hi0 = flipped ? P[0] : Q[0], hi1 = flipped ? P[1] : Q[1];
-    f->ex[e] = hi0 - lo0;
-    f->ey[e] = hi1 - lo1;
-    f->lx[e] = lo0;
-    f->ly[e] = lo1;
-    if (up != flipped) f->pos |= 1u << e;
-}
-
 // false: area == 0, the face contributes nothing
 template <bool VF64, bool I64>
 __device__ __forceinline__ bool face_setup(const void* verts, i64 nv, const void* faces, i64 f, const Frame& fr, const Vol& v, Face* o) {
@@ -84,7 +57,7 @@ __device__ __forceinline__ bool face_setup(const void* verts, i64 nv, const void
     lattice<VF64>(verts, wrap(load_index<I64>(faces, 3 * f), nv), fr, A);
     lattice<VF64>(verts, wrap(load_index<I64>(faces, 3 * f + 1), nv), fr, B);
     lattice<VF64>(verts, wrap(load_index<I64>(faces, 3 * f + 2), nv), fr, C);
-    const double area = (B[0] - A[0]) * (C[1] - A[1]) - (B[1] - A[1]) * (C[0] - A[0]);
+    const double area = cross_area(A, B, C);
     if (area == 0.0) return false;
     // clamped in float64 first: the conversions below see values in [0, n - 1] (or an empty range)
     const double ilo = fmax(0.0, ceil(fmin(fmin(A[0], B[0]), C[0]))), ihi = fmin((double)(v.n0 - 1), floor(fmax(fmax(A[0], B[0]), C[0])));
@@ -92,15 +65,8 @@ __device__ __forceinline__ bool face_setup(const void* verts, i64 nv, const void
     const bool some = ilo <= ihi && jlo <= jhi;
     o->i0 = some ? (int)ilo : 0; o->i1 = some ? (int)ihi : -1;
     o->j0 = some ? (int)jlo : 0; o->j1 = some ? (int)jhi : -1;
-    o->pos = 0;
-    const bool up = area > 0.0;
-    set_edge(o, 0, A, B, up);
-    set_edge(o, 1, B, C, up);
-    set_edge(o, 2, C, A, up);
-    o->nx = (B[1] - A[1]) * (C[2] - A[2]) - (B[2] - A[2]) * (C[1] - A[1]);
-    o->ny = (B[2] - A[2]) * (C[0] - A[0]) - (B[0] - A[0]) * (C[2] - A[2]);
-    o->a0 = A[0]; o->a1 = A[1]; o->a2 = A[2];
-    o->area = area;
+    cross_edges(A, B, C, area, o);
+    cross_plane(A, B, C, o);
     return true;
 }
 
@@ -108,15 +74,8 @@ __device__ __forceinline__ bool face_setup(const void* verts, i64 nv, const void
 // k is clamped below and sent to the overflow bit above: no store leaves the column's W dwords
 __device__ __forceinline__ u32 cross_column(const Face& f, int i, int j, const Vol& v) {
     const double x = (double)i, y = (double)j;
-    bool in = true;
-#pragma unroll
-    for (int e = 0; e < 3; ++e) {
-        const double E = f.ex[e] * (y - f.ly[e]) - f.ey[e] * (x - f.lx[e]);
-        in &= ((f.pos >> e) & 1u) ? E >= 0.0 : E < 0.0;
-    }
-    if (!in) return 0;
-    const double z = f.a2 - __ddiv_rn(f.nx * (x - f.a0) + f.ny * (y - f.a1), f.area);
-    const double kz = ceil(z);
+    if (!cross_covers(f, x, y)) return 0;
+    const double kz = ceil(cross_height(f, x, y));
     u32* col = v.bits + ((i64)i * v.n1 + j) * v.W;
     if (kz <= (double)(v.n2 - 1)) {
         const int k = (int)fmax(kz, 0.0);

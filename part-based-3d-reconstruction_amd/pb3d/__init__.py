@@ -39,6 +39,8 @@ from .simplify import compact_mesh, compact_mesh_resident, simplify_mesh, simpli
 from .meshcomp import (keep_mesh_components, keep_mesh_components_resident, mesh_components, mesh_components_resident,  # noqa: F401
                        mesh_topology, mesh_topology_resident, select_faces, select_faces_resident)
 from .voxelize import grid_overlap_counts, grid_overlap_counts_resident, mesh_grid_iou, voxelize_mesh, voxelize_mesh_resident  # noqa: F401
+from .inside import (points_in_mesh, points_in_mesh_last, points_in_mesh_resident, select_points_in_mesh,  # noqa: F401
+                     select_points_in_mesh_resident, signed_point_to_mesh_distances, signed_point_to_mesh_distances_resident)
 from .distance import (close_grid, close_grid_resident, dilate_grid, dilate_grid_resident, distance_transform,  # noqa: F401
                        distance_transform_resident, erode_grid, erode_grid_resident, grid_surface_metrics, grid_surface_metrics_resident,
                        open_grid, open_grid_resident)

@@ -192,6 +192,10 @@ _SIGNATURES = {
                                     vp, i64p],
     "pb3d_voxelize_last": [vp, dblp],
     "pb3d_grid_overlap_resident": [vp, vp, C.c_int, vp, C.c_int, i64, i64p],
+    "pb3d_points_in_mesh_resident": [vp, vp, C.c_int, i64, vp, C.c_int, i64, vp, C.c_int, i64, vp, vp, i64p],
+    "pb3d_points_in_mesh_last": [vp, i64p, dblp],
+    "pb3d_mesh_dist_sign_resident": [vp, vp, vp, i64, vp],
+    "pb3d_flags_not_resident": [vp, vp, i64, vp],
     "pb3d_edt_resident": [vp, vp, C.c_int, i64, i64, i64, C.c_int, C.c_int, vp, vp, i64p],
     "pb3d_edt_distances_resident": [vp, vp, i64, C.c_double, C.c_int, vp],
     "pb3d_edt_apply_resident": [vp, vp, C.c_int, i64, vp, vp, C.c_int, i64, vp],

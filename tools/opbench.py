@@ -1,5 +1,5 @@
 """Device-resident timing of every op of the path (M1..M8 of SURVEY.md 8(d), plus the N1/N2 kernels of the notebook-1 chain) on
-synthetic inputs.  Development/measurement tool: python tools/opbench.py [--size 1024] [--shape WxHxD] [--ops M1,M3,...,N2,overlays,ICP,PLANE,MESHD,CLUSTER,DOWNSAMPLE,SMOOTH,SIMPLIFY,VOXELIZE,EDT,RENDER,ISO,MESHCOMP]; one JSON
+synthetic inputs.  Development/measurement tool: python tools/opbench.py [--size 1024] [--shape WxHxD] [--ops M1,M3,...,N2,overlays,ICP,PLANE,MESHD,CLUSTER,DOWNSAMPLE,SMOOTH,SIMPLIFY,VOXELIZE,EDT,RENDER,ISO,MESHCOMP,INSIDE]; one JSON
 line per op.  Pricing: `alg_B_per_voxel` is SURVEY 8(d)'s algorithmic figure for the sweeps that are EXECUTED (a folded 0-degree step
 moves nothing and is not priced); ops whose intermediates are not bytes (the bit-sliced chains) also carry `moved_B_per_voxel`, the
 bytes that cross the HBM by design, and their `frac_of_8TBs` is computed from THAT (never from bytes that are not moved)."""
@@ -280,6 +280,8 @@ def main():
         mesh_target(a.reps, res)
     if "MESHCOMP" in ops:
         mesh_components(a.reps, res)
+    if "INSIDE" in ops:
+        inside(a.reps, res)
     if "overlays" in ops:
         overlays(a.reps, res)
     if d_col is not None:
@@ -1420,6 +1422,170 @@ def mesh_target(reps, res):
         print(json.dumps(r), flush=True)
         res.append(r)
     for b in (d_g, d_tp, d_tc, dv, df, dn, dc, d_nn):
+        b.free()
+
+
+def inside(reps, res):
+    """INSIDE, points_in_mesh (csrc/inside.hip) against the stride-1 mesh of the stored Taj grid (float32 vertices, int32 faces, resident,
+    meshify's frame), every call whole: index build and host waits included, by device events, the variants of a row timed in turn, rep
+    by rep, in the same run (median and min / max of reps after one warm-up of each).
+    INSIDE/lattice: every sample point of the grid (the points voxelize_mesh decides), mapped into the mesh's frame, in the grid's order;
+      the flags must equal the grid's occupancy or the op stops.  In that frame the rays run along the grid's first axis, so a wavefront
+      of consecutive queries holds 64 columns: timed in input order and in cell order (knob inside_order), each with the call's own
+      index / query split (knob inside_timing), beside the yardstick voxelize_mesh of the same mesh into the same grid.
+    INSIDE/lattice_a2: the same with the mesh mapped into the lattice frame instead, rays along a2 as the voxelization's: a wavefront
+      shares one column, and the flags must equal voxelize_mesh's bytes.
+    INSIDE/points: the grid's own points (the queries of MESHD) -- containment in both orders beside point_to_mesh_distances and the
+      signed distance on the same queries.
+    INSIDE/sfm20k: the 20 k SfM sample in the mesh's frame -- containment with its stats, the unsigned and the signed distance.
+    INSIDE/order: shuffled samples of the grid's points from 20 k to all of them, input order against cell order: where the query
+      binning starts to pay.
+    Set-ups recomputed from the corner rows against the table of finished set-ups (knob inside_table) beside every lattice row."""
+    from pb3d.eval_helpers import point_to_mesh_distances_resident
+    lib, L = pb3d._lib.load(), pb3d._lib
+    taj = np.load(os.path.join(ROOT, "tests", "golden", "stored_Taj_voxel_grid.npz"))["voxel_grid"]
+    shape = taj.shape[:3]
+    nvox = int(np.prod(shape))
+    occ = np.any(taj > 0, axis=-1)
+    D = np.float32(shape[2])
+    d_g = dev.from_numpy(taj)
+    (dv, df, dn, dc), (nv, nf) = dev.meshify(d_g, taj.shape, stride=1, download=False)
+    for b in (d_g, dn, dc):
+        b.free()
+    verts = dv.download((nv, 3), np.float32)
+    ijk = np.indices(shape, dtype=np.float32).reshape(3, -1).T
+    q_mesh = np.ascontiguousarray(np.stack([ijk[:, 2], ijk[:, 1], D - ijk[:, 0]], axis=1))      # voxel (i, j, k) in meshify's frame
+    d_lattice, d_ijk = dev.from_numpy(q_mesh), dev.from_numpy(np.ascontiguousarray(ijk))
+    d_vl = dev.from_numpy(np.ascontiguousarray(np.stack([D - verts[:, 2], verts[:, 1], verts[:, 0]], axis=1)))   # the mesh in the lattice frame
+    pts = q_mesh[occ.reshape(-1)]
+    d_pts = dev.from_numpy(pts)
+    meta = json.load(open(os.path.join(ROOT, "tests", "golden", "inter_ref.json")))
+    scale = float.fromhex(meta["taj_transform"]["scale"])
+    offset = np.array([float.fromhex(v) for v in meta["taj_transform"]["offset"]])
+    sfm = np.load(os.path.join(ROOT, "tests", "golden", "inter_sfm20k.npz"))["sfm"]
+    sfm_vox = ((sfm - offset) / scale)[:, ::-1]                                                   # (a2, a1, a0)
+    sfm_mesh = np.ascontiguousarray(np.stack([sfm_vox[:, 0], sfm_vox[:, 1], float(D) - sfm_vox[:, 2]], axis=1))
+    d_sfm = dev.from_numpy(sfm_mesh)
+    d_in, d_vox = dev.DeviceBuffer(nvox), dev.DeviceBuffer(nvox)
+
+    def contain(d_q, n, f64, d_verts=dv, order=0, table=0, **kw):
+        def run():
+            L.set_tuning("inside_order", order)
+            L.set_tuning("inside_table", table)
+            try:
+                return pb3d.points_in_mesh_resident(d_q, n, d_verts, nv, df, nf, f64, False, False, out=d_in, **kw)
+            finally:
+                L.set_tuning("inside_order", 0)
+                L.set_tuning("inside_table", 0)
+        return run
+
+    def once(fn):
+        def run():
+            out = fn()
+            for b in (out if isinstance(out, tuple) else (out,)):
+                if isinstance(b, dev.DeviceBuffer) and b is not d_in and b is not d_vox:
+                    b.free()
+        return timeit(run, 1, warm=0)
+
+    def stats(t):
+        return {"ms": round(float(np.median(t)), 4), "min_max_ms": [round(min(t), 4), round(max(t), 4)]}
+
+    def in_turn(fns):
+        """every variant once as a warm-up, then reps rounds of all of them in turn"""
+        for fn in fns.values():
+            once(fn)
+        t = {k: [] for k in fns}
+        for _ in range(reps):
+            for k, fn in fns.items():
+                t[k].append(once(fn))
+        return t
+
+    def split(fn):
+        """(index ms, query ms) of the call's own events: the best of reps after one warm-up"""
+        L.set_tuning("inside_timing", 1)
+        try:
+            got = []
+            for _ in range(reps + 1):
+                fn()
+                got.append(pb3d.points_in_mesh_last(timed=True))
+        finally:
+            L.set_tuning("inside_timing", 0)
+        return got[-1][:3], min(g[3][0] for g in got[1:]), min(g[3][1] for g in got[1:])
+
+    base = {"grid_shape": list(shape), "nverts": int(nv), "nfaces": int(nf), "reps": reps}
+    rows = []
+
+    # ---- 1: the grid's sample points; equality first
+    _, st = contain(d_lattice, nvox, False, return_stats=True)()
+    got = d_in.download(shape)
+    assert np.array_equal(got != 0, occ), "points_in_mesh at the grid's sample points differs from the grid's occupancy"
+    contain(d_lattice, nvox, False, order=1)()
+    assert np.array_equal(d_in.download(shape), got), "the query order changed a byte"
+    pb3d.voxelize_mesh_resident(dv, nv, df, nf, shape, frame="meshify", out=d_vox)
+    contain(d_ijk, nvox, False, d_verts=d_vl)()
+    assert np.array_equal(d_in.download(shape), d_vox.download(shape)), "lattice frame: points_in_mesh differs from voxelize_mesh"
+    for order in (0, 1):
+        contain(d_lattice, nvox, False, order=order, table=1)()
+        assert np.array_equal(d_in.download(shape), got), "the set-up table changed a byte"
+    fns = {"input_order": contain(d_lattice, nvox, False), "cell_order": contain(d_lattice, nvox, False, order=1),
+           "input_order_table": contain(d_lattice, nvox, False, table=1), "cell_order_table": contain(d_lattice, nvox, False, order=1, table=1),
+           "lattice_frame": contain(d_ijk, nvox, False, d_verts=d_vl), "lattice_frame_cell_order": contain(d_ijk, nvox, False, d_verts=d_vl, order=1),
+           "lattice_frame_table": contain(d_ijk, nvox, False, d_verts=d_vl, table=1),
+           "voxelize": lambda: pb3d.voxelize_mesh_resident(dv, nv, df, nf, shape, frame="meshify", out=d_vox)}
+    t = in_turn(fns)
+    for key, op, name, d_q, d_verts, order, table in (
+            ("input_order", "INSIDE/lattice", "every sample point of the grid, mesh frame, input order", d_lattice, dv, 0, 0),
+            ("cell_order", "INSIDE/lattice", "every sample point of the grid, mesh frame, cell order (inside_order = 1)", d_lattice, dv, 1, 0),
+            ("input_order_table", "INSIDE/lattice", "every sample point of the grid, mesh frame, input order, set-up table (inside_table = 1)",
+             d_lattice, dv, 0, 1),
+            ("cell_order_table", "INSIDE/lattice", "every sample point of the grid, mesh frame, cell order, set-up table", d_lattice, dv, 1, 1),
+            ("lattice_frame", "INSIDE/lattice_a2", "every sample point of the grid, lattice frame (rays along a2), input order", d_ijk, d_vl, 0, 0),
+            ("lattice_frame_cell_order", "INSIDE/lattice_a2", "every sample point of the grid, lattice frame, cell order", d_ijk, d_vl, 1, 0),
+            ("lattice_frame_table", "INSIDE/lattice_a2", "every sample point of the grid, lattice frame, input order, set-up table", d_ijk, d_vl, 0, 1)):
+        (cells, entries, halvings), ms_index, ms_query = split(contain(d_q, nvox, False, d_verts=d_verts, order=order, table=table))
+        rows.append(dict(base, op=op, name="points_in_mesh: " + name, queries=nvox, **stats(t[key]), Mquery_s=round(nvox / float(np.median(t[key])) / 1e3, 1),
+                         index_ms=round(ms_index, 4), query_ms=round(ms_query, 4), index_share=round(ms_index / (ms_index + ms_query), 4),
+                         cells=list(cells), entries=entries, entries_per_face=round(entries / nf, 3), halvings=halvings,
+                         ratio_to_voxelize=round(float(np.median(t[key])) / float(np.median(t["voxelize"])), 1),
+                         equals_occupancy=True, **(st if key == "input_order" else {})))
+    rows.append(dict(base, op="INSIDE/lattice", name="yardstick: voxelize_mesh of the same mesh into the same grid", **stats(t["voxelize"])))
+
+    # ---- 2 and 3: the grid's own points and the SfM sample; containment, distance, signed distance
+    for tag, d_q, n, f64, host in (("points", d_pts, len(pts), False, pts), ("sfm20k", d_sfm, len(sfm_mesh), True, sfm_mesh)):
+        _, st = contain(d_q, n, f64, return_stats=True)()
+        fns = {"input_order": contain(d_q, n, f64), "cell_order": contain(d_q, n, f64, order=1), "table": contain(d_q, n, f64, table=1),
+               "dist": lambda d_q=d_q, n=n, f64=f64: point_to_mesh_distances_resident(d_q, n, dv, nv, df, nf, f64, False, False),
+               "signed": lambda d_q=d_q, n=n, f64=f64: pb3d.signed_point_to_mesh_distances_resident(d_q, n, dv, nv, df, nf, f64, False, False)}
+        t = in_turn(fns)
+        (cells, entries, halvings), ms_index, ms_query = split(contain(d_q, n, f64))
+        med = {k: float(np.median(v)) for k, v in t.items()}
+        what = "the grid's own points (MESHD's queries)" if tag == "points" else "the 20 k SfM sample in the mesh's frame"
+        rows.append(dict(base, op="INSIDE/" + tag, name=f"points_in_mesh: {what}, input order", queries=int(n), **stats(t["input_order"]),
+                         Mquery_s=round(n / med["input_order"] / 1e3, 1), index_ms=round(ms_index, 4), query_ms=round(ms_query, 4),
+                         index_share=round(ms_index / (ms_index + ms_query), 4), ratio_to_unsigned_distance=round(med["input_order"] / med["dist"], 4),
+                         fraction_outside=round(1.0 - st["inside"] / n, 4), **st))
+        rows.append(dict(base, op="INSIDE/" + tag, name=f"points_in_mesh: {what}, cell order (inside_order = 1)", queries=int(n),
+                         **stats(t["cell_order"]), ratio_to_input_order=round(med["cell_order"] / med["input_order"], 3)))
+        rows.append(dict(base, op="INSIDE/" + tag, name=f"points_in_mesh: {what}, input order, set-up table (inside_table = 1)", queries=int(n),
+                         **stats(t["table"]), ratio_to_input_order=round(med["table"] / med["input_order"], 3)))
+        rows.append(dict(base, op="INSIDE/" + tag, name=f"yardstick: point_to_mesh_distances_resident, {what}", queries=int(n), **stats(t["dist"])))
+        rows.append(dict(base, op="INSIDE/" + tag, name=f"signed_point_to_mesh_distances_resident, {what}", queries=int(n), **stats(t["signed"]),
+                         ratio_to_unsigned_distance=round(med["signed"] / med["dist"], 4)))
+    # ---- where the cell order starts to pay: shuffled samples of the grid's points (a cloud's order says nothing about its cells)
+    rng = np.random.default_rng(0)
+    for n in (20000, 100000, 300000, 1000000, 3000000, len(pts)):
+        d_s = dev.from_numpy(pts[rng.permutation(len(pts))[:n]])
+        t = in_turn({"input_order": contain(d_s, n, False), "cell_order": contain(d_s, n, False, order=1)})
+        med = {k: float(np.median(v)) for k, v in t.items()}
+        rows.append(dict(base, op="INSIDE/order", name="points_in_mesh: a shuffled sample of the grid's points, input order against cell order",
+                         queries=int(n), input_order_ms=round(med["input_order"], 4), cell_order_ms=round(med["cell_order"], 4),
+                         cell_over_input=round(med["cell_order"] / med["input_order"], 3),
+                         min_max_ms={k: [round(min(v), 4), round(max(v), 4)] for k, v in t.items()}))
+        d_s.free()
+    for r in rows:
+        print(json.dumps(r), flush=True)
+        res.append(r)
+    for b in (dv, df, d_lattice, d_ijk, d_vl, d_pts, d_sfm, d_in, d_vox):
         b.free()
 
 
