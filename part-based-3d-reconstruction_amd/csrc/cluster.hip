@@ -188,28 +188,6 @@ int check_args(const char* who, const void* d_pts, i64 n, double eps) {
     return PB3D_OK;
 }
 
-// the passes' time stamps (knob "cluster_timing"): six events, created per call, read after one more host wait
-struct Stamps {
-    bool on;
-    int k;
-    hipEvent_t ev[6];
-    int mark(pb3d_ctx* ctx) {
-        if (!on) return PB3D_OK;
-        PB3D_HIP(hipEventCreate(&ev[k]));
-        PB3D_HIP(hipEventRecord(ev[k], ctx->stream));
-        ++k;
-        return PB3D_OK;
-    }
-    int finish(pb3d_ctx* ctx) {
-        if (!on) return PB3D_OK;
-        PB3D_TRY(pb3d_stream_sync(ctx));
-        for (int i = 0; i + 1 < k; ++i) PB3D_HIP(hipEventElapsedTime(&ctx->cluster_last.ms[i], ev[i], ev[i + 1]));
-        ctx->cluster_last.timed = k == 6;
-        return PB3D_OK;
-    }
-    ~Stamps() { for (int i = 0; i < k; ++i) (void)hipEventDestroy(ev[i]); }
-};
-
 }  // namespace
 
 extern "C" {
@@ -239,7 +217,7 @@ int pb3d_cluster_points_resident(pb3d_ctx* ctx, const void* d_pts, int pts_f64, 
     PB3D_REQUIRE(ctx != nullptr, "pb3d_cluster_points: null context");
     *nclusters = 0;
     if (n == 0) return PB3D_OK;
-    Stamps t = {ctx->tune_cluster_timing != 0, 0, {}};
+    pb3d_stamps<6> t = {ctx->tune_cluster_timing != 0, 0, {}};       // knob "cluster_timing"
     Index ix;
     const u32* order;
     void *parent, *flags, *ranks;
@@ -271,7 +249,7 @@ int pb3d_cluster_points_resident(pb3d_ctx* ctx, const void* d_pts, int pts_f64, 
                        (unsigned long long*)d_sizes);
     PB3D_CHECK_LAUNCH();
     PB3D_TRY(t.mark(ctx));
-    PB3D_TRY(t.finish(ctx));
+    PB3D_TRY(t.finish(ctx, ctx->cluster_last.ms, &ctx->cluster_last.timed));
     *nclusters = nc;
     return PB3D_OK;
 }

@@ -3,8 +3,10 @@
 // point gets the bytes of the voxel there.  include/pb3d.h states the rule ("mesh -> grid", FACE steps 1, 3 and 4); the box of step 2
 // stays with each user, since one clamps integer columns to a grid and the other compares a query with the corners.
 // Every product, sum, difference and quotient is one rounded float64 operation (the Makefile passes -ffp-contract=off).
-// Also here: k_check_mesh, the sweep both entries run, and wait for, in front of everything that gathers through the face indices.
+// Also here: k_check_mesh, the sweep both entries run, and wait for, in front of everything that gathers through the face indices,
+// with its host side: check_mesh, and report_mesh_flag for csrc/render.hip, whose set-up kernel raises the same flag.
 #pragma once
+#include <algorithm>
 #include <cmath>
 
 #include "mesh_index.h"
@@ -27,6 +29,33 @@ __global__ __launch_bounds__(256) void k_check_mesh(const void* __restrict__ ver
         if (!isfinite(x)) bad |= 2u;
     }
     if (bad) atomicOr(flag, bad);
+}
+
+// what a raised flag means to the caller of entry `what`: PB3D_EINDEX for bit 0, else PB3D_EINVAL for bit 1
+inline int report_mesh_flag(const char* what, u32 bad, i64 nv) {
+    if (bad & 1u) {
+        pb3d_set_error("%s: index out of bounds for %lld entries", what, (long long)nv);
+        return PB3D_EINDEX;
+    }
+    PB3D_REQUIRE(!(bad & 2u), "%s: a vertex coordinate is not finite", what);
+    return PB3D_OK;
+}
+
+// the sweep over a mesh with a vertex or a face, the flag cleared first, and its verdict: one host wait.  (A template only so that a
+// file which includes this header for the rule alone carries no copy of the four kernels)
+template <class = void>
+int check_mesh(pb3d_ctx* ctx, const char* what, const void* d_verts, int verts_f64, i64 nv, const void* d_faces, int faces_i64, i64 nf,
+                      u32* d_flag) {
+    PB3D_HIP(hipMemsetAsync(d_flag, 0, sizeof(u32), ctx->stream));
+    const unsigned nb = pb3d_stream_blocks(ctx, 3 * std::max<i64>(nv, nf), 256, 8);
+    with_mesh_types(verts_f64, faces_i64, [&](auto V, auto I) {
+        hipLaunchKernelGGL((k_check_mesh<decltype(V)::value, decltype(I)::value>), dim3(nb), dim3(256), 0, ctx->stream, d_verts, nv, d_faces, nf,
+                           d_flag);
+    });
+    PB3D_CHECK_LAUNCH();
+    u32 bad;
+    PB3D_TRY(pb3d_read_back(ctx, &bad, d_flag, sizeof(bad)));
+    return report_mesh_flag(what, bad, nv);
 }
 
 // what a face needs per ray (x, y): edge e accepts where ex * (y - ly) - ey * (x - lx) is >= 0 (bit e of pos) or < 0

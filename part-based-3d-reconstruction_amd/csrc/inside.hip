@@ -4,25 +4,18 @@
 // replaced by the query's (q0, q1): at a lattice point the byte is the voxel's.  What differs is everything around the rule: the
 // queries are scattered, so nothing is rasterised and the faces need an index.
 //
-// Index: a 2-D cell grid over the exact (a0, a1) box of ALL vertices -- the Grid of csrc/ring_walk.h with one cell along a2, so cell_of,
-// cell_index and make_grid (sized from nf, two faces per cell) are the searches' own.  A face with area != 0 is listed in every cell
-// of cell_of(min corner) .. cell_of(max corner) per axis: count pass, the exclusive scan of csrc/points.hip, scatter of face ids (order
-// within a cell is free: integer atomics on the cursors).  cell_of is monotone, so a face whose projected box holds (q0, q1) is listed
-// in the query's cell.  As in csrc/meshdist.hip, while the (cell, face) entries exceed kEntryCap = 8 per face and the grid has more
-// than one cell, the cells per axis are halved and the entries recounted.  In 2-D one wall among small faces cannot break the cap (it
-// adds one entry per cell, nf / 2 in all); a mesh whose typical face is several cells wide does.  The stride-1 mesh of the stored Taj
+// Index: csrc/face_index.hip's (the passes are described there), the one csrc/meshdist.hip searches, asked for a 2-D cell grid over the
+// exact (a0, a1) box of ALL vertices -- one cell along a2 -- and for the faces with area == 0 to be listed nowhere and counted.
+// cell_of is monotone, so a face whose projected box holds (q0, q1) is listed in the query's cell.  The stride-1 mesh of the stored Taj
 // grid (1 518 156 faces, 1 112 342 of them flat in projection and listed nowhere) makes 2.78 entries per face in 1167 x 651 cells.
-//   k_inside_corners   the corners of every face, widened, into an nf x 9 float64 table (one indirection per candidate whatever the
-//                      mesh's dtypes are); counts the faces with area == 0
-//   k_inside_entries   the entry total of a grid, without touching a cell
-//   k_inside_bin       counts per cell, then the scatter
 //   k_inside_query     one lane per query.  Outside the vertices' (a0, a1) box, or with a NaN coordinate: outside, no walk.  Otherwise
 //                      the list of the query's one cell: per candidate the projected box from six of the nine corner values, then the
 //                      three edge set-ups and tests, and only for a covering face the plane and its one division.
 //                      below and total live in registers; one byte and, if asked, two int32 are written.  NO atomics: with stats
 //                      each workgroup leaves three partial counts and k_inside_totals adds them, so the result is a function of the
 //                      input alone.  60-62 VGPRs (46-48 in the table form below), no scratch, no spills
-//   k_inside_setup     knob "inside_table" = 1 only: a 184-byte row of finished set-ups per face for the query to read
+//   k_inside_setup     knob "inside_table" = 1 only: a 184-byte row of finished set-ups per face, from the index's corner table, for
+//                      the query to read
 // Two choices, both measured on that mesh (profiles/inside_opbench.jsonl, whole calls, variants in turn, medians of 5) and both left
 // as knobs that change no byte:
 //   * The set-up is recomputed per candidate from the 72-byte corner row.  Reading it from the table instead (some twenty operations
@@ -38,7 +31,6 @@
 //   k_flags_not        out = flags == 0: the bytes pb3d_points_select_resident takes to keep the points outside
 // Host waits per call: the index / finiteness check, the box, one per count of the entries (1 + the number of halvings), one more for
 // stats, one more under knob "inside_timing".
-#include <algorithm>
 #include <cmath>
 
 #include "wave.h"
@@ -49,58 +41,6 @@
 namespace {
 
 constexpr i64 kMaxElems = (1ll << 31) - 1;
-constexpr i64 kEntryCap = 8;            // (cell, face) entries per face the index accepts before it coarsens the grid
-
-template <bool VF64, bool I64>
-__global__ __launch_bounds__(256) void k_inside_corners(const void* __restrict__ verts, i64 nv, const void* __restrict__ faces, i64 nf,
-                                                        double* __restrict__ tri, u64* __restrict__ flat) {
-    u64 n = 0;
-    for (i64 f = (i64)blockIdx.x * 256 + threadIdx.x; f < nf; f += (i64)gridDim.x * 256) {
-        double t[9];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) pb3d_load3<VF64>(verts, wrap(load_index<I64>(faces, 3 * f + c), nv), t + 3 * c);
-#pragma unroll
-        for (int k = 0; k < 9; ++k) tri[9 * f + k] = t[k];
-        n += cross_area(t, t + 3, t + 6) == 0.0;
-    }
-    group_add(n, flat);
-}
-
-// the cells a face is listed in; false: area == 0, listed nowhere
-__device__ __forceinline__ bool face_cells(const Grid& g, const double* __restrict__ t, int lo[2], int hi[2]) {
-    if (cross_area(t, t + 3, t + 6) == 0.0) return false;
-#pragma unroll
-    for (int a = 0; a < 2; ++a) {
-        lo[a] = cell_of(g, a, fmin(fmin(t[a], t[3 + a]), t[6 + a]));
-        hi[a] = cell_of(g, a, fmax(fmax(t[a], t[3 + a]), t[6 + a]));
-    }
-    return true;
-}
-
-__global__ __launch_bounds__(256) void k_inside_entries(const double* __restrict__ tri, i64 nf, Grid g, u64* __restrict__ total) {
-    u64 n = 0;
-    for (i64 f = (i64)blockIdx.x * 256 + threadIdx.x; f < nf; f += (i64)gridDim.x * 256) {
-        int lo[2], hi[2];
-        if (face_cells(g, tri + 9 * f, lo, hi)) n += (u64)(hi[0] - lo[0] + 1) * (u64)(hi[1] - lo[1] + 1);
-    }
-    group_add(n, total);
-}
-
-// FILL false: counts[cell] += 1 per entry;  FILL true: ids[start[cell] + cursor[cell]++] = face (cursor: zeroed per-cell counters)
-template <bool FILL>
-__global__ __launch_bounds__(256) void k_inside_bin(const double* __restrict__ tri, i64 nf, Grid g, u32* __restrict__ counts,
-                                                    const i64* __restrict__ start, int* __restrict__ ids) {
-    for (i64 f = (i64)blockIdx.x * 256 + threadIdx.x; f < nf; f += (i64)gridDim.x * 256) {
-        int lo[2], hi[2];
-        if (!face_cells(g, tri + 9 * f, lo, hi)) continue;
-        for (int i = lo[0]; i <= hi[0]; ++i)
-            for (int j = lo[1]; j <= hi[1]; ++j) {
-                const i64 c = cell_index(g, i, j, 0);
-                if (FILL) ids[start[c] + atomicAdd(&counts[c], 1u)] = (int)f;
-                else atomicAdd(&counts[c], 1u);
-            }
-    }
-}
 
 // knob "inside_table" = 1: the finished set-up of every face with an area, kSetupRow doubles a face -- the projected box (min0, max0,
 // min1, max1), ex, ey, lx, ly, pos, then a0, a1, a2, nx, ny, area -- by the same functions, so the query reads the very doubles it
@@ -188,7 +128,7 @@ __global__ __launch_bounds__(256) void k_inside_query(const void* __restrict__ q
     }
 }
 
-// one workgroup: stats[0], [1], [3] = the sums of the nb workgroups' partial counts (stats[2], the flat faces, is k_inside_corners')
+// one workgroup: stats[0], [1], [3] = the sums of the nb workgroups' partial counts (stats[2], the flat faces, is the index build's)
 __global__ __launch_bounds__(1024) void k_inside_totals(const u32* __restrict__ partials, i64 nb, u64* __restrict__ stats) {
     __shared__ u64 w0[16], w1[16], w2[16];
     u64 a = 0, b = 0, c = 0;
@@ -210,105 +150,17 @@ __global__ __launch_bounds__(256) void k_flags_not(const u8* flags, i64 n, u8* o
     if (i < n) out[i] = flags[i] == 0;
 }
 
-// halve the cells of the two axes (the box stays)
-Grid coarsen(Grid g) {
-    g.ncells = 1;
-    for (int a = 0; a < 2; ++a) {
-        g.n[a] = (g.n[a] + 1) / 2;
-        const double ext = g.hi[a] - g.lo[a];
-        g.inv[a] = g.n[a] > 1 ? (double)g.n[a] / ext : 0.0;
-        g.h[a] = g.n[a] > 1 ? ext / (double)g.n[a] : 0.0;
-        g.ncells *= g.n[a];
-    }
-    return g;
-}
-
-// the passes' time stamps (knob "inside_timing"): three events, created per call, read after one more host wait
-struct Stamps {
-    bool on;
-    int k;
-    hipEvent_t ev[3];
-    int mark(pb3d_ctx* ctx) {
-        if (!on) return PB3D_OK;
-        PB3D_HIP(hipEventCreate(&ev[k]));
-        PB3D_HIP(hipEventRecord(ev[k], ctx->stream));
-        ++k;
-        return PB3D_OK;
-    }
-    int finish(pb3d_ctx* ctx) {
-        if (!on) return PB3D_OK;
-        PB3D_TRY(pb3d_stream_sync(ctx));
-        for (int i = 0; i + 1 < k; ++i) PB3D_HIP(hipEventElapsedTime(&ctx->inside_last.ms[i], ev[i], ev[i + 1]));
-        ctx->inside_last.timed = k == 3;
-        return PB3D_OK;
-    }
-    ~Stamps() { for (int i = 0; i < k; ++i) (void)hipEventDestroy(ev[i]); }
-};
-
-struct FaceIndex { Grid g; const i64* starts; const int* ids; const double* tri; const double* setup; };     // setup: null unless inside_table
-
-// mesh checked; nv, nf >= 1.  rb: the read-back slot (the box at [0, 6), the entry total at [6]); d_flat: where the flat faces are counted
-int build_index(pb3d_ctx* ctx, const void* d_verts, int verts_f64, i64 nv, const void* d_faces, int faces_i64, i64 nf, void* rb, u64* d_flat,
-                FaceIndex* ix) {
-    void *tri, *cnt, *st, *ids;
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_INSIDE_CORNERS, (size_t)nf * 9 * sizeof(double), &tri));
-    const unsigned nb = pb3d_stream_blocks(ctx, nf, 256, 8);
-    with_mesh_types(verts_f64, faces_i64, [&](auto V, auto I) {
-        hipLaunchKernelGGL((k_inside_corners<decltype(V)::value, decltype(I)::value>), dim3(nb), dim3(256), 0, ctx->stream, d_verts, nv, d_faces, nf,
-                           (double*)tri, d_flat);
-    });
-    PB3D_CHECK_LAUNCH();
-    double b[6];
-    PB3D_TRY(pb3d_points_box(ctx, d_verts, verts_f64, nv, PB3D_SLOT_INSIDE_READBACK, b));
-    const double b2[6] = {b[0], b[1], 0.0, b[3], b[4], 0.0};        // one cell along a2
-    Grid g = make_grid(b2, nf);
-    u64* d_total = (u64*)rb + 6;
-    u64 total = 0;
-    i64 coarsenings = 0;
-    for (;;) {
-        PB3D_HIP(hipMemsetAsync(d_total, 0, sizeof(u64), ctx->stream));
-        hipLaunchKernelGGL(k_inside_entries, dim3(nb), dim3(256), 0, ctx->stream, (const double*)tri, nf, g, d_total);
-        PB3D_CHECK_LAUNCH();
-        PB3D_TRY(pb3d_read_back(ctx, &total, d_total, sizeof(total)));
-        if (total <= (u64)(kEntryCap * nf) || g.ncells == 1) break;
-        g = coarsen(g);
-        ++coarsenings;
-    }
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_INSIDE_COUNTS, (size_t)g.ncells * sizeof(u32), &cnt));
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_INSIDE_STARTS, (size_t)(g.ncells + 1) * sizeof(i64), &st));
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_INSIDE_IDS, (size_t)total * sizeof(int), &ids));
-    PB3D_HIP(hipMemsetAsync(cnt, 0, (size_t)g.ncells * sizeof(u32), ctx->stream));
-    hipLaunchKernelGGL(k_inside_bin<false>, dim3(nb), dim3(256), 0, ctx->stream, (const double*)tri, nf, g, (u32*)cnt, (const i64*)nullptr,
-                       (int*)nullptr);
-    PB3D_CHECK_LAUNCH();
-    PB3D_TRY(pb3d_scan_counts(ctx, (const u32*)cnt, g.ncells, (i64*)st, PB3D_SLOT_INSIDE_SCAN_LOCAL, PB3D_SLOT_INSIDE_SCAN_SEGS));
-    PB3D_HIP(hipMemsetAsync(cnt, 0, (size_t)g.ncells * sizeof(u32), ctx->stream));      // the scatter's cursors
-    hipLaunchKernelGGL(k_inside_bin<true>, dim3(nb), dim3(256), 0, ctx->stream, (const double*)tri, nf, g, (u32*)cnt, (const i64*)st, (int*)ids);
-    PB3D_CHECK_LAUNCH();
-    void* setup = nullptr;
-    if (ctx->tune_inside_table) {
-        PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_INSIDE_SETUP, (size_t)nf * kSetupRow * sizeof(double), &setup));
-        hipLaunchKernelGGL(k_inside_setup, dim3(nb), dim3(256), 0, ctx->stream, (const double*)tri, nf, (double*)setup);
-        PB3D_CHECK_LAUNCH();
-    }
-    *ix = {g, (const i64*)st, (const int*)ids, (const double*)tri, (const double*)setup};
-    ctx->inside_last.info[0] = g.n[0];
-    ctx->inside_last.info[1] = g.n[1];
-    ctx->inside_last.info[2] = (i64)total;
-    ctx->inside_last.info[3] = coarsenings;
-    return PB3D_OK;
-}
-
+// setup: null unless inside_table
 template <bool QF64, bool ORDERED>
-void launch_query(pb3d_ctx* ctx, unsigned nb, const void* d_P, i64 nP, const u32* order, const FaceIndex& ix, u8* d_inside, int* d_counts,
-                  u32* partials) {
+void launch_query(pb3d_ctx* ctx, unsigned nb, const void* d_P, i64 nP, const u32* order, const pb3d_face_index& ix, const double* setup,
+                  u8* d_inside, int* d_counts, u32* partials) {
     auto go = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(nb), dim3(256), 0, ctx->stream, d_P, nP, order, ix.g, ix.starts, ix.ids, ix.tri, ix.setup, d_inside, d_counts,
+        hipLaunchKernelGGL(kernel, dim3(nb), dim3(256), 0, ctx->stream, d_P, nP, order, ix.g, ix.starts, ix.ids, ix.tri, setup, d_inside, d_counts,
                            partials);
     };
-    if (partials && ix.setup) go(k_inside_query<QF64, ORDERED, true, true>);
+    if (partials && setup) go(k_inside_query<QF64, ORDERED, true, true>);
     else if (partials) go(k_inside_query<QF64, ORDERED, true, false>);
-    else if (ix.setup) go(k_inside_query<QF64, ORDERED, false, true>);
+    else if (setup) go(k_inside_query<QF64, ORDERED, false, true>);
     else go(k_inside_query<QF64, ORDERED, false, false>);
 }
 
@@ -328,23 +180,7 @@ int pb3d_points_in_mesh_resident(pb3d_ctx* ctx, const void* d_P, int p_f64, int6
     PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_INSIDE_READBACK, 8 * sizeof(u64), &rb));
     PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_INSIDE_STATS, 4 * sizeof(u64), &sv));
     u64* d_stats = (u64*)sv;
-    if (nv > 0 || nf > 0) {
-        u32* d_flag = (u32*)((u64*)rb + 7);
-        PB3D_HIP(hipMemsetAsync(d_flag, 0, sizeof(u32), ctx->stream));
-        const unsigned nb = pb3d_stream_blocks(ctx, 3 * std::max<i64>(nv, nf), 256, 8);
-        with_mesh_types(verts_f64, faces_i64, [&](auto V, auto I) {
-            hipLaunchKernelGGL((k_check_mesh<decltype(V)::value, decltype(I)::value>), dim3(nb), dim3(256), 0, ctx->stream, d_verts, (i64)nv, d_faces,
-                               (i64)nf, d_flag);
-        });
-        PB3D_CHECK_LAUNCH();
-        u32 bad;
-        PB3D_TRY(pb3d_read_back(ctx, &bad, d_flag, sizeof(bad)));
-        if (bad & 1u) {
-            pb3d_set_error("pb3d_points_in_mesh: index out of bounds for %lld entries", (long long)nv);
-            return PB3D_EINDEX;
-        }
-        PB3D_REQUIRE(!(bad & 2u), "pb3d_points_in_mesh: a vertex coordinate is not finite");
-    }
+    if (nv > 0 || nf > 0) PB3D_TRY(check_mesh(ctx, "pb3d_points_in_mesh", d_verts, verts_f64, nv, d_faces, faces_i64, nf, (u32*)((u64*)rb + 7)));
     if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0;
     if (nP == 0) return PB3D_OK;
     ctx->inside_last = {true, false, {0.0f, 0.0f}, {0, 0, 0, 0}};
@@ -355,11 +191,24 @@ int pb3d_points_in_mesh_resident(pb3d_ctx* ctx, const void* d_P, int p_f64, int6
         return PB3D_OK;
     }
 
-    Stamps t = {ctx->tune_inside_timing != 0, 0, {}};
+    pb3d_stamps<3> t = {ctx->tune_inside_timing != 0, 0, {}};       // knob "inside_timing"
     PB3D_TRY(t.mark(ctx));
     PB3D_HIP(hipMemsetAsync(d_stats, 0, 4 * sizeof(u64), ctx->stream));
-    FaceIndex ix;
-    PB3D_TRY(build_index(ctx, d_verts, verts_f64, nv, d_faces, faces_i64, nf, rb, d_stats + 2, &ix));
+    // the index over (a0, a1), flat faces left out and counted into stats[2]; the mesh is checked, so its box is finite
+    const pb3d_face_index_slots slots = {PB3D_SLOT_INSIDE_CORNERS, PB3D_SLOT_INSIDE_READBACK, PB3D_SLOT_INSIDE_COUNTS, PB3D_SLOT_INSIDE_STARTS,
+                                         PB3D_SLOT_INSIDE_IDS, PB3D_SLOT_INSIDE_SCAN_LOCAL, PB3D_SLOT_INSIDE_SCAN_SEGS};
+    pb3d_face_index ix;
+    PB3D_TRY(pb3d_face_index_build(ctx, "pb3d_points_in_mesh", d_verts, verts_f64, nv, d_faces, faces_i64, nf, 2, true, d_stats + 2, slots, &ix));
+    ctx->inside_last.info[0] = ix.g.n[0];
+    ctx->inside_last.info[1] = ix.g.n[1];
+    ctx->inside_last.info[2] = ix.entries;
+    ctx->inside_last.info[3] = ix.coarsenings;
+    void* setup = nullptr;
+    if (ctx->tune_inside_table) {
+        PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_INSIDE_SETUP, (size_t)nf * kSetupRow * sizeof(double), &setup));
+        hipLaunchKernelGGL(k_inside_setup, dim3(pb3d_stream_blocks(ctx, nf, 256, 8)), dim3(256), 0, ctx->stream, ix.tri, (i64)nf, (double*)setup);
+        PB3D_CHECK_LAUNCH();
+    }
     PB3D_TRY(t.mark(ctx));
     const unsigned nb = (unsigned)((nP + 255) / 256);
     void* pt = nullptr;
@@ -367,11 +216,11 @@ int pb3d_points_in_mesh_resident(pb3d_ctx* ctx, const void* d_P, int p_f64, int6
     const u32* order = nullptr;
     if (ctx->tune_inside_order) PB3D_TRY(pb3d_nn_order_queries(ctx, d_P, p_f64, nP, ix.g, &order));
     if (order) {
-        if (p_f64) launch_query<true, true>(ctx, nb, d_P, nP, order, ix, d_inside, (int*)d_counts, (u32*)pt);
-        else launch_query<false, true>(ctx, nb, d_P, nP, order, ix, d_inside, (int*)d_counts, (u32*)pt);
+        if (p_f64) launch_query<true, true>(ctx, nb, d_P, nP, order, ix, (const double*)setup, d_inside, (int*)d_counts, (u32*)pt);
+        else launch_query<false, true>(ctx, nb, d_P, nP, order, ix, (const double*)setup, d_inside, (int*)d_counts, (u32*)pt);
     } else {
-        if (p_f64) launch_query<true, false>(ctx, nb, d_P, nP, order, ix, d_inside, (int*)d_counts, (u32*)pt);
-        else launch_query<false, false>(ctx, nb, d_P, nP, order, ix, d_inside, (int*)d_counts, (u32*)pt);
+        if (p_f64) launch_query<true, false>(ctx, nb, d_P, nP, order, ix, (const double*)setup, d_inside, (int*)d_counts, (u32*)pt);
+        else launch_query<false, false>(ctx, nb, d_P, nP, order, ix, (const double*)setup, d_inside, (int*)d_counts, (u32*)pt);
     }
     PB3D_CHECK_LAUNCH();
     if (stats) {
@@ -380,7 +229,7 @@ int pb3d_points_in_mesh_resident(pb3d_ctx* ctx, const void* d_P, int p_f64, int6
     }
     PB3D_TRY(t.mark(ctx));
     if (stats) PB3D_TRY(pb3d_read_back(ctx, stats, d_stats, 4 * sizeof(i64)));
-    return t.finish(ctx);
+    return t.finish(ctx, ctx->inside_last.ms, &ctx->inside_last.timed);
 }
 
 int pb3d_points_in_mesh_last(pb3d_ctx* ctx, int64_t info[4], double pass_ms[2]) {

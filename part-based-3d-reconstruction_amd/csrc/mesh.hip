@@ -526,28 +526,8 @@ pb3d_ctx::IsoArgs iso_args(const void* vol, i64 n0, i64 n1, i64 n2, double level
     return pb3d_ctx::IsoArgs{vol, n0, n1, n2, nv, nf, lb, db};
 }
 
-// the passes' time stamps of an isosurface count or fill (knob "iso_timing"): three events, created per call; read() wants the
-// stream waited for
-struct IsoStamps {
-    bool on;
-    int k;
-    hipEvent_t ev[3];
-    int mark(pb3d_ctx* ctx) {
-        if (!on) return PB3D_OK;
-        PB3D_HIP(hipEventCreate(&ev[k]));
-        PB3D_HIP(hipEventRecord(ev[k], ctx->stream));
-        ++k;
-        return PB3D_OK;
-    }
-    int read(float ms[2], bool* timed) {
-        *timed = false;
-        if (!on || k != 3) return PB3D_OK;
-        for (int i = 0; i < 2; ++i) PB3D_HIP(hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
-        *timed = true;
-        return PB3D_OK;
-    }
-    ~IsoStamps() { for (int i = 0; i < k; ++i) (void)hipEventDestroy(ev[i]); }
-};
+// the passes' time stamps of an isosurface count or fill (knob "iso_timing"): two passes each; each half clears its *_timed flag first
+using IsoStamps = pb3d_stamps<3>;
 
 // bitmask of the lattice into PB3D_SLOT_MESH_BITS
 int build_bits(pb3d_ctx* ctx, const MeshParams& p, u64** bits) {
@@ -763,6 +743,7 @@ int pb3d_iso_fill_resident(pb3d_ctx* ctx, const float* d_vol, int64_t n0, int64_
     PB3D_TRY(counted_lattice(ctx, p, "pb3d_iso_fill", "pb3d_iso_count_resident", &bits));
     void* vb;
     PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESH_VERT_BASE, (size_t)p.ncubes * sizeof(int), &vb));
+    ctx->iso_last.fill_timed = false;
     IsoStamps st = {ctx->tune_iso_timing != 0, 0, {}};
     PB3D_TRY(st.mark(ctx));
     hipLaunchKernelGGL(k_iso_verts, dim3((unsigned)nb), dim3(256), 0, ctx->stream, p, bits, (const i64*)ctx->scratch[PB3D_SLOT_MESH_VERT_OFFSETS],
@@ -771,8 +752,7 @@ int pb3d_iso_fill_resident(pb3d_ctx* ctx, const float* d_vol, int64_t n0, int64_
     PB3D_TRY(st.mark(ctx));
     PB3D_TRY(fill_faces(ctx, p, bits, (const int*)vb, d_faces));
     PB3D_TRY(st.mark(ctx));
-    if (st.on) PB3D_TRY(pb3d_stream_sync(ctx));
-    return st.read(&ctx->iso_last.ms[2], &ctx->iso_last.fill_timed);
+    return st.finish(ctx, &ctx->iso_last.ms[2], &ctx->iso_last.fill_timed);
 }
 
 int pb3d_iso_last(pb3d_ctx* ctx, double pass_ms[4]) {

@@ -7,12 +7,10 @@
 // __dsqrt_rn at the end.  Float64 throughout, float32 widened first; the Makefile passes -ffp-contract=off, so every product, sum and
 // quotient below is one rounded operation.
 //
-// Index: the cell grid of csrc/nn.hip (csrc/ring_walk.h: make_grid from the exact box of the vertices and the face count), with a face
-// listed in every cell of the box cell_of(min corner) .. cell_of(max corner) per axis: count pass, the exclusive scan of
-// csrc/points.hip, scatter of face ids (order within a cell is free: atomics).  One giant face among small ones would be listed in
-// nearly every cell: while the (cell, face) entries exceed kEntryCap = 8 per face and the grid has more than one cell, the cells per
-// axis are halved and the entries recounted.  The corners of every face are gathered once into an nf x 9 float64 table, so the
-// search follows one indirection (cell -> face id -> 72 bytes) whatever the vertex and index dtypes are.
+// Index: csrc/face_index.hip's (the passes are described there), the one csrc/inside.hip walks in 2-D: the cell grid of csrc/nn.hip over
+// the exact box of the vertices, every face listed in the cells of cell_of(min corner) .. cell_of(max corner) per axis, the cells halved
+// while the entries exceed the cap, and the corners of every face gathered once into an nf x 9 float64 table, so the search follows
+// one indirection (cell -> face id -> 72 bytes) whatever the vertex and index dtypes are.
 // Host waits per call: the index check, the box, and one per count of the entries (1 + the number of coarsenings).
 //
 // Search: one lane per query, queries in cell order, ring_walk of csrc/ring_walk.h itself with (d2, face) as its Best.  Why the walk's
@@ -57,12 +55,10 @@
 
 #include "mesh_index.h"
 #include "pb3d_internal.h"
-#include "wave.h"
 #include "ring_walk.h"
 
 namespace {
 
-constexpr i64 kEntryCap = 8;            // (cell, face) entries per face the index accepts before it coarsens the grid
 constexpr int kPrefixBlock = 1024;      // faces per block of the cumulative area sum (include/pb3d.h)
 constexpr int kNoFace = 0x7fffffff;
 
@@ -160,56 +156,6 @@ __device__ __forceinline__ double face_closest(const double* t, const double (&q
     return dist2(q, cp);
 }
 
-// ---- the triangle index ---------------------------------------------------------------------------------------------------------------
-template <bool VF64, bool I64>
-__global__ __launch_bounds__(256) void k_face_corners(const void* __restrict__ verts, i64 nv, const void* __restrict__ faces, i64 nf,
-                                                      double* __restrict__ tri) {
-    const i64 f = (i64)blockIdx.x * 256 + threadIdx.x;
-    if (f >= nf) return;
-    double t[9];
-    load_face<VF64, I64>(verts, nv, faces, f, t);
-#pragma unroll
-    for (int k = 0; k < 9; ++k) tri[9 * f + k] = t[k];
-}
-
-// the cells a face is listed in: cell_of(min corner) .. cell_of(max corner), per axis
-__device__ __forceinline__ void face_cells(const Grid& g, const double* __restrict__ t, int lo[3], int hi[3]) {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        lo[a] = cell_of(g, a, fmin(fmin(t[a], t[3 + a]), t[6 + a]));
-        hi[a] = cell_of(g, a, fmax(fmax(t[a], t[3 + a]), t[6 + a]));
-    }
-}
-
-// the number of (cell, face) entries of the grid, without touching a cell
-__global__ __launch_bounds__(256) void k_face_entries(const double* __restrict__ tri, i64 nf, Grid g, unsigned long long* __restrict__ total) {
-    unsigned long long n = 0;
-    for (i64 f = (i64)blockIdx.x * 256 + threadIdx.x; f < nf; f += (i64)gridDim.x * 256) {
-        int lo[3], hi[3];
-        face_cells(g, tri + 9 * f, lo, hi);
-        n += (unsigned long long)(hi[0] - lo[0] + 1) * (unsigned long long)(hi[1] - lo[1] + 1) * (unsigned long long)(hi[2] - lo[2] + 1);
-    }
-    n = wave_sum(n);
-    if ((threadIdx.x & 63) == 0 && n) atomicAdd(total, n);
-}
-
-// FILL false: counts[cell] += 1 per entry;  FILL true: ids[start[cell] + cursor[cell]++] = face (cursor: zeroed per-cell counters)
-template <bool FILL>
-__global__ __launch_bounds__(256) void k_face_bin(const double* __restrict__ tri, i64 nf, Grid g, u32* __restrict__ counts,
-                                                  const i64* __restrict__ start, int* __restrict__ ids) {
-    for (i64 f = (i64)blockIdx.x * 256 + threadIdx.x; f < nf; f += (i64)gridDim.x * 256) {
-        int lo[3], hi[3];
-        face_cells(g, tri + 9 * f, lo, hi);
-        for (int i = lo[0]; i <= hi[0]; ++i)
-            for (int j = lo[1]; j <= hi[1]; ++j)
-                for (int k = lo[2]; k <= hi[2]; ++k) {
-                    const i64 c = cell_index(g, i, j, k);
-                    if (FILL) ids[start[c] + atomicAdd(&counts[c], 1u)] = (int)f;
-                    else atomicAdd(&counts[c], 1u);
-                }
-    }
-}
-
 // ---- the search -------------------------------------------------------------------------------------------------------------------------
 struct Faces { const int* ids; const double* tri; };       // face ids in cell order, the corner table
 
@@ -261,70 +207,6 @@ __global__ __launch_bounds__(256) void k_mesh_query(const void* __restrict__ q, 
         if (found) face_closest(tri + 9 * (i64)best.face, qv, cp);
         out_closest[3 * (i64)qi] = cp[0]; out_closest[3 * (i64)qi + 1] = cp[1]; out_closest[3 * (i64)qi + 2] = cp[2];
     }
-}
-
-// halve the cells per axis (the box stays)
-Grid coarsen(Grid g) {
-    g.ncells = 1;
-    for (int a = 0; a < 3; ++a) {
-        g.n[a] = (g.n[a] + 1) / 2;
-        const double ext = g.hi[a] - g.lo[a];
-        g.inv[a] = g.n[a] > 1 ? (double)g.n[a] / ext : 0.0;
-        g.h[a] = g.n[a] > 1 ? ext / (double)g.n[a] : 0.0;
-        g.ncells *= g.n[a];
-    }
-    return g;
-}
-
-struct MeshIndex { Grid g; const i64* starts; const int* ids; const double* tri; };
-
-// faces checked; nv, nf >= 1
-int build_index(pb3d_ctx* ctx, const void* d_verts, int verts_f64, i64 nv, const void* d_faces, int faces_i64, i64 nf, MeshIndex* ix) {
-    void *tri, *cnt, *st, *ids;
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESHD_CORNERS, (size_t)nf * 9 * sizeof(double), &tri));
-    with_mesh_types(verts_f64, faces_i64, [&](auto V, auto I) {
-        hipLaunchKernelGGL((k_face_corners<decltype(V)::value, decltype(I)::value>), dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, ctx->stream,
-                           d_verts, nv, d_faces, nf, (double*)tri);
-    });
-    PB3D_CHECK_LAUNCH();
-    // the exact box of ALL vertices (k_bounds_* of csrc/nn.hip): an unreferenced vertex only enlarges it.  The slot holds 8 doubles:
-    // the box, then the entry total at + 6
-    void* rb;
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESHD_READBACK, 8 * sizeof(double), &rb));
-    double b[6];
-    PB3D_TRY(pb3d_points_box(ctx, d_verts, verts_f64, nv, PB3D_SLOT_MESHD_READBACK, b));
-    for (int a = 0; a < 6; ++a) PB3D_REQUIRE(std::isfinite(b[a]), "pb3d_mesh_dist: the vertices must be finite");
-    Grid g = make_grid(b, nf);
-    unsigned long long* d_total = (unsigned long long*)rb + 6;
-    const unsigned nb = pb3d_stream_blocks(ctx, nf, 256, 8);
-    unsigned long long total = 0;
-    i64 coarsenings = 0;
-    for (;;) {
-        PB3D_HIP(hipMemsetAsync(d_total, 0, sizeof(unsigned long long), ctx->stream));
-        hipLaunchKernelGGL(k_face_entries, dim3(nb), dim3(256), 0, ctx->stream, (const double*)tri, nf, g, d_total);
-        PB3D_CHECK_LAUNCH();
-        PB3D_TRY(pb3d_read_back(ctx, &total, d_total, sizeof(total)));
-        if (total <= (unsigned long long)(kEntryCap * nf) || g.ncells == 1) break;
-        g = coarsen(g);
-        ++coarsenings;
-    }
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESHD_COUNTS, (size_t)g.ncells * sizeof(u32), &cnt));
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESHD_STARTS, (size_t)(g.ncells + 1) * sizeof(i64), &st));
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESHD_IDS, (size_t)total * sizeof(int), &ids));
-    PB3D_HIP(hipMemsetAsync(cnt, 0, (size_t)g.ncells * sizeof(u32), ctx->stream));
-    hipLaunchKernelGGL(k_face_bin<false>, dim3(nb), dim3(256), 0, ctx->stream, (const double*)tri, nf, g, (u32*)cnt, (const i64*)nullptr,
-                       (int*)nullptr);
-    PB3D_CHECK_LAUNCH();
-    PB3D_TRY(pb3d_scan_counts(ctx, (const u32*)cnt, g.ncells, (i64*)st, PB3D_SLOT_MESHD_SCAN_LOCAL, PB3D_SLOT_MESHD_SCAN_SEGS));
-    PB3D_HIP(hipMemsetAsync(cnt, 0, (size_t)g.ncells * sizeof(u32), ctx->stream));      // the scatter's cursors
-    hipLaunchKernelGGL(k_face_bin<true>, dim3(nb), dim3(256), 0, ctx->stream, (const double*)tri, nf, g, (u32*)cnt, (const i64*)st, (int*)ids);
-    PB3D_CHECK_LAUNCH();
-    ix->g = g;
-    ix->starts = (const i64*)st;
-    ix->ids = (const int*)ids;
-    ix->tri = (const double*)tri;
-    ctx->mesh_grid_last = {true, {g.n[0], g.n[1], g.n[2]}, (i64)total, coarsenings};
-    return PB3D_OK;
 }
 
 // ---- sampling ---------------------------------------------------------------------------------------------------------------------------
@@ -421,9 +303,12 @@ int pb3d_mesh_dist_resident(pb3d_ctx* ctx, const void* d_q, int q_f64, int64_t n
     PB3D_REQUIRE(d_q != nullptr && d_dist != nullptr, "pb3d_mesh_dist: null buffer");
     PB3D_REQUIRE(ctx != nullptr, "pb3d_mesh_dist: null context");
     PB3D_TRY(pb3d_check_index_range(ctx, d_faces, faces_i64, 3 * nf, -nv, nv, "pb3d_mesh_dist"));
-    MeshIndex ix;
+    const pb3d_face_index_slots slots = {PB3D_SLOT_MESHD_CORNERS, PB3D_SLOT_MESHD_READBACK, PB3D_SLOT_MESHD_COUNTS, PB3D_SLOT_MESHD_STARTS,
+                                         PB3D_SLOT_MESHD_IDS, PB3D_SLOT_MESHD_SCAN_LOCAL, PB3D_SLOT_MESHD_SCAN_SEGS};
+    pb3d_face_index ix;
     const u32* order;
-    PB3D_TRY(build_index(ctx, d_verts, verts_f64, nv, d_faces, faces_i64, nf, &ix));
+    PB3D_TRY(pb3d_face_index_build(ctx, "pb3d_mesh_dist", d_verts, verts_f64, nv, d_faces, faces_i64, nf, 3, false, nullptr, slots, &ix));
+    ctx->mesh_grid_last = {true, {ix.g.n[0], ix.g.n[1], ix.g.n[2]}, ix.entries, ix.coarsenings};
     PB3D_TRY(pb3d_nn_order_queries(ctx, d_q, q_f64, nq, ix.g, &order));
     hipLaunchKernelGGL((q_f64 ? k_mesh_query<true> : k_mesh_query<false>), dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, ctx->stream, d_q,
                        (i64)nq, order, ix.g, ix.starts, ix.ids, ix.tri, d_dist, (int*)d_face, d_closest);

@@ -161,7 +161,8 @@ enum pb3d_slot : int {
     PB3D_SLOT_SELECT = 81,
     // call-local, csrc/icp.hip: a trimmed step's header (candidate count, rank, tau) and the selection keys of its pairs
     PB3D_SLOT_ICP_KEYS = 82,
-    // call-local, csrc/meshdist.hip, the triangle index of pb3d_mesh_dist_resident: the nf x 9 float64 corner table, the vertex box and the
+    // call-local, csrc/meshdist.hip, the triangle index of pb3d_mesh_dist_resident (built by csrc/face_index.hip, as containment's
+    // below, each in its caller's slots): the nf x 9 float64 corner table, the vertex box and the
     // entry total read back by the host, per-cell counts (then the scatter's cursors), cell starts, face ids in cell order and the two
     // slots of its pb3d_scan_counts.  The query half and the bounds pass inside use NN_QUERY_*, NN_ORDER, NN_SCAN_* and NN_BOUNDS_PARTIALS
     PB3D_SLOT_MESHD_CORNERS = 83,
@@ -413,8 +414,8 @@ struct pb3d_ctx {
     int tune_inside_timing;     // knob "inside_timing": 1 = pb3d_points_in_mesh_resident times its index build and its query with events (one more host wait)
     int tune_inside_order;      // knob "inside_order": 0 = queries in input order, 1 = in the cell order of the index (csrc/nn.hip's query binning)
     int tune_inside_table;      // knob "inside_table": 0 = the query recomputes a face's set-up from its 72-byte corner row, 1 = it reads a 184-byte row of finished set-ups (development A/B)
-    // the last pb3d_points_in_mesh_resident (csrc/inside.hip) for pb3d_points_in_mesh_last: cells per axis of its index, (cell, face)
-    // entries and halvings; with inside_timing the milliseconds of the index build and of the query
+    // the last pb3d_points_in_mesh_resident (csrc/inside.hip) for pb3d_points_in_mesh_last: cells along a0 and a1 of its index, (cell, face)
+    // entries and halvings, as pb3d_face_index_build reports them; with inside_timing the milliseconds of the index build and of the query
     struct InsideLast { bool valid, timed; float ms[2]; i64 info[4]; } inside_last;
     // Growable device scratch slots, named by enum pb3d_slot (no hipMalloc / hipFree per call once warm).
     void* scratch[PB3D_SLOT_COUNT];
@@ -448,8 +449,8 @@ struct pb3d_ctx {
     // the target index of an alignment (csrc/icp.hip, PB3D_SLOT_ICP_INDEX_*): built by pb3d_icp_index_resident for this (pointer, count,
     // width), read by every pb3d_icp_step_resident.  gen = scratch_slot_gen of the three slots when it was written.
     struct IcpIndex { bool valid; const void* tgt; i64 nt; int f64; u64 gen[3]; pb3d_nn_index ix; } icp_index;
-    // the triangle index of the last pb3d_mesh_dist_resident (csrc/meshdist.hip), for pb3d_mesh_grid_shape: cells per axis, (cell, face)
-    // entries, and how often the grid was coarsened to respect the entry cap
+    // the triangle index of the last pb3d_mesh_dist_resident (csrc/meshdist.hip, from pb3d_face_index_build), for pb3d_mesh_grid_shape:
+    // cells per axis, (cell, face) entries, and how often the grid was coarsened to respect the entry cap
     struct MeshGridLast { bool valid; i64 cells[3], entries, coarsenings; } mesh_grid_last;
     // Device block pool behind pb3d_dev_alloc / pb3d_dev_free: a freed block is kept (no hipFree, no stream synchronisation) and handed
     // to the next request of about its size.  Everything that touches such a block runs on ctx->stream, in order, so a re-used block
@@ -534,6 +535,35 @@ constexpr size_t pb3d_pinned_flag = 64;
 // d_src[0, bytes) -> host_dst through the head of the pinned area: one copy, one host wait (pb3d_stream_sync), one memcpy out
 int pb3d_read_back(pb3d_ctx* ctx, void* host_dst, const void* d_src, size_t bytes);
 
+// The time stamps of an entry's passes (the *_timing knobs; off: nothing happens): N events, created per call, mark() records the
+// next one.  read() wants the stream waited for and gives the milliseconds between consecutive marks; *timed = all N were made.
+// finish() is the one more host wait, then read()
+template <int N>
+struct pb3d_stamps {
+    bool on;
+    int k;
+    hipEvent_t ev[N];
+    int mark(pb3d_ctx* ctx) {
+        if (!on) return PB3D_OK;
+        PB3D_HIP(hipEventCreate(&ev[k]));
+        PB3D_HIP(hipEventRecord(ev[k], ctx->stream));
+        ++k;
+        return PB3D_OK;
+    }
+    int read(float* ms, bool* timed) {
+        if (!on) return PB3D_OK;
+        for (int i = 0; i + 1 < k; ++i) PB3D_HIP(hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]));
+        *timed = k == N;
+        return PB3D_OK;
+    }
+    int finish(pb3d_ctx* ctx, float* ms, bool* timed) {
+        if (!on) return PB3D_OK;
+        PB3D_TRY(pb3d_stream_sync(ctx));
+        return read(ms, timed);
+    }
+    ~pb3d_stamps() { for (int i = 0; i < k; ++i) (void)hipEventDestroy(ev[i]); }
+};
+
 // grid size for grid-stride streaming kernels: enough blocks to fill 256 CUs, capped
 // blocks_per_cu <= 0: no cap -- one workgroup per tile of the stream.  For write-heavy or latency-heavy streams the dispatcher balances
 // many small workgroups better than a persistent grid-stride loop does (colour apply 0.84 -> 0.70 ms, float32 projection 1.03 -> 0.90 ms
@@ -615,6 +645,16 @@ int pb3d_nn_index_nearest(pb3d_ctx* ctx, const pb3d_nn_index& ix, const double* 
 // csrc/nn.hip for csrc/meshdist.hip: the positions of the nq >= 1 queries in the cell order of grid g -> *order (PB3D_SLOT_NN_ORDER;
 // enqueued)
 int pb3d_nn_order_queries(pb3d_ctx* ctx, const void* d_q, int q_f64, i64 nq, const pb3d_nn_grid& g, const u32** order);
+// csrc/face_index.hip for csrc/meshdist.hip and csrc/inside.hip: the triangle cell index of a mesh (face indices checked; nv, nf >= 1)
+// in the caller's slots -- cell starts, face ids in cell order, the nf x 9 float64 corner table -- with the (cell, face) entries and
+// the halvings of the grid that the entry cap asked for.  axes: 3, or 2 for one cell along a2; skip_flat: a face without an area in
+// (a0, a1) is listed nowhere; d_flat: where those faces are counted, or null.  PB3D_EINVAL "<what>: the vertices must be finite" on a
+// box that is not.  Host waits: the box and 1 + halvings entry counts; the rest is enqueued.  The read-back slot takes eight 64-bit
+// words: the box at [0, 6), the entry total at [6], and [7] is the caller's
+struct pb3d_face_index { pb3d_nn_grid g; const i64* starts; const int* ids; const double* tri; i64 entries, coarsenings; };
+struct pb3d_face_index_slots { pb3d_slot corners, readback, counts, starts, ids, scan_local, scan_segs; };
+int pb3d_face_index_build(pb3d_ctx* ctx, const char* what, const void* d_verts, int verts_f64, i64 nv, const void* d_faces, int faces_i64, i64 nf,
+                          int axes, bool skip_flat, u64* d_flat, const pb3d_face_index_slots& slots, pb3d_face_index* out);
 // csrc/select.hip for csrc/icp.hip: pb3d_kth_smallest_resident with the rank read from device memory when the selection runs
 // (0 <= *d_rank < n; 1 <= n <= 2^31 - 1; enqueued)
 int pb3d_select_kth(pb3d_ctx* ctx, const double* d_vals, i64 n, const i64* d_rank, double* d_out);

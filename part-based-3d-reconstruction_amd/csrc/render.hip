@@ -22,6 +22,7 @@
 #include <cmath>
 
 #include "wave.h"
+#include "cross_rule.h"         // report_mesh_flag: the flag k_render_setup raises is k_check_mesh's
 #include "mesh_index.h"
 #include "pb3d_internal.h"
 
@@ -217,28 +218,6 @@ __global__ __launch_bounds__(256) void k_render_fill(u64* __restrict__ p, i64 n,
     for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (i64)gridDim.x * 256) p[i] = value;
 }
 
-// the passes' time stamps (knob "render_timing"): six events, created per call, read after one more host wait
-struct Stamps {
-    bool on;
-    int k;
-    hipEvent_t ev[6];
-    int mark(pb3d_ctx* ctx) {
-        if (!on) return PB3D_OK;
-        PB3D_HIP(hipEventCreate(&ev[k]));
-        PB3D_HIP(hipEventRecord(ev[k], ctx->stream));
-        ++k;
-        return PB3D_OK;
-    }
-    int finish(pb3d_ctx* ctx) {
-        if (!on) return PB3D_OK;
-        PB3D_TRY(pb3d_stream_sync(ctx));
-        for (int i = 0; i + 1 < k; ++i) PB3D_HIP(hipEventElapsedTime(&ctx->render_last.ms[i], ev[i], ev[i + 1]));
-        ctx->render_last.timed = k == 6;
-        return PB3D_OK;
-    }
-    ~Stamps() { for (int i = 0; i < k; ++i) (void)hipEventDestroy(ev[i]); }
-};
-
 bool finite_all(const double* p, int n) {
     for (int i = 0; i < n; ++i)
         if (!std::isfinite(p[i])) return false;
@@ -287,11 +266,7 @@ int pb3d_render_mesh_resident(pb3d_ctx* ctx, const void* d_verts, int verts_f64,
         PB3D_CHECK_LAUNCH();
         u32 bad;
         PB3D_TRY(pb3d_read_back(ctx, &bad, counts + 3, sizeof(bad)));
-        if (bad & 1u) {
-            pb3d_set_error("pb3d_render_mesh: index out of bounds for %lld entries", (long long)nv);
-            return PB3D_EINDEX;
-        }
-        PB3D_REQUIRE(!(bad & 2u), "pb3d_render_mesh: a vertex coordinate is not finite");
+        PB3D_TRY(report_mesh_flag("pb3d_render_mesh", bad, nv));
     }
 
     const bool want_face = d_face != nullptr || d_bary != nullptr;
@@ -303,7 +278,7 @@ int pb3d_render_mesh_resident(pb3d_ctx* ctx, const void* d_verts, int verts_f64,
     }
     ctx->render_last.valid = false;
     ctx->render_last.timed = false;
-    Stamps st = {ctx->tune_render_timing != 0, 0, {}};
+    pb3d_stamps<6> st = {ctx->tune_render_timing != 0, 0, {}};       // knob "render_timing"
     u64* dimg = (u64*)d_depth;
     u32* win = (u32*)wn;
     const unsigned pixel_blocks = pb3d_stream_blocks(ctx, npix, 256, 8);
@@ -358,7 +333,7 @@ int pb3d_render_mesh_resident(pb3d_ctx* ctx, const void* d_verts, int verts_f64,
     PB3D_TRY(st.mark(ctx));
     for (int i = 0; i < 4; ++i) ctx->render_last.stats[i] = host[i];
     ctx->render_last.valid = true;
-    return st.finish(ctx);
+    return st.finish(ctx, ctx->render_last.ms, &ctx->render_last.timed);
 }
 
 int pb3d_render_shade_resident(pb3d_ctx* ctx, const int32_t* d_face, const double* d_bary, int64_t npix, const void* d_faces, int faces_i64,

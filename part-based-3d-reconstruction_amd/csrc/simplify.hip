@@ -133,27 +133,7 @@ __global__ __launch_bounds__(256) void k_face_gather(i64 nf, const u32* __restri
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
 inline dim3 grid_for(i64 n) { return dim3((unsigned)((n + 255) / 256)); }
 
-// the passes' time stamps (knob "simplify_timing"): six events, created per call, read after one more host wait
-struct Stamps {
-    bool on;
-    int k;
-    hipEvent_t ev[6];
-    int mark(pb3d_ctx* ctx) {
-        if (!on) return PB3D_OK;
-        PB3D_HIP(hipEventCreate(&ev[k]));
-        PB3D_HIP(hipEventRecord(ev[k], ctx->stream));
-        ++k;
-        return PB3D_OK;
-    }
-    int finish(pb3d_ctx* ctx) {
-        if (!on) return PB3D_OK;
-        PB3D_TRY(pb3d_stream_sync(ctx));
-        for (int i = 0; i + 1 < k; ++i) PB3D_HIP(hipEventElapsedTime(&ctx->simplify_last.ms[i], ev[i], ev[i + 1]));
-        ctx->simplify_last.timed = k == 6;
-        return PB3D_OK;
-    }
-    ~Stamps() { for (int i = 0; i < k; ++i) (void)hipEventDestroy(ev[i]); }
-};
+using Stamps = pb3d_stamps<6>;      // knob "simplify_timing"
 
 // what both entries share
 struct Mesh {
@@ -247,7 +227,7 @@ int face_tail(pb3d_ctx* ctx, const Mesh& s, const int* inv, const int* first, co
     counts[1] = got[1];
     ctx->simplify_last.counts[1] = got[0];
     ctx->simplify_last.counts[2] = got[1];
-    return t.finish(ctx);
+    return t.finish(ctx, ctx->simplify_last.ms, &ctx->simplify_last.timed);
 }
 
 // the result without a face: nothing stays.  Enqueued

@@ -232,28 +232,6 @@ __global__ __launch_bounds__(256) void k_overlap(const u8* __restrict__ a, const
     group_add(nb, &counts[2]);
 }
 
-// the passes' time stamps (knob "voxelize_timing"): three events, created per call, read after one more host wait
-struct Stamps {
-    bool on;
-    int k;
-    hipEvent_t ev[3];
-    int mark(pb3d_ctx* ctx) {
-        if (!on) return PB3D_OK;
-        PB3D_HIP(hipEventCreate(&ev[k]));
-        PB3D_HIP(hipEventRecord(ev[k], ctx->stream));
-        ++k;
-        return PB3D_OK;
-    }
-    int finish(pb3d_ctx* ctx) {
-        if (!on) return PB3D_OK;
-        PB3D_TRY(pb3d_stream_sync(ctx));
-        for (int i = 0; i + 1 < k; ++i) PB3D_HIP(hipEventElapsedTime(&ctx->voxelize_last.ms[i], ev[i], ev[i + 1]));
-        ctx->voxelize_last.timed = k == 3;
-        return PB3D_OK;
-    }
-    ~Stamps() { for (int i = 0; i < k; ++i) (void)hipEventDestroy(ev[i]); }
-};
-
 }  // namespace
 
 extern "C" {
@@ -279,29 +257,15 @@ int pb3d_voxelize_mesh_resident(pb3d_ctx* ctx, const void* d_verts, int verts_f6
     void *cn, *bt, *lg = nullptr;
     PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_VOXELIZE_COUNTS, 5 * sizeof(u64), &cn));
     u64* counts = (u64*)cn;                          // the four stats, then the check's flag
-    PB3D_HIP(hipMemsetAsync(cn, 0, 5 * sizeof(u64), ctx->stream));
-    if (nv > 0 || nf > 0) {
-        const unsigned nb = pb3d_stream_blocks(ctx, 3 * std::max<i64>(nv, nf), 256, 8);
-        with_mesh_types(verts_f64, faces_i64, [&](auto V, auto I) {
-            hipLaunchKernelGGL((k_check_mesh<decltype(V)::value, decltype(I)::value>), dim3(nb), dim3(256), 0, ctx->stream, d_verts, (i64)nv, d_faces,
-                               (i64)nf, (u32*)(counts + 4));
-        });
-        PB3D_CHECK_LAUNCH();
-        u32 bad;
-        PB3D_TRY(pb3d_read_back(ctx, &bad, counts + 4, sizeof(bad)));
-        if (bad & 1u) {
-            pb3d_set_error("pb3d_voxelize_mesh: index out of bounds for %lld entries", (long long)nv);
-            return PB3D_EINDEX;
-        }
-        PB3D_REQUIRE(!(bad & 2u), "pb3d_voxelize_mesh: a vertex coordinate is not finite");
-    }
+    PB3D_HIP(hipMemsetAsync(cn, 0, 4 * sizeof(u64), ctx->stream));
+    if (nv > 0 || nf > 0) PB3D_TRY(check_mesh(ctx, "pb3d_voxelize_mesh", d_verts, verts_f64, nv, d_faces, faces_i64, nf, (u32*)(counts + 4)));
 
     const i64 ncol = n0 * n1, Wd = (n2 + 31) / 32, W = Wd + 1;
     PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_VOXELIZE_BITS, (size_t)ncol * W * sizeof(u32), &bt));
     if (nf > 0) PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_VOXELIZE_LARGE, (size_t)(nf + 1) * sizeof(u32), &lg));
     ctx->voxelize_last.valid = true;
     ctx->voxelize_last.timed = false;
-    Stamps t = {ctx->tune_voxelize_timing != 0, 0, {}};
+    pb3d_stamps<3> t = {ctx->tune_voxelize_timing != 0, 0, {}};      // knob "voxelize_timing"
     PB3D_TRY(t.mark(ctx));
     PB3D_HIP(hipMemsetAsync(bt, 0, (size_t)ncol * W * sizeof(u32), ctx->stream));
     const Vol vol = {(u32*)bt, n0, n1, n2, W};
@@ -334,7 +298,7 @@ int pb3d_voxelize_mesh_resident(pb3d_ctx* ctx, const void* d_verts, int verts_f6
     PB3D_CHECK_LAUNCH();
     PB3D_TRY(t.mark(ctx));
     if (stats) PB3D_TRY(pb3d_read_back(ctx, stats, counts, 4 * sizeof(i64)));
-    return t.finish(ctx);
+    return t.finish(ctx, ctx->voxelize_last.ms, &ctx->voxelize_last.timed);
 }
 
 int pb3d_voxelize_last(pb3d_ctx* ctx, double pass_ms[2]) {

@@ -151,3 +151,20 @@ def first_grid_entries(verts, faces, cap_per_cell=2.0):
     area = (t[:, 1, 0] - t[:, 0, 0]) * (t[:, 2, 1] - t[:, 0, 1]) - (t[:, 1, 1] - t[:, 0, 1]) * (t[:, 2, 0] - t[:, 0, 0])
     span = cell(t.max(axis=1)) - cell(t.min(axis=1)) + 1
     return (int(n[0]), int(n[1])), int((span[:, 0] * span[:, 1])[area != 0].sum())
+
+
+def grid_entries(verts, faces, cells):
+    """the (cell, face) entries of the index on a grid of `cells` = (cells along a0, cells along a1) over the (a0, a1) box of ALL
+    vertices, by the arithmetic of mesh_cases.index_entries: inv = n / extent (0 on a one-cell axis), cell = clip(floor((p - lo) * inv),
+    0, n - 1), a face listed in cell(min corner) .. cell(max corner) per axis -- and a face whose projected area is 0 nowhere.  The
+    same float64 operations as the device's, so the count is the device's exactly"""
+    v = np.asarray(verts).astype(np.float64)
+    f = wrapped(faces, len(v))
+    n = np.array(cells, np.int64)
+    lo, ext = v[:, :2].min(axis=0), v[:, :2].max(axis=0) - v[:, :2].min(axis=0)
+    inv = np.where(n > 1, n / np.where(n > 1, ext, 1.0), 0.0)
+    t = v[f][:, :, :2]
+    area = (t[:, 1, 0] - t[:, 0, 0]) * (t[:, 2, 1] - t[:, 0, 1]) - (t[:, 1, 1] - t[:, 0, 1]) * (t[:, 2, 0] - t[:, 0, 0])
+    first = np.clip(np.floor((t.min(axis=1) - lo) * inv), 0, n - 1)
+    last = np.clip(np.floor((t.max(axis=1) - lo) * inv), 0, n - 1)
+    return int((last - first + 1).prod(axis=1)[area != 0].sum())

@@ -132,6 +132,23 @@ def test_wall_mesh_exceeds_the_entry_cap_by_construction():
     assert len(f) == 502 and cells == (16, 16) and entries > 8 * len(f)
 
 
+def flattened_icosphere():
+    """the float64 icosphere with every vertex at one a0: no face has a projected area"""
+    flat = float_mesh("icosphere", np.float64)[0].copy()
+    flat[:, 0] = 0.25
+    return flat, float_mesh("icosphere", np.float64)[1]
+
+
+def test_grid_entries_restates_the_listing_rule():
+    v, f = ir.wall_among_small()
+    cells, entries = ir.first_grid_entries(v, f)
+    assert ir.grid_entries(v, f, cells) == entries
+    assert ir.grid_entries(v, f, (1, 1)) == len(f)         # one cell lists every face once: none of them is flat
+    flat, faces = flattened_icosphere()
+    for cells in ((1, 1), (1, 13)):                         # a box without an a0 extent has one cell there
+        assert ir.grid_entries(flat, faces, cells) == 0
+
+
 def test_argument_errors_need_no_device():
     q, v, f, _ = pinned_box()
     for fn in (pb3d.points_in_mesh, pb3d.signed_point_to_mesh_distances, pb3d.select_points_in_mesh):
@@ -320,13 +337,13 @@ def test_resident_nan_query(pb3d_gpu):
 @gpu
 def test_degenerate_box(pb3d_gpu):
     """every vertex shares one a0: the box has no extent there, every face is flat, nothing is inside"""
-    v, f = float_mesh("icosphere", np.float64)
-    flat = v.copy()
-    flat[:, 0] = 0.25
+    flat, f = flattened_icosphere()
     q = np.concatenate([float_queries("icosphere", np.float64)[0][:500], np.column_stack([np.full(50, 0.25), flat[:50, 1], flat[:50, 2]])])
     inside, counts, _, _ = run(pb3d_gpu, q, flat, f, "degenerate")
     assert not inside.any() and not counts.any()
-    assert pb3d_gpu.points_in_mesh_last()[1] == 0          # no face has an area: no entry
+    cells, entries, _ = pb3d_gpu.points_in_mesh_last()
+    assert entries == 0                                     # no face has an area: no entry
+    assert entries == ir.grid_entries(flat, f, cells)
 
 
 @gpu
@@ -341,6 +358,7 @@ def test_cell_without_a_face(pb3d_gpu):
     assert not counts[:300].any() and inside[300:].sum() > 100
     cells, entries, _ = pb3d_gpu.points_in_mesh_last()
     assert cells[0] * cells[1] > entries                    # more cells than entries: some cell is empty
+    assert entries == ir.grid_entries(verts, faces, cells)  # the listing rule, to the entry
 
 
 @gpu
@@ -352,7 +370,31 @@ def test_wall_among_small_faces_coarsens_the_index(pb3d_gpu):
     inside, counts, _, _ = run(pb3d_gpu, q, v, f, "wall")
     got_cells, got_entries, halvings = pb3d_gpu.points_in_mesh_last()
     assert halvings >= 1 and got_cells[0] < cells[0] and got_cells[1] < cells[1] and got_entries <= 8 * len(f)
+    assert got_entries == ir.grid_entries(v, f, got_cells)  # the listing rule on the halved grid, to the entry
     assert counts[:, 1].max() >= 3 and 0 < inside.sum() < len(q)
+
+
+@gpu
+def test_host_waits_of_the_resident_call(pb3d_gpu):
+    """the waits csrc/inside.hip's header states: the mesh check, the box, 1 + halvings entry counts, one more for the stats.  The
+    outputs stay on the device inside the counted span"""
+    from pb3d import device as dev
+    q, v, f, _ = pinned_box()
+    bufs = [dev.from_numpy(q), dev.from_numpy(v), dev.from_numpy(f)]
+    try:
+        for with_stats in (False, True):
+            for _ in range(2):                              # the second call finds every scratch slot large enough: no wait for a regrow
+                before = dev.sync_count()
+                out = pb3d_gpu.points_in_mesh_resident(bufs[0], len(q), bufs[1], len(v), bufs[2], len(f), verts_f64=True, faces_i64=True,
+                                                       return_stats=with_stats)
+                waits = dev.sync_count() - before
+                bufs.append(out[0] if with_stats else out)
+            halvings = pb3d_gpu.points_in_mesh_last()[2]
+            print("host waits of the resident call:", waits, "halvings", halvings, "stats", with_stats)
+            assert waits == 3 + halvings + with_stats
+    finally:
+        for b in bufs:
+            b.free()
 
 
 @gpu
