@@ -854,6 +854,76 @@ int pb3d_render_shade_resident(pb3d_ctx* ctx, const int32_t* d_face, const doubl
 int pb3d_render_last(const pb3d_ctx* ctx, int64_t stats[4]);
 int pb3d_render_last_ms(const pb3d_ctx* ctx, double pass_ms[5]);
 
+/* ---- rays against a mesh: the first hit, or any hit, of arbitrary rays on a triangle mesh (csrc/raycast.hip) --------------------------
+ * "What does this ray hit first?" for rays the caller chooses: occlusion of the segment from a point to an eye, distances along a normal,
+ * orthographic depths, thickness.  There is no upstream text, so the rules below are the specification, and the result is a function
+ * of the input alone, to the bit: every output is written once by the one lane that owns the ray, and there are no atomics.  The face test
+ * is "mesh -> image"'s (Woop, Benthin and Wald 2013) with the ray's own shear in place of the pixel's.
+ *   ARITHMETIC all float64; float32 input is widened first, which is exact.  Every product, sum, difference and quotient below is one
+ *              correctly rounded IEEE operation, no FMA.
+ *   INPUT      origins o and directions d: (nrays, 3) rows of float32 (rays_f64 = 0) or float64 (1), one flag for both arrays.  verts
+ *              and faces exactly as pb3d_render_mesh_resident takes them (float32 / float64, int32 / int64, indices in [-nv, nv)
+ *              wrapping; any other index PB3D_EINDEX, a vertex that is not finite PB3D_EINVAL, both checked on the device before anything
+ *              gathers: one host wait, and no output is written when they fail).  t_min finite, t_max finite or +inf, t_min <= t_max.
+ *              nf == 0 or nrays == 0 is legal: every ray misses, no index is built.  Limits: nv, nf, nrays <= 2^31 - 1; ray buffers
+ *              aligned to their element, d_t and d_bary to 8 bytes, d_face to 4.  Anything else is PB3D_EINVAL before any device work.
+ *   BAD RAY    a ray with a component of o or d that is not finite, or with d == (0, 0, 0), hits nothing (and is counted).
+ *   RAY        once per ray: kz = the axis of the largest |d| (a later axis replaces an earlier one only if it is strictly larger);
+ *              kx = (kz + 1) % 3; ky = (kz + 2) % 3; Sx = d[kx] / d[kz]; Sy = d[ky] / d[kz]; Sz = 1.0 / d[kz].  No winding swap:
+ *              nothing is culled by orientation.
+ *   FACE against RAY, corners a, b, c:  A' = a - o per component, B', C' likewise;
+ *              ax = A'[kx] - Sx*A'[kz], ay = A'[ky] - Sy*A'[kz] (a product, then a difference), b and c likewise;
+ *              U = cx*by - cy*bx; V = ax*cy - ay*cx; W = bx*ay - by*ax; det = (U + V) + W;
+ *              T = (U*(Sz*A'[kz]) + V*(Sz*B'[kz])) + W*(Sz*C'[kz]); t = T / det.
+ *              The face HITS iff it is not the case that some of U, V, W is < 0 while another is > 0, and det != 0, and t >= t_min, and
+ *              t <= t_max, every comparison an IEEE comparison of doubles: -0.0 >= 0.0 holds, a NaN fails.  The hit point is o + t d;
+ *              t is in units of |d|.
+ *   RESULT     each ray takes the hitting face with the smallest (t, face number); t is compared as a double, so -0.0 and +0.0 tie and
+ *              the face number decides.  t[r] = that face's t as computed, +inf when nothing hits; face[r] = its number as int32, -1
+ *              when nothing hits; bary[r] = (U/det, V/det, W/det) of that face, zeros when nothing hits.
+ *   ANY HIT    any_hit != 0: hit[r] = 1 iff some face hits, which is face[r] >= 0 of the first-hit mode; the walk may stop at the first
+ *              hit it meets, and which face that is is not a function of the input, so d_t, d_face and d_bary must be NULL
+ *              (PB3D_EINVAL otherwise).  With any_hit == 0 d_hit must be NULL, d_t and d_face are required and d_bary may be NULL.
+ * Two properties the tests lean on:
+ *   SHARED EDGES  carries over from "mesh -> image": a sheared corner depends on its vertex and the ray only, so the value on an edge
+ *              is the same number up to sign in both faces that share it; a ray cannot pass between two faces that share an edge, and a
+ *              ray exactly on the edge hits both.
+ *   RENDER     With o = cam for every ray, R the identity and d = (sx, sy, 1) for the pixel's sx, sy with |sx|, |sy| < 1, the operations
+ *              are pb3d_render_mesh_resident's (frame 0), one for one: kz = 2, Sx = sx / 1 = sx, Sz = 1, the camera coordinates are
+ *              p - cam (the products with the identity's 0 and 1 add zeros), and t_min = near, t_max = +inf.  So t and face equal its
+ *              depth and face images bit for bit on any mesh.
+ * The walk.  The faces are binned by csrc/face_index.hip over all three axes, nothing skipped: a face is listed in every cell of
+ * cell_of(min corner) .. cell_of(max corner) per axis, and cell_of is monotone.  One lane per ray walks the layers of cells along kz, in
+ * the ray's direction, over the ray's kz range (o[kz] + t_min d[kz] .. o[kz] + t_max d[kz]) clipped to the box of the vertices.  Per layer
+ * it evaluates o[k] + S (z - o[kz]) for k = kx, ky at the layer's two bounding planes (the first and last layers reach the box's exact
+ * faces; both planes clipped to the ray's range), widens each interval, skips the layer if an interval misses the box, converts both ends
+ * with cell_of and tests every face listed in every cell of that rectangle (|Sx|, |Sy| <= 1: usually 1 - 4 cells).  A face listed in
+ * several visited cells is tested again; the minimum is idempotent.
+ *   MARGINS    tol = 1e-12 x the largest absolute coordinate among the box corners and the origin.  The ray's kz range is widened by tol
+ *              and each kx / ky interval by 4 tol.  Why that is conservative: where U, V, W agree in sign, U/det, V/det, W/det are
+ *              weights in [0, 1] up to rounding, t d[kz] is that weighted mean of the corners' A'[kz], and the sheared corners' weighted
+ *              mean is zero -- so the point of the EXACT ray at the hit's kz lies in the face's box on all three axes, up to the
+ *              rounding of some twenty operations on numbers no larger than |a - o|: a few 1e-16 of the largest coordinate, four
+ *              orders below tol.  The plane positions lo + c h and cell_of's own product differ from each other by as little.  Hence the
+ *              face is listed in a cell of the rectangle of the layer that holds that point.
+ *   EXIT       after a layer the walk stops when the best t so far is STRICTLY below t_far - (2 tol |Sz| + 1e-12 |t_far|), t_far =
+ *              (z - o[kz]) Sz of the layer's far plane z as it stands, unwidened: a face not yet tested hits, if at all, at or beyond
+ *              that plane up to the same roundings, so its t can neither be smaller nor tie.  (A far plane taken from the widened
+ *              interval with a single tol rounds to a tiny positive t for a plane through the origin, and stops one layer early on a
+ *              tie at t = -0.0 whose lower face number sits in the next layer.)
+ *   FAR ORIGINS  an origin 1e15 box sizes away makes tol exceed the box: every layer visits all its cells.  Slow, and correct.
+ * Host waits: the mesh check, the box of the vertices, one per count of the index's entries (1 + its halvings).  Knob "raycast_stats"
+ * (pb3d_set_tuning; one more host wait) counts, for pb3d_cast_rays_last, {rays that hit, bad rays, rays that visit no cell (they miss
+ * the box), face tests, cells visited, (cell, face) entries of the index}; PB3D_EINVAL if the context's last call was not counted.  Knob
+ * "raycast_timing" (one more host wait) times the index build and the query with events for pb3d_cast_rays_last_ms; PB3D_EINVAL if the
+ * last call was not timed.  Scratch: 72 bytes per face for the corners, 12 per cell and 4 per entry (at most 8 entries a face). */
+int pb3d_cast_rays_resident(pb3d_ctx* ctx, const void* d_origins, const void* d_dirs, int rays_f64, int64_t nrays, const void* d_verts,
+                            int verts_f64, int64_t nv, const void* d_faces, int faces_i64, int64_t nf, double t_min, double t_max, int any_hit,
+                            double* d_t /* nrays */, int32_t* d_face /* nrays */, double* d_bary /* nrays*3, or NULL */,
+                            uint8_t* d_hit /* nrays, any_hit only */);
+int pb3d_cast_rays_last(const pb3d_ctx* ctx, int64_t stats[6]);
+int pb3d_cast_rays_last_ms(const pb3d_ctx* ctx, double ms[2]);
+
 /* ---- density volume of a point cloud, reference utils/eval_helpers.py:178-189 (pointcloud_to_voxel_grid) ---------------------------
  * d_out: grid_size^3 float32, bit for bit the reference's volume for the resident (n, 3) list d_pts (float32 rows, or float64 with
  * pts_f64 = 1; any 4- / 8-byte aligned base):

@@ -147,7 +147,9 @@ const Knob kKnobs[] = {
     {"inside_timing", &pb3d_ctx::tune_inside_timing, 0, 1, "0 or 1 (time the index build and the query of a containment test with events)"},
     {"inside_order", &pb3d_ctx::tune_inside_order, 0, 1, "0 (queries in input order) or 1 (in the cell order of the index)"},
     {"inside_table", &pb3d_ctx::tune_inside_table, 0, 1, "0 (set-ups recomputed from the corner table) or 1 (read from a table of finished set-ups)"},
-    {"orient_tile", &pb3d_ctx::tune_orient_tile, 0, 1, "0 (128-pixel tiles where they apply) or 1 (never)"},
+    {"raycast_timing", &pb3d_ctx::tune_raycast_timing, 0, 1, "0 or 1 (time the index build and the query of a ray cast with events)"},
+    {"raycast_stats", &pb3d_ctx::tune_raycast_stats, 0, 1, "0 or 1 (count hits, bad rays, face tests and cells of a ray cast for pb3d_cast_rays_last)"},
+    {"orient_tile",&pb3d_ctx::tune_orient_tile, 0, 1, "0 (128-pixel tiles where they apply) or 1 (never)"},
     {"global_composed", &pb3d_ctx::tune_global_composed, 0, 1, "0 (mask bits -> sliced chain -> colours) or 1 (ones -> process -> colour)"},
     {"per_job", &pb3d_ctx::tune_per_job, 0, 1, "0 (merged / fused forms) or 1 (job by job)"},
     {"no_table_cache", &pb3d_ctx::tune_no_table_cache, 0, 1, "0 (tables cached across calls) or 1 (rebuilt every call)"},

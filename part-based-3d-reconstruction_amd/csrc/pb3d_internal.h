@@ -309,8 +309,20 @@ enum pb3d_slot : int {
     PB3D_SLOT_INSIDE_STATS = 173,
     PB3D_SLOT_INSIDE_PARTIALS = 174,
     PB3D_SLOT_INSIDE_SETUP = 175,                       // knob "inside_table" = 1 only: 184 bytes of finished set-up per face
+    // call-local, csrc/raycast.hip, all of them: the seven of its pb3d_face_index_build as above (the eighth read-back word is the flag
+    // of the mesh check in front); under knob "raycast_stats" six 64-bit totals and the five u64 partial counts of every workgroup of
+    // the query kernel.  The box pass inside uses NN_BOUNDS_PARTIALS
+    PB3D_SLOT_RAYCAST_CORNERS = 176,
+    PB3D_SLOT_RAYCAST_READBACK = 177,
+    PB3D_SLOT_RAYCAST_COUNTS = 178,
+    PB3D_SLOT_RAYCAST_STARTS = 179,
+    PB3D_SLOT_RAYCAST_IDS = 180,
+    PB3D_SLOT_RAYCAST_SCAN_LOCAL = 181,
+    PB3D_SLOT_RAYCAST_SCAN_SEGS = 182,
+    PB3D_SLOT_RAYCAST_STATS = 183,
+    PB3D_SLOT_RAYCAST_PARTIALS = 184,
 
-    PB3D_SLOT_COUNT = 176
+    PB3D_SLOT_COUNT = 185
 };
 
 // ---- the cell index of the exact nearest-neighbour search (csrc/nn.hip) -----------------------------------
@@ -417,6 +429,11 @@ struct pb3d_ctx {
     // the last pb3d_points_in_mesh_resident (csrc/inside.hip) for pb3d_points_in_mesh_last: cells along a0 and a1 of its index, (cell, face)
     // entries and halvings, as pb3d_face_index_build reports them; with inside_timing the milliseconds of the index build and of the query
     struct InsideLast { bool valid, timed; float ms[2]; i64 info[4]; } inside_last;
+    int tune_raycast_timing;    // knob "raycast_timing": 1 = pb3d_cast_rays_resident times its index build and its query with events (one more host wait)
+    int tune_raycast_stats;     // knob "raycast_stats": 1 = pb3d_cast_rays_resident counts hits, bad rays, face tests and cells for pb3d_cast_rays_last (one more host wait)
+    // the last pb3d_cast_rays_resident (csrc/raycast.hip) for pb3d_cast_rays_last / _last_ms: the six counts of a call under
+    // raycast_stats, the milliseconds of the index build and of the query of a call under raycast_timing
+    struct RaycastLast { bool counted, timed; float ms[2]; i64 stats[6]; } raycast_last;
     // Growable device scratch slots, named by enum pb3d_slot (no hipMalloc / hipFree per call once warm).
     void* scratch[PB3D_SLOT_COUNT];
     size_t scratch_bytes[PB3D_SLOT_COUNT];

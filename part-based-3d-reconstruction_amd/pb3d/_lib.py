@@ -205,6 +205,9 @@ _SIGNATURES = {
     "pb3d_render_shade_resident": [vp, vp, vp, i64, vp, C.c_int, i64, i64, vp, C.c_int, u8p, vp],
     "pb3d_render_last": [vp, i64p],
     "pb3d_render_last_ms": [vp, dblp],
+    "pb3d_cast_rays_resident": [vp, vp, vp, C.c_int, i64, vp, C.c_int, i64, vp, C.c_int, i64, C.c_double, C.c_double, C.c_int, vp, vp, vp, vp],
+    "pb3d_cast_rays_last": [vp, i64p],
+    "pb3d_cast_rays_last_ms": [vp, dblp],
 }
 class IouRow(C.Structure):
     """pb3d_iou_row (include/pb3d.h)"""

@@ -1,5 +1,5 @@
 """Device-resident timing of every op of the path (M1..M8 of SURVEY.md 8(d), plus the N1/N2 kernels of the notebook-1 chain) on
-synthetic inputs.  Development/measurement tool: python tools/opbench.py [--size 1024] [--shape WxHxD] [--ops M1,M3,...,N2,overlays,ICP,PLANE,MESHD,CLUSTER,DOWNSAMPLE,SMOOTH,SIMPLIFY,VOXELIZE,EDT,RENDER,ISO,MESHCOMP,INSIDE]; one JSON
+synthetic inputs.  Development/measurement tool: python tools/opbench.py [--size 1024] [--shape WxHxD] [--ops M1,M3,...,N2,overlays,ICP,PLANE,MESHD,CLUSTER,DOWNSAMPLE,SMOOTH,SIMPLIFY,VOXELIZE,EDT,RENDER,ISO,MESHCOMP,INSIDE,RAYCAST]; one JSON
 line per op.  Pricing: `alg_B_per_voxel` is SURVEY 8(d)'s algorithmic figure for the sweeps that are EXECUTED (a folded 0-degree step
 moves nothing and is not priced); ops whose intermediates are not bytes (the bit-sliced chains) also carry `moved_B_per_voxel`, the
 bytes that cross the HBM by design, and their `frac_of_8TBs` is computed from THAT (never from bytes that are not moved)."""
@@ -282,6 +282,8 @@ def main():
         mesh_components(a.reps, res)
     if "INSIDE" in ops:
         inside(a.reps, res)
+    if "RAYCAST" in ops:
+        raycast(a.reps, res)
     if "overlays" in ops:
         overlays(a.reps, res)
     if d_col is not None:
@@ -1586,6 +1588,141 @@ def inside(reps, res):
         print(json.dumps(r), flush=True)
         res.append(r)
     for b in (dv, df, d_lattice, d_ijk, d_vl, d_pts, d_sfm, d_in, d_vox):
+        b.free()
+
+
+def raycast(reps, res):
+    """RAYCAST, cast_rays / rays_occluded (csrc/raycast.hip) against the stride-1 mesh of the stored Taj grid (float32 vertices, int32
+    faces, resident, meshify's frame), every call whole: index build and host waits included, by device events, a row's call and its
+    yardstick timed in turn, rep by rep, in the same run (median and min / max of reps after one warm-up of each).  Every row carries the
+    call's own index / query split (knob raycast_timing) and face tests and cells per ray (knob raycast_stats); the rows also go to
+    profiles/raycast_opbench.jsonl.
+    RAYCAST/camera: the H x W rays of the stored final front camera (camera_rays, mapped into the mesh's frame), first hit, beside
+      render_mesh of the same view (depth and face); the share of pixels whose face agrees is reported, no bit equality is claimed.
+    RAYCAST/occlusion: the segments from the grid's own points (MESHD's queries) to that camera's centre, any hit on [1e-6, 1], beside
+      point_to_mesh_distances on the same queries.
+    RAYCAST/random: 1 M rays with uniform origins in the box of the vertices and normal directions, first hit and any hit."""
+    import pb3d.eval_helpers_intra as ev
+    import pb3d.render as rd
+    from pb3d.eval_helpers import point_to_mesh_distances_resident
+    L = pb3d._lib
+    g = os.path.join(ROOT, "tests", "golden")
+    taj = np.ascontiguousarray(np.load(os.path.join(g, "stored_Taj_voxel_grid.npz"))["voxel_grid"])
+    shape = taj.shape[:3]
+    D = float(shape[2])
+    cam = ev.load_camera_json(os.path.join(g, "stored_Taj_camera_params_final.json"), "front")
+    H, W = ev.resize_mask_to_voxel_grid(ev.load_mask(os.path.join(g, "data_Taj_front_mask.png")), taj).shape[:2]
+    d_g = dev.from_numpy(taj)
+    (dv, df, dn, dc), (nv, nf) = dev.meshify(d_g, taj.shape, stride=1, download=False)
+    for b in (d_g, dn, dc):
+        b.free()
+    verts = dv.download((nv, 3), np.float32)
+    to_mesh = lambda p: np.ascontiguousarray(np.stack([p[:, 0], p[:, 1], D - p[:, 2]], axis=1))       # noqa: E731  (points frame -> meshify's)
+    view = (cam["cam_pos"], cam["target"], cam["f"], cam["cx"], cam["cy"])
+
+    def stats(t):
+        return {"ms": round(float(np.median(t)), 4), "min_max_ms": [round(min(t), 4), round(max(t), 4)]}
+
+    def once(fn):
+        def run():
+            out = fn()
+            for b in (out if isinstance(out, tuple) else (out,)):
+                if isinstance(b, dev.DeviceBuffer):
+                    b.free()
+        return timeit(run, 1, warm=0)
+
+    def in_turn(fns):
+        for fn in fns.values():
+            once(fn)
+        t = {k: [] for k in fns}
+        for _ in range(reps):
+            for k, fn in fns.items():
+                t[k].append(once(fn))
+        return t
+
+    def own(fn, n):
+        """the call's own events (best of reps after a warm-up) and its counts"""
+        L.set_tuning("raycast_timing", 1)
+        L.set_tuning("raycast_stats", 1)
+        try:
+            ms = []
+            for _ in range(reps + 1):
+                once(fn)
+                ms.append(pb3d.cast_rays_last(timed=True))
+            st = pb3d.cast_rays_last()
+        finally:
+            L.set_tuning("raycast_timing", 0)
+            L.set_tuning("raycast_stats", 0)
+        i_ms, q_ms = min(m[0] for m in ms[1:]), min(m[1] for m in ms[1:])
+        return dict(index_ms=round(i_ms, 4), query_ms=round(q_ms, 4), index_share=round(i_ms / (i_ms + q_ms), 4),
+                    face_tests_per_ray=round(st["face_tests"] / n, 2), cells_per_ray=round(st["cells"] / n, 2),
+                    entries_per_face=round(st["entries"] / nf, 3), **st)
+
+    base = {"grid_shape": list(shape), "nverts": int(nv), "nfaces": int(nf), "reps": reps}
+    rows = []
+
+    # ---- (a) the camera's rays beside render_mesh
+    o, d = pb3d.camera_rays(*view, H, W)
+    n = H * W
+    d_o, d_d = dev.from_numpy(to_mesh(o)), dev.from_numpy(np.ascontiguousarray(d * np.array([1.0, 1.0, -1.0])))
+    first = lambda: pb3d.cast_rays_resident(d_o, d_d, n, dv, nv, df, nf, 1e-6, np.inf)                 # noqa: E731
+    render = lambda: rd.render_mesh_resident(dv, nv, df, nf, *view, H, W, frame="meshify", depth=shape[2])   # noqa: E731
+    a, b = first(), render()
+    face_r, face_c = b[1].download((H, W), np.int32), a[1].download((n,), np.int32).reshape(H, W)
+    t_r, t_c = b[0].download((H, W), np.float64), a[0].download((n,), np.float64).reshape(H, W)
+    for x in a + b:
+        x.free()
+    both = (face_r >= 0) & (face_c >= 0)
+    t = in_turn({"cast": first, "render": render})
+    med = {k: float(np.median(v)) for k, v in t.items()}
+    rows.append(dict(base, op="RAYCAST/camera", name="cast_rays: the rays of the stored final front camera, first hit", rays=n, image=[H, W],
+                     **stats(t["cast"]), Mray_s=round(n / med["cast"] / 1e3, 2), ratio_to_render_mesh=round(med["cast"] / med["render"], 3),
+                     hit_pixels=int((face_c >= 0).sum()), render_hit_pixels=int((face_r >= 0).sum()),
+                     same_face_share=round(float((face_r == face_c).mean()), 6),
+                     max_depth_difference=float(np.abs(t_r[both] - t_c[both]).max()) if both.any() else 0.0, **own(first, n)))
+    rows.append(dict(base, op="RAYCAST/camera", name="yardstick: render_mesh of the same view (depth and face)", image=[H, W], **stats(t["render"])))
+    d_o.free()
+    d_d.free()
+
+    # ---- (b) occlusion of the grid's own points towards the camera's centre beside the nearest-point search
+    occ = np.any(taj > 0, axis=-1)
+    ijk = np.argwhere(occ).astype(np.float64)
+    pts = np.ascontiguousarray(np.stack([ijk[:, 2], ijk[:, 1], D - ijk[:, 0]], axis=1))                 # voxel (i, j, k) in meshify's frame
+    n = len(pts)
+    eye = to_mesh(np.asarray(cam["cam_pos"], np.float64)[None, :])[0]
+    d_o, d_d = dev.from_numpy(pts), dev.from_numpy(np.ascontiguousarray(eye[None, :] - pts))
+    hidden = lambda: pb3d.rays_occluded_resident(d_o, d_d, n, dv, nv, df, nf, 1e-6, 1.0)               # noqa: E731
+    dist = lambda: point_to_mesh_distances_resident(d_o, n, dv, nv, df, nf, True, False, False)        # noqa: E731
+    t = in_turn({"occluded": hidden, "dist": dist})
+    med = {k: float(np.median(v)) for k, v in t.items()}
+    rows.append(dict(base, op="RAYCAST/occlusion", name="rays_occluded: the grid's own points towards the camera's centre, any hit on [1e-6, 1]",
+                     rays=n, **stats(t["occluded"]), Mray_s=round(n / med["occluded"] / 1e3, 2),
+                     ratio_to_point_to_mesh_distances=round(med["occluded"] / med["dist"], 3), **own(hidden, n)))
+    rows[-1]["visible_share"] = round(1.0 - rows[-1]["hits"] / n, 4)
+    rows.append(dict(base, op="RAYCAST/occlusion", name="yardstick: point_to_mesh_distances_resident on the same queries", queries=n,
+                     **stats(t["dist"])))
+    d_o.free()
+    d_d.free()
+
+    # ---- (c) scattered rays: uniform origins in the box, normal directions
+    rng = np.random.default_rng(0)
+    n = 1000000
+    lo, hi = verts.min(axis=0).astype(np.float64), verts.max(axis=0).astype(np.float64)
+    d_o, d_d = dev.from_numpy(rng.uniform(lo, hi, (n, 3))), dev.from_numpy(rng.normal(size=(n, 3)))
+    first = lambda: pb3d.cast_rays_resident(d_o, d_d, n, dv, nv, df, nf)                                # noqa: E731
+    anyh = lambda: pb3d.rays_occluded_resident(d_o, d_d, n, dv, nv, df, nf)                             # noqa: E731
+    t = in_turn({"first": first, "any": anyh})
+    med = {k: float(np.median(v)) for k, v in t.items()}
+    rows.append(dict(base, op="RAYCAST/random", name="cast_rays: 1 M rays, uniform origins in the box, normal directions, first hit", rays=n,
+                     **stats(t["first"]), Mray_s=round(n / med["first"] / 1e3, 2), **own(first, n)))
+    rows.append(dict(base, op="RAYCAST/random", name="rays_occluded: the same rays, any hit", rays=n, **stats(t["any"]),
+                     Mray_s=round(n / med["any"] / 1e3, 2), ratio_to_first_hit=round(med["any"] / med["first"], 3), **own(anyh, n)))
+    with open(os.path.join(ROOT, "profiles", "raycast_opbench.jsonl"), "w") as fh:
+        for r in rows:
+            print(json.dumps(r), flush=True)
+            fh.write(json.dumps(r) + "\n")
+            res.append(r)
+    for b in (dv, df, d_o, d_d):
         b.free()
 
 
