@@ -607,6 +607,78 @@ int pb3d_mesh_select_faces_resident(pb3d_ctx* ctx, const void* d_verts, int vert
                                     int32_t* d_index /* nv, or NULL */, int32_t* d_inverse /* nv, or NULL */,
                                     int32_t* d_face_index /* nf, or NULL */, int64_t counts[2] /* vertices, faces written */);
 
+/* ---- mesh repair: welding vertices by coordinate equality (csrc/weld.hip) and a consistent winding (csrc/orient.hip) -----------------------
+ * What a triangle soup (an STL-style CAD export: three vertices of its own per face) or a mesh of mixed winding needs before
+ * mesh_components, mesh_adjacency, mesh_smooth, mesh_simplify and the signed volumes mean anything.  trimesh's merge_vertices and
+ * repair.fix_winding / fix_inversion, Open3D's remove_duplicated_vertices and orient_triangles are the relatives; there is no upstream
+ * text, so the rules below are the specification, and both results are functions of the input and its order alone, to the bit.
+ *
+ * weld_vertices
+ *   INPUT      verts: (nv, 3) rows of float32 (verts_f64 = 0) or float64 (1), finite (the caller's promise: pb3d.weld_vertices checks
+ *              it on the host; a NaN would be compared by its bits).  faces (or NULL with nf = 0): (nf, 3) rows of int32 or int64 with
+ *              entries in [-nv, nv), wrapping as NumPy's do; anything else is PB3D_EINDEX, checked before anything is written (one host
+ *              wait).  Limits: nv <= 2^31 - 1, 3 nf <= 2^31 - 1.
+ *   EQUALITY   two vertices are one iff their three coordinates compare equal as IEEE numbers of the input's width: -0.0 == +0.0,
+ *              and nothing else that differs in a bit is equal.
+ *   CLASSES    a class's representative is its smallest input position; classes are numbered 0 .. m - 1 in the order of their
+ *              representatives (first appearance: voxel_downsample's FIRST numbering with equality classes for voxels).
+ *              out_verts[k] = the representative's row byte for byte (a -0.0 stays -0.0); index[k] = its position; inverse[i] = the
+ *              class of vertex i; class_counts[k] = the class's size.  A vertex no face names is welded like any other.
+ *   FACES      out_faces[j][a] = inverse[wrap(faces[j][a])] in the caller's index dtype, order and corner order: never negative.  A
+ *              face that becomes degenerate or a repeat stays (mesh_compact removes those).
+ *   ATTRIBUTES with d_colors ((nv, channels) uint8, channels 1 or 3): out_colors[k] = colors[index[k]], unblended.
+ *   EMPTY      nv = 0: *classes = 0, no host wait (nf > 0 is then PB3D_EINDEX).
+ * Outputs: d_out_verts room for nv rows, d_out_colors (given iff d_colors is) nv x channels, d_index and d_class_counts (nv int32 /
+ *   uint32, or NULL) of which the first *classes entries are written; d_inverse (nv int32, or NULL) and d_out_faces (nf rows, NULL iff
+ *   nf = 0) whole.  No output may alias an input.  Host waits: the index check (nf > 0) and *classes.
+ * One key word per 32 bits of coordinate (the raw bits, -0.0 mapped to +0.0: for finite values key equality is IEEE equality) and
+ * one stable radix sort of (word, position) pairs per word, three or six: the positions start ascending, so the first record of every
+ * run of equal rows is the class's smallest position.  No hashing, no per-class state, no atomics.  Scratch: about 50 bytes a vertex.
+ *
+ * mesh_orient
+ *   INPUT, RECORDS, EDGES  mesh_components' exactly, limits included.  verts (or NULL) are read for the volumes alone.
+ *   PAIR EDGES an undirected edge with c == 2 records is a PAIR EDGE; its two faces AGREE iff exactly one of the records is forward
+ *              (f == 1: they traverse the edge in opposite directions) and DISAGREE otherwise.  Edges with c == 1 or c > 2 connect
+ *              nothing: no winding is carried across a non-manifold edge.
+ *   PATCHES    the classes of the faces under pair edges alone, numbered 0 .. np - 1 by their smallest face position.  A patch is
+ *              ORIENTABLE iff a bit per face exists with flip[a] ^ flip[b] == disagree(a, b) on every pair edge; it is then unique
+ *              up to complementing the patch.
+ *   ANCHOR     in an orientable patch the smallest face keeps its winding (flip = 0), which fixes every other bit.  A patch that is
+ *              not orientable keeps every face as it came (flip = 0 throughout) and is reported.
+ *   SIGN       volume_sign = PB3D_ORIENT_POSITIVE or _NEGATIVE (needs verts, else PB3D_EINVAL) applies to the orientable patches
+ *              without a boundary edge.  V = mesh_components' ordered sum over the patch (its faces in ascending position in blocks
+ *              of 256, then the blocks, divided by 6.0) of the terms S_j of the INPUT winding, negated for a face the anchor rule
+ *              flips (swapping corners 1 and 2 negates S_j exactly, so this is the S_j of the flipped face).  If V has the wrong sign
+ *              (V < 0 under POSITIVE, V > 0 under NEGATIVE) the patch is INVERTED: every flip bit is complemented and V negated.
+ *              V == 0 or NaN changes nothing.  The rule is per patch: nested shells are not analysed, a cavity's shell ends with the
+ *              same sign as the outer one.  PB3D_ORIENT_KEEP: the anchor rule alone.
+ *   FACES OUT  d_out_faces (or NULL): row j as it came, negative entries included, in the caller's index dtype; a flipped face
+ *              (a, b, c) becomes (a, c, b), so the first corner stays.  Vertices are not touched.
+ *   COUNTS     d_counts (8 nf int64) holds eight arrays of np, one behind the other: faces, pair edges, disagreeing pair edges (of
+ *              the input), boundary edges (c == 1, counted for the patch of their face), records of the patch's faces on edges with
+ *              c > 2, flipped faces (final), orientable (0 / 1), inverted (0 / 1).  d_volume (or NULL; needs verts; nf float64): V
+ *              per patch, computed for every patch whether the sign rule covers it or not.
+ *   TOTALS     totals[8] = patches, orientable patches, pair edges, disagreeing pair edges, flipped faces, inverted patches, boundary
+ *              edges, non-manifold edges.  Read back once, the call's one host wait behind the index check.
+ *   EMPTY      nf = 0: totals all 0, no host wait.
+ * Outputs: d_flip (nf uint8) and d_patch (nf int32) whole.  No output may alias an input.
+ * The records, sorts, heads and scans are mesh_components' own (one copy).  Orientation is the same min-root union-find on a doubled
+ * forest of 2 nf nodes -- node j is "face j as it came", node nf + j "face j flipped" -- in which a pair edge with faces a, b and
+ * disagreement d unites a ~ b + d nf and a + nf ~ b + (1 - d) nf.  With r0, r1 the roots of j and nf + j: the patch is not orientable
+ * iff r0 == r1, its smallest face is min(r0, r1), and the anchor rule flips j iff r0 > r1 (roots are minima and every nf + k exceeds
+ * every face number, so the set that holds the anchor unflipped is rooted at the anchor; DESIGN.md "Mesh repair").  Scratch:
+ * mesh_components' and 8 + 16 bytes per face. */
+#define PB3D_ORIENT_KEEP 0
+#define PB3D_ORIENT_POSITIVE 1
+#define PB3D_ORIENT_NEGATIVE 2
+int pb3d_weld_vertices_resident(pb3d_ctx* ctx, const void* d_verts, int verts_f64, int64_t nv, const void* d_faces /* or NULL */, int faces_i64,
+                                int64_t nf, const uint8_t* d_colors /* nv x channels, or NULL */, int channels, void* d_out_verts /* nv rows */,
+                                void* d_out_faces /* nf rows */, uint8_t* d_out_colors /* or NULL */, int32_t* d_index /* nv, or NULL */,
+                                int32_t* d_inverse /* nv, or NULL */, uint32_t* d_class_counts /* nv, or NULL */, int64_t* classes);
+int pb3d_mesh_orient_resident(pb3d_ctx* ctx, const void* d_verts /* or NULL */, int verts_f64, int64_t nv, const void* d_faces, int faces_i64,
+                              int64_t nf, int volume_sign, uint8_t* d_flip /* nf */, int32_t* d_patch /* nf */, void* d_out_faces /* nf rows, or NULL */,
+                              int64_t* d_counts /* 8 nf */, double* d_volume /* nf, or NULL */, int64_t totals[8]);
+
 /* ---- mesh -> grid: exact solid voxelization of a triangle mesh by crossing parity, and the overlap of two grids (csrc/voxelize.hip) ------
  * The one conversion the other sections lack: a mesh (a CAD model, a smoothed marching-cubes mesh) becomes an occupancy, label or RGB grid
  * that the carve, paint, points and labelling entries take as it is.  Solid voxelization by crossing parity (Schwarz & Seidel 2010) with a

@@ -24,6 +24,7 @@
 #include <algorithm>
 
 #include "mesh_index.h"
+#include "mesh_records.h"
 #include "ordered_sum.h"
 #include "pb3d_internal.h"
 #include "union_find.h"
@@ -36,52 +37,9 @@ constexpr int kUnset = 0x7f7f7f7f;          // hipMemsetAsync(0x7f): above every
 constexpr int kBlock = 256;                 // faces per block of a component's sum
 constexpr int kCountBlocks = 4;             // workgroups per CU of the counting kernels: each wavefront flushes its counts once
 
-struct Rec { u32 src, dst; };
-// record r = 3j + a is the directed edge (corner a, corner a + 1 mod 3) of face j
-__device__ __forceinline__ Rec load_rec(const u32* __restrict__ W, u32 r) {
-    const u32 a = r % 3u;
-    return Rec{W[r], a == 2u ? W[r - 2u] : W[r + 1u]};
-}
-__device__ __forceinline__ bool is_loop(const Rec& e) { return e.src == e.dst; }
-__device__ __forceinline__ u32 lo_of(const Rec& e) { return e.src < e.dst ? e.src : e.dst; }
-__device__ __forceinline__ u32 hi_of(const Rec& e) { return e.src < e.dst ? e.dst : e.src; }
-
-// ---- counting by integer atomics, few of them ------------------------------------------------------------------------------------------
-// The counting kernels walk their items in a grid-stride loop whose trip count is the same in every lane of a wavefront (wave_base),
-// and keep what they count in wave-uniform registers: an atomic on one word costs about as much as a whole wavefront of plain work, and
-// a mesh that is mostly one component would send every wavefront's count to the same word.
-__device__ __forceinline__ i64 wave_base() { return (i64)blockIdx.x * 256 + (threadIdx.x & ~63u); }
-__device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63u); }
-
-// a total: the lanes with `flag`, added up per wavefront and flushed once
-struct WaveTotal {
-    unsigned long long n = 0;
-    __device__ __forceinline__ void add(bool flag) { n += (unsigned long long)__popcll(__ballot(flag)); }
-    __device__ __forceinline__ void flush(unsigned long long* dst) const { if (n && lane_id() == 0) atomicAdd(dst, n); }
-};
-// a count per label, add_size of csrc/cluster.hip carried across the loop: the lanes that hold the first counting lane's label go to
-// the run (flushed when that label changes, and at the end), every other counting lane adds on its own.  lab < 0 or !flag: no count
-struct RunCount {
-    int lab = -1;
-    unsigned long long n = 0;
-    __device__ __forceinline__ void flush(unsigned long long* sizes) {
-        if (n && lane_id() == 0) atomicAdd(&sizes[lab], n);
-        n = 0;
-    }
-    __device__ __forceinline__ void add(unsigned long long* sizes, int l, bool flag) {
-        const bool counts = flag && l >= 0;
-        const unsigned long long active = __ballot(counts);
-        if (!active) return;
-        const int first = __shfl(l, __ffsll(active) - 1);
-        if (first != lab) { flush(sizes); lab = first; }
-        n += (unsigned long long)__popcll(__ballot(counts && l == first));
-        if (counts && l != first) atomicAdd(&sizes[l], 1ull);
-    }
-};
-
 template <bool I64>
 __global__ __launch_bounds__(256) void k_records(const void* __restrict__ faces, i64 nf, i64 nv, u32* __restrict__ W, u32* __restrict__ key,
-                                                 u32* __restrict__ val, int* __restrict__ face_parent, unsigned long long* totals) {
+                                                 u32* __restrict__ val, int* __restrict__ face_parent, unsigned long long* loops_total) {
     const i64 j = (i64)blockIdx.x * 256 + threadIdx.x;
     if (j >= nf) return;
     u32 w[3];
@@ -99,7 +57,7 @@ __global__ __launch_bounds__(256) void k_records(const void* __restrict__ faces,
         loops += is_loop(e) ? 1 : 0;
     }
     if (face_parent) face_parent[j] = (int)j;
-    if (loops) atomicAdd(&totals[7], (unsigned long long)loops);
+    if (loops && loops_total) atomicAdd(loops_total, (unsigned long long)loops);
 }
 
 // key[p] = lo of the record at sorted place p
@@ -267,11 +225,11 @@ __global__ __launch_bounds__(256) void k_vertex_labels(const int* __restrict__ l
 }
 
 // ---- the measures --------------------------------------------------------------------------------------------------------------------
-// AS[2j] = A_j, AS[2j + 1] = S_j, every operation one rounded float64 operation (-ffp-contract=off); and the first pairs of the
-// (label, face) sort
+// AS[2j] = A_j, AS[2j + 1] = S_j (-S_j where negate, unless null, is not 0: csrc/orient.hip's flipped faces), every operation one
+// rounded float64 operation (-ffp-contract=off); and the first pairs of the (label, face) sort
 template <bool F64>
 __global__ __launch_bounds__(256) void k_face_measures(const void* __restrict__ verts, const u32* __restrict__ W, i64 nf, const int* __restrict__ face_labels,
-                                                       double* __restrict__ AS, u32* __restrict__ key, u32* __restrict__ val) {
+                                                       const u32* __restrict__ negate, double* __restrict__ AS, u32* __restrict__ key, u32* __restrict__ val) {
     const i64 j = (i64)blockIdx.x * 256 + threadIdx.x;
     if (j >= nf) return;
     double a[3], b[3], c[3];
@@ -283,7 +241,8 @@ __global__ __launch_bounds__(256) void k_face_measures(const void* __restrict__ 
     const double nx = e1y * e2z - e1z * e2y, ny = e1z * e2x - e1x * e2z, nz = e1x * e2y - e1y * e2x;
     AS[2 * j] = 0.5 * __dsqrt_rn((nx * nx + ny * ny) + nz * nz);
     const double mx = b[1] * c[2] - b[2] * c[1], my = b[2] * c[0] - b[0] * c[2], mz = b[0] * c[1] - b[1] * c[0];
-    AS[2 * j + 1] = (a[0] * mx + a[1] * my) + a[2] * mz;
+    const double S = (a[0] * mx + a[1] * my) + a[2] * mz;
+    AS[2 * j + 1] = negate && negate[j] ? -S : S;
     key[j] = (u32)face_labels[j];
     val[j] = (u32)j;
 }
@@ -336,6 +295,17 @@ __global__ __launch_bounds__(256) void k_component_sums(const double* __restrict
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
 inline dim3 grid_for(i64 n) { return dim3((unsigned)((n + 255) / 256)); }
 
+int scan(pb3d_ctx* ctx, const u32* flags, i64 n, i64* ranks) {
+    return pb3d_scan_counts(ctx, flags, n, ranks, PB3D_SLOT_MESHCOMP_SCAN_LOCAL, PB3D_SLOT_MESHCOMP_SCAN_SEGS);
+}
+int sort(pb3d_ctx* ctx, u32*& key, u32*& val, u32*& key2, u32*& val2, i64 n, i64 m) {
+    const u32 *ks, *vs;
+    PB3D_TRY(pb3d_sort_pairs(ctx, key, val, key2, val2, n, m, PB3D_SLOT_MESHCOMP_SORT_HIST, PB3D_SLOT_MESHCOMP_SCAN_LOCAL,
+                             PB3D_SLOT_MESHCOMP_SCAN_SEGS, &ks, &vs));
+    if (vs != val) { std::swap(key, key2); std::swap(val, val2); }
+    return PB3D_OK;
+}
+
 struct Args {
     const void* verts; int verts_f64; i64 nv;
     const void* faces; int faces_i64; i64 nf;
@@ -349,115 +319,57 @@ struct Args {
 int run(pb3d_ctx* ctx, const Args& s, int64_t totals[8]) {
     const i64 nf = s.nf, nv = s.nv, R = 3 * nf;
     const bool measured = s.measures != nullptr;
-    void *ww, *kv, *fl, *rk, *hp, *pa, *mf = nullptr, *rf, *rr, *vl, *sg = nullptr, *ms = nullptr, *tt;
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESHCOMP_CORNERS, (size_t)R * sizeof(u32), &ww));
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESHCOMP_PAIRS, (size_t)R * 4 * sizeof(u32), &kv));
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESHCOMP_FLAGS, (size_t)R * 2 * sizeof(u32), &fl));
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESHCOMP_RANKS, (size_t)(R + 1) * 2 * sizeof(i64), &rk));
-    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESHCOMP_HEADS, (size_t)(R + 1) * sizeof(u32), &hp));
+    void *pa, *mf = nullptr, *rf, *rr, *vl, *own = nullptr, *tt;
+    pb3d_edge_records rec;
+    PB3D_TRY(pb3d_mesh_edge_records_reserve(ctx, nf, &rec));
     PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESHCOMP_PARENT, (size_t)(s.by_edge ? nf : nv) * sizeof(int), &pa));
     if (!s.by_edge) PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESHCOMP_MIN_FACE, (size_t)nv * sizeof(int), &mf));
     PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESHCOMP_ROOT_FLAGS, (size_t)nf * sizeof(u32), &rf));
     PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESHCOMP_ROOT_RANKS, (size_t)(nf + 1) * sizeof(i64), &rr));
     PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESHCOMP_VERTEX_LABELS, (size_t)nv * sizeof(int), &vl));
-    // the segments' slot: [face counts | block counts] u32, [segment starts | block starts] int64, then the counts nobody asked for
-    const size_t seg_u32 = (size_t)nf * 2 * sizeof(u32), seg_i64 = (size_t)(nf + 1) * 2 * sizeof(i64);
-    if (measured || !s.counts)
-        PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESHCOMP_SEGMENTS, seg_u32 + seg_i64 + (s.counts ? 0 : (size_t)nf * 5 * sizeof(i64)), &sg));
-    if (measured) PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESHCOMP_MEASURES, (size_t)nf * 4 * sizeof(double), &ms));
+    // the segments' slot: the sums' tables, then the counts nobody asked for
+    if (measured || !s.counts) PB3D_TRY(pb3d_mesh_ordered_sums_reserve(ctx, nf, measured, s.counts ? 0 : (size_t)nf * 5 * sizeof(i64), &own));
     PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESHCOMP_TOTALS, 8 * sizeof(i64), &tt));
-    // the scans of the call are the sorts' run tables and the flag arrays': size both scan slots for the largest now, so that none
-    // regrows (and waits) midway
-    PB3D_TRY(pb3d_scan_reserve(ctx, std::max<i64>(R, pb3d_sort_scan_items(R)), PB3D_SLOT_MESHCOMP_SCAN_LOCAL, PB3D_SLOT_MESHCOMP_SCAN_SEGS));
-    u32 *W = (u32*)ww, *head = (u32*)fl, *fwd = (u32*)fl + R, *pos = (u32*)hp, *root_flag = (u32*)rf;
-    i64 *head_rank = (i64*)rk, *fwd_rank = (i64*)rk + (R + 1), *root_rank = (i64*)rr;
+    u32* root_flag = (u32*)rf;
+    i64* root_rank = (i64*)rr;
     int *parent = (int*)pa, *min_face = (int*)mf, *vlab = (int*)vl;
     unsigned long long* tot = (unsigned long long*)tt;
-    unsigned long long* counts = s.counts ? (unsigned long long*)s.counts : (unsigned long long*)((char*)sg + seg_u32 + seg_i64);
+    unsigned long long* counts = s.counts ? (unsigned long long*)s.counts : (unsigned long long*)own;
     const i64* nc = root_rank + nf;
-    auto scan = [&](const u32* flags, i64 n, i64* ranks) -> int {
-        return pb3d_scan_counts(ctx, flags, n, ranks, PB3D_SLOT_MESHCOMP_SCAN_LOCAL, PB3D_SLOT_MESHCOMP_SCAN_SEGS);
-    };
-    auto sort = [&](u32*& key, u32*& val, u32*& key2, u32*& val2, i64 n, i64 m) -> int {
-        const u32 *ks, *vs;
-        PB3D_TRY(pb3d_sort_pairs(ctx, key, val, key2, val2, n, m, PB3D_SLOT_MESHCOMP_SORT_HIST, PB3D_SLOT_MESHCOMP_SCAN_LOCAL,
-                                 PB3D_SLOT_MESHCOMP_SCAN_SEGS, &ks, &vs));
-        if (vs != val) { std::swap(key, key2); std::swap(val, val2); }
-        return PB3D_OK;
-    };
 
     PB3D_HIP(hipMemsetAsync(tot, 0, 8 * sizeof(i64), ctx->stream));
     PB3D_HIP(hipMemsetAsync(vlab, 0x7f, (size_t)nv * sizeof(int), ctx->stream));
-    // ---- the records in (lo, hi) order
-    u32 *key = (u32*)kv, *val = key + R, *key2 = key + 2 * R, *val2 = key + 3 * R;
-    hipLaunchKernelGGL((s.faces_i64 ? k_records<true> : k_records<false>), grid_for(nf), dim3(256), 0, ctx->stream, s.faces, nf, nv, W, key, val,
-                       s.by_edge ? parent : (int*)nullptr, tot);
-    PB3D_CHECK_LAUNCH();
-    PB3D_TRY(sort(key, val, key2, val2, R, nv + 1));
-    hipLaunchKernelGGL(k_next_key, grid_for(R), dim3(256), 0, ctx->stream, (const u32*)W, (const u32*)val, R, (u32)nv, key);
-    PB3D_CHECK_LAUNCH();
-    PB3D_TRY(sort(key, val, key2, val2, R, nv + 1));
-    // ---- run heads, forward bits and, under "edge", the unions
-    hipLaunchKernelGGL(k_heads, grid_for(R), dim3(256), 0, ctx->stream, (const u32*)W, (const u32*)val, R, head, fwd,
-                       s.by_edge ? parent : (int*)nullptr);
-    PB3D_CHECK_LAUNCH();
-    PB3D_TRY(scan(head, R, head_rank));
-    PB3D_TRY(scan(fwd, R, fwd_rank));
-    hipLaunchKernelGGL(k_head_positions, grid_for(R + 1), dim3(256), 0, ctx->stream, (const u32*)W, (const u32*)val, R, (const u32*)head,
-                       (const i64*)head_rank, pos);
-    PB3D_CHECK_LAUNCH();
+    // ---- the records in (lo, hi) order, run heads, forward bits and, under "edge", the unions
+    PB3D_TRY(pb3d_mesh_edge_records_build(ctx, s.faces, s.faces_i64, nf, nv, s.by_edge ? parent : (int*)nullptr, &tot[7], &rec));
+    const u32 *W = rec.W, *val = rec.val;
     // ---- the components and their numbers
     if (s.by_edge) {
-        hipLaunchKernelGGL(k_flatten, grid_for(nf), dim3(256), 0, ctx->stream, nf, parent, root_flag);
-        PB3D_CHECK_LAUNCH();
+        PB3D_TRY(pb3d_forest_flatten(ctx, nf, parent, root_flag));
     } else {
         PB3D_HIP(hipMemsetAsync(min_face, 0x7f, (size_t)nv * sizeof(int), ctx->stream));
-        hipLaunchKernelGGL(k_iota, grid_for(nv), dim3(256), 0, ctx->stream, parent, nv);
+        PB3D_TRY(pb3d_forest_init(ctx, parent, nv));
+        hipLaunchKernelGGL(k_union_vertices, grid_for(nf), dim3(256), 0, ctx->stream, W, nf, parent);
         PB3D_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_union_vertices, grid_for(nf), dim3(256), 0, ctx->stream, (const u32*)W, nf, parent);
+        PB3D_TRY(pb3d_forest_flatten(ctx, nv, parent, nullptr));
+        hipLaunchKernelGGL(k_min_face, grid_for(nf), dim3(256), 0, ctx->stream, W, nf, (const int*)parent, min_face);
         PB3D_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_flatten, grid_for(nv), dim3(256), 0, ctx->stream, nv, parent, (u32*)nullptr);
-        PB3D_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_min_face, grid_for(nf), dim3(256), 0, ctx->stream, (const u32*)W, nf, (const int*)parent, min_face);
-        PB3D_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_first_faces, grid_for(nf), dim3(256), 0, ctx->stream, (const u32*)W, nf, (const int*)parent, (const int*)min_face, root_flag);
+        hipLaunchKernelGGL(k_first_faces, grid_for(nf), dim3(256), 0, ctx->stream, W, nf, (const int*)parent, (const int*)min_face, root_flag);
         PB3D_CHECK_LAUNCH();
     }
-    PB3D_TRY(scan(root_flag, nf, root_rank));
+    PB3D_TRY(scan(ctx, root_flag, nf, root_rank));
     hipLaunchKernelGGL(k_clear_counts, dim3(pb3d_stream_blocks(ctx, 5 * nf, 256, 8)), dim3(256), 0, ctx->stream, counts, nc,
-                       (const i64*)head_rank + R, nf, tot);
+                       (const i64*)rec.head_rank + R, nf, tot);
     PB3D_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_labels, dim3(pb3d_stream_blocks(ctx, nf, 256, kCountBlocks)), dim3(256), 0, ctx->stream, (const u32*)W, nf, (const int*)parent, (const int*)min_face,
+    hipLaunchKernelGGL(k_labels, dim3(pb3d_stream_blocks(ctx, nf, 256, kCountBlocks)), dim3(256), 0, ctx->stream, W, nf, (const int*)parent, (const int*)min_face,
                        (const i64*)root_rank, s.face_labels, vlab, counts);
     PB3D_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_edges, dim3(pb3d_stream_blocks(ctx, R, 256, kCountBlocks)), dim3(256), 0, ctx->stream, (const u32*)val, R, (const i64*)head_rank, (const i64*)fwd_rank,
-                       (const u32*)pos, (const int*)s.face_labels, nc, counts, tot);
+    hipLaunchKernelGGL(k_edges, dim3(pb3d_stream_blocks(ctx, R, 256, kCountBlocks)), dim3(256), 0, ctx->stream, val, R, (const i64*)rec.head_rank, (const i64*)rec.fwd_rank,
+                       (const u32*)rec.pos, (const int*)s.face_labels, nc, counts, tot);
     PB3D_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_vertex_labels, dim3(pb3d_stream_blocks(ctx, nv, 256, kCountBlocks)), dim3(256), 0, ctx->stream, (const int*)vlab, nv, s.vertex_labels, tot);
     PB3D_CHECK_LAUNCH();
     // ---- area and volume
-    if (measured) {
-        double *AS = (double*)ms, *block_sum = AS + 2 * nf;
-        u32 *nfaces = (u32*)sg, *nblocks = nfaces + nf;
-        i64 *seg_start = (i64*)((char*)sg + seg_u32), *block_start = seg_start + (nf + 1);
-        key = (u32*)kv; val = key + nf; key2 = key + 2 * nf; val2 = key + 3 * nf;      // the records are spent
-        if (s.verts_f64)
-            hipLaunchKernelGGL(k_face_measures<true>, grid_for(nf), dim3(256), 0, ctx->stream, s.verts, (const u32*)W, nf, (const int*)s.face_labels, AS, key, val);
-        else
-            hipLaunchKernelGGL(k_face_measures<false>, grid_for(nf), dim3(256), 0, ctx->stream, s.verts, (const u32*)W, nf, (const int*)s.face_labels, AS, key, val);
-        PB3D_CHECK_LAUNCH();
-        PB3D_TRY(sort(key, val, key2, val2, nf, nf));
-        hipLaunchKernelGGL(k_segment_counts, grid_for(nf), dim3(256), 0, ctx->stream, (const unsigned long long*)counts, nc, nf, nfaces, nblocks);
-        PB3D_CHECK_LAUNCH();
-        PB3D_TRY(scan(nfaces, nf, seg_start));
-        PB3D_TRY(scan(nblocks, nf, block_start));
-        hipLaunchKernelGGL(k_block_sums, dim3(pb3d_stream_blocks(ctx, nf / kBlock + nf / 64 + 1, 4, 32)), dim3(256), 0, ctx->stream, (const u32*)val,
-                           (const double*)AS, (const i64*)seg_start, (const i64*)block_start, nc, block_sum);
-        PB3D_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_component_sums, dim3(pb3d_stream_blocks(ctx, nf / 64 + 1, 4, 32)), dim3(256), 0, ctx->stream, (const double*)block_sum,
-                           (const i64*)block_start, nc, s.measures);
-        PB3D_CHECK_LAUNCH();
-    }
+    if (measured) PB3D_TRY(pb3d_mesh_ordered_sums(ctx, s.verts, s.verts_f64, rec, nf, s.face_labels, nullptr, counts, nc, s.measures));
     i64 got[8];
     PB3D_TRY(pb3d_read_back(ctx, got, tot, sizeof(got)));
     for (int a = 0; a < 8; ++a) totals[a] = got[a];
@@ -465,6 +377,94 @@ int run(pb3d_ctx* ctx, const Args& s, int64_t totals[8]) {
 }
 
 }  // namespace
+
+// ---- what csrc/orient.hip shares (pb3d_internal.h) ------------------------------------------------------------------------------------------
+int pb3d_mesh_edge_records_reserve(pb3d_ctx* ctx, i64 nf, pb3d_edge_records* rec) {
+    const i64 R = 3 * nf;
+    void *ww, *kv, *fl, *rk, *hp;
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESHCOMP_CORNERS, (size_t)R * sizeof(u32), &ww));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESHCOMP_PAIRS, (size_t)R * 4 * sizeof(u32), &kv));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESHCOMP_FLAGS, (size_t)R * 2 * sizeof(u32), &fl));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESHCOMP_RANKS, (size_t)(R + 1) * 2 * sizeof(i64), &rk));
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESHCOMP_HEADS, (size_t)(R + 1) * sizeof(u32), &hp));
+    // the scans of the call are the sorts' run tables and the flag arrays': size both scan slots for the largest now, so that none
+    // regrows (and waits) midway
+    PB3D_TRY(pb3d_scan_reserve(ctx, std::max<i64>(R, pb3d_sort_scan_items(R)), PB3D_SLOT_MESHCOMP_SCAN_LOCAL, PB3D_SLOT_MESHCOMP_SCAN_SEGS));
+    *rec = {(u32*)ww, (u32*)kv, nullptr, (u32*)fl, (u32*)fl + R, (i64*)rk, (i64*)rk + (R + 1), (u32*)hp};
+    return PB3D_OK;
+}
+
+int pb3d_mesh_edge_records_build(pb3d_ctx* ctx, const void* d_faces, int faces_i64, i64 nf, i64 nv, int* face_parent, unsigned long long* loops,
+                                 pb3d_edge_records* rec) {
+    const i64 R = 3 * nf;
+    u32 *W = rec->W, *key = rec->pairs, *val = key + R, *key2 = key + 2 * R, *val2 = key + 3 * R;
+    hipLaunchKernelGGL((faces_i64 ? k_records<true> : k_records<false>), grid_for(nf), dim3(256), 0, ctx->stream, d_faces, nf, nv, W, key, val, face_parent,
+                       loops);
+    PB3D_CHECK_LAUNCH();
+    PB3D_TRY(sort(ctx, key, val, key2, val2, R, nv + 1));
+    hipLaunchKernelGGL(k_next_key, grid_for(R), dim3(256), 0, ctx->stream, (const u32*)W, (const u32*)val, R, (u32)nv, key);
+    PB3D_CHECK_LAUNCH();
+    PB3D_TRY(sort(ctx, key, val, key2, val2, R, nv + 1));
+    hipLaunchKernelGGL(k_heads, grid_for(R), dim3(256), 0, ctx->stream, (const u32*)W, (const u32*)val, R, rec->head, rec->fwd, face_parent);
+    PB3D_CHECK_LAUNCH();
+    PB3D_TRY(scan(ctx, rec->head, R, rec->head_rank));
+    PB3D_TRY(scan(ctx, rec->fwd, R, rec->fwd_rank));
+    hipLaunchKernelGGL(k_head_positions, grid_for(R + 1), dim3(256), 0, ctx->stream, (const u32*)W, (const u32*)val, R, (const u32*)rec->head,
+                       (const i64*)rec->head_rank, rec->pos);
+    PB3D_CHECK_LAUNCH();
+    rec->val = val;
+    return PB3D_OK;
+}
+
+int pb3d_forest_init(pb3d_ctx* ctx, int* parent, i64 n) {
+    hipLaunchKernelGGL(k_iota, grid_for(n), dim3(256), 0, ctx->stream, parent, n);
+    PB3D_CHECK_LAUNCH();
+    return PB3D_OK;
+}
+
+int pb3d_forest_flatten(pb3d_ctx* ctx, i64 n, int* parent, u32* root_flag) {
+    hipLaunchKernelGGL(k_flatten, grid_for(n), dim3(256), 0, ctx->stream, n, parent, root_flag);
+    PB3D_CHECK_LAUNCH();
+    return PB3D_OK;
+}
+
+// the segments' slot: [face counts | block counts] u32, [segment starts | block starts] int64, then the caller's bytes
+static size_t seg_u32_bytes(i64 nf) { return (size_t)nf * 2 * sizeof(u32); }
+static size_t seg_i64_bytes(i64 nf) { return (size_t)(nf + 1) * 2 * sizeof(i64); }
+
+int pb3d_mesh_ordered_sums_reserve(pb3d_ctx* ctx, i64 nf, bool sums, size_t extra_bytes, void** extra) {
+    void *sg, *ms;
+    PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESHCOMP_SEGMENTS, seg_u32_bytes(nf) + seg_i64_bytes(nf) + extra_bytes, &sg));
+    if (sums) PB3D_TRY(pb3d_scratch(ctx, PB3D_SLOT_MESHCOMP_MEASURES, (size_t)nf * 4 * sizeof(double), &ms));
+    if (extra) *extra = (char*)sg + seg_u32_bytes(nf) + seg_i64_bytes(nf);
+    return PB3D_OK;
+}
+
+int pb3d_mesh_ordered_sums(pb3d_ctx* ctx, const void* d_verts, int verts_f64, const pb3d_edge_records& rec, i64 nf, const int* face_labels,
+                           const u32* negate, const unsigned long long* faces_of, const i64* nc, double* measures) {
+    void *sg = ctx->scratch[PB3D_SLOT_MESHCOMP_SEGMENTS], *ms = ctx->scratch[PB3D_SLOT_MESHCOMP_MEASURES];     // _reserve's
+    double *AS = (double*)ms, *block_sum = AS + 2 * nf;
+    u32 *nfaces = (u32*)sg, *nblocks = nfaces + nf;
+    i64 *seg_start = (i64*)((char*)sg + seg_u32_bytes(nf)), *block_start = seg_start + (nf + 1);
+    u32 *key = rec.pairs, *val = key + nf, *key2 = key + 2 * nf, *val2 = key + 3 * nf;      // the records are spent
+    if (verts_f64)
+        hipLaunchKernelGGL(k_face_measures<true>, grid_for(nf), dim3(256), 0, ctx->stream, d_verts, (const u32*)rec.W, nf, face_labels, negate, AS, key, val);
+    else
+        hipLaunchKernelGGL(k_face_measures<false>, grid_for(nf), dim3(256), 0, ctx->stream, d_verts, (const u32*)rec.W, nf, face_labels, negate, AS, key, val);
+    PB3D_CHECK_LAUNCH();
+    PB3D_TRY(sort(ctx, key, val, key2, val2, nf, nf));
+    hipLaunchKernelGGL(k_segment_counts, grid_for(nf), dim3(256), 0, ctx->stream, faces_of, nc, nf, nfaces, nblocks);
+    PB3D_CHECK_LAUNCH();
+    PB3D_TRY(scan(ctx, nfaces, nf, seg_start));
+    PB3D_TRY(scan(ctx, nblocks, nf, block_start));
+    hipLaunchKernelGGL(k_block_sums, dim3(pb3d_stream_blocks(ctx, nf / kBlock + nf / 64 + 1, 4, 32)), dim3(256), 0, ctx->stream, (const u32*)val,
+                       (const double*)AS, (const i64*)seg_start, (const i64*)block_start, nc, block_sum);
+    PB3D_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_component_sums, dim3(pb3d_stream_blocks(ctx, nf / 64 + 1, 4, 32)), dim3(256), 0, ctx->stream, (const double*)block_sum,
+                       (const i64*)block_start, nc, measures);
+    PB3D_CHECK_LAUNCH();
+    return PB3D_OK;
+}
 
 extern "C" {
 

@@ -321,8 +321,30 @@ enum pb3d_slot : int {
     PB3D_SLOT_RAYCAST_SCAN_SEGS = 182,
     PB3D_SLOT_RAYCAST_STATS = 183,
     PB3D_SLOT_RAYCAST_PARTIALS = 184,
+    // call-local, csrc/orient.hip.  The records, their sorts, flags, ranks and edge starts are csrc/meshcomp.hip's front half in the
+    // MESHCOMP_* slots (pb3d_mesh_edge_records), and the signed sums its MESHCOMP_SEGMENTS / MESHCOMP_MEASURES (pb3d_mesh_ordered_sums).
+    // Its own: the doubled forest's parent (2 nf int32: node j is face j as it came, node nf + j face j flipped); the "smallest face
+    // of its patch" flags and the anchor-rule flip bits (nf u32 each); the flags' ranks (nf + 1 int64); area and volume per patch as
+    // the sums leave them (2 nf float64); the eight totals
+    PB3D_SLOT_ORIENT_PARENT = 185,
+    PB3D_SLOT_ORIENT_FLAGS = 186,
+    PB3D_SLOT_ORIENT_RANKS = 187,
+    PB3D_SLOT_ORIENT_MEASURES = 188,
+    PB3D_SLOT_ORIENT_TOTALS = 189,
+    // call-local, csrc/weld.hip, all of them: the (key word, position) pairs of the three or six stable sorts (key, val and their
+    // ping-pong twins, nv u32 each) and the sorts' run table; the run-head flags in sorted order and the "representative" flags in
+    // input order (nv u32 each); their ranks (nv + 1 int64 each); where every run starts (nv + 1 u32), each vertex's representative
+    // (nv int32) and each representative's class size (nv u32); the two slots of every pb3d_scan_counts of the call.  The class count the
+    // host reads back is the last rank.  The index check in front uses SURF_FLAG
+    PB3D_SLOT_WELD_PAIRS = 190,
+    PB3D_SLOT_WELD_SORT_HIST = 191,
+    PB3D_SLOT_WELD_FLAGS = 192,
+    PB3D_SLOT_WELD_RANKS = 193,
+    PB3D_SLOT_WELD_RUNS = 194,
+    PB3D_SLOT_WELD_SCAN_LOCAL = 195,
+    PB3D_SLOT_WELD_SCAN_SEGS = 196,
 
-    PB3D_SLOT_COUNT = 185
+    PB3D_SLOT_COUNT = 197
 };
 
 // ---- the cell index of the exact nearest-neighbour search (csrc/nn.hip) -----------------------------------
@@ -640,7 +662,8 @@ int pb3d_scan_counts(pb3d_ctx* ctx, const u32* d_counts, i64 n, i64* d_offsets, 
 // the two slots grown for a scan of n counts (pb3d_scan_counts does it itself): a caller with several scans ahead reserves for the
 // largest first, so that no slot regrows (and waits) midway
 int pb3d_scan_reserve(pb3d_ctx* ctx, i64 n, pb3d_slot local_slot, pb3d_slot seg_slot);
-// csrc/sort_pairs.hip for csrc/downsample.hip and csrc/smooth.hip: the n >= 1 pairs (key[i], val[i]) sorted stably by key < m, through
+// csrc/sort_pairs.hip for csrc/downsample.hip and csrc/smooth.hip: the n >= 1 pairs (key[i], val[i]) sorted stably by key < m
+// (2 <= m <= 2^32: with m = 2^32 every bit of the key counts, as csrc/weld.hip's coordinate words need), through
 // the ping-pong twins key2 / val2 (four arrays of n u32, none overlapping).  *key_sorted (unless null) and *val_sorted = the two of
 // the four that hold the result.  hist_slot takes the run table (256 runs per tile of pb3d_sort_tile pairs: int64 starts, then u32
 // counts); the scans inside use scan_local_slot and scan_segs_slot, for pb3d_sort_scan_items(n) counts each.  Enqueued
@@ -678,6 +701,31 @@ int pb3d_select_kth(pb3d_ctx* ctx, const double* d_vals, i64 n, const i64* d_ran
 // csrc/surface.hip for csrc/normals.hip: PB3D_EINDEX (message "<what>: index out of bounds ...") if any of the n int32 (int64 with
 // i64_entries) values of d_idx is outside [lo, hi); the flag is in PB3D_SLOT_SURF_FLAG; one host wait
 int pb3d_check_index_range(pb3d_ctx* ctx, const void* d_idx, int i64_entries, i64 n, i64 lo, i64 hi, const char* what);
+// csrc/meshcomp.hip for itself and csrc/orient.hip: the edge records of a checked face list (nv, nf >= 1; R = 3 nf), in the MESHCOMP_*
+// slots.  _reserve requests them (before the caller enqueues anything, so that no regrow waits midway); _build enqueues k_records,
+// the two stable sorts, k_heads, the two scans and k_head_positions.  face_parent (or null): nf entries that k_records sets to their
+// own position and k_heads unites across every shared edge (mesh_components under "edge").  loops: where the loop records are added
+struct pb3d_edge_records {
+    u32* W;                   // nf x 3 wrapped corners
+    u32* pairs;               // 4 R u32: the sorts' arrays; `val` is one of them, the other three are spent after _build
+    const u32* val;           // R records in (lo, hi, record) order, the loops last
+    u32 *head, *fwd;          // R each: first record of its undirected edge; source is lo
+    i64 *head_rank, *fwd_rank;  // R + 1 each: exclusive scans of the two; head_rank[R] = the number of edges E
+    u32* pos;                 // E + 1: where edge e's records start; pos[E] = behind the last record that is no loop
+};
+int pb3d_mesh_edge_records_reserve(pb3d_ctx* ctx, i64 nf, pb3d_edge_records* rec);
+int pb3d_mesh_edge_records_build(pb3d_ctx* ctx, const void* d_faces, int faces_i64, i64 nf, i64 nv, int* face_parent, unsigned long long* loops,
+                                 pb3d_edge_records* rec);
+// ... a forest of n entries, each its own root; and every entry replaced by its root (root_flag, or null: 1 where entry == root)
+int pb3d_forest_init(pb3d_ctx* ctx, int* parent, i64 n);
+int pb3d_forest_flatten(pb3d_ctx* ctx, i64 n, int* parent, u32* root_flag);
+// ... the ordered sums of A_j and S_j (include/pb3d.h, mesh_components MEASURES) per label: measures[l] = area, measures[nc + l] =
+// volume for the *nc labels that face_labels holds, faces_of[l] faces each.  negate (or null): nf u32, S_j enters with a minus where
+// it is not 0.  _reserve requests MESHCOMP_SEGMENTS (extra_bytes more behind its tables, for the caller) and, with `sums`,
+// MESHCOMP_MEASURES; the (label, face) sort runs in rec.pairs, which spends rec.val
+int pb3d_mesh_ordered_sums_reserve(pb3d_ctx* ctx, i64 nf, bool sums, size_t extra_bytes, void** extra);
+int pb3d_mesh_ordered_sums(pb3d_ctx* ctx, const void* d_verts, int verts_f64, const pb3d_edge_records& rec, i64 nf, const int* face_labels,
+                           const u32* negate, const unsigned long long* faces_of, const i64* nc, double* measures);
 // process_voxel_grid through the bit-sliced chain (csrc/sliced.hip); *took = 0: not applicable, nothing written
 int pb3d_process_grid_sliced(pb3d_ctx* ctx, const u8* d_occ, i64 W, i64 H, i64 D, const u8* d_mask_wh, int angle_interval, u8* d_out,
                              int known_binary, int* took);

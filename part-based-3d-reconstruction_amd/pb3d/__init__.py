@@ -45,6 +45,8 @@ from .distance import (close_grid, close_grid_resident, dilate_grid, dilate_grid
                        distance_transform_resident, erode_grid, erode_grid_resident, grid_surface_metrics, grid_surface_metrics_resident,
                        open_grid, open_grid_resident)
 from .render import mesh_projection_iou, render_mesh, render_mesh_resident, render_shade_resident  # noqa: F401
+from .orient import mesh_orientation, mesh_orientation_resident, orient_mesh, orient_mesh_resident  # noqa: F401
+from .weld import weld_vertices, weld_vertices_resident  # noqa: F401
 from .raycast import (camera_rays, cast_rays, cast_rays_last, cast_rays_resident, points_visible_from, rays_occluded,  # noqa: F401
                       rays_occluded_resident)
 from .eval_helpers_intra import (color_presence, compute_binary_gt, compute_global_depth_buffer, grid_depth_buffer, grid_visible_bits,  # noqa: F401

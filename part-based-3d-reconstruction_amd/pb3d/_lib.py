@@ -208,6 +208,8 @@ _SIGNATURES = {
     "pb3d_cast_rays_resident": [vp, vp, vp, C.c_int, i64, vp, C.c_int, i64, vp, C.c_int, i64, C.c_double, C.c_double, C.c_int, vp, vp, vp, vp],
     "pb3d_cast_rays_last": [vp, i64p],
     "pb3d_cast_rays_last_ms": [vp, dblp],
+    "pb3d_weld_vertices_resident": [vp, vp, C.c_int, i64, vp, C.c_int, i64, vp, C.c_int, vp, vp, vp, vp, vp, vp, i64p],
+    "pb3d_mesh_orient_resident": [vp, vp, C.c_int, i64, vp, C.c_int, i64, C.c_int, vp, vp, vp, vp, vp, i64p],
 }
 class IouRow(C.Structure):
     """pb3d_iou_row (include/pb3d.h)"""

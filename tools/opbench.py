@@ -1,5 +1,5 @@
 """Device-resident timing of every op of the path (M1..M8 of SURVEY.md 8(d), plus the N1/N2 kernels of the notebook-1 chain) on
-synthetic inputs.  Development/measurement tool: python tools/opbench.py [--size 1024] [--shape WxHxD] [--ops M1,M3,...,N2,overlays,ICP,PLANE,MESHD,CLUSTER,DOWNSAMPLE,SMOOTH,SIMPLIFY,VOXELIZE,EDT,RENDER,ISO,MESHCOMP,INSIDE,RAYCAST]; one JSON
+synthetic inputs.  Development/measurement tool: python tools/opbench.py [--size 1024] [--shape WxHxD] [--ops M1,M3,...,N2,overlays,ICP,PLANE,MESHD,CLUSTER,DOWNSAMPLE,SMOOTH,SIMPLIFY,VOXELIZE,EDT,RENDER,ISO,MESHCOMP,ORIENT,WELD,INSIDE,RAYCAST]; one JSON
 line per op.  Pricing: `alg_B_per_voxel` is SURVEY 8(d)'s algorithmic figure for the sweeps that are EXECUTED (a folded 0-degree step
 moves nothing and is not priced); ops whose intermediates are not bytes (the bit-sliced chains) also carry `moved_B_per_voxel`, the
 bytes that cross the HBM by design, and their `frac_of_8TBs` is computed from THAT (never from bytes that are not moved)."""
@@ -280,6 +280,8 @@ def main():
         mesh_target(a.reps, res)
     if "MESHCOMP" in ops:
         mesh_components(a.reps, res)
+    if "ORIENT" in ops or "WELD" in ops:
+        mesh_repair(a.reps, res, "ORIENT" in ops, "WELD" in ops)
     if "INSIDE" in ops:
         inside(a.reps, res)
     if "RAYCAST" in ops:
@@ -1926,6 +1928,106 @@ def mesh_components(reps, res):
         print(json.dumps(r), flush=True)
         res.append(r)
         free((d_v, d_f, d_keep))
+    d_g.free()
+
+
+def mesh_repair(reps, res, orient=True, weld=True):
+    """ORIENT and WELD, mesh_orientation / orient_mesh (csrc/orient.hip) and weld_vertices (csrc/weld.hip) on the two meshes of the
+    MESHCOMP rows.  Resident, by device events (best mean of reps, host waits inside).  ORIENT: mesh_orientation without vertices, with
+    them and with the sign rule; orient_mesh on a copy with a seeded random half of the faces wound the other way.  Its yardstick, not
+    the code under test, on the same faces in the same run: mesh_components_resident(connectivity="edge") without measures -- the same
+    two sorts, half the unions and a forest half as long.  WELD: weld_vertices of the mesh's soup (three vertices of its own per
+    face), float32 and float64.  Its yardsticks: mesh_vertex_adjacency_resident on the welded mesh (two sorts of 6 m pairs) and a
+    device-to-device copy of the soup's vertex bytes."""
+    from pb3d import meshcomp as mcp, orient as ori, smooth as smo, weld as wl
+    from pb3d.eval_helpers import density_grid_resident
+    lib, L = pb3d._lib.load(), pb3d._lib
+    taj = np.load(os.path.join(ROOT, "tests", "golden", "stored_Taj_voxel_grid.npz"))["voxel_grid"]
+    nvox = int(np.prod(taj.shape[:3]))
+    d_g = dev.from_numpy(taj)
+
+    def best(fn):
+        return min(timeit(fn, reps, warm=1) for _ in range(2))
+
+    def free(bufs):
+        for b in bufs:
+            if hasattr(b, "free"):
+                b.free()
+
+    def taj_mesh():
+        (d_v, d_f, d_n, d_c), (nv, nf) = dev.meshify(d_g, taj.shape, download=False)
+        free((d_n, d_c))
+        return d_v, d_f, nv, nf
+
+    def iso_mesh():
+        d_tp, d_tc = dev.DeviceBuffer(nvox * 12), dev.DeviceBuffer(nvox * 3)
+        n = C.c_int64(0)
+        L.check(lib.pb3d_points_extract_dev(L.ctx(), C.c_void_p(d_g.ptr), *taj.shape[:3], 3, None, 0, nvox, C.c_void_p(d_tp.ptr),
+                                            C.c_void_p(d_tc.ptr), C.byref(n)))
+        d_vol = density_grid_resident(d_tp, n.value, 512, 1.0, f64=False)
+        (d_v, d_f), (nv, nf) = dev.isosurface(d_vol, (512, 512, 512), 0.1, 512, download=False)
+        free((d_tp, d_tc, d_vol))
+        return d_v, d_f, nv, nf
+
+    for name, make in (("stored Taj, stride-1 mesh", taj_mesh), ("512^3 isosurface of the Taj density volume, level 0.1", iso_mesh)):
+        d_v, d_f, nv, nf = make()
+        F = d_f.download((nf, 3), np.int32)
+        if orient:
+            r = {"op": "ORIENT", "name": f"mesh_orientation: {name}", "nverts": int(nv), "nfaces": int(nf), "records": 3 * int(nf), "reps": reps}
+            swapped = F.copy()
+            k = np.random.default_rng(1).random(nf) < 0.5
+            swapped[k] = swapped[k][:, [0, 2, 1]]
+            d_s = dev.from_numpy(swapped)
+
+            def run(d_faces, d_verts, sign, out_faces=False):
+                *bufs, t = ori.mesh_orientation_resident(d_faces, nf, nv, d_verts, sign, out_faces=out_faces)
+                free(bufs)
+                return t
+            r["orientation_ms"] = round(best(lambda: run(d_f, None, None)), 4)
+            r["orientation_volumes_ms"] = round(best(lambda: run(d_f, d_v, None)), 4)
+            r["orientation_sign_rule_ms"] = round(best(lambda: run(d_f, d_v, "negative")), 4)
+            r["orient_mesh_half_swapped_ms"] = round(best(lambda: run(d_s, d_v, "negative", True)), 4)
+            r["totals"] = run(d_f, d_v, "negative")
+            r["totals_half_swapped"] = run(d_s, d_v, "negative", True)
+
+            def components():
+                *bufs, t = mcp.mesh_components_resident(d_f, nf, nv, None, "edge")
+                free(bufs)
+            r["yardstick_components_edge_ms"] = round(best(components), 4)
+            for key in ("orientation_ms", "orientation_volumes_ms", "orientation_sign_rule_ms", "orient_mesh_half_swapped_ms"):
+                r[key.replace("_ms", "_over_components_edge")] = round(r[key] / r["yardstick_components_edge_ms"], 3)
+            print(json.dumps(r), flush=True)
+            res.append(r)
+            d_s.free()
+        if weld:
+            V = d_v.download((nv, 3), np.float32)
+            soup = V[F].reshape(-1, 3)
+            SF = np.arange(3 * nf, dtype=np.int32).reshape(nf, 3)
+            d_sf = dev.from_numpy(SF)
+            r = {"op": "WELD", "name": f"weld_vertices of the soup: {name}", "soup_vertices": 3 * int(nf), "nfaces": int(nf), "reps": reps}
+            for f64 in (False, True):
+                host = soup.astype(np.float64) if f64 else soup
+                d_sv = dev.from_numpy(host)
+                d_copy = dev.DeviceBuffer(host.nbytes)
+                tag = "float64" if f64 else "float32"
+
+                def run():
+                    *bufs, m = wl.weld_vertices_resident(d_sv, 3 * nf, d_sf, nf, verts_f64=f64)
+                    free(bufs)
+                    return m
+                r[f"weld_{tag}_ms"] = round(best(run), 4)
+                r[f"classes_{tag}"] = run()
+                r[f"yardstick_copy_{tag}_ms"] = round(best(lambda: L.check(lib.pb3d_d2d(L.ctx(), C.c_void_p(d_copy.ptr), C.c_void_p(d_sv.ptr), host.nbytes))), 4)
+                r[f"weld_{tag}_over_copy"] = round(r[f"weld_{tag}_ms"] / r[f"yardstick_copy_{tag}_ms"], 1)
+                free((d_sv, d_copy))
+            r["yardstick_adjacency_ms"] = round(best(lambda: free(smo.mesh_vertex_adjacency_resident(d_f, nv, nf)[:4])), 4)
+            for tag in ("float32", "float64"):
+                r[f"weld_{tag}_over_adjacency"] = round(r[f"weld_{tag}_ms"] / r["yardstick_adjacency_ms"], 3)
+            r["classes_equal_vertices_named"] = bool(r["classes_float32"] == mcp.mesh_topology_resident(d_f, nf, nv)["vertices"])
+            print(json.dumps(r), flush=True)
+            res.append(r)
+            d_sf.free()
+        free((d_v, d_f))
     d_g.free()
 
 
